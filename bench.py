@@ -1,7 +1,15 @@
 #!/usr/bin/env python3
 """bench.py — headline benchmark: Mray/s of the path-tracing hot path on MI355X.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c2|...] [--no-cpu] [--no-secondary] [--no-counters]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c2|...] [--dump-outputs DIR]
+  python bench.py --full [--no-cpu] [--no-secondary] [--no-counters] [--no-tolerance] ...
+
+A plain run sets up, runs W untimed and K timed steps, writes the last timed step's frame if --dump-outputs is given, and prints the
+line: the headline figure and the frame's description, nothing else. --full adds everything below (CPU baselines, counter passes,
+parity against the reference's rows, secondary and tolerance-build legs, the full record) - minutes instead of seconds.
+
+--dump-outputs DIR: DIR/radiance.npy, the [H, W, 3] float64 radiance of the last timed step (rank 0's assembled frame at N > 1),
+what a caller of Context.render_device receives. Inputs are fixed (scene image, SEED), so two builds can be compared frame for frame.
 
 One "step" = one full frame of the workload: every owned pixel traced with spp samples by the HIP integrator kernel(s)
 (ray generation, BVH traversal, shading, NEE shadow rays, film accumulation), the image rows left in HBM; with N > 1 the
@@ -12,7 +20,7 @@ Headline workload (BASELINE.json configs[1], the config the metric is quoted on)
 1920x1080 @ 256 spp, scene image tests/golden/hexagon_room.mcrt (flattened by the reference's own loader/BVH builder).
 Inputs (scene arrays, Sobol tables, photon maps) are resident in HBM before the timed region.
 
-Rank 0 prints ONE JSON line (contract in the task statement). At N = 1 it also carries
+Rank 0 prints ONE JSON line. With --full at N = 1 it also carries
   roofline      of the frame's kernels, the SAME block for the headline and every secondary leg (leg_roofline): three fractions of
                 physical peaks - `hbm_frac_measured` (fabric bytes of one frame from rocprofv3 PMC passes made inside this run - child
                 processes of this script - / kernel time / 8 TB/s), `valu_issue_frac` (SQ_THREAD_CYCLES_VALU / kernel time / 1024 SIMDs x
@@ -513,8 +521,9 @@ def setup_workload(name, args, m, tiling, rank, world, local_rank, dist, sqrtspp
         t_pass = time.perf_counter()
         ps = wl.ctx.photon_pass_device(wl.emissions, 10.0, SEED, sc.bb_min[:], sc.bb_max[:], 200, 50, False)
         cold_s = time.perf_counter() - t_pass
-        # once more: the pass as it costs per frame of an animation (work buffers pooled in the context, DevPool); same maps
-        if not getattr(args, "child_frame", False):
+        # once more (--full, and tools/ whose own arguments have no --full): the pass as it costs per frame of an animation (work buffers
+        # pooled in the context, DevPool); same maps
+        if getattr(args, "full", True) and not getattr(args, "child_frame", False):
             t_pass = time.perf_counter()
             ps = wl.ctx.photon_pass_device(wl.emissions, 10.0, SEED, sc.bb_min[:], sc.bb_max[:], 200, 50, False)
         wl.emit_info = dict(paths=ps["emission_paths"], rays=ps["rays"], kernel_ms=ps["emission_ms"], global_photons=int(ps["global_count"]),
@@ -599,9 +608,10 @@ def setup_workload(name, args, m, tiling, rank, world, local_rank, dist, sqrtspp
     return wl
 
 
-def run_steps(wl, steps, warmup, world, dist, warm_sqrtspp=None):
+def run_steps(wl, steps, warmup, world, dist, warm_sqrtspp=None, time_gather=True):
     """W untimed steps, then exactly K timed steps between barrier + synchronize; returns (seconds, per-step stats).
-    warm_sqrtspp (secondary legs whose frame takes tens of seconds): the untimed frame runs at that spp."""
+    warm_sqrtspp (secondary legs whose frame takes tens of seconds): the untimed frame runs at that spp. time_gather (N > 1): the
+    frame's gather timed by itself after the timed region (wl.gather_ms)."""
     import torch
 
     def step(cam=None):
@@ -628,7 +638,7 @@ def run_steps(wl, steps, warmup, world, dist, warm_sqrtspp=None):
     sync()
     elapsed = time.perf_counter() - t0
     wl.gather_ms = None
-    if _collectives(world):  # after the timed region: what the frame's one collective costs by itself (the same tiles again)
+    if _collectives(world) and time_gather:  # after the timed region: what the frame's one collective costs by itself (the same tiles again)
         t1 = time.perf_counter()
         for _ in range(3):
             dist.gather(wl.tile, wl.gathered, dst=0)
@@ -809,8 +819,9 @@ def compact_line(result):
             out[k] = result[k]
     if result.get("parity"):
         out["parity"] = {k: result["parity"].get(k) for k in ("rows", "pixels", "max_rel", "outliers_gt_1e-4", "bit_identical", "tolerance")}
-    out["cpu_baseline"] = compact_cpu(result.get("cpu_baseline"))
-    out["roofline"] = compact_roofline(result.get("roofline"))
+    if result.get("cpu_baseline") or result.get("roofline"):  # (--full)
+        out["cpu_baseline"] = compact_cpu(result.get("cpu_baseline"))
+        out["roofline"] = compact_roofline(result.get("roofline"))
     legs = {}
     for name, leg in (result.get("secondary") or {}).items():
         if "error" in leg:
@@ -848,7 +859,8 @@ def compact_line(result):
             out["tolerance_build"][name] = t
         if isinstance(tol, dict) and "error" in tol:
             out["tolerance_build"] = {"error": str(tol["error"])[:120]}
-    out["detail"] = "gpurun_out/bench_profiles/bench_full.json (+ pmc_<leg>.md); committed as profiles/rNN_bench_full.json"
+    if "roofline" in out:
+        out["detail"] = "%s (+ pmc_<leg>.md); committed as profiles/rNN_bench_full.json" % os.path.relpath(FULL_RECORD, ROOT)
     out = _rnd(out)
     # shed optional keys, least important first, until the line fits (never the contract's keys)
     shed = [("secondary", k) for k in ("workload", "measured_clock_GHz", "lane_utilisation", "frac_necessary", "launches_per_step", "cpu", "kernel_ms")] + \
@@ -891,7 +903,7 @@ def measure(name, args, m, tiling, rank, world, local_rank, dist, steps, warmup,
     plan = {} if headline else LEG_PLAN.get(name, {})
     steps = plan.get("steps") or steps
     wl = setup_workload(name, args, m, tiling, rank, world, local_rank, dist, sqrtspp=args.sqrtspp if headline else None)
-    elapsed, stats = run_steps(wl, steps, warmup, world, dist, warm_sqrtspp=plan.get("warm_sqrtspp"))
+    elapsed, stats = run_steps(wl, steps, warmup, world, dist, warm_sqrtspp=plan.get("warm_sqrtspp"), time_gather=args.full)
     dev = wl.dev
     t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
     acc = torch.tensor([float(sum(s["rays"] for s in stats)), float(sum(s["paths"] for s in stats)),
@@ -936,7 +948,7 @@ def measure(name, args, m, tiling, rank, world, local_rank, dist, steps, warmup,
                        "knn_searches_per_s": total_knn / elapsed if total_knn else None,
                        "photon_pass": wl.emit_info if wl.photon else None},
         }
-        if wl.photon and wl.emit_info and wl.emit_info.get("photon_pass_s") is not None:
+        if args.full and wl.photon and wl.emit_info and wl.emit_info.get("photon_pass_s") is not None:
             # PhotonMapper's constructor (photon-mapper.cpp:24-223) is part of what BASELINE configs[4] names: the frame with its photon
             # pass (emission + both maps, on the device) beside the eye-pass figure the step times
             pp_ms = wl.emit_info["photon_pass_s"] * 1e3
@@ -944,12 +956,16 @@ def measure(name, args, m, tiling, rank, world, local_rank, dist, steps, warmup,
             result["value_with_photon_pass"] = (total_rays / steps + wl.emit_info["rays"]) / (result["frame_with_photon_pass_ms"] * 1e-3) / 1e6
         if per_rank:
             result["per_rank"] = {k: per_rank[k] for k in ("ms_per_step", "kernel_ms")}
-            result["gather_ms"] = per_rank["gather_ms"]
+            if per_rank["gather_ms"]:
+                result["gather_ms"] = per_rank["gather_ms"]
             if per_rank["photon_allgather_ms"]:
                 result["photon_allgather_ms"] = per_rank["photon_allgather_ms"]
             if REHEARSE_DIST:
                 result["rehearsal"] = "collectives of the N > 1 path run with a process group of one rank (--rehearse-dist): not a scaling measurement"
-        par = c2_parity(wl, frame)  # any world: rank 0 holds the assembled frame of the last timed step
+        if headline and args.dump_outputs:
+            dump_outputs(args.dump_outputs, frame)  # any world: rank 0 holds the assembled frame of the last timed step
+    if rank == 0 and args.full:
+        par = c2_parity(wl, frame)
         if par:
             result["parity"] = par
         counts = None
@@ -969,7 +985,7 @@ def measure(name, args, m, tiling, rank, world, local_rank, dist, steps, warmup,
     wl.ctx.close()
     del wl.tile, wl.gathered
     torch.cuda.empty_cache()
-    if rank == 0:
+    if rank == 0 and args.full:
         pmc = None
         if world == 1 and want_counters:
             # counters of ONE frame; C3's frame takes 8 s under nothing and longer under counters: taken at 64 spp and scaled
@@ -986,6 +1002,12 @@ def measure(name, args, m, tiling, rank, world, local_rank, dist, steps, warmup,
         if world == 1 and want_counters:
             write_leg_profile(name, wl.desc, raw, pmc, result["roofline"])
     return result, ref_threads
+
+
+def dump_outputs(out_dir, frame):
+    """--dump-outputs: the frame of the last timed step as out_dir/radiance.npy ([H, W, 3] float64; 50 MB at 1920x1080)."""
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "radiance.npy"), np.ascontiguousarray(frame.cpu().numpy(), dtype=np.float64))
 
 
 def rows_parity(m, name):
@@ -1056,7 +1078,7 @@ def tolerance_legs(args, exact):
         return {"error": "libmcrt_hip_tol.so not built"}
     for name in TOLERANCE_LEGS:
         cmd = [sys.executable, os.path.abspath(__file__), "--child-leg", "--workload", name, "--steps", str(min(args.steps, 5) if name == "c2" else args.secondary_steps),
-               "--warmup", "1"]
+               "--warmup", "1", "--full"]
         if args.emissions:
             cmd += ["--emissions", str(args.emissions)]
         try:
@@ -1102,9 +1124,14 @@ def main():
     ap.add_argument("--steps", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--workload", default="c2", choices=sorted(WORKLOADS))
-    ap.add_argument("--no-cpu", action="store_true", help="skip the cpu_baseline legs (stored per-ray counts are used for the algorithmic bytes)")
-    ap.add_argument("--no-secondary", action="store_true", help="headline only")
-    ap.add_argument("--no-counters", action="store_true", help="skip the rocprofv3 PMC child passes")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's frame as DIR/radiance.npy ([H, W, 3] float64; fixed inputs: the same arguments give the same frame)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the CPU baselines, counter passes, parity, secondary and tolerance-build legs and the full record (minutes); "
+                         "a plain run times the headline workload only")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the cpu_baseline legs (stored per-ray counts are used for the algorithmic bytes)")
+    ap.add_argument("--no-secondary", action="store_true", help="with --full: headline only")
+    ap.add_argument("--no-counters", action="store_true", help="with --full: skip the rocprofv3 PMC child passes")
     ap.add_argument("--secondary-steps", type=int, default=3)
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
     ap.add_argument("--sqrtspp", type=int, default=None, help="override the workload's samples per pixel (debugging; the line says so)")
@@ -1115,7 +1142,7 @@ def main():
                     help="one GPU: run the collectives of the N > 1 path (RCCL init, gathers, reductions, destroy) with a process group of one rank")
     ap.add_argument("--child-frame", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--child-leg", action="store_true", help=argparse.SUPPRESS)
-    ap.add_argument("--no-tolerance", action="store_true", help="skip the legs of the opt-in tolerance build (libmcrt_hip_tol.so)")
+    ap.add_argument("--no-tolerance", action="store_true", help="with --full: skip the legs of the opt-in tolerance build (libmcrt_hip_tol.so)")
     args = ap.parse_args()
 
     import torch
@@ -1162,8 +1189,10 @@ def main():
     tiling = importlib.import_module("monte-carlo-ray-tracer_amd.tiling")
     single = world == 1 and not REHEARSE_DIST   # (the rehearsal is the N > 1 line's shape: no CPU leg, no counter passes, no secondary legs)
     result, ref_threads = measure(args.workload, args, m, tiling, rank, world, local_rank, dist, args.steps, args.warmup,
-                                  want_cpu=single and not args.no_cpu, want_counters=single and not args.no_counters, headline=True)
-    if single and args.workload == "c2" and not args.no_secondary:
+                                  want_cpu=single and args.full and not args.no_cpu, want_counters=single and args.full and not args.no_counters,
+                                  headline=True)
+    full = single and args.full and args.workload == "c2"
+    if full and not args.no_secondary:
         # driver-timed legs on the kernels that walk trees in HBM / search photon maps (their own step counts: C3 is 8 s a frame)
         result["secondary"] = {}
         for name in SECONDARY:
@@ -1177,7 +1206,7 @@ def main():
             except Exception as ex:  # a leg that cannot run here (scene image absent) must not cost the headline
                 leg = {"error": repr(ex)}
             result["secondary"][name] = leg
-    if single and args.workload == "c2" and not args.no_secondary and not args.no_tolerance:
+    if full and not args.no_secondary and not args.no_tolerance:
         exact = dict(result.get("secondary") or {}, c2=result)
         result["tolerance_build"] = tolerance_legs(args, exact)
     # the process group goes first: whatever RCCL / torch print while it is torn down must not follow the line the driver parses
@@ -1185,15 +1214,16 @@ def main():
         dist.barrier()
         dist.destroy_process_group()
     if rank == 0:
-        # the full record: a file (and stderr), never stdout - the driver parses the LAST stdout line and keeps ~8 KB of it
-        try:
-            os.makedirs(PROFILE_DIR, exist_ok=True)
-            with open(FULL_RECORD, "w") as f:
-                json.dump(result, f)
-        except OSError:
-            pass
-        sys.stderr.write("bench.py full record: %s\n" % json.dumps(result))
-        sys.stderr.flush()
+        if args.full:
+            # the full record: a file (and stderr), never stdout - the driver parses the LAST stdout line and keeps ~8 KB of it
+            try:
+                os.makedirs(PROFILE_DIR, exist_ok=True)
+                with open(FULL_RECORD, "w") as f:
+                    json.dump(result, f)
+            except OSError:
+                pass
+            sys.stderr.write("bench.py full record: %s\n" % json.dumps(result))
+            sys.stderr.flush()
         sys.stdout.flush()
         os.write(real_stdout, (compact_line(result) + "\n").encode())
 

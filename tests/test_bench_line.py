@@ -66,3 +66,54 @@ def test_non_finite_numbers_do_not_break_the_line():
     d = json.loads(b.compact_line(full))          # strict JSON: NaN / Infinity would not load in other parsers
     assert "NaN" not in b.compact_line(full) and "Infinity" not in b.compact_line(full)
     assert d["secondary"]["c3"]["value"] is None
+
+
+# what only --full adds to the result (measure / main); a plain run's result has none of it
+FULL_ONLY = ("parity", "cpu_baseline", "roofline", "secondary", "tolerance_build", "frame_with_photon_pass_ms", "value_with_photon_pass")
+
+
+def test_plain_line_is_the_headline_alone():
+    """A plain run (no --full) times the headline only: its line has the contract's keys and the frame's description, and no
+    block it did not measure (no roofline, cpu_baseline, parity, secondary legs, nor a pointer to a full record it did not write)."""
+    b = _bench()
+    full = json.load(open(RECORDS[-1]))
+    plain = {k: v for k, v in full.items() if k not in FULL_ONLY}
+    d = json.loads(b.compact_line(plain))
+    for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype", "data", "config"):
+        assert k in d, k
+    assert d["value"] == pytest.approx(full["value"], rel=1e-5) and d["ms_per_step"] == pytest.approx(full["ms_per_step"], rel=1e-5)
+    for k in FULL_ONLY + ("detail",):
+        assert k not in d, k
+
+
+@pytest.mark.gpu
+def test_plain_run_times_k_steps_and_dumps_the_last_frame(tmp_path, pkg):
+    """bench.py without --full: exactly --steps timed steps, the lean line, and --dump-outputs writes the last timed step's frame - the
+    frame the library renders for those inputs (Context.sample_image on the same camera and seed), bit for bit."""
+    import subprocess
+    import sys
+
+    import numpy as np
+
+    b = _bench()
+    out = tmp_path / "outputs"
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--workload", "c1", "--steps", "3", "--warmup", "1",
+                        "--dump-outputs", str(out)], capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert p.returncode == 0, (p.stdout[-2000:], p.stderr[-2000:])
+    d = json.loads(p.stdout.rstrip().splitlines()[-1])
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["ms_per_step"] > 0 and d["value"] > 0 and d["config"]["frame_finite"]
+    for k in FULL_ONLY:
+        assert k not in d, k
+    assert sorted(os.listdir(out)) == ["radiance.npy"]
+    frame = np.load(out / "radiance.npy")
+    image_file, W, H, s, _ = b.WORKLOADS["c1"]
+    assert frame.dtype == np.float64 and frame.shape == (H, W, 3)
+    img = pkg.SceneImage(os.path.join(ROOT, "tests", "golden", image_file))
+    cam = img.camera
+    cam.width, cam.height, cam.sqrtspp = W, H, s
+    ctx = pkg.Context(0)
+    ctx.upload_image(img)
+    want, _ = ctx.sample_image(cam, b.SEED, pkg.INTEGRATOR_PATH_TRACER)
+    ctx.close()
+    np.testing.assert_array_equal(frame, want)
+    assert float(frame.mean()) == pytest.approx(d["config"]["frame_mean_radiance"], rel=1e-5)

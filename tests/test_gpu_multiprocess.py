@@ -126,7 +126,7 @@ def _bench(gpus, extra, env=None):
 def test_bench_n2_line_equals_n1_work(workload, extra):
     """bench.py --gpus 2 (row sharding, sharded photon emission + all-gather of the lists, the gather, frame assembly on rank
     0, max-over-ranks timing, the one JSON line) against --gpus 1 on the same workload: same paths, same rays, same frame."""
-    common = ["--workload", workload, "--steps", "2", "--warmup", "1", "--no-cpu", "--no-counters", "--no-secondary"] + extra
+    common = ["--workload", workload, "--steps", "2", "--warmup", "1", "--full", "--no-cpu", "--no-counters", "--no-secondary"] + extra
     one = _bench(1, common)
     two = _bench(2, common)
     assert two["n_gpus"] == 2 and one["n_gpus"] == 1 and two["steps"] == 2 and two["scaling"] == "strong"
@@ -148,7 +148,7 @@ def test_bench_rccl_branch_rehearsal_on_one_gpu(workload, extra):
     """bench.py --rehearse-dist: the N > 1 branch with backend "nccl" (RCCL) and a process group of ONE rank on this box's GPU - init
     with device_id, the barrier, the photon all-gathers on device pointers, the per-frame gather into rank 0's list, the reductions of
     the timing, destroy. Same work as the plain N = 1 line; the line names itself a rehearsal and carries the per-rank figures."""
-    common = ["--workload", workload, "--steps", "2", "--warmup", "1", "--no-cpu", "--no-counters", "--no-secondary"] + extra
+    common = ["--workload", workload, "--steps", "2", "--warmup", "1", "--full", "--no-cpu", "--no-counters", "--no-secondary"] + extra
     one = _bench(1, common, env={"MCRT_BENCH_SHARE_GPU": "0"})
     reh = _bench(1, common + ["--rehearse-dist"], env={"MCRT_BENCH_SHARE_GPU": "0"})
     assert "rehearsal" in reh and reh["n_gpus"] == 1

@@ -9,11 +9,11 @@ mkdir -p $O
 export TMPDIR=/tmp
 ( time timeout 1200 python -m pytest tests -m gpu -q -rA ) > $O/pytest_gpu.log 2>&1
 tail -3 $O/pytest_gpu.log
-( time timeout 1800 python bench.py --gpus 1 --steps 20 --warmup 5 ) > $O/bench_default.json 2> $O/bench_default.err  # as the driver runs it
+( time timeout 1800 python bench.py --full --gpus 1 --steps 20 --warmup 5 ) > $O/bench_default.json 2> $O/bench_default.err  # every leg, the full record
 tail -c 400 $O/bench_default.json; tail -4 $O/bench_default.err
 cp -r $R/gpurun_out/bench_profiles $O/ 2>/dev/null
 cd /tmp
-timeout 1500 rocprofv3 --kernel-trace --stats -d $O/kt_default -- python $R/bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu --no-counters --no-tolerance > $O/kt_default.json 2> $O/kt_default.err
+timeout 1500 rocprofv3 --kernel-trace --stats -d $O/kt_default -- python $R/bench.py --full --gpus 1 --steps 20 --warmup 5 --no-cpu --no-counters --no-tolerance > $O/kt_default.json 2> $O/kt_default.err
 cd $R
 python tools/summarize_rocprof.py $O/kt_default > $O/rocprof_kernel_trace.md 2>&1
 find $O -name "*.db" -delete; find $O -name "*.csv" -size +1M -delete; find $O -type d -empty -delete
