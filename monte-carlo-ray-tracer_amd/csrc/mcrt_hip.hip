@@ -23,6 +23,7 @@
 #include "mcrt_layout.hpp"
 #include "mcrt_internal.hpp"
 #include "mcrt_plan.hpp"
+#include "mcrt_select.hpp"
 #include "mcrt_octree_shared.hpp"
 #include "mcrt_lean.hpp"
 
@@ -87,7 +88,7 @@ struct mcrt_ctx {
     size_t max_lds_trace = 0;  // ... a kernel that only walks the tree (no static LDS)
 
     bool has_scene = false;
-    bool q_single = false;  // HostLayout::q_single of the uploaded scene
+    SceneFacts facts;  // what kernel selection reads of the uploaded scene (mcrt_select.hpp)
     std::vector<float> flat_pre_host;  // the flat loop's cull records, host copy: renderKernelFlatK takes them as a kernel argument
     DeviceScene scene{};
     DevBuf node_bounds, node_meta, nodes64, qblocks, quadrics, prim, flat_prim, flat_index, flat_pre, surf_v, surf_normal, surf_rec, surf_vn, surf_area, surf_material, surf_kind, materials,
@@ -125,8 +126,7 @@ struct mcrt_ctx {
     double* last_film = nullptr;
     hipStream_t last_stream = nullptr;
     bool force_wf = false;
-    mutable bool lean_used = false;  // the last launch (frame, photon pass) ran a lean instance: mcrt_get_option("MCRT_LEAN_USED")
-    uint32_t material_flags_or = 0xFFFFFFFFu;  // OR of the uploaded scene's material flags: which compiled-out features a lean kernel instance may lack (leanOf)
+    bool lean_used = false;  // the last launch (frame, photon pass) ran a lean instance: mcrt_get_option("MCRT_LEAN_USED")
     uint32_t iors_depth = kMaxIorsDeep;  // RefractionHistory entries per pipeline slot (8 in LDS + deep rows); grows when a frame nests deeper
     DevBuf wf_iors_deep;
     DevPool pass_pool;  // work buffers of the device photon pass (mcrt_photon_device.hpp)
@@ -167,7 +167,7 @@ int fail(mcrt_ctx* ctx, int code, const std::string& msg) {
             return fail(ctx, MCRT_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(e_));      \
     } while (0)
 
-int planSampleStore(mcrt_ctx* ctx, uint32_t width, uint32_t owned_rows, uint32_t spp, PassPlan& pp);  // below
+int planSampleStore(mcrt_ctx* ctx, double store_gb, uint32_t width, uint32_t owned_rows, uint32_t spp, PassPlan& pp);  // below
 
 template <class T>
 int uploadArray(mcrt_ctx* ctx, DevBuf& buf, const T* host, size_t count) {
@@ -199,19 +199,27 @@ struct LaunchGeom {
     uint32_t grid, lds_bytes, total_lanes, block = kBlock;
 };
 
-template <class K>
-int launchGeometry(mcrt_ctx* ctx, K kernel, const DeviceScene& s, LaunchGeom& g, int plan = 0) {  // plan 2: flat-scene instance
-    g.block = plan == 4 ? 1024u : plan == 3 ? 768u : kBlock;  // plan 2 / 3 / 4: the flat-scene instances (512 / 768 / 1024 lanes, no stack in LDS)
-    g.lds_bytes = plan == 1 ? planSmLds(s, kBlock).total : planLds(s, g.block, plan < 2).total;
-    if (g.lds_bytes > ctx->max_lds) return fail(ctx, MCRT_ERR_INVALID, "LDS plan exceeds the device limit");
-    HIP_TRY(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                     (int)g.lds_bytes));
+// Sizes `kernel`'s dynamic LDS and asks how many of its workgroups a CU holds: g.grid = that x the CUs. hipFuncSetAttribute is state of
+// the kernel FUNCTION, shared by every context of the process: a frame's launches call this under the device mutex of launchRender
+// (DeviceOrder's comment).
+int occupancyGrid(mcrt_ctx* ctx, const void* kernel, uint32_t block, uint32_t lds_bytes, LaunchGeom& g) {
+    HIP_TRY(ctx, hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
     int per_cu = 0;
-    HIP_TRY(ctx, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, (int)g.block, g.lds_bytes));
+    HIP_TRY(ctx, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, (int)block, lds_bytes));
     if (per_cu < 1) per_cu = 1;
+    g.block = block;
+    g.lds_bytes = lds_bytes;
     g.grid = (uint32_t)(per_cu * ctx->num_cus);
-    g.total_lanes = g.grid * g.block;
+    g.total_lanes = g.grid * block;
     return MCRT_OK;
+}
+
+// ... of a kernel with the 512-lane plan of the wave-synchronous code (the emission pass, mcrt_intersect of a staged scene)
+template <class K>
+int launchGeometry(mcrt_ctx* ctx, K kernel, const DeviceScene& s, LaunchGeom& g) {
+    const uint32_t lds_bytes = planLds(s, kBlock).total;
+    if (lds_bytes > ctx->max_lds) return fail(ctx, MCRT_ERR_INVALID, "LDS plan exceeds the device limit");
+    return occupancyGrid(ctx, reinterpret_cast<const void*>(kernel), kBlock, lds_bytes, g);
 }
 
 int ensureSpill(mcrt_ctx* ctx, size_t bytes) {  // traversal-stack spill area, shared by every kernel (one render at a time)
@@ -282,7 +290,7 @@ int validateCamera(mcrt_ctx* ctx, const mcrt_camera_desc* cam) {
     return MCRT_OK;
 }
 
-// Launch geometry of the trace kernel: one workgroup per CU (MCRT_TRACE_WAVES waves, default 16), its LDS split
+// Launch geometry of the trace kernel: one workgroup per CU (kTraceWaves waves), its LDS split
 // between the lanes' traversal stacks and as many top-of-tree child blocks as fit.
 struct TracePlan {
     uint32_t grid, block, lds_bytes;
@@ -310,58 +318,110 @@ using mcrt::ctxOpt;
 using mcrt::ctxOptL;
 using mcrt::ctxOptOn;
 
-// Lean kernel instances (csrc/mcrt_hip_lean.hip: the default path's kernels compiled without Oren-Nayar, GGX and conductor Fresnel). A
-// scene whose materials carry none of those flags renders through them - same bits, fewer registers (mcrt_shade.hpp) - unless
-// MCRT_LEAN_KERNELS=0. `full` is the instance the selection code above chose; the table says which of them has a lean twin.
-bool leanScene(const mcrt_ctx* ctx) { return (ctx->material_flags_or & MCRT_LEAN_FEATURES_OFF) == 0u && ctxOptL(ctx, "MCRT_LEAN_KERNELS", 1) != 0; }
-template <class K>
-K leanOf(mcrt_ctx* ctx, K full) {
-    if (!full || !leanScene(ctx)) return full;
-    constexpr int PT = MCRT_INTEGRATOR_PATH_TRACER;
-    static const struct { const void* full; int id; } twins[] = {
-        {reinterpret_cast<const void*>(renderKernelFlatK<>), MCRT_LEAN_FLATK_512},
-        {reinterpret_cast<const void*>(renderKernelFlatK<768>), MCRT_LEAN_FLATK_768},
-        {reinterpret_cast<const void*>(renderKernel<PT, false, true, false, 1>), MCRT_LEAN_FLAT_512},
-        {reinterpret_cast<const void*>(renderKernel<PT, false, true, false, 2>), MCRT_LEAN_FLAT_768},
-        // (the photon-mapping kernel of trees in MEMORY keeps its full instance: lean it spills 883 registers instead of 769 and a C5 frame
-        // takes 845 ms instead of 815 - that kernel's frame time follows its spill placement, not its instruction count, DESIGN 4.4 -
-        // while the LDS-resident scenes' instance gains 7 %: profiles/r06_ab_lean_kernels.log)
-        {reinterpret_cast<const void*>(renderKernelPM<false, true, 1024>), MCRT_LEAN_PM_1024_ALL},
-        {reinterpret_cast<const void*>(renderKernelPM<false, true>), MCRT_LEAN_PM_512_ALL},
-        {reinterpret_cast<const void*>(renderKernelSM<false, false>), MCRT_LEAN_SM},
-        {reinterpret_cast<const void*>(renderKernelSM<false, true>), MCRT_LEAN_SM_ALL},
-        {reinterpret_cast<const void*>(wfShadeKernel<false>), MCRT_LEAN_SHADE},
-        {reinterpret_cast<const void*>(wfShadeKernel<true>), MCRT_LEAN_SHADE_PM},
-        {reinterpret_cast<const void*>(emitKernel<false>), MCRT_LEAN_EMIT},
-        {reinterpret_cast<const void*>(emitKernel<true>), MCRT_LEAN_EMIT_ALL},
-        {reinterpret_cast<const void*>(wfKnnKernel<true>), MCRT_LEAN_KNN_EVAL},
-    };
-    const void* f = reinterpret_cast<const void*>(full);
-    for (const auto& t : twins)
-        if (t.full == f)
-            if (const void* l = mcrt_lean_kernel(t.id)) {
-                ctx->lean_used = true;
-                return reinterpret_cast<K>(const_cast<void*>(l));
-            }
-    return full;
+static_assert(kSelBlock == kBlock && kSelWfBlock == kWfBlock && kSelLdsStack == kLdsStackDepth && kSelIorsDeep == kMaxIorsDeep &&
+                  kSelWaveK == waveMaxK(kWaveRows) && kSelWaveKMax == waveMaxK(kWaveRowsLarge) && kSelWaveKnnBytes == waveKnnBytes(kWaveRows) &&
+                  kSelWaveKnnBytesLarge == waveKnnBytes(kWaveRowsLarge) && kSelWaveStateBytes == kWaveStateBytes &&
+                  kSelFlatArgFloats == kFlatPreArgFloats && kSelVisit == kMaxVisit && kSelVisitLimit == kMaxVisitLimit &&
+                  kSelKnnOverflow == kKnnOverflowFlag && kSelLeanFeaturesOff == MCRT_LEAN_FEATURES_OFF,
+              "mcrt_select.hpp restates these by value");
+
+// RenderInstance (mcrt_select.hpp) -> the kernel's address and the id of its lean twin (csrc/mcrt_hip_lean.hip), -1: it has none.
+struct InstanceEntry {
+    const void* full = nullptr;
+    int lean_id = -1;
+};
+const InstanceEntry* instanceTable() {
+    static InstanceEntry t[kInstCount];
+    static const bool filled = [] {
+        constexpr int PT = MCRT_INTEGRATOR_PATH_TRACER, PM = MCRT_INTEGRATOR_PHOTON_MAPPER;
+        // (the compiler emits the kernels in the order they are first named, which is here: reordering these lines moves every kernel in the
+        // code object - tests/golden/device_code_hashes.json changes and has to be validated on the GPU again)
+        auto set = [](int id, auto kernel, int lean_id = -1) { t[id] = InstanceEntry{reinterpret_cast<const void*>(kernel), lean_id}; };
+        set(kInstFlatK512, renderKernelFlatK<>, MCRT_LEAN_FLATK_512);
+        set(kInstFlatK768, renderKernelFlatK<768>);
+        set(kInstFlat512, renderKernel<PT, false, true, false, 1>, MCRT_LEAN_FLAT_512);
+        set(kInstPM1024_All, renderKernelPM<false, true, 1024>, MCRT_LEAN_PM_1024_ALL);
+        set(kInstPM512_All, renderKernelPM<false, true>, MCRT_LEAN_PM_512_ALL);
+        set(kInstSM, renderKernelSM<false, false>, MCRT_LEAN_SM);
+        set(kInstSM_All, renderKernelSM<false, true>, MCRT_LEAN_SM_ALL);
+        set(kInstShadePT, wfShadeKernel<false>, MCRT_LEAN_SHADE);
+        set(kInstShadePM, wfShadeKernel<true>, MCRT_LEAN_SHADE_PM);
+        set(kInstEmit, emitKernel<false>, MCRT_LEAN_EMIT);
+        set(kInstEmit_All, emitKernel<true>, MCRT_LEAN_EMIT_ALL);
+        set(kInstKnnEval, wfKnnKernel<true>, MCRT_LEAN_KNN_EVAL);
+        set(kInstTraceLeanSingle, wfTraceKernel<PoolRays, false, 3>);
+        set(kInstTraceLean, wfTraceKernel<PoolRays, false, 1>);
+        set(kInstTrace_Count, wfTraceKernel<PoolRays, true>);
+        set(kInstTrace, wfTraceKernel<PoolRays, false>);
+        set(kInstKnnEvalWide, wfKnnKernel<true, kWaveRowsLarge>);
+        set(kInstKnnRawWide, wfKnnKernel<false, kWaveRowsLarge>);
+        set(kInstKnnRaw, wfKnnKernel<false>);
+        set(kInstPT, renderKernel<PT, false, false>);
+        set(kInstPT_All, renderKernel<PT, false, true>);
+        set(kInstPT_Count, renderKernel<PT, true, false>);
+        set(kInstPT_CountAll, renderKernel<PT, true, true>);
+        set(kInstPMLane, renderKernel<PM, false, false>);
+        set(kInstPMLane_All, renderKernel<PM, false, true>);
+        set(kInstPMLane_Count, renderKernel<PM, true, false>);
+        set(kInstPMLane_CountAll, renderKernel<PM, true, true>);
+        set(kInstPT_ProfAll, renderKernel<PT, false, true, true>);
+        set(kInstPT_Prof, renderKernel<PT, false, false, true>);
+        set(kInstSM_Count, renderKernelSM<true, false>);
+        set(kInstSM_CountAll, renderKernelSM<true, true>);
+        set(kInstSM_ProfAll, renderKernelSM<false, true, true>);
+        set(kInstSM_Prof, renderKernelSM<false, false, true>);
+        set(kInstPM512, renderKernelPM<false, false>);
+        set(kInstPM512_Count, renderKernelPM<true, false>);
+        set(kInstPM512_CountAll, renderKernelPM<true, true>);
+        set(kInstPM1024, renderKernelPM<false, false, 1024>);
+        set(kInstPM1024_Count, renderKernelPM<true, false, 1024>);
+        set(kInstPM1024_CountAll, renderKernelPM<true, true, 1024>);
+        set(kInstPMWide, renderKernelPM<false, false, (int)kBlock, kWaveRowsLarge>);
+        set(kInstPMWide_All, renderKernelPM<false, true, (int)kBlock, kWaveRowsLarge>);
+        set(kInstPMWide_Count, renderKernelPM<true, false, (int)kBlock, kWaveRowsLarge>);
+        set(kInstPMWide_CountAll, renderKernelPM<true, true, (int)kBlock, kWaveRowsLarge>);
+        return true;
+    }();
+    (void)filled;
+    return t;
 }
+// The address to launch; null: the selection asked for a lean twin that does not exist.
+const void* instanceAddress(int id, bool lean) {
+    const InstanceEntry& e = instanceTable()[id];
+    return !lean ? e.full : e.lean_id >= 0 ? mcrt_lean_kernel(e.lean_id) : nullptr;
+}
+template <class K>
+K kernelAs(const void* address) {
+    return reinterpret_cast<K>(const_cast<void*>(address));
+}
+using RenderKernelT = void (*)(const DeviceScene, const RenderParams);
+using PmKernelT = void (*)(const DeviceScene, const RenderParams, const PmExtra);
+using FlatKernelT = void (*)(const DeviceScene, const RenderParams, const FlatPreArg);
+using ShadeKernelT = void (*)(const DeviceScene, const WfShadeArgs);
+using KnnKernelT = void (*)(const WfKnnArgs);
+using TraceKernelT = void (*)(WfTraceArgs, PoolRays);
+
+// The trace kernel's launch values that were once A/B switches, at what the measurements left them:
+constexpr uint32_t kTraceWaves = 16;       // waves per workgroup, one workgroup per CU
+constexpr int kTraceRefillLanes = 16;      // (32 while the queue cursor was one global atomic)
+constexpr int kTraceLeafItems = 1 << 20;
+constexpr int kTraceMinInner = 8;
+constexpr uint32_t kTraceDealShift = 6;
+static_assert(kTraceWaves * 64u <= kTraceMaxBlock, "the trace kernel's launch bounds");
 
 template <class K>
-int planTrace(mcrt_ctx* ctx, K kernel, uint64_t max_items, TracePlan& tp) {
-    auto envi = [ctx](const char* k, long d) { return ctxOptL(ctx, k, d); };
-    const uint32_t waves = (uint32_t)std::min<long>(std::max<long>(envi("MCRT_TRACE_WAVES", 16), 1), kTraceMaxBlock / 64);
+int planTrace(mcrt_ctx* ctx, K kernel, uint64_t max_items, int leaf_lanes, TracePlan& tp) {
+    const uint32_t waves = kTraceWaves;
     tp.block = waves * 64u;
-    const uint32_t lds_stack = (uint32_t)std::min<long>(std::max<long>(envi("MCRT_TRACE_STACK", kLdsStackDepth), 4), kLdsStackDepth);
+    const uint32_t lds_stack = kLdsStackDepth;
     const uint32_t stack_bytes = lds_stack * tp.block * (uint32_t)sizeof(SmStackEntry);
-    const long lds_cap = std::min<long>((long)ctx->max_lds_trace, envi("MCRT_TRACE_LDS", (long)ctx->max_lds_trace));
+    const long lds_cap = (long)ctx->max_lds_trace;
     if ((long)stack_bytes + 128 + (long)(waves * kShareMapBytes) > lds_cap) return fail(ctx, MCRT_ERR_INVALID, "trace kernel: traversal stacks exceed the LDS");
     const uint32_t lds_blocks = (uint32_t)std::min<uint64_t>(ctx->scene.num_qblocks, ((uint64_t)lds_cap - stack_bytes - 128u - waves * kShareMapBytes) / 64u);
     tp.lds_bytes = lds_blocks * 64u + stack_bytes + 64u + waves * kShareMapBytes + 64u;  // + the workgroup's queue cursor + the waves' shared-leaf maps + the root's record
-    HIP_TRY(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)tp.lds_bytes));
-    int per_cu = 0;
-    HIP_TRY(ctx, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, (int)tp.block, tp.lds_bytes));
-    if (per_cu < 1) per_cu = 1;
-    tp.grid = (uint32_t)std::min<uint64_t>((uint64_t)per_cu * ctx->num_cus, (max_items + tp.block - 1) / tp.block);
+    LaunchGeom g;
+    if (int rc = occupancyGrid(ctx, reinterpret_cast<const void*>(kernel), tp.block, tp.lds_bytes, g)) return rc;
+    tp.grid = (uint32_t)std::min<uint64_t>(g.grid, (max_items + tp.block - 1) / tp.block);
     if (tp.grid < 1) tp.grid = 1;
     const uint32_t total_lanes = tp.grid * tp.block;
     if (!ctx->stats.p) HIP_TRY(ctx, ctx->stats.alloc(kStatsWords * sizeof(unsigned long long)));
@@ -379,13 +439,32 @@ int planTrace(mcrt_ctx* ctx, K kernel, uint64_t max_items, TracePlan& tp) {
     ta.prim = ctx->scene.prim;
     ta.spill = ctx->spill.as<SmStackEntry>();
     ta.total_lanes = total_lanes;
-    ta.refill_lanes = (int)envi("MCRT_WF_REFILL", 16);  // (32 while the queue cursor was one global atomic)
-    ta.leaf_lanes = (int)envi("MCRT_WF_LEAF", 16);  // (shared step, C3 64 spp: 8 / 12 / 16 / 20 pending lanes 412.7 / 402.1 / 398.1 / 402.3 ms; gating on 48-56 offered primitives instead: 398.4-399.0)
-    ta.leaf_items = (int)envi("MCRT_WF_LEAF_ITEMS", 1 << 20);
-    ta.min_inner = (int)envi("MCRT_WF_MININNER", 8);
+    ta.refill_lanes = kTraceRefillLanes;
+    ta.leaf_lanes = leaf_lanes;  // MCRT_WF_LEAF, default 16 (shared step, C3 64 spp: 8 / 12 / 16 / 20 pending lanes 412.7 / 402.1 / 398.1 / 402.3 ms; gating on 48-56 offered primitives instead: 398.4-399.0)
+    ta.leaf_items = kTraceLeafItems;
+    ta.min_inner = kTraceMinInner;
     ta.lds_stack = (int)lds_stack;
     ta.max_stack = ctx->scene.stack_depth;
-    ta.deal_shift = (uint32_t)std::min<long>(std::max<long>(envi("MCRT_WF_DEAL", 6), 6), 20);
+    ta.deal_shift = kTraceDealShift;
+    return MCRT_OK;
+}
+
+// The start of every frame: the statistics cleared, the clocks started, ev0 recorded (each pass clears the work counter itself).
+int beginFrame(mcrt_ctx* ctx, hipStream_t stream, uint32_t kernel_id) {
+    if (!ctx->work_counter.p) HIP_TRY(ctx, ctx->work_counter.alloc(sizeof(unsigned long long)));
+    if (!ctx->stats.p) HIP_TRY(ctx, ctx->stats.alloc(kStatsWords * sizeof(unsigned long long)));
+    ctx->t_begin = std::chrono::steady_clock::now();
+    ctx->launches = 0;
+    ctx->kernel_id = kernel_id;
+    HIP_TRY(ctx, hipMemsetAsync(ctx->stats.p, 0, kStatsWords * sizeof(unsigned long long), stream));
+    HIP_TRY(ctx, hipEventRecord(ctx->ev0, stream));
+    return MCRT_OK;
+}
+// ... and its end; a shard that owns no row ends right after it began.
+int endFrame(mcrt_ctx* ctx, hipStream_t stream) {
+    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, hipEventRecord(ctx->ev1, stream));
+    ctx->pending = true;
     return MCRT_OK;
 }
 
@@ -395,8 +474,8 @@ int planTrace(mcrt_ctx* ctx, K kernel, uint64_t max_items, TracePlan& tp) {
 // film_out != NULL (mcrt_render_film_device): the splats of this shard's samples stay in the caller's full-frame RGBW buffer
 // and the resolve is left to mcrt_film_resolve_device, after the caller has summed the shards' buffers.
 int launchWavefront(mcrt_ctx* ctx, const mcrt_camera_desc* cam, uint32_t global_seed, double* d_out, hipStream_t stream,
-                    bool count_tests, bool photon, double* film_out = nullptr) {
-    auto envi = [ctx](const char* k, long d) { return ctxOptL(ctx, k, d); };
+                    const RenderOptions& opt, const KernelChoice& choice, double* film_out = nullptr) {
+    const bool photon = choice.form == MCRT_KERNEL_WAVEFRONT_PM;
     WfFrame fr;
     memset(&fr, 0, sizeof(fr));
     fr.cam = *cam;
@@ -435,26 +514,16 @@ int launchWavefront(mcrt_ctx* ctx, const mcrt_camera_desc* cam, uint32_t global_
         HIP_TRY(ctx, hipMemsetAsync(f.blob, 0, blob_bytes, stream));
     }
 
-    if (!ctx->work_counter.p) HIP_TRY(ctx, ctx->work_counter.alloc(sizeof(unsigned long long)));
-    if (!ctx->stats.p) HIP_TRY(ctx, ctx->stats.alloc(kStatsWords * sizeof(unsigned long long)));
-    ctx->t_begin = std::chrono::steady_clock::now();
-    ctx->launches = 0;
-    ctx->kernel_id = owned_rows == 0 ? MCRT_KERNEL_NONE : photon ? MCRT_KERNEL_WAVEFRONT_PM : MCRT_KERNEL_WAVEFRONT;
-    HIP_TRY(ctx, hipMemsetAsync(ctx->work_counter.p, 0, sizeof(unsigned long long), stream));
-    HIP_TRY(ctx, hipMemsetAsync(ctx->stats.p, 0, kStatsWords * sizeof(unsigned long long), stream));
-    HIP_TRY(ctx, hipEventRecord(ctx->ev0, stream));
-    if (owned_rows == 0) {
-        HIP_TRY(ctx, hipEventRecord(ctx->ev1, stream));
-        ctx->pending = true;
-        return MCRT_OK;
-    }
+    if (int rc = beginFrame(ctx, stream, owned_rows == 0 ? (uint32_t)MCRT_KERNEL_NONE : choice.form)) return rc;
+    if (owned_rows == 0) return endFrame(ctx, stream);
+    ctx->lean_used = choice.lean || choice.knn_lean;
 
     // Passes: as many rows as the per-sample store holds (box filter; splat frames keep no samples and are one pass).
     const bool splats = fr.film.type != MCRT_FILM_BOX;
     uint64_t pass_rows = owned_rows;
     if (!splats) {
         PassPlan pp;
-        if (int rc = planSampleStore(ctx, cam->width, (uint32_t)owned_rows, fr.spp, pp)) return rc;
+        if (int rc = planSampleStore(ctx, opt.sample_store_gb, cam->width, (uint32_t)owned_rows, fr.spp, pp)) return rc;
         pass_rows = pp.pass_rows;
         fr.samples = ctx->samples.as<double>();
     }
@@ -464,7 +533,7 @@ int launchWavefront(mcrt_ctx* ctx, const mcrt_camera_desc* cam, uint32_t global_
     const uint64_t pixels = (uint64_t)cam->width * std::min<uint64_t>(pass_rows, owned_rows);
     // (round 4: 16 M by default - C3 at 1024 spp 2024 / 2068 / 2072 Mray/s with 8 / 16 / 32 M; 10 GB of pool and queue - but never more
     // than an eighth of the memory that is free on this device)
-    uint64_t slots = (uint64_t)envi("MCRT_WF_SLOTS", 1l << 24);
+    uint64_t slots = opt.wf_slots;  // MCRT_WF_SLOTS
     {
         size_t free_b = 0, total_b = 0;
         if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) {
@@ -476,13 +545,12 @@ int launchWavefront(mcrt_ctx* ctx, const mcrt_camera_desc* cam, uint32_t global_
         }
     }
     // ... and no more than the pass has work for: paths / 48, at least 2.5 M, never fewer than 4 samples per slot (planPoolSlots,
-    // mcrt_plan.hpp: the measurements; options MCRT_WF_SLOT_PATHS, MCRT_WF_SLOT_FLOOR)
+    // mcrt_plan.hpp: the measurements)
     // (photon-mapped frames: 16 path samples per slot - their iterations carry a kNN launch whose tails a larger pool amortises: C5 at
     // full size 2 757 ms with 48, 2 725 with 24, 2 713 with 12, 2 874 with 96: profiles/r06_ab_c5_pipeline_pool.log)
-    slots = planPoolSlots(pixels * fr.spp, slots, kWfBlock, (uint64_t)std::max(1l, (long)envi("MCRT_WF_SLOT_PATHS", photon ? 16 : 48)),
-                          (uint64_t)std::max(1l, (long)envi("MCRT_WF_SLOT_FLOOR", 2500000)), ctxOpt(ctx, "MCRT_WF_SLOT_PATHS") != nullptr);
+    slots = planPoolSlots(pixels * fr.spp, slots, kWfBlock, photon ? 16 : 48);
     {
-        const ChunkPlan cp = planChunks(fr.spp, unitsWanted(slots, 16, pixels, ctxOpt(ctx, "MCRT_CHUNKS")));
+        const ChunkPlan cp = planChunks(fr.spp, unitsWanted(slots, 16, pixels, opt.chunks));
         fr.chunk_shift = cp.shift;
         fr.chunk = cp.chunk;
     }
@@ -509,21 +577,16 @@ int launchWavefront(mcrt_ctx* ctx, const mcrt_camera_desc* cam, uint32_t global_
     HIP_TRY(ctx, hipMemsetAsync(ctx->wf_pool.as<unsigned long long>() + (size_t)kWfFlags * slots, 0, (size_t)slots * 8, stream));
     HIP_TRY(ctx, hipMemsetAsync(ctx->wf_pool.as<unsigned long long>() + (size_t)kWfSeq * slots, 0, (size_t)slots * 8, stream));
 
-    // MCRT_WF_LEAN (round 5; default 1): the inner visit is travInnerStepQLean - with one block per visit when the tree has no node with
-    // more than four children (every quaternary tree); 0 (and MCRT_COUNT_TESTS): round 4's visit; 2: the block loop kept on a quaternary tree
-    const int lean = !count_tests && ctxOptL(ctx, "MCRT_WF_LEAN", 1) != 0 ? (ctx->q_single && ctxOptL(ctx, "MCRT_WF_LEAN", 1) != 2 ? 3 : 1) : 0;
-    void (*trace)(WfTraceArgs, PoolRays) = lean == 3   ? wfTraceKernel<PoolRays, false, 3>
-                                           : lean == 1 ? wfTraceKernel<PoolRays, false, 1>
-                                                       : (count_tests ? wfTraceKernel<PoolRays, true> : wfTraceKernel<PoolRays, false>);
-    // + the materials and the light tables when they are small (MCRT_WF_LDS_TABLES=0: read them from memory)
+    const auto trace = kernelAs<TraceKernelT>(instanceAddress(choice.trace_instance, false));
+    // + the materials and the light tables when they are small
     uint32_t shade_tables = wfShadeTableBytes(ctx->scene.num_materials, ctx->scene.num_lights);
-    if (shade_tables > kWfShadeTableMax || ctxOptL(ctx, "MCRT_WF_LDS_TABLES", 1) == 0) shade_tables = 0;
+    if (shade_tables > kWfShadeTableMax) shade_tables = 0;
     const uint32_t shade_lds = kSobolTableWords * 4u + kMaxIors * kWfBlock * 8u + shade_tables;
-    // (the instances without the material features this scene does not use, when it uses none of them: leanOf)
-    const auto shade_pt = leanOf(ctx, wfShadeKernel<false>);
-    const auto shade_pm = leanOf(ctx, wfShadeKernel<true>);
+    const auto shade = kernelAs<ShadeKernelT>(instanceAddress(choice.instance, choice.lean));
+    const auto knn = photon ? kernelAs<KnnKernelT>(instanceAddress(choice.knn_instance, choice.knn_lean)) : nullptr;
+    if (!shade || (photon && !knn)) return fail(ctx, MCRT_ERR_INVALID, "internal error: no such lean kernel instance");
     TracePlan tp;
-    if (int rc = planTrace(ctx, trace, slots * 2, tp)) return rc;
+    if (int rc = planTrace(ctx, trace, slots * 2, opt.wf_leaf, tp)) return rc;
 
     // control words: {count[2] (one per iteration parity), pop} of the ray queue; 4..6 = {rcount[2], rpop} of the estimate requests
     unsigned long long* ctrl = ctx->wf_ctrl.as<unsigned long long>();
@@ -559,9 +622,7 @@ int launchWavefront(mcrt_ctx* ctx, const mcrt_camera_desc* cam, uint32_t global_
     bool knn_eval = false;
     if (photon) {
         const uint32_t k = ctx->k_nearest;
-        // MCRT_WF_PM_EVAL (default 1): the kNN launch evaluates the estimates from staged Interactions; 0: it hands the k photons
-        // back and the shade launch sums them per lane (round 2's form)
-        knn_eval = ctxOptL(ctx, "MCRT_WF_PM_EVAL", 1) != 0;
+        knn_eval = opt.wf_pm_eval;  // (selectKernel: which kNN kernel)
         if (ctx->wf_res_slots != slots || ctx->wf_res_k != k || (knn_eval ? !ctx->wf_stage.p : !ctx->wf_res_idx.p)) {
             HIP_TRY(ctx, ctx->wf_requests.alloc((size_t)slots * sizeof(uint32_t)));
             if (knn_eval) {
@@ -607,8 +668,8 @@ int launchWavefront(mcrt_ctx* ctx, const mcrt_camera_desc* cam, uint32_t global_
         s0.stage = knn_eval ? ctx->wf_stage.as<double>() : nullptr;
     }
 
-    // The host looks at the queue length every MCRT_WF_CHECK iterations (a launch with nothing to do costs microseconds)
-    const uint64_t check_every = (uint64_t)std::max<long>(2, envi("MCRT_WF_CHECK", 16));
+    // The host looks at the queue length every 16 iterations (a launch with nothing to do costs microseconds)
+    const uint64_t check_every = 16;
     for (uint64_t it = 0;; it++) {
         sa.count_out = ctrl + (it & 1);
         sa.count_reset = ctrl + ((it + 1) & 1);
@@ -618,10 +679,8 @@ int launchWavefront(mcrt_ctx* ctx, const mcrt_camera_desc* cam, uint32_t global_
         if (photon) {
             sa.rcount_out = ctrl + 4 + (it & 1);
             sa.rcount_reset = ctrl + 4 + ((it + 1) & 1);
-            hipLaunchKernelGGL(shade_pm, dim3(shade_grid), dim3(kWfBlock), shade_lds, stream, ctx->scene, sa);
-        } else {
-            hipLaunchKernelGGL(shade_pt, dim3(shade_grid), dim3(kWfBlock), shade_lds, stream, ctx->scene, sa);
         }
+        hipLaunchKernelGGL(shade, dim3(shade_grid), dim3(kWfBlock), shade_lds, stream, ctx->scene, sa);
         ctx->launches++;
         if (it % check_every == check_every - 1 || it < 2) {
             HIP_TRY(ctx, hipGetLastError());
@@ -629,7 +688,7 @@ int launchWavefront(mcrt_ctx* ctx, const mcrt_camera_desc* cam, uint32_t global_
             if (photon)  // requests count as work too
                 HIP_TRY(ctx, hipMemcpyAsync(ctx->wf_host + 1, ctrl + 4 + (it & 1), sizeof(unsigned long long), hipMemcpyDeviceToHost, stream));
             HIP_TRY(ctx, hipStreamSynchronize(stream));
-            if (ctxOptOn(ctx, "MCRT_WF_LOG"))  // queue length over the frame
+            if (opt.wf_log)  // MCRT_WF_LOG: queue length over the frame
                 fprintf(stderr, "[mcrt wf] iteration %llu queued %llu at %.2f ms\n", (unsigned long long)it, ctx->wf_host[0],
                         std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - ctx->t_begin).count());
             if (ctx->wf_host[0] == 0ull && (!photon || ctx->wf_host[1] == 0ull)) break;  // nothing queued: every slot is done
@@ -639,9 +698,7 @@ int launchWavefront(mcrt_ctx* ctx, const mcrt_camera_desc* cam, uint32_t global_
         ctx->launches++;
         if (photon) {
             ka.count = ctrl + 4 + (it & 1);
-            const bool large_k = ctx->k_nearest > waveMaxK(kWaveRows);  // the wide candidate buffer (mcrt_waveknn.hpp)
-            if (knn_eval) hipLaunchKernelGGL((large_k ? wfKnnKernel<true, kWaveRowsLarge> : leanOf(ctx, wfKnnKernel<true>)), dim3(knn_grid), dim3(256), 0, stream, ka);
-            else hipLaunchKernelGGL((large_k ? wfKnnKernel<false, kWaveRowsLarge> : wfKnnKernel<false>), dim3(knn_grid), dim3(256), 0, stream, ka);
+            hipLaunchKernelGGL(knn, dim3(knn_grid), dim3(256), 0, stream, ka);
             ctx->launches++;
         }
     }
@@ -667,9 +724,7 @@ int launchWavefront(mcrt_ctx* ctx, const mcrt_camera_desc* cam, uint32_t global_
         HIP_TRY(ctx, hipGetLastError());
         ctx->launches++;
     }
-    HIP_TRY(ctx, hipEventRecord(ctx->ev1, stream));
-    ctx->pending = true;
-    return MCRT_OK;
+    return endFrame(ctx, stream);
 }
 
 // Frames of DIFFERENT contexts on ONE device never overlap on the GPU: a launch waits (on the GPU, hipStreamWaitEvent) for the
@@ -691,21 +746,22 @@ struct DeviceOrder {
 DeviceOrder g_device_order[64];
 
 int launchRenderImpl(mcrt_ctx* ctx, const mcrt_camera_desc* cam, uint32_t global_seed, int integrator, double* d_out, hipStream_t stream,
-                     double* film_out);
+                     double* film_out, const RenderOptions& opt);
 int launchRender(mcrt_ctx* ctx, const mcrt_camera_desc* cam, uint32_t global_seed, int integrator, double* d_out, hipStream_t stream,
                  double* film_out = nullptr) {
     if (!ctx) return MCRT_ERR_INVALID;
     // Option MCRT_DEVICE_ORDER=0 (per context, like every option; TEST ONLY: tools/shared_gpu_stress.py, which looks for the fault the
     // ordering was added against): this context's frames do not wait on the GPU for the device's previous launcher. The mutex stays
     // either way - "size this kernel's dynamic LDS, then launch it" must be one step (DeviceOrder's comment).
-    const bool gpu_wait = ctxOptL(ctx, "MCRT_DEVICE_ORDER", 1) != 0;
+    const RenderOptions opt = parseRenderOptions(ctx->options);  // the one place a launch reads its options
+    const bool gpu_wait = opt.device_order;
     DeviceOrder& o = g_device_order[(unsigned)ctx->device & 63u];
     std::lock_guard<std::mutex> guard(o.m);
     if (gpu_wait && o.owner && o.owner != ctx) {
         HIP_TRY(ctx, hipSetDevice(ctx->device));
         HIP_TRY(ctx, hipStreamWaitEvent(stream, o.last, 0));
     }
-    const int rc = launchRenderImpl(ctx, cam, global_seed, integrator, d_out, stream, film_out);
+    const int rc = launchRenderImpl(ctx, cam, global_seed, integrator, d_out, stream, film_out, opt);
     if (rc == MCRT_OK && ctx->pending) {
         o.last = ctx->ev1;
         o.owner = ctx;
@@ -719,9 +775,12 @@ int launchRender(mcrt_ctx* ctx, const mcrt_camera_desc* cam, uint32_t global_see
     return rc;
 }
 
+// The state machine's scheduling thresholds (RenderParams::sm_*, mcrt_lanesm.hpp), at what the measurements left them
+constexpr int kSmShadeLanes = 40, kSmRegenLanes = 16, kSmMinTrav = 20, kSmLeafLanes = 32, kSmMinInner = 8;
+
+// validate -> selectKernel (mcrt_select.hpp) -> the instance's address -> launch geometry -> prologue -> one launch per pass
 int launchRenderImpl(mcrt_ctx* ctx, const mcrt_camera_desc* cam, uint32_t global_seed, int integrator, double* d_out, hipStream_t stream,
-                     double* film_out) {
-    if (!ctx) return MCRT_ERR_INVALID;
+                     double* film_out, const RenderOptions& opt) {
     if (!ctx->has_scene) return fail(ctx, MCRT_ERR_NO_SCENE, "mcrt_render before mcrt_upload_scene");
     if (int rc = validateCamera(ctx, cam)) return rc;
     const bool photon = integrator == MCRT_INTEGRATOR_PHOTON_MAPPER;
@@ -731,208 +790,56 @@ int launchRenderImpl(mcrt_ctx* ctx, const mcrt_camera_desc* cam, uint32_t global
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     ctx->lean_used = false;
 
-    const bool count_tests = ctxOptOn(ctx, "MCRT_COUNT_TESTS");
-    using KernelT = void (*)(const DeviceScene, const RenderParams);
-    const bool all = ctx->scene.stage_all != 0;
-    constexpr int PT = MCRT_INTEGRATOR_PATH_TRACER, PM = MCRT_INTEGRATOR_PHOTON_MAPPER;
-    static const KernelT table[2][2][2] = {
-        {{renderKernel<PT, false, false>, renderKernel<PT, false, true>}, {renderKernel<PT, true, false>, renderKernel<PT, true, true>}},
-        {{renderKernel<PM, false, false>, renderKernel<PM, false, true>}, {renderKernel<PM, true, false>, renderKernel<PM, true, true>}}};
-    KernelT kernel = table[photon ? 1 : 0][count_tests ? 1 : 0][all ? 1 : 0];
-    const bool profile_phases = ctxOptOn(ctx, "MCRT_PROFILE_PHASES");
-    if (profile_phases && !photon) kernel = all ? renderKernel<PT, false, true, true> : renderKernel<PT, false, false, true>;
-    const bool flat_only = !photon && ctx->scene.flat && ctx->scene.flat_pre && all && !count_tests && !profile_phases && !ctxOptOn(ctx, "MCRT_FLAT_GENERIC");
-    // Flat-mode scenes get their own instance of the kernel: without the BVH walk in the code it needs no traversal stack
-    // (64 KB of LDS at 512 lanes), so a CU can hold more waves; measured on the C2 frame (ms): generic instance 862,
-    // flat instance with 512 lanes (2 waves/SIMD, 256 VGPRs, no scratch) 795, 768 lanes (3, 168 VGPRs, 336 B/lane of
-    // scratch) 716, 1024 lanes (4, 128 VGPRs, 524 B/lane) 690 — the FP64 dependency chains of the primitive tests and the
-    // BSDF code want the extra waves more than they mind the spills.
-    // With the FP32 cull in front of the FP64 tests (mcrt_scene.hpp) the order is reversed: 512 lanes 448.7 ms, 768 lanes 455.8,
-    // 1024 lanes 485.2 (split next-event estimate: 454 / 493 / 563) — fewer instructions per ray, and the spills of the
-    // narrow instances (107 / 169 VGPRs) now cost more than the extra waves hide.
-    // MCRT_FLAT_KARG (round 5, default 1): the cull records travel in the kernel's argument block and are read with scalar loads
-    // (renderKernelFlatK) - when they fit it. With the records in SGPRs the 768-lane shape (3 waves per SIMD, 168 VGPRs) is the
-    // fastest: C2 439.6 ms against 442.8 at 512 lanes and 478 at 1024, C2-GGX 596.9 against 614.6 and 649
-    // (profiles/r05_ab_c2_flat_karg.log) - so that is the default where the argument-block form applies, 512 lanes elsewhere.
-    const bool flat_karg = flat_only && ctxOptL(ctx, "MCRT_FLAT_KARG", 1) != 0 && !ctx->flat_pre_host.empty() && ctx->flat_pre_host.size() <= kFlatPreArgFloats &&
-                           ctx->flat_pre_host.size() == (size_t)ctx->scene.pre_tri_pairs * kTriPairFloats + (size_t)ctx->scene.pre_sph_pairs * kSphPairFloats;
-    // (... of the full instance. The lean one - a scene without rough / conductor materials, leanOf - spills NOTHING at 512 lanes and is
-    // fastest there: C2 108.2 ms per 64-spp frame against 111.0 at 768 lanes and the full instance's 112.0, profiles/r06_ab_feature_strip_probe.log)
-    int flat_block = (int)ctxOptL(ctx, "MCRT_FLAT_BLOCK", flat_karg && !leanScene(ctx) ? 768 : 512);
-    if (flat_block != 512 && flat_block != 768 && flat_block != 1024) flat_block = 512;
-    // (Round 4 built a form that dealt a wave's (ray, cull survivor) pairs over all 64 lanes for the FP64 tests; measured in round 5 it
-    // LOST 8 % on C2 and on C2-GGX - 482 ms against 446, 663 against 614, profiles/r05_ab_c2_flat_share.log - and was removed.)
-    if (flat_only)
-        kernel = leanOf(ctx, flat_block == 1024 ? renderKernel<PT, false, true, false, 3>
-                                                : flat_block == 768 ? renderKernel<PT, false, true, false, 2> : renderKernel<PT, false, true, false, 1>);
-    // path tracing of scenes whose BVH is walked: lane-state-machine kernel (MCRT_KERNEL=legacy keeps the
-    // wave-synchronous one for A/B runs)
-    const char* kenv = ctxOpt(ctx, "MCRT_KERNEL");
-    const bool use_sm = !photon && !ctx->scene.flat && !(kenv && strcmp(kenv, "legacy") == 0);
-    // ... and when the tree lives in HBM, the wavefront pipeline (MCRT_KERNEL=sm keeps the megakernel, MCRT_KERNEL=wf
-    // forces the wavefront pipeline for any scene that has a BVH)
-    const bool filtered = filmSplats(cam->film_filter, cam->film_radius);  // per-sample splats: the wavefront pipeline's shade kernel has them
-    if (film_out && !filtered)
-        return fail(ctx, MCRT_ERR_INVALID, "mcrt_render_film_device is for splatted frames (a reconstruction filter, or the box filter with a radius other than 0.5)");
-    // (a scene without a BVH is walked through a tree over index ranges by the pipeline's trace kernel, mcrt_layout.hpp)
-    const bool has_tree = ctx->scene.q_nodes > 0;
-    if (filtered && !has_tree)
-        return fail(ctx, MCRT_ERR_UNSUPPORTED, "reconstruction filters need the wavefront pipeline, and this scene has neither a BVH nor finite surface bounds to build its stand-in from");
-    // Film::Film(w, h, json) with "filter": "box" and a radius other than the default 0.5 splats too (film.cpp:27-30); that case
-    // is not built, so it is refused rather than rendered as the default box
-    constexpr uint32_t kWaveKMax = waveMaxK(kWaveRowsLarge);  // 768: what the wave-cooperative search's widest candidate buffer serves
-    if (filtered && photon && ctx->k_nearest > kWaveKMax)
-        return fail(ctx, MCRT_ERR_UNSUPPORTED, "reconstruction filters on photon-mapped frames need k_nearest_photons <= 768 (wavefront pipeline)");
-    const bool want_wf = filtered || (kenv && strcmp(kenv, "wf") == 0) || ctx->force_wf;
-    // measured: the pipeline wins on deep trees (metal_bunnies 169 k nodes +28 %, spaceship with hulls 154 k
-    // nodes +7 %), the megakernel on small ones (spaceship cockpit 23 k nodes: 1352 vs 940 Mray/s)
-    const char* mn = ctxOpt(ctx, "MCRT_WF_MIN_NODES");
-    const uint32_t wf_min_nodes = mn ? (uint32_t)strtoul(mn, nullptr, 0) : 65536u;
-    // ... and, since round 4's trace kernel, on ANY tree in memory once the frame is large enough to amortise the pipeline's launches
-    // (spaceship cockpit, 23 k nodes, 1080p, ms per frame megakernel / pipeline: 2 M paths 9.4 / 19.1, 8 M 24.5 / 35.3, 33 M 80.9 /
-    // 77.3, 133 M 311 / 228): MCRT_WF_MIN_PATHS path samples in this call's rows, default 32 M
-    const char* mp = ctxOpt(ctx, "MCRT_WF_MIN_PATHS");
-    const uint64_t wf_min_paths = mp ? strtoull(mp, nullptr, 0) : 32000000ull;
-    const uint64_t frame_paths = (uint64_t)mcrt_shard_rows(cam, nullptr) * cam->width * cam->sqrtspp * cam->sqrtspp;
-    if (!photon && has_tree && (want_wf || (use_sm && !all && !kenv && (ctx->scene.num_nodes >= wf_min_nodes || frame_paths >= wf_min_paths))))
-        return launchWavefront(ctx, cam, global_seed, d_out, stream, count_tests, false, film_out);
-    // photon-mapped frames go through the pipeline (trace / kNN / shade launches) on request only: measured slower than
-    // renderKernelPM (C5 9.3 vs 7.4 s per frame, hexagon_room map 308 vs 242 ms) — the kNN search is bound by the number of
-    // wave instructions per query (one query per wave leaves most lanes idle), which more waves per SIMD do not fix, and
-    // the pipeline adds its shade launches on top. k must fit the per-wave candidate buffer.
-    // Round 6: ... and by itself for a scene whose tree stays in memory, whose materials allow the lean instances (leanOf) and whose k
-    // fits the narrow buffers, once the frame is large enough (MCRT_WF_PM_MIN_PATHS path samples in this call's rows, default 32 M). With
-    // the lean kNN launch (17 instead of 61 spilled registers, 6 waves per SIMD) and the lean shade launch (8 instead of 192) C5 renders
-    // in 739 ms per 64-spp frame against the megakernel's 817 (profiles/r06_ab_lean_knn_occupancy.log): the pipeline's kernels each run at
-    // their own register budget, the megakernel's estimates at the budget of its bounce code. LDS-resident scenes stay with the
-    // megakernel (hexagon_room_pm 93.7 ms against 136).
-    const char* pmp = ctxOpt(ctx, "MCRT_WF_PM_MIN_PATHS");
-    const uint64_t wf_pm_min_paths = pmp ? strtoull(pmp, nullptr, 0) : 32000000ull;
-    const bool pm_pipeline = photon && has_tree && !all && !kenv && !count_tests && leanScene(ctx) && ctx->k_nearest <= waveMaxK(kWaveRows) &&
-                             frame_paths >= wf_pm_min_paths;
-    if (photon && has_tree && ctx->k_nearest <= kWaveKMax && (want_wf || pm_pipeline) && !ctx->force_pm_lane)
-        return launchWavefront(ctx, cam, global_seed, d_out, stream, count_tests, true, film_out);
-    // workgroup size of the state-machine kernel for trees that stay in HBM (MCRT_SM_BLOCK: 512 / 768 / 1024 lanes) and the
-    // stack entries per lane it keeps in LDS (MCRT_SM_STACK; the rest of a lane's stack is in the HBM spill area)
-    int sm_block = (int)kBlock, sm_depth = kLdsStackDepth;
-    if (use_sm) {
-        static const KernelT sm_table[2][2] = {{renderKernelSM<false, false>, renderKernelSM<false, true>},
-                                               {renderKernelSM<true, false>, renderKernelSM<true, true>}};
-        kernel = leanOf(ctx, sm_table[count_tests ? 1 : 0][all ? 1 : 0]);
-        if (profile_phases) kernel = all ? renderKernelSM<false, true, true> : renderKernelSM<false, false, true>;
-        const int want = (int)ctxOptL(ctx, "MCRT_SM_BLOCK", (long)kBlock);
-        if (!all && !count_tests && !profile_phases && (want == 768 || want == 1024)) {
-            sm_block = want;
-            sm_depth = want == 768 ? 8 : 6;
-            kernel = want == 768 ? renderKernelSM<false, false, false, 768> : renderKernelSM<false, false, false, 1024>;
-        }
-        if (ctxOpt(ctx, "MCRT_SM_STACK")) sm_depth = std::min(std::max((int)ctxOptL(ctx, "MCRT_SM_STACK", 0), 2), (int)kLdsStackDepth);
-    }
+    const uint32_t owned_rows = mcrt_shard_rows(cam, nullptr);
+    FrameFacts frame;
+    frame.photon = photon;
+    frame.paths = (uint64_t)owned_rows * cam->width * cam->sqrtspp * cam->sqrtspp;
+    // Film::Film(w, h, json) with "filter": "box" and a radius other than the default 0.5 splats too (film.cpp:27-30)
+    frame.filtered = filmSplats(cam->film_filter, cam->film_radius);
+    frame.film_out = film_out != nullptr;
+    frame.k_nearest = ctx->k_nearest;
+    frame.max_lds = (uint32_t)ctx->max_lds;
+    frame.force_wf = ctx->force_wf;
+    frame.force_pm_lane = ctx->force_pm_lane;
+    const KernelChoice choice = selectKernel(ctx->facts, frame, opt);
+    if (choice.err != MCRT_OK) return fail(ctx, choice.err, choice.message);
+    if (choice.form == MCRT_KERNEL_WAVEFRONT || choice.form == MCRT_KERNEL_WAVEFRONT_PM)
+        return launchWavefront(ctx, cam, global_seed, d_out, stream, opt, choice, film_out);
 
-    // photon mapping: wave-cooperative estimates unless k is too large for the widest per-wave buffer (k <= 128: 256 candidates per
-    // wave; k <= 768: 1024 candidates per wave, 512 lanes per workgroup)
-    bool use_pm_wave = photon && ctx->k_nearest <= kWaveKMax && !(kenv && strcmp(kenv, "legacy") == 0) && !ctx->force_pm_lane;
-    const bool pm_large_k = use_pm_wave && ctx->k_nearest > waveMaxK(kWaveRows);
-    if (pm_large_k) {
-        // the wide buffers take 100 KB of a 512-lane workgroup's LDS: a BVH staged whole with its 16 stack entries per lane may not
-        // leave that (a tree in HBM keeps as few as 2 entries per lane in LDS, a flat scene has no stack) - then the per-lane kernel
-        DeviceScene probe = ctx->scene;
-        if (!probe.stage_all) probe.stage_nodes = std::min<uint32_t>(probe.stage_nodes, 128u);
-        const uint32_t least = alignUp(planLds(probe, kBlock, true, probe.stage_all ? (uint32_t)kLdsStackDepth : 2u, kPmLdsIors).total, 16) +
-                               (kBlock / 64) * (waveKnnBytes(kWaveRowsLarge) + kWaveStateBytes);
-        if (least > ctx->max_lds) use_pm_wave = false;
-    }
-    using PmKernelT = void (*)(const DeviceScene, const RenderParams, const PmExtra);
-    PmKernelT pm_kernel = nullptr;
-    using FlatKT = void (*)(const DeviceScene, const RenderParams, const FlatPreArg);
-    FlatKT flatk_kernel = nullptr;
+    const void* kernel = instanceAddress(choice.instance, choice.lean);
+    if (!kernel) return fail(ctx, MCRT_ERR_INVALID, "internal error: no such lean kernel instance");
+    const bool pm_wave = choice.form == MCRT_KERNEL_PM_WAVE, use_sm = choice.form == MCRT_KERNEL_LANE_SM;
+    const bool pm_wide = pm_wave && choice.instance >= kInstPMWide && choice.instance <= kInstPMWide_CountAll;
+    const bool flat_karg = choice.instance == kInstFlatK512 || choice.instance == kInstFlatK768;
     DeviceScene launch_scene = ctx->scene;
-    if (ctxOpt(ctx, "MCRT_FLAT_CULL") && !ctxOptOn(ctx, "MCRT_FLAT_CULL")) launch_scene.flat_pre = nullptr;  // A/B: every primitive in FP64
-    LaunchGeom g;
-    uint32_t pm_stack_depth = kLdsStackDepth;
-    if (use_pm_wave) {
-        static const PmKernelT pm_table[2][2][2] = {{{renderKernelPM<false, false>, renderKernelPM<false, true>},
-                                                     {renderKernelPM<true, false>, renderKernelPM<true, true>}},
-                                                    {{renderKernelPM<false, false, 1024>, renderKernelPM<false, true, 1024>},
-                                                     {renderKernelPM<true, false, 1024>, renderKernelPM<true, true, 1024>}}};
+    uint32_t lds_bytes;
+    if (pm_wave) {
         if (!launch_scene.stage_all) launch_scene.stage_nodes = std::min<uint32_t>(launch_scene.stage_nodes, 128u);
-        // 1024 lanes per workgroup (4 waves per SIMD) when the LDS plan allows it: flat scenes have no traversal stack; a tree in
-        // HBM is walked with the state machine's stack, of which then only a few entries per lane stay in LDS (the rest
-        // spills to HBM); a staged BVH walked by the wave-synchronous code needs its 16 entries (512 lanes).
-        static const PmKernelT pm_table_large[2][2] = {{renderKernelPM<false, false, (int)kBlock, kWaveRowsLarge>, renderKernelPM<false, true, (int)kBlock, kWaveRowsLarge>},
-                                                       {renderKernelPM<true, false, (int)kBlock, kWaveRowsLarge>, renderKernelPM<true, true, (int)kBlock, kWaveRowsLarge>}};
-        const int want = pm_large_k ? (int)kBlock : (int)ctxOptL(ctx, "MCRT_PM_BLOCK", 1024);
-        const uint32_t knn_bytes = waveKnnBytes(pm_large_k ? kWaveRowsLarge : kWaveRows) + (all ? 0u : kWaveStateBytes);
-        g.block = kBlock;
-        // (the 1024-lane instance keeps two refraction-history entries per lane in LDS, the deeper ones in global memory)
-        auto ldsBytes = [&](uint32_t block, uint32_t depth) {
-            return alignUp(planLds(launch_scene, block, true, depth, (block != 1024u && !pm_large_k) ? (uint32_t)kMaxIors : kPmLdsIors).total, 16) + (block / 64) * knn_bytes;
-        };
-        if (pm_large_k && !launch_scene.stage_all) {
-            pm_stack_depth = 2;
-            for (uint32_t depth = 16u; depth > 2u; depth -= 2)
-                if (ldsBytes(kBlock, depth) <= ctx->max_lds) {
-                    pm_stack_depth = depth;
-                    break;
-                }
-        }
-        // (round 5: a 768-lane instance - 3 waves per SIMD, 168 VGPRs, 639 instead of 769 spill instructions - measured 895 ms against
-        // 762 on the C5 probe and 112 against 101 on pm, profiles/r05_ab_pm768.log: this kernel wants its four waves)
-        if (want == 1024) {
-            const uint32_t wb = 1024u;
-            if (launch_scene.flat && ldsBytes(wb, kLdsStackDepth) <= ctx->max_lds) {
-                g.block = wb;
-            } else if (!launch_scene.stage_all) {
-                const uint32_t depth_max = ctxOpt(ctx, "MCRT_PM_STACK") ? (uint32_t)std::max(2, (int)ctxOptL(ctx, "MCRT_PM_STACK", 16)) & ~1u : 16u;
-                for (uint32_t depth = depth_max; depth >= 2 && g.block == kBlock; depth -= 2)
-                    if (ldsBytes(wb, depth) <= ctx->max_lds) {
-                        g.block = wb;
-                        pm_stack_depth = depth;
-                    }
-            }
-        }
-        pm_kernel = pm_large_k ? pm_table_large[count_tests ? 1 : 0][all ? 1 : 0] : pm_table[g.block == 1024 ? 1 : 0][count_tests ? 1 : 0][all ? 1 : 0];
-        pm_kernel = leanOf(ctx, pm_kernel);
-        g.lds_bytes = ldsBytes(g.block, pm_stack_depth);
-        if (g.lds_bytes > ctx->max_lds) return fail(ctx, MCRT_ERR_INVALID, "LDS plan exceeds the device limit");
-        HIP_TRY(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(pm_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)g.lds_bytes));
-        int per_cu = 0;
-        HIP_TRY(ctx, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, pm_kernel, (int)g.block, g.lds_bytes));
-        if (per_cu < 1) per_cu = 1;
-        g.grid = (uint32_t)(per_cu * ctx->num_cus);
-        g.total_lanes = g.grid * g.block;
+        const uint32_t knn_bytes = waveKnnBytes(pm_wide ? kWaveRowsLarge : kWaveRows) + (launch_scene.stage_all ? 0u : kWaveStateBytes);
+        lds_bytes = alignUp(planLds(launch_scene, choice.block, true, choice.stack_depth, (choice.block != 1024u && !pm_wide) ? (uint32_t)kMaxIors : kPmLdsIors).total, 16) +
+                    (choice.block / 64) * knn_bytes;
     } else if (use_sm) {
-        // the staged top of the tree shrinks to what the larger workgroup's stacks and refraction histories leave
-        g.block = (uint32_t)sm_block;
-        const uint32_t fixed = planSmLds(DeviceScene{}, g.block, (uint32_t)sm_depth).total;
+        // the staged top of the tree shrinks to what the workgroup's stacks and refraction histories leave
+        const uint32_t fixed = planSmLds(DeviceScene{}, choice.block, choice.stack_depth).total;
         if (!launch_scene.stage_all && fixed < ctx->max_lds)
             launch_scene.stage_nodes = std::min<uint32_t>(launch_scene.stage_nodes, (ctx->max_lds - fixed) / 64u);
-        g.lds_bytes = planSmLds(launch_scene, g.block, (uint32_t)sm_depth).total;
-        if (g.lds_bytes > ctx->max_lds) return fail(ctx, MCRT_ERR_INVALID, "LDS plan exceeds the device limit");
-        HIP_TRY(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)g.lds_bytes));
-        int per_cu = 0;
-        HIP_TRY(ctx, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, (int)g.block, g.lds_bytes));
-        if (per_cu < 1) per_cu = 1;
-        g.grid = (uint32_t)(per_cu * ctx->num_cus);
-        g.total_lanes = g.grid * g.block;
-    } else if (flat_karg && launch_scene.flat_pre) {
-        flatk_kernel = leanOf(ctx, flat_block == 1024 ? renderKernelFlatK<1024> : flat_block == 768 ? renderKernelFlatK<768> : renderKernelFlatK<>);
-        if (int rc = launchGeometry(ctx, flatk_kernel, launch_scene, g, flat_block == 1024 ? 4 : flat_block == 768 ? 3 : 2)) return rc;
-    } else if (int rc = launchGeometry(ctx, kernel, launch_scene, g, flat_only ? (flat_block == 1024 ? 4 : flat_block == 768 ? 3 : 2) : 0)) {
-        return rc;
+        lds_bytes = planSmLds(launch_scene, choice.block, choice.stack_depth).total;
+    } else {
+        lds_bytes = planLds(launch_scene, choice.block, choice.form != MCRT_KERNEL_FLAT).total;  // (the flat loop has no stack in LDS)
     }
-    if (int rc = ensureScratch(ctx, g.total_lanes, photon && !use_pm_wave)) return rc;
-    if (use_sm && sm_depth < kLdsStackDepth)
-        if (int rc = ensureSpill(ctx, (size_t)g.total_lanes * (ctx->scene.stack_depth - sm_depth) * sizeof(StackEntry))) return rc;
-    if (use_pm_wave && pm_stack_depth < (uint32_t)kLdsStackDepth)
-        if (int rc = ensureSpill(ctx, (size_t)g.total_lanes * (ctx->scene.stack_depth - pm_stack_depth) * sizeof(StackEntry))) return rc;
+    if (lds_bytes > ctx->max_lds) return fail(ctx, MCRT_ERR_INVALID, "LDS plan exceeds the device limit");
+    LaunchGeom g;
+    if (int rc = occupancyGrid(ctx, kernel, choice.block, lds_bytes, g)) return rc;
+    if (int rc = ensureScratch(ctx, g.total_lanes, photon && !pm_wave)) return rc;
+    if (pm_wave && choice.stack_depth < (uint32_t)kLdsStackDepth)
+        if (int rc = ensureSpill(ctx, (size_t)g.total_lanes * (ctx->scene.stack_depth - choice.stack_depth) * sizeof(StackEntry))) return rc;
 
     RenderParams prm;
     memset(&prm, 0, sizeof(prm));
     prm.cam = *cam;
     prm.global_seed = global_seed;
     prm.spp = cam->sqrtspp * cam->sqrtspp;
-    prm.owned_rows = mcrt_shard_rows(cam, nullptr);
+    prm.owned_rows = owned_rows;
     prm.tiles_x = (cam->width + 7) / 8;
     prm.tiles_y = (prm.owned_rows + 7) / 8;
     prm.work_items = (uint64_t)prm.tiles_x * prm.tiles_y * 64ull;
@@ -940,15 +847,12 @@ int launchRenderImpl(mcrt_ctx* ctx, const mcrt_camera_desc* cam, uint32_t global
     prm.stats = ctx->stats.as<unsigned long long>();
     prm.spill = ctx->spill.as<StackEntry>();
     prm.total_lanes = g.total_lanes;
-    {
-        auto envi = [ctx](const char* k, int d) { return (int)ctxOptL(ctx, k, d); };
-        prm.sm_shade_lanes = envi("MCRT_SM_SHADE", 40);
-        prm.sm_regen_lanes = envi("MCRT_SM_REGEN", 16);
-        prm.sm_min_trav = envi("MCRT_SM_MINTRAV", 20);
-        prm.sm_leaf_lanes = envi("MCRT_SM_LEAF", 32);
-        prm.sm_min_inner = envi("MCRT_SM_MININNER", 8);
-        prm.sm_lds_depth = sm_depth;
-    }
+    prm.sm_shade_lanes = kSmShadeLanes;
+    prm.sm_regen_lanes = kSmRegenLanes;
+    prm.sm_min_trav = kSmMinTrav;
+    prm.sm_leaf_lanes = kSmLeafLanes;
+    prm.sm_min_inner = kSmMinInner;
+    prm.sm_lds_depth = kLdsStackDepth;
     if (photon) {
         prm.global_map = ctx->maps[0];
         prm.caustic_map = ctx->maps[1];
@@ -960,85 +864,64 @@ int launchRenderImpl(mcrt_ctx* ctx, const mcrt_camera_desc* cam, uint32_t global
         prm.knn_visit_oct = ctx->knn_visit_oct.as<uint32_t>();
         prm.knn_max_visit = ctx->knn_visit_alloc;
     }
-    ctx->kernel_id = prm.owned_rows == 0 ? MCRT_KERNEL_NONE
-                     : use_pm_wave   ? MCRT_KERNEL_PM_WAVE
-                     : photon        ? MCRT_KERNEL_PM_LANE
-                     : use_sm        ? MCRT_KERNEL_LANE_SM
-                     : flat_only     ? MCRT_KERNEL_FLAT
-                                     : MCRT_KERNEL_WAVESYNC;
-    if (prm.owned_rows == 0) {
-        ctx->pending = true;
-        ctx->launches = 0;
-        ctx->t_begin = std::chrono::steady_clock::now();
-        HIP_TRY(ctx, hipMemsetAsync(ctx->stats.p, 0, kStatsWords * sizeof(unsigned long long), stream));
-        HIP_TRY(ctx, hipEventRecord(ctx->ev0, stream));
-        HIP_TRY(ctx, hipEventRecord(ctx->ev1, stream));
-        return MCRT_OK;
-    }
-    ctx->t_begin = std::chrono::steady_clock::now();
-    ctx->launches = 0;
-    HIP_TRY(ctx, hipMemsetAsync(ctx->stats.p, 0, kStatsWords * sizeof(unsigned long long), stream));
-    HIP_TRY(ctx, hipEventRecord(ctx->ev0, stream));
-    {
-        // Sample-chunked work units (RenderParams): the frame goes through in passes of as many rows as the per-sample
-        // store holds (MCRT_SAMPLE_STORE_GB, default 64: mcrt_plan.hpp), each pass = one
-        // integrator launch + the in-order resolve.
-        PassPlan pp;
-        if (int rc = planSampleStore(ctx, cam->width, prm.owned_rows, prm.spp, pp)) return rc;
-        const uint64_t pass_rows = pp.pass_rows;
-        prm.samples = ctx->samples.as<double>();
-        PmExtra pmx;
-        if (use_pm_wave) {
-            pmx.global_map = waveMapView(ctx, 0);
-            pmx.caustic_map = waveMapView(ctx, 1);
-            pmx.stack_depth = pm_stack_depth;
-            pmx.iors_global = nullptr;
-            HIP_TRY(ctx, ctx->pm_stage.reserve((size_t)kStageDoubles * g.total_lanes * sizeof(double)));
-            pmx.stage = ctx->pm_stage.as<double>();
-            HIP_TRY(ctx, ctx->knn_spill.reserve((size_t)(g.total_lanes / 64) * kWaveSpill * 12));
-            pmx.knn_spill = ctx->knn_spill.as<uint32_t>();
-            if (g.block == 1024u || pm_large_k) {  // (two refraction-history entries per lane in LDS, the deeper ones in memory)
-                HIP_TRY(ctx, ctx->pm_iors.reserve((size_t)kMaxIors * g.total_lanes * sizeof(double)));
-                pmx.iors_global = ctx->pm_iors.as<double>();
-            }
-        }
-        for (uint32_t row = 0; row < prm.owned_rows; row += (uint32_t)pass_rows) {
-            prm.row_base = row;
-            prm.row_end = (uint32_t)std::min<uint64_t>(prm.owned_rows, row + pass_rows);
-            prm.pass_pixels = (uint64_t)(prm.row_end - prm.row_base) * cam->width;
-            // units per pixel: a power of two that gives every resident lane >= 128 units in chunks of at least 16 samples
-            // (planChunksMega, mcrt_plan.hpp: the measurements behind it)
-            // (photon-mapped frames keep the short chunks: their paths differ far more in cost - a search per diffuse hit - and the
-            // balance is worth more than the units' fixed cost: C5 at 64 spp 770 ms with 64 units of 4 samples, 791 with 16 of 16)
-            const ChunkPlan cp = photon ? planChunks(prm.spp, unitsWanted(g.total_lanes, 128, prm.pass_pixels, ctxOpt(ctx, "MCRT_CHUNKS")))
-                                        : planChunksMega(prm.spp, g.total_lanes, prm.pass_pixels, ctxOpt(ctx, "MCRT_CHUNKS"));
-            const uint32_t shift = cp.shift;
-            prm.chunk_shift = cp.shift;
-            prm.chunk = cp.chunk;
-            const uint64_t tiles = (uint64_t)prm.tiles_x * ((prm.row_end - prm.row_base + 7) / 8);
-            prm.work_items = (tiles * 64ull) << shift;
-            // never launch more lanes than there is work
-            const uint32_t grid = (uint32_t)std::min<uint64_t>(g.grid, (prm.work_items + g.block - 1) / g.block);
-            HIP_TRY(ctx, hipMemsetAsync(ctx->work_counter.p, 0, sizeof(unsigned long long), stream));
-            if (use_pm_wave) {
-                hipLaunchKernelGGL(pm_kernel, dim3(grid), dim3(g.block), g.lds_bytes, stream, launch_scene, prm, pmx);
-            } else if (flat_karg && launch_scene.flat_pre) {
-                FlatPreArg pre;
-                memset(&pre, 0, sizeof(pre));
-                memcpy(pre.v, ctx->flat_pre_host.data(), ctx->flat_pre_host.size() * sizeof(float));
-                hipLaunchKernelGGL(flatk_kernel, dim3(grid), dim3(g.block), g.lds_bytes, stream, launch_scene, prm, pre);
-            } else {
-                hipLaunchKernelGGL(kernel, dim3(grid), dim3(g.block), g.lds_bytes, stream, launch_scene, prm);
-            }
-            hipLaunchKernelGGL(sampleResolveKernel, dim3((uint32_t)((prm.pass_pixels + 255) / 256)), dim3(256), 0, stream, prm.samples,
-                               prm.pass_pixels, prm.spp, d_out + (size_t)prm.row_base * cam->width * 3);
-            ctx->launches += 2;
+    if (int rc = beginFrame(ctx, stream, owned_rows == 0 ? (uint32_t)MCRT_KERNEL_NONE : choice.form)) return rc;
+    if (owned_rows == 0) return endFrame(ctx, stream);
+    ctx->lean_used = choice.lean;
+
+    // Sample-chunked work units (RenderParams): the frame goes through in passes of as many rows as the per-sample store holds
+    // (MCRT_SAMPLE_STORE_GB, default 64: mcrt_plan.hpp), each pass = one integrator launch + the in-order resolve.
+    PassPlan pp;
+    if (int rc = planSampleStore(ctx, opt.sample_store_gb, cam->width, prm.owned_rows, prm.spp, pp)) return rc;
+    const uint64_t pass_rows = pp.pass_rows;
+    prm.samples = ctx->samples.as<double>();
+    PmExtra pmx;
+    if (pm_wave) {
+        pmx.global_map = waveMapView(ctx, 0);
+        pmx.caustic_map = waveMapView(ctx, 1);
+        pmx.stack_depth = choice.stack_depth;
+        pmx.iors_global = nullptr;
+        HIP_TRY(ctx, ctx->pm_stage.reserve((size_t)kStageDoubles * g.total_lanes * sizeof(double)));
+        pmx.stage = ctx->pm_stage.as<double>();
+        HIP_TRY(ctx, ctx->knn_spill.reserve((size_t)(g.total_lanes / 64) * kWaveSpill * 12));
+        pmx.knn_spill = ctx->knn_spill.as<uint32_t>();
+        if (g.block == 1024u || pm_wide) {  // (two refraction-history entries per lane in LDS, the deeper ones in memory)
+            HIP_TRY(ctx, ctx->pm_iors.reserve((size_t)kMaxIors * g.total_lanes * sizeof(double)));
+            pmx.iors_global = ctx->pm_iors.as<double>();
         }
     }
-    HIP_TRY(ctx, hipGetLastError());
-    HIP_TRY(ctx, hipEventRecord(ctx->ev1, stream));
-    ctx->pending = true;
-    return MCRT_OK;
+    FlatPreArg pre;
+    if (flat_karg) {  // the cull records travel in the kernel's argument block
+        memset(&pre, 0, sizeof(pre));
+        memcpy(pre.v, ctx->flat_pre_host.data(), ctx->flat_pre_host.size() * sizeof(float));
+    }
+    for (uint32_t row = 0; row < prm.owned_rows; row += (uint32_t)pass_rows) {
+        prm.row_base = row;
+        prm.row_end = (uint32_t)std::min<uint64_t>(prm.owned_rows, row + pass_rows);
+        prm.pass_pixels = (uint64_t)(prm.row_end - prm.row_base) * cam->width;
+        // units per pixel: a power of two that gives every resident lane >= 128 units in chunks of at least 16 samples
+        // (planChunksMega, mcrt_plan.hpp: the measurements behind it)
+        // (photon-mapped frames keep the short chunks: their paths differ far more in cost - a search per diffuse hit - and the
+        // balance is worth more than the units' fixed cost: C5 at 64 spp 770 ms with 64 units of 4 samples, 791 with 16 of 16)
+        const ChunkPlan cp = photon ? planChunks(prm.spp, unitsWanted(g.total_lanes, 128, prm.pass_pixels, opt.chunks))
+                                    : planChunksMega(prm.spp, g.total_lanes, prm.pass_pixels, opt.chunks);
+        prm.chunk_shift = cp.shift;
+        prm.chunk = cp.chunk;
+        const uint64_t tiles = (uint64_t)prm.tiles_x * ((prm.row_end - prm.row_base + 7) / 8);
+        prm.work_items = (tiles * 64ull) << cp.shift;
+        // never launch more lanes than there is work
+        const uint32_t grid = (uint32_t)std::min<uint64_t>(g.grid, (prm.work_items + g.block - 1) / g.block);
+        HIP_TRY(ctx, hipMemsetAsync(ctx->work_counter.p, 0, sizeof(unsigned long long), stream));
+        if (pm_wave)
+            hipLaunchKernelGGL(kernelAs<PmKernelT>(kernel), dim3(grid), dim3(g.block), g.lds_bytes, stream, launch_scene, prm, pmx);
+        else if (flat_karg)
+            hipLaunchKernelGGL(kernelAs<FlatKernelT>(kernel), dim3(grid), dim3(g.block), g.lds_bytes, stream, launch_scene, prm, pre);
+        else
+            hipLaunchKernelGGL(kernelAs<RenderKernelT>(kernel), dim3(grid), dim3(g.block), g.lds_bytes, stream, launch_scene, prm);
+        hipLaunchKernelGGL(sampleResolveKernel, dim3((uint32_t)((prm.pass_pixels + 255) / 256)), dim3(256), 0, stream, prm.samples,
+                           prm.pass_pixels, prm.spp, d_out + (size_t)prm.row_base * cam->width * 3);
+        ctx->launches += 2;
+    }
+    return endFrame(ctx, stream);
 }
 
 
@@ -1047,8 +930,8 @@ int launchRenderImpl(mcrt_ctx* ctx, const mcrt_camera_desc* cam, uint32_t global
 // 1080p @ 1024 spp frame (51 GB in one pass on a 288 GB MI355X) goes through in more passes on a smaller or shared device instead of
 // failing with out-of-memory; if the allocation still fails (fragmentation, another process grew meanwhile) the store is halved
 // until it fits or one 8-row pass does not. Returns the plan through `pp`.
-int planSampleStore(mcrt_ctx* ctx, uint32_t width, uint32_t owned_rows, uint32_t spp, PassPlan& pp) {
-    double gb = sampleStoreGb(ctxOpt(ctx, "MCRT_SAMPLE_STORE_GB"));
+int planSampleStore(mcrt_ctx* ctx, double store_gb, uint32_t width, uint32_t owned_rows, uint32_t spp, PassPlan& pp) {
+    double gb = store_gb;
     size_t free_b = 0, total_b = 0;
     if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) gb = std::min(gb, 0.4 * (double)(free_b + ctx->samples.bytes) / 1e9);
     else (void)hipGetLastError();
@@ -1266,8 +1149,10 @@ int mcrt_upload_scene(mcrt_ctx* ctx, const mcrt_scene_desc* s) {
     if (int rc = uploadArray(ctx, ctx->surf_material, s->surf_material, ns)) return rc;
     if (int rc = uploadArray(ctx, ctx->surf_kind, s->surf_kind, ns)) return rc;
     if (int rc = uploadArray(ctx, ctx->materials, s->materials, (size_t)s->num_materials)) return rc;
-    ctx->material_flags_or = 0u;
-    for (uint32_t i = 0; i < s->num_materials; i++) ctx->material_flags_or |= s->materials[i].flags;
+    SceneFacts& facts = ctx->facts;
+    facts = SceneFacts{};
+    facts.material_flags = 0u;
+    for (uint32_t i = 0; i < s->num_materials; i++) facts.material_flags |= s->materials[i].flags;
     if (int rc = uploadArray(ctx, ctx->light_surface, s->light_surface, (size_t)s->num_lights)) return rc;
     if (int rc = uploadArray(ctx, ctx->light_cdf, s->light_cdf, (size_t)s->num_lights)) return rc;
 
@@ -1303,7 +1188,7 @@ int mcrt_upload_scene(mcrt_ctx* ctx, const mcrt_scene_desc* s) {
     }
     d.q_root_a = L.q_root_a;
     d.q_root_m = L.q_root_m;
-    ctx->q_single = L.q_single;
+    facts.q_single = L.q_single;
     d.prim = ctx->prim.as<double>();
     d.flat_prim = ctx->flat_prim.as<double>();
     d.flat_index = ctx->flat_index.as<uint32_t>();
@@ -1350,6 +1235,20 @@ int mcrt_upload_scene(mcrt_ctx* ctx, const mcrt_scene_desc* s) {
     const char* fm = ctxOpt(ctx, "MCRT_FLAT_MAX");
     const uint32_t flat_max = fm ? (uint32_t)strtoul(fm, nullptr, 0) : 64u;
     d.flat = (d.stage_all && d.num_surfaces <= flat_max && !L.flat_prim.empty() && L.num_quadric_surfaces == 0) ? 1u : 0u;  // the flat loop knows triangles and spheres
+    facts.flat = d.flat != 0;
+    facts.cull = d.flat_pre != nullptr;
+    // (the cull records travel as a kernel argument only when the host copy is what the device's counts say)
+    facts.cull_floats = L.flat_pre.size() == (size_t)d.pre_tri_pairs * kTriPairFloats + (size_t)d.pre_sph_pairs * kSphPairFloats ? (uint32_t)L.flat_pre.size() : 0u;
+    facts.stage_all = d.stage_all != 0;
+    facts.num_nodes = d.num_nodes;
+    facts.q_nodes = d.q_nodes;
+    DeviceScene pm = d;  // as the photon-mapping kernel stages it (launchRenderImpl)
+    if (!pm.stage_all) pm.stage_nodes = std::min<uint32_t>(pm.stage_nodes, 128u);
+    for (uint32_t i = 0; i < 8; i++) {
+        facts.pm_lds[0][i] = alignUp(planLds(pm, kBlock, true, 2 * (i + 1), kPmLdsIors).total, 16);
+        facts.pm_lds[1][i] = alignUp(planLds(pm, 1024u, true, 2 * (i + 1), kPmLdsIors).total, 16);
+    }
+    facts.pm_lds_full = alignUp(planLds(pm, kBlock, true, kLdsStackDepth, kMaxIors).total, 16);
     ctx->has_scene = true;
     return MCRT_OK;
 }
@@ -1456,55 +1355,31 @@ int mcrt_render_finish(mcrt_ctx* ctx, mcrt_stats* stats) {
     // are made for the k it searches with)
     const bool pm_wave_frame = ctx->kernel_id == MCRT_KERNEL_PM_WAVE || ctx->kernel_id == MCRT_KERNEL_WAVEFRONT_PM;
     if (pm_wave_frame && !ctx->force_pm_lane && ctxOptOn(ctx, "MCRT_TEST_KNN_OVERFLOW")) h[5] |= kKnnOverflowFlag;
-    if (h[5] >= kKnnOverflowFlag) {
-        // The reference's frontier is an unbounded priority queue (linear-octree.cpp:33). A wave-cooperative search keeps 128 entries
-        // in registers and 1 024 in a list in memory; a frame in which one of them ran out is rendered AGAIN by the per-lane kernel (the
-        // reference's two queues per lane, in memory), whose own frontier - 160 entries per lane to begin with - grows eightfold per
-        // attempt, up to kMaxVisitLimit. Slower, and correct (round 6; until then: MCRT_ERR_UNSUPPORTED, and the per-lane search DROPPED
-        // the entry without a word).
-        const bool lane_frame = ctx->kernel_id == MCRT_KERNEL_PM_LANE;
-        const bool splats = filmSplats(ctx->last_cam.film_filter, ctx->last_cam.film_radius);  // (only the pipeline splats: no second kernel for such a frame)
-        if (!splats && ((pm_wave_frame && !ctx->force_pm_lane) || (lane_frame && ctx->knn_visit_cap < kMaxVisitLimit))) {
-            if (lane_frame) ctx->knn_visit_cap = std::min<uint32_t>(ctx->knn_visit_cap * 8u, kMaxVisitLimit);
-            else ctx->knn_visit_cap = std::max<uint32_t>(ctx->knn_visit_cap, 2048u);
-            const bool keep = ctx->force_pm_lane;
-            ctx->force_pm_lane = true;
-            const int rc = launchRender(ctx, &ctx->last_cam, ctx->last_seed, ctx->last_integrator, ctx->last_out, ctx->last_stream, ctx->last_film);
-            if (rc != MCRT_OK) {
-                ctx->force_pm_lane = keep;
-                return rc;
-            }
-            const int rc2 = mcrt_render_finish(ctx, stats);
-            ctx->force_pm_lane = keep;
-            return rc2;
-        }
-        return fail(ctx, MCRT_ERR_UNSUPPORTED, "kNN frontier overflow: a search had more than " + std::to_string(kMaxVisitLimit) + " octants pending at once in the per-lane "
-                                               "kernel's frontier (the reference's queue is unbounded, linear-octree.cpp:33)");
-    }
-    if (h[5])
-        return fail(ctx, MCRT_ERR_UNSUPPORTED, "traversal stack overflow (internal error: the stacks are sized to the tree's own bound, HostLayout::stack_bound)");
-    if (h[7]) {
-        // RefractionHistory (ray.cpp:74-98) is an unbounded vector. The megakernels keep kMaxIors (8) entries per lane, the pipeline
-        // ctx->iors_depth per slot (32 to begin with). A frame that nested deeper is rendered AGAIN: a megakernel frame through the
-        // pipeline, a pipeline frame with four times the rows (round 6; until then the frame failed beyond 32) - slower, and correct.
-        // The rows a scene needed stay with the context. (No scene of the reference nests deeper than 4.)
-        const bool was_pipeline = ctx->kernel_id == MCRT_KERNEL_WAVEFRONT || ctx->kernel_id == MCRT_KERNEL_WAVEFRONT_PM;
-        const bool photon = ctx->last_integrator == MCRT_INTEGRATOR_PHOTON_MAPPER;
-        const bool can_pipeline = ctx->scene.q_nodes > 0 && (!photon || ctx->k_nearest <= waveMaxK(kWaveRowsLarge));
-        constexpr uint32_t kIorsDepthLimit = 1u << 15;  // (32 768 nested media - a slot keeps the history's size in 16 bits; beyond it something other than a scene is going on)
-        if (can_pipeline && ((!was_pipeline && !ctx->force_wf) || (was_pipeline && ctx->iors_depth < kIorsDepthLimit))) {
-            if (was_pipeline) ctx->iors_depth *= 4u;
-            const bool keep = ctx->force_wf;
-            ctx->force_wf = true;
-            const int rc = launchRender(ctx, &ctx->last_cam, ctx->last_seed, ctx->last_integrator, ctx->last_out, ctx->last_stream, ctx->last_film);
-            ctx->force_wf = keep;
-            if (rc != MCRT_OK) return rc;
-            return mcrt_render_finish(ctx, stats);
-        }
-        return fail(ctx, MCRT_ERR_UNSUPPORTED, "a path entered more nested dielectric media than this frame can keep (RefractionHistory, ray.cpp:74-98: 8 per lane in the "
-                                               "megakernels of scenes the pipeline cannot take; 32 768 per slot in the pipeline)");
-    }
-    return MCRT_OK;
+    // Done, refused, or rendered again with a flag raised or a capacity grown: nextRender (mcrt_select.hpp) decides. The flags hold
+    // until this frame is delivered or refused; the capacities a scene needed stay with the context.
+    RetryState state;
+    state.force_wf = ctx->force_wf;
+    state.force_pm_lane = ctx->force_pm_lane;
+    state.knn_visit_cap = ctx->knn_visit_cap;
+    state.iors_depth = ctx->iors_depth;
+    FrameOutcome frame;
+    frame.kernel_id = ctx->kernel_id;
+    frame.overflow = h[5];
+    frame.iors_overflow = h[7] != 0;
+    frame.splats = filmSplats(ctx->last_cam.film_filter, ctx->last_cam.film_radius);
+    frame.can_pipeline = ctx->scene.q_nodes > 0 && (ctx->last_integrator != MCRT_INTEGRATOR_PHOTON_MAPPER || ctx->k_nearest <= waveMaxK(kWaveRowsLarge));
+    const RetryStep step = nextRender(state, frame);
+    if (step.action == kRetryDone) return MCRT_OK;
+    if (step.action == kRetryError) return fail(ctx, step.err, step.message);
+    ctx->knn_visit_cap = step.next.knn_visit_cap;
+    ctx->iors_depth = step.next.iors_depth;
+    ctx->force_wf = step.next.force_wf;
+    ctx->force_pm_lane = step.next.force_pm_lane;
+    int rc = launchRender(ctx, &ctx->last_cam, ctx->last_seed, ctx->last_integrator, ctx->last_out, ctx->last_stream, ctx->last_film);
+    if (rc == MCRT_OK) rc = mcrt_render_finish(ctx, stats);
+    ctx->force_wf = state.force_wf;
+    ctx->force_pm_lane = state.force_pm_lane;
+    return rc;
 }
 
 int mcrt_render(mcrt_ctx* ctx, const mcrt_camera_desc* cam, uint32_t global_seed, int integrator, double* out_rgb,
@@ -1577,8 +1452,9 @@ int emitOnDevice(mcrt_ctx* ctx, double emissions, double caustic_factor, uint32_
     if (int rc = uploadArray(ctx, ctx->emit_flux, pflux.data(), pflux.size())) return rc;
     if (!ctx->emit_counters.p) HIP_TRY(ctx, ctx->emit_counters.alloc(8 * sizeof(unsigned long long)));
 
-    ctx->lean_used = false;
-    auto kernel = leanOf(ctx, ctx->scene.stage_all ? emitKernel<true> : emitKernel<false>);
+    ctx->lean_used = leanScene(ctx->facts, parseRenderOptions(ctx->options));
+    auto kernel = kernelAs<void (*)(const DeviceScene, const EmitParams)>(instanceAddress(ctx->scene.stage_all ? kInstEmit_All : kInstEmit, ctx->lean_used));
+    if (!kernel) return fail(ctx, MCRT_ERR_INVALID, "internal error: no such lean kernel instance");
     DeviceScene scene = ctx->scene;
     scene.flat = 0;  // the emission kernel walks the BVH
     LaunchGeom g;
@@ -1814,10 +1690,11 @@ int mcrt_intersect(mcrt_ctx* ctx, uint64_t n, const double* start, const double*
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     if (!ctx->scene.stage_all && ctx->scene.num_nodes > 0 && n <= 0xFFF00000ull) {  // (32-bit queue cursors with room for the waves' overshoot)
         // tree in HBM: the trace kernel of the wavefront pipeline, fed from the arrays
-        const int lean = ctxOptL(ctx, "MCRT_WF_LEAN", 1) != 0 ? (ctx->q_single && ctxOptL(ctx, "MCRT_WF_LEAN", 1) != 2 ? 3 : 1) : 0;  // as launchWavefront
+        const RenderOptions opt = parseRenderOptions(ctx->options);
+        const int lean = traceVisit(opt, ctx->facts.q_single, false);
         auto trace = lean == 3 ? wfTraceKernel<ArrayRays, false, 3> : lean == 1 ? wfTraceKernel<ArrayRays, false, 1> : wfTraceKernel<ArrayRays, false>;
         TracePlan tp;
-        if (int rc = planTrace(ctx, trace, n, tp)) return rc;
+        if (int rc = planTrace(ctx, trace, n, opt.wf_leaf, tp)) return rc;
         DevBuf &ds = ctx->op_buf[0], &dd = ctx->op_buf[1], &dt = ctx->op_buf[2], &dsf = ctx->op_buf[3], &duv = ctx->op_buf[4];
         if (int rc = uploadInto(ctx, ds, start, n * 3)) return rc;
         if (int rc = uploadInto(ctx, dd, direction, n * 3)) return rc;
@@ -1968,9 +1845,8 @@ int mcrt_knn(mcrt_ctx* ctx, int which, uint64_t n, const double* p, uint32_t k, 
         HIP_TRY(ctx, flags.reserve(8));
         HIP_TRY(ctx, hipMemsetAsync(flags.p, 0, 8, ctx->stream));
         const PhotonMapViewW mv = waveMapView(ctx, which);
-        HIP_TRY(ctx, ctx->knn_spill.reserve((size_t)ctx->num_cus * std::max(1, (int)ctxOptL(ctx, "MCRT_KNN_BLOCKS", 8)) * 4 * kWaveSpill * 12));
-        // MCRT_KNN_BLOCKS: 256-lane workgroups per CU (occupancy experiments); MCRT_KNN_TIME=1: kernel time on stderr
-        const int per_cu = std::max(1, (int)ctxOptL(ctx, "MCRT_KNN_BLOCKS", 8));
+        const int per_cu = 8;  // 256-lane workgroups per CU; MCRT_KNN_TIME=1: kernel time on stderr
+        HIP_TRY(ctx, ctx->knn_spill.reserve((size_t)ctx->num_cus * per_cu * 4 * kWaveSpill * 12));
         const uint32_t grid = (uint32_t)std::min<uint64_t>((uint64_t)ctx->num_cus * per_cu, (n + 3) / 4);
         // MCRT_KNN_GROUPS=1: four queries per wave, one per row of 16 lanes (mcrt_groupknn.hpp)
         const bool groups = k <= kGrpMaxK && ctxOptOn(ctx, "MCRT_KNN_GROUPS");

@@ -47,9 +47,7 @@ extern "C" const void* mcrt_lean_kernel(int id) {
     constexpr int PT = MCRT_INTEGRATOR_PATH_TRACER;
     switch (id) {
         case MCRT_LEAN_FLATK_512: return reinterpret_cast<const void*>(renderKernelFlatK<>);
-        case MCRT_LEAN_FLATK_768: return reinterpret_cast<const void*>(renderKernelFlatK<768>);
         case MCRT_LEAN_FLAT_512: return reinterpret_cast<const void*>(renderKernel<PT, false, true, false, 1>);
-        case MCRT_LEAN_FLAT_768: return reinterpret_cast<const void*>(renderKernel<PT, false, true, false, 2>);
         case MCRT_LEAN_PM_1024_ALL: return reinterpret_cast<const void*>(renderKernelPM<false, true, 1024>);
         case MCRT_LEAN_PM_512_ALL: return reinterpret_cast<const void*>(renderKernelPM<false, true>);
         case MCRT_LEAN_SM: return reinterpret_cast<const void*>(renderKernelSM<false, false>);

@@ -451,7 +451,7 @@ struct FlatPreArg {
     float v[kFlatPreArgFloats];
 };
 static_assert(sizeof(DeviceScene) + sizeof(RenderParams) + sizeof(FlatPreArg) + 64 <= 4096, "the argument block of renderKernelFlatK");
-template <int kLanes = (int)kBlock>  // 512, 768 (3 waves per SIMD, 168 VGPRs) or 1024 (4 waves, 128 VGPRs): MCRT_FLAT_BLOCK
+template <int kLanes = (int)kBlock>  // 512 or 768 (3 waves per SIMD, 168 VGPRs): selectKernel, mcrt_select.hpp
 __global__ void __launch_bounds__(kLanes) renderKernelFlatK(const DeviceScene scene, const RenderParams prm, const FlatPreArg pre) {
     renderKernelBody<MCRT_INTEGRATOR_PATH_TRACER, false, true, false, kLanes == 1024 ? 3 : kLanes == 768 ? 2 : 1, true>(scene, prm, pre.v);
 }
@@ -754,7 +754,7 @@ struct WfTraceArgs {
     SmStackEntry* spill;
     uint32_t total_lanes;
     int refill_lanes, leaf_lanes, min_inner, lds_stack;
-    int leaf_items;                     // shared leaf step: offered primitives from which a step is issued (MCRT_WF_LEAF_ITEMS)
+    int leaf_items;                     // shared leaf step: offered primitives from which a step is issued
     uint32_t max_stack;                 // stack entries per lane in all (DeviceScene::stack_depth)
     uint32_t deal_shift;                // queue entries are dealt to the workgroups in blocks of 2^deal_shift
 };

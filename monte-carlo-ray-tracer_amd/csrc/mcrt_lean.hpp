@@ -6,9 +6,7 @@
 // The instances mcrt_hip_lean.hip holds; mcrt_lean_kernel(id) returns the address hipLaunchKernel takes (the host stub), or null.
 enum McrtLeanKernelId {
     MCRT_LEAN_FLATK_512 = 0,   // renderKernelFlatK<512>
-    MCRT_LEAN_FLATK_768,       // renderKernelFlatK<768>
     MCRT_LEAN_FLAT_512,        // renderKernel<path tracer, false, true, false, 1>  (flat scene whose cull records do not fit the argument block)
-    MCRT_LEAN_FLAT_768,        // renderKernel<path tracer, false, true, false, 2>
     MCRT_LEAN_PM_1024_ALL,     // renderKernelPM<false, true, 1024>
     MCRT_LEAN_PM_512_ALL,      // renderKernelPM<false, true>
     MCRT_LEAN_SM,              // renderKernelSM<false, false>

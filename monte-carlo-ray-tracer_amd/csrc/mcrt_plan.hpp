@@ -47,8 +47,8 @@ inline ChunkPlan planChunks(uint32_t spp, uint64_t want, uint32_t min_chunk = kM
 // shard of 1 / 2 / 4 / 8 (what one rank renders) with 4 / 16 / 64 units per pixel: 446.9 / 227.1 / 116.4 / 61.5, 445.3 / 225.4 /
 // 113.2 / 57.2, - / 264.5 / 132.5 / 66.5. So: 128 units per lane for balance, but chunks of at least 16 samples; shorter chunks (down
 // to kMinChunk) only when that leaves a lane fewer than 4 units (small frames).
-inline ChunkPlan planChunksMega(uint32_t spp, uint64_t lanes, uint64_t pass_pixels, const char* chunks_override = nullptr) {
-    if (chunks_override) return planChunks(spp, strtoull(chunks_override, nullptr, 0));  // option MCRT_CHUNKS: units per pixel
+inline ChunkPlan planChunksMega(uint32_t spp, uint64_t lanes, uint64_t pass_pixels, long long chunks_override = -1) {
+    if (chunks_override >= 0) return planChunks(spp, (uint64_t)chunks_override);  // option MCRT_CHUNKS: units per pixel
     const uint64_t pixels = std::max<uint64_t>(pass_pixels, 1);
     ChunkPlan c = planChunks(spp, (128 * lanes + pixels - 1) / pixels, 16);
     if ((pixels << c.shift) < 4 * lanes) c = planChunks(spp, (4 * lanes + pixels - 1) / pixels);
@@ -56,9 +56,9 @@ inline ChunkPlan planChunksMega(uint32_t spp, uint64_t lanes, uint64_t pass_pixe
 }
 
 // Units per pixel that give each of `consumers` (resident lanes, pool slots) `per_consumer` units; the option MCRT_CHUNKS
-// (`chunks_override`, its value or null) overrides.
-inline uint64_t unitsWanted(uint64_t consumers, uint64_t per_consumer, uint64_t pass_pixels, const char* chunks_override = nullptr) {
-    if (chunks_override) return strtoull(chunks_override, nullptr, 0);
+// (`chunks_override`, its value or -1) overrides.
+inline uint64_t unitsWanted(uint64_t consumers, uint64_t per_consumer, uint64_t pass_pixels, long long chunks_override = -1) {
+    if (chunks_override >= 0) return (uint64_t)chunks_override;
     return (per_consumer * consumers + pass_pixels - 1) / pass_pixels;
 }
 
@@ -69,13 +69,10 @@ inline uint64_t unitsWanted(uint64_t consumers, uint64_t per_consumer, uint64_t 
 // slot 64 / 32 / 16 / 8 / 4): spaceship 8 M paths 46 / 38 / 35 / 36 / 35, 33 M 85 / 78 / 77 / 85 / 90, 133 M 228 / 229 / 243 / 286 /
 // 288; C3 8 M 77 / 53 / 42 / 38 / 36, 33 M 141 / 119 / 111 / 113 / 116, 133 M 390 / 371 / 378 / 410 / 411 - i.e. 2-4 M slots until
 // the frame is large enough for more: paths / per_slot (48), at least floor_slots (2.5 M), never fewer than 4 samples per slot.
-// per_slot_alone: the option MCRT_WF_SLOT_PATHS was given - it alone decides (A/B runs).
-inline uint64_t planPoolSlots(uint64_t pass_paths, uint64_t max_slots, uint64_t block, uint64_t per_slot = 48, uint64_t floor_slots = 2500000,
-                              bool per_slot_alone = false) {
+inline uint64_t planPoolSlots(uint64_t pass_paths, uint64_t max_slots, uint64_t block, uint64_t per_slot = 48, uint64_t floor_slots = 2500000) {
     pass_paths = std::max<uint64_t>(pass_paths, 1);
-    per_slot = std::max<uint64_t>(per_slot, 1);
-    uint64_t want = std::max<uint64_t>(pass_paths / per_slot, per_slot_alone ? 1 : std::max<uint64_t>(floor_slots, 1));
-    if (!per_slot_alone) want = std::min<uint64_t>(want, std::max<uint64_t>(pass_paths / 4, 1));
+    uint64_t want = std::max<uint64_t>(pass_paths / std::max<uint64_t>(per_slot, 1), floor_slots);
+    want = std::min<uint64_t>(want, std::max<uint64_t>(pass_paths / 4, 1));
     const uint64_t slots = std::min<uint64_t>(max_slots, (want + block - 1) / block * block);
     return std::max<uint64_t>(slots, block);
 }

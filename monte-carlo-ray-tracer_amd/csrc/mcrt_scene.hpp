@@ -524,7 +524,7 @@ MCRT_HD Hit sceneIntersect(const SceneViewT<kAll>& sv, const Ray& ray, const Lan
         if (kFlat || (kAll && sv.flat_prim)) {
             const uint32_t nt = sv.flat_tris, ns = sv.num_surfaces;
             // kFlat instances only carry the culled form; without cull
-            // records (MCRT_FLAT_CULL=0) every primitive is a survivor
+            // records every primitive is a survivor
             if (kFlat || sv.pre_tri_pairs + sv.pre_sph_pairs != 0u) {
                 // FP32 cull over all primitives (wave-uniform, packed), then the FP64 tests of each lane's survivors
                 const CullRay cr = cullRay(sv, ray.start, ray.direction);

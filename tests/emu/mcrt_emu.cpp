@@ -22,6 +22,7 @@
 #include "../../monte-carlo-ray-tracer_amd/csrc/mcrt_output.hpp"
 #include "../../monte-carlo-ray-tracer_amd/csrc/mcrt_plan.hpp"
 #include "../../monte-carlo-ray-tracer_amd/csrc/mcrt_qbvh.hpp"
+#include "../../monte-carlo-ray-tracer_amd/csrc/mcrt_select.hpp"
 #include "../../monte-carlo-ray-tracer_amd/csrc/mcrt_wavefront.hpp"
 
 using namespace mcrt;
@@ -1211,6 +1212,79 @@ void emu_plan_mega(uint32_t spp, uint64_t lanes, uint64_t pass_pixels, uint64_t*
     const ChunkPlan cp = planChunksMega(spp, lanes, pass_pixels);
     out[0] = cp.shift;
     out[1] = cp.chunk;
+}
+
+// selectKernel (mcrt_select.hpp). scene = {flat, cull, cull_floats, stage_all, num_nodes, q_nodes, q_single, material_flags, pm_lds_full,
+// pm_lds[0][0..7], pm_lds[1][0..7]}; frame = {photon, paths, filtered, film_out, k_nearest, max_lds, force_wf, force_pm_lane}; the options as the MCRT_* names and
+// their values (parseRenderOptions); out = {form, instance, knn_instance, lean, knn_lean, block, stack_depth, trace_visit, trace_instance}.
+// Returns the refusal's code, its text in msg.
+int emu_select_kernel(const uint64_t* scene, const uint64_t* frame, int n_options, const char* const* keys, const char* const* values, uint64_t* out,
+                      char* msg, int msg_cap) {
+    SceneFacts s;
+    s.flat = scene[0] != 0;
+    s.cull = scene[1] != 0;
+    s.cull_floats = (uint32_t)scene[2];
+    s.stage_all = scene[3] != 0;
+    s.num_nodes = (uint32_t)scene[4];
+    s.q_nodes = (uint32_t)scene[5];
+    s.q_single = scene[6] != 0;
+    s.material_flags = (uint32_t)scene[7];
+    s.pm_lds_full = (uint32_t)scene[8];
+    for (int i = 0; i < 16; i++) s.pm_lds[i / 8][i % 8] = (uint32_t)scene[9 + i];
+    FrameFacts f;
+    f.photon = frame[0] != 0;
+    f.paths = frame[1];
+    f.filtered = frame[2] != 0;
+    f.film_out = frame[3] != 0;
+    f.k_nearest = (uint32_t)frame[4];
+    f.max_lds = (uint32_t)frame[5];
+    f.force_wf = frame[6] != 0;
+    f.force_pm_lane = frame[7] != 0;
+    std::map<std::string, std::string> options;
+    for (int i = 0; i < n_options; i++) options[keys[i]] = values[i];
+    const KernelChoice c = selectKernel(s, f, parseRenderOptions(options));
+    const uint64_t o[9] = {c.form, (uint64_t)(int64_t)c.instance, (uint64_t)(int64_t)c.knn_instance, c.lean, c.knn_lean, c.block, c.stack_depth,
+                           (uint64_t)c.trace_visit, (uint64_t)(int64_t)c.trace_instance};
+    std::copy(o, o + 9, out);
+    if (msg && msg_cap > 0) snprintf(msg, (size_t)msg_cap, "%s", c.message.c_str());
+    return c.err;
+}
+
+// nextRender (mcrt_select.hpp). state = {force_wf, force_pm_lane, knn_visit_cap, iors_depth}; outcome = {kernel_id, stats word 5, stats
+// word 7, splats, can_pipeline}; next = the state to render again with. Returns the action (0 done, 1 error, 2 again); err / msg: the error.
+int emu_next_render(const uint64_t* state, const uint64_t* outcome, uint64_t* next, int* err, char* msg, int msg_cap) {
+    RetryState st;
+    st.force_wf = state[0] != 0;
+    st.force_pm_lane = state[1] != 0;
+    st.knn_visit_cap = (uint32_t)state[2];
+    st.iors_depth = (uint32_t)state[3];
+    FrameOutcome r;
+    r.kernel_id = (uint32_t)outcome[0];
+    r.overflow = outcome[1];
+    r.iors_overflow = outcome[2] != 0;
+    r.splats = outcome[3] != 0;
+    r.can_pipeline = outcome[4] != 0;
+    const RetryStep step = nextRender(st, r);
+    next[0] = step.next.force_wf;
+    next[1] = step.next.force_pm_lane;
+    next[2] = step.next.knn_visit_cap;
+    next[3] = step.next.iors_depth;
+    *err = step.err;
+    if (msg && msg_cap > 0) snprintf(msg, (size_t)msg_cap, "%s", step.message.c_str());
+    return step.action;
+}
+
+// out = {kSelVisit, kSelVisitLimit, kSelIorsDeep, kSelIorsDepthLimit, kSelKnnOverflow, kInstCount}
+void emu_select_constants(uint64_t* out) {
+    const uint64_t o[6] = {kSelVisit, kSelVisitLimit, kSelIorsDeep, kSelIorsDepthLimit, kSelKnnOverflow, (uint64_t)kInstCount};
+    std::copy(o, o + 6, out);
+}
+
+// the RenderInstance ids the test names, in the order of its INSTANCES list
+void emu_instance_ids(int* out) {
+    const int o[] = {kInstFlat512, kInstFlatK512, kInstFlatK768, kInstSM, kInstSM_Count, kInstPT, kInstPT_Prof, kInstPMLane, kInstPM1024, kInstPM1024_All,
+                     kInstPMWide, kInstShadePT, kInstShadePM, kInstKnnEval, kInstKnnEvalWide, kInstTrace_Count, kInstTraceLean, kInstTraceLeanSingle};
+    std::copy(o, o + sizeof(o) / sizeof(o[0]), out);
 }
 
 }  // extern "C"
