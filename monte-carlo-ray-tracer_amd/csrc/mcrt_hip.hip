@@ -24,6 +24,7 @@
 #include "mcrt_internal.hpp"
 #include "mcrt_plan.hpp"
 #include "mcrt_select.hpp"
+#include "mcrt_launch.hpp"
 #include "mcrt_octree_shared.hpp"
 #include "mcrt_lean.hpp"
 
@@ -35,6 +36,8 @@ using namespace mcrt;
 
 namespace {
 #include "mcrt_kernels.hpp"
+#define MCRT_LAUNCH_KERNEL_ARGS  // the builders of the kernels' arguments, in this scope
+#include "mcrt_launch.hpp"
 
 // ------------------------------------------------------------------------------------------------
 // host side
@@ -183,10 +186,6 @@ int uploadInto(mcrt_ctx* ctx, DevBuf& buf, const T* host, size_t count) {  // li
     if (count) HIP_TRY(ctx, hipMemcpy(buf.p, host, count * sizeof(T), hipMemcpyHostToDevice));
     return MCRT_OK;
 }
-
-// Control words of the wavefront pipeline, one allocation of this size wherever it is made: {count[2], pop, -} per half of
-// the pool (words 0..3 and 4..7; the photon mapper uses 4..6 as {rcount[2], rpop}). mcrt_intersect uses words 0..3.
-constexpr size_t kWfCtrlWords = 8;
 
 // Operator-level entry points and the emission pass share the context's stats buffer, events and scratch with a render:
 // they are refused while one is in flight.
@@ -401,51 +400,24 @@ using ShadeKernelT = void (*)(const DeviceScene, const WfShadeArgs);
 using KnnKernelT = void (*)(const WfKnnArgs);
 using TraceKernelT = void (*)(WfTraceArgs, PoolRays);
 
-// The trace kernel's launch values that were once A/B switches, at what the measurements left them:
-constexpr uint32_t kTraceWaves = 16;       // waves per workgroup, one workgroup per CU
-constexpr int kTraceRefillLanes = 16;      // (32 while the queue cursor was one global atomic)
-constexpr int kTraceLeafItems = 1 << 20;
-constexpr int kTraceMinInner = 8;
-constexpr uint32_t kTraceDealShift = 6;
-static_assert(kTraceWaves * 64u <= kTraceMaxBlock, "the trace kernel's launch bounds");
-
+// Launch geometry of the trace kernel over a queue of at most max_items rays whose control words are ctx->wf_ctrl (planTraceLds,
+// fillTraceArgs: mcrt_launch.hpp)
 template <class K>
 int planTrace(mcrt_ctx* ctx, K kernel, uint64_t max_items, int leaf_lanes, TracePlan& tp) {
-    const uint32_t waves = kTraceWaves;
-    tp.block = waves * 64u;
-    const uint32_t lds_stack = kLdsStackDepth;
-    const uint32_t stack_bytes = lds_stack * tp.block * (uint32_t)sizeof(SmStackEntry);
-    const long lds_cap = (long)ctx->max_lds_trace;
-    if ((long)stack_bytes + 128 + (long)(waves * kShareMapBytes) > lds_cap) return fail(ctx, MCRT_ERR_INVALID, "trace kernel: traversal stacks exceed the LDS");
-    const uint32_t lds_blocks = (uint32_t)std::min<uint64_t>(ctx->scene.num_qblocks, ((uint64_t)lds_cap - stack_bytes - 128u - waves * kShareMapBytes) / 64u);
-    tp.lds_bytes = lds_blocks * 64u + stack_bytes + 64u + waves * kShareMapBytes + 64u;  // + the workgroup's queue cursor + the waves' shared-leaf maps + the root's record
+    tp.block = kTraceWaves * 64u;
+    uint32_t lds_blocks = 0;
+    if (!planTraceLds(kTraceWaves, kLdsStackDepth, ctx->max_lds_trace, ctx->scene.num_qblocks, lds_blocks))
+        return fail(ctx, MCRT_ERR_INVALID, "trace kernel: traversal stacks exceed the LDS");
+    tp.lds_bytes = traceLdsBytes(kTraceWaves, kLdsStackDepth, lds_blocks);
     LaunchGeom g;
     if (int rc = occupancyGrid(ctx, reinterpret_cast<const void*>(kernel), tp.block, tp.lds_bytes, g)) return rc;
     tp.grid = (uint32_t)std::min<uint64_t>(g.grid, (max_items + tp.block - 1) / tp.block);
     if (tp.grid < 1) tp.grid = 1;
     const uint32_t total_lanes = tp.grid * tp.block;
     if (!ctx->stats.p) HIP_TRY(ctx, ctx->stats.alloc(kStatsWords * sizeof(unsigned long long)));
-    // a region holds stack_depth entries per lane whatever part of them lives in LDS
     if (int rc = ensureSpill(ctx, (size_t)total_lanes * ctx->scene.stack_depth * sizeof(StackEntry))) return rc;
-    WfTraceArgs& ta = tp.args;
-    memset(&ta, 0, sizeof(ta));
-    ta.stats = ctx->stats.as<unsigned long long>();
-    ta.nodes = ctx->scene.nodes64;
-    ta.qblocks = ctx->scene.qblocks;
-    ta.num_nodes = ctx->scene.q_nodes;
-    ta.lds_blocks = lds_blocks;
-    ta.q_root_a = ctx->scene.q_root_a;
-    ta.q_root_m = ctx->scene.q_root_m;
-    ta.prim = ctx->scene.prim;
-    ta.spill = ctx->spill.as<SmStackEntry>();
-    ta.total_lanes = total_lanes;
-    ta.refill_lanes = kTraceRefillLanes;
-    ta.leaf_lanes = leaf_lanes;  // MCRT_WF_LEAF, default 16 (shared step, C3 64 spp: 8 / 12 / 16 / 20 pending lanes 412.7 / 402.1 / 398.1 / 402.3 ms; gating on 48-56 offered primitives instead: 398.4-399.0)
-    ta.leaf_items = kTraceLeafItems;
-    ta.min_inner = kTraceMinInner;
-    ta.lds_stack = (int)lds_stack;
-    ta.max_stack = ctx->scene.stack_depth;
-    ta.deal_shift = kTraceDealShift;
+    fillTraceArgs(tp.args, ctx->scene, ctx->wf_ctrl.as<unsigned long long>(), ctx->stats.as<unsigned long long>(), ctx->spill.as<SmStackEntry>(), total_lanes,
+                  lds_blocks, leaf_lanes);
     return MCRT_OK;
 }
 
@@ -468,161 +440,38 @@ int endFrame(mcrt_ctx* ctx, hipStream_t stream) {
     return MCRT_OK;
 }
 
-// The wavefront frame loop: shade(0), then trace(i), shade(i+1) until a shade launch queues no ray. The host
-// looks at the queue length every few iterations (a launch with nothing to do costs microseconds), so the
-// call returns when the frame is complete; mcrt_render_finish() then only collects the statistics.
-// film_out != NULL (mcrt_render_film_device): the splats of this shard's samples stay in the caller's full-frame RGBW buffer
-// and the resolve is left to mcrt_film_resolve_device, after the caller has summed the shards' buffers.
-int launchWavefront(mcrt_ctx* ctx, const mcrt_camera_desc* cam, uint32_t global_seed, double* d_out, hipStream_t stream,
-                    const RenderOptions& opt, const KernelChoice& choice, double* film_out = nullptr) {
+// One pass of the wavefront frame loop, the rows [fr.row_base, fr.row_end): shade(0), then trace(i), [knn(i),] shade(i+1) until a shade
+// launch queues nothing. The host looks at the queue length every few iterations (a launch with nothing to do costs microseconds).
+int runWavefrontPass(mcrt_ctx* ctx, const WfFrame& fr, uint64_t slots, hipStream_t stream, const RenderOptions& opt, const KernelChoice& choice) {
     const bool photon = choice.form == MCRT_KERNEL_WAVEFRONT_PM;
-    WfFrame fr;
-    memset(&fr, 0, sizeof(fr));
-    fr.cam = *cam;
-    fr.global_seed = global_seed;
-    fr.spp = cam->sqrtspp * cam->sqrtspp;
-    const uint32_t owned_rows = mcrt_shard_rows(cam, nullptr);
-    if (cam->width > 0xFFFFu || owned_rows > 0xFFFFu)  // kWfUnit keeps a slot's pixel as two 16-bit numbers
-        return fail(ctx, MCRT_ERR_INVALID, "camera: the wavefront integrator takes at most 65535 columns and 65535 rows per shard");
-    fr.tiles_x = (cam->width + 7) / 8;
-    fr.film.type = MCRT_FILM_BOX;
-    if (filmSplats(cam->film_filter, cam->film_radius)) {  // Film::Film(width, height, json), film.cpp:19-58
-        if (cam->film_filter > MCRT_FILM_LANCZOS) return fail(ctx, MCRT_ERR_INVALID, "camera: unknown film filter");
-        if (cam->shard_count > 1 && !film_out)
-            return fail(ctx, MCRT_ERR_UNSUPPORTED, "reconstruction filters splat across row groups: render them unsharded (shard_count <= 1) "
-                                                   "or with mcrt_render_film_device + mcrt_film_resolve_device");
-        FilmView& f = fr.film;
-        f.type = filmViewType(cam->film_filter);
-        f.width = cam->width;
-        f.height = cam->height;
-        f.radius = cam->film_radius > 0.0 ? cam->film_radius : filmDefaultRadius(cam->film_filter);
-        f.two_inv_radius = 2.0 / f.radius;
-        f.cache_size = cam->film_cache_size;
-        f.inv_dx = 0.0;
-        f.cache = nullptr;
-        if (f.cache_size) {
-            if (f.cache_size < 2) return fail(ctx, MCRT_ERR_INVALID, "camera: film_cache_size must be 0 or at least 2");
-            std::vector<double> table(f.cache_size);
-            for (uint32_t i = 0; i < f.cache_size; i++) table[i] = filmFilterFunction(f.type, (2.0 * (int)i) / (double)(f.cache_size - 1));
-            if (int rc = uploadArray(ctx, ctx->wf_film_cache, table.data(), table.size())) return rc;
-            f.cache = ctx->wf_film_cache.as<double>();
-            f.inv_dx = (double)(f.cache_size - 1) / f.radius;
-        }
-        const size_t blob_bytes = (size_t)cam->width * cam->height * 4 * sizeof(double);
-        if (!film_out && ctx->wf_film.bytes < blob_bytes) HIP_TRY(ctx, ctx->wf_film.alloc(blob_bytes));
-        f.blob = film_out ? film_out : ctx->wf_film.as<double>();
-        HIP_TRY(ctx, hipMemsetAsync(f.blob, 0, blob_bytes, stream));
-    }
-
-    if (int rc = beginFrame(ctx, stream, owned_rows == 0 ? (uint32_t)MCRT_KERNEL_NONE : choice.form)) return rc;
-    if (owned_rows == 0) return endFrame(ctx, stream);
-    ctx->lean_used = choice.lean || choice.knn_lean;
-
-    // Passes: as many rows as the per-sample store holds (box filter; splat frames keep no samples and are one pass).
-    const bool splats = fr.film.type != MCRT_FILM_BOX;
-    uint64_t pass_rows = owned_rows;
-    if (!splats) {
-        PassPlan pp;
-        if (int rc = planSampleStore(ctx, opt.sample_store_gb, cam->width, (uint32_t)owned_rows, fr.spp, pp)) return rc;
-        pass_rows = pp.pass_rows;
-        fr.samples = ctx->samples.as<double>();
-    }
-    // Pool size: up to 16 M slots (5.6 GB of pool, 4.6 GB of queue) — more slots = fewer, longer trace launches (their tails amortised; metal_bunnies
-    // 1447 / 1492 / 1507 Mray/s with 4 / 8 / 16 M) — but no more than the pass has work for (below); units per pixel: the power of two
-    // that gives a slot up to 16 work units of at least 4 samples.
-    const uint64_t pixels = (uint64_t)cam->width * std::min<uint64_t>(pass_rows, owned_rows);
-    // (round 4: 16 M by default - C3 at 1024 spp 2024 / 2068 / 2072 Mray/s with 8 / 16 / 32 M; 10 GB of pool and queue - but never more
-    // than an eighth of the memory that is free on this device)
-    uint64_t slots = opt.wf_slots;  // MCRT_WF_SLOTS
-    {
-        size_t free_b = 0, total_b = 0;
-        if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) {
-            const uint64_t per_slot = (uint64_t)kWfWords * 8u + 2u * (2u * sizeof(uint32_t) + 2u * 8u * sizeof(double));
-            const uint64_t have = (uint64_t)ctx->wf_slots * per_slot;  // what this context's pool and queue already hold
-            slots = std::min<uint64_t>(slots, std::max<uint64_t>(((uint64_t)free_b + have) / 8u / per_slot, (uint64_t)kWfBlock));
-        } else {
-            (void)hipGetLastError();
-        }
-    }
-    // ... and no more than the pass has work for: paths / 48, at least 2.5 M, never fewer than 4 samples per slot (planPoolSlots,
-    // mcrt_plan.hpp: the measurements)
-    // (photon-mapped frames: 16 path samples per slot - their iterations carry a kNN launch whose tails a larger pool amortises: C5 at
-    // full size 2 757 ms with 48, 2 725 with 24, 2 713 with 12, 2 874 with 96: profiles/r06_ab_c5_pipeline_pool.log)
-    slots = planPoolSlots(pixels * fr.spp, slots, kWfBlock, photon ? 16 : 48);
-    {
-        const ChunkPlan cp = planChunks(fr.spp, unitsWanted(slots, 16, pixels, opt.chunks));
-        fr.chunk_shift = cp.shift;
-        fr.chunk = cp.chunk;
-    }
-    if (ctx->wf_slots != slots) {
-        HIP_TRY(ctx, ctx->wf_pool.alloc((size_t)slots * kWfWords * 8));
-        // ray queue, two entries per slot (bounce + shadow ray): item and light words, and two sets of eight planes of doubles
-        // (WfRayQueue): a shade launch fills one set and reads the bounce rays of its slots back from the other
-        HIP_TRY(ctx, ctx->wf_queue.alloc(((size_t)slots + 2 * kWfBlock) * 2 * (2 * sizeof(uint32_t) + 2 * 8 * sizeof(double))));
-        ctx->wf_slots = (uint32_t)slots;
-    }
-    {   // deep refraction-history rows: [iors_depth - kMaxIors][slots] doubles (never initialised: an entry is written before it is read)
-        const size_t need = (size_t)(ctx->iors_depth - kMaxIors) * slots * sizeof(double);
-        if (ctx->wf_iors_deep.bytes < need) HIP_TRY(ctx, ctx->wf_iors_deep.alloc(need));
-        fr.iors_deep = ctx->wf_iors_deep.as<double>();
-        fr.iors_deep_rows = ctx->iors_depth - (uint32_t)kMaxIors;
-    }
-    if (!ctx->wf_ctrl.p) HIP_TRY(ctx, ctx->wf_ctrl.alloc(kWfCtrlWords * sizeof(unsigned long long)));
-    if (!ctx->wf_host) HIP_TRY(ctx, hipHostMalloc(reinterpret_cast<void**>(&ctx->wf_host), 2 * sizeof(unsigned long long)));
-    auto runPass = [&]() -> int {  // the rows [fr.row_base, fr.row_end): shade / trace launches until nothing is queued
+    unsigned long long* const pool = ctx->wf_pool.as<unsigned long long>();
+    unsigned long long* const ctrl = ctx->wf_ctrl.as<unsigned long long>();
+    unsigned long long* const stats = ctx->stats.as<unsigned long long>();
     HIP_TRY(ctx, hipMemsetAsync(ctx->work_counter.p, 0, sizeof(unsigned long long), stream));
-    HIP_TRY(ctx, hipMemsetAsync(ctx->wf_ctrl.p, 0, kWfCtrlWords * sizeof(unsigned long long), stream));
+    HIP_TRY(ctx, hipMemsetAsync(ctrl, 0, kWfCtrlWords * sizeof(unsigned long long), stream));
     // a fresh slot is all-zero flags (no path, no pixel); nothing else is used before it is written (kWfSeq is cleared too: the
     // sampler is rebuilt from it before the flags are looked at; tests/emu runs the same code on a pool of garbage)
-    HIP_TRY(ctx, hipMemsetAsync(ctx->wf_pool.as<unsigned long long>() + (size_t)kWfFlags * slots, 0, (size_t)slots * 8, stream));
-    HIP_TRY(ctx, hipMemsetAsync(ctx->wf_pool.as<unsigned long long>() + (size_t)kWfSeq * slots, 0, (size_t)slots * 8, stream));
+    HIP_TRY(ctx, hipMemsetAsync(pool + (size_t)kWfFlags * slots, 0, (size_t)slots * 8, stream));
+    HIP_TRY(ctx, hipMemsetAsync(pool + (size_t)kWfSeq * slots, 0, (size_t)slots * 8, stream));
 
     const auto trace = kernelAs<TraceKernelT>(instanceAddress(choice.trace_instance, false));
-    // + the materials and the light tables when they are small
-    uint32_t shade_tables = wfShadeTableBytes(ctx->scene.num_materials, ctx->scene.num_lights);
-    if (shade_tables > kWfShadeTableMax) shade_tables = 0;
-    const uint32_t shade_lds = kSobolTableWords * 4u + kMaxIors * kWfBlock * 8u + shade_tables;
     const auto shade = kernelAs<ShadeKernelT>(instanceAddress(choice.instance, choice.lean));
     const auto knn = photon ? kernelAs<KnnKernelT>(instanceAddress(choice.knn_instance, choice.knn_lean)) : nullptr;
     if (!shade || (photon && !knn)) return fail(ctx, MCRT_ERR_INVALID, "internal error: no such lean kernel instance");
     TracePlan tp;
     if (int rc = planTrace(ctx, trace, slots * 2, opt.wf_leaf, tp)) return rc;
-
-    // control words: {count[2] (one per iteration parity), pop} of the ray queue; 4..6 = {rcount[2], rpop} of the estimate requests
-    unsigned long long* ctrl = ctx->wf_ctrl.as<unsigned long long>();
-    WfTraceArgs ta = tp.args;
-    ta.pop = ctrl + 2;
-    PoolRays pr;
-    pr.pool.w = ctx->wf_pool.as<unsigned long long>();
-    pr.pool.n = (uint32_t)slots;
-    const size_t qcap = ((size_t)slots + 2 * kWfBlock) * 2;
-    double* const ray_set0 = reinterpret_cast<double*>(ctx->wf_queue.as<uint32_t>() + 2 * qcap);  // iteration parity 0; parity 1: + 8 * qcap
-    pr.q.item = ctx->wf_queue.as<uint32_t>();
-    pr.q.light = pr.q.item + qcap;
-    pr.q.ray = ray_set0;
-    pr.q.prev_ray = ray_set0 + 8 * qcap;
-    pr.q.cap = qcap;
+    WfTraceArgs& ta = tp.args;
+    PoolRays pr = bindQueue(pool, ctx->wf_queue.as<uint32_t>(), slots);
     WfShadeArgs sa;
-    memset(&sa, 0, sizeof(WfShadeArgs));
-    sa.pool = pr.pool;
-    sa.slot_base = 0u;
-    sa.slot_count = (uint32_t)slots;
-    sa.fr = fr;
-    sa.queue = pr.q;
-    sa.pop_reset = ctrl + 2;
-    sa.work = ctx->work_counter.as<unsigned long long>();
-    sa.stats = ctx->stats.as<unsigned long long>();
-    sa.lds_tables = shade_tables;
-    const uint32_t shade_grid = (sa.slot_count + kWfBlock - 1) / kWfBlock;
+    fillShadeArgs(sa, pr, fr, ctx->scene, ctrl, ctx->work_counter.as<unsigned long long>(), stats);
+    const uint32_t shade_grid = (sa.slot_count + kWfBlock - 1) / kWfBlock, shade_lds = wfShadeLdsBytes(sa);
 
-    // photon mapper: estimate requests and the kNN launch that serves them (control words 4..6 = {rcount[2], rpop})
     WfKnnArgs ka;
     memset(&ka, 0, sizeof(ka));
-    uint32_t knn_grid = 0;
-    bool knn_eval = false;
+    const uint32_t knn_grid = (uint32_t)ctx->num_cus * 8u;
     if (photon) {
         const uint32_t k = ctx->k_nearest;
-        knn_eval = opt.wf_pm_eval;  // (selectKernel: which kNN kernel)
+        const bool knn_eval = opt.wf_pm_eval;  // (selectKernel: which kNN kernel)
         if (ctx->wf_res_slots != slots || ctx->wf_res_k != k || (knn_eval ? !ctx->wf_stage.p : !ctx->wf_res_idx.p)) {
             HIP_TRY(ctx, ctx->wf_requests.alloc((size_t)slots * sizeof(uint32_t)));
             if (knn_eval) {
@@ -637,80 +486,113 @@ int launchWavefront(mcrt_ctx* ctx, const mcrt_camera_desc* cam, uint32_t global_
             ctx->wf_res_slots = (uint32_t)slots;
             ctx->wf_res_k = k;
         }
-        ka.pool = pr.pool;
-        ka.requests = ctx->wf_requests.as<uint32_t>();
-        ka.pop = ctrl + 6;
-        ka.stats = ctx->stats.as<unsigned long long>();
-        ka.maps[0] = waveMapView(ctx, 0);
-        ka.maps[1] = waveMapView(ctx, 1);
-        ka.k = k;
-        ka.res_n = ctx->wf_res_n.as<uint32_t>();
-        ka.res_r2 = ctx->wf_res_r2.as<double>();
-        ka.res_idx = ctx->wf_res_idx.as<uint32_t>();
-        ka.res_d2 = ctx->wf_res_d2.as<double>();
-        ka.stage = knn_eval ? ctx->wf_stage.as<double>() : nullptr;
-        ka.est = knn_eval ? ctx->wf_est.as<double>() : nullptr;
-        knn_grid = (uint32_t)ctx->num_cus * 8u;
-        HIP_TRY(ctx, ctx->knn_spill.reserve((size_t)knn_grid * 4 * kWaveSpill * 12));
-        ka.spill = ctx->knn_spill.as<uint32_t>();
-        WfShadeArgs& s0 = sa;
-        s0.requests = ctx->wf_requests.as<uint32_t>();
-        s0.rpop_reset = ctrl + 6;
-        s0.pm.photons[0] = ctx->maps[0].photons;
-        s0.pm.photons[1] = ctx->maps[1].photons;
-        s0.pm.res_n = ka.res_n;
-        s0.pm.res_r2 = ka.res_r2;
-        s0.pm.res_idx = ka.res_idx;
-        s0.pm.res_d2 = ka.res_d2;
-        s0.pm.k = k;
-        s0.pm.direct_visualization = ctx->direct_visualization != 0;
-        s0.pm.est = ka.est;
-        s0.stage = knn_eval ? ctx->wf_stage.as<double>() : nullptr;
+        HIP_TRY(ctx, ctx->knn_spill.reserve(wfKnnSpillBytes(knn_grid)));
+        fillKnnArgs(ka, sa, ctrl, waveMapView(ctx, 0), waveMapView(ctx, 1), k, ctx->direct_visualization, ctx->wf_requests.as<uint32_t>(),
+                    knn_eval ? ctx->wf_stage.as<double>() : nullptr, knn_eval ? ctx->wf_est.as<double>() : nullptr, ctx->knn_spill.as<uint32_t>(),
+                    ctx->wf_res_n.as<uint32_t>(), ctx->wf_res_r2.as<double>(), ctx->wf_res_idx.as<uint32_t>(), ctx->wf_res_d2.as<double>());
     }
 
-    // The host looks at the queue length every 16 iterations (a launch with nothing to do costs microseconds)
     const uint64_t check_every = 16;
     for (uint64_t it = 0;; it++) {
-        sa.count_out = ctrl + (it & 1);
-        sa.count_reset = ctrl + ((it + 1) & 1);
-        pr.q.ray = ray_set0 + (it & 1) * 8 * qcap;
-        pr.q.prev_ray = ray_set0 + ((it + 1) & 1) * 8 * qcap;
-        sa.queue = pr.q;
-        if (photon) {
-            sa.rcount_out = ctrl + 4 + (it & 1);
-            sa.rcount_reset = ctrl + 4 + ((it + 1) & 1);
-        }
+        bindIteration(it, ctrl, sa, ta, ka, pr);
         hipLaunchKernelGGL(shade, dim3(shade_grid), dim3(kWfBlock), shade_lds, stream, ctx->scene, sa);
         ctx->launches++;
         if (it % check_every == check_every - 1 || it < 2) {
             HIP_TRY(ctx, hipGetLastError());
-            HIP_TRY(ctx, hipMemcpyAsync(ctx->wf_host, ctrl + (it & 1), sizeof(unsigned long long), hipMemcpyDeviceToHost, stream));
+            HIP_TRY(ctx, hipMemcpyAsync(ctx->wf_host, sa.count_out, sizeof(unsigned long long), hipMemcpyDeviceToHost, stream));
             if (photon)  // requests count as work too
-                HIP_TRY(ctx, hipMemcpyAsync(ctx->wf_host + 1, ctrl + 4 + (it & 1), sizeof(unsigned long long), hipMemcpyDeviceToHost, stream));
+                HIP_TRY(ctx, hipMemcpyAsync(ctx->wf_host + 1, sa.rcount_out, sizeof(unsigned long long), hipMemcpyDeviceToHost, stream));
             HIP_TRY(ctx, hipStreamSynchronize(stream));
             if (opt.wf_log)  // MCRT_WF_LOG: queue length over the frame
                 fprintf(stderr, "[mcrt wf] iteration %llu queued %llu at %.2f ms\n", (unsigned long long)it, ctx->wf_host[0],
                         std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - ctx->t_begin).count());
             if (ctx->wf_host[0] == 0ull && (!photon || ctx->wf_host[1] == 0ull)) break;  // nothing queued: every slot is done
         }
-        ta.count = ctrl + (it & 1);
         hipLaunchKernelGGL(trace, dim3(tp.grid), dim3(tp.block), tp.lds_bytes, stream, ta, pr);
         ctx->launches++;
         if (photon) {
-            ka.count = ctrl + 4 + (it & 1);
             hipLaunchKernelGGL(knn, dim3(knn_grid), dim3(256), 0, stream, ka);
             ctx->launches++;
         }
     }
     HIP_TRY(ctx, hipGetLastError());
     return MCRT_OK;
-    };
+}
+
+// The wavefront frame: the film, the pool and the passes (runWavefrontPass), so the call returns when the frame is complete;
+// mcrt_render_finish() then only collects the statistics.
+// film_out != NULL (mcrt_render_film_device): the splats of this shard's samples stay in the caller's full-frame RGBW buffer
+// and the resolve is left to mcrt_film_resolve_device, after the caller has summed the shards' buffers.
+int launchWavefront(mcrt_ctx* ctx, const mcrt_camera_desc* cam, uint32_t global_seed, double* d_out, hipStream_t stream,
+                    const RenderOptions& opt, const KernelChoice& choice, double* film_out = nullptr) {
+    const bool photon = choice.form == MCRT_KERNEL_WAVEFRONT_PM, splats = filmSplats(cam->film_filter, cam->film_radius);
+    const uint32_t spp = cam->sqrtspp * cam->sqrtspp, owned_rows = mcrt_shard_rows(cam, nullptr);
+    if (cam->width > 0xFFFFu || owned_rows > 0xFFFFu)  // kWfUnit keeps a slot's pixel as two 16-bit numbers
+        return fail(ctx, MCRT_ERR_INVALID, "camera: the wavefront integrator takes at most 65535 columns and 65535 rows per shard");
+    FilmView film;
+    if (splats) {  // Film::Film(width, height, json), film.cpp:19-58
+        if (cam->film_filter > MCRT_FILM_LANCZOS) return fail(ctx, MCRT_ERR_INVALID, "camera: unknown film filter");
+        if (cam->shard_count > 1 && !film_out)
+            return fail(ctx, MCRT_ERR_UNSUPPORTED, "reconstruction filters splat across row groups: render them unsharded (shard_count <= 1) "
+                                                   "or with mcrt_render_film_device + mcrt_film_resolve_device");
+        if (cam->film_cache_size == 1) return fail(ctx, MCRT_ERR_INVALID, "camera: film_cache_size must be 0 or at least 2");
+        if (cam->film_cache_size) {
+            const std::vector<double> table = filmCacheTable(*cam);
+            if (int rc = uploadArray(ctx, ctx->wf_film_cache, table.data(), table.size())) return rc;
+        }
+        const size_t blob_bytes = (size_t)cam->width * cam->height * 4 * sizeof(double);
+        if (!film_out && ctx->wf_film.bytes < blob_bytes) HIP_TRY(ctx, ctx->wf_film.alloc(blob_bytes));
+        film = makeFilmView(*cam, ctx->wf_film_cache.as<double>(), film_out ? film_out : ctx->wf_film.as<double>());
+        HIP_TRY(ctx, hipMemsetAsync(film.blob, 0, blob_bytes, stream));
+    }
+
+    if (int rc = beginFrame(ctx, stream, owned_rows == 0 ? (uint32_t)MCRT_KERNEL_NONE : choice.form)) return rc;
+    if (owned_rows == 0) return endFrame(ctx, stream);
+    ctx->lean_used = choice.lean || choice.knn_lean;
+
+    // Passes: as many rows as the per-sample store holds (box filter; splat frames keep no samples and are one pass).
+    uint64_t pass_rows = owned_rows;
+    if (!splats) {
+        PassPlan pp;
+        if (int rc = planSampleStore(ctx, opt.sample_store_gb, cam->width, (uint32_t)owned_rows, spp, pp)) return rc;
+        pass_rows = pp.pass_rows;
+    }
+    // Pool size: up to 16 M slots (5.6 GB of pool, 4.6 GB of queue) — more slots = fewer, longer trace launches (their tails amortised; metal_bunnies
+    // 1447 / 1492 / 1507 Mray/s with 4 / 8 / 16 M) — but no more than the pass has work for (below); units per pixel: the power of two
+    // that gives a slot up to 16 work units of at least 4 samples.
+    const uint64_t pixels = (uint64_t)cam->width * std::min<uint64_t>(pass_rows, owned_rows);
+    // (round 4: 16 M by default - C3 at 1024 spp 2024 / 2068 / 2072 Mray/s with 8 / 16 / 32 M; 10 GB of pool and queue - but never more
+    // than an eighth of the memory that is free on this device)
+    uint64_t slots = opt.wf_slots;  // MCRT_WF_SLOTS
+    {
+        size_t free_b = 0, total_b = 0;
+        if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) {
+            const uint64_t have = (uint64_t)ctx->wf_slots * kWfSlotBytes;  // what this context's pool and queue already hold
+            slots = std::min<uint64_t>(slots, std::max<uint64_t>(((uint64_t)free_b + have) / 8u / kWfSlotBytes, (uint64_t)kWfBlock));
+        } else {
+            (void)hipGetLastError();
+        }
+    }
+    // ... and no more than the pass has work for: paths / 48, at least 2.5 M, never fewer than 4 samples per slot (planPoolSlots,
+    // mcrt_plan.hpp: the measurements)
+    // (photon-mapped frames: 16 path samples per slot - their iterations carry a kNN launch whose tails a larger pool amortises: C5 at
+    // full size 2 757 ms with 48, 2 725 with 24, 2 713 with 12, 2 874 with 96: profiles/r06_ab_c5_pipeline_pool.log)
+    slots = planPoolSlots(pixels * spp, slots, kWfBlock, photon ? 16 : 48);
+    if (ctx->wf_slots != slots) {
+        HIP_TRY(ctx, ctx->wf_pool.alloc(wfPoolBytes(slots)));
+        HIP_TRY(ctx, ctx->wf_queue.alloc(wfQueueBytes(slots)));
+        ctx->wf_slots = (uint32_t)slots;
+    }
+    const size_t iors_need = (size_t)(ctx->iors_depth - kMaxIors) * slots * sizeof(double);
+    if (ctx->wf_iors_deep.bytes < iors_need) HIP_TRY(ctx, ctx->wf_iors_deep.alloc(iors_need));
+    if (!ctx->wf_ctrl.p) HIP_TRY(ctx, ctx->wf_ctrl.alloc(kWfCtrlWords * sizeof(unsigned long long)));
+    if (!ctx->wf_host) HIP_TRY(ctx, hipHostMalloc(reinterpret_cast<void**>(&ctx->wf_host), 2 * sizeof(unsigned long long)));
+    WfFrame fr;
+    fillWfFrame(fr, *cam, global_seed, planChunks(spp, unitsWanted(slots, 16, pixels, opt.chunks)), splats ? nullptr : ctx->samples.as<double>(),
+                splats ? &film : nullptr, ctx->wf_iors_deep.as<double>(), ctx->iors_depth);
     for (uint32_t row = 0; row < owned_rows; row += (uint32_t)pass_rows) {
-        fr.row_base = row;
-        fr.row_end = (uint32_t)std::min<uint64_t>(owned_rows, row + pass_rows);
-        fr.pass_pixels = (unsigned long long)(fr.row_end - fr.row_base) * cam->width;
-        fr.work_items = ((unsigned long long)fr.tiles_x * ((fr.row_end - fr.row_base + 7) / 8) * 64ull) << fr.chunk_shift;
-        if (int rc = runPass()) return rc;
+        setWfPass(fr, row, (uint32_t)std::min<uint64_t>(owned_rows, row + pass_rows));
+        if (int rc = runWavefrontPass(ctx, fr, slots, stream, opt, choice)) return rc;
         if (!splats) {  // the pass's samples, added up in sample order
             hipLaunchKernelGGL(sampleResolveKernel, dim3((uint32_t)((fr.pass_pixels + 255) / 256)), dim3(256), 0, stream, fr.samples,
                                (uint64_t)fr.pass_pixels, fr.spp, d_out + (size_t)fr.row_base * cam->width * 3);
@@ -718,9 +600,9 @@ int launchWavefront(mcrt_ctx* ctx, const mcrt_camera_desc* cam, uint32_t global_
             ctx->launches++;
         }
     }
-    if (fr.film.type != MCRT_FILM_BOX && !film_out) {
-        const uint64_t pixels = (uint64_t)cam->width * cam->height;
-        hipLaunchKernelGGL(filmResolveKernel, dim3((uint32_t)((pixels + 255) / 256)), dim3(256), 0, stream, fr.film.blob, pixels, d_out);
+    if (splats && !film_out) {
+        const uint64_t all_pixels = (uint64_t)cam->width * cam->height;
+        hipLaunchKernelGGL(filmResolveKernel, dim3((uint32_t)((all_pixels + 255) / 256)), dim3(256), 0, stream, fr.film.blob, all_pixels, d_out);
         HIP_TRY(ctx, hipGetLastError());
         ctx->launches++;
     }
@@ -775,10 +657,8 @@ int launchRender(mcrt_ctx* ctx, const mcrt_camera_desc* cam, uint32_t global_see
     return rc;
 }
 
-// The state machine's scheduling thresholds (RenderParams::sm_*, mcrt_lanesm.hpp), at what the measurements left them
-constexpr int kSmShadeLanes = 40, kSmRegenLanes = 16, kSmMinTrav = 20, kSmLeafLanes = 32, kSmMinInner = 8;
-
-// validate -> selectKernel (mcrt_select.hpp) -> the instance's address -> launch geometry -> prologue -> one launch per pass
+// validate -> selectKernel (mcrt_select.hpp) -> the instance's address -> launch geometry and arguments (mcrt_launch.hpp) -> prologue ->
+// one launch per pass
 int launchRenderImpl(mcrt_ctx* ctx, const mcrt_camera_desc* cam, uint32_t global_seed, int integrator, double* d_out, hipStream_t stream,
                      double* film_out, const RenderOptions& opt) {
     if (!ctx->has_scene) return fail(ctx, MCRT_ERR_NO_SCENE, "mcrt_render before mcrt_upload_scene");
@@ -808,62 +688,15 @@ int launchRenderImpl(mcrt_ctx* ctx, const mcrt_camera_desc* cam, uint32_t global
 
     const void* kernel = instanceAddress(choice.instance, choice.lean);
     if (!kernel) return fail(ctx, MCRT_ERR_INVALID, "internal error: no such lean kernel instance");
-    const bool pm_wave = choice.form == MCRT_KERNEL_PM_WAVE, use_sm = choice.form == MCRT_KERNEL_LANE_SM;
-    const bool pm_wide = pm_wave && choice.instance >= kInstPMWide && choice.instance <= kInstPMWide_CountAll;
+    const bool pm_wave = choice.form == MCRT_KERNEL_PM_WAVE;
     const bool flat_karg = choice.instance == kInstFlatK512 || choice.instance == kInstFlatK768;
     DeviceScene launch_scene = ctx->scene;
-    uint32_t lds_bytes;
-    if (pm_wave) {
-        if (!launch_scene.stage_all) launch_scene.stage_nodes = std::min<uint32_t>(launch_scene.stage_nodes, 128u);
-        const uint32_t knn_bytes = waveKnnBytes(pm_wide ? kWaveRowsLarge : kWaveRows) + (launch_scene.stage_all ? 0u : kWaveStateBytes);
-        lds_bytes = alignUp(planLds(launch_scene, choice.block, true, choice.stack_depth, (choice.block != 1024u && !pm_wide) ? (uint32_t)kMaxIors : kPmLdsIors).total, 16) +
-                    (choice.block / 64) * knn_bytes;
-    } else if (use_sm) {
-        // the staged top of the tree shrinks to what the workgroup's stacks and refraction histories leave
-        const uint32_t fixed = planSmLds(DeviceScene{}, choice.block, choice.stack_depth).total;
-        if (!launch_scene.stage_all && fixed < ctx->max_lds)
-            launch_scene.stage_nodes = std::min<uint32_t>(launch_scene.stage_nodes, (ctx->max_lds - fixed) / 64u);
-        lds_bytes = planSmLds(launch_scene, choice.block, choice.stack_depth).total;
-    } else {
-        lds_bytes = planLds(launch_scene, choice.block, choice.form != MCRT_KERNEL_FLAT).total;  // (the flat loop has no stack in LDS)
-    }
+    const uint32_t lds_bytes = planMegaLds(launch_scene, choice, (uint32_t)ctx->max_lds);
     if (lds_bytes > ctx->max_lds) return fail(ctx, MCRT_ERR_INVALID, "LDS plan exceeds the device limit");
     LaunchGeom g;
     if (int rc = occupancyGrid(ctx, kernel, choice.block, lds_bytes, g)) return rc;
     if (int rc = ensureScratch(ctx, g.total_lanes, photon && !pm_wave)) return rc;
-    if (pm_wave && choice.stack_depth < (uint32_t)kLdsStackDepth)
-        if (int rc = ensureSpill(ctx, (size_t)g.total_lanes * (ctx->scene.stack_depth - choice.stack_depth) * sizeof(StackEntry))) return rc;
-
-    RenderParams prm;
-    memset(&prm, 0, sizeof(prm));
-    prm.cam = *cam;
-    prm.global_seed = global_seed;
-    prm.spp = cam->sqrtspp * cam->sqrtspp;
-    prm.owned_rows = owned_rows;
-    prm.tiles_x = (cam->width + 7) / 8;
-    prm.tiles_y = (prm.owned_rows + 7) / 8;
-    prm.work_items = (uint64_t)prm.tiles_x * prm.tiles_y * 64ull;
-    prm.work_counter = ctx->work_counter.as<unsigned long long>();
-    prm.stats = ctx->stats.as<unsigned long long>();
-    prm.spill = ctx->spill.as<StackEntry>();
-    prm.total_lanes = g.total_lanes;
-    prm.sm_shade_lanes = kSmShadeLanes;
-    prm.sm_regen_lanes = kSmRegenLanes;
-    prm.sm_min_trav = kSmMinTrav;
-    prm.sm_leaf_lanes = kSmLeafLanes;
-    prm.sm_min_inner = kSmMinInner;
-    prm.sm_lds_depth = kLdsStackDepth;
-    if (photon) {
-        prm.global_map = ctx->maps[0];
-        prm.caustic_map = ctx->maps[1];
-        prm.k_nearest = ctx->k_nearest;
-        prm.direct_visualization = (uint32_t)ctx->direct_visualization;
-        prm.knn_res_d2 = ctx->knn_res_d2.as<double>();
-        prm.knn_res_idx = ctx->knn_res_idx.as<uint32_t>();
-        prm.knn_visit_d2 = ctx->knn_visit_d2.as<double>();
-        prm.knn_visit_oct = ctx->knn_visit_oct.as<uint32_t>();
-        prm.knn_max_visit = ctx->knn_visit_alloc;
-    }
+    if (int rc = ensureSpill(ctx, megaSpillEntries(ctx->scene, choice, g.total_lanes) * sizeof(StackEntry))) return rc;
     if (int rc = beginFrame(ctx, stream, owned_rows == 0 ? (uint32_t)MCRT_KERNEL_NONE : choice.form)) return rc;
     if (owned_rows == 0) return endFrame(ctx, stream);
     ctx->lean_used = choice.lean;
@@ -871,43 +704,32 @@ int launchRenderImpl(mcrt_ctx* ctx, const mcrt_camera_desc* cam, uint32_t global
     // Sample-chunked work units (RenderParams): the frame goes through in passes of as many rows as the per-sample store holds
     // (MCRT_SAMPLE_STORE_GB, default 64: mcrt_plan.hpp), each pass = one integrator launch + the in-order resolve.
     PassPlan pp;
-    if (int rc = planSampleStore(ctx, opt.sample_store_gb, cam->width, prm.owned_rows, prm.spp, pp)) return rc;
-    const uint64_t pass_rows = pp.pass_rows;
-    prm.samples = ctx->samples.as<double>();
+    if (int rc = planSampleStore(ctx, opt.sample_store_gb, cam->width, owned_rows, cam->sqrtspp * cam->sqrtspp, pp)) return rc;
+    RenderParams prm;
+    fillRenderParams(prm, *cam, global_seed, owned_rows, ctx->work_counter.as<unsigned long long>(), ctx->stats.as<unsigned long long>(),
+                     ctx->spill.as<StackEntry>(), ctx->samples.as<double>(), g.total_lanes);
+    if (photon) {
+        setRenderMaps(prm, ctx->maps[0], ctx->maps[1], ctx->k_nearest, ctx->direct_visualization);
+        prm.knn_res_d2 = ctx->knn_res_d2.as<double>();  // the per-lane searches' scratch (ensureScratch)
+        prm.knn_res_idx = ctx->knn_res_idx.as<uint32_t>();
+        prm.knn_visit_d2 = ctx->knn_visit_d2.as<double>();
+        prm.knn_visit_oct = ctx->knn_visit_oct.as<uint32_t>();
+        prm.knn_max_visit = ctx->knn_visit_alloc;
+    }
     PmExtra pmx;
     if (pm_wave) {
-        pmx.global_map = waveMapView(ctx, 0);
-        pmx.caustic_map = waveMapView(ctx, 1);
-        pmx.stack_depth = choice.stack_depth;
-        pmx.iors_global = nullptr;
-        HIP_TRY(ctx, ctx->pm_stage.reserve((size_t)kStageDoubles * g.total_lanes * sizeof(double)));
-        pmx.stage = ctx->pm_stage.as<double>();
-        HIP_TRY(ctx, ctx->knn_spill.reserve((size_t)(g.total_lanes / 64) * kWaveSpill * 12));
-        pmx.knn_spill = ctx->knn_spill.as<uint32_t>();
-        if (g.block == 1024u || pm_wide) {  // (two refraction-history entries per lane in LDS, the deeper ones in memory)
-            HIP_TRY(ctx, ctx->pm_iors.reserve((size_t)kMaxIors * g.total_lanes * sizeof(double)));
-            pmx.iors_global = ctx->pm_iors.as<double>();
-        }
+        HIP_TRY(ctx, ctx->pm_stage.reserve(pmStageBytes(g.total_lanes)));
+        HIP_TRY(ctx, ctx->knn_spill.reserve(pmKnnSpillBytes(g.total_lanes)));
+        if (pmIorsInMemory(choice)) HIP_TRY(ctx, ctx->pm_iors.reserve(pmIorsBytes(g.total_lanes)));
+        fillPmExtra(pmx, waveMapView(ctx, 0), waveMapView(ctx, 1), choice, ctx->pm_stage.as<double>(), ctx->knn_spill.as<uint32_t>(), ctx->pm_iors.as<double>());
     }
     FlatPreArg pre;
     if (flat_karg) {  // the cull records travel in the kernel's argument block
         memset(&pre, 0, sizeof(pre));
         memcpy(pre.v, ctx->flat_pre_host.data(), ctx->flat_pre_host.size() * sizeof(float));
     }
-    for (uint32_t row = 0; row < prm.owned_rows; row += (uint32_t)pass_rows) {
-        prm.row_base = row;
-        prm.row_end = (uint32_t)std::min<uint64_t>(prm.owned_rows, row + pass_rows);
-        prm.pass_pixels = (uint64_t)(prm.row_end - prm.row_base) * cam->width;
-        // units per pixel: a power of two that gives every resident lane >= 128 units in chunks of at least 16 samples
-        // (planChunksMega, mcrt_plan.hpp: the measurements behind it)
-        // (photon-mapped frames keep the short chunks: their paths differ far more in cost - a search per diffuse hit - and the
-        // balance is worth more than the units' fixed cost: C5 at 64 spp 770 ms with 64 units of 4 samples, 791 with 16 of 16)
-        const ChunkPlan cp = photon ? planChunks(prm.spp, unitsWanted(g.total_lanes, 128, prm.pass_pixels, opt.chunks))
-                                    : planChunksMega(prm.spp, g.total_lanes, prm.pass_pixels, opt.chunks);
-        prm.chunk_shift = cp.shift;
-        prm.chunk = cp.chunk;
-        const uint64_t tiles = (uint64_t)prm.tiles_x * ((prm.row_end - prm.row_base + 7) / 8);
-        prm.work_items = (tiles * 64ull) << cp.shift;
+    for (uint32_t row = 0; row < owned_rows; row += pp.pass_rows) {
+        setRenderPass(prm, row, pp.pass_rows, photon, opt.chunks);
         // never launch more lanes than there is work
         const uint32_t grid = (uint32_t)std::min<uint64_t>(g.grid, (prm.work_items + g.block - 1) / g.block);
         HIP_TRY(ctx, hipMemsetAsync(ctx->work_counter.p, 0, sizeof(unsigned long long), stream));
@@ -1149,10 +971,6 @@ int mcrt_upload_scene(mcrt_ctx* ctx, const mcrt_scene_desc* s) {
     if (int rc = uploadArray(ctx, ctx->surf_material, s->surf_material, ns)) return rc;
     if (int rc = uploadArray(ctx, ctx->surf_kind, s->surf_kind, ns)) return rc;
     if (int rc = uploadArray(ctx, ctx->materials, s->materials, (size_t)s->num_materials)) return rc;
-    SceneFacts& facts = ctx->facts;
-    facts = SceneFacts{};
-    facts.material_flags = 0u;
-    for (uint32_t i = 0; i < s->num_materials; i++) facts.material_flags |= s->materials[i].flags;
     if (int rc = uploadArray(ctx, ctx->light_surface, s->light_surface, (size_t)s->num_lights)) return rc;
     if (int rc = uploadArray(ctx, ctx->light_cdf, s->light_cdf, (size_t)s->num_lights)) return rc;
 
@@ -1188,7 +1006,6 @@ int mcrt_upload_scene(mcrt_ctx* ctx, const mcrt_scene_desc* s) {
     }
     d.q_root_a = L.q_root_a;
     d.q_root_m = L.q_root_m;
-    facts.q_single = L.q_single;
     d.prim = ctx->prim.as<double>();
     d.flat_prim = ctx->flat_prim.as<double>();
     d.flat_index = ctx->flat_index.as<uint32_t>();
@@ -1211,44 +1028,10 @@ int mcrt_upload_scene(mcrt_ctx* ctx, const mcrt_scene_desc* s) {
     d.sobol_tab = ctx->sobol_tab.as<uint32_t>();
     d.scene_ior = s->scene_ior;
 
-    ctx->host_light_flux.assign((size_t)s->num_lights * 3, 0.0);
-    for (uint32_t i = 0; i < s->num_lights; i++) {
-        const uint32_t ls = s->light_surface[i];
-        for (int c = 0; c < 3; c++) ctx->host_light_flux[(size_t)i * 3 + c] = s->materials[s->surf_material[ls]].emittance[c] * s->surf_area[ls];
-    }
-
-    // Staging plan: whole scene when its LDS image is <= 48 KiB, else the top 512 nodes of the BVH.
-    d.stage_all = 1;
-    d.stage_nodes = 0;
-    const uint32_t fixed = planLds(DeviceScene{}, kBlock).total;
-    // (... and only when the plan of the 512-lane kernels - tables, stacks, histories AND the image - fits the device's LDS: an image of
-    // 40-48 KiB did not, and its mcrt_intersect / legacy frames failed with "LDS plan exceeds the device limit" until round 4)
-    if (planLds(d, kBlock).total - fixed > 48u * 1024u || planLds(d, kBlock).total > ctx->max_lds ||
-        L.num_quadric_surfaces) {  // quadric code lives in the kAll == false kernels
-        d.stage_all = 0;
-        d.stage_nodes = std::min<uint32_t>(d.num_nodes, 512u);
-    }
-    // Tiny scenes: a BVH of a few dozen primitives costs more in wavefront divergence (every lane walks
-    // its own node sequence) than it saves in tests. With <= MCRT_FLAT_MAX primitives (default 64) all
-    // lanes test all primitives in one wave-uniform loop, as Scene::intersect does without a "bvh" key
-    // (scene.cpp:161-173); the closest hit is the same.
+    ctx->host_light_flux = lightFlux(*s);
     const char* fm = ctxOpt(ctx, "MCRT_FLAT_MAX");
-    const uint32_t flat_max = fm ? (uint32_t)strtoul(fm, nullptr, 0) : 64u;
-    d.flat = (d.stage_all && d.num_surfaces <= flat_max && !L.flat_prim.empty() && L.num_quadric_surfaces == 0) ? 1u : 0u;  // the flat loop knows triangles and spheres
-    facts.flat = d.flat != 0;
-    facts.cull = d.flat_pre != nullptr;
-    // (the cull records travel as a kernel argument only when the host copy is what the device's counts say)
-    facts.cull_floats = L.flat_pre.size() == (size_t)d.pre_tri_pairs * kTriPairFloats + (size_t)d.pre_sph_pairs * kSphPairFloats ? (uint32_t)L.flat_pre.size() : 0u;
-    facts.stage_all = d.stage_all != 0;
-    facts.num_nodes = d.num_nodes;
-    facts.q_nodes = d.q_nodes;
-    DeviceScene pm = d;  // as the photon-mapping kernel stages it (launchRenderImpl)
-    if (!pm.stage_all) pm.stage_nodes = std::min<uint32_t>(pm.stage_nodes, 128u);
-    for (uint32_t i = 0; i < 8; i++) {
-        facts.pm_lds[0][i] = alignUp(planLds(pm, kBlock, true, 2 * (i + 1), kPmLdsIors).total, 16);
-        facts.pm_lds[1][i] = alignUp(planLds(pm, 1024u, true, 2 * (i + 1), kPmLdsIors).total, 16);
-    }
-    facts.pm_lds_full = alignUp(planLds(pm, kBlock, true, kLdsStackDepth, kMaxIors).total, 16);
+    planStaging(d, (uint32_t)ctx->max_lds, fm ? (uint32_t)strtoul(fm, nullptr, 0) : 64u, L);
+    ctx->facts = sceneFacts(d, L, *s);
     ctx->has_scene = true;
     return MCRT_OK;
 }
@@ -1428,23 +1211,11 @@ int emitOnDevice(mcrt_ctx* ctx, double emissions, double caustic_factor, uint32_
     if (nl == 0 || nl > 0xFFFFu) return nl == 0 ? MCRT_OK : fail(ctx, MCRT_ERR_UNSUPPORTED, "more than 65535 lights");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
 
-    // work split, photon-mapper.cpp:31-78
-    const size_t photon_emissions = (size_t)((double)(size_t)emissions * caustic_factor);
-    double total_add_flux = 0.0;
-    for (uint32_t i = 0; i < nl; i++) {
-        const double* f = &ctx->host_light_flux[(size_t)i * 3];
-        total_add_flux += 0.0 + f[0] + f[1] + f[2];  // glm::compAdd
-    }
-    std::vector<unsigned long long> first(nl + 1, 0ull);
-    std::vector<double> pflux((size_t)nl * 3);
-    for (uint32_t i = 0; i < nl; i++) {
-        const double* f = &ctx->host_light_flux[(size_t)i * 3];
-        const double share = (0.0 + f[0] + f[1] + f[2]) / total_add_flux;
-        const size_t n = (size_t)((double)photon_emissions * share);
-        if (n > 0xFFFFFFFFull) return fail(ctx, MCRT_ERR_UNSUPPORTED, "more than 2^32 emissions from one light");
-        first[i + 1] = first[i] + n;
-        for (int c = 0; c < 3; c++) pflux[(size_t)i * 3 + c] = f[c] / (double)n;
-    }
+    std::vector<unsigned long long> first;
+    std::vector<double> pflux;
+    planEmission(ctx->host_light_flux, emissions, caustic_factor, first, pflux);
+    for (uint32_t i = 0; i < nl; i++)
+        if (first[i + 1] - first[i] > 0xFFFFFFFFull) return fail(ctx, MCRT_ERR_UNSUPPORTED, "more than 2^32 emissions from one light");
     const unsigned long long all_paths = first[nl];
     const unsigned long long shard_begin = all_paths * shard_index / shard_count, shard_end = all_paths * (shard_index + 1ull) / shard_count;
     const unsigned long long total = shard_end - shard_begin;  // paths of this shard
@@ -1476,24 +1247,13 @@ int emitOnDevice(mcrt_ctx* ctx, double emissions, double caustic_factor, uint32_
             if (ctx->emit_keys[w].bytes < cap[w] * 8) HIP_TRY(ctx, ctx->emit_keys[w].alloc(cap[w] * 8));
             cap[w] = std::min<unsigned long long>(ctx->emit_photons[w].bytes / 32, ctx->emit_keys[w].bytes / 8);
         }
+        float* const lists[2] = {ctx->emit_photons[0].as<float>(), ctx->emit_photons[1].as<float>()};
+        unsigned long long* const keys[2] = {ctx->emit_keys[0].as<unsigned long long>(), ctx->emit_keys[1].as<unsigned long long>()};
+        const unsigned long long none[2] = {0ull, 0ull};
         EmitParams prm;
-        memset(&prm, 0, sizeof(prm));
-        prm.num_lights = nl;
-        prm.light_first = ctx->emit_first.as<unsigned long long>();
-        prm.light_photon_flux = ctx->emit_flux.as<double>();
-        prm.total_emissions = shard_end;
-        prm.first_emission = shard_begin;
-        prm.stride = counting ? kPilotStride : 1u;
-        prm.global_seed = global_seed;
-        prm.non_caustic_reject = 1.0 / caustic_factor;
-        for (int w = 0; w < 2; w++) {
-            prm.photons[w] = ctx->emit_photons[w].as<float>();
-            prm.keys[w] = ctx->emit_keys[w].as<unsigned long long>();
-            prm.capacity[w] = counting ? 0ull : cap[w];
-        }
-        prm.counters = ctx->emit_counters.as<unsigned long long>();
-        prm.spill = ctx->spill.as<StackEntry>();
-        prm.total_lanes = g.total_lanes;
+        fillEmitParams(prm, nl, ctx->emit_first.as<unsigned long long>(), ctx->emit_flux.as<double>(), shard_begin, shard_end, counting ? kPilotStride : 1u,
+                       global_seed, caustic_factor, lists, keys, counting ? none : cap, ctx->emit_counters.as<unsigned long long>(),
+                       ctx->spill.as<StackEntry>(), g.total_lanes);
         const uint32_t grid = (uint32_t)std::min<unsigned long long>(g.grid, (total + kBlock - 1) / kBlock + 1);
         HIP_TRY(ctx, hipMemsetAsync(ctx->emit_counters.p, 0, 8 * sizeof(unsigned long long), ctx->stream));
         HIP_TRY(ctx, hipEventRecord(ctx->ev0, ctx->stream));
@@ -1693,6 +1453,7 @@ int mcrt_intersect(mcrt_ctx* ctx, uint64_t n, const double* start, const double*
         const RenderOptions opt = parseRenderOptions(ctx->options);
         const int lean = traceVisit(opt, ctx->facts.q_single, false);
         auto trace = lean == 3 ? wfTraceKernel<ArrayRays, false, 3> : lean == 1 ? wfTraceKernel<ArrayRays, false, 1> : wfTraceKernel<ArrayRays, false>;
+        if (!ctx->wf_ctrl.p) HIP_TRY(ctx, ctx->wf_ctrl.alloc(kWfCtrlWords * sizeof(unsigned long long)));
         TracePlan tp;
         if (int rc = planTrace(ctx, trace, n, opt.wf_leaf, tp)) return rc;
         DevBuf &ds = ctx->op_buf[0], &dd = ctx->op_buf[1], &dt = ctx->op_buf[2], &dsf = ctx->op_buf[3], &duv = ctx->op_buf[4];
@@ -1701,17 +1462,14 @@ int mcrt_intersect(mcrt_ctx* ctx, uint64_t n, const double* start, const double*
         HIP_TRY(ctx, dt.reserve(n * 8));
         HIP_TRY(ctx, dsf.reserve(n * 4));
         HIP_TRY(ctx, duv.reserve(n * 16));
-        if (!ctx->wf_ctrl.p) HIP_TRY(ctx, ctx->wf_ctrl.alloc(kWfCtrlWords * sizeof(unsigned long long)));
-        const unsigned long long ctrl_init[4] = {n, 0ull, 0ull, 0ull};
+        unsigned long long ctrl_init[kWfCtrlRCount] = {};  // the ray queue's words: n rays queued, none handed out
+        ctrl_init[kWfCtrlCount] = n;
         HIP_TRY(ctx, hipMemcpyAsync(ctx->wf_ctrl.p, ctrl_init, sizeof(ctrl_init), hipMemcpyHostToDevice, ctx->stream));
         HIP_TRY(ctx, hipMemsetAsync(ctx->stats.p, 0, kStatsWords * sizeof(unsigned long long), ctx->stream));
-        WfTraceArgs ta = tp.args;
-        ta.count = ctx->wf_ctrl.as<unsigned long long>();
-        ta.pop = ctx->wf_ctrl.as<unsigned long long>() + 2;
         ArrayRays ar{ds.as<double>(), dd.as<double>(), dt.as<double>(), dsf.as<uint32_t>(), duv.as<double>()};
         const bool op_time = ctxOptOn(ctx, "MCRT_OP_TIME");  // kernel time of the operator to stderr
         if (op_time) HIP_TRY(ctx, hipEventRecord(ctx->ev0, ctx->stream));
-        hipLaunchKernelGGL(trace, dim3(tp.grid), dim3(tp.block), tp.lds_bytes, ctx->stream, ta, ar);
+        hipLaunchKernelGGL(trace, dim3(tp.grid), dim3(tp.block), tp.lds_bytes, ctx->stream, tp.args, ar);
         HIP_TRY(ctx, hipGetLastError());
         if (op_time) HIP_TRY(ctx, hipEventRecord(ctx->ev1, ctx->stream));
         HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));

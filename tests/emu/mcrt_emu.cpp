@@ -17,6 +17,7 @@
 #include "../../monte-carlo-ray-tracer_amd/csrc/mcrt_libm_pow.hpp"
 #include "../../monte-carlo-ray-tracer_amd/csrc/mcrt_integrator.hpp"
 #include "../../monte-carlo-ray-tracer_amd/csrc/mcrt_lanesm.hpp"
+#include "../../monte-carlo-ray-tracer_amd/csrc/mcrt_launch.hpp"
 #include "../../monte-carlo-ray-tracer_amd/csrc/mcrt_layout.hpp"
 #include "../../monte-carlo-ray-tracer_amd/csrc/mcrt_octree_shared.hpp"
 #include "../../monte-carlo-ray-tracer_amd/csrc/mcrt_output.hpp"
@@ -550,48 +551,24 @@ static int renderWf(const mcrt_scene_desc* scene, const mcrt_photon_map_desc* gm
     WfPool P;
     P.w = pool.data();
     P.n = slots;
-    WfFrame fr;
-    fr.cam = *cam;
-    fr.global_seed = global_seed;
-    fr.spp = cam->sqrtspp * cam->sqrtspp;
-    fr.tiles_x = (cam->width + 7) / 8;
-    fr.iors_deep = iors_deep.data();
-    fr.iors_deep_rows = (uint32_t)(kMaxIorsDeep - kMaxIors);
-    // one pass over the owned rows; units per pixel 1, 2 or 4 depending on the slot count, so that the tests cover whole-pixel
-    // units, chunks, and chunk counts that do not divide spp (empty last chunk)
-    fr.chunk_shift = slots % 3u;
-    fr.chunk = (fr.spp + (1u << fr.chunk_shift) - 1u) >> fr.chunk_shift;
-    fr.row_base = 0;
-    fr.row_end = owned_rows;
-    fr.pass_pixels = (unsigned long long)owned_rows * cam->width;
-    fr.work_items = ((unsigned long long)fr.tiles_x * ((owned_rows + 7) / 8) * 64ull) << fr.chunk_shift;
-    std::vector<double> samples;
-    fr.film.type = MCRT_FILM_BOX;
-    std::vector<double> blob, cache;
-    if (filmSplats(cam->film_filter, cam->film_radius)) {  // as launchWavefront sets the film up
-        FilmView& f = fr.film;
-        f.type = filmViewType(cam->film_filter);
-        f.width = cam->width;
-        f.height = cam->height;
-        f.radius = cam->film_radius > 0.0 ? cam->film_radius : filmDefaultRadius(cam->film_filter);
-        f.two_inv_radius = 2.0 / f.radius;
-        f.cache_size = cam->film_cache_size;
-        f.inv_dx = 0.0;
-        f.cache = nullptr;
-        if (f.cache_size) {
-            cache.resize(f.cache_size);
-            for (uint32_t i = 0; i < f.cache_size; i++) cache[i] = filmFilterFunction(f.type, (2.0 * (int)i) / (double)(f.cache_size - 1));
-            f.cache = cache.data();
-            f.inv_dx = (double)(f.cache_size - 1) / f.radius;
-        }
+    // one pass over the owned rows; units per pixel 1, 2 or 4 depending on the slot count (a test override of the host's plan), so that
+    // the tests cover whole-pixel units, chunks, and chunk counts that do not divide spp (empty last chunk)
+    const uint32_t spp = cam->sqrtspp * cam->sqrtspp, chunk_shift = slots % 3u;
+    const ChunkPlan cp{chunk_shift, (spp + (1u << chunk_shift) - 1u) >> chunk_shift};
+    const bool splats = filmSplats(cam->film_filter, cam->film_radius);
+    std::vector<double> samples, blob;
+    const std::vector<double> cache = filmCacheTable(*cam);
+    FilmView film;
+    if (splats) {
         if (film_out) std::fill(film_out, film_out + (size_t)cam->width * cam->height * 4, 0.0);
         else blob.assign((size_t)cam->width * cam->height * 4, 0.0);
-        f.blob = film_out ? film_out : blob.data();
+        film = makeFilmView(*cam, cache.data(), film_out ? film_out : blob.data());
+    } else {
+        samples.assign((size_t)spp * owned_rows * cam->width * 3, 0.0);
     }
-    if (fr.film.type == MCRT_FILM_BOX) {
-        samples.assign((size_t)fr.spp * fr.pass_pixels * 3, 0.0);
-        fr.samples = samples.data();
-    }
+    WfFrame fr;
+    fillWfFrame(fr, *cam, global_seed, cp, splats ? nullptr : samples.data(), splats ? &film : nullptr, iors_deep.data(), (uint32_t)kMaxIorsDeep);
+    setWfPass(fr, 0, owned_rows);
     unsigned long long work = 0;
     std::vector<HostRayRec> queue, prev_queue;
     std::vector<uint32_t> requests;
@@ -658,22 +635,15 @@ int emu_emit_photons(const mcrt_scene_desc* scene, double emissions, double caus
                      uint64_t* ccount, uint64_t* rays) {
     Emu E;
     if (int rc = setup(E, scene, stage_all ? 1 : 0)) return rc;
-    const size_t photon_emissions = (size_t)((double)(size_t)emissions * caustic_factor);
     const double non_caustic_reject = 1.0 / caustic_factor;
-    std::vector<double> lf((size_t)scene->num_lights * 3);
-    double total = 0.0;
-    for (uint32_t i = 0; i < scene->num_lights; i++) {
-        const uint32_t ls = scene->light_surface[i];
-        for (int c = 0; c < 3; c++) lf[i * 3 + c] = scene->materials[scene->surf_material[ls]].emittance[c] * scene->surf_area[ls];
-        total += 0.0 + lf[i * 3] + lf[i * 3 + 1] + lf[i * 3 + 2];
-    }
+    std::vector<unsigned long long> first;
+    std::vector<double> pflux;
+    planEmission(lightFlux(*scene), emissions, caustic_factor, first, pflux);
     TraceCounters cnt = {0, 0, 0, 0};
     uint64_t ng = 0, nc = 0;
     for (uint32_t i = 0; i < scene->num_lights; i++) {
-        const double share = (0.0 + lf[i * 3] + lf[i * 3 + 1] + lf[i * 3 + 2]) / total;
-        const size_t n = (size_t)((double)photon_emissions * share);
-        const d3 pf = d3{lf[i * 3] / (double)n, lf[i * 3 + 1] / (double)n, lf[i * 3 + 2] / (double)n};
-        for (size_t j = 0; j < n; j++) {
+        const d3 pf = d3{pflux[i * 3], pflux[i * 3 + 1], pflux[i * 3 + 2]};
+        for (size_t j = 0, n = (size_t)(first[i + 1] - first[i]); j < n; j++) {
             EmitState es;
             if (stage_all) emitBegin(es, E.rh, E.sh_all, i, (uint32_t)j, pf, global_seed, E.tab.data());
             else emitBegin(es, E.rh, E.sh_top, i, (uint32_t)j, pf, global_seed, E.tab.data());

@@ -473,3 +473,41 @@ def test_lean_photon_mapping_kernel_on_the_host(pkg, wave_kernel_emu, wave_kerne
     rc1, lean, st1, kid1 = _emulated_frame(pkg, wave_kernel_emu_lean, img, cam, manifest["seed"], pkg.INTEGRATOR_PHOTON_MAPPER)
     assert rc0 == 0 and rc1 == 0 and kid0 == kid1 == 5 and int(st0[4]) == int(st1[4]) > 0
     np.testing.assert_array_equal(lean, full)
+
+
+@pytest.mark.parametrize("name,photon,force", [("hexagon_room", False, 0), ("hexagon_room", False, 6), ("hexagon_room_ggx", False, 6), ("veach_mis", False, 0),
+                                               ("coffee_maker_qsah", False, 0), ("quadric", False, 0), ("dragon_room", False, 0),
+                                               ("hexagon_room_pm", True, 0)])
+def test_emulated_frames_run_the_instance_the_host_selects(pkg, wave_kernel_emu, manifest, name, photon, force):
+    """wemu_render asks the host's own selectKernel (csrc/mcrt_select.hpp) with SceneFacts derived by the host's sceneFacts
+    (csrc/mcrt_launch.hpp). Here the same question is put to selectKernel from outside - the scene's facts, the frame, and the call
+    written as the options a user would set - and the emulated frame must have run the instance, workgroup size and stack depth it names."""
+    from conftest import camera_for
+    case = manifest["cases"][name]
+    img = pkg.SceneImage(golden_path(case["image"]))
+    cam = camera_for(img, case["renders"][0])
+    cam.width, cam.height, cam.sqrtspp = 16, 8, 1
+    integ = pkg.INTEGRATOR_PHOTON_MAPPER if photon else pkg.INTEGRATOR_PATH_TRACER
+    facts = (C.c_uint64 * 26)()
+    assert wave_kernel_emu.wemu_scene_facts(C.byref(img.scene), facts) == 0
+    k = img.param("k_nearest_photons") or 50
+    frame = (C.c_uint64 * 8)(int(photon), cam.width * cam.height, 0, 0, k, facts[25], 0, 0)
+    options = {"MCRT_LEAN_KERNELS": "0"}  # (the full library)
+    if not facts[0]:
+        options["MCRT_KERNEL"] = "sm"
+    elif force == 0:
+        options["MCRT_FLAT_KARG"] = "0"
+    keys = (C.c_char_p * len(options))(*[k_.encode() for k_ in options])
+    values = (C.c_char_p * len(options))(*[v.encode() for v in options.values()])
+    choice, msg = (C.c_uint64 * 9)(), C.create_string_buffer(256)
+    assert wave_kernel_emu.emu_select_kernel(facts, frame, len(options), keys, values, choice, msg, 256) == 0, msg.value
+    rc, out, stats, kid = _emulated_frame(pkg, wave_kernel_emu, img, cam, manifest["seed"], integ, force, 1)
+    assert rc == 0
+    launch = (C.c_uint64 * 4)()
+    wave_kernel_emu.wemu_last_launch(launch)
+    form, instance, block, stack_depth = int(choice[0]), int(choice[1]), int(choice[5]), int(choice[6])
+    print("%s: form %d instance %d, %d lanes, %d stack entries in LDS, %d bytes of LDS" % (name, form, instance, block, stack_depth, launch[3]))
+    assert (int(launch[0]), int(launch[1]), int(launch[2])) == (instance, block, stack_depth)
+    assert kid == (16 if force == 6 and form == 1 else form)
+    if force == 6 and form == 1:
+        assert block == 768  # the full instance with its records as an argument: the shape the host launches
