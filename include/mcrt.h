@@ -273,6 +273,44 @@ int mcrt_render_multi(mcrt_ctx* const* ctxs, uint32_t count, const mcrt_camera_d
 /* Number of rows owned by (shard_index, shard_count, shard_rows) of `cam`, and their indices. */
 uint32_t mcrt_shard_rows(const mcrt_camera_desc* cam, uint32_t* rows /* may be NULL */);
 
+/* ------------------------------------------------------------------------------------------
+ * First-hit AOV pass: the geometry buffers compositing, denoising and scene debugging read next to the beauty frame. The
+ * reference has no such output; every value is one it computes on the way to a pixel. The samples are the beauty frame's
+ * own: for sample i in 0..sqrtspp^2-1 of pixel (x, y) the ray is Camera::samplePixel's (camera/camera.cpp:79-95, thin lens
+ * included) with the sampler at initiate(y*width+x), setIndex(i) (camera.cpp:73-77) and Sampler::global_seed = global_seed,
+ * so a frame made with the camera and seed of an mcrt_render lines up with it sample for sample. Per sample, with
+ * hit = Scene::intersect(ray) (scene/scene.cpp:151-176) and what Interaction's constructor derives from it before any material
+ * decision (ray/interaction.cpp:12-36):
+ *   P  = ray(t) (ray/ray.cpp:69-72) · N = surface->normal(P) · Ns = interpolate ? interpolatedNormal(uv) : N, back to N when
+ *   (dot(d,N) < 0) != (dot(d,Ns) < 0) (:23-30) · both negated when dot(d,N) > 0 (:32-36) · albedo = material->reflectance.
+ * Per pixel every channel word is summed by ONE FP64 accumulator in ascending sample index - the frame does not depend on
+ * chunking (option MCRT_AOV_CHUNK_RAYS: rays per launch group, default 2^24, always whole pixels), sharding or launch shape, bit
+ * for bit:
+ *   coverage                        hits / spp
+ *   normal, shading_normal, albedo  (sum over the hit samples) / spp  - a miss adds zero
+ *   position                        (sum over the hit samples) / hits - zeros at coverage 0
+ *   depth                           (sum of t over the hit samples) / hits - DBL_MAX at coverage 0 (ray/intersection.hpp:14)
+ *   surface, material               the hit of sample 0: index into the uploaded surface / material arrays, 0xFFFFFFFF on a miss
+ * cam->shard_* is honoured exactly as in mcrt_render_device; cam->film_* is IGNORED: AOVs are per-pixel box means whatever filter
+ * the beauty frame is reconstructed with. The closest hits come from the kernels behind mcrt_intersect, unchanged. Both calls are
+ * synchronous on the context's stream, and refused while a render is in flight or before mcrt_upload_scene.
+ * stats: paths = rays = samples traced, kernel_ms (HIP events around the pass's launches), total_ms, kernel_launches. */
+typedef struct mcrt_aov_buffers {      /* every pointer may be NULL = channel not wanted; DEVICE memory, owned rows only,  */
+    double*   depth;           /* [rows][width]     packed in ascending row order like mcrt_render_device's d_out_rgb      */
+    double*   position;        /* [rows][width][3] */
+    double*   normal;          /* [rows][width][3] */
+    double*   shading_normal;  /* [rows][width][3] */
+    double*   albedo;          /* [rows][width][3] */
+    double*   coverage;        /* [rows][width]    */
+    uint32_t* surface;         /* [rows][width]    */
+    uint32_t* material;        /* [rows][width]    */
+} mcrt_aov_buffers;
+int mcrt_render_aov_device(mcrt_ctx* ctx, const mcrt_camera_desc* cam, uint32_t global_seed, const mcrt_aov_buffers* buffers,
+                           mcrt_stats* stats /* may be NULL */);
+/* Same with HOST pointers to FULL frames ([height][width]...): rows this shard does not own are left untouched. */
+int mcrt_render_aov(mcrt_ctx* ctx, const mcrt_camera_desc* cam, uint32_t global_seed, const mcrt_aov_buffers* buffers,
+                    mcrt_stats* stats /* may be NULL */);
+
 /* Photon emission pass on the GPU. Replaces the thread fan-out of
  * PhotonMapper::PhotonMapper (integrator/photon-mapper/photon-mapper.cpp:80-115: per emission
  * Sampler::initiate(light), setIndex(offset+i), light point + cosine direction, emitPhoton :225-277) for
@@ -359,6 +397,12 @@ int mcrt_photon_map_download(mcrt_ctx* ctx, int which, struct mcrt_photon_map** 
  * no hit), uv[2] (meaningful when the surface interpolates normals). */
 int mcrt_intersect(mcrt_ctx* ctx, uint64_t n, const double* start, const double* direction,
                    double* out_t, uint32_t* out_surface, double* out_uv);
+/* The same query on DEVICE arrays (the form for hosts that only want the traversal engine and keep their rays on the GPU: nothing
+ * crosses PCIe): d_start[n][3], d_direction[n][3] in, d_t[n], d_surface[n], d_uv[n][2] (may be NULL) out, same values as
+ * mcrt_intersect. Inputs follow the STREAM CONTRACT above (complete when the call is made); the call is synchronous on the
+ * context's stream. */
+int mcrt_intersect_device(mcrt_ctx* ctx, uint64_t n, const double* d_start, const double* d_direction, double* d_t,
+                          uint32_t* d_surface, double* d_uv /* may be NULL */);
 
 /* Sampler (sampling/sampler.hpp:13-90): for each (pixel[i], index[i]) runs initiate(pixel),
  * setIndex(index), then `shuffles` times shuffle(); writes get<0,7>() after the last step

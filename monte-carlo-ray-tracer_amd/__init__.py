@@ -155,6 +155,17 @@ class PhotonPassStats(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class AovBuffers(C.Structure):
+    """mcrt_aov_buffers: one pointer per channel of the first-hit AOV pass, NULL = channel not wanted."""
+    _fields_ = [("depth", C.c_void_p), ("position", C.c_void_p), ("normal", C.c_void_p), ("shading_normal", C.c_void_p),
+                ("albedo", C.c_void_p), ("coverage", C.c_void_p), ("surface", C.c_void_p), ("material", C.c_void_p)]
+
+
+# channel -> (dtype, values per pixel), in mcrt_aov_buffers order
+AOV_CHANNELS = {"depth": (np.float64, 1), "position": (np.float64, 3), "normal": (np.float64, 3), "shading_normal": (np.float64, 3),
+                "albedo": (np.float64, 3), "coverage": (np.float64, 1), "surface": (np.uint32, 1), "material": (np.uint32, 1)}
+
+
 class PhotonEmissionDevice(C.Structure):
     _fields_ = [("global_count", C.c_uint64), ("caustic_count", C.c_uint64), ("d_global_photons", C.c_void_p), ("d_caustic_photons", C.c_void_p),
                 ("emission_paths", C.c_uint64), ("rays", C.c_uint64), ("kernel_ms", C.c_double)]
@@ -239,6 +250,10 @@ def lib():
     L.mcrt_upload_photons_device.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint64, _dp, _dp, C.c_uint32, C.c_uint32, C.c_int, C.POINTER(PhotonPassStats)]
     L.mcrt_photon_map_download.argtypes = [vp, C.c_int, C.POINTER(vp)]
     L.mcrt_intersect.argtypes = [vp, C.c_uint64, _dp, _dp, _dp, _u32p, _dp]
+    if hasattr(L, "mcrt_render_aov"):  # (absent from older libraries that tools/ab_builds.sh swaps in)
+        L.mcrt_intersect_device.argtypes = [vp, C.c_uint64, vp, vp, vp, vp, vp]
+        L.mcrt_render_aov.argtypes = [vp, C.POINTER(CameraDesc), C.c_uint32, C.POINTER(AovBuffers), C.POINTER(Stats)]
+        L.mcrt_render_aov_device.argtypes = [vp, C.POINTER(CameraDesc), C.c_uint32, C.POINTER(AovBuffers), C.POINTER(Stats)]
     L.mcrt_sampler.argtypes = [vp, C.c_uint64, _u32p, _u32p, C.c_uint32, C.c_uint32, _dp]
     L.mcrt_knn.argtypes = [vp, C.c_int, C.c_uint64, _dp, C.c_uint32, _u32p, _u32p, _dp]
     L.mcrt_bsdf.argtypes = [vp, C.c_uint64, _dp, _dp, _dp]
@@ -640,6 +655,45 @@ class Context:
                                              _ptr(surf, C.c_uint32), _ptr(uv, C.c_double)),
                     "mcrt_intersect")
         return t, surf, uv
+
+    def intersect_device(self, n, d_start, d_direction, d_t, d_surface, d_uv=None):
+        """mcrt_intersect_device: mcrt_intersect on raw device pointers (e.g. tensor.data_ptr()): start[n][3], direction[n][3] in,
+        t[n], surface[n] (uint32), uv[n][2] (optional) out. The inputs must be complete (torch.cuda.synchronize()) when this is called."""
+        self._sync_env()
+        self._check(self._lib.mcrt_intersect_device(self._h, int(n), C.c_void_p(int(d_start)), C.c_void_p(int(d_direction)), C.c_void_p(int(d_t)),
+                                                    C.c_void_p(int(d_surface)), C.c_void_p(int(d_uv)) if d_uv else None), "mcrt_intersect_device")
+
+    def render_aov(self, cam, global_seed, channels=None, out=None, stats=None):
+        """mcrt_render_aov: the first-hit AOV frame -> dict channel -> array [H,W] or [H,W,3]. channels: the names wanted (AOV_CHANNELS;
+        None = all). out: a dict of arrays to write into instead of fresh zeros - the call only writes the rows cam's shard owns, the
+        others keep their contents. stats: a dict that receives mcrt_stats."""
+        self._sync_env()
+        names = list(AOV_CHANNELS) if channels is None else list(channels)
+        res, bufs = {}, AovBuffers()
+        for name in names:
+            dtype, k = AOV_CHANNELS[name]
+            shape = (cam.height, cam.width) + ((k,) if k > 1 else ())
+            a = out[name] if out is not None and name in out else np.zeros(shape, dtype=dtype)
+            assert a.dtype == dtype and a.shape == shape and a.flags["C_CONTIGUOUS"], name
+            res[name] = a
+            setattr(bufs, name, a.ctypes.data)
+        st = Stats()
+        self._check(self._lib.mcrt_render_aov(self._h, C.byref(cam), int(global_seed), C.byref(bufs), C.byref(st)), "mcrt_render_aov")
+        if stats is not None:
+            stats.update(st.as_dict())
+        return res
+
+    def render_aov_device(self, cam, global_seed, pointers):
+        """mcrt_render_aov_device: pointers = dict channel -> raw device pointer (owned rows only, packed like render_device's
+        output); channels left out are not computed. Synchronous; returns the stats dict."""
+        self._sync_env()
+        bufs = AovBuffers()
+        for name, ptr in pointers.items():
+            assert name in AOV_CHANNELS, name
+            setattr(bufs, name, int(ptr))
+        st = Stats()
+        self._check(self._lib.mcrt_render_aov_device(self._h, C.byref(cam), int(global_seed), C.byref(bufs), C.byref(st)), "mcrt_render_aov_device")
+        return st.as_dict()
 
     def sampler(self, pixel, index, shuffles, global_seed):
         pixel = np.ascontiguousarray(pixel, dtype=np.uint32)

@@ -22,6 +22,7 @@
 #include "mcrt_widerec.hpp"
 #include "mcrt_layout.hpp"
 #include "mcrt_internal.hpp"
+#include "mcrt_aov.hpp"
 #include "mcrt_plan.hpp"
 #include "mcrt_select.hpp"
 #include "mcrt_launch.hpp"
@@ -119,6 +120,7 @@ struct mcrt_ctx {
     // scratch of the operator-level entry points (mcrt_intersect / mcrt_knn / mcrt_sampler / mcrt_bsdf): kept between calls, grown
     // on demand, so that a host that only wants traversal or k-NN does not pay five hipMalloc / hipFree pairs per call
     DevBuf op_buf[6];
+    DevBuf aov_buf[mcrt::kAovScratchBufs];  // the first-hit AOV pass's rays, hits and host-call channels (mcrt_aov_host.hip), grown on demand too
     std::map<std::string, std::string> options;  // mcrt_set_option; seeded from the MCRT_* environment variables at mcrt_create
     DevBuf pm_iors;  // refraction histories of the 1024-lane photon-mapping kernel
     // the frame in flight, kept so that mcrt_render_finish can run it again through the wavefront pipeline (deep refraction histories)
@@ -1440,14 +1442,12 @@ int mcrt_photon_map_download(mcrt_ctx* ctx, int which, mcrt_photon_map** out) {
     return MCRT_OK;
 }
 
-int mcrt_intersect(mcrt_ctx* ctx, uint64_t n, const double* start, const double* direction, double* out_t, uint32_t* out_surface,
-                   double* out_uv) {
-    if (!ctx) return MCRT_ERR_INVALID;
-    if (!ctx->has_scene) return fail(ctx, MCRT_ERR_NO_SCENE, "mcrt_intersect before mcrt_upload_scene");
-    REJECT_IF_PENDING(ctx, "mcrt_intersect");
-    if (n == 0) return MCRT_OK;
-    if (!start || !direction || !out_t || !out_surface) return fail(ctx, MCRT_ERR_INVALID, "null argument");
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
+}  // extern "C"
+
+namespace mcrt {
+// (kept HERE, where mcrt_intersect's body stood: kernel instantiations are emitted in the order of their first use, and that order is part
+// of the code object tests/golden/device_code_hashes.json lists)
+int intersectDeviceArrays(mcrt_ctx* ctx, uint64_t n, const double* d_start, const double* d_dir, double* d_t, uint32_t* d_surf, double* d_uv) {
     if (!ctx->scene.stage_all && ctx->scene.num_nodes > 0 && n <= 0xFFF00000ull) {  // (32-bit queue cursors with room for the waves' overshoot)
         // tree in HBM: the trace kernel of the wavefront pipeline, fed from the arrays
         const RenderOptions opt = parseRenderOptions(ctx->options);
@@ -1456,17 +1456,11 @@ int mcrt_intersect(mcrt_ctx* ctx, uint64_t n, const double* start, const double*
         if (!ctx->wf_ctrl.p) HIP_TRY(ctx, ctx->wf_ctrl.alloc(kWfCtrlWords * sizeof(unsigned long long)));
         TracePlan tp;
         if (int rc = planTrace(ctx, trace, n, opt.wf_leaf, tp)) return rc;
-        DevBuf &ds = ctx->op_buf[0], &dd = ctx->op_buf[1], &dt = ctx->op_buf[2], &dsf = ctx->op_buf[3], &duv = ctx->op_buf[4];
-        if (int rc = uploadInto(ctx, ds, start, n * 3)) return rc;
-        if (int rc = uploadInto(ctx, dd, direction, n * 3)) return rc;
-        HIP_TRY(ctx, dt.reserve(n * 8));
-        HIP_TRY(ctx, dsf.reserve(n * 4));
-        HIP_TRY(ctx, duv.reserve(n * 16));
         unsigned long long ctrl_init[kWfCtrlRCount] = {};  // the ray queue's words: n rays queued, none handed out
         ctrl_init[kWfCtrlCount] = n;
         HIP_TRY(ctx, hipMemcpyAsync(ctx->wf_ctrl.p, ctrl_init, sizeof(ctrl_init), hipMemcpyHostToDevice, ctx->stream));
         HIP_TRY(ctx, hipMemsetAsync(ctx->stats.p, 0, kStatsWords * sizeof(unsigned long long), ctx->stream));
-        ArrayRays ar{ds.as<double>(), dd.as<double>(), dt.as<double>(), dsf.as<uint32_t>(), duv.as<double>()};
+        ArrayRays ar{d_start, d_dir, d_t, d_surf, d_uv};
         const bool op_time = ctxOptOn(ctx, "MCRT_OP_TIME");  // kernel time of the operator to stderr
         if (op_time) HIP_TRY(ctx, hipEventRecord(ctx->ev0, ctx->stream));
         hipLaunchKernelGGL(trace, dim3(tp.grid), dim3(tp.block), tp.lds_bytes, ctx->stream, tp.args, ar);
@@ -1481,31 +1475,57 @@ int mcrt_intersect(mcrt_ctx* ctx, uint64_t n, const double* start, const double*
         unsigned long long h[kStatsWords];
         HIP_TRY(ctx, hipMemcpy(h, ctx->stats.p, sizeof(h), hipMemcpyDeviceToHost));
         if (h[5]) return fail(ctx, MCRT_ERR_UNSUPPORTED, "traversal stack overflow (internal error: the stacks are sized to the tree's own bound, HostLayout::stack_bound)");
-        HIP_TRY(ctx, hipMemcpy(out_t, dt.p, n * 8, hipMemcpyDeviceToHost));
-        HIP_TRY(ctx, hipMemcpy(out_surface, dsf.p, n * 4, hipMemcpyDeviceToHost));
-        if (out_uv) HIP_TRY(ctx, hipMemcpy(out_uv, duv.p, n * 16, hipMemcpyDeviceToHost));
         return MCRT_OK;
     }
     LaunchGeom g;
     auto ikernel = ctx->scene.stage_all ? intersectKernel<true> : intersectKernel<false>;
     if (int rc = launchGeometry(ctx, ikernel, ctx->scene, g)) return rc;
     if (int rc = ensureScratch(ctx, g.total_lanes, false)) return rc;
+    const uint32_t grid = (uint32_t)std::min<uint64_t>(g.grid, (n + kBlock - 1) / kBlock);
+    hipLaunchKernelGGL(ikernel, dim3(grid), dim3(kBlock), g.lds_bytes, ctx->stream, ctx->scene, n, d_start, d_dir, d_t, d_surf, d_uv,
+                       ctx->spill.as<StackEntry>(), g.total_lanes);
+    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return MCRT_OK;
+}
+}  // namespace mcrt
+
+extern "C" {
+
+int mcrt_intersect(mcrt_ctx* ctx, uint64_t n, const double* start, const double* direction, double* out_t, uint32_t* out_surface,
+                   double* out_uv) {
+    if (!ctx) return MCRT_ERR_INVALID;
+    if (!ctx->has_scene) return fail(ctx, MCRT_ERR_NO_SCENE, "mcrt_intersect before mcrt_upload_scene");
+    REJECT_IF_PENDING(ctx, "mcrt_intersect");
+    if (n == 0) return MCRT_OK;
+    if (!start || !direction || !out_t || !out_surface) return fail(ctx, MCRT_ERR_INVALID, "null argument");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
     DevBuf &ds = ctx->op_buf[0], &dd = ctx->op_buf[1], &dt = ctx->op_buf[2], &dsf = ctx->op_buf[3], &duv = ctx->op_buf[4];
     if (int rc = uploadInto(ctx, ds, start, n * 3)) return rc;
     if (int rc = uploadInto(ctx, dd, direction, n * 3)) return rc;
     HIP_TRY(ctx, dt.reserve(n * 8));
     HIP_TRY(ctx, dsf.reserve(n * 4));
     HIP_TRY(ctx, duv.reserve(n * 16));
-    const uint32_t grid = (uint32_t)std::min<uint64_t>(g.grid, (n + kBlock - 1) / kBlock);
-    hipLaunchKernelGGL(ikernel, dim3(grid), dim3(kBlock), g.lds_bytes, ctx->stream, ctx->scene, n, ds.as<double>(),
-                       dd.as<double>(), dt.as<double>(), dsf.as<uint32_t>(), duv.as<double>(), ctx->spill.as<StackEntry>(),
-                       g.total_lanes);
-    HIP_TRY(ctx, hipGetLastError());
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    if (int rc = intersectDeviceArrays(ctx, n, ds.as<double>(), dd.as<double>(), dt.as<double>(), dsf.as<uint32_t>(), duv.as<double>())) return rc;
     HIP_TRY(ctx, hipMemcpy(out_t, dt.p, n * 8, hipMemcpyDeviceToHost));
     HIP_TRY(ctx, hipMemcpy(out_surface, dsf.p, n * 4, hipMemcpyDeviceToHost));
     if (out_uv) HIP_TRY(ctx, hipMemcpy(out_uv, duv.p, n * 16, hipMemcpyDeviceToHost));
     return MCRT_OK;
+}
+
+int mcrt_intersect_device(mcrt_ctx* ctx, uint64_t n, const double* d_start, const double* d_direction, double* d_t, uint32_t* d_surface,
+                          double* d_uv) {
+    if (!ctx) return MCRT_ERR_INVALID;
+    if (!ctx->has_scene) return fail(ctx, MCRT_ERR_NO_SCENE, "mcrt_intersect_device before mcrt_upload_scene");
+    REJECT_IF_PENDING(ctx, "mcrt_intersect_device");
+    if (n == 0) return MCRT_OK;
+    if (!d_start || !d_direction || !d_t || !d_surface) return fail(ctx, MCRT_ERR_INVALID, "null argument");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (!d_uv) {  // the kernels write every hit's uv: a caller that does not want them gets the operators' scratch behind it
+        HIP_TRY(ctx, ctx->op_buf[4].reserve(n * 16));
+        d_uv = ctx->op_buf[4].as<double>();
+    }
+    return intersectDeviceArrays(ctx, n, d_start, d_direction, d_t, d_surface, d_uv);
 }
 
 int mcrt_sampler(mcrt_ctx* ctx, uint64_t n, const uint32_t* pixel, const uint32_t* index, uint32_t shuffles, uint32_t global_seed,
@@ -1679,4 +1699,36 @@ namespace mcrt {
 int ctxDevice(const mcrt_ctx* ctx) { return ctx->device; }
 void* ctxStream(const mcrt_ctx* ctx) { return (void*)ctx->stream; }
 int ctxFail(mcrt_ctx* ctx, int code, const std::string& msg) { return fail(ctx, code, msg); }
+
+int ctxAovReady(mcrt_ctx* ctx, const char* what) {
+    if (!ctx->has_scene) return fail(ctx, MCRT_ERR_NO_SCENE, std::string(what) + " before mcrt_upload_scene");
+    if (ctx->pending) return fail(ctx, MCRT_ERR_INVALID, std::string(what) + ": a render is in flight, call mcrt_render_finish first");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    return MCRT_OK;
+}
+void ctxAovScene(const mcrt_ctx* ctx, AovScene* out, const uint32_t** sobol_tab) {
+    const DeviceScene& d = ctx->scene;
+    out->sh.surf_v = d.surf_v;
+    out->sh.surf_normal = d.surf_normal;
+    out->sh.surf_vn = d.surf_vn;
+    out->sh.surf_area = d.surf_area;
+    out->sh.surf_material = d.surf_material;
+    out->sh.surf_kind = d.surf_kind;
+    out->sh.surf_rec = d.surf_rec;
+    out->sh.materials = d.materials;
+    out->sh.num_lights = d.num_lights;
+    out->sh.light_surface = d.light_surface;
+    out->sh.light_cdf = d.light_cdf;
+    out->sh.scene_ior = d.scene_ior;
+    out->prim = d.prim;
+    *sobol_tab = d.sobol_tab;
+}
+void* ctxAovScratch(mcrt_ctx* ctx, int which, size_t bytes) {
+    if (which < 0 || which >= kAovScratchBufs) return nullptr;
+    if (ctx->aov_buf[which].reserve(std::max<size_t>(bytes, 8)) != hipSuccess) {
+        (void)hipGetLastError();
+        return nullptr;
+    }
+    return ctx->aov_buf[which].p;
+}
 }  // namespace mcrt

@@ -22,4 +22,15 @@ int bvhSahGpu(mcrt_ctx* ctx, const mcrt_scene_desc* scene, int arity, int bins, 
 // mcrt_output.hip: refPow (mcrt_libm_pow.hpp, the output stage's one libm call) on device arrays, launched on `stream`: out[i] =
 // pow(a[i], b[i]). The known-answer kernel behind mcrt_libm's MCRT_LIBM_POW; returns the hipError_t of the launch as an int.
 int launchPowKat(void* stream, uint64_t n, const double* a, const double* b, double* out);
+// mcrt_hip.hip: Scene::intersect on n rays in DEVICE arrays - the body of mcrt_intersect behind its uploads (trees in memory: the trace
+// kernel fed from the arrays, otherwise the intersect kernel). d_uv must not be null. Synchronous on the context's stream.
+int intersectDeviceArrays(mcrt_ctx* ctx, uint64_t n, const double* d_start, const double* d_dir, double* d_t, uint32_t* d_surf, double* d_uv);
+// mcrt_aov_host.hip (the first-hit AOV pass's host side) reaches the context through these. ctxAovReady: device selected, MCRT_ERR_NO_SCENE / MCRT_ERR_INVALID (render in flight)
+// recorded under `what`. ctxAovScene: the uploaded scene's arrays in device memory. ctxAovScratch: buffer `which` (0..kAovScratchBufs-1)
+// of the pass's scratch, kept in the context and grown on demand like the operators'; nullptr when the allocation fails.
+struct AovScene;
+constexpr int kAovScratchBufs = 6;
+int ctxAovReady(mcrt_ctx* ctx, const char* what);
+void ctxAovScene(const mcrt_ctx* ctx, AovScene* out, const uint32_t** sobol_tab);
+void* ctxAovScratch(mcrt_ctx* ctx, int which, size_t bytes);
 }  // namespace mcrt

@@ -1,0 +1,249 @@
+"""First-hit AOV pass, CPU tier: csrc/mcrt_aov.hpp - the text the two kernels of csrc/mcrt_aov.hip run - driven on the host
+(tests/emu/aov_emu.cpp) against an expectation computed HERE, in numpy, from the oracle's hits on the same camera rays with the
+formulas of include/mcrt.h ("First-hit AOV pass") written out.
+
+Frames are 70 x 13 pixels (width no multiple of 64, 910 pixels no multiple of 256) at sqrtspp 1 and 3; the four scene images reach
+spheres behind a thin lens in a staged flat scene (hexagon_room_dof), vertex normals through the trace kernel's walk (coffee_maker_qsah),
+quadrics (quadric) and a scene without a BVH (ior_test).
+
+Bounds: t is the oracle's bits; surfaces may differ from the oracle's only at exact-t ties (conftest.check_hits_against_reference's cap,
+max(3, n // 500)), where the expectation takes the emulation's surface; coverage and ids are equal; the FP64 means agree within 1e-12
+relative (conftest.rel_error) - the bound include/mcrt.h states for sums that agree to rounding: numpy normalises by a division, the
+device code by a multiplication with the reciprocal, two roundings apart per addend."""
+import ctypes as C
+import functools
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+from conftest import ROOT, TESTS, golden_path, rel_error
+
+WIDTH, HEIGHT = 70, 13
+SEED = 0x5EED0A0F
+# scene image -> emu_intersect's flavour of the walk: 4 flat loop behind the FP32 cull, 3 the trace kernel's walk, 0 top of the tree staged,
+# 1 everything staged (ior_test has no BVH: the brute-force loop)
+SCENES = {"hexagon_room_dof": 4, "coffee_maker_qsah": 3, "quadric": 0, "ior_test": 1}
+FLOAT_CHANNELS = ("depth", "position", "normal", "shading_normal", "albedo")
+NO_SURFACE = 0xFFFFFFFF
+DBL_MAX = np.finfo(np.float64).max
+
+
+def load_aov_emu():
+    """Host build of the AOV pass (tests/emu/aov_emu.cpp = mcrt_emu.cpp + csrc/mcrt_aov.hpp), the way conftest.load_emu builds its library."""
+    src = os.path.join(TESTS, "emu", "aov_emu.cpp")
+    out = os.path.join(TESTS, "emu", "_build", "libaov_emu.so")
+    csrc = os.path.join(ROOT, "monte-carlo-ray-tracer_amd", "csrc")
+    deps = [src, os.path.join(TESTS, "emu", "mcrt_emu.cpp")] + [os.path.join(csrc, f) for f in os.listdir(csrc) if f.endswith(".hpp")]
+    if not os.path.exists(out) or any(os.path.getmtime(d) > os.path.getmtime(out) for d in deps):
+        os.makedirs(os.path.dirname(out), exist_ok=True)
+        tmp = "%s.%d.tmp" % (out, os.getpid())
+        subprocess.check_call(["g++", "-std=c++17", "-O2", "-ffp-contract=off", "-fPIC", "-shared", "-o", tmp, src])
+        os.replace(tmp, out)
+    L = C.CDLL(out)
+    vp = C.c_void_p
+    L.aov_emu_rows.argtypes = [vp]
+    L.aov_emu_rows.restype = C.c_uint32
+    L.aov_emu_rays.argtypes = [vp, vp, C.c_uint32, vp, vp]
+    L.aov_emu_frame.argtypes = [vp, vp, C.c_uint32, C.c_int, C.c_uint64, vp, vp, vp, vp]
+    return L
+
+
+@functools.lru_cache(maxsize=None)
+def _emu():
+    return load_aov_emu()
+
+
+@functools.lru_cache(maxsize=None)
+def _image(scene):
+    import importlib
+    return importlib.import_module("monte-carlo-ray-tracer_amd").SceneImage(golden_path(scene + ".mcrt"))
+
+
+def camera(scene, sqrtspp, shard=None):
+    cam = _image(scene).camera
+    cam.width, cam.height, cam.sqrtspp = WIDTH, HEIGHT, sqrtspp
+    cam.shard_index, cam.shard_count, cam.shard_rows = shard if shard else (0, 1, 0)
+    return cam
+
+
+def emu_frame(scene, sqrtspp, chunk_rays=0, shard=None):
+    """The emulation's frame over the camera's packed owned rows: (channels dict, t[P,S], surface[P,S], uv[P,S,2])."""
+    import importlib
+    pkg = importlib.import_module("monte-carlo-ray-tracer_amd")
+    img, cam, L = _image(scene), camera(scene, sqrtspp, shard), _emu()
+    pixels, spp = L.aov_emu_rows(C.byref(cam)) * WIDTH, sqrtspp * sqrtspp
+    ch = {k: np.empty((pixels,) + ((n,) if n > 1 else ()), dtype=dt) for k, (dt, n) in pkg.AOV_CHANNELS.items()}
+    bufs = pkg.AovBuffers()
+    for k, a in ch.items():
+        a.view(np.uint8).fill(0xAB)  # (whatever is not written shows)
+        setattr(bufs, k, a.ctypes.data)
+    t, surf, uv = np.empty((pixels, spp)), np.empty((pixels, spp), dtype=np.uint32), np.empty((pixels, spp, 2))
+    rc = L.aov_emu_frame(C.byref(img.scene), C.byref(cam), SEED, SCENES[scene], chunk_rays, C.byref(bufs), t.ctypes.data, surf.ctypes.data, uv.ctypes.data)
+    assert rc == 0, "aov_emu_frame: %d" % rc
+    return ch, t, surf, uv
+
+
+def emu_rays(scene, sqrtspp):
+    img, cam, L = _image(scene), camera(scene, sqrtspp), _emu()
+    n = WIDTH * HEIGHT * sqrtspp * sqrtspp
+    start, direction = np.empty((n, 3)), np.empty((n, 3))
+    assert L.aov_emu_rays(C.byref(img.scene), C.byref(cam), SEED, start.ctypes.data, direction.ctypes.data) == 0
+    return start, direction
+
+
+def scene_arrays(scene):
+    s = _image(scene).scene
+    n = s.num_surfaces
+
+    def grab(ptr, count, dtype):
+        return np.ctypeslib.as_array(ptr, shape=(count,)).astype(dtype, copy=True)
+    return dict(kind=grab(s.surf_kind, n, np.uint8), interpolate=grab(s.surf_interpolate, n, np.uint8), material=grab(s.surf_material, n, np.uint32),
+                v=grab(s.surf_v, n * 9, np.float64).reshape(n, 9), e=grab(s.surf_e, n * 9, np.float64).reshape(n, 9),
+                vn=grab(s.surf_vn, n * 9, np.float64).reshape(n, 9) if s.surf_vn else np.zeros((n, 9)),
+                reflectance=np.array([list(s.materials[i].reflectance) for i in range(s.num_materials)]),
+                quadrics=grab(s.quadrics, s.num_quadrics * 22, np.float64).reshape(-1, 22) if s.num_quadrics else np.zeros((0, 22)))
+
+
+def _normalize(v):
+    return v / np.sqrt((v * v).sum(axis=-1, keepdims=True))
+
+
+def expected_frame(scene, start, direction, t, surf, uv, spp):
+    """include/mcrt.h's formulas on per-sample hits ([P*S] arrays in [pixel][sample] order) -> channels dict over P pixels."""
+    A = scene_arrays(scene)
+    n = t.shape[0]
+    hit = surf != NO_SURFACE
+    s = np.where(hit, surf, 0)
+    P = start + direction * np.where(hit, t, 0.0)[:, None]                                    # ray(t), ray/ray.cpp:69-72
+    kind = A["kind"][s]
+    N = A["e"][s, 6:9].copy()                                             # Triangle::normal_, triangle.cpp:99-102
+    sph = kind == 1
+    N[sph] = (P[sph] - A["v"][s[sph], 0:3]) / A["v"][s[sph], 3:4]          # sphere.cpp:46-49
+    for i in np.nonzero(hit & (kind == 2))[0]:                            # quadric.cpp:127-130: normalize(G (P, 1)), G = 2 * upper rows of Q
+        q = A["quadrics"][int(A["v"][s[i], 0])]
+        g = np.array([2.0 * q[r] * P[i, 0] + 2.0 * q[4 + r] * P[i, 1] + 2.0 * q[8 + r] * P[i, 2] + 2.0 * q[12 + r] for r in range(3)])
+        N[i] = _normalize(g)
+    cos_theta = (direction * N).sum(axis=1)
+    Ns = N.copy()
+    interp = hit & (A["interpolate"][s] == 1)                             # interaction.cpp:23-30
+    u, v = uv[interp, 0:1], uv[interp, 1:2]
+    vn = A["vn"][s[interp]]
+    smooth = _normalize((1.0 - u - v) * vn[:, 0:3] + u * vn[:, 3:6] + v * vn[:, 6:9])  # triangle.cpp:109-113
+    keep = (cos_theta[interp] < 0.0) == ((direction[interp] * smooth).sum(axis=1) < 0.0)
+    Ns[interp] = np.where(keep[:, None], smooth, N[interp])
+    flip = cos_theta > 0.0                                                # interaction.cpp:32-36
+    N[flip], Ns[flip] = -N[flip], -Ns[flip]
+    material = A["material"][s]
+    albedo = A["reflectance"][material]
+
+    pixels = n // spp
+    shape = lambda a: a.reshape((pixels, spp) + a.shape[1:])
+    hit_p, t_p, P_p, N_p, Ns_p, alb_p = shape(hit), shape(t), shape(P), shape(N), shape(Ns), shape(albedo)
+    hits = hit_p.sum(axis=1)
+    acc = {k: np.zeros((pixels, 3)) for k in ("position", "normal", "shading_normal", "albedo")}
+    depth = np.zeros(pixels)
+    for i in range(spp):                                                  # one accumulator, ascending sample index
+        m = hit_p[:, i]
+        depth[m] += t_p[m, i]
+        for k, a in (("position", P_p), ("normal", N_p), ("shading_normal", Ns_p), ("albedo", alb_p)):
+            acc[k][m] += a[m, i]
+    some = hits > 0
+    out = dict(coverage=hits / float(spp), surface=np.where(hit_p[:, 0], shape(surf)[:, 0], NO_SURFACE).astype(np.uint32),
+               material=np.where(hit_p[:, 0], shape(material)[:, 0], NO_SURFACE).astype(np.uint32))
+    out["depth"] = np.where(some, depth / np.maximum(hits, 1), DBL_MAX)
+    out["position"] = np.where(some[:, None], acc["position"] / np.maximum(hits, 1)[:, None], 0.0)
+    for k in ("normal", "shading_normal", "albedo"):
+        out[k] = acc[k] / float(spp)
+    return out
+
+
+@functools.lru_cache(maxsize=None)
+def case(scene, sqrtspp):
+    """Everything the tests of one (scene, sqrtspp) share, computed once: the emulation's rays and frame, the oracle's hits on those
+    rays, the number of exact-t ties and the numpy expectation (tie surfaces and their uv taken from the emulation)."""
+    import oracle_lib
+    spp = sqrtspp * sqrtspp
+    start, direction = emu_rays(scene, sqrtspp)
+    frame, t_e, s_e, uv_e = emu_frame(scene, sqrtspp)
+    t_o, s_o, uv_o, _ = oracle_lib.intersect(_image(scene), start, direction)
+    t_e, s_e, uv_e = t_e.reshape(-1), s_e.reshape(-1), uv_e.reshape(-1, 2)
+    ties = s_e != s_o
+    surf = np.where(ties, s_e, s_o)
+    uv = np.where(ties[:, None], uv_e, uv_o)
+    return dict(start=start, direction=direction, frame=frame, t_emu=t_e, surf_emu=s_e, t_oracle=t_o, surf_oracle=s_o, ties=int(ties.sum()),
+                expected=expected_frame(scene, start, direction, t_o, surf, uv, spp), spp=spp)
+
+
+def check_against_expectation(frame, expected, what):
+    for k in ("coverage", "surface", "material"):
+        np.testing.assert_array_equal(frame[k].reshape(expected[k].shape), expected[k], err_msg="%s %s" % (what, k))
+    for k in FLOAT_CHANNELS:
+        err = rel_error(frame[k].reshape(expected[k].shape), expected[k]).max()
+        print("%s %-14s max rel error %.3e" % (what, k, err))
+        assert err <= 1e-12, "%s %s: %.3e" % (what, k, err)
+
+
+@pytest.mark.parametrize("sqrtspp", [1, 3])
+@pytest.mark.parametrize("scene", list(SCENES))
+def test_emulated_frame_against_numpy_from_oracle_hits(scene, sqrtspp, oracle):
+    c = case(scene, sqrtspp)
+    n = c["t_emu"].shape[0]
+    assert n == WIDTH * HEIGHT * sqrtspp * sqrtspp
+    np.testing.assert_array_equal(c["t_emu"].view(np.uint64), c["t_oracle"].view(np.uint64))  # the oracle's bits, every sample
+    print("%s sqrtspp %d: %d samples, %d hits, %d exact-t ties" % (scene, sqrtspp, n, int((c["surf_emu"] != NO_SURFACE).sum()), c["ties"]))
+    assert c["ties"] <= max(3, n // 500)
+    assert 0 < (c["surf_emu"] != NO_SURFACE).sum()
+    check_against_expectation(c["frame"], c["expected"], "%s sqrtspp %d" % (scene, sqrtspp))
+
+
+def test_scenes_reach_the_branches_they_are_here_for():
+    """Misses, partial coverage and quadric normals (quadric), vertex normals that differ from the face's (coffee_maker_qsah), a thin
+    lens (hexagon_room_dof), no BVH (ior_test)."""
+    part = case("quadric", 3)["frame"]["coverage"]
+    assert (part == 1).any() and ((part > 0) & (part < 1)).any()
+    cov = case("quadric", 1)["frame"]  # (one sample per pixel: the 11 rays that leave the scene are whole pixels)
+    assert (cov["coverage"] == 0).any() and (cov["coverage"] == 1).any()
+    assert (cov["depth"][cov["coverage"] == 0] == DBL_MAX).all() and (cov["surface"][cov["coverage"] == 0] == NO_SURFACE).all()
+    assert (cov["position"][cov["coverage"] == 0] == 0).all() and (cov["material"][cov["coverage"] == 0] == NO_SURFACE).all()
+    assert camera("hexagon_room_dof", 1).thin_lens == 1 and camera("quadric", 1).thin_lens == 1
+    assert len(np.unique(case("hexagon_room_dof", 3)["start"], axis=0)) > 8000  # (lens samples: every ray starts elsewhere)
+    A = scene_arrays("coffee_maker_qsah")
+    cm = case("coffee_maker_qsah", 1)
+    hit = cm["surf_emu"] != NO_SURFACE
+    assert (A["interpolate"][cm["surf_emu"][hit]] == 1).sum() > 100
+    assert not np.array_equal(cm["frame"]["normal"], cm["frame"]["shading_normal"])
+    Q = scene_arrays("quadric")
+    q = case("quadric", 1)
+    assert (Q["kind"][q["surf_emu"][q["surf_emu"] != NO_SURFACE]] == 2).sum() > 10
+    assert _image("ior_test").scene.num_nodes == 0
+
+
+def test_emulated_frame_does_not_depend_on_chunks_or_shards():
+    """Chunks of 64 pixels (15 of them, the last ragged) and of one pixel; three shards of 5-row groups (the last group ragged)."""
+    whole = case("coffee_maker_qsah", 3)["frame"]
+    for chunk_rays in (64 * 9, 1):
+        chunked = emu_frame("coffee_maker_qsah", 3, chunk_rays=chunk_rays)[0]
+        for k in whole:
+            assert whole[k].tobytes() == chunked[k].tobytes(), "chunk_rays %d: %s" % (chunk_rays, k)
+    import importlib
+    pkg = importlib.import_module("monte-carlo-ray-tracer_amd")
+    seen = 0
+    for index in range(3):
+        cam = camera("coffee_maker_qsah", 3, (index, 3, 5))
+        rows = pkg.shard_rows(cam)
+        part = emu_frame("coffee_maker_qsah", 3, shard=(index, 3, 5))[0]
+        for k in whole:
+            full = whole[k].reshape((HEIGHT, WIDTH) + whole[k].shape[1:])
+            assert full[rows].tobytes() == part[k].tobytes(), "shard %d: %s" % (index, k)
+        seen += len(rows)
+    assert seen == HEIGHT
+
+
+def test_null_context_is_refused(pkg):
+    L = pkg.lib()
+    cam, bufs = pkg.CameraDesc(), pkg.AovBuffers()
+    assert L.mcrt_render_aov(None, C.byref(cam), 1, C.byref(bufs), None) == -1      # MCRT_ERR_INVALID
+    assert L.mcrt_render_aov_device(None, C.byref(cam), 1, C.byref(bufs), None) == -1
+    assert L.mcrt_intersect_device(None, 0, None, None, None, None, None) == -1
