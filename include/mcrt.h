@@ -311,6 +311,58 @@ int mcrt_render_aov_device(mcrt_ctx* ctx, const mcrt_camera_desc* cam, uint32_t 
 int mcrt_render_aov(mcrt_ctx* ctx, const mcrt_camera_desc* cam, uint32_t global_seed, const mcrt_aov_buffers* buffers,
                     mcrt_stats* stats /* may be NULL */);
 
+/* ------------------------------------------------------------------------------------------
+ * Denoised output: the edge-avoiding a-trous wavelet filter of Dammertz et al. 2010 on a beauty frame, guided by the AOV frame
+ * of the same camera and seed (mcrt_render_aov*). The reference has no such output. The filter uses only FP64 + - * /, compare
+ * and select, in the order written here, uncontracted: the result is a function of its inputs bit for bit, whatever the launch
+ * shape, tiling or stream, and no libm routine takes part.
+ *
+ * Inputs are FULL frames [height][width]...: the beauty frame c (FP64 RGB) and guides->shading_normal Ns, normal N, position P,
+ * coverage, albedo (depth, surface, material are not read). A frame gathered from shards is filtered after the gather: the
+ * filter reads neighbouring rows, so there is no shard form.
+ *   dot(a, b) = (a.x*b.x + a.y*b.y) + a.z*b.z, |a|^2 = dot(a, a);  max0(x) = x < 0 ? 0 : x (a NaN stays a NaN).
+ * Demodulate, per pixel and channel: a = albedo > albedo_floor ? albedo : 1.0, I_0 = c / a. With MCRT_DENOISE_NO_ALBEDO a = 1 and
+ * guides->albedo may be NULL.
+ * Iterate, for i = 0 .. iterations-1 with step s = 2^i and inv_c = 1.0 / (sc * sc), sc = sigma_color * 2^-i, sz2 = sigma_plane *
+ * sigma_plane (both computed once on the host):
+ *   a pixel p with coverage(p) == 0 keeps its value, I_{i+1}(p) = I_i(p). For every other p the taps q = p + s * (dx, dy) are
+ *   visited with dy = -2..2 as the outer and dx = -2..2 as the inner loop; taps outside the frame are skipped;
+ *   h = {1/16, 1/4, 3/8, 1/4, 1/16}.
+ *     the centre tap (dx = dy = 0) has weight w = 9/64 exactly (so the weight sum is never zero);
+ *     a tap with coverage(q) == 0 is skipped (weight 0: it contributes nothing);
+ *     every other tap has w = (((h[dy] * h[dx]) * w_n) * w_z) * w_c with
+ *       w_n = max0(dot(Ns_p, Ns_q)), then squared normal_power_log2 times (w_n = w_n * w_n)
+ *       D = P_q - P_p, dd = |D|^2, d = dot(N_p, D), x_z = dd == 0 ? 0 : (d * d) / (sz2 * dd), w_z = max0(1 - x_z), w_z = w_z * w_z
+ *         (scale-free: sine^2 of the angle between the offset and p's tangent plane, against sigma_plane)
+ *       e = |I_i(p) - I_i(q)|^2, den = |I_i(p)|^2 + |I_i(q)|^2, x_c = den == 0 ? 0 : (e / den) * inv_c, w_c = max0(1 - x_c),
+ *         w_c = w_c * w_c  (scale-free too; e <= 2 den, so sigma_color 2 gives w_c >= 1/4 in the first iteration)
+ *     sum_ch += w * I_i(q)_ch, wsum += w (both from 0.0, in tap order); I_{i+1}(p)_ch = sum_ch * (1.0 / wsum).
+ * Remodulate: out = I_n * a.
+ * NaN and Inf are not filtered out: a NaN or Inf in the beauty frame, in Ns, N or P reaches every pixel whose taps read it (through
+ * the sums, or through a NaN weight), and spreads with every iteration; a NaN coverage counts as covered; a NaN albedo counts as
+ * below the floor (a = 1).
+ * d_out_rgb may be d_rgb; intermediate frames live in scratch the context owns (128 B per pixel, kept between calls). The call is
+ * synchronous on the context's stream, needs no uploaded scene, and is refused (MCRT_ERR_INVALID) while a render is in flight,
+ * when a pointer it needs is NULL, when width * height is 0 or >= 2^32, or with more than 16 iterations.
+ * stats: kernel_ms (HIP events of the pass's own around its launches), total_ms, kernel_launches (1 + iterations).
+ * Option MCRT_DENOISE_FORM: "tile" (a workgroup stages a tile of one residue class of the step plus its halo in LDS), "plain" (one
+ * lane per pixel, taps from memory), unset = the measured choice per step; the forms run the same text and give the same bits. */
+#define MCRT_DENOISE_NO_ALBEDO 1u
+typedef struct mcrt_denoise_params {   /* NULL or a zero field = the default */
+    uint32_t iterations;         /* default 5; more than 16: MCRT_ERR_INVALID */
+    uint32_t normal_power_log2;  /* default 7 (exponent 128); more than 32: MCRT_ERR_INVALID */
+    double   sigma_color;        /* default 2.0 */
+    double   sigma_plane;        /* default 0.1 */
+    double   albedo_floor;       /* default 1e-3 */
+    uint32_t flags, reserved;    /* MCRT_DENOISE_NO_ALBEDO */
+} mcrt_denoise_params;
+int mcrt_denoise_device(mcrt_ctx* ctx, uint32_t width, uint32_t height, const double* d_rgb,
+                        const mcrt_aov_buffers* guides /* full-frame DEVICE pointers */, const mcrt_denoise_params* params,
+                        double* d_out_rgb, mcrt_stats* stats /* may be NULL */);
+/* Same with HOST pointers (out_rgb may be rgb). */
+int mcrt_denoise(mcrt_ctx* ctx, uint32_t width, uint32_t height, const double* rgb, const mcrt_aov_buffers* guides,
+                 const mcrt_denoise_params* params, double* out_rgb, mcrt_stats* stats /* may be NULL */);
+
 /* Photon emission pass on the GPU. Replaces the thread fan-out of
  * PhotonMapper::PhotonMapper (integrator/photon-mapper/photon-mapper.cpp:80-115: per emission
  * Sampler::initiate(light), setIndex(offset+i), light point + cosine direction, emitPhoton :225-277) for

@@ -166,6 +166,17 @@ AOV_CHANNELS = {"depth": (np.float64, 1), "position": (np.float64, 3), "normal":
                 "albedo": (np.float64, 3), "coverage": (np.float64, 1), "surface": (np.uint32, 1), "material": (np.uint32, 1)}
 
 
+class DenoiseParams(C.Structure):
+    """mcrt_denoise_params: a zero field = the default (include/mcrt.h)."""
+    _fields_ = [("iterations", C.c_uint32), ("normal_power_log2", C.c_uint32), ("sigma_color", C.c_double), ("sigma_plane", C.c_double),
+                ("albedo_floor", C.c_double), ("flags", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+DENOISE_NO_ALBEDO = 1
+# the guide channels mcrt_denoise reads (albedo not with DENOISE_NO_ALBEDO)
+DENOISE_GUIDES = ("shading_normal", "normal", "position", "coverage", "albedo")
+
+
 class PhotonEmissionDevice(C.Structure):
     _fields_ = [("global_count", C.c_uint64), ("caustic_count", C.c_uint64), ("d_global_photons", C.c_void_p), ("d_caustic_photons", C.c_void_p),
                 ("emission_paths", C.c_uint64), ("rays", C.c_uint64), ("kernel_ms", C.c_double)]
@@ -254,6 +265,9 @@ def lib():
         L.mcrt_intersect_device.argtypes = [vp, C.c_uint64, vp, vp, vp, vp, vp]
         L.mcrt_render_aov.argtypes = [vp, C.POINTER(CameraDesc), C.c_uint32, C.POINTER(AovBuffers), C.POINTER(Stats)]
         L.mcrt_render_aov_device.argtypes = [vp, C.POINTER(CameraDesc), C.c_uint32, C.POINTER(AovBuffers), C.POINTER(Stats)]
+    if hasattr(L, "mcrt_denoise"):  # (likewise)
+        L.mcrt_denoise.argtypes = [vp, C.c_uint32, C.c_uint32, vp, C.POINTER(AovBuffers), C.POINTER(DenoiseParams), vp, C.POINTER(Stats)]
+        L.mcrt_denoise_device.argtypes = [vp, C.c_uint32, C.c_uint32, vp, C.POINTER(AovBuffers), C.POINTER(DenoiseParams), vp, C.POINTER(Stats)]
     L.mcrt_sampler.argtypes = [vp, C.c_uint64, _u32p, _u32p, C.c_uint32, C.c_uint32, _dp]
     L.mcrt_knn.argtypes = [vp, C.c_int, C.c_uint64, _dp, C.c_uint32, _u32p, _u32p, _dp]
     L.mcrt_bsdf.argtypes = [vp, C.c_uint64, _dp, _dp, _dp]
@@ -693,6 +707,45 @@ class Context:
             setattr(bufs, name, int(ptr))
         st = Stats()
         self._check(self._lib.mcrt_render_aov_device(self._h, C.byref(cam), int(global_seed), C.byref(bufs), C.byref(st)), "mcrt_render_aov_device")
+        return st.as_dict()
+
+    def denoise(self, rgb, aov, stats=None, **params):
+        """mcrt_denoise: the edge-avoiding a-trous filter on the beauty frame rgb [H,W,3], guided by aov - render_aov's dict of the same
+        camera and seed (shading_normal, normal, position, coverage, albedo are read) -> the filtered frame [H,W,3]. params: the fields
+        of mcrt_denoise_params (iterations, normal_power_log2, sigma_color, sigma_plane, albedo_floor, flags); left out = the default.
+        stats: a dict that receives mcrt_stats."""
+        self._sync_env()
+        rgb = np.ascontiguousarray(rgb, dtype=np.float64)
+        assert rgb.ndim == 3 and rgb.shape[2] == 3, rgb.shape
+        height, width = rgb.shape[:2]
+        par = DenoiseParams(**params)
+        bufs, keep = AovBuffers(), []
+        for name in DENOISE_GUIDES:
+            if name not in aov or aov[name] is None:
+                continue  # (the library names a channel it misses)
+            a = np.ascontiguousarray(aov[name], dtype=np.float64)
+            assert a.shape == (height, width) + ((3,) if AOV_CHANNELS[name][1] == 3 else ()), (name, a.shape)
+            keep.append(a)
+            setattr(bufs, name, a.ctypes.data)
+        out = np.empty_like(rgb)
+        st = Stats()
+        self._check(self._lib.mcrt_denoise(self._h, width, height, rgb.ctypes.data, C.byref(bufs), C.byref(par), out.ctypes.data, C.byref(st)), "mcrt_denoise")
+        if stats is not None:
+            stats.update(st.as_dict())
+        return out
+
+    def denoise_device(self, width, height, rgb_ptr, pointers, out_ptr, **params):
+        """mcrt_denoise_device: rgb_ptr / out_ptr (may be the same) and pointers = dict guide channel -> raw device pointer, all full
+        frames that are complete when this is called. Synchronous; returns the stats dict."""
+        self._sync_env()
+        bufs = AovBuffers()
+        for name, ptr in pointers.items():
+            assert name in AOV_CHANNELS, name
+            setattr(bufs, name, int(ptr) if ptr else None)
+        par = DenoiseParams(**params)
+        st = Stats()
+        self._check(self._lib.mcrt_denoise_device(self._h, int(width), int(height), C.c_void_p(int(rgb_ptr)) if rgb_ptr else None, C.byref(bufs), C.byref(par),
+                                                  C.c_void_p(int(out_ptr)) if out_ptr else None, C.byref(st)), "mcrt_denoise_device")
         return st.as_dict()
 
     def sampler(self, pixel, index, shuffles, global_seed):

@@ -23,6 +23,9 @@ RENDER_BIN = os.path.join(HOST, "mcrt_render")
 # set tests/golden/device_code_hashes.json lists; tests/test_aov_library.py holds what each library may contain.
 # libmcrt_aov.so has to lie next to libmcrt_hip.so wherever that goes (RUNPATH $ORIGIN).
 LIB_AOV = os.path.join(CSRC, "libmcrt_aov.so")
+# The a-trous filter's three kernels (csrc/mcrt_denoise.hip) likewise: a third code object, linked and found the same way;
+# tests/test_denoise_library.py holds what it contains.
+LIB_DENOISE = os.path.join(CSRC, "libmcrt_denoise.so")
 
 # -ffp-contract=off: the CPU reference is compiled by g++ for baseline x86-64 (no FMA contraction);
 # per-pixel FP64 parity needs the same rounding sequence on the GPU.
@@ -59,7 +62,7 @@ def sources():
 
 # the translation units that hold kernels of the render path: the tolerance library has its own objects of these
 KERNEL_TUS = ("mcrt_hip.hip", "mcrt_hip_lean.hip")
-TUS = ["mcrt_hip.hip", "mcrt_hip_lean.hip", "mcrt_octree_gpu.hip", "mcrt_sah_gpu.hip", "mcrt_output.hip", "mcrt_aov_host.hip", "mcrt_multi.hip", "mcrt_image.cpp", "mcrt_octree.cpp", "mcrt_bvh.cpp"]
+TUS = ["mcrt_hip.hip", "mcrt_hip_lean.hip", "mcrt_octree_gpu.hip", "mcrt_sah_gpu.hip", "mcrt_output.hip", "mcrt_aov_host.hip", "mcrt_denoise_host.hip", "mcrt_multi.hip", "mcrt_image.cpp", "mcrt_octree.cpp", "mcrt_bvh.cpp"]
 OBJ = os.path.join(CSRC, "_obj")
 
 
@@ -129,17 +132,17 @@ def build_lib(force=False, verbose=True, tolerance=False, both=False):
                 print("[build] a dependency changed during the compile: again", flush=True)
         raise RuntimeError("sources kept changing while %s was being compiled" % cmd[-3])
 
-    aov_src, aov_dep = os.path.join(CSRC, "mcrt_aov.hip"), os.path.join(OBJ, "libmcrt_aov.d")
-    aov_stale = force or not os.path.exists(LIB_AOV) or _stale(LIB_AOV, aov_dep)
-    if aov_stale:
-        jobs.append([_hipcc()] + HIPCC_FLAGS + ["-MD", "-MF", aov_dep, aov_src, "-o", LIB_AOV])
+    for side_lib, side_src in ((LIB_AOV, "mcrt_aov.hip"), (LIB_DENOISE, "mcrt_denoise.hip")):  # one translation unit each, compiled and linked in one step
+        side_dep = os.path.join(OBJ, os.path.basename(side_lib)[:-3] + ".d")
+        if force or not os.path.exists(side_lib) or _stale(side_lib, side_dep):
+            jobs.append([_hipcc()] + HIPCC_FLAGS + ["-MD", "-MF", side_dep, os.path.join(CSRC, side_src), "-o", side_lib])
     if jobs:
         with ThreadPoolExecutor(max_workers=min(len(jobs), os.cpu_count() or 4)) as ex:
             list(ex.map(run, jobs))
     for tol in variants:
         lib, objs = (LIB_TOL if tol else LIB), _objects(tol)
         if jobs or not os.path.exists(lib) or any(os.path.getmtime(o) > os.path.getmtime(lib) for o in objs):
-            run([_hipcc(), "--offload-arch=gfx950", "-shared", "-fPIC", "-o", lib] + objs + ["-L" + CSRC, "-lmcrt_aov", "-Wl,-rpath,$ORIGIN"])
+            run([_hipcc(), "--offload-arch=gfx950", "-shared", "-fPIC", "-o", lib] + objs + ["-L" + CSRC, "-lmcrt_aov", "-lmcrt_denoise", "-Wl,-rpath,$ORIGIN"])
     return LIB_TOL if tolerance and not both else LIB
 
 

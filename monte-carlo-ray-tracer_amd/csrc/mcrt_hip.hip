@@ -121,6 +121,7 @@ struct mcrt_ctx {
     // on demand, so that a host that only wants traversal or k-NN does not pay five hipMalloc / hipFree pairs per call
     DevBuf op_buf[6];
     DevBuf aov_buf[mcrt::kAovScratchBufs];  // the first-hit AOV pass's rays, hits and host-call channels (mcrt_aov_host.hip), grown on demand too
+    DevBuf denoise_buf[mcrt::kDenoiseScratchBufs];  // the a-trous filter's packed guides, two irradiance frames and host-call staging (mcrt_denoise_host.hip)
     std::map<std::string, std::string> options;  // mcrt_set_option; seeded from the MCRT_* environment variables at mcrt_create
     DevBuf pm_iors;  // refraction histories of the 1024-lane photon-mapping kernel
     // the frame in flight, kept so that mcrt_render_finish can run it again through the wavefront pipeline (deep refraction histories)
@@ -1730,5 +1731,19 @@ void* ctxAovScratch(mcrt_ctx* ctx, int which, size_t bytes) {
         return nullptr;
     }
     return ctx->aov_buf[which].p;
+}
+
+int ctxDenoiseReady(mcrt_ctx* ctx, const char* what) {
+    if (ctx->pending) return fail(ctx, MCRT_ERR_INVALID, std::string(what) + ": a render is in flight, call mcrt_render_finish first");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    return MCRT_OK;
+}
+void* ctxDenoiseScratch(mcrt_ctx* ctx, int which, size_t bytes) {
+    if (which < 0 || which >= kDenoiseScratchBufs) return nullptr;
+    if (ctx->denoise_buf[which].reserve(std::max<size_t>(bytes, 8)) != hipSuccess) {
+        (void)hipGetLastError();
+        return nullptr;
+    }
+    return ctx->denoise_buf[which].p;
 }
 }  // namespace mcrt

@@ -33,4 +33,9 @@ constexpr int kAovScratchBufs = 6;
 int ctxAovReady(mcrt_ctx* ctx, const char* what);
 void ctxAovScene(const mcrt_ctx* ctx, AovScene* out, const uint32_t** sobol_tab);
 void* ctxAovScratch(mcrt_ctx* ctx, int which, size_t bytes);
+// mcrt_denoise_host.hip (the a-trous filter's host side) likewise. ctxDenoiseReady: device selected, MCRT_ERR_INVALID (render in flight)
+// recorded under `what`; no scene is needed. ctxDenoiseScratch: buffer `which` (0..kDenoiseScratchBufs-1) of the filter's scratch.
+constexpr int kDenoiseScratchBufs = 4;
+int ctxDenoiseReady(mcrt_ctx* ctx, const char* what);
+void* ctxDenoiseScratch(mcrt_ctx* ctx, int which, size_t bytes);
 }  // namespace mcrt

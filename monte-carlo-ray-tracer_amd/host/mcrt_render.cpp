@@ -4,12 +4,16 @@
 //
 //   mcrt_render scene.mcrt out.f64 [--width W --height H --sqrtspp S] [--seed N] [--photon] [--device D | --devices D0,D1,...]
 //               [--tga out.tga [--tonemapper hable|aces] [--exposure EV] [--gain EV] [--plain]] [--aov PREFIX]
+//               [--denoise OUT.f64 [--denoise-iterations N]]
 //
 // Writes the frame as raw FP64 RGB, row-major (what Image::operator() holds, camera/image.cpp:53-56),
 // and prints the statistics. --tga also develops it the way Image::save does (auto exposure / gain, tone map, sRGB bytes:
 // mcrt_tonemap) and writes the reference's .tga; the "image" options default to the ones stored in the scene image.
 // --aov also writes the first-hit AOV frame of the same camera and seed (mcrt_render_aov, device 0): PREFIX.depth.f64, .position.f64,
 // .normal.f64, .shading_normal.f64, .albedo.f64, .coverage.f64 (raw FP64, row-major) and PREFIX.surface.u32, .material.u32.
+// --denoise also writes the frame filtered by mcrt_denoise (the edge-avoiding a-trous filter guided by that AOV frame; default parameters,
+// --denoise-iterations N sets the one that sizes the footprint) as raw FP64 RGB, and with --tga develops the filtered frame too, to OUT's
+// stem + ".tga".
 // --devices renders the frame on several GPUs from this one process (mcrt_render_multi: one host thread per GPU).
 #include <cstdio>
 #include <cstdlib>
@@ -38,7 +42,8 @@ int main(int argc, char** argv) {
     image.plain = (uint32_t)mcrt_image_param(img, "image_plain");
     image.exposure_compensation = from_bits(mcrt_image_param(img, "image_exposure_ev_bits"));
     image.gain_compensation = from_bits(mcrt_image_param(img, "image_gain_ev_bits"));
-    std::string tga, aov;
+    std::string tga, aov, denoise;
+    mcrt_denoise_params dparams{};
     std::vector<int> devices;
     for (int i = 3; i < argc; i++) {
         std::string k = argv[i];
@@ -57,6 +62,8 @@ int main(int argc, char** argv) {
         else if (k == "--photon") photon = 1;
         else if (k == "--tga" && i + 1 < argc) tga = argv[++i];
         else if (k == "--aov" && i + 1 < argc) aov = argv[++i];
+        else if (k == "--denoise" && i + 1 < argc) denoise = argv[++i];
+        else if (k == "--denoise-iterations") dparams.iterations = (uint32_t)val();
         else if (k == "--tonemapper" && i + 1 < argc) image.tonemapper = (argv[++i][0] | 0x20) == 'a' ? MCRT_TONEMAP_ACES : MCRT_TONEMAP_HABLE;
         else if (k == "--exposure" && i + 1 < argc) image.exposure_compensation = std::strtod(argv[++i], nullptr);
         else if (k == "--gain" && i + 1 < argc) image.gain_compensation = std::strtod(argv[++i], nullptr);
@@ -95,28 +102,29 @@ int main(int argc, char** argv) {
         return 1;
     }
     std::fclose(f);
-    if (!tga.empty()) {
+    auto develop = [&](const std::vector<double>& frame, const std::string& path) {
         image.width = cam.width;
         image.height = cam.height;
         std::vector<uint8_t> bgr((size_t)cam.width * cam.height * 3);
         double factors[2];
-        rc = mcrt_tonemap(ctx, rgb.data(), &image, bgr.data(), factors);
-        if (rc == MCRT_OK) rc = mcrt_tga_save(tga.c_str(), cam.width, cam.height, bgr.data());
-        if (rc != MCRT_OK) {
-            std::fprintf(stderr, "mcrt error %d writing %s: %s\n", rc, tga.c_str(), mcrt_last_error(ctx));
-            return 1;
+        int r = mcrt_tonemap(ctx, frame.data(), &image, bgr.data(), factors);
+        if (r == MCRT_OK) r = mcrt_tga_save(path.c_str(), cam.width, cam.height, bgr.data());
+        if (r != MCRT_OK) {
+            std::fprintf(stderr, "mcrt error %d writing %s: %s\n", r, path.c_str(), mcrt_last_error(ctx));
+            return false;
         }
-        std::printf("{\"tga\":\"%s\",\"exposure_factor\":%.17g,\"gain_factor\":%.17g}\n", tga.c_str(), factors[0], factors[1]);
-    }
-    if (!aov.empty()) {
+        std::printf("{\"tga\":\"%s\",\"exposure_factor\":%.17g,\"gain_factor\":%.17g}\n", path.c_str(), factors[0], factors[1]);
+        return true;
+    };
+    if (!tga.empty() && !develop(rgb, tga)) return 1;
+    if (!aov.empty() || !denoise.empty()) {
         const size_t px = (size_t)cam.width * cam.height;
         std::vector<double> depth(px), position(px * 3), normal(px * 3), shading_normal(px * 3), albedo(px * 3), coverage(px);
         std::vector<uint32_t> surface(px), material(px);
         const mcrt_aov_buffers b{depth.data(), position.data(), normal.data(), shading_normal.data(), albedo.data(), coverage.data(), surface.data(), material.data()};
         mcrt_stats ast;
         rc = mcrt_render_aov(ctx, &cam, seed, &b, &ast);
-        auto dump = [&](const char* name, const void* data, size_t bytes) {
-            const std::string path = aov + "." + name;
+        auto dump = [&](const std::string& path, const void* data, size_t bytes) {
             FILE* o = std::fopen(path.c_str(), "wb");
             const bool ok = o && std::fwrite(data, 1, bytes, o) == bytes;
             if (o) std::fclose(o);
@@ -127,12 +135,32 @@ int main(int argc, char** argv) {
             std::fprintf(stderr, "mcrt error %d: %s\n", rc, mcrt_last_error(ctx));
             return 1;
         }
-        if (!(dump("depth.f64", depth.data(), px * 8) && dump("position.f64", position.data(), px * 24) && dump("normal.f64", normal.data(), px * 24) &&
-              dump("shading_normal.f64", shading_normal.data(), px * 24) && dump("albedo.f64", albedo.data(), px * 24) &&
-              dump("coverage.f64", coverage.data(), px * 8) && dump("surface.u32", surface.data(), px * 4) && dump("material.u32", material.data(), px * 4)))
-            return 1;
-        std::printf("{\"aov\":\"%s\",\"rays\":%llu,\"kernel_ms\":%.3f,\"total_ms\":%.3f,\"Mray_s\":%.1f}\n", aov.c_str(), (unsigned long long)ast.rays,
-                    ast.kernel_ms, ast.total_ms, ast.rays / ast.kernel_ms / 1e3);
+        if (!aov.empty()) {
+            if (!(dump(aov + ".depth.f64", depth.data(), px * 8) && dump(aov + ".position.f64", position.data(), px * 24) &&
+                  dump(aov + ".normal.f64", normal.data(), px * 24) && dump(aov + ".shading_normal.f64", shading_normal.data(), px * 24) &&
+                  dump(aov + ".albedo.f64", albedo.data(), px * 24) && dump(aov + ".coverage.f64", coverage.data(), px * 8) &&
+                  dump(aov + ".surface.u32", surface.data(), px * 4) && dump(aov + ".material.u32", material.data(), px * 4)))
+                return 1;
+            std::printf("{\"aov\":\"%s\",\"rays\":%llu,\"kernel_ms\":%.3f,\"total_ms\":%.3f,\"Mray_s\":%.1f}\n", aov.c_str(), (unsigned long long)ast.rays,
+                        ast.kernel_ms, ast.total_ms, ast.rays / ast.kernel_ms / 1e3);
+        }
+        if (!denoise.empty()) {
+            std::vector<double> filtered(px * 3);
+            mcrt_stats dst;
+            rc = mcrt_denoise(ctx, cam.width, cam.height, rgb.data(), &b, &dparams, filtered.data(), &dst);
+            if (rc != MCRT_OK) {
+                std::fprintf(stderr, "mcrt error %d: %s\n", rc, mcrt_last_error(ctx));
+                return 1;
+            }
+            if (!dump(denoise, filtered.data(), px * 24)) return 1;
+            std::printf("{\"denoise\":\"%s\",\"kernel_launches\":%u,\"kernel_ms\":%.3f,\"total_ms\":%.3f}\n", denoise.c_str(), dst.kernel_launches,
+                        dst.kernel_ms, dst.total_ms);
+            if (!tga.empty()) {
+                const size_t dot = denoise.find_last_of('.'), slash = denoise.find_last_of('/');
+                const bool has_ext = dot != std::string::npos && (slash == std::string::npos || dot > slash);
+                if (!develop(filtered, (has_ext ? denoise.substr(0, dot) : denoise) + ".tga")) return 1;
+            }
+        }
     }
     std::printf("{\"width\":%u,\"height\":%u,\"spp\":%u,\"paths\":%llu,\"rays\":%llu,\"kernel_ms\":%.3f,\"total_ms\":%.3f,\"Mray_s\":%.1f}\n",
                 cam.width, cam.height, cam.sqrtspp * cam.sqrtspp, (unsigned long long)st.paths, (unsigned long long)st.rays,

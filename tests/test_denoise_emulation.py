@@ -1,0 +1,283 @@
+"""Denoised output (mcrt_denoise*), CPU tier: csrc/mcrt_denoise.hpp - the text the three kernels of csrc/mcrt_denoise.hip run - driven on
+the host (tests/emu/denoise_emu.cpp: the plain form as a loop, the tile form on wave_emu.hpp's emulated workgroup with its barrier)
+against the formulas of include/mcrt.h ("Denoised output") written out HERE in numpy, tap by tap in the stated order.
+
+Bound: assert_array_equal. Derived, not measured: both sides execute the same IEEE-754 double operations (+ - * /, compare, select) in
+the same order, none of them a libm call, neither side contracted (the harness is built with -ffp-contract=off, numpy's ufuncs are
+one operation each) - so every bit agrees, NaNs included."""
+import ctypes as C
+import functools
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+import test_aov_emulation as aov
+from conftest import ROOT, TESTS
+
+NO_ALBEDO = 1
+GUIDES = ("shading_normal", "normal", "position", "coverage", "albedo")
+# explicit parameters everywhere (not the defaults: retuning those must not touch a test)
+PARAMS = dict(normal_power_log2=5, sigma_color=1.5, sigma_plane=0.25, albedo_floor=0.01)
+
+
+def load_denoise_emu():
+    src = os.path.join(TESTS, "emu", "denoise_emu.cpp")
+    out = os.path.join(TESTS, "emu", "_build", "libdenoise_emu.so")
+    csrc = os.path.join(ROOT, "monte-carlo-ray-tracer_amd", "csrc")
+    deps = [src, os.path.join(TESTS, "emu", "wave_emu.hpp"), os.path.join(csrc, "mcrt_denoise.hpp"), os.path.join(csrc, "mcrt_math.hpp"),
+            os.path.join(ROOT, "include", "mcrt.h")]
+    if not os.path.exists(out) or any(os.path.getmtime(d) > os.path.getmtime(out) for d in deps):
+        os.makedirs(os.path.dirname(out), exist_ok=True)
+        tmp = "%s.%d.tmp" % (out, os.getpid())
+        subprocess.check_call(["g++", "-std=c++17", "-O2", "-ffp-contract=off", "-fPIC", "-shared", "-o", tmp, src])
+        os.replace(tmp, out)
+    L = C.CDLL(out)
+    vp = C.c_void_p
+    L.denoise_emu.argtypes = [C.c_uint32, C.c_uint32, vp, vp, vp, C.c_int, vp]
+    L.denoise_emu_tile_blocks.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32]
+    L.denoise_emu_tile_blocks.restype = C.c_uint64
+    return L
+
+
+@functools.lru_cache(maxsize=None)
+def _emu():
+    return load_denoise_emu()
+
+
+def _pkg():
+    import importlib
+    return importlib.import_module("monte-carlo-ray-tracer_amd")
+
+
+def emu_denoise(rgb, guides, form, flags=0, **params):
+    """The emulation's filtered frame. form: "plain" or "tile". guides: dict channel -> array (albedo may be missing with NO_ALBEDO)."""
+    pkg = _pkg()
+    rgb = np.ascontiguousarray(rgb, dtype=np.float64)
+    height, width = rgb.shape[:2]
+    bufs, keep = pkg.AovBuffers(), []
+    for k in GUIDES:
+        if guides.get(k) is not None:
+            keep.append(np.ascontiguousarray(guides[k], dtype=np.float64))
+            setattr(bufs, k, keep[-1].ctypes.data)
+    par = pkg.DenoiseParams(flags=flags, **params)
+    out = np.full_like(rgb, -7.0)
+    rc = _emu().denoise_emu(width, height, rgb.ctypes.data, C.byref(bufs), C.byref(par), {"plain": 0, "tile": 1}[form], out.ctypes.data)
+    assert rc == 0, "denoise_emu: %d" % rc
+    return out
+
+
+def _dot(a, b):
+    return (a[..., 0] * b[..., 0] + a[..., 1] * b[..., 1]) + a[..., 2] * b[..., 2]
+
+
+def _max0(x):
+    return np.where(x < 0.0, 0.0, x)
+
+
+def numpy_denoise(rgb, guides, iterations, normal_power_log2, sigma_color, sigma_plane, albedo_floor, flags=0):
+    """include/mcrt.h's "Denoised output" in numpy: whole-frame arrays per tap, the taps accumulated one by one, dy outer, dx inner."""
+    H, W = rgb.shape[:2]
+    Ns, N, P, cov = (np.asarray(guides[k], dtype=np.float64) for k in ("shading_normal", "normal", "position", "coverage"))
+    a = np.ones_like(rgb) if flags & NO_ALBEDO else np.where(guides["albedo"] > albedo_floor, guides["albedo"], 1.0)
+    h = (1.0 / 16.0, 1.0 / 4.0, 3.0 / 8.0, 1.0 / 4.0, 1.0 / 16.0)
+    sz2 = sigma_plane * sigma_plane
+    with np.errstate(all="ignore"):
+        I = rgb / a
+        for i in range(iterations):
+            s = 1 << i
+            sc = sigma_color * 2.0 ** -i
+            inv_c = 1.0 / (sc * sc)
+            total, wsum = np.zeros((H, W, 3)), np.zeros((H, W))
+            for dy in range(-2, 3):
+                for dx in range(-2, 3):
+                    y0, y1, x0, x1 = max(0, -s * dy), min(H, H - s * dy), max(0, -s * dx), min(W, W - s * dx)  # the p whose tap is inside the frame
+                    if y0 >= y1 or x0 >= x1:
+                        continue
+                    p, q = (slice(y0, y1), slice(x0, x1)), (slice(y0 + s * dy, y1 + s * dy), slice(x0 + s * dx, x1 + s * dx))
+                    if dx == 0 and dy == 0:
+                        total[p] = total[p] + (9.0 / 64.0) * I[q]
+                        wsum[p] = wsum[p] + 9.0 / 64.0
+                        continue
+                    wn = _max0(_dot(Ns[p], Ns[q]))
+                    for _ in range(normal_power_log2):
+                        wn = wn * wn
+                    D = P[q] - P[p]
+                    dd, d = _dot(D, D), _dot(N[p], D)
+                    wz = _max0(1.0 - np.where(dd == 0.0, 0.0, (d * d) / (sz2 * dd)))
+                    wz = wz * wz
+                    di = I[p] - I[q]
+                    e, den = _dot(di, di), _dot(I[p], I[p]) + _dot(I[q], I[q])
+                    wc = _max0(1.0 - np.where(den == 0.0, 0.0, (e / den) * inv_c))
+                    wc = wc * wc
+                    w = (((h[dy + 2] * h[dx + 2]) * wn) * wz) * wc
+                    skipped = cov[q] == 0.0  # weight 0: contributes nothing (not even 0 * Inf)
+                    total[p] = np.where(skipped[..., None], total[p], total[p] + w[..., None] * I[q])
+                    wsum[p] = np.where(skipped, wsum[p], wsum[p] + w)
+            I = np.where((cov == 0.0)[..., None], I, total * (1.0 / wsum)[..., None])
+        return I * a
+
+
+# ---- guides from the AOV emulation, a synthetic beauty frame ---------------------------------------------------------------------------
+SCENES = ("hexagon_room_dof", "coffee_maker_qsah", "quadric")
+
+
+def synthetic_beauty(albedo, seed):
+    """albedo x (a smooth field + seeded noise), some pixels exactly zero."""
+    H, W = albedo.shape[:2]
+    rng = np.random.default_rng(seed)
+    y, x = np.mgrid[0:H, 0:W]
+    smooth = 0.6 + 0.4 * np.sin(x / 9.0)[..., None] * np.cos(y / 4.0)[..., None] * np.array([1.0, 0.8, 0.5])
+    light = smooth + rng.uniform(0.0, 1.5, size=(H, W, 3)) * (rng.random((H, W, 1)) < 0.5)
+    rgb = np.maximum(albedo, 0.02) * light
+    rgb[rng.random((H, W)) < 0.04] = 0.0
+    return np.ascontiguousarray(rgb)
+
+
+@functools.lru_cache(maxsize=None)
+def scene_case(scene):
+    frame = aov.emu_frame(scene, 1)[0]
+    guides = {k: frame[k].reshape((aov.HEIGHT, aov.WIDTH) + frame[k].shape[1:]).copy() for k in GUIDES}
+    return guides, synthetic_beauty(guides["albedo"], 1234 + len(scene))
+
+
+@pytest.mark.parametrize("iterations", [1, 3, 5])
+@pytest.mark.parametrize("scene", SCENES)
+def test_emulation_is_the_numpy_restatement(scene, iterations):
+    """70 x 13: at 5 iterations the last step is 16 > 13 rows, so every vertical tap but the centre row's leaves the frame."""
+    guides, rgb = scene_case(scene)
+    want = numpy_denoise(rgb, guides, iterations, **PARAMS)
+    for form in ("plain", "tile"):
+        np.testing.assert_array_equal(emu_denoise(rgb, guides, form, iterations=iterations, **PARAMS), want, err_msg="%s %s" % (scene, form))
+    assert np.isfinite(want).all() and not np.array_equal(want, rgb)
+
+
+def test_the_scenes_bring_what_they_are_here_for():
+    assert (scene_case("quadric")[0]["coverage"] == 0).any() and (scene_case("quadric")[0]["coverage"] == 1).any()
+    g = scene_case("coffee_maker_qsah")[0]
+    assert not np.array_equal(g["normal"], g["shading_normal"])
+    assert all((scene_case(s)[1] == 0).all(axis=2).any() for s in SCENES)
+
+
+# ---- hand-made frames ------------------------------------------------------------------------------------------------------------------
+def hand_made(width, height, seed=7):
+    """A wavy height field seen from above with noisy normals; a rectangle without coverage (albedo 0 there, as the AOV pass gives it); one
+    pixel whose shading normal is so short that Ns . Ns underflows to 0; albedo below the floor in a stripe; exact zeros in the beauty frame.
+    -> guides, rgb, (rows, columns) of the rectangle, (y, x) of the short normal."""
+    rng = np.random.default_rng(seed)
+    y, x = np.mgrid[0:height, 0:width].astype(np.float64)
+    z = 0.3 * np.sin(x / 5.0) + 0.2 * np.cos(y / 3.0) + (x > width * 0.6) * 2.0
+    position = np.stack([x * 0.1, y * 0.1, z], axis=-1)
+    normal = np.stack([-0.6 * np.cos(x / 5.0), 0.6 * np.sin(y / 3.0), np.ones_like(x)], axis=-1)
+    normal /= np.sqrt((normal * normal).sum(axis=-1, keepdims=True))
+    shading = normal + rng.normal(0.0, 0.05, size=normal.shape)
+    albedo = rng.uniform(0.2, 0.9, size=(height, width, 3))
+    albedo[:, width // 3] = 0.004  # below PARAMS' floor of 0.01, above the default's
+    coverage = np.where(rng.random((height, width)) < 0.1, 0.75, 1.0)
+    rows, cols = slice(height // 4, max(height // 4 + 1, height // 2)), slice(width // 2, max(width // 2 + 1, width // 2 + 9))
+    if width * height > 1:
+        coverage[rows, cols] = 0.0
+        albedo[rows, cols] = 0.0
+    tiny = (height - 1, 0)
+    shading[tiny] = (1e-200, -1e-200, 1e-200)
+    rgb = albedo * (1.0 + rng.uniform(0.0, 2.0, size=(height, width, 3)) * (rng.random((height, width, 1)) < 0.5))
+    rgb[rows, cols] = rng.uniform(0.0, 5.0, size=rgb[rows, cols].shape)  # (what shows behind the scene: any values)
+    rgb[rng.random((height, width)) < 0.03] = 0.0
+    guides = dict(shading_normal=shading, normal=normal, position=position, coverage=coverage, albedo=albedo)
+    return {k: np.ascontiguousarray(v) for k, v in guides.items()}, np.ascontiguousarray(rgb), (rows, cols), tiny
+
+
+@pytest.mark.parametrize("flags", [0, NO_ALBEDO])
+@pytest.mark.parametrize("width,height", [(1, 1), (3, 2), (131, 67)])
+def test_hand_made_frames(width, height, flags):
+    """131 x 67: 9 x 5 tiles at step 1, both directions ragged (131 = 8 x 16 + 3, 67 = 4 x 16 + 3); 5 iterations reach step 16, where a
+    residue class is 9 x 5 pixels - one ragged tile each."""
+    guides, rgb, (rows, cols), tiny = hand_made(width, height)
+    if flags & NO_ALBEDO:
+        guides = dict(guides, albedo=None)
+    par = dict(PARAMS, iterations=5)
+    plain, tile = emu_denoise(rgb, guides, "plain", flags=flags, **par), emu_denoise(rgb, guides, "tile", flags=flags, **par)
+    np.testing.assert_array_equal(tile, plain)
+    np.testing.assert_array_equal(plain, numpy_denoise(rgb, guides, flags=flags, **par))
+    assert np.isfinite(plain).all()
+    if width * height == 1:
+        # only the centre tap: per iteration 9/64 I, 1 / (9/64) and their product round once each, demodulation and back once each:
+        # 5 x 3 + 2 = 17 half-ulps (2^-53 relative each) to first order, 18 with room for the second
+        np.testing.assert_allclose(plain, rgb, rtol=18 * 2.0 ** -53, atol=0)
+        return
+    # without coverage: the input's bits (c / 1 * 1), and nothing of it in the neighbours - any other values there, the same frame around
+    assert plain[rows, cols].tobytes() == rgb[rows, cols].tobytes()
+    other = rgb.copy()
+    other[rows, cols] = 1e30
+    again = emu_denoise(other, guides, "tile", flags=flags, **par)
+    outside = np.ones((height, width), dtype=bool)
+    outside[rows, cols] = False
+    np.testing.assert_array_equal(again[outside], plain[outside])
+    # the short normal: every w_n of this pixel is 0, the centre tap alone carries it (wsum = 9/64) - its own value back, to rounding
+    a = 1.0 if flags & NO_ALBEDO else np.where(guides["albedo"][tiny] > par["albedo_floor"], guides["albedo"][tiny], 1.0)
+    one = emu_denoise(rgb, guides, "plain", flags=flags, **dict(par, iterations=1))
+    np.testing.assert_allclose(one[tiny], rgb[tiny], rtol=6 * 2.0 ** -53, atol=0)  # (1 x 3 + 2 half-ulps, as above)
+    assert np.isfinite(one[tiny] / a).all()
+
+
+def test_albedo_below_the_floor_counts_as_one():
+    """The stripe of albedo 0.004: with the floor at 0.01 the filter works on c itself there, with the floor at 0.001 on c / 0.004."""
+    guides, rgb, _, _ = hand_made(31, 9)
+    stripe = 31 // 3
+    hi = emu_denoise(rgb, guides, "tile", iterations=2, **PARAMS)
+    lo = emu_denoise(rgb, guides, "tile", iterations=2, **dict(PARAMS, albedo_floor=0.001))
+    np.testing.assert_array_equal(lo, numpy_denoise(rgb, guides, 2, **dict(PARAMS, albedo_floor=0.001)))
+    assert not np.array_equal(hi[:, stripe], lo[:, stripe])
+    flat = dict(guides, albedo=np.where(guides["albedo"] > 0.01, guides["albedo"], 1.0))
+    np.testing.assert_array_equal(emu_denoise(rgb, flat, "plain", iterations=2, **PARAMS), hi)
+
+
+def test_nan_and_inf_propagate():
+    """Nothing is filtered out: a NaN in the beauty frame reaches exactly the pixels whose taps read it (5 x 5 at one iteration)."""
+    guides, rgb, _, _ = hand_made(20, 11, seed=3)
+    guides["coverage"][:] = 1.0
+    rgb[5, 9, 1] = np.nan
+    rgb[0, 0, 0] = np.inf
+    want = numpy_denoise(rgb, guides, 1, **PARAMS)
+    for form in ("plain", "tile"):
+        np.testing.assert_array_equal(emu_denoise(rgb, guides, form, iterations=1, **PARAMS), want)
+    bad = np.isnan(want).any(axis=2)
+    assert bad[3:8, 7:12].all() and not bad[:, 12:].any() and not bad[8:, 3:].any()
+    assert not np.isfinite(want[0, 0]).all()
+
+
+def test_defaults_and_refusals_of_the_settings():
+    """A zero field is the default (5, 7, 2.0, 0.1, 1e-3); more than 16 iterations, more than 32 squarings and missing frames are refused."""
+    pkg = _pkg()
+    guides, rgb, _, _ = hand_made(9, 7)
+    np.testing.assert_array_equal(emu_denoise(rgb, guides, "tile"),
+                                  numpy_denoise(rgb, guides, 5, normal_power_log2=7, sigma_color=2.0, sigma_plane=0.1, albedo_floor=1e-3))
+    bufs = pkg.AovBuffers()
+    keep = {k: np.ascontiguousarray(v) for k, v in guides.items()}
+    for k, v in keep.items():
+        setattr(bufs, k, v.ctypes.data)
+    out = np.empty_like(rgb)
+    run = lambda w, h, b, par: _emu().denoise_emu(w, h, rgb.ctypes.data, C.byref(b), C.byref(par), 1, out.ctypes.data)
+    assert run(9, 7, bufs, pkg.DenoiseParams(iterations=16)) == 0
+    assert run(9, 7, bufs, pkg.DenoiseParams(iterations=17)) == -1
+    assert run(9, 7, bufs, pkg.DenoiseParams(normal_power_log2=33)) == -1
+    assert run(0, 7, bufs, pkg.DenoiseParams()) == -1
+    bufs.position = None
+    assert run(9, 7, bufs, pkg.DenoiseParams()) == -1
+
+
+def test_tile_grid_covers_every_residue_class():
+    L = _emu()
+    assert L.denoise_emu_tile_blocks(131, 67, 1) == 9 * 5
+    assert L.denoise_emu_tile_blocks(131, 67, 16) == 16 * 16
+    assert L.denoise_emu_tile_blocks(70, 13, 16) == 16 * 13  # 13 rows: 13 classes of one row each
+    assert L.denoise_emu_tile_blocks(1920, 1080, 4) == 4 * 30 * 4 * 17
+
+
+def test_null_context_is_refused(pkg):
+    L = pkg.lib()
+    bufs, par = pkg.AovBuffers(), pkg.DenoiseParams()
+    assert L.mcrt_denoise(None, 1, 1, None, C.byref(bufs), C.byref(par), None, None) == -1      # MCRT_ERR_INVALID
+    assert L.mcrt_denoise_device(None, 1, 1, None, C.byref(bufs), C.byref(par), None, None) == -1
+    assert C.sizeof(pkg.DenoiseParams) == 40

@@ -1,0 +1,111 @@
+#!/usr/bin/env python3
+"""The a-trous filter (mcrt_denoise_device) measured: its time next to the beauty frame and the AOV pass of the same camera, and what
+it does to the error of a low-sample frame.
+
+  python tools/denoise_probe.py [--width 1920 --height 1080 --sqrtspp 4] [--runs 5] [--scenes hexagon_room]
+      Time: HIP-event milliseconds from mcrt_stats, one warm-up, then the median of --runs runs, for 1 .. iterations iterations in the
+      tile form, the plain form and the default choice; "step_ms" are the differences (the first includes the prep pass, the default
+      count's last one the remodulation). One JSON line per scene.
+
+  python tools/denoise_probe.py --errors [--width 192 --height 108] [--truth-sqrtspp 32] [--scenes a,b,...] [--grid]
+      Error: per scene and sqrtspp 1, 2, 4 the mean squared error (all channels, pixels with coverage > 0) of the unfiltered and of the
+      filtered frame (default parameters) against a render at --truth-sqrtspp with another seed. --grid adds a small grid of parameters.
+      One JSON line per (scene, sqrtspp)."""
+import argparse
+import importlib
+import itertools
+import json
+import os
+import statistics
+import sys
+
+ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
+sys.path.insert(0, ROOT)
+
+GUIDES = ("shading_normal", "normal", "position", "coverage", "albedo")
+GRID = dict(iterations=(3, 5), sigma_color=(1.0, 2.0, 4.0), sigma_plane=(0.1, 0.3), normal_power_log2=(5, 7))
+
+
+def setup(m, name, width, height, sqrtspp):
+    img = m.SceneImage(os.path.join(ROOT, "tests", "golden", name + ".mcrt"))
+    cam = img.camera
+    cam.width, cam.height, cam.sqrtspp = width, height, sqrtspp
+    cam.shard_index, cam.shard_count = 0, 1
+    ctx = m.Context(0)
+    ctx.upload_scene(img.scene)
+    return img, cam, ctx
+
+
+def timing(m, args):
+    import torch
+    for name in args.scenes.split(","):
+        img, cam, ctx = setup(m, name, args.width, args.height, args.sqrtspp)
+        bufs = {k: torch.empty((cam.height, cam.width) + ((3,) if m.AOV_CHANNELS[k][1] == 3 else ()), dtype=torch.float64, device="cuda:0") for k in GUIDES}
+        rgb = torch.empty((cam.height, cam.width, 3), dtype=torch.float64, device="cuda:0")
+        out = torch.empty_like(rgb)
+        torch.cuda.synchronize()
+        ptrs = {k: v.data_ptr() for k, v in bufs.items()}
+        for _ in range(2):  # warm-up, then the ones that count
+            aov = ctx.render_aov_device(cam, args.seed, ptrs)
+            ctx.render_device(cam, args.seed, m.INTEGRATOR_PATH_TRACER, rgb.data_ptr())
+            beauty = ctx.render_finish()
+        rec = {"scene": name, "width": cam.width, "height": cam.height, "spp": cam.sqrtspp ** 2, "beauty_ms": round(beauty["kernel_ms"], 3),
+               "aov_ms": round(aov["kernel_ms"], 3), "pixels": cam.width * cam.height}
+        for form in ("tile", "plain", None):
+            ctx.set_option("MCRT_DENOISE_FORM", form)
+            total = []
+            for n in range(1, args.iterations + 1):
+                ctx.denoise_device(cam.width, cam.height, rgb.data_ptr(), ptrs, out.data_ptr(), iterations=n)
+                runs = [ctx.denoise_device(cam.width, cam.height, rgb.data_ptr(), ptrs, out.data_ptr(), iterations=n)["kernel_ms"] for _ in range(max(args.runs, 1))]
+                total.append(statistics.median(runs))
+            rec[form or "default"] = {"total_ms": [round(t, 4) for t in total], "step_ms": [round(b - a, 4) for a, b in zip([0.0] + total, total)]}
+        print(json.dumps(rec), flush=True)
+        ctx.close()
+        img.close()
+
+
+def errors(m, args):
+    import numpy as np
+    combos = [dict(zip(GRID, v)) for v in itertools.product(*GRID.values())] if args.grid else []
+    for name in args.scenes.split(","):
+        img, cam, ctx = setup(m, name, args.width, args.height, args.truth_sqrtspp)
+        truth, _ = ctx.sample_image(cam, args.seed ^ 0x00ABCDEF, m.INTEGRATOR_PATH_TRACER)
+        for sqrtspp in (1, 2, 4):
+            cam.sqrtspp = sqrtspp
+            noisy, _ = ctx.sample_image(cam, args.seed, m.INTEGRATOR_PATH_TRACER)
+            guides = ctx.render_aov(cam, args.seed, channels=GUIDES)
+            covered = guides["coverage"] > 0
+            mse = lambda frame: float(((frame - truth)[covered] ** 2).mean())
+            before, after = mse(noisy), mse(ctx.denoise(noisy, guides))
+            rec = {"scene": name, "width": cam.width, "height": cam.height, "spp": sqrtspp ** 2, "truth_spp": args.truth_sqrtspp ** 2,
+                   "mse_unfiltered": before, "mse_filtered": after, "ratio": round(after / before, 4)}
+            if combos:
+                rec["grid"] = [[c["iterations"], c["sigma_color"], c["sigma_plane"], c["normal_power_log2"], round(mse(ctx.denoise(noisy, guides, **c)) / before, 4)]
+                               for c in combos]
+            print(json.dumps(rec), flush=True)
+        ctx.close()
+        img.close()
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--errors", action="store_true")
+    ap.add_argument("--grid", action="store_true")
+    ap.add_argument("--width", type=int)
+    ap.add_argument("--height", type=int)
+    ap.add_argument("--sqrtspp", type=int, default=4)
+    ap.add_argument("--truth-sqrtspp", type=int, default=32)
+    ap.add_argument("--iterations", type=int, default=5)
+    ap.add_argument("--runs", type=int, default=5)
+    ap.add_argument("--seed", type=int, default=0x12345678)
+    ap.add_argument("--scenes")
+    args = ap.parse_args()
+    args.width = args.width or (192 if args.errors else 1920)
+    args.height = args.height or (108 if args.errors else 1080)
+    args.scenes = args.scenes or ("hexagon_room_diffuse,hexagon_room,hexagon_room_ggx,coffee_maker_qsah" if args.errors else "hexagon_room")
+    m = importlib.import_module("monte-carlo-ray-tracer_amd")
+    (errors if args.errors else timing)(m, args)
+
+
+if __name__ == "__main__":
+    main()
