@@ -363,6 +363,58 @@ int mcrt_denoise_device(mcrt_ctx* ctx, uint32_t width, uint32_t height, const do
 int mcrt_denoise(mcrt_ctx* ctx, uint32_t width, uint32_t height, const double* rgb, const mcrt_aov_buffers* guides,
                  const mcrt_denoise_params* params, double* out_rgb, mcrt_stats* stats /* may be NULL */);
 
+/* ------------------------------------------------------------------------------------------
+ * Per-pixel sample statistics: the spread of a pixel's samples next to their mean - the sample variance and the two half-buffers
+ * (the means of the even and of the odd samples) that error estimators, stopping rules and denoisers start from. The reference
+ * has no such output. Every box-filter frame keeps the radiance of every sample until its pass is resolved; the statistics are
+ * a second reader of that store, whatever kernel form filled it. Only FP64 + - * /, compare and select, in the order written
+ * here, uncontracted, no libm routine: a function of the samples bit for bit.
+ *
+ * Per pixel and channel, with x_i the radiance of sample i (i = 0 .. n-1, n = sqrtspp^2):
+ *   S = (((0.0 + x_0) + x_1) + ...) in ascending i, m = S / (double)n     (the frame's own sum: the frame is max(m, 0))
+ *   Q = (((0.0 + (x_0 - m) * (x_0 - m)) + (x_1 - m) * (x_1 - m)) + ...) in ascending i
+ *   variance = n > 1 ? Q / (double)(n - 1) : 0.0         (two passes on purpose: one-pass formulas cancel on a firefly)
+ *   half_a   = (((0.0 + x_0) + x_2) + ...) / (double)((n + 1) / 2)                      (even i, ascending)
+ *   half_b   = n > 1 ? (((0.0 + x_1) + x_3) + ...) / (double)(n / 2) : 0.0              (odd i, ascending)
+ * None of them is clamped. NaN and Inf are not filtered: they reach the outputs of their own pixel and of no other.
+ *
+ * mcrt_render_pixel_stats_device renders the frame mcrt_render_device + mcrt_render_finish deliver - the same bits in d_out_rgb,
+ * the same kernel_id, cam->shard_* honoured the same way - and fills the channels of d_buffers that are not NULL, packed like
+ * d_out_rgb (the owned rows). The call is synchronous on the context's stream. kernel_launches counts one launch more per
+ * pass (MCRT_SAMPLE_STORE_GB) when a channel is wanted; the statistics do not depend on passes, shards, the kernel form of
+ * one integrator family or the launch shape. A frame that mcrt_render_finish renders again (nested media, a kNN overflow)
+ * delivers the statistics of the run it delivers. d_buffers NULL or all-NULL: a plain render.
+ * Refused: a camera whose film splats (a reconstruction filter, or a box of another radius) when a channel is wanted -
+ * MCRT_ERR_UNSUPPORTED, such frames keep no samples; a render in flight, no scene, d_out_rgb NULL as in mcrt_render_device. */
+typedef struct mcrt_pixel_stats_buffers {   /* every pointer may be NULL = not wanted; owned rows packed like d_out_rgb */
+    double* variance;   /* [rows][width][3] */
+    double* half_a;     /* [rows][width][3] */
+    double* half_b;     /* [rows][width][3] */
+} mcrt_pixel_stats_buffers;
+int mcrt_render_pixel_stats_device(mcrt_ctx* ctx, const mcrt_camera_desc* cam, uint32_t global_seed, int integrator,
+                                   double* d_out_rgb, const mcrt_pixel_stats_buffers* d_buffers, mcrt_stats* stats /* may be NULL */);
+/* Same with HOST pointers to FULL frames ([height][width][3]): rows this shard does not own are left untouched. */
+int mcrt_render_pixel_stats(mcrt_ctx* ctx, const mcrt_camera_desc* cam, uint32_t global_seed, int integrator, double* out_rgb,
+                            const mcrt_pixel_stats_buffers* buffers, mcrt_stats* stats /* may be NULL */);
+
+/* The frame summary a stopping rule reads. Per pixel p of `pixels`, from the frame rgb [pixels][3] and its variance [pixels][3]:
+ *   e_p = ((v_r + v_g) + v_b) / (double)spp          (the estimated variance of the pixel's mean, channels added)
+ *   g_p = (r * r + g * g) + b * b
+ * noise = treesum(e), signal = treesum(g), where treesum is fixed so that the result is a function of the input bit for bit:
+ *   the values are taken in blocks of 256 consecutive ones (the last one may be shorter: len values); inside a block, for
+ *   stride = 128, 64, ..., 1: t[k] = t[k] + t[k + stride] for every k < stride with k + stride < len; the block's value is t[0];
+ *   the block values are reduced the same way again until one is left.
+ * relative_error = signal > 0 ? sqrt(noise / signal) : 0, computed on the host. A NaN or Inf anywhere reaches noise or signal.
+ * The call needs no scene, is synchronous on the context's stream (device inputs must be complete when it is called), moves only
+ * the results across PCIe, and is refused (MCRT_ERR_INVALID) while a render is in flight, with a NULL pointer, pixels == 0 or
+ * >= 2^38, or spp == 0. A sharded frame is summarised after the gather. */
+typedef struct mcrt_frame_noise_result { double noise, signal, relative_error; uint64_t pixels; } mcrt_frame_noise_result;
+int mcrt_frame_noise_device(mcrt_ctx* ctx, uint64_t pixels, uint32_t spp, const double* d_rgb, const double* d_variance,
+                            mcrt_frame_noise_result* out);
+/* Same with HOST pointers. */
+int mcrt_frame_noise(mcrt_ctx* ctx, uint64_t pixels, uint32_t spp, const double* rgb, const double* variance,
+                     mcrt_frame_noise_result* out);
+
 /* Photon emission pass on the GPU. Replaces the thread fan-out of
  * PhotonMapper::PhotonMapper (integrator/photon-mapper/photon-mapper.cpp:80-115: per emission
  * Sampler::initiate(light), setIndex(offset+i), light point + cosine direction, emitPhoton :225-277) for

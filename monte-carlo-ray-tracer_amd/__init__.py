@@ -177,6 +177,22 @@ DENOISE_NO_ALBEDO = 1
 DENOISE_GUIDES = ("shading_normal", "normal", "position", "coverage", "albedo")
 
 
+class PixelStatsBuffers(C.Structure):
+    """mcrt_pixel_stats_buffers: a null pointer = channel not wanted."""
+    _fields_ = [("variance", C.c_void_p), ("half_a", C.c_void_p), ("half_b", C.c_void_p)]
+
+
+PIXEL_STATS_CHANNELS = ("variance", "half_a", "half_b")
+
+
+class FrameNoise(C.Structure):
+    """mcrt_frame_noise_result."""
+    _fields_ = [("noise", C.c_double), ("signal", C.c_double), ("relative_error", C.c_double), ("pixels", C.c_uint64)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 class PhotonEmissionDevice(C.Structure):
     _fields_ = [("global_count", C.c_uint64), ("caustic_count", C.c_uint64), ("d_global_photons", C.c_void_p), ("d_caustic_photons", C.c_void_p),
                 ("emission_paths", C.c_uint64), ("rays", C.c_uint64), ("kernel_ms", C.c_double)]
@@ -268,6 +284,11 @@ def lib():
     if hasattr(L, "mcrt_denoise"):  # (likewise)
         L.mcrt_denoise.argtypes = [vp, C.c_uint32, C.c_uint32, vp, C.POINTER(AovBuffers), C.POINTER(DenoiseParams), vp, C.POINTER(Stats)]
         L.mcrt_denoise_device.argtypes = [vp, C.c_uint32, C.c_uint32, vp, C.POINTER(AovBuffers), C.POINTER(DenoiseParams), vp, C.POINTER(Stats)]
+    if hasattr(L, "mcrt_render_pixel_stats"):  # (likewise)
+        L.mcrt_render_pixel_stats.argtypes = [vp, C.POINTER(CameraDesc), C.c_uint32, C.c_int, vp, C.POINTER(PixelStatsBuffers), C.POINTER(Stats)]
+        L.mcrt_render_pixel_stats_device.argtypes = [vp, C.POINTER(CameraDesc), C.c_uint32, C.c_int, vp, C.POINTER(PixelStatsBuffers), C.POINTER(Stats)]
+        L.mcrt_frame_noise.argtypes = [vp, C.c_uint64, C.c_uint32, vp, vp, C.POINTER(FrameNoise)]
+        L.mcrt_frame_noise_device.argtypes = [vp, C.c_uint64, C.c_uint32, vp, vp, C.POINTER(FrameNoise)]
     L.mcrt_sampler.argtypes = [vp, C.c_uint64, _u32p, _u32p, C.c_uint32, C.c_uint32, _dp]
     L.mcrt_knn.argtypes = [vp, C.c_int, C.c_uint64, _dp, C.c_uint32, _u32p, _u32p, _dp]
     L.mcrt_bsdf.argtypes = [vp, C.c_uint64, _dp, _dp, _dp]
@@ -747,6 +768,58 @@ class Context:
         self._check(self._lib.mcrt_denoise_device(self._h, int(width), int(height), C.c_void_p(int(rgb_ptr)) if rgb_ptr else None, C.byref(bufs), C.byref(par),
                                                   C.c_void_p(int(out_ptr)) if out_ptr else None, C.byref(st)), "mcrt_denoise_device")
         return st.as_dict()
+
+    def render_pixel_stats(self, cam, global_seed, integrator=INTEGRATOR_PATH_TRACER, channels=None, stats=None, out=None):
+        """mcrt_render_pixel_stats: the frame of sample_image plus the per-pixel sample statistics -> dict "rgb" and the channels wanted
+        (PIXEL_STATS_CHANNELS; None = all, () = a plain render), each [H,W,3]. out: a dict of arrays to write into instead of fresh zeros -
+        the call only writes the rows cam's shard owns. stats: a dict that receives mcrt_stats."""
+        self._sync_env()
+        names = list(PIXEL_STATS_CHANNELS) if channels is None else list(channels)
+        shape = (cam.height, cam.width, 3)
+        res, bufs = {}, PixelStatsBuffers()
+        for name in ["rgb"] + names:
+            assert name == "rgb" or name in PIXEL_STATS_CHANNELS, name
+            a = out[name] if out is not None and name in out else np.zeros(shape, dtype=np.float64)
+            assert a.dtype == np.float64 and a.shape == shape and a.flags["C_CONTIGUOUS"], name
+            res[name] = a
+            if name != "rgb":
+                setattr(bufs, name, a.ctypes.data)
+        st = Stats()
+        self._check(self._lib.mcrt_render_pixel_stats(self._h, C.byref(cam), int(global_seed), int(integrator), res["rgb"].ctypes.data, C.byref(bufs),
+                                                      C.byref(st)), "mcrt_render_pixel_stats")
+        if stats is not None:
+            stats.update(st.as_dict())
+        return res
+
+    def render_pixel_stats_device(self, cam, global_seed, integrator, rgb_ptr, pointers=None):
+        """mcrt_render_pixel_stats_device: rgb_ptr and pointers = dict channel -> raw device pointer (owned rows only, packed like
+        render_device's output); channels left out or None are not computed. Synchronous; returns the stats dict."""
+        self._sync_env()
+        bufs = PixelStatsBuffers()
+        for name, ptr in (pointers or {}).items():
+            assert name in PIXEL_STATS_CHANNELS, name
+            setattr(bufs, name, int(ptr) if ptr else None)
+        st = Stats()
+        self._check(self._lib.mcrt_render_pixel_stats_device(self._h, C.byref(cam), int(global_seed), int(integrator),
+                                                             C.c_void_p(int(rgb_ptr)) if rgb_ptr else None, C.byref(bufs) if pointers is not None else None,
+                                                             C.byref(st)), "mcrt_render_pixel_stats_device")
+        return st.as_dict()
+
+    def frame_noise(self, rgb, variance, spp):
+        """mcrt_frame_noise: the summary of a frame [.., 3] and its variance -> dict noise, signal, relative_error, pixels."""
+        rgb = np.ascontiguousarray(rgb, dtype=np.float64)
+        variance = np.ascontiguousarray(variance, dtype=np.float64)
+        assert rgb.shape == variance.shape and rgb.shape[-1] == 3, (rgb.shape, variance.shape)
+        r = FrameNoise()
+        self._check(self._lib.mcrt_frame_noise(self._h, rgb.size // 3, int(spp), rgb.ctypes.data, variance.ctypes.data, C.byref(r)), "mcrt_frame_noise")
+        return r.as_dict()
+
+    def frame_noise_device(self, pixels, spp, rgb_ptr, variance_ptr):
+        """mcrt_frame_noise_device on device pointers of frames that are complete when this is called."""
+        r = FrameNoise()
+        self._check(self._lib.mcrt_frame_noise_device(self._h, int(pixels), int(spp), C.c_void_p(int(rgb_ptr)) if rgb_ptr else None,
+                                                      C.c_void_p(int(variance_ptr)) if variance_ptr else None, C.byref(r)), "mcrt_frame_noise_device")
+        return r.as_dict()
 
     def sampler(self, pixel, index, shuffles, global_seed):
         pixel = np.ascontiguousarray(pixel, dtype=np.uint32)

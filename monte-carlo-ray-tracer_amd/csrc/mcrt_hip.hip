@@ -28,6 +28,7 @@
 #include "mcrt_launch.hpp"
 #include "mcrt_octree_shared.hpp"
 #include "mcrt_lean.hpp"
+#include "mcrt_pixel_stats_launch.hpp"
 
 #include <hipcub/hipcub.hpp>
 
@@ -122,6 +123,10 @@ struct mcrt_ctx {
     DevBuf op_buf[6];
     DevBuf aov_buf[mcrt::kAovScratchBufs];  // the first-hit AOV pass's rays, hits and host-call channels (mcrt_aov_host.hip), grown on demand too
     DevBuf denoise_buf[mcrt::kDenoiseScratchBufs];  // the a-trous filter's packed guides, two irradiance frames and host-call staging (mcrt_denoise_host.hip)
+    DevBuf pixel_stats_buf[mcrt::kPixelStatsScratchBufs];  // host-call frames and the summary's block values (mcrt_pixel_stats_host.hip)
+    // per-pixel sample statistics wanted from the renders of this context (set for the length of a mcrt_render_pixel_stats* call, so that a
+    // frame mcrt_render_finish renders again fills them again): packed like the frame; all nullptr = none, nothing in a render changes
+    mcrt_pixel_stats_buffers stats_targets{nullptr, nullptr, nullptr};
     std::map<std::string, std::string> options;  // mcrt_set_option; seeded from the MCRT_* environment variables at mcrt_create
     DevBuf pm_iors;  // refraction histories of the 1024-lane photon-mapping kernel
     // the frame in flight, kept so that mcrt_render_finish can run it again through the wavefront pipeline (deep refraction histories)
@@ -522,6 +527,24 @@ int runWavefrontPass(mcrt_ctx* ctx, const WfFrame& fr, uint64_t slots, hipStream
     return MCRT_OK;
 }
 
+// The statistics of a pass whose samples are complete in the store (include/mcrt.h "Per-pixel sample statistics"), when the context
+// holds targets: one launch of libmcrt_pixel_stats.so's kernel, the outputs offset to the pass's first row.
+int launchPassStats(mcrt_ctx* ctx, hipStream_t stream, const double* samples, uint64_t pass_pixels, uint32_t spp, size_t first_word) {
+    const mcrt_pixel_stats_buffers& t = ctx->stats_targets;
+    if (!t.variance && !t.half_a && !t.half_b) return MCRT_OK;
+    PixelStatsPass ps;
+    ps.samples = samples;
+    ps.words = pass_pixels * 3;
+    ps.spp = spp;
+    ps.vec = pixelStatsVec(samples, ps.words);
+    ps.variance = t.variance ? t.variance + first_word : nullptr;
+    ps.half_a = t.half_a ? t.half_a + first_word : nullptr;
+    ps.half_b = t.half_b ? t.half_b + first_word : nullptr;
+    HIP_TRY(ctx, (hipError_t)launchPixelStats(stream, ps));
+    ctx->launches++;
+    return MCRT_OK;
+}
+
 // The wavefront frame: the film, the pool and the passes (runWavefrontPass), so the call returns when the frame is complete;
 // mcrt_render_finish() then only collects the statistics.
 // film_out != NULL (mcrt_render_film_device): the splats of this shard's samples stay in the caller's full-frame RGBW buffer
@@ -601,6 +624,7 @@ int launchWavefront(mcrt_ctx* ctx, const mcrt_camera_desc* cam, uint32_t global_
                                (uint64_t)fr.pass_pixels, fr.spp, d_out + (size_t)fr.row_base * cam->width * 3);
             HIP_TRY(ctx, hipGetLastError());
             ctx->launches++;
+            if (int rc = launchPassStats(ctx, stream, fr.samples, fr.pass_pixels, fr.spp, (size_t)fr.row_base * cam->width * 3)) return rc;
         }
     }
     if (splats && !film_out) {
@@ -745,6 +769,7 @@ int launchRenderImpl(mcrt_ctx* ctx, const mcrt_camera_desc* cam, uint32_t global
         hipLaunchKernelGGL(sampleResolveKernel, dim3((uint32_t)((prm.pass_pixels + 255) / 256)), dim3(256), 0, stream, prm.samples,
                            prm.pass_pixels, prm.spp, d_out + (size_t)prm.row_base * cam->width * 3);
         ctx->launches += 2;
+        if (int rc = launchPassStats(ctx, stream, prm.samples, prm.pass_pixels, prm.spp, (size_t)prm.row_base * cam->width * 3)) return rc;
     }
     return endFrame(ctx, stream);
 }
@@ -1745,5 +1770,31 @@ void* ctxDenoiseScratch(mcrt_ctx* ctx, int which, size_t bytes) {
         return nullptr;
     }
     return ctx->denoise_buf[which].p;
+}
+
+int ctxPixelStatsReady(mcrt_ctx* ctx, const char* what) {
+    if (ctx->pending) return fail(ctx, MCRT_ERR_INVALID, std::string(what) + ": a render is in flight, call mcrt_render_finish first");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    return MCRT_OK;
+}
+int ctxPixelStatsBegin(mcrt_ctx* ctx, const mcrt_camera_desc* cam, const mcrt_pixel_stats_buffers* targets, const char* what) {
+    if (int rc = ctxPixelStatsReady(ctx, what)) return rc;
+    if (!ctx->has_scene) return fail(ctx, MCRT_ERR_NO_SCENE, std::string(what) + " before mcrt_upload_scene");
+    if (!cam) return fail(ctx, MCRT_ERR_INVALID, std::string(what) + ": camera is NULL");
+    const bool wanted = targets && (targets->variance || targets->half_a || targets->half_b);
+    if (wanted && filmSplats(cam->film_filter, cam->film_radius))
+        return fail(ctx, MCRT_ERR_UNSUPPORTED, std::string(what) + ": a frame whose film splats (a reconstruction filter, or a box of another radius) keeps no "
+                                               "samples: there is nothing to take the statistics of");
+    ctx->stats_targets = wanted ? *targets : mcrt_pixel_stats_buffers{nullptr, nullptr, nullptr};
+    return MCRT_OK;
+}
+void ctxPixelStatsEnd(mcrt_ctx* ctx) { ctx->stats_targets = mcrt_pixel_stats_buffers{nullptr, nullptr, nullptr}; }
+void* ctxPixelStatsScratch(mcrt_ctx* ctx, int which, size_t bytes) {
+    if (which < 0 || which >= kPixelStatsScratchBufs) return nullptr;
+    if (ctx->pixel_stats_buf[which].reserve(std::max<size_t>(bytes, 8)) != hipSuccess) {
+        (void)hipGetLastError();
+        return nullptr;
+    }
+    return ctx->pixel_stats_buf[which].p;
 }
 }  // namespace mcrt

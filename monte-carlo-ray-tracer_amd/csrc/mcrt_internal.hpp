@@ -38,4 +38,14 @@ void* ctxAovScratch(mcrt_ctx* ctx, int which, size_t bytes);
 constexpr int kDenoiseScratchBufs = 4;
 int ctxDenoiseReady(mcrt_ctx* ctx, const char* what);
 void* ctxDenoiseScratch(mcrt_ctx* ctx, int which, size_t bytes);
+// mcrt_pixel_stats_host.hip (per-pixel sample statistics, frame summary). ctxPixelStatsReady: device selected, MCRT_ERR_INVALID (render in
+// flight) recorded under `what`; no scene is needed. ctxPixelStatsBegin: that, MCRT_ERR_NO_SCENE, MCRT_ERR_UNSUPPORTED for a camera whose
+// film splats when a channel is wanted - then the channels (nullptr: none) are the targets that the pass loops of the next renders of
+// this context fill (one launch per pass after the integrator's), until ctxPixelStatsEnd. ctxPixelStatsScratch: buffer `which`
+// (0..kPixelStatsScratchBufs-1: four frames of the host-pointer forms, two of the summary's block values).
+constexpr int kPixelStatsScratchBufs = 6;
+int ctxPixelStatsReady(mcrt_ctx* ctx, const char* what);
+int ctxPixelStatsBegin(mcrt_ctx* ctx, const mcrt_camera_desc* cam, const mcrt_pixel_stats_buffers* targets, const char* what);
+void ctxPixelStatsEnd(mcrt_ctx* ctx);
+void* ctxPixelStatsScratch(mcrt_ctx* ctx, int which, size_t bytes);
 }  // namespace mcrt

@@ -4,7 +4,7 @@
 //
 //   mcrt_render scene.mcrt out.f64 [--width W --height H --sqrtspp S] [--seed N] [--photon] [--device D | --devices D0,D1,...]
 //               [--tga out.tga [--tonemapper hable|aces] [--exposure EV] [--gain EV] [--plain]] [--aov PREFIX]
-//               [--denoise OUT.f64 [--denoise-iterations N]]
+//               [--denoise OUT.f64 [--denoise-iterations N]] [--stats PREFIX]
 //
 // Writes the frame as raw FP64 RGB, row-major (what Image::operator() holds, camera/image.cpp:53-56),
 // and prints the statistics. --tga also develops it the way Image::save does (auto exposure / gain, tone map, sRGB bytes:
@@ -14,6 +14,8 @@
 // --denoise also writes the frame filtered by mcrt_denoise (the edge-avoiding a-trous filter guided by that AOV frame; default parameters,
 // --denoise-iterations N sets the one that sizes the footprint) as raw FP64 RGB, and with --tga develops the filtered frame too, to OUT's
 // stem + ".tga".
+// --stats renders the frame through mcrt_render_pixel_stats (the same frame) and also writes the per-pixel sample statistics,
+// PREFIX.variance.f64, .half_a.f64 and .half_b.f64 (raw FP64 RGB, row-major), and prints the frame summary of mcrt_frame_noise (one device).
 // --devices renders the frame on several GPUs from this one process (mcrt_render_multi: one host thread per GPU).
 #include <cstdio>
 #include <cstdlib>
@@ -42,7 +44,7 @@ int main(int argc, char** argv) {
     image.plain = (uint32_t)mcrt_image_param(img, "image_plain");
     image.exposure_compensation = from_bits(mcrt_image_param(img, "image_exposure_ev_bits"));
     image.gain_compensation = from_bits(mcrt_image_param(img, "image_gain_ev_bits"));
-    std::string tga, aov, denoise;
+    std::string tga, aov, denoise, pstats;
     mcrt_denoise_params dparams{};
     std::vector<int> devices;
     for (int i = 3; i < argc; i++) {
@@ -63,6 +65,7 @@ int main(int argc, char** argv) {
         else if (k == "--tga" && i + 1 < argc) tga = argv[++i];
         else if (k == "--aov" && i + 1 < argc) aov = argv[++i];
         else if (k == "--denoise" && i + 1 < argc) denoise = argv[++i];
+        else if (k == "--stats" && i + 1 < argc) pstats = argv[++i];
         else if (k == "--denoise-iterations") dparams.iterations = (uint32_t)val();
         else if (k == "--tonemapper" && i + 1 < argc) image.tonemapper = (argv[++i][0] | 0x20) == 'a' ? MCRT_TONEMAP_ACES : MCRT_TONEMAP_HABLE;
         else if (k == "--exposure" && i + 1 < argc) image.exposure_compensation = std::strtod(argv[++i], nullptr);
@@ -89,7 +92,18 @@ int main(int argc, char** argv) {
     std::vector<double> rgb((size_t)cam.width * cam.height * 3);
     mcrt_stats st;
     const int mode = photon ? MCRT_INTEGRATOR_PHOTON_MAPPER : MCRT_INTEGRATOR_PATH_TRACER;
-    if (rc == MCRT_OK)
+    std::vector<double> variance, half_a, half_b;
+    if (rc == MCRT_OK && !pstats.empty()) {
+        if (ctxs.size() > 1) {
+            std::fprintf(stderr, "--stats takes one device\n");
+            return 2;
+        }
+        variance.resize(rgb.size());
+        half_a.resize(rgb.size());
+        half_b.resize(rgb.size());
+        const mcrt_pixel_stats_buffers b{variance.data(), half_a.data(), half_b.data()};
+        rc = mcrt_render_pixel_stats(ctx, &cam, seed, mode, rgb.data(), &b, &st);
+    } else if (rc == MCRT_OK)
         rc = ctxs.size() > 1 ? mcrt_render_multi(ctxs.data(), (uint32_t)ctxs.size(), &cam, seed, mode, rgb.data(), &st)
                              : mcrt_render(ctx, &cam, seed, mode, rgb.data(), &st);
     if (rc != MCRT_OK) {
@@ -102,6 +116,30 @@ int main(int argc, char** argv) {
         return 1;
     }
     std::fclose(f);
+    if (!pstats.empty()) {
+        const struct {
+            const char* ext;
+            const std::vector<double>* data;
+        } files[3] = {{".variance.f64", &variance}, {".half_a.f64", &half_a}, {".half_b.f64", &half_b}};
+        for (const auto& c : files) {
+            const std::string path = pstats + c.ext;
+            FILE* o = std::fopen(path.c_str(), "wb");
+            const bool ok = o && std::fwrite(c.data->data(), sizeof(double), c.data->size(), o) == c.data->size();
+            if (o) std::fclose(o);
+            if (!ok) {
+                std::fprintf(stderr, "cannot write %s\n", path.c_str());
+                return 1;
+            }
+        }
+        mcrt_frame_noise_result fn;
+        rc = mcrt_frame_noise(ctx, (uint64_t)cam.width * cam.height, cam.sqrtspp * cam.sqrtspp, rgb.data(), variance.data(), &fn);
+        if (rc != MCRT_OK) {
+            std::fprintf(stderr, "mcrt error %d: %s\n", rc, mcrt_last_error(ctx));
+            return 1;
+        }
+        std::printf("{\"stats\":\"%s\",\"noise\":%.17g,\"signal\":%.17g,\"relative_error\":%.17g,\"pixels\":%llu}\n", pstats.c_str(), fn.noise, fn.signal,
+                    fn.relative_error, (unsigned long long)fn.pixels);
+    }
     auto develop = [&](const std::vector<double>& frame, const std::string& path) {
         image.width = cam.width;
         image.height = cam.height;

@@ -1,0 +1,261 @@
+"""Per-pixel sample statistics and the frame summary (mcrt_render_pixel_stats*, mcrt_frame_noise*), CPU tier: csrc/mcrt_pixel_stats.hpp -
+the text the two kernels of csrc/mcrt_pixel_stats.hip run - driven on the host (tests/emu/pixel_stats_emu.cpp: the statistics as a loop
+over the lanes, the summary's block reduction on wave_emu.hpp's emulated workgroup with its barrier) against the formulas of
+include/mcrt.h ("Per-pixel sample statistics") written out HERE in numpy, sample by sample in the stated order. The samples are the
+oracle's own per-sample radiance (oracle_lib.render(per_sample=True)) and hand-made stores.
+
+Bound: assert_array_equal on the bits. Derived, not measured: both sides execute the same IEEE-754 double operations (+ - * /, compare,
+select) in the same order, none of them a libm call, neither side contracted (the harness is built with -ffp-contract=off, numpy's
+ufuncs are one operation each) - so every bit agrees, NaNs included. The half-buffer identity is the one tolerance: the mean of the two
+halves, weighted by their counts, is the mean up to the rounding of two differently ordered sums of n <= 9 terms and three divisions,
+far inside 1e-14 relative where no cancellation happens (the radiance samples are non-negative)."""
+import ctypes as C
+import functools
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+import test_aov_emulation as aov
+from conftest import ROOT, TESTS
+
+WIDTH, HEIGHT, SEED = 70, 13, 0x5EED0A0F
+ORACLE_SCENES = ("hexagon_room_diffuse", "coffee_maker_qsah", "ior_test")
+
+
+def load_pixel_stats_emu():
+    src = os.path.join(TESTS, "emu", "pixel_stats_emu.cpp")
+    out = os.path.join(TESTS, "emu", "_build", "libpixel_stats_emu.so")
+    csrc = os.path.join(ROOT, "monte-carlo-ray-tracer_amd", "csrc")
+    deps = [src, os.path.join(TESTS, "emu", "wave_emu.hpp"), os.path.join(csrc, "mcrt_pixel_stats.hpp"), os.path.join(csrc, "mcrt_math.hpp"),
+            os.path.join(ROOT, "include", "mcrt.h")]
+    if not os.path.exists(out) or any(os.path.getmtime(d) > os.path.getmtime(out) for d in deps):
+        os.makedirs(os.path.dirname(out), exist_ok=True)
+        tmp = "%s.%d.tmp" % (out, os.getpid())
+        subprocess.check_call(["g++", "-std=c++17", "-O2", "-ffp-contract=off", "-fPIC", "-shared", "-o", tmp, src])
+        os.replace(tmp, out)
+    L = C.CDLL(out)
+    vp = C.c_void_p
+    L.pixel_stats_emu.argtypes = [vp, C.c_uint64, C.c_uint32, C.c_int, vp, vp, vp]
+    L.frame_noise_emu.argtypes = [C.c_uint64, C.c_uint32, vp, vp, vp]
+    return L
+
+
+@functools.lru_cache(maxsize=None)
+def _emu():
+    return load_pixel_stats_emu()
+
+
+SENTINEL = -7.25
+CHANNELS = ("variance", "half_a", "half_b")
+
+
+def emu_pixel_stats(store, channels=CHANNELS, vec=-1):
+    """The emulation on a store [spp][pixels][3] -> dict channel -> [pixels][3]; channels left out get a NULL pointer and come back as
+    the sentinel they were filled with."""
+    store = np.ascontiguousarray(store, dtype=np.float64)
+    spp, pixels = store.shape[:2]
+    out = {k: np.full((pixels, 3), SENTINEL) for k in CHANNELS}
+    rc = _emu().pixel_stats_emu(store.ctypes.data, pixels, spp, vec, *[out[k].ctypes.data if k in channels else None for k in CHANNELS])
+    assert rc >= 0, "pixel_stats_emu: %d" % rc
+    return out
+
+
+def numpy_pixel_stats(store):
+    """include/mcrt.h's "Per-pixel sample statistics" in numpy on a store [spp][...]: sample by sample, ascending.
+    -> dict mean (before the clamp), variance, half_a, half_b."""
+    store = np.asarray(store, dtype=np.float64)
+    n = store.shape[0]
+    with np.errstate(all="ignore"):
+        S, A, B = np.zeros(store.shape[1:]), np.zeros(store.shape[1:]), np.zeros(store.shape[1:])
+        for i in range(n):
+            S = S + store[i]
+            if i % 2 == 0:
+                A = A + store[i]
+            else:
+                B = B + store[i]
+        m = S / float(n)
+        Q = np.zeros(store.shape[1:])
+        for i in range(n):
+            Q = Q + (store[i] - m) * (store[i] - m)
+        return {"mean": m, "variance": Q / float(n - 1) if n > 1 else np.zeros_like(m), "half_a": A / float((n + 1) // 2),
+                "half_b": B / float(n // 2) if n > 1 else np.zeros_like(m)}
+
+
+def numpy_treesum(values):
+    """include/mcrt.h's treesum: blocks of 256 consecutive values, stride 128 .. 1 pairing k with k + stride, again on the block values."""
+    t = np.array(values, dtype=np.float64).ravel()
+    assert t.size > 0
+    with np.errstate(all="ignore"):
+        while True:
+            blocks = (t.size + 255) // 256
+            padded = np.zeros(blocks * 256)
+            padded[:t.size] = t
+            padded = padded.reshape(blocks, 256)
+            length = np.minimum(256, t.size - 256 * np.arange(blocks))[:, None]
+            stride = 128
+            while stride:
+                k = np.arange(stride)[None, :]
+                pair = k + stride < length  # [blocks][stride]
+                padded[:, :stride] = np.where(pair, padded[:, :stride] + padded[:, stride:2 * stride], padded[:, :stride])
+                stride //= 2
+            t = padded[:, 0].copy()
+            if blocks == 1:
+                return float(t[0])
+
+
+def numpy_frame_noise(rgb, variance, spp):
+    rgb, v = np.asarray(rgb, dtype=np.float64).reshape(-1, 3), np.asarray(variance, dtype=np.float64).reshape(-1, 3)
+    with np.errstate(all="ignore"):
+        e = ((v[:, 0] + v[:, 1]) + v[:, 2]) / float(spp)
+        g = (rgb[:, 0] * rgb[:, 0] + rgb[:, 1] * rgb[:, 1]) + rgb[:, 2] * rgb[:, 2]
+    return numpy_treesum(e), numpy_treesum(g)
+
+
+def emu_frame_noise(rgb, variance, spp):
+    rgb = np.ascontiguousarray(rgb, dtype=np.float64).reshape(-1, 3)
+    variance = np.ascontiguousarray(variance, dtype=np.float64).reshape(-1, 3)
+    out = np.zeros(2)
+    levels = _emu().frame_noise_emu(rgb.shape[0], spp, rgb.ctypes.data, variance.ctypes.data, out.ctypes.data)
+    assert levels > 0
+    return float(out[0]), float(out[1]), levels
+
+
+def bits(x):
+    return np.asarray(x, dtype=np.float64).view(np.uint64)
+
+
+@functools.lru_cache(maxsize=None)
+def oracle_case(scene, sqrtspp, integrator=None, width=WIDTH, height=HEIGHT, seed=SEED):
+    """The oracle's frame and per-sample radiance of one camera, as a store [spp][H][W][3], with the numpy statistics: computed once."""
+    import importlib
+    import oracle_lib
+    pkg = importlib.import_module("monte-carlo-ray-tracer_amd")
+    img = aov._image(scene)
+    cam = img.camera
+    cam.width, cam.height, cam.sqrtspp = width, height, sqrtspp
+    cam.shard_index, cam.shard_count, cam.shard_rows = 0, 1, 0
+    frame, info = oracle_lib.render(img, cam, seed, pkg.INTEGRATOR_PATH_TRACER if integrator is None else integrator, per_sample=True)
+    store = np.ascontiguousarray(np.moveaxis(info["samples"], 2, 0))  # [H][W][spp][3] -> [spp][H][W][3]
+    want = numpy_pixel_stats(store)
+    for a in (frame, store) + tuple(want.values()):
+        a.setflags(write=False)
+    return frame, store, want
+
+
+@pytest.mark.parametrize("sqrtspp", [1, 2, 3])
+@pytest.mark.parametrize("scene", ORACLE_SCENES)
+def test_text_on_the_oracles_samples_is_the_header_in_numpy(scene, sqrtspp):
+    frame, store, want = oracle_case(scene, sqrtspp)
+    spp = sqrtspp * sqrtspp
+    assert store.shape == (spp, HEIGHT, WIDTH, 3) and np.isfinite(store).all()
+    np.testing.assert_array_equal(bits(np.where(want["mean"] < 0.0, 0.0, want["mean"])), bits(frame))  # max(m, 0) is the oracle's frame
+    got = emu_pixel_stats(store.reshape(spp, -1, 3))
+    for k in CHANNELS:
+        np.testing.assert_array_equal(bits(got[k]), bits(want[k].reshape(-1, 3)), err_msg="%s sqrtspp %d %s" % (scene, sqrtspp, k))
+    if spp > 1:
+        assert (want["variance"] > 0).any()
+    else:
+        assert not want["variance"].any() and not want["half_b"].any()
+        np.testing.assert_array_equal(bits(want["half_a"]), bits(want["mean"]))
+    # the half-buffer identity (module docstring)
+    m = want["mean"]
+    back = (float((spp + 1) // 2) * want["half_a"] + float(spp // 2) * want["half_b"]) / float(spp)
+    err = np.abs(back - m)
+    print("%s sqrtspp %d: half-buffer identity, max relative error %.3e" % (scene, sqrtspp, (err / np.maximum(np.abs(m), 1e-300)).max()))
+    assert (err <= 1e-14 * np.abs(m)).all()
+
+
+def _store(spp, pixels, seed):
+    rng = np.random.default_rng(seed)
+    return rng.random((spp, pixels, 3)) * rng.choice([1e-3, 1.0, 40.0], size=(1, pixels, 1))
+
+
+@pytest.mark.parametrize("pixels", [910, 1, 171])  # 910: a ragged last workgroup; 171 pixels = 513 words, odd: no 16-byte loads, a lane with one word
+@pytest.mark.parametrize("spp", [1, 2, 3, 16, 21])  # 16 and 21: whole batches of 8 planes, and a batch with a rest
+def test_hand_made_stores(pixels, spp):
+    store = _store(spp, pixels, 1000 * spp + pixels)
+    want = numpy_pixel_stats(store)
+    forms = [-1, 0] + ([1] if (pixels * 3) % 2 == 0 and store.ctypes.data % 16 == 0 else [])  # (1: only where the launch would choose it)
+    for vec in forms:
+        got = emu_pixel_stats(store, vec=vec)
+        for k in CHANNELS:
+            np.testing.assert_array_equal(bits(got[k]), bits(want[k]), err_msg="%d pixels, %d spp, %s, loads %d" % (pixels, spp, k, vec))
+
+
+@pytest.mark.parametrize("spp", [2, 3, 16])
+def test_equal_samples_have_no_variance(spp):
+    """Exactly 0 wherever the header's sum is exact: for any value at n = 2 (x + x and its half are exact), and at every n for values
+    of few mantissa bits (here 24: the partial sums k * x, k <= 16, need 4 more). A value whose multiples round has S / n one ulp off x
+    and a variance of the order of ulp(x)^2 - that is the two-pass formula as defined, not an error of the kernel."""
+    short = np.round(_store(1, 910, 5) * 2.0 ** 18) / 2.0 ** 18
+    assert (short > 0).any()
+    stores = [np.repeat(short, spp, axis=0)] + ([np.repeat(_store(1, 910, 6), 2, axis=0)] if spp == 2 else [])
+    for store in stores:
+        got = emu_pixel_stats(store)
+        assert not got["variance"].any()
+        np.testing.assert_array_equal(bits(got["half_a"]), bits(store[0]))
+        np.testing.assert_array_equal(bits(got["half_b"]), bits(store[0]))
+
+
+def test_nan_and_inf_stay_in_their_pixel_and_negative_samples_are_not_clamped():
+    spp, pixels = 9, 910
+    store = _store(spp, pixels, 9)
+    clean = emu_pixel_stats(store)
+    dirty = store.copy()
+    dirty[4, 100, 1] = np.nan      # an even sample
+    dirty[3, 909, 2] = np.inf      # an odd sample, the last word of the store
+    dirty[:, 500, :] = -dirty[:, 500, :]
+    got = emu_pixel_stats(dirty)
+    want = numpy_pixel_stats(dirty)
+    for k in CHANNELS:
+        np.testing.assert_array_equal(bits(got[k]), bits(want[k]), err_msg=k)
+        other = np.ones((pixels, 3), dtype=bool)
+        other[100, 1] = other[909, 2] = False
+        other[500, :] = False
+        np.testing.assert_array_equal(bits(got[k][other]), bits(clean[k][other]), err_msg=k)
+    assert np.isnan(got["variance"][100, 1]) and np.isnan(got["half_a"][100, 1]) and np.isfinite(got["half_b"][100, 1])
+    assert np.isnan(got["variance"][909, 2]) and np.isinf(got["half_b"][909, 2]) and np.isfinite(got["half_a"][909, 2])
+    assert (got["half_a"][500] < 0).all() and (got["half_b"][500] < 0).all()
+    np.testing.assert_array_equal(bits(got["half_a"][500]), bits(-clean["half_a"][500]))
+    np.testing.assert_array_equal(bits(got["variance"][500]), bits(clean["variance"][500]))
+
+
+@pytest.mark.parametrize("left_out", CHANNELS)
+def test_a_null_channel_is_not_written(left_out):
+    store = _store(5, 910, 11)
+    full = emu_pixel_stats(store)
+    got = emu_pixel_stats(store, channels=[k for k in CHANNELS if k != left_out])
+    assert (got[left_out] == SENTINEL).all()
+    for k in CHANNELS:
+        if k != left_out:
+            np.testing.assert_array_equal(bits(got[k]), bits(full[k]))
+    none = emu_pixel_stats(store, channels=())
+    assert all((none[k] == SENTINEL).all() for k in CHANNELS)
+
+
+@pytest.mark.parametrize("count", [1, 255, 256, 257, 65536, 65537])
+def test_treesum(count):
+    rng = np.random.default_rng(count)
+    rgb = rng.random((count, 3)) * rng.choice([1e-6, 1.0, 1e6], size=(count, 1))
+    variance = rng.random((count, 3)) * rng.choice([1e-9, 1.0, 1e3], size=(count, 1))
+    noise, signal, levels = emu_frame_noise(rgb, variance, 9)
+    assert levels == (1 if count <= 256 else 2 if count <= 65536 else 3)
+    want = numpy_frame_noise(rgb, variance, 9)
+    assert bits(noise) == bits(want[0]) and bits(signal) == bits(want[1])
+    assert abs(signal - float((rgb * rgb).sum())) <= 1e-12 * signal  # (it is a sum)
+
+
+def test_frame_noise_of_an_oracle_frame_and_of_a_frame_with_a_nan():
+    frame, store, want = oracle_case("coffee_maker_qsah", 3)
+    noise, signal, levels = emu_frame_noise(frame, want["variance"], 9)
+    assert levels == 2 and noise > 0 and signal > 0
+    ref = numpy_frame_noise(frame, want["variance"], 9)
+    assert bits(noise) == bits(ref[0]) and bits(signal) == bits(ref[1])
+    v = np.array(want["variance"])
+    v[5, 17, 0] = np.nan
+    noise2, signal2, _ = emu_frame_noise(frame, v, 9)
+    assert np.isnan(noise2) and bits(signal2) == bits(signal)
+    ref2 = numpy_frame_noise(frame, v, 9)
+    assert np.isnan(ref2[0])
