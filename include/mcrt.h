@@ -415,6 +415,79 @@ int mcrt_frame_noise_device(mcrt_ctx* ctx, uint64_t pixels, uint32_t spp, const 
 int mcrt_frame_noise(mcrt_ctx* ctx, uint64_t pixels, uint32_t spp, const double* rgb, const double* variance,
                      mcrt_frame_noise_result* out);
 
+/* ------------------------------------------------------------------------------------------
+ * Firefly suppression: the brightest samples of every pixel kept aside while the per-sample store still holds them (the
+ * highlights of a render), and a robust frame that clamps them against the level of the pixel's neighbourhood. The reference
+ * has no such output. A pixel that sees only itself cannot tell a firefly from the edge of a directly visible light - two
+ * bright samples out of sixteen look like outliers there -, so the bound comes from the largest robust level in a window.
+ * Only FP64 + - * /, compare and select, in the order written here, uncontracted, no libm routine: functions of their inputs
+ * bit for bit.
+ *
+ *   L(x) = (0.2126 * x.r + 0.7152 * x.g) + 0.0722 * x.b;   n = sqrtspp^2;   max0(x) = x < 0 ? 0 : x
+ *   K = min(4, n / 4) (integer division): 0 below 4 spp, 1 at 4, 2 at 9, 4 (MCRT_ROBUST_TOPS) from 16 on.
+ *
+ * 1. Highlights of a render. Per pixel, with x_i the radiance of sample i (i = 0 .. n-1) and L_i = L(x_i):
+ *   a list of at most K entries starts empty. For i ascending: a sample whose L_i is NaN never enters; any other sample is
+ *   inserted before the first entry e with L_i > L_e, or appended when there is no such e and the list holds fewer than K
+ *   entries; an entry pushed past position K-1 is dropped. (Without NaN this is the stable order: L descending, i ascending.)
+ *   tops[k]  = the rgb of entry k of the final list, 0.0 for k >= the number of entries (k = 0 .. 3)
+ *   rest_c   = (((0.0 + x_a,c) + x_b,c) + ...) over the samples that are not in the final list, ascending i
+ *   level    = L(rest / (double)(n - K))          (the division per channel; K, not the number of entries)
+ * Nothing is clamped. With K = 0 the list is empty and level = L(S / n) of the frame's own sum S.
+ * mcrt_render_highlights_device renders the frame mcrt_render_device + mcrt_render_finish deliver - the same bits in d_out_rgb,
+ * the same kernel_id, cam->shard_* honoured the same way - and fills the channels of d_highlights that are not NULL, packed
+ * like d_out_rgb (the owned rows); d_stats_buffers, when given, is filled as by mcrt_render_pixel_stats_device in the same
+ * render. The call is synchronous on the context's stream. kernel_launches counts one launch more per pass
+ * (MCRT_SAMPLE_STORE_GB) when a highlight channel is wanted, and one more when a statistics channel is; the highlights do not
+ * depend on passes, shards, the kernel form of one integrator family or the launch shape. A frame that mcrt_render_finish
+ * renders again (nested media, a kNN overflow) delivers the highlights of the run it delivers. d_highlights NULL or all-NULL:
+ * no highlights. Refused as the statistics are: a camera whose film splats when a channel is wanted - MCRT_ERR_UNSUPPORTED -;
+ * a render in flight, no scene, d_out_rgb NULL as in mcrt_render_device. */
+#define MCRT_ROBUST_TOPS 4
+typedef struct mcrt_highlight_buffers {   /* every pointer may be NULL = not wanted; owned rows packed like d_out_rgb */
+    double* tops;    /* [rows][width][MCRT_ROBUST_TOPS][3] */
+    double* level;   /* [rows][width] */
+} mcrt_highlight_buffers;
+int mcrt_render_highlights_device(mcrt_ctx* ctx, const mcrt_camera_desc* cam, uint32_t global_seed, int integrator, double* d_out_rgb,
+                                  const mcrt_highlight_buffers* d_highlights, const mcrt_pixel_stats_buffers* d_stats_buffers /* may be NULL */,
+                                  mcrt_stats* stats /* may be NULL */);
+/* Same with HOST pointers to FULL frames ([height][width]...): rows this shard does not own are left untouched. */
+int mcrt_render_highlights(mcrt_ctx* ctx, const mcrt_camera_desc* cam, uint32_t global_seed, int integrator, double* out_rgb,
+                           const mcrt_highlight_buffers* highlights, const mcrt_pixel_stats_buffers* stats_buffers /* may be NULL */,
+                           mcrt_stats* stats /* may be NULL */);
+
+/* 2. Robust resolve, on FULL frames [height][width]... after the gather (it reads neighbouring rows: there is no shard form):
+ * the frame rgb, its tops and its level, of a render with spp = n samples per pixel. Per pixel p, with R = radius:
+ *   M = -inf; the window is visited with dy = -R..R as the outer and dx = -R..R as the inner loop, taps q outside the frame are
+ *   skipped; at each tap M = M < level_q ? level_q : M   (a NaN level is never taken)
+ *   t = kappa * M;  T = t > floor ? t : floor
+ *   removed_c = 0.0, count = 0; for k = 0 .. K-1 with L_k = L(tops_k): if L_k > T then f = T / L_k,
+ *     removed_c = removed_c + (tops_k,c - tops_k,c * f), count = count + 1
+ *   removed (out) = removed_c / (double)n;   out_c = max0(rgb_c - removed_c / (double)n);   clamped = count
+ * Where nothing is clamped (count == 0) out is rgb bit for bit (also a negative value of a frame that is no render's, which
+ * max0 would cut: out_c = count ? max0(...) : rgb_c). NaN and Inf are not filtered: they stay in their own pixel,
+ * except that an Inf level switches the clamp off in every window that holds it.
+ * d_out_rgb may be d_rgb; buffers (or either of its pointers) may be NULL. The call is synchronous on the context's stream,
+ * needs no uploaded scene, and is refused (MCRT_ERR_INVALID) while a render is in flight, when d_rgb, d_tops, d_level or
+ * d_out_rgb is NULL, when width * height is 0 or >= 2^32, when spp is 0, or with a parameter out of range.
+ * stats: kernel_ms (HIP events of the call's own around its launch), total_ms, kernel_launches (1). */
+typedef struct mcrt_robust_params {   /* NULL or a zero field = the default */
+    double   kappa;              /* default 8.0; must be finite and >= 1 */
+    double   floor;              /* default 0.0; must be finite and >= 0 */
+    uint32_t radius, reserved;   /* default 1; more than 8: MCRT_ERR_INVALID */
+} mcrt_robust_params;
+typedef struct mcrt_robust_buffers {  /* every pointer may be NULL = not wanted */
+    double*   removed;   /* [height][width][3] */
+    uint32_t* clamped;   /* [height][width]    */
+} mcrt_robust_buffers;
+int mcrt_robust_resolve_device(mcrt_ctx* ctx, uint32_t width, uint32_t height, uint32_t spp, const double* d_rgb, const double* d_tops,
+                               const double* d_level, const mcrt_robust_params* params, double* d_out_rgb,
+                               const mcrt_robust_buffers* d_buffers /* may be NULL */, mcrt_stats* stats /* may be NULL */);
+/* Same with HOST pointers (out_rgb may be rgb). */
+int mcrt_robust_resolve(mcrt_ctx* ctx, uint32_t width, uint32_t height, uint32_t spp, const double* rgb, const double* tops,
+                        const double* level, const mcrt_robust_params* params, double* out_rgb,
+                        const mcrt_robust_buffers* buffers /* may be NULL */, mcrt_stats* stats /* may be NULL */);
+
 /* Photon emission pass on the GPU. Replaces the thread fan-out of
  * PhotonMapper::PhotonMapper (integrator/photon-mapper/photon-mapper.cpp:80-115: per emission
  * Sampler::initiate(light), setIndex(offset+i), light point + cosine direction, emitPhoton :225-277) for

@@ -193,6 +193,26 @@ class FrameNoise(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class HighlightBuffers(C.Structure):
+    """mcrt_highlight_buffers: a null pointer = channel not wanted."""
+    _fields_ = [("tops", C.c_void_p), ("level", C.c_void_p)]
+
+
+ROBUST_TOPS = 4
+# channel -> the shape of a pixel, in mcrt_highlight_buffers order
+HIGHLIGHT_CHANNELS = {"tops": (ROBUST_TOPS, 3), "level": ()}
+
+
+class RobustParams(C.Structure):
+    """mcrt_robust_params: a zero field = the default (include/mcrt.h)."""
+    _fields_ = [("kappa", C.c_double), ("floor", C.c_double), ("radius", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class RobustBuffers(C.Structure):
+    """mcrt_robust_buffers: a null pointer = not wanted."""
+    _fields_ = [("removed", C.c_void_p), ("clamped", C.c_void_p)]
+
+
 class PhotonEmissionDevice(C.Structure):
     _fields_ = [("global_count", C.c_uint64), ("caustic_count", C.c_uint64), ("d_global_photons", C.c_void_p), ("d_caustic_photons", C.c_void_p),
                 ("emission_paths", C.c_uint64), ("rays", C.c_uint64), ("kernel_ms", C.c_double)]
@@ -289,6 +309,11 @@ def lib():
         L.mcrt_render_pixel_stats_device.argtypes = [vp, C.POINTER(CameraDesc), C.c_uint32, C.c_int, vp, C.POINTER(PixelStatsBuffers), C.POINTER(Stats)]
         L.mcrt_frame_noise.argtypes = [vp, C.c_uint64, C.c_uint32, vp, vp, C.POINTER(FrameNoise)]
         L.mcrt_frame_noise_device.argtypes = [vp, C.c_uint64, C.c_uint32, vp, vp, C.POINTER(FrameNoise)]
+    if hasattr(L, "mcrt_render_highlights"):  # (likewise)
+        L.mcrt_render_highlights.argtypes = [vp, C.POINTER(CameraDesc), C.c_uint32, C.c_int, vp, C.POINTER(HighlightBuffers), C.POINTER(PixelStatsBuffers), C.POINTER(Stats)]
+        L.mcrt_render_highlights_device.argtypes = L.mcrt_render_highlights.argtypes
+        L.mcrt_robust_resolve.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, C.POINTER(RobustParams), vp, C.POINTER(RobustBuffers), C.POINTER(Stats)]
+        L.mcrt_robust_resolve_device.argtypes = L.mcrt_robust_resolve.argtypes
     L.mcrt_sampler.argtypes = [vp, C.c_uint64, _u32p, _u32p, C.c_uint32, C.c_uint32, _dp]
     L.mcrt_knn.argtypes = [vp, C.c_int, C.c_uint64, _dp, C.c_uint32, _u32p, _u32p, _dp]
     L.mcrt_bsdf.argtypes = [vp, C.c_uint64, _dp, _dp, _dp]
@@ -820,6 +845,93 @@ class Context:
         self._check(self._lib.mcrt_frame_noise_device(self._h, int(pixels), int(spp), C.c_void_p(int(rgb_ptr)) if rgb_ptr else None,
                                                       C.c_void_p(int(variance_ptr)) if variance_ptr else None, C.byref(r)), "mcrt_frame_noise_device")
         return r.as_dict()
+
+    def render_highlights(self, cam, global_seed, integrator=INTEGRATOR_PATH_TRACER, channels=None, stats_channels=(), stats=None, out=None):
+        """mcrt_render_highlights: the frame of sample_image plus the highlights of its samples -> dict "rgb" [H,W,3] and the channels
+        wanted (HIGHLIGHT_CHANNELS: "tops" [H,W,4,3], "level" [H,W]; None = both, () = none), plus the per-pixel statistics named in
+        stats_channels (PIXEL_STATS_CHANNELS), filled by the same render. out: a dict of arrays to write into instead of fresh zeros -
+        the call only writes the rows cam's shard owns. stats: a dict that receives mcrt_stats."""
+        self._sync_env()
+        names = list(HIGHLIGHT_CHANNELS) if channels is None else list(channels)
+        frame = (cam.height, cam.width)
+        res, hl, ps = {}, HighlightBuffers(), PixelStatsBuffers()
+        for name in ["rgb"] + names + list(stats_channels):
+            assert name == "rgb" or name in HIGHLIGHT_CHANNELS or name in PIXEL_STATS_CHANNELS, name
+            shape = frame + HIGHLIGHT_CHANNELS.get(name, (3,))
+            a = out[name] if out is not None and name in out else np.zeros(shape, dtype=np.float64)
+            assert a.dtype == np.float64 and a.shape == shape and a.flags["C_CONTIGUOUS"], name
+            res[name] = a
+            if name != "rgb":
+                setattr(hl if name in HIGHLIGHT_CHANNELS else ps, name, a.ctypes.data)
+        st = Stats()
+        self._check(self._lib.mcrt_render_highlights(self._h, C.byref(cam), int(global_seed), int(integrator), res["rgb"].ctypes.data, C.byref(hl),
+                                                     C.byref(ps) if stats_channels else None, C.byref(st)), "mcrt_render_highlights")
+        if stats is not None:
+            stats.update(st.as_dict())
+        return res
+
+    def render_highlights_device(self, cam, global_seed, integrator, rgb_ptr, pointers=None, stats_pointers=None):
+        """mcrt_render_highlights_device: rgb_ptr, pointers = dict highlight channel -> raw device pointer and stats_pointers = dict
+        statistics channel -> raw device pointer (owned rows only, packed like render_device's output); channels left out or None are
+        not computed. Synchronous; returns the stats dict."""
+        self._sync_env()
+        hl, ps = HighlightBuffers(), PixelStatsBuffers()
+        for name, ptr in (pointers or {}).items():
+            assert name in HIGHLIGHT_CHANNELS, name
+            setattr(hl, name, int(ptr) if ptr else None)
+        for name, ptr in (stats_pointers or {}).items():
+            assert name in PIXEL_STATS_CHANNELS, name
+            setattr(ps, name, int(ptr) if ptr else None)
+        st = Stats()
+        self._check(self._lib.mcrt_render_highlights_device(self._h, C.byref(cam), int(global_seed), int(integrator),
+                                                            C.c_void_p(int(rgb_ptr)) if rgb_ptr else None, C.byref(hl) if pointers is not None else None,
+                                                            C.byref(ps) if stats_pointers is not None else None, C.byref(st)), "mcrt_render_highlights_device")
+        return st.as_dict()
+
+    def robust_resolve(self, rgb, tops, level, spp, stats=None, out=None, **params):
+        """mcrt_robust_resolve: the robust frame of the full frames rgb [H,W,3], tops [H,W,4,3] and level [H,W] of a render with spp
+        samples per pixel -> dict "robust" [H,W,3], "removed" [H,W,3], "clamped" [H,W] uint32. params: the fields of mcrt_robust_params
+        (kappa, floor, radius); left out = the default. out: an array to take the robust frame (may be rgb itself). stats: a dict that
+        receives mcrt_stats."""
+        self._sync_env()
+        rgb = rgb if out is rgb else np.ascontiguousarray(rgb, dtype=np.float64)
+        tops, level = np.ascontiguousarray(tops, dtype=np.float64), np.ascontiguousarray(level, dtype=np.float64)
+        assert rgb.ndim == 3 and rgb.shape[2] == 3 and rgb.dtype == np.float64 and rgb.flags["C_CONTIGUOUS"], rgb.shape
+        height, width = rgb.shape[:2]
+        assert tops.shape == (height, width, ROBUST_TOPS, 3) and level.shape == (height, width), (tops.shape, level.shape)
+        robust = np.empty_like(rgb) if out is None else out
+        assert robust.shape == rgb.shape and robust.dtype == np.float64 and robust.flags["C_CONTIGUOUS"]
+        res = {"robust": robust, "removed": np.empty((height, width, 3), dtype=np.float64), "clamped": np.empty((height, width), dtype=np.uint32)}
+        bufs = RobustBuffers(res["removed"].ctypes.data, res["clamped"].ctypes.data)
+        par, st = RobustParams(**params), Stats()
+        self._check(self._lib.mcrt_robust_resolve(self._h, width, height, int(spp), rgb.ctypes.data, tops.ctypes.data, level.ctypes.data, C.byref(par),
+                                                  robust.ctypes.data, C.byref(bufs), C.byref(st)), "mcrt_robust_resolve")
+        if stats is not None:
+            stats.update(st.as_dict())
+        return res
+
+    def robust_resolve_device(self, width, height, spp, rgb_ptr, tops_ptr, level_ptr, out_ptr, removed_ptr=None, clamped_ptr=None, **params):
+        """mcrt_robust_resolve_device on raw device pointers of full frames that are complete when this is called (out_ptr may be
+        rgb_ptr; removed_ptr / clamped_ptr None = not wanted). Synchronous; returns the stats dict."""
+        self._sync_env()
+        p = lambda v: C.c_void_p(int(v)) if v else None
+        bufs = RobustBuffers(int(removed_ptr) if removed_ptr else None, int(clamped_ptr) if clamped_ptr else None)
+        par, st = RobustParams(**params), Stats()
+        self._check(self._lib.mcrt_robust_resolve_device(self._h, int(width), int(height), int(spp), p(rgb_ptr), p(tops_ptr), p(level_ptr), C.byref(par),
+                                                         p(out_ptr), C.byref(bufs) if (removed_ptr or clamped_ptr) else None, C.byref(st)),
+                    "mcrt_robust_resolve_device")
+        return st.as_dict()
+
+    def render_robust(self, cam, global_seed, integrator=INTEGRATOR_PATH_TRACER, stats=None, **params):
+        """The two steps for an unsharded camera: render_highlights, then robust_resolve with params -> dict "rgb" (the plain frame),
+        "robust", "removed", "clamped". stats: a dict that receives the render's mcrt_stats and the resolve's as "resolve"."""
+        assert cam.shard_count <= 1, "the resolve reads neighbouring rows: gather the shards' highlights, then robust_resolve"
+        st, st2 = {}, {}
+        hl = self.render_highlights(cam, global_seed, integrator, stats=st)
+        res = self.robust_resolve(hl["rgb"], hl["tops"], hl["level"], cam.sqrtspp * cam.sqrtspp, stats=st2, **params)
+        if stats is not None:
+            stats.update(st, resolve=st2)
+        return {"rgb": hl["rgb"], "robust": res["robust"], "removed": res["removed"], "clamped": res["clamped"]}
 
     def sampler(self, pixel, index, shuffles, global_seed):
         pixel = np.ascontiguousarray(pixel, dtype=np.uint32)

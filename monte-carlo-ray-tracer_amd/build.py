@@ -29,6 +29,9 @@ LIB_DENOISE = os.path.join(CSRC, "libmcrt_denoise.so")
 # The per-pixel sample statistics' two kernels (csrc/mcrt_pixel_stats.hip) likewise: a fourth code object;
 # tests/test_pixel_stats_library.py holds what it contains.
 LIB_PIXEL_STATS = os.path.join(CSRC, "libmcrt_pixel_stats.so")
+# The firefly suppression's two kernels (csrc/mcrt_robust.hip) likewise: a fifth code object; tests/test_robust_library.py holds what it
+# contains.
+LIB_ROBUST = os.path.join(CSRC, "libmcrt_robust.so")
 
 # -ffp-contract=off: the CPU reference is compiled by g++ for baseline x86-64 (no FMA contraction);
 # per-pixel FP64 parity needs the same rounding sequence on the GPU.
@@ -65,7 +68,7 @@ def sources():
 
 # the translation units that hold kernels of the render path: the tolerance library has its own objects of these
 KERNEL_TUS = ("mcrt_hip.hip", "mcrt_hip_lean.hip")
-TUS = ["mcrt_hip.hip", "mcrt_hip_lean.hip", "mcrt_octree_gpu.hip", "mcrt_sah_gpu.hip", "mcrt_output.hip", "mcrt_aov_host.hip", "mcrt_denoise_host.hip", "mcrt_pixel_stats_host.hip", "mcrt_multi.hip", "mcrt_image.cpp", "mcrt_octree.cpp", "mcrt_bvh.cpp"]
+TUS = ["mcrt_hip.hip", "mcrt_hip_lean.hip", "mcrt_octree_gpu.hip", "mcrt_sah_gpu.hip", "mcrt_output.hip", "mcrt_aov_host.hip", "mcrt_denoise_host.hip", "mcrt_pixel_stats_host.hip", "mcrt_robust_host.hip", "mcrt_multi.hip", "mcrt_image.cpp", "mcrt_octree.cpp", "mcrt_bvh.cpp"]
 OBJ = os.path.join(CSRC, "_obj")
 
 
@@ -135,7 +138,8 @@ def build_lib(force=False, verbose=True, tolerance=False, both=False):
                 print("[build] a dependency changed during the compile: again", flush=True)
         raise RuntimeError("sources kept changing while %s was being compiled" % cmd[-3])
 
-    for side_lib, side_src in ((LIB_AOV, "mcrt_aov.hip"), (LIB_DENOISE, "mcrt_denoise.hip"), (LIB_PIXEL_STATS, "mcrt_pixel_stats.hip")):  # one translation unit each, compiled and linked in one step
+    for side_lib, side_src in ((LIB_AOV, "mcrt_aov.hip"), (LIB_DENOISE, "mcrt_denoise.hip"), (LIB_PIXEL_STATS, "mcrt_pixel_stats.hip"),
+                               (LIB_ROBUST, "mcrt_robust.hip")):  # one translation unit each, compiled and linked in one step
         side_dep = os.path.join(OBJ, os.path.basename(side_lib)[:-3] + ".d")
         if force or not os.path.exists(side_lib) or _stale(side_lib, side_dep):
             jobs.append([_hipcc()] + HIPCC_FLAGS + ["-MD", "-MF", side_dep, os.path.join(CSRC, side_src), "-o", side_lib])
@@ -145,7 +149,7 @@ def build_lib(force=False, verbose=True, tolerance=False, both=False):
     for tol in variants:
         lib, objs = (LIB_TOL if tol else LIB), _objects(tol)
         if jobs or not os.path.exists(lib) or any(os.path.getmtime(o) > os.path.getmtime(lib) for o in objs):
-            run([_hipcc(), "--offload-arch=gfx950", "-shared", "-fPIC", "-o", lib] + objs + ["-L" + CSRC, "-lmcrt_aov", "-lmcrt_denoise", "-lmcrt_pixel_stats", "-Wl,-rpath,$ORIGIN"])
+            run([_hipcc(), "--offload-arch=gfx950", "-shared", "-fPIC", "-o", lib] + objs + ["-L" + CSRC, "-lmcrt_aov", "-lmcrt_denoise", "-lmcrt_pixel_stats", "-lmcrt_robust", "-Wl,-rpath,$ORIGIN"])
     return LIB_TOL if tolerance and not both else LIB
 
 

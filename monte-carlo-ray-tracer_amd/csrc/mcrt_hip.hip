@@ -29,6 +29,7 @@
 #include "mcrt_octree_shared.hpp"
 #include "mcrt_lean.hpp"
 #include "mcrt_pixel_stats_launch.hpp"
+#include "mcrt_robust_launch.hpp"
 
 #include <hipcub/hipcub.hpp>
 
@@ -127,6 +128,9 @@ struct mcrt_ctx {
     // per-pixel sample statistics wanted from the renders of this context (set for the length of a mcrt_render_pixel_stats* call, so that a
     // frame mcrt_render_finish renders again fills them again): packed like the frame; all nullptr = none, nothing in a render changes
     mcrt_pixel_stats_buffers stats_targets{nullptr, nullptr, nullptr};
+    DevBuf robust_buf[mcrt::kRobustScratchBufs];  // host-call frames of the firefly suppression (mcrt_robust_host.hip)
+    // the highlights wanted from the renders of this context (set for the length of a mcrt_render_highlights* call, like stats_targets)
+    mcrt_highlight_buffers highlight_targets{nullptr, nullptr};
     std::map<std::string, std::string> options;  // mcrt_set_option; seeded from the MCRT_* environment variables at mcrt_create
     DevBuf pm_iors;  // refraction histories of the 1024-lane photon-mapping kernel
     // the frame in flight, kept so that mcrt_render_finish can run it again through the wavefront pipeline (deep refraction histories)
@@ -545,6 +549,23 @@ int launchPassStats(mcrt_ctx* ctx, hipStream_t stream, const double* samples, ui
     return MCRT_OK;
 }
 
+// The highlights of a pass likewise (include/mcrt.h "Firefly suppression"): one launch of libmcrt_robust.so's kernel when the context
+// holds targets, the outputs offset to the pass's first pixel.
+int launchPassHighlights(mcrt_ctx* ctx, hipStream_t stream, const double* samples, uint64_t pass_pixels, uint32_t spp, size_t first_pixel) {
+    const mcrt_highlight_buffers& t = ctx->highlight_targets;
+    if (!t.tops && !t.level) return MCRT_OK;
+    HighlightsPass hp;
+    hp.samples = samples;
+    hp.pixels = pass_pixels;
+    hp.spp = spp;
+    hp.reserved = 0;
+    hp.tops = t.tops ? t.tops + first_pixel * (MCRT_ROBUST_TOPS * 3) : nullptr;
+    hp.level = t.level ? t.level + first_pixel : nullptr;
+    HIP_TRY(ctx, (hipError_t)launchHighlights(stream, hp));
+    ctx->launches++;
+    return MCRT_OK;
+}
+
 // The wavefront frame: the film, the pool and the passes (runWavefrontPass), so the call returns when the frame is complete;
 // mcrt_render_finish() then only collects the statistics.
 // film_out != NULL (mcrt_render_film_device): the splats of this shard's samples stay in the caller's full-frame RGBW buffer
@@ -625,6 +646,7 @@ int launchWavefront(mcrt_ctx* ctx, const mcrt_camera_desc* cam, uint32_t global_
             HIP_TRY(ctx, hipGetLastError());
             ctx->launches++;
             if (int rc = launchPassStats(ctx, stream, fr.samples, fr.pass_pixels, fr.spp, (size_t)fr.row_base * cam->width * 3)) return rc;
+            if (int rc = launchPassHighlights(ctx, stream, fr.samples, fr.pass_pixels, fr.spp, (size_t)fr.row_base * cam->width)) return rc;
         }
     }
     if (splats && !film_out) {
@@ -770,6 +792,7 @@ int launchRenderImpl(mcrt_ctx* ctx, const mcrt_camera_desc* cam, uint32_t global
                            prm.pass_pixels, prm.spp, d_out + (size_t)prm.row_base * cam->width * 3);
         ctx->launches += 2;
         if (int rc = launchPassStats(ctx, stream, prm.samples, prm.pass_pixels, prm.spp, (size_t)prm.row_base * cam->width * 3)) return rc;
+        if (int rc = launchPassHighlights(ctx, stream, prm.samples, prm.pass_pixels, prm.spp, (size_t)prm.row_base * cam->width)) return rc;
     }
     return endFrame(ctx, stream);
 }
@@ -1796,5 +1819,26 @@ void* ctxPixelStatsScratch(mcrt_ctx* ctx, int which, size_t bytes) {
         return nullptr;
     }
     return ctx->pixel_stats_buf[which].p;
+}
+
+int ctxHighlightsBegin(mcrt_ctx* ctx, const mcrt_camera_desc* cam, const mcrt_highlight_buffers* targets, const char* what) {
+    if (int rc = ctxPixelStatsReady(ctx, what)) return rc;
+    if (!ctx->has_scene) return fail(ctx, MCRT_ERR_NO_SCENE, std::string(what) + " before mcrt_upload_scene");
+    if (!cam) return fail(ctx, MCRT_ERR_INVALID, std::string(what) + ": camera is NULL");
+    const bool wanted = targets && (targets->tops || targets->level);
+    if (wanted && filmSplats(cam->film_filter, cam->film_radius))
+        return fail(ctx, MCRT_ERR_UNSUPPORTED, std::string(what) + ": a frame whose film splats (a reconstruction filter, or a box of another radius) keeps no "
+                                               "samples: there is nothing to take the highlights of");
+    ctx->highlight_targets = wanted ? *targets : mcrt_highlight_buffers{nullptr, nullptr};
+    return MCRT_OK;
+}
+void ctxHighlightsEnd(mcrt_ctx* ctx) { ctx->highlight_targets = mcrt_highlight_buffers{nullptr, nullptr}; }
+void* ctxRobustScratch(mcrt_ctx* ctx, int which, size_t bytes) {
+    if (which < 0 || which >= kRobustScratchBufs) return nullptr;
+    if (ctx->robust_buf[which].reserve(std::max<size_t>(bytes, 8)) != hipSuccess) {
+        (void)hipGetLastError();
+        return nullptr;
+    }
+    return ctx->robust_buf[which].p;
 }
 }  // namespace mcrt

@@ -48,4 +48,12 @@ int ctxPixelStatsReady(mcrt_ctx* ctx, const char* what);
 int ctxPixelStatsBegin(mcrt_ctx* ctx, const mcrt_camera_desc* cam, const mcrt_pixel_stats_buffers* targets, const char* what);
 void ctxPixelStatsEnd(mcrt_ctx* ctx);
 void* ctxPixelStatsScratch(mcrt_ctx* ctx, int which, size_t bytes);
+// mcrt_robust_host.hip (firefly suppression) likewise; its ready check is ctxPixelStatsReady. ctxHighlightsBegin: that check,
+// MCRT_ERR_NO_SCENE, MCRT_ERR_UNSUPPORTED for a camera whose film splats when a channel is wanted - then the channels are the targets
+// that the pass loops of the next renders of this context fill (one launch per pass), until ctxHighlightsEnd. ctxRobustScratch: buffer
+// `which` (0..kRobustScratchBufs-1: the frames of the host-pointer forms).
+constexpr int kRobustScratchBufs = 6;
+int ctxHighlightsBegin(mcrt_ctx* ctx, const mcrt_camera_desc* cam, const mcrt_highlight_buffers* targets, const char* what);
+void ctxHighlightsEnd(mcrt_ctx* ctx);
+void* ctxRobustScratch(mcrt_ctx* ctx, int which, size_t bytes);
 }  // namespace mcrt

@@ -4,7 +4,7 @@
 //
 //   mcrt_render scene.mcrt out.f64 [--width W --height H --sqrtspp S] [--seed N] [--photon] [--device D | --devices D0,D1,...]
 //               [--tga out.tga [--tonemapper hable|aces] [--exposure EV] [--gain EV] [--plain]] [--aov PREFIX]
-//               [--denoise OUT.f64 [--denoise-iterations N]] [--stats PREFIX]
+//               [--denoise OUT.f64 [--denoise-iterations N]] [--stats PREFIX] [--robust PREFIX [--robust-kappa X] [--robust-radius R]]
 //
 // Writes the frame as raw FP64 RGB, row-major (what Image::operator() holds, camera/image.cpp:53-56),
 // and prints the statistics. --tga also develops it the way Image::save does (auto exposure / gain, tone map, sRGB bytes:
@@ -16,6 +16,9 @@
 // stem + ".tga".
 // --stats renders the frame through mcrt_render_pixel_stats (the same frame) and also writes the per-pixel sample statistics,
 // PREFIX.variance.f64, .half_a.f64 and .half_b.f64 (raw FP64 RGB, row-major), and prints the frame summary of mcrt_frame_noise (one device).
+// --robust renders the frame through mcrt_render_highlights (the same frame; with --stats the statistics come from the same render) and
+// also writes the robust frame of mcrt_robust_resolve, PREFIX.robust.f64 and PREFIX.removed.f64 (raw FP64 RGB) and PREFIX.clamped.u32,
+// and prints how many pixels and samples were clamped and the luminance removed next to the frame's (one device).
 // --devices renders the frame on several GPUs from this one process (mcrt_render_multi: one host thread per GPU).
 #include <cstdio>
 #include <cstdlib>
@@ -44,7 +47,8 @@ int main(int argc, char** argv) {
     image.plain = (uint32_t)mcrt_image_param(img, "image_plain");
     image.exposure_compensation = from_bits(mcrt_image_param(img, "image_exposure_ev_bits"));
     image.gain_compensation = from_bits(mcrt_image_param(img, "image_gain_ev_bits"));
-    std::string tga, aov, denoise, pstats;
+    std::string tga, aov, denoise, pstats, robust;
+    mcrt_robust_params rparams{};
     mcrt_denoise_params dparams{};
     std::vector<int> devices;
     for (int i = 3; i < argc; i++) {
@@ -66,6 +70,9 @@ int main(int argc, char** argv) {
         else if (k == "--aov" && i + 1 < argc) aov = argv[++i];
         else if (k == "--denoise" && i + 1 < argc) denoise = argv[++i];
         else if (k == "--stats" && i + 1 < argc) pstats = argv[++i];
+        else if (k == "--robust" && i + 1 < argc) robust = argv[++i];
+        else if (k == "--robust-kappa" && i + 1 < argc) rparams.kappa = std::strtod(argv[++i], nullptr);
+        else if (k == "--robust-radius") rparams.radius = (uint32_t)val();
         else if (k == "--denoise-iterations") dparams.iterations = (uint32_t)val();
         else if (k == "--tonemapper" && i + 1 < argc) image.tonemapper = (argv[++i][0] | 0x20) == 'a' ? MCRT_TONEMAP_ACES : MCRT_TONEMAP_HABLE;
         else if (k == "--exposure" && i + 1 < argc) image.exposure_compensation = std::strtod(argv[++i], nullptr);
@@ -93,16 +100,26 @@ int main(int argc, char** argv) {
     mcrt_stats st;
     const int mode = photon ? MCRT_INTEGRATOR_PHOTON_MAPPER : MCRT_INTEGRATOR_PATH_TRACER;
     std::vector<double> variance, half_a, half_b;
-    if (rc == MCRT_OK && !pstats.empty()) {
+    std::vector<double> tops, level;
+    if (rc == MCRT_OK && (!pstats.empty() || !robust.empty())) {
         if (ctxs.size() > 1) {
-            std::fprintf(stderr, "--stats takes one device\n");
+            std::fprintf(stderr, "--stats and --robust take one device\n");
             return 2;
         }
-        variance.resize(rgb.size());
-        half_a.resize(rgb.size());
-        half_b.resize(rgb.size());
-        const mcrt_pixel_stats_buffers b{variance.data(), half_a.data(), half_b.data()};
-        rc = mcrt_render_pixel_stats(ctx, &cam, seed, mode, rgb.data(), &b, &st);
+        if (!pstats.empty()) {
+            variance.resize(rgb.size());
+            half_a.resize(rgb.size());
+            half_b.resize(rgb.size());
+        }
+        const bool ps = !pstats.empty();
+        const mcrt_pixel_stats_buffers b{ps ? variance.data() : nullptr, ps ? half_a.data() : nullptr, ps ? half_b.data() : nullptr};
+        if (!robust.empty()) {
+            tops.resize(rgb.size() * MCRT_ROBUST_TOPS);
+            level.resize(rgb.size() / 3);
+            const mcrt_highlight_buffers h{tops.data(), level.data()};
+            rc = mcrt_render_highlights(ctx, &cam, seed, mode, rgb.data(), &h, &b, &st);
+        } else
+            rc = mcrt_render_pixel_stats(ctx, &cam, seed, mode, rgb.data(), &b, &st);
     } else if (rc == MCRT_OK)
         rc = ctxs.size() > 1 ? mcrt_render_multi(ctxs.data(), (uint32_t)ctxs.size(), &cam, seed, mode, rgb.data(), &st)
                              : mcrt_render(ctx, &cam, seed, mode, rgb.data(), &st);
@@ -139,6 +156,44 @@ int main(int argc, char** argv) {
         }
         std::printf("{\"stats\":\"%s\",\"noise\":%.17g,\"signal\":%.17g,\"relative_error\":%.17g,\"pixels\":%llu}\n", pstats.c_str(), fn.noise, fn.signal,
                     fn.relative_error, (unsigned long long)fn.pixels);
+    }
+    if (!robust.empty()) {
+        const size_t px = (size_t)cam.width * cam.height;
+        std::vector<double> out(px * 3), removed(px * 3);
+        std::vector<uint32_t> clamped(px);
+        const mcrt_robust_buffers b{removed.data(), clamped.data()};
+        mcrt_stats rst;
+        rc = mcrt_robust_resolve(ctx, cam.width, cam.height, cam.sqrtspp * cam.sqrtspp, rgb.data(), tops.data(), level.data(), &rparams, out.data(), &b, &rst);
+        if (rc != MCRT_OK) {
+            std::fprintf(stderr, "mcrt error %d: %s\n", rc, mcrt_last_error(ctx));
+            return 1;
+        }
+        const struct {
+            const char* ext;
+            const void* data;
+            size_t bytes;
+        } files[3] = {{".robust.f64", out.data(), px * 24}, {".removed.f64", removed.data(), px * 24}, {".clamped.u32", clamped.data(), px * 4}};
+        for (const auto& c : files) {
+            const std::string path = robust + c.ext;
+            FILE* o = std::fopen(path.c_str(), "wb");
+            const bool ok = o && std::fwrite(c.data, 1, c.bytes, o) == c.bytes;
+            if (o) std::fclose(o);
+            if (!ok) {
+                std::fprintf(stderr, "cannot write %s\n", path.c_str());
+                return 1;
+            }
+        }
+        unsigned long long pixels = 0, samples = 0;
+        double gone = 0.0, all = 0.0;  // luminance, added up in pixel order
+        for (size_t p = 0; p < px; p++) {
+            pixels += clamped[p] ? 1 : 0;
+            samples += clamped[p];
+            gone += (0.2126 * removed[p * 3] + 0.7152 * removed[p * 3 + 1]) + 0.0722 * removed[p * 3 + 2];
+            all += (0.2126 * rgb[p * 3] + 0.7152 * rgb[p * 3 + 1]) + 0.0722 * rgb[p * 3 + 2];
+        }
+        std::printf("{\"robust\":\"%s\",\"clamped_pixels\":%llu,\"clamped_samples\":%llu,\"removed_energy\":%.17g,\"frame_energy\":%.17g,"
+                    "\"removed_fraction\":%.17g,\"kernel_ms\":%.3f}\n",
+                    robust.c_str(), pixels, samples, gone, all, all > 0.0 ? gone / all : 0.0, rst.kernel_ms);
     }
     auto develop = [&](const std::vector<double>& frame, const std::string& path) {
         image.width = cam.width;
