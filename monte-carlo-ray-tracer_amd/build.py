@@ -18,20 +18,13 @@ LIB = os.path.join(CSRC, "libmcrt_hip.so")
 LIB_TOL = os.path.join(CSRC, "libmcrt_hip_tol.so")
 TOL_FLAGS = ["-ffp-contract=fast", "-DMCRT_PLATFORM_LIBM", "-DMCRT_TOLERANCE_BUILD"]
 RENDER_BIN = os.path.join(HOST, "mcrt_render")
-# The first-hit AOV pass's two kernels and their launch functions (csrc/mcrt_aov.hip) are a shared library of their own, which both
-# libraries above link (the tolerance one too: the exact object): the gfx950 functions of libmcrt_hip.so stay the render path's, the
-# set tests/golden/device_code_hashes.json lists; tests/test_aov_library.py holds what each library may contain.
-# libmcrt_aov.so has to lie next to libmcrt_hip.so wherever that goes (RUNPATH $ORIGIN).
-LIB_AOV = os.path.join(CSRC, "libmcrt_aov.so")
-# The a-trous filter's three kernels (csrc/mcrt_denoise.hip) likewise: a third code object, linked and found the same way;
-# tests/test_denoise_library.py holds what it contains.
-LIB_DENOISE = os.path.join(CSRC, "libmcrt_denoise.so")
-# The per-pixel sample statistics' two kernels (csrc/mcrt_pixel_stats.hip) likewise: a fourth code object;
-# tests/test_pixel_stats_library.py holds what it contains.
-LIB_PIXEL_STATS = os.path.join(CSRC, "libmcrt_pixel_stats.so")
-# The firefly suppression's two kernels (csrc/mcrt_robust.hip) likewise: a fifth code object; tests/test_robust_library.py holds what it
-# contains.
-LIB_ROBUST = os.path.join(CSRC, "libmcrt_robust.so")
+# The kernels of the image passes are shared libraries of their own, one translation unit each, which both libraries above link (the
+# tolerance one too: the exact objects): the gfx950 functions of libmcrt_hip.so stay the render path's, the set
+# tests/golden/device_code_hashes.json lists; tests/test_{aov,denoise,pixel_stats,robust}_library.py hold what each library may contain.
+# They have to lie next to libmcrt_hip.so wherever that goes (RUNPATH $ORIGIN). In link order: the first-hit AOV pass, the a-trous filter,
+# the per-pixel sample statistics, the firefly suppression.
+SIDE_LIBS = [(os.path.join(CSRC, "lib%s.so" % name), name + ".hip") for name in ("mcrt_aov", "mcrt_denoise", "mcrt_pixel_stats", "mcrt_robust")]
+LIB_AOV, LIB_DENOISE, LIB_PIXEL_STATS, LIB_ROBUST = (lib for lib, _ in SIDE_LIBS)
 
 # -ffp-contract=off: the CPU reference is compiled by g++ for baseline x86-64 (no FMA contraction);
 # per-pixel FP64 parity needs the same rounding sequence on the GPU.
@@ -138,8 +131,7 @@ def build_lib(force=False, verbose=True, tolerance=False, both=False):
                 print("[build] a dependency changed during the compile: again", flush=True)
         raise RuntimeError("sources kept changing while %s was being compiled" % cmd[-3])
 
-    for side_lib, side_src in ((LIB_AOV, "mcrt_aov.hip"), (LIB_DENOISE, "mcrt_denoise.hip"), (LIB_PIXEL_STATS, "mcrt_pixel_stats.hip"),
-                               (LIB_ROBUST, "mcrt_robust.hip")):  # one translation unit each, compiled and linked in one step
+    for side_lib, side_src in SIDE_LIBS:  # one translation unit each, compiled and linked in one step
         side_dep = os.path.join(OBJ, os.path.basename(side_lib)[:-3] + ".d")
         if force or not os.path.exists(side_lib) or _stale(side_lib, side_dep):
             jobs.append([_hipcc()] + HIPCC_FLAGS + ["-MD", "-MF", side_dep, os.path.join(CSRC, side_src), "-o", side_lib])
@@ -149,7 +141,7 @@ def build_lib(force=False, verbose=True, tolerance=False, both=False):
     for tol in variants:
         lib, objs = (LIB_TOL if tol else LIB), _objects(tol)
         if jobs or not os.path.exists(lib) or any(os.path.getmtime(o) > os.path.getmtime(lib) for o in objs):
-            run([_hipcc(), "--offload-arch=gfx950", "-shared", "-fPIC", "-o", lib] + objs + ["-L" + CSRC, "-lmcrt_aov", "-lmcrt_denoise", "-lmcrt_pixel_stats", "-lmcrt_robust", "-Wl,-rpath,$ORIGIN"])
+            run([_hipcc(), "--offload-arch=gfx950", "-shared", "-fPIC", "-o", lib] + objs + ["-L" + CSRC] + ["-l" + os.path.basename(side_lib)[3:-3] for side_lib, _ in SIDE_LIBS] + ["-Wl,-rpath,$ORIGIN"])
     return LIB_TOL if tolerance and not both else LIB
 
 

@@ -122,13 +122,12 @@ struct mcrt_ctx {
     // scratch of the operator-level entry points (mcrt_intersect / mcrt_knn / mcrt_sampler / mcrt_bsdf): kept between calls, grown
     // on demand, so that a host that only wants traversal or k-NN does not pay five hipMalloc / hipFree pairs per call
     DevBuf op_buf[6];
-    DevBuf aov_buf[mcrt::kAovScratchBufs];  // the first-hit AOV pass's rays, hits and host-call channels (mcrt_aov_host.hip), grown on demand too
-    DevBuf denoise_buf[mcrt::kDenoiseScratchBufs];  // the a-trous filter's packed guides, two irradiance frames and host-call staging (mcrt_denoise_host.hip)
-    DevBuf pixel_stats_buf[mcrt::kPixelStatsScratchBufs];  // host-call frames and the summary's block values (mcrt_pixel_stats_host.hip)
+    // scratch of the image passes (mcrt_pass_host.hpp: AOV, a-trous filter, sample statistics, firefly suppression), grown on demand too:
+    // every (family, slot) a buffer of its own (ctxPassScratch)
+    DevBuf pass_buf[mcrt::kPassFamilies][mcrt::kPassSlots];
     // per-pixel sample statistics wanted from the renders of this context (set for the length of a mcrt_render_pixel_stats* call, so that a
     // frame mcrt_render_finish renders again fills them again): packed like the frame; all nullptr = none, nothing in a render changes
     mcrt_pixel_stats_buffers stats_targets{nullptr, nullptr, nullptr};
-    DevBuf robust_buf[mcrt::kRobustScratchBufs];  // host-call frames of the firefly suppression (mcrt_robust_host.hip)
     // the highlights wanted from the renders of this context (set for the length of a mcrt_render_highlights* call, like stats_targets)
     mcrt_highlight_buffers highlight_targets{nullptr, nullptr};
     std::map<std::string, std::string> options;  // mcrt_set_option; seeded from the MCRT_* environment variables at mcrt_create
@@ -1749,11 +1748,23 @@ int ctxDevice(const mcrt_ctx* ctx) { return ctx->device; }
 void* ctxStream(const mcrt_ctx* ctx) { return (void*)ctx->stream; }
 int ctxFail(mcrt_ctx* ctx, int code, const std::string& msg) { return fail(ctx, code, msg); }
 
-int ctxAovReady(mcrt_ctx* ctx, const char* what) {
-    if (!ctx->has_scene) return fail(ctx, MCRT_ERR_NO_SCENE, std::string(what) + " before mcrt_upload_scene");
+// the hooks of the image passes' host toolkit (mcrt_internal.hpp)
+int ctxIdle(mcrt_ctx* ctx, const char* what) {
     if (ctx->pending) return fail(ctx, MCRT_ERR_INVALID, std::string(what) + ": a render is in flight, call mcrt_render_finish first");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     return MCRT_OK;
+}
+int ctxNeedScene(mcrt_ctx* ctx, const char* what) {
+    return ctx->has_scene ? MCRT_OK : fail(ctx, MCRT_ERR_NO_SCENE, std::string(what) + " before mcrt_upload_scene");
+}
+void* ctxPassScratch(mcrt_ctx* ctx, PassFamily family, int which, size_t bytes) {
+    if (family < 0 || family >= kPassFamilies || which < 0 || which >= kPassSlots) return nullptr;
+    DevBuf& buf = ctx->pass_buf[family][which];
+    if (buf.reserve(std::max<size_t>(bytes, 8)) != hipSuccess) {
+        (void)hipGetLastError();
+        return nullptr;
+    }
+    return buf.p;
 }
 void ctxAovScene(const mcrt_ctx* ctx, AovScene* out, const uint32_t** sobol_tab) {
     const DeviceScene& d = ctx->scene;
@@ -1772,73 +1783,30 @@ void ctxAovScene(const mcrt_ctx* ctx, AovScene* out, const uint32_t** sobol_tab)
     out->prim = d.prim;
     *sobol_tab = d.sobol_tab;
 }
-void* ctxAovScratch(mcrt_ctx* ctx, int which, size_t bytes) {
-    if (which < 0 || which >= kAovScratchBufs) return nullptr;
-    if (ctx->aov_buf[which].reserve(std::max<size_t>(bytes, 8)) != hipSuccess) {
-        (void)hipGetLastError();
-        return nullptr;
-    }
-    return ctx->aov_buf[which].p;
-}
-
-int ctxDenoiseReady(mcrt_ctx* ctx, const char* what) {
-    if (ctx->pending) return fail(ctx, MCRT_ERR_INVALID, std::string(what) + ": a render is in flight, call mcrt_render_finish first");
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    return MCRT_OK;
-}
-void* ctxDenoiseScratch(mcrt_ctx* ctx, int which, size_t bytes) {
-    if (which < 0 || which >= kDenoiseScratchBufs) return nullptr;
-    if (ctx->denoise_buf[which].reserve(std::max<size_t>(bytes, 8)) != hipSuccess) {
-        (void)hipGetLastError();
-        return nullptr;
-    }
-    return ctx->denoise_buf[which].p;
-}
-
-int ctxPixelStatsReady(mcrt_ctx* ctx, const char* what) {
-    if (ctx->pending) return fail(ctx, MCRT_ERR_INVALID, std::string(what) + ": a render is in flight, call mcrt_render_finish first");
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
+// what a render may take per-sample `noun` for: idle, a scene, a camera, and a film that keeps its samples when a channel is wanted
+static int sampleTargetsCheck(mcrt_ctx* ctx, const mcrt_camera_desc* cam, bool wanted, const char* what, const char* noun) {
+    if (int rc = ctxIdle(ctx, what)) return rc;
+    if (int rc = ctxNeedScene(ctx, what)) return rc;
+    if (!cam) return fail(ctx, MCRT_ERR_INVALID, std::string(what) + ": camera is NULL");
+    if (wanted && filmSplats(cam->film_filter, cam->film_radius))
+        return fail(ctx, MCRT_ERR_UNSUPPORTED, std::string(what) + ": a frame whose film splats (a reconstruction filter, or a box of another radius) keeps no "
+                                               "samples: there is nothing to take the " + noun + " of");
     return MCRT_OK;
 }
 int ctxPixelStatsBegin(mcrt_ctx* ctx, const mcrt_camera_desc* cam, const mcrt_pixel_stats_buffers* targets, const char* what) {
-    if (int rc = ctxPixelStatsReady(ctx, what)) return rc;
-    if (!ctx->has_scene) return fail(ctx, MCRT_ERR_NO_SCENE, std::string(what) + " before mcrt_upload_scene");
-    if (!cam) return fail(ctx, MCRT_ERR_INVALID, std::string(what) + ": camera is NULL");
     const bool wanted = targets && (targets->variance || targets->half_a || targets->half_b);
-    if (wanted && filmSplats(cam->film_filter, cam->film_radius))
-        return fail(ctx, MCRT_ERR_UNSUPPORTED, std::string(what) + ": a frame whose film splats (a reconstruction filter, or a box of another radius) keeps no "
-                                               "samples: there is nothing to take the statistics of");
+    if (int rc = sampleTargetsCheck(ctx, cam, wanted, what, "statistics")) return rc;
     ctx->stats_targets = wanted ? *targets : mcrt_pixel_stats_buffers{nullptr, nullptr, nullptr};
     return MCRT_OK;
 }
-void ctxPixelStatsEnd(mcrt_ctx* ctx) { ctx->stats_targets = mcrt_pixel_stats_buffers{nullptr, nullptr, nullptr}; }
-void* ctxPixelStatsScratch(mcrt_ctx* ctx, int which, size_t bytes) {
-    if (which < 0 || which >= kPixelStatsScratchBufs) return nullptr;
-    if (ctx->pixel_stats_buf[which].reserve(std::max<size_t>(bytes, 8)) != hipSuccess) {
-        (void)hipGetLastError();
-        return nullptr;
-    }
-    return ctx->pixel_stats_buf[which].p;
-}
-
 int ctxHighlightsBegin(mcrt_ctx* ctx, const mcrt_camera_desc* cam, const mcrt_highlight_buffers* targets, const char* what) {
-    if (int rc = ctxPixelStatsReady(ctx, what)) return rc;
-    if (!ctx->has_scene) return fail(ctx, MCRT_ERR_NO_SCENE, std::string(what) + " before mcrt_upload_scene");
-    if (!cam) return fail(ctx, MCRT_ERR_INVALID, std::string(what) + ": camera is NULL");
     const bool wanted = targets && (targets->tops || targets->level);
-    if (wanted && filmSplats(cam->film_filter, cam->film_radius))
-        return fail(ctx, MCRT_ERR_UNSUPPORTED, std::string(what) + ": a frame whose film splats (a reconstruction filter, or a box of another radius) keeps no "
-                                               "samples: there is nothing to take the highlights of");
+    if (int rc = sampleTargetsCheck(ctx, cam, wanted, what, "highlights")) return rc;
     ctx->highlight_targets = wanted ? *targets : mcrt_highlight_buffers{nullptr, nullptr};
     return MCRT_OK;
 }
-void ctxHighlightsEnd(mcrt_ctx* ctx) { ctx->highlight_targets = mcrt_highlight_buffers{nullptr, nullptr}; }
-void* ctxRobustScratch(mcrt_ctx* ctx, int which, size_t bytes) {
-    if (which < 0 || which >= kRobustScratchBufs) return nullptr;
-    if (ctx->robust_buf[which].reserve(std::max<size_t>(bytes, 8)) != hipSuccess) {
-        (void)hipGetLastError();
-        return nullptr;
-    }
-    return ctx->robust_buf[which].p;
+void ctxSampleTargetsEnd(mcrt_ctx* ctx) {
+    ctx->stats_targets = mcrt_pixel_stats_buffers{nullptr, nullptr, nullptr};
+    ctx->highlight_targets = mcrt_highlight_buffers{nullptr, nullptr};
 }
 }  // namespace mcrt

@@ -25,35 +25,23 @@ int launchPowKat(void* stream, uint64_t n, const double* a, const double* b, dou
 // mcrt_hip.hip: Scene::intersect on n rays in DEVICE arrays - the body of mcrt_intersect behind its uploads (trees in memory: the trace
 // kernel fed from the arrays, otherwise the intersect kernel). d_uv must not be null. Synchronous on the context's stream.
 int intersectDeviceArrays(mcrt_ctx* ctx, uint64_t n, const double* d_start, const double* d_dir, double* d_t, uint32_t* d_surf, double* d_uv);
-// mcrt_aov_host.hip (the first-hit AOV pass's host side) reaches the context through these. ctxAovReady: device selected, MCRT_ERR_NO_SCENE / MCRT_ERR_INVALID (render in flight)
-// recorded under `what`. ctxAovScene: the uploaded scene's arrays in device memory. ctxAovScratch: buffer `which` (0..kAovScratchBufs-1)
-// of the pass's scratch, kept in the context and grown on demand like the operators'; nullptr when the allocation fails.
+// The hooks of the image passes' host toolkit (mcrt_pass_host.hpp; DESIGN.md "Image passes"), which mcrt_aov_host.hip, mcrt_denoise_host.hip,
+// mcrt_pixel_stats_host.hip and mcrt_robust_host.hip reach the context through.
+// ctxIdle: no render in flight (MCRT_ERR_INVALID recorded under `what`), device selected. ctxNeedScene: MCRT_ERR_NO_SCENE under `what`.
+// ctxPassScratch: buffer `which` (0..kPassSlots-1) of a family's scratch - every (family, slot) a buffer of its own, kept in the context
+// and grown on demand like the operators'; at least 8 bytes; nullptr, the HIP error cleared, when the allocation fails.
+// ctxAovScene: the uploaded scene's arrays in device memory.
+// ctxPixelStatsBegin / ctxHighlightsBegin: ctxIdle, ctxNeedScene, MCRT_ERR_INVALID for no camera, MCRT_ERR_UNSUPPORTED for a camera whose
+// film splats when a channel is wanted - then the channels (nullptr: none) are the targets that the pass loops of the next renders of this
+// context fill (one launch per pass after the integrator's), until ctxSampleTargetsEnd clears both sets (SampleTargetsScope does).
 struct AovScene;
-constexpr int kAovScratchBufs = 6;
-int ctxAovReady(mcrt_ctx* ctx, const char* what);
+enum PassFamily { kPassAov, kPassDenoise, kPassPixelStats, kPassRobust, kPassFamilies };
+constexpr int kPassSlots = 6;
+int ctxIdle(mcrt_ctx* ctx, const char* what);
+int ctxNeedScene(mcrt_ctx* ctx, const char* what);
+void* ctxPassScratch(mcrt_ctx* ctx, PassFamily family, int which, size_t bytes);
 void ctxAovScene(const mcrt_ctx* ctx, AovScene* out, const uint32_t** sobol_tab);
-void* ctxAovScratch(mcrt_ctx* ctx, int which, size_t bytes);
-// mcrt_denoise_host.hip (the a-trous filter's host side) likewise. ctxDenoiseReady: device selected, MCRT_ERR_INVALID (render in flight)
-// recorded under `what`; no scene is needed. ctxDenoiseScratch: buffer `which` (0..kDenoiseScratchBufs-1) of the filter's scratch.
-constexpr int kDenoiseScratchBufs = 4;
-int ctxDenoiseReady(mcrt_ctx* ctx, const char* what);
-void* ctxDenoiseScratch(mcrt_ctx* ctx, int which, size_t bytes);
-// mcrt_pixel_stats_host.hip (per-pixel sample statistics, frame summary). ctxPixelStatsReady: device selected, MCRT_ERR_INVALID (render in
-// flight) recorded under `what`; no scene is needed. ctxPixelStatsBegin: that, MCRT_ERR_NO_SCENE, MCRT_ERR_UNSUPPORTED for a camera whose
-// film splats when a channel is wanted - then the channels (nullptr: none) are the targets that the pass loops of the next renders of
-// this context fill (one launch per pass after the integrator's), until ctxPixelStatsEnd. ctxPixelStatsScratch: buffer `which`
-// (0..kPixelStatsScratchBufs-1: four frames of the host-pointer forms, two of the summary's block values).
-constexpr int kPixelStatsScratchBufs = 6;
-int ctxPixelStatsReady(mcrt_ctx* ctx, const char* what);
 int ctxPixelStatsBegin(mcrt_ctx* ctx, const mcrt_camera_desc* cam, const mcrt_pixel_stats_buffers* targets, const char* what);
-void ctxPixelStatsEnd(mcrt_ctx* ctx);
-void* ctxPixelStatsScratch(mcrt_ctx* ctx, int which, size_t bytes);
-// mcrt_robust_host.hip (firefly suppression) likewise; its ready check is ctxPixelStatsReady. ctxHighlightsBegin: that check,
-// MCRT_ERR_NO_SCENE, MCRT_ERR_UNSUPPORTED for a camera whose film splats when a channel is wanted - then the channels are the targets
-// that the pass loops of the next renders of this context fill (one launch per pass), until ctxHighlightsEnd. ctxRobustScratch: buffer
-// `which` (0..kRobustScratchBufs-1: the frames of the host-pointer forms).
-constexpr int kRobustScratchBufs = 6;
 int ctxHighlightsBegin(mcrt_ctx* ctx, const mcrt_camera_desc* cam, const mcrt_highlight_buffers* targets, const char* what);
-void ctxHighlightsEnd(mcrt_ctx* ctx);
-void* ctxRobustScratch(mcrt_ctx* ctx, int which, size_t bytes);
+void ctxSampleTargetsEnd(mcrt_ctx* ctx);
 }  // namespace mcrt
