@@ -364,6 +364,70 @@ int mcrt_denoise(mcrt_ctx* ctx, uint32_t width, uint32_t height, const double* r
                  const mcrt_denoise_params* params, double* out_rgb, mcrt_stats* stats /* may be NULL */);
 
 /* ------------------------------------------------------------------------------------------
+ * Variance-guided denoised output: the same a-trous filter with its colour weight measured in units of the pixels' estimated
+ * variance instead of a fixed contrast, and that variance carried through the iterations - the filtered frame comes back with
+ * an estimate of its own error in the form mcrt_frame_noise reads. The reference has no such output. Only FP64 + - * /, compare
+ * and select, in the order written here, uncontracted, no libm routine: a function of its inputs bit for bit.
+ *
+ * Inputs are FULL frames [height][width]...: the beauty frame c, its per-pixel sample variance v (the `variance` channel of
+ * mcrt_render_pixel_stats* at the same camera, seed and spp = n samples per pixel), and the guides mcrt_denoise reads (Ns, N, P,
+ * coverage, albedo). dot, max0, h, the tap order, the coverage rules, w_n and w_z are exactly mcrt_denoise's (above);
+ * g(V) = (V.x + V.y) + V.z.
+ * Demodulate, per pixel and channel: a as in mcrt_denoise, I_0 = c / a, and the variance of the pixel's mean in the demodulated
+ * frame u_ch = (v_ch / (double)n) / (a_ch * a_ch).
+ * Prefilter the variance (a sample variance of 4 samples is itself noisy): a pixel with coverage(p) == 0 has V_0(p) = u(p). For
+ * every other p the taps q = p + (dx, dy) are visited with dy = -1..1 as the outer and dx = -1..1 as the inner loop,
+ * k = {1/4, 1/2, 1/4}, kw = k[dy] * k[dx]; taps outside the frame or with coverage(q) == 0 are skipped;
+ *   s_ch += kw * u_ch(q), ks += kw (both from 0.0, in tap order); V_0(p)_ch = s_ch * (1.0 / ks) (the centre always counts).
+ * Iterate, for i = 0 .. iterations-1 with step s = 2^i; sv2 = sigma_variance * sigma_variance, sf2 = sigma_floor * sigma_floor,
+ * sz2 = sigma_plane * sigma_plane are computed once on the host and neither sigma shrinks with i (the variance shrinks by itself
+ * as the filter averages):
+ *   a pixel p with coverage(p) == 0 keeps I and V. For every other p the 25 taps q = p + s * (dx, dy) are visited as in mcrt_denoise;
+ *     the centre tap has weight w = 9/64 exactly; a tap outside the frame or with coverage(q) == 0 is skipped;
+ *     every other tap has w = (((h[dy] * h[dx]) * w_n) * w_z) * w_c with
+ *       e = |I_i(p) - I_i(q)|^2, m = |I_i(p)|^2 + |I_i(q)|^2, den = (sv2 * (g(V_i(p)) + g(V_i(q)))) + (sf2 * m),
+ *       x_c = e == 0 ? 0 : e / den (a zero den with e > 0 gives +Inf and so weight 0), w_c = max0(1 - x_c), w_c = w_c * w_c
+ *         (the squared difference against sigma_variance^2 times the variance of that difference, plus a scale-free floor for
+ *         pixels whose few samples happened to agree)
+ *     sum_ch += w * I_i(q)_ch, vsum_ch += (w * w) * V_i(q)_ch, wsum += w (all from 0.0, in tap order);
+ *     r = 1.0 / wsum, I_{i+1}(p)_ch = sum_ch * r, V_{i+1}(p)_ch = vsum_ch * (r * r).
+ * Remodulate: out = I_n * a, out_variance_ch = (V_n,ch * (a_ch * a_ch)) * (double)n - a sample-variance equivalent, so
+ * mcrt_frame_noise(out, out_variance, n) is the filtered frame's summary with no new call.
+ * out_variance is the estimate under INDEPENDENT inputs. The prefilter already, and every iteration from the second on, combine
+ * pixels that share samples, and the filter's bias is not in it, so it underestimates the filter's own part. Measured (four scenes,
+ * 192 x 108, sigma_variance 3.0 and sigma_floor 0.05 - not the defaults; profiles/NOTES_denoise_variance.md): the mean of g(out_variance) / n over the covered pixels is 0.59 - 3.2 times the
+ * filtered frame's mean squared error to a 1024-spp render at 4 and 16 spp - below 1 on the specular scenes, above 1 where the
+ * render's stratified samples make a pixel's mean better than v / n says - and 0 at 1 spp, where v is 0: a guide, not a bound.
+ * NaN, Inf and negative variances are not filtered out. A NaN or Inf in c, v, Ns, N or P reaches every pixel whose taps read it
+ * (through the sums, or through a NaN weight) and spreads with every iteration; the prefilter spreads one in v over its 3 x 3
+ * neighbours first. A negative variance enters den as it is: den < 0 with e > 0 gives x_c < 0 and so w_c > 1, and it is carried
+ * into out_variance. A NaN coverage counts as covered; a NaN albedo counts as below the floor (a = 1).
+ * d_out_rgb may be d_rgb and d_out_variance may be d_variance; d_out_variance NULL: the frame alone. Intermediate frames live in
+ * scratch the context owns (176 B per pixel, kept between calls). The call is synchronous on the context's stream, needs no
+ * uploaded scene, and is refused (MCRT_ERR_INVALID) while a render is in flight, when a pointer it needs is NULL (albedo only
+ * without MCRT_DENOISE_NO_ALBEDO), when spp is 0, when width * height is 0 or >= 2^32, with more than 16 iterations,
+ * normal_power_log2 > 32, or a sigma that is negative or not finite.
+ * stats: kernel_ms, total_ms, kernel_launches (1 + iterations).
+ * Option MCRT_DENOISE_VAR_FORM: "tile" / "plain" / unset = the measured choice per step, as MCRT_DENOISE_FORM; the same bits. */
+typedef struct mcrt_denoise_variance_params {   /* NULL or a zero field = the default */
+    uint32_t iterations;         /* default 5; more than 16: MCRT_ERR_INVALID */
+    uint32_t normal_power_log2;  /* default 7 (exponent 128); more than 32: MCRT_ERR_INVALID */
+    double   sigma_variance;     /* default 6.0 */
+    double   sigma_floor;        /* default 0.02 */
+    double   sigma_plane;        /* default 0.1 */
+    double   albedo_floor;       /* default 1e-3 */
+    uint32_t flags, reserved;    /* MCRT_DENOISE_NO_ALBEDO */
+} mcrt_denoise_variance_params;                  /* 48 bytes */
+int mcrt_denoise_variance_device(mcrt_ctx* ctx, uint32_t width, uint32_t height, uint32_t spp, const double* d_rgb,
+                                 const double* d_variance, const mcrt_aov_buffers* guides /* full-frame DEVICE pointers */,
+                                 const mcrt_denoise_variance_params* params, double* d_out_rgb,
+                                 double* d_out_variance /* may be NULL */, mcrt_stats* stats /* may be NULL */);
+/* Same with HOST pointers (out_rgb may be rgb, out_variance may be variance or NULL). */
+int mcrt_denoise_variance(mcrt_ctx* ctx, uint32_t width, uint32_t height, uint32_t spp, const double* rgb, const double* variance,
+                          const mcrt_aov_buffers* guides, const mcrt_denoise_variance_params* params, double* out_rgb,
+                          double* out_variance /* may be NULL */, mcrt_stats* stats /* may be NULL */);
+
+/* ------------------------------------------------------------------------------------------
  * Per-pixel sample statistics: the spread of a pixel's samples next to their mean - the sample variance and the two half-buffers
  * (the means of the even and of the odd samples) that error estimators, stopping rules and denoisers start from. The reference
  * has no such output. Every box-filter frame keeps the radiance of every sample until its pass is resolved; the statistics are

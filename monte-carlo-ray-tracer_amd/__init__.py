@@ -177,6 +177,12 @@ DENOISE_NO_ALBEDO = 1
 DENOISE_GUIDES = ("shading_normal", "normal", "position", "coverage", "albedo")
 
 
+class DenoiseVarianceParams(C.Structure):
+    """mcrt_denoise_variance_params: a zero field = the default (include/mcrt.h)."""
+    _fields_ = [("iterations", C.c_uint32), ("normal_power_log2", C.c_uint32), ("sigma_variance", C.c_double), ("sigma_floor", C.c_double),
+                ("sigma_plane", C.c_double), ("albedo_floor", C.c_double), ("flags", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 class PixelStatsBuffers(C.Structure):
     """mcrt_pixel_stats_buffers: a null pointer = channel not wanted."""
     _fields_ = [("variance", C.c_void_p), ("half_a", C.c_void_p), ("half_b", C.c_void_p)]
@@ -304,6 +310,10 @@ def lib():
     if hasattr(L, "mcrt_denoise"):  # (likewise)
         L.mcrt_denoise.argtypes = [vp, C.c_uint32, C.c_uint32, vp, C.POINTER(AovBuffers), C.POINTER(DenoiseParams), vp, C.POINTER(Stats)]
         L.mcrt_denoise_device.argtypes = [vp, C.c_uint32, C.c_uint32, vp, C.POINTER(AovBuffers), C.POINTER(DenoiseParams), vp, C.POINTER(Stats)]
+    if hasattr(L, "mcrt_denoise_variance"):  # (likewise)
+        L.mcrt_denoise_variance.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, C.POINTER(AovBuffers), C.POINTER(DenoiseVarianceParams), vp, vp,
+                                            C.POINTER(Stats)]
+        L.mcrt_denoise_variance_device.argtypes = L.mcrt_denoise_variance.argtypes
     if hasattr(L, "mcrt_render_pixel_stats"):  # (likewise)
         L.mcrt_render_pixel_stats.argtypes = [vp, C.POINTER(CameraDesc), C.c_uint32, C.c_int, vp, C.POINTER(PixelStatsBuffers), C.POINTER(Stats)]
         L.mcrt_render_pixel_stats_device.argtypes = [vp, C.POINTER(CameraDesc), C.c_uint32, C.c_int, vp, C.POINTER(PixelStatsBuffers), C.POINTER(Stats)]
@@ -793,6 +803,63 @@ class Context:
         self._check(self._lib.mcrt_denoise_device(self._h, int(width), int(height), C.c_void_p(int(rgb_ptr)) if rgb_ptr else None, C.byref(bufs), C.byref(par),
                                                   C.c_void_p(int(out_ptr)) if out_ptr else None, C.byref(st)), "mcrt_denoise_device")
         return st.as_dict()
+
+    def denoise_variance(self, rgb, variance, aov, spp, stats=None, want_variance=True, **params):
+        """mcrt_denoise_variance: the a-trous filter steered by the per-pixel sample variance [H,W,3] of the beauty frame rgb [H,W,3]
+        (render_pixel_stats' "variance" at spp samples per pixel), guided by aov as denoise is -> (the filtered frame, its variance in
+        the form frame_noise reads; None with want_variance=False). params: the fields of mcrt_denoise_variance_params (iterations,
+        normal_power_log2, sigma_variance, sigma_floor, sigma_plane, albedo_floor, flags); left out = the default. stats: a dict that
+        receives mcrt_stats."""
+        self._sync_env()
+        rgb = np.ascontiguousarray(rgb, dtype=np.float64)
+        variance = np.ascontiguousarray(variance, dtype=np.float64)
+        assert rgb.ndim == 3 and rgb.shape[2] == 3 and variance.shape == rgb.shape, (rgb.shape, variance.shape)
+        height, width = rgb.shape[:2]
+        par = DenoiseVarianceParams(**params)
+        bufs, keep = AovBuffers(), []
+        for name in DENOISE_GUIDES:
+            if name not in aov or aov[name] is None:
+                continue  # (the library names a channel it misses)
+            a = np.ascontiguousarray(aov[name], dtype=np.float64)
+            assert a.shape == (height, width) + ((3,) if AOV_CHANNELS[name][1] == 3 else ()), (name, a.shape)
+            keep.append(a)
+            setattr(bufs, name, a.ctypes.data)
+        out, out_var = np.empty_like(rgb), (np.empty_like(rgb) if want_variance else None)
+        st = Stats()
+        self._check(self._lib.mcrt_denoise_variance(self._h, width, height, int(spp), rgb.ctypes.data, variance.ctypes.data, C.byref(bufs), C.byref(par),
+                                                    out.ctypes.data, out_var.ctypes.data if want_variance else None, C.byref(st)), "mcrt_denoise_variance")
+        if stats is not None:
+            stats.update(st.as_dict())
+        return out, out_var
+
+    def denoise_variance_device(self, width, height, spp, rgb_ptr, variance_ptr, pointers, out_ptr, out_variance_ptr=None, **params):
+        """mcrt_denoise_variance_device: rgb_ptr / out_ptr and variance_ptr / out_variance_ptr (each pair may be the same; out_variance_ptr
+        None = not wanted) and pointers = dict guide channel -> raw device pointer, all full frames that are complete when this is called.
+        Synchronous; returns the stats dict."""
+        self._sync_env()
+        bufs = AovBuffers()
+        for name, ptr in pointers.items():
+            assert name in AOV_CHANNELS, name
+            setattr(bufs, name, int(ptr) if ptr else None)
+        par = DenoiseVarianceParams(**params)
+        st = Stats()
+        p = lambda x: C.c_void_p(int(x)) if x else None
+        self._check(self._lib.mcrt_denoise_variance_device(self._h, int(width), int(height), int(spp), p(rgb_ptr), p(variance_ptr), C.byref(bufs), C.byref(par),
+                                                           p(out_ptr), p(out_variance_ptr), C.byref(st)), "mcrt_denoise_variance_device")
+        return st.as_dict()
+
+    def render_denoised(self, cam, global_seed, integrator=INTEGRATOR_PATH_TRACER, **params):
+        """A frame with its statistics, its guides and the variance-guided filter in one call: render_pixel_stats ("variance"), render_aov
+        (DENOISE_GUIDES) and denoise_variance -> dict "rgb" (the filtered frame), "variance" (its variance), "raw" (the unfiltered frame),
+        "noise" and "raw_noise" (frame_noise of the filtered and of the unfiltered frame). cam is one whole frame (no shard: the filter
+        reads neighbouring rows)."""
+        assert cam.shard_count <= 1, "render_denoised filters a whole frame: gather the shards first"
+        spp = cam.sqrtspp * cam.sqrtspp
+        raw = self.render_pixel_stats(cam, global_seed, integrator, channels=("variance",))
+        aov = self.render_aov(cam, global_seed, channels=DENOISE_GUIDES)
+        rgb, variance = self.denoise_variance(raw["rgb"], raw["variance"], aov, spp, **params)
+        return {"rgb": rgb, "variance": variance, "raw": raw["rgb"], "noise": self.frame_noise(rgb, variance, spp),
+                "raw_noise": self.frame_noise(raw["rgb"], raw["variance"], spp)}
 
     def render_pixel_stats(self, cam, global_seed, integrator=INTEGRATOR_PATH_TRACER, channels=None, stats=None, out=None):
         """mcrt_render_pixel_stats: the frame of sample_image plus the per-pixel sample statistics -> dict "rgb" and the channels wanted

@@ -102,21 +102,29 @@ MCRT_HD void denoisePrepPixel(const DenoiseFrame& f, uint64_t p) {
     f.irr[3 * p] = irr.x, f.irr[3 * p + 1] = irr.y, f.irr[3 * p + 2] = irr.z;
 }
 
-// Weight of tap q of centre c, h = h[dy] * h[dx]: (((h w_n) w_z) w_c).
-MCRT_HD double denoiseWeight(const DenoiseStep& st, const DenoiseRec& c, const DenoiseRec& q, double h) {
-    double wn = denoiseMax0(dot(c.ns, q.ns));
-    for (uint32_t k = 0; k < st.normal_power_log2; k++) wn = wn * wn;
-    const d3 delta = q.p - c.p;
-    const double dd = dot(delta, delta), d = dot(c.n, delta);
-    const double xz = dd == 0.0 ? 0.0 : (d * d) / (st.sz2 * dd);
+// The geometric part of a tap's weight, (h w_n) w_z, from the centre's Ns, N, P and the tap's Ns, P: shared with the variance-guided
+// filter (mcrt_denoise_var.hpp), whose colour weight alone differs.
+MCRT_HD double denoiseGeometricWeight(uint32_t normal_power_log2, double sz2, const d3& c_ns, const d3& c_n, const d3& c_p, const d3& q_ns,
+                                      const d3& q_p, double h) {
+    double wn = denoiseMax0(dot(c_ns, q_ns));
+    for (uint32_t k = 0; k < normal_power_log2; k++) wn = wn * wn;
+    const d3 delta = q_p - c_p;
+    const double dd = dot(delta, delta), d = dot(c_n, delta);
+    const double xz = dd == 0.0 ? 0.0 : (d * d) / (sz2 * dd);
     double wz = denoiseMax0(1.0 - xz);
     wz = wz * wz;
+    return (h * wn) * wz;
+}
+
+// Weight of tap q of centre c, h = h[dy] * h[dx]: (((h w_n) w_z) w_c).
+MCRT_HD double denoiseWeight(const DenoiseStep& st, const DenoiseRec& c, const DenoiseRec& q, double h) {
+    const double wg = denoiseGeometricWeight(st.normal_power_log2, st.sz2, c.ns, c.n, c.p, q.ns, q.p, h);
     const d3 di = c.irr - q.irr;
     const double e = dot(di, di), den = dot(c.irr, c.irr) + dot(q.irr, q.irr);
     const double xc = den == 0.0 ? 0.0 : (e / den) * st.inv_c;
     double wc = denoiseMax0(1.0 - xc);
     wc = wc * wc;
-    return ((h * wn) * wz) * wc;
+    return wg * wc;
 }
 
 // I_{i+1} of a covered pixel whose own record is c. src.tap(dx, dy, q): the record of tap (dx, dy) into q, false when the tap is outside

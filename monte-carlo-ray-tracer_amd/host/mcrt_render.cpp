@@ -4,7 +4,7 @@
 //
 //   mcrt_render scene.mcrt out.f64 [--width W --height H --sqrtspp S] [--seed N] [--photon] [--device D | --devices D0,D1,...]
 //               [--tga out.tga [--tonemapper hable|aces] [--exposure EV] [--gain EV] [--plain]] [--aov PREFIX]
-//               [--denoise OUT.f64 [--denoise-iterations N]] [--stats PREFIX] [--robust PREFIX [--robust-kappa X] [--robust-radius R]]
+//               [--denoise OUT.f64 [--denoise-iterations N]] [--denoise-variance OUT.f64 [--denoise-variance-out VAR.f64]] [--stats PREFIX] [--robust PREFIX [--robust-kappa X] [--robust-radius R]]
 //
 // Writes the frame as raw FP64 RGB, row-major (what Image::operator() holds, camera/image.cpp:53-56),
 // and prints the statistics. --tga also develops it the way Image::save does (auto exposure / gain, tone map, sRGB bytes:
@@ -14,6 +14,10 @@
 // --denoise also writes the frame filtered by mcrt_denoise (the edge-avoiding a-trous filter guided by that AOV frame; default parameters,
 // --denoise-iterations N sets the one that sizes the footprint) as raw FP64 RGB, and with --tga develops the filtered frame too, to OUT's
 // stem + ".tga".
+// --denoise-variance renders the frame through mcrt_render_pixel_stats (the same frame) and also writes the frame filtered by
+// mcrt_denoise_variance (the a-trous filter steered by the per-pixel sample variance; default parameters, --denoise-iterations N as above)
+// as raw FP64 RGB - with --tga developed too, to OUT's stem + ".tga" -, and with --denoise-variance-out (refused without
+// --denoise-variance) the filtered frame's variance, in the form mcrt_frame_noise reads; prints that summary for the unfiltered and the filtered frame (one device).
 // --stats renders the frame through mcrt_render_pixel_stats (the same frame) and also writes the per-pixel sample statistics,
 // PREFIX.variance.f64, .half_a.f64 and .half_b.f64 (raw FP64 RGB, row-major), and prints the frame summary of mcrt_frame_noise (one device).
 // --robust renders the frame through mcrt_render_highlights (the same frame; with --stats the statistics come from the same render) and
@@ -47,7 +51,7 @@ int main(int argc, char** argv) {
     image.plain = (uint32_t)mcrt_image_param(img, "image_plain");
     image.exposure_compensation = from_bits(mcrt_image_param(img, "image_exposure_ev_bits"));
     image.gain_compensation = from_bits(mcrt_image_param(img, "image_gain_ev_bits"));
-    std::string tga, aov, denoise, pstats, robust;
+    std::string tga, aov, denoise, dvar, dvar_out, pstats, robust;
     mcrt_robust_params rparams{};
     mcrt_denoise_params dparams{};
     std::vector<int> devices;
@@ -69,6 +73,8 @@ int main(int argc, char** argv) {
         else if (k == "--tga" && i + 1 < argc) tga = argv[++i];
         else if (k == "--aov" && i + 1 < argc) aov = argv[++i];
         else if (k == "--denoise" && i + 1 < argc) denoise = argv[++i];
+        else if (k == "--denoise-variance" && i + 1 < argc) dvar = argv[++i];
+        else if (k == "--denoise-variance-out" && i + 1 < argc) dvar_out = argv[++i];
         else if (k == "--stats" && i + 1 < argc) pstats = argv[++i];
         else if (k == "--robust" && i + 1 < argc) robust = argv[++i];
         else if (k == "--robust-kappa" && i + 1 < argc) rparams.kappa = std::strtod(argv[++i], nullptr);
@@ -78,6 +84,10 @@ int main(int argc, char** argv) {
         else if (k == "--exposure" && i + 1 < argc) image.exposure_compensation = std::strtod(argv[++i], nullptr);
         else if (k == "--gain" && i + 1 < argc) image.gain_compensation = std::strtod(argv[++i], nullptr);
         else if (k == "--plain") image.plain = 1;
+    }
+    if (!dvar_out.empty() && dvar.empty()) {
+        std::fprintf(stderr, "--denoise-variance-out needs --denoise-variance\n");
+        return 2;
     }
     cam.shard_index = 0;
     cam.shard_count = 1;
@@ -101,18 +111,19 @@ int main(int argc, char** argv) {
     const int mode = photon ? MCRT_INTEGRATOR_PHOTON_MAPPER : MCRT_INTEGRATOR_PATH_TRACER;
     std::vector<double> variance, half_a, half_b;
     std::vector<double> tops, level;
-    if (rc == MCRT_OK && (!pstats.empty() || !robust.empty())) {
+    if (rc == MCRT_OK && (!pstats.empty() || !robust.empty() || !dvar.empty())) {
         if (ctxs.size() > 1) {
-            std::fprintf(stderr, "--stats and --robust take one device\n");
+            std::fprintf(stderr, "--stats, --robust and --denoise-variance take one device\n");
             return 2;
         }
+        if (!dvar.empty()) variance.resize(rgb.size());
         if (!pstats.empty()) {
             variance.resize(rgb.size());
             half_a.resize(rgb.size());
             half_b.resize(rgb.size());
         }
         const bool ps = !pstats.empty();
-        const mcrt_pixel_stats_buffers b{ps ? variance.data() : nullptr, ps ? half_a.data() : nullptr, ps ? half_b.data() : nullptr};
+        const mcrt_pixel_stats_buffers b{ps || !dvar.empty() ? variance.data() : nullptr, ps ? half_a.data() : nullptr, ps ? half_b.data() : nullptr};
         if (!robust.empty()) {
             tops.resize(rgb.size() * MCRT_ROBUST_TOPS);
             level.resize(rgb.size() / 3);
@@ -210,7 +221,7 @@ int main(int argc, char** argv) {
         return true;
     };
     if (!tga.empty() && !develop(rgb, tga)) return 1;
-    if (!aov.empty() || !denoise.empty()) {
+    if (!aov.empty() || !denoise.empty() || !dvar.empty()) {
         const size_t px = (size_t)cam.width * cam.height;
         std::vector<double> depth(px), position(px * 3), normal(px * 3), shading_normal(px * 3), albedo(px * 3), coverage(px);
         std::vector<uint32_t> surface(px), material(px);
@@ -252,6 +263,31 @@ int main(int argc, char** argv) {
                 const size_t dot = denoise.find_last_of('.'), slash = denoise.find_last_of('/');
                 const bool has_ext = dot != std::string::npos && (slash == std::string::npos || dot > slash);
                 if (!develop(filtered, (has_ext ? denoise.substr(0, dot) : denoise) + ".tga")) return 1;
+            }
+        }
+        if (!dvar.empty()) {
+            const uint32_t spp = cam.sqrtspp * cam.sqrtspp;
+            std::vector<double> filtered(px * 3), filtered_var(px * 3);
+            mcrt_denoise_variance_params vparams{};
+            vparams.iterations = dparams.iterations;
+            mcrt_stats dst;
+            mcrt_frame_noise_result raw, fn;
+            rc = mcrt_denoise_variance(ctx, cam.width, cam.height, spp, rgb.data(), variance.data(), &b, &vparams, filtered.data(), filtered_var.data(), &dst);
+            if (rc == MCRT_OK) rc = mcrt_frame_noise(ctx, px, spp, rgb.data(), variance.data(), &raw);
+            if (rc == MCRT_OK) rc = mcrt_frame_noise(ctx, px, spp, filtered.data(), filtered_var.data(), &fn);
+            if (rc != MCRT_OK) {
+                std::fprintf(stderr, "mcrt error %d: %s\n", rc, mcrt_last_error(ctx));
+                return 1;
+            }
+            if (!dump(dvar, filtered.data(), px * 24)) return 1;
+            if (!dvar_out.empty() && !dump(dvar_out, filtered_var.data(), px * 24)) return 1;
+            std::printf("{\"denoise_variance\":\"%s\",\"kernel_launches\":%u,\"kernel_ms\":%.3f,\"total_ms\":%.3f,\"relative_error_raw\":%.17g,"
+                        "\"relative_error\":%.17g}\n",
+                        dvar.c_str(), dst.kernel_launches, dst.kernel_ms, dst.total_ms, raw.relative_error, fn.relative_error);
+            if (!tga.empty()) {
+                const size_t dot = dvar.find_last_of('.'), slash = dvar.find_last_of('/');
+                const bool has_ext = dot != std::string::npos && (slash == std::string::npos || dot > slash);
+                if (!develop(filtered, (has_ext ? dvar.substr(0, dot) : dvar) + ".tga")) return 1;
             }
         }
     }

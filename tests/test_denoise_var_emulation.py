@@ -1,0 +1,363 @@
+"""Variance-guided denoised output (mcrt_denoise_variance*), CPU tier: csrc/mcrt_denoise_var.hpp - the text the three kernels of
+csrc/mcrt_denoise_var.hip run - driven on the host (tests/emu/denoise_var_emu.cpp: the plain form as a loop, the tile form on
+wave_emu.hpp's emulated workgroup with its barrier) against the formulas of include/mcrt.h ("Variance-guided denoised output") written
+out HERE in numpy, tap by tap in the stated order, for the frame and for its variance.
+
+Bound: assert_array_equal. Derived, not measured: both sides execute the same IEEE-754 double operations (+ - * /, compare, select) in
+the same order, none of them a libm call, neither side contracted (the harness is built with -ffp-contract=off, numpy's ufuncs are
+one operation each) - so every bit agrees, NaNs included."""
+import ctypes as C
+import functools
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+import test_denoise_emulation as dn
+from conftest import ROOT, TESTS
+
+NO_ALBEDO = dn.NO_ALBEDO
+GUIDES = dn.GUIDES
+# explicit parameters everywhere (not the defaults: retuning those must not touch a test)
+PARAMS = dict(normal_power_log2=5, sigma_variance=2.5, sigma_floor=0.08, sigma_plane=0.25, albedo_floor=0.01)
+_dot, _max0 = dn._dot, dn._max0
+
+
+def load_denoise_var_emu():
+    src = os.path.join(TESTS, "emu", "denoise_var_emu.cpp")
+    out = os.path.join(TESTS, "emu", "_build", "libdenoise_var_emu.so")
+    csrc = os.path.join(ROOT, "monte-carlo-ray-tracer_amd", "csrc")
+    deps = [src, os.path.join(TESTS, "emu", "wave_emu.hpp"), os.path.join(csrc, "mcrt_denoise_var.hpp"), os.path.join(csrc, "mcrt_denoise.hpp"),
+            os.path.join(csrc, "mcrt_math.hpp"), os.path.join(ROOT, "include", "mcrt.h")]
+    if not os.path.exists(out) or any(os.path.getmtime(d) > os.path.getmtime(out) for d in deps):
+        os.makedirs(os.path.dirname(out), exist_ok=True)
+        tmp = "%s.%d.tmp" % (out, os.getpid())
+        subprocess.check_call(["g++", "-std=c++17", "-O2", "-ffp-contract=off", "-fPIC", "-shared", "-o", tmp, src])
+        os.replace(tmp, out)
+    L = C.CDLL(out)
+    vp = C.c_void_p
+    L.denoise_var_emu.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, vp, C.c_int, vp, vp]
+    L.denoise_var_emu_tile_lds_bytes.restype = C.c_uint32
+    return L
+
+
+@functools.lru_cache(maxsize=None)
+def _emu():
+    return load_denoise_var_emu()
+
+
+def _pkg():
+    import importlib
+    return importlib.import_module("monte-carlo-ray-tracer_amd")
+
+
+def _buffers(pkg, guides):
+    bufs, keep = pkg.AovBuffers(), []
+    for k in GUIDES:
+        if guides.get(k) is not None:
+            keep.append(np.ascontiguousarray(guides[k], dtype=np.float64))
+            setattr(bufs, k, keep[-1].ctypes.data)
+    return bufs, keep
+
+
+def emu_denoise_var(rgb, variance, guides, spp, form, flags=0, want_variance=True, **params):
+    """The emulation's filtered frame and its variance. form: "plain" or "tile". guides: dict channel -> array (albedo may be missing with
+    NO_ALBEDO)."""
+    pkg = _pkg()
+    rgb = np.ascontiguousarray(rgb, dtype=np.float64)
+    variance = np.ascontiguousarray(variance, dtype=np.float64)
+    height, width = rgb.shape[:2]
+    bufs, keep = _buffers(pkg, guides)
+    par = pkg.DenoiseVarianceParams(flags=flags, **params)
+    out, out_var = np.full_like(rgb, -7.0), (np.full_like(rgb, -9.0) if want_variance else None)
+    rc = _emu().denoise_var_emu(width, height, spp, rgb.ctypes.data, variance.ctypes.data, C.byref(bufs), C.byref(par), {"plain": 0, "tile": 1}[form],
+                                out.ctypes.data, out_var.ctypes.data if want_variance else None)
+    assert rc == 0, "denoise_var_emu: %d" % rc
+    return out, out_var
+
+
+def _g(v):
+    return (v[..., 0] + v[..., 1]) + v[..., 2]
+
+
+def _taps(H, W, s, radius):
+    """(dy, dx, p, q): the slices of the pixels p whose tap q = p + s (dx, dy) is inside the frame; dy outer, dx inner."""
+    for dy in range(-radius, radius + 1):
+        for dx in range(-radius, radius + 1):
+            y0, y1, x0, x1 = max(0, -s * dy), min(H, H - s * dy), max(0, -s * dx), min(W, W - s * dx)
+            if y0 < y1 and x0 < x1:
+                yield dy, dx, (slice(y0, y1), slice(x0, x1)), (slice(y0 + s * dy, y1 + s * dy), slice(x0 + s * dx, x1 + s * dx))
+
+
+def numpy_denoise_var(rgb, variance, guides, spp, iterations, normal_power_log2, sigma_variance, sigma_floor, sigma_plane, albedo_floor, flags=0,
+                      unit_colour_weight=False):
+    """include/mcrt.h's "Variance-guided denoised output" in numpy: whole-frame arrays per tap, the taps accumulated one by one.
+    unit_colour_weight: the same text with w_c = 1 (test_a_large_variance_opens_the_colour_weight)."""
+    H, W = rgb.shape[:2]
+    Ns, N, P, cov = (np.asarray(guides[k], dtype=np.float64) for k in ("shading_normal", "normal", "position", "coverage"))
+    a = np.ones_like(rgb) if flags & NO_ALBEDO else np.where(guides["albedo"] > albedo_floor, guides["albedo"], 1.0)
+    h = (1.0 / 16.0, 1.0 / 4.0, 3.0 / 8.0, 1.0 / 4.0, 1.0 / 16.0)
+    k = (1.0 / 4.0, 1.0 / 2.0, 1.0 / 4.0)
+    n = float(spp)
+    sv2, sf2, sz2 = sigma_variance * sigma_variance, sigma_floor * sigma_floor, sigma_plane * sigma_plane
+    uncovered = cov == 0.0
+    with np.errstate(all="ignore"):
+        I = rgb / a
+        u = (variance / n) / (a * a)
+        s3, ks = np.zeros((H, W, 3)), np.zeros((H, W))
+        for dy, dx, p, q in _taps(H, W, 1, 1):
+            kw = k[dy + 1] * k[dx + 1]
+            skipped = uncovered[q]
+            s3[p] = np.where(skipped[..., None], s3[p], s3[p] + kw * u[q])
+            ks[p] = np.where(skipped, ks[p], ks[p] + kw)
+        V = np.where(uncovered[..., None], u, s3 * (1.0 / ks)[..., None])
+        for i in range(iterations):
+            s = 1 << i
+            total, vtotal, wsum = np.zeros((H, W, 3)), np.zeros((H, W, 3)), np.zeros((H, W))
+            gV = _g(V)
+            for dy, dx, p, q in _taps(H, W, s, 2):
+                if dx == 0 and dy == 0:
+                    w = 9.0 / 64.0
+                    total[p] = total[p] + w * I[q]
+                    vtotal[p] = vtotal[p] + (w * w) * V[q]
+                    wsum[p] = wsum[p] + w
+                    continue
+                wn = _max0(_dot(Ns[p], Ns[q]))
+                for _ in range(normal_power_log2):
+                    wn = wn * wn
+                D = P[q] - P[p]
+                dd, d = _dot(D, D), _dot(N[p], D)
+                wz = _max0(1.0 - np.where(dd == 0.0, 0.0, (d * d) / (sz2 * dd)))
+                wz = wz * wz
+                di = I[p] - I[q]
+                e, m = _dot(di, di), _dot(I[p], I[p]) + _dot(I[q], I[q])
+                den = (sv2 * (gV[p] + gV[q])) + (sf2 * m)
+                wc = _max0(1.0 - np.where(e == 0.0, 0.0, e / den))
+                wc = wc * wc
+                if unit_colour_weight:
+                    wc = np.ones_like(wc)
+                w = (((h[dy + 2] * h[dx + 2]) * wn) * wz) * wc
+                skipped = uncovered[q]  # weight 0: contributes nothing (not even 0 * Inf)
+                total[p] = np.where(skipped[..., None], total[p], total[p] + w[..., None] * I[q])
+                vtotal[p] = np.where(skipped[..., None], vtotal[p], vtotal[p] + (w * w)[..., None] * V[q])
+                wsum[p] = np.where(skipped, wsum[p], wsum[p] + w)
+            r = 1.0 / wsum
+            I = np.where(uncovered[..., None], I, total * r[..., None])
+            V = np.where(uncovered[..., None], V, vtotal * (r * r)[..., None])
+        return I * a, (V * (a * a)) * n
+
+
+def with_variance(rgb, seed):
+    """-> (rgb', variance): a seeded positive sample variance for the frame, with exact zeros (samples that agreed), a column of huge
+    variance, and - in rgb' - a bright pixel whose left neighbour has variance zero."""
+    H, W = rgb.shape[:2]
+    rng = np.random.default_rng(seed)
+    rgb = rgb.copy()
+    v = (0.05 + 0.5 * rgb) ** 2 * rng.uniform(0.2, 3.0, size=(H, W, 3))
+    v[rng.random((H, W)) < 0.05] = 0.0
+    if W > 8:
+        v[:, W // 4] = 1e12
+    if W >= 3:
+        rgb[H - 1, W - 1], v[H - 1, W - 1] = 50.0, 400.0
+        v[H - 1, W - 2] = 0.0
+    return np.ascontiguousarray(rgb), np.ascontiguousarray(v)
+
+
+@functools.lru_cache(maxsize=None)
+def scene_case(scene):
+    guides, rgb = dn.scene_case(scene)
+    return (guides,) + with_variance(rgb, 99 + len(scene))
+
+
+def both_forms_equal(rgb, variance, guides, spp, want, msg="", **kw):
+    for form in ("plain", "tile"):
+        got = emu_denoise_var(rgb, variance, guides, spp, form, **kw)
+        np.testing.assert_array_equal(got[0], want[0], err_msg="frame %s %s" % (form, msg))
+        np.testing.assert_array_equal(got[1], want[1], err_msg="variance %s %s" % (form, msg))
+
+
+@pytest.mark.parametrize("flags", [0, NO_ALBEDO])
+@pytest.mark.parametrize("iterations", [1, 3, 5])
+@pytest.mark.parametrize("scene", dn.SCENES)
+def test_emulation_is_the_numpy_restatement(scene, iterations, flags):
+    """70 x 13 guides of the AOV emulation: at 5 iterations the last step is 16 > 13 rows. 3 iterations run at 9 spp (divisions by a
+    number that is no power of two), the others at 4. With NO_ALBEDO the albedo pointer is NULL."""
+    guides, rgb, variance = scene_case(scene)
+    if flags & NO_ALBEDO:
+        guides = dict(guides, albedo=None)
+    spp = 9 if iterations == 3 else 4
+    want = numpy_denoise_var(rgb, variance, guides, spp, iterations, flags=flags, **PARAMS)
+    both_forms_equal(rgb, variance, guides, spp, want, scene, iterations=iterations, flags=flags, **PARAMS)
+    assert np.isfinite(want[0]).all() and np.isfinite(want[1]).all()
+    assert not np.array_equal(want[0], rgb) and not np.array_equal(want[1], variance)
+    assert (variance == 0).any() and (variance == 1e12).any()
+
+
+@pytest.mark.parametrize("flags", [0, NO_ALBEDO])
+@pytest.mark.parametrize("width,height", [(1, 1), (3, 2), (131, 67)])
+def test_hand_made_frames(width, height, flags):
+    """131 x 67: 9 x 5 tiles at step 1, both directions ragged; 5 iterations reach step 16, where a residue class is 9 x 5 pixels - one
+    ragged tile each. 4 spp: v / 4 and * 4 are exact, so a pixel without coverage keeps the bits of both inputs."""
+    guides, rgb, (rows, cols), _ = dn.hand_made(width, height)
+    rgb, variance = with_variance(rgb, 5)
+    if flags & NO_ALBEDO:
+        guides = dict(guides, albedo=None)
+    par = dict(PARAMS, iterations=5)
+    want = numpy_denoise_var(rgb, variance, guides, 4, flags=flags, **par)
+    both_forms_equal(rgb, variance, guides, 4, want, flags=flags, **par)
+    assert np.isfinite(want[0]).all() and np.isfinite(want[1]).all()
+    if width * height == 1:
+        # only the centre tap: per iteration w I, 1 / w and their product round once each, demodulation and back once each: 5 x 3 + 2 = 17
+        # half-ulps to first order, 18 with room for the second. The variance:
+        # (w w) V, r twice in r r, r r itself and the product with it per iteration (w w is exact), a a and the division by it, a a and the product
+        # with it (v / 4, the prefilter of one tap and x 4 are exact): 5 x 5 + 4 = 29, 30 with room.
+        np.testing.assert_allclose(want[0], rgb, rtol=18 * 2.0 ** -53, atol=0)
+        np.testing.assert_allclose(want[1], variance, rtol=30 * 2.0 ** -53, atol=0)
+        return
+    # without coverage: the inputs' bits, and nothing of them in the neighbours - any other values there, the same frames around
+    assert want[0][rows, cols].tobytes() == rgb[rows, cols].tobytes()
+    assert want[1][rows, cols].tobytes() == variance[rows, cols].tobytes()
+    other, other_v = rgb.copy(), variance.copy()
+    other[rows, cols], other_v[rows, cols] = 1e30, 1e40
+    outside = np.ones((height, width), dtype=bool)
+    outside[rows, cols] = False
+    for form in ("plain", "tile"):
+        again = emu_denoise_var(other, other_v, guides, 4, form, flags=flags, **par)
+        np.testing.assert_array_equal(again[0][outside], want[0][outside], err_msg=form)
+        np.testing.assert_array_equal(again[1][outside], want[1][outside], err_msg=form)
+
+
+def test_no_variance_output_gives_the_same_frame():
+    guides, rgb, _, _ = dn.hand_made(40, 21)
+    rgb, variance = with_variance(rgb, 6)
+    par = dict(PARAMS, iterations=3)
+    for form in ("plain", "tile"):
+        frame, none = emu_denoise_var(rgb, variance, guides, 4, form, want_variance=False, **par)
+        assert none is None
+        np.testing.assert_array_equal(frame, emu_denoise_var(rgb, variance, guides, 4, form, **par)[0])
+
+
+def test_flat_plane_constant_frame():
+    """Derived: a flat plane seen from above (Ns = N = (0, 0, 1), P in the plane z = 0), constant irradiance c and variance v, full
+    coverage, no albedo, 4 spp, one iteration, the centre pixel of 9 x 9 (its taps and their 3 x 3 prefilters stay inside). w_n = 1 (1 x 1
+    exactly), w_z = 1 (d = 0), w_c = 1 (e = 0): every weight is h[dy] h[dx], exact in binary, and so are their sum 1 and r = 1.
+    The frame: 25 products w I and 24 additions that round (0.0 + x does not) - the first term passes through all of them: 25 half-ulps to
+    first order, 26 with room for the second. The variance: V_0 = s (1 / ks) with u = v / 4 exact, 9 products and 8 rounding additions,
+    ks = 1: 9 half-ulps; V_1 = sum (w w) V_0, w w exact: 25 more; x (r r) = 1 and x 4 exact. V_1 / V_0 = sum w^2 = (sum h^2)^2 =
+    (70 / 256)^2 = 1225 / 16384: rtol 34 half-ulps to first order, 35 with room."""
+    H = W = 9
+    y, x = np.mgrid[0:H, 0:W].astype(np.float64)
+    up = np.broadcast_to(np.array([0.0, 0.0, 1.0]), (H, W, 3)).copy()
+    guides = dict(shading_normal=up, normal=up.copy(), position=np.ascontiguousarray(np.stack([x * 0.1, y * 0.1, np.zeros_like(x)], axis=-1)),
+                  coverage=np.ones((H, W)), albedo=None)
+    c, v = np.array([0.7, 0.3, 1.1]), np.array([0.05, 0.02, 0.3])
+    rgb, variance = np.broadcast_to(c, (H, W, 3)).copy(), np.broadcast_to(v, (H, W, 3)).copy()
+    for form in ("plain", "tile"):
+        frame, var = emu_denoise_var(rgb, variance, guides, 4, form, flags=NO_ALBEDO, iterations=1, **PARAMS)
+        np.testing.assert_allclose(frame[4, 4], c, rtol=26 * 2.0 ** -53, atol=0)
+        np.testing.assert_allclose(var[4, 4], v * (1225.0 / 16384.0), rtol=35 * 2.0 ** -53, atol=0)
+
+
+def test_nan_and_inf_propagate():
+    """Nothing is filtered out. One iteration, full coverage: a NaN in the beauty frame reaches the 5 x 5 pixels whose taps read it, in both
+    outputs (a NaN weight); a NaN in the variance is spread over 3 x 3 by the prefilter and reaches the 7 x 7 pixels whose taps read one
+    of those - and no pixel further away."""
+    guides, rgb, _, _ = dn.hand_made(30, 11, seed=3)
+    guides["coverage"][:] = 1.0
+    rgb, variance = with_variance(rgb, 8)
+    variance[5, 4, 2] = np.nan
+    rgb[5, 22, 1] = np.nan
+    rgb[10, 13, 0] = np.inf
+    want = numpy_denoise_var(rgb, variance, guides, 4, 1, **PARAMS)
+    both_forms_equal(rgb, variance, guides, 4, want, iterations=1, **PARAMS)
+    bad, bad_v = np.isnan(want[0]).any(axis=2), np.isnan(want[1]).any(axis=2)
+    assert bad_v[2:9, 1:8].all() and bad[2:9, 1:8].any()
+    assert bad[3:8, 20:25].all() and bad_v[3:8, 20:25].all()
+    for b in (bad, bad_v):
+        assert not b[:, 8:11].any() and not b[:8, 16:20].any() and not b[:, 25:].any() and not b[:, 0].any() and not b[9:, :8].any()
+    assert not np.isfinite(want[0][10, 13]).all()
+
+
+def test_defaults_and_refusals_of_the_settings():
+    """A zero field is the default (5, 7, 6.0, 0.02, 0.1, 1e-3); more than 16 iterations, more than 32 squarings, no samples, missing
+    frames and sigmas that are negative or not finite are refused."""
+    pkg = _pkg()
+    guides, rgb, _, _ = dn.hand_made(9, 7)
+    rgb, variance = with_variance(rgb, 9)
+    got = emu_denoise_var(rgb, variance, guides, 4, "tile")
+    want = numpy_denoise_var(rgb, variance, guides, 4, 5, normal_power_log2=7, sigma_variance=6.0, sigma_floor=0.02, sigma_plane=0.1, albedo_floor=1e-3)
+    np.testing.assert_array_equal(got[0], want[0])
+    np.testing.assert_array_equal(got[1], want[1])
+    bufs, keep = _buffers(pkg, guides)
+    out, out_v = np.empty_like(rgb), np.empty_like(rgb)
+    P = pkg.DenoiseVarianceParams
+
+    def run(par, w=9, h=7, spp=4, b=bufs, c=rgb, v=variance, o=out):
+        return _emu().denoise_var_emu(w, h, spp, c.ctypes.data if c is not None else None, v.ctypes.data if v is not None else None, C.byref(b),
+                                      C.byref(par), 1, o.ctypes.data if o is not None else None, out_v.ctypes.data)
+
+    assert run(P(iterations=16)) == 0
+    assert run(P(iterations=17)) == -1
+    assert run(P(normal_power_log2=32)) == 0
+    assert run(P(normal_power_log2=33)) == -1
+    assert run(P(), w=0) == -1 and run(P(), h=0) == -1
+    assert run(P(), w=65536, h=65536) == -1  # width * height = 2^32 (refused before a pixel is touched)
+    assert run(P(), spp=0) == -1
+    assert run(P(), c=None) == -1 and run(P(), v=None) == -1 and run(P(), o=None) == -1
+    for field in ("sigma_variance", "sigma_floor", "sigma_plane"):
+        for bad in (-1.0, float("inf"), float("-inf"), float("nan")):
+            assert run(P(**{field: bad})) == -1, (field, bad)
+        assert run(P(**{field: 1e-300})) == 0
+    bare, _keep = _buffers(pkg, dict(guides, albedo=None))
+    assert run(P(), b=bare) == -1 and run(P(flags=NO_ALBEDO), b=bare) == 0
+    for channel in ("shading_normal", "normal", "position", "coverage"):
+        missing, _keep = _buffers(pkg, dict(guides, **{channel: None}))
+        assert run(P(), b=missing) == -1 and run(P(flags=NO_ALBEDO), b=missing) == -1, channel
+
+
+def test_a_large_variance_opens_the_colour_weight():
+    """That the variance steers the filter. The frame scaled by 2^-40 (exact) and the variance, at least 1e-3, by 1e12. In every iteration
+    a covered pixel's I is a mean with non-negative weights of what it reads, so |I| stays <= 250 x 2^-40 (the bright pixel's 50 over an
+    albedo of at least 0.2; to rounding) and e <= 3 x 250^2 x 2^-80 < 2e-19 throughout. V_0 >= 1e9 / 4 per channel (a <= 1 only raises u;
+    the prefilter is a mean), and V_{i+1} = sum w^2 V_i / (sum w)^2 >= min V_i / 25 (Cauchy-Schwarz over at most 25 taps), so the
+    fifth iteration still reads V_4 >= 1e9 / 4 / 25^4 = 640 and den >= sv2 (g(V_p) + g(V_q)) >= 6.25 x 2 x 3 x 640 > 2e4 - x_c < 1e-23 <
+    2^-54 in all five iterations and 1 - x_c rounds to 1: the filter equals the same numpy text with w_c = 1, bit for bit.
+    Its twin: with the variance all zero and sigma_floor 1e-6 the colour weight closes (e / den >= 1 unless two pixels agree to 1e-6 in
+    every channel), only the centre tap counts and the noisy frame comes back to rounding: 5 x 3 + 2 = 18 half-ulps with room, as in
+    test_hand_made_frames."""
+    guides, rgb, _, _ = dn.hand_made(40, 21)
+    rgb, variance = with_variance(rgb, 10)
+    par = dict(PARAMS, iterations=5)
+    small, big = rgb * 2.0 ** -40, np.maximum(variance, 1e-3) * 1e12
+    want = numpy_denoise_var(small, big, guides, 4, unit_colour_weight=True, **par)
+    both_forms_equal(small, big, guides, 4, want, **par)
+    steered = numpy_denoise_var(small, variance * 2.0 ** -80, guides, 4, **par)  # the variance on the frame's own scale: the weight acts
+    assert not np.array_equal(steered[0], want[0])
+    closed = emu_denoise_var(small, np.zeros_like(variance), guides, 4, "tile", **dict(par, sigma_floor=1e-6))
+    np.testing.assert_allclose(closed[0], small, rtol=18 * 2.0 ** -53, atol=0)
+    assert (closed[1] == 0).all()
+    covered = guides["coverage"] > 0
+    assert np.abs(want[0] - small)[covered].max() > 1e-3 * small.max()  # (the open filter did move the frame)
+    assert not np.array_equal(closed[0], want[0])
+
+
+def test_albedo_below_the_floor_counts_as_one():
+    guides, rgb, _, _ = dn.hand_made(31, 9)
+    rgb, variance = with_variance(rgb, 11)
+    stripe = 31 // 3
+    hi = emu_denoise_var(rgb, variance, guides, 4, "tile", iterations=2, **PARAMS)
+    lo = emu_denoise_var(rgb, variance, guides, 4, "tile", iterations=2, **dict(PARAMS, albedo_floor=0.001))
+    assert not np.array_equal(hi[0][:, stripe], lo[0][:, stripe]) and not np.array_equal(hi[1][:, stripe], lo[1][:, stripe])
+    flat = dict(guides, albedo=np.where(guides["albedo"] > 0.01, guides["albedo"], 1.0))
+    again = emu_denoise_var(rgb, variance, flat, 4, "plain", iterations=2, **PARAMS)
+    np.testing.assert_array_equal(again[0], hi[0])
+    np.testing.assert_array_equal(again[1], hi[1])
+
+
+def test_null_context_is_refused(pkg):
+    L = pkg.lib()
+    bufs, par = pkg.AovBuffers(), pkg.DenoiseVarianceParams()
+    assert L.mcrt_denoise_variance(None, 1, 1, 4, None, None, C.byref(bufs), C.byref(par), None, None, None) == -1      # MCRT_ERR_INVALID
+    assert L.mcrt_denoise_variance_device(None, 1, 1, 4, None, None, C.byref(bufs), C.byref(par), None, None, None) == -1
+    assert C.sizeof(pkg.DenoiseVarianceParams) == 48

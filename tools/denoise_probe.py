@@ -1,16 +1,19 @@
 #!/usr/bin/env python3
-"""The a-trous filter (mcrt_denoise_device) measured: its time next to the beauty frame and the AOV pass of the same camera, and what
-it does to the error of a low-sample frame.
+"""The a-trous filters (mcrt_denoise_device and the variance-guided mcrt_denoise_variance_device) measured on the same frames in one
+session: their time next to the beauty frame and the AOV pass of the same camera, and what they do to the error of a low-sample frame.
 
   python tools/denoise_probe.py [--width 1920 --height 1080 --sqrtspp 4] [--runs 5] [--scenes hexagon_room]
       Time: HIP-event milliseconds from mcrt_stats, one warm-up, then the median of --runs runs, for 1 .. iterations iterations in the
       tile form, the plain form and the default choice; "step_ms" are the differences (the first includes the prep pass, the default
-      count's last one the remodulation). One JSON line per scene.
+      count's last one the remodulation); "variance_tile" / "variance_plain" / "variance_default" are the guided filter's. One JSON line
+      per scene.
 
   python tools/denoise_probe.py --errors [--width 192 --height 108] [--truth-sqrtspp 32] [--scenes a,b,...] [--grid]
       Error: per scene and sqrtspp 1, 2, 4 the mean squared error (all channels, pixels with coverage > 0) of the unfiltered and of the
-      filtered frame (default parameters) against a render at --truth-sqrtspp with another seed. --grid adds a small grid of parameters.
-      One JSON line per (scene, sqrtspp)."""
+      filtered frame (default parameters) against a render at --truth-sqrtspp with another seed. The guided filter (default parameters) runs on the same frame with the variance of
+      render_pixel_stats: "mse_variance_guided", and "calibration" = the mean over those pixels of g(out_variance) / spp over the mean of
+      the filtered frame's squared error (channels added). --grid adds a small grid of parameters for each filter ("grid", "variance_grid":
+      [sigma_variance, sigma_floor, ratio]). One JSON line per (scene, sqrtspp)."""
 import argparse
 import importlib
 import itertools
@@ -23,6 +26,7 @@ ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 sys.path.insert(0, ROOT)
 
 GUIDES = ("shading_normal", "normal", "position", "coverage", "albedo")
+VARIANCE_GRID = dict(sigma_variance=(2.0, 3.0, 4.0, 6.0), sigma_floor=(0.02, 0.05, 0.1))
 GRID = dict(iterations=(3, 5), sigma_color=(1.0, 2.0, 4.0), sigma_plane=(0.1, 0.3), normal_power_log2=(5, 7))
 
 
@@ -42,9 +46,10 @@ def timing(m, args):
         img, cam, ctx = setup(m, name, args.width, args.height, args.sqrtspp)
         bufs = {k: torch.empty((cam.height, cam.width) + ((3,) if m.AOV_CHANNELS[k][1] == 3 else ()), dtype=torch.float64, device="cuda:0") for k in GUIDES}
         rgb = torch.empty((cam.height, cam.width, 3), dtype=torch.float64, device="cuda:0")
-        out = torch.empty_like(rgb)
+        out, var, out_var = torch.empty_like(rgb), torch.empty_like(rgb), torch.empty_like(rgb)
         torch.cuda.synchronize()
         ptrs = {k: v.data_ptr() for k, v in bufs.items()}
+        ctx.render_pixel_stats_device(cam, args.seed, m.INTEGRATOR_PATH_TRACER, rgb.data_ptr(), {"variance": var.data_ptr()})
         for _ in range(2):  # warm-up, then the ones that count
             aov = ctx.render_aov_device(cam, args.seed, ptrs)
             ctx.render_device(cam, args.seed, m.INTEGRATOR_PATH_TRACER, rgb.data_ptr())
@@ -59,6 +64,16 @@ def timing(m, args):
                 runs = [ctx.denoise_device(cam.width, cam.height, rgb.data_ptr(), ptrs, out.data_ptr(), iterations=n)["kernel_ms"] for _ in range(max(args.runs, 1))]
                 total.append(statistics.median(runs))
             rec[form or "default"] = {"total_ms": [round(t, 4) for t in total], "step_ms": [round(b - a, 4) for a, b in zip([0.0] + total, total)]}
+        ctx.set_option("MCRT_DENOISE_FORM", None)
+        guided = lambda n: ctx.denoise_variance_device(cam.width, cam.height, cam.sqrtspp ** 2, rgb.data_ptr(), var.data_ptr(), ptrs, out.data_ptr(),
+                                                       out_var.data_ptr(), iterations=n)["kernel_ms"]
+        for form in ("tile", "plain", None):
+            ctx.set_option("MCRT_DENOISE_VAR_FORM", form)
+            total = []
+            for n in range(1, args.iterations + 1):
+                guided(n)
+                total.append(statistics.median([guided(n) for _ in range(max(args.runs, 1))]))
+            rec["variance_" + (form or "default")] = {"total_ms": [round(t, 4) for t in total], "step_ms": [round(b - a, 4) for a, b in zip([0.0] + total, total)]}
         print(json.dumps(rec), flush=True)
         ctx.close()
         img.close()
@@ -67,21 +82,30 @@ def timing(m, args):
 def errors(m, args):
     import numpy as np
     combos = [dict(zip(GRID, v)) for v in itertools.product(*GRID.values())] if args.grid else []
+    vcombos = [dict(zip(VARIANCE_GRID, v)) for v in itertools.product(*VARIANCE_GRID.values())] if args.grid else []
     for name in args.scenes.split(","):
         img, cam, ctx = setup(m, name, args.width, args.height, args.truth_sqrtspp)
         truth, _ = ctx.sample_image(cam, args.seed ^ 0x00ABCDEF, m.INTEGRATOR_PATH_TRACER)
         for sqrtspp in (1, 2, 4):
             cam.sqrtspp = sqrtspp
-            noisy, _ = ctx.sample_image(cam, args.seed, m.INTEGRATOR_PATH_TRACER)
+            stats = ctx.render_pixel_stats(cam, args.seed, m.INTEGRATOR_PATH_TRACER, channels=("variance",))
+            noisy, variance, spp = stats["rgb"], stats["variance"], sqrtspp ** 2
             guides = ctx.render_aov(cam, args.seed, channels=GUIDES)
             covered = guides["coverage"] > 0
             mse = lambda frame: float(((frame - truth)[covered] ** 2).mean())
             before, after = mse(noisy), mse(ctx.denoise(noisy, guides))
             rec = {"scene": name, "width": cam.width, "height": cam.height, "spp": sqrtspp ** 2, "truth_spp": args.truth_sqrtspp ** 2,
                    "mse_unfiltered": before, "mse_filtered": after, "ratio": round(after / before, 4)}
+            guided, guided_var = ctx.denoise_variance(noisy, variance, guides, spp)
+            rec["mse_variance_guided"] = mse(guided)
+            rec["ratio_variance_guided"] = round(rec["mse_variance_guided"] / before, 4)
+            estimate = float((guided_var[covered].sum(axis=-1) / spp).mean())
+            rec["calibration"] = round(estimate / float((((guided - truth)[covered]) ** 2).sum(axis=-1).mean()), 4)
             if combos:
                 rec["grid"] = [[c["iterations"], c["sigma_color"], c["sigma_plane"], c["normal_power_log2"], round(mse(ctx.denoise(noisy, guides, **c)) / before, 4)]
                                for c in combos]
+                rec["variance_grid"] = [[c["sigma_variance"], c["sigma_floor"],
+                                         round(mse(ctx.denoise_variance(noisy, variance, guides, spp, want_variance=False, **c)[0]) / before, 4)] for c in vcombos]
             print(json.dumps(rec), flush=True)
         ctx.close()
         img.close()
