@@ -552,6 +552,104 @@ int mcrt_robust_resolve(mcrt_ctx* ctx, uint32_t width, uint32_t height, uint32_t
                         const double* level, const mcrt_robust_params* params, double* out_rgb,
                         const mcrt_robust_buffers* buffers /* may be NULL */, mcrt_stats* stats /* may be NULL */);
 
+/* ------------------------------------------------------------------------------------------
+ * Accumulated rendering: independent renders of one camera merged per pixel, and a render that stops at a target noise. The
+ * reference has no such output. A render delivers the sufficient statistics of a pixel's samples - rgb, variance, half_a,
+ * half_b (mcrt_render_pixel_stats*), tops, level (mcrt_render_highlights*) -, and two renders of one camera at different
+ * global_seeds are independent estimates of the same pixels: the summary of their union follows from the two summaries alone.
+ * No render kernel takes part. Only FP64 + - * /, compare and select, in the order written here, uncontracted, no libm routine:
+ * a function of the inputs bit for bit.
+ *
+ * 1. mcrt_frame_merge: the summary of the sample sequence "A's n_a samples, then B's n_b samples" (sample j of B has index
+ * n_a + j), n_a, n_b >= 1. With a = (double)n_a, b = (double)n_b, t = a + b, per pixel and channel:
+ *   m        = (a * m_a + b * m_b) / t               (m_a, m_b: the inputs' rgb, TAKEN AS THE MEANS THEY ARE - a render's frame is
+ *                                                     max(mean, 0), which is the mean wherever no sample is negative; m is not clamped)
+ *   d        = m_b - m_a
+ *   Q        = ((a - 1) * v_a + (b - 1) * v_b) + (d * d) * ((a * b) / t)
+ *   variance = Q / (t - 1)
+ * The half-buffers follow the parity of the index in the concatenation: B's even samples stay even when n_a is even and become
+ * odd when n_a is odd. With the counts e_x = (n_x + 1) / 2, o_x = n_x / 2 (integer division) and
+ *   wmean(c1, x1, c2, x2) = (c1 > 0 ? (c2 > 0 ? (double)c1 * x1 + (double)c2 * x2 : (double)c1 * x1) : (double)c2 * x2) / (double)(c1 + c2)
+ * (a term whose count is 0 is skipped by the select, not multiplied by 0: half_b of a 1-sample input takes no part):
+ *   n_a even:  half_a = wmean(e_a, half_a_A, e_b, half_a_B)    half_b = wmean(o_a, half_b_A, o_b, half_b_B)
+ *   n_a odd:   half_a = wmean(e_a, half_a_A, o_b, half_b_B)    half_b = wmean(o_a, half_b_A, e_b, half_a_B)
+ * so the merged halves are again the means of (n + 1) / 2 and n / 2 samples, n = n_a + n_b.
+ * The highlights need full lists on both sides, n_a >= 16 and n_b >= 16 (K = MCRT_ROBUST_TOPS): below that the second-brightest
+ * sample of the union may sit in an input's rest. With L as in "Firefly suppression":
+ *   the list starts as A's four entries in order, with their luminances L(tops_A,k). For j = 0 .. 3, B's entry x = tops_B,j with
+ *   l = L(x): it is inserted before the first entry e with l > L_e (never when l is NaN) and the entry pushed past position 3
+ *   leaves; when there is no such e, x itself leaves. g_j = the luminance of what left at step j (L of the old entry 3, or l).
+ *   Ties go to A and to the lower index, as in the concatenated render.
+ *   tops  = the final list
+ *   level = (((a - 4) * level_A + (b - 4) * level_B) + ((((0.0 + g_0) + g_1) + g_2) + g_3)) / (t - 4)
+ * (from luminances, L being linear; not as a sum minus the tops, which cancels exactly when a firefly is present).
+ * NaN and Inf are not filtered: they stay in their own pixel.
+ *
+ * The channels form three groups, each optional as a whole: {rgb, variance}, {half_a, half_b}, {tops, level}. A group is wanted
+ * when out names it (both pointers; variance alone may be NULL: the mean only) and then needs the same channels of a and of b.
+ * Every output may be the corresponding buffer of a (an accumulator merged into in place); it must not overlap anything else.
+ * All buffers are [pixels]... packed, so the owned rows of a shard merge as they are. One launch, synchronous on the context's
+ * stream, no scene needed. Refused with MCRT_ERR_INVALID: a render in flight, pixels 0 or >= 2^32, n_a or n_b 0, n_a + n_b
+ * past UINT32_MAX, a, b or out NULL, no group wanted, half a group, a wanted group without its inputs; with MCRT_ERR_UNSUPPORTED:
+ * {tops, level} wanted with n_a or n_b below 16.
+ * stats: kernel_ms (HIP events of the call's own around its launch), total_ms, kernel_launches (1).
+ *
+ * Merging batches gives up the Sobol stratification across them: batch j restarts the sequence under another scramble instead of
+ * continuing it. Measured on the oracle's samples (profiles/NOTES_accumulate.md; 192 x 108, summed squared error against 4096 spp
+ * of another seed, 8 seed groups): 4 x 16 spp merged carries 1.27 times the squared error of 1 x 64 spp on hexagon_room_diffuse
+ * and 1.21 times on coffee_maker_qsah - what a caller pays for not having to choose sqrtspp before the first ray. */
+typedef struct mcrt_frame_summary {   /* a pointer may be NULL = channel not given / not wanted; [pixels]... packed */
+    double* rgb;        /* [pixels][3] */
+    double* variance;   /* [pixels][3] */
+    double* half_a;     /* [pixels][3] */
+    double* half_b;     /* [pixels][3] */
+    double* tops;       /* [pixels][MCRT_ROBUST_TOPS][3] */
+    double* level;      /* [pixels] */
+} mcrt_frame_summary;
+int mcrt_frame_merge_device(mcrt_ctx* ctx, uint64_t pixels, const mcrt_frame_summary* d_a, uint32_t n_a, const mcrt_frame_summary* d_b,
+                            uint32_t n_b, const mcrt_frame_summary* d_out, mcrt_stats* stats /* may be NULL */);
+/* Same with HOST pointers. */
+int mcrt_frame_merge(mcrt_ctx* ctx, uint64_t pixels, const mcrt_frame_summary* a, uint32_t n_a, const mcrt_frame_summary* b, uint32_t n_b,
+                     const mcrt_frame_summary* out, mcrt_stats* stats /* may be NULL */);
+
+/* 2. mcrt_render_converged: the stopping rule. Batches of cam->sqrtspp^2 samples are rendered, merged and summarised until the
+ * frame is quiet enough. Batch j (j = 0, 1, ...) is one mcrt_render_highlights_device (when a highlight channel is wanted) or
+ * mcrt_render_pixel_stats_device of cam as given, with the seed global_seed + j (wrapping in uint32_t). Batch 0 fills accumulators
+ * kept in the context; every later batch is merged into them in place by mcrt_frame_merge_device (accumulator = A, batch = B).
+ * After each batch, mcrt_frame_noise_device of the accumulated rgb and variance at the accumulated sample count gives
+ * relative_error. The loop ends when at least min_batches were rendered and relative_error <= target_relative_error, or when
+ * one more batch would exceed max_spp. The frame delivered is the accumulated one either way: ending above the target is not an
+ * error, result->final.relative_error says where the frame stands. The frame is the merged mean (not clamped again), so with
+ * one batch every output is that render's, bit for bit.
+ * out_rgb / d_out_rgb and the channels of stats_buffers and highlights that are not NULL are filled with FULL frames
+ * ([height][width]...). stats: paths, rays, node_tests, prim_tests, knn_searches, kernel_ms and kernel_launches summed over the
+ * batches (a merge counts one launch), kernel_id of the last batch, total_ms of the call.
+ * Refused with MCRT_ERR_UNSUPPORTED: what the statistics refuse (a camera whose film splats); cam->shard_count > 1 - the summary
+ * needs the whole frame: a sharded host merges its owned rows per shard with mcrt_frame_merge_device and decides after its
+ * gather -; a highlight channel wanted with fewer than 16 samples per batch. With MCRT_ERR_INVALID: a render in flight, cam or
+ * the frame NULL, sqrtspp 0, a target that is negative or not finite, max_spp below one batch. */
+#define MCRT_CONVERGE_TRACE 64
+typedef struct mcrt_converge_params {   /* NULL or a zero field = the default */
+    double   target_relative_error;   /* default 0.0: no target, render until max_spp; must be finite and >= 0 */
+    uint32_t max_spp;                 /* default: 1024, or one batch where that is more */
+    uint32_t min_batches;             /* default 1; with sqrtspp 1 it is 2 (a 1-sample batch has variance 0 and would stop at once) */
+} mcrt_converge_params;
+typedef struct mcrt_converge_result {
+    uint32_t batches, spp;                        /* batches rendered, samples per pixel accumulated */
+    mcrt_frame_noise_result final;                /* the summary of the delivered frame */
+    double relative_error[MCRT_CONVERGE_TRACE];   /* after each of the first 64 batches; 0.0 past `batches` */
+} mcrt_converge_result;
+int mcrt_render_converged_device(mcrt_ctx* ctx, const mcrt_camera_desc* cam, uint32_t global_seed, int integrator,
+                                 const mcrt_converge_params* params /* may be NULL */, double* d_out_rgb,
+                                 const mcrt_pixel_stats_buffers* d_stats_buffers /* may be NULL */,
+                                 const mcrt_highlight_buffers* d_highlights /* may be NULL */, mcrt_converge_result* result /* may be NULL */,
+                                 mcrt_stats* stats /* may be NULL */);
+/* Same with HOST pointers. */
+int mcrt_render_converged(mcrt_ctx* ctx, const mcrt_camera_desc* cam, uint32_t global_seed, int integrator,
+                          const mcrt_converge_params* params /* may be NULL */, double* out_rgb,
+                          const mcrt_pixel_stats_buffers* stats_buffers /* may be NULL */, const mcrt_highlight_buffers* highlights /* may be NULL */,
+                          mcrt_converge_result* result /* may be NULL */, mcrt_stats* stats /* may be NULL */);
+
 /* Photon emission pass on the GPU. Replaces the thread fan-out of
  * PhotonMapper::PhotonMapper (integrator/photon-mapper/photon-mapper.cpp:80-115: per emission
  * Sampler::initiate(light), setIndex(offset+i), light point + cosine direction, emitPhoton :225-277) for

@@ -219,6 +219,31 @@ class RobustBuffers(C.Structure):
     _fields_ = [("removed", C.c_void_p), ("clamped", C.c_void_p)]
 
 
+class FrameSummary(C.Structure):
+    """mcrt_frame_summary: a null pointer = channel not given / not wanted."""
+    _fields_ = [("rgb", C.c_void_p), ("variance", C.c_void_p), ("half_a", C.c_void_p), ("half_b", C.c_void_p), ("tops", C.c_void_p), ("level", C.c_void_p)]
+
+
+# channel -> the shape of a pixel, in mcrt_frame_summary order; the groups that mcrt_frame_merge takes or leaves as a whole
+FRAME_SUMMARY_CHANNELS = {"rgb": (3,), "variance": (3,), "half_a": (3,), "half_b": (3,), "tops": (ROBUST_TOPS, 3), "level": ()}
+FRAME_SUMMARY_GROUPS = (("rgb", "variance"), ("half_a", "half_b"), ("tops", "level"))
+CONVERGE_TRACE = 64
+
+
+class ConvergeParams(C.Structure):
+    """mcrt_converge_params: a zero field = the default (include/mcrt.h)."""
+    _fields_ = [("target_relative_error", C.c_double), ("max_spp", C.c_uint32), ("min_batches", C.c_uint32)]
+
+
+class ConvergeResult(C.Structure):
+    """mcrt_converge_result."""
+    _fields_ = [("batches", C.c_uint32), ("spp", C.c_uint32), ("final", FrameNoise), ("relative_error", C.c_double * CONVERGE_TRACE)]
+
+    def as_dict(self):
+        return {"batches": self.batches, "spp": self.spp, "final": self.final.as_dict(),
+                "relative_error": [self.relative_error[i] for i in range(min(self.batches, CONVERGE_TRACE))]}
+
+
 class PhotonEmissionDevice(C.Structure):
     _fields_ = [("global_count", C.c_uint64), ("caustic_count", C.c_uint64), ("d_global_photons", C.c_void_p), ("d_caustic_photons", C.c_void_p),
                 ("emission_paths", C.c_uint64), ("rays", C.c_uint64), ("kernel_ms", C.c_double)]
@@ -324,6 +349,12 @@ def lib():
         L.mcrt_render_highlights_device.argtypes = L.mcrt_render_highlights.argtypes
         L.mcrt_robust_resolve.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, C.POINTER(RobustParams), vp, C.POINTER(RobustBuffers), C.POINTER(Stats)]
         L.mcrt_robust_resolve_device.argtypes = L.mcrt_robust_resolve.argtypes
+    if hasattr(L, "mcrt_frame_merge"):  # (likewise)
+        L.mcrt_frame_merge.argtypes = [vp, C.c_uint64, C.POINTER(FrameSummary), C.c_uint32, C.POINTER(FrameSummary), C.c_uint32, C.POINTER(FrameSummary), C.POINTER(Stats)]
+        L.mcrt_frame_merge_device.argtypes = L.mcrt_frame_merge.argtypes
+        L.mcrt_render_converged.argtypes = [vp, C.POINTER(CameraDesc), C.c_uint32, C.c_int, C.POINTER(ConvergeParams), vp, C.POINTER(PixelStatsBuffers),
+                                            C.POINTER(HighlightBuffers), C.POINTER(ConvergeResult), C.POINTER(Stats)]
+        L.mcrt_render_converged_device.argtypes = L.mcrt_render_converged.argtypes
     L.mcrt_sampler.argtypes = [vp, C.c_uint64, _u32p, _u32p, C.c_uint32, C.c_uint32, _dp]
     L.mcrt_knn.argtypes = [vp, C.c_int, C.c_uint64, _dp, C.c_uint32, _u32p, _u32p, _dp]
     L.mcrt_bsdf.argtypes = [vp, C.c_uint64, _dp, _dp, _dp]
@@ -999,6 +1030,94 @@ class Context:
         if stats is not None:
             stats.update(st, resolve=st2)
         return {"rgb": hl["rgb"], "robust": res["robust"], "removed": res["removed"], "clamped": res["clamped"]}
+
+    def frame_merge(self, a, n_a, b, n_b, stats=None, in_place=False):
+        """mcrt_frame_merge: the summary of a's n_a samples followed by b's n_b. a and b are dicts channel -> array
+        (FRAME_SUMMARY_CHANNELS: "rgb", "variance", "half_a", "half_b" [.., 3], "tops" [.., 4, 3], "level" [..]); the channels both hold
+        are merged (whole groups, FRAME_SUMMARY_GROUPS; "rgb" alone gives the mean only) -> dict of the same channels. in_place: the
+        outputs are a's own arrays (which must then be contiguous float64). stats: a dict that receives mcrt_stats."""
+        self._sync_env()
+        names = [k for k in FRAME_SUMMARY_CHANNELS if k in a and k in b]
+        assert "rgb" in names or "half_a" in names or "tops" in names, names
+        first = names[0]
+        lead = np.shape(a[first])[:np.ndim(a[first]) - len(FRAME_SUMMARY_CHANNELS[first])]
+        sa, sb, so, res, keep = FrameSummary(), FrameSummary(), FrameSummary(), {}, []
+        for k in names:
+            shape = tuple(lead) + FRAME_SUMMARY_CHANNELS[k]
+            xa = a[k] if in_place else np.ascontiguousarray(a[k], dtype=np.float64)
+            xb = np.ascontiguousarray(b[k], dtype=np.float64)
+            assert xa.dtype == np.float64 and xa.flags["C_CONTIGUOUS"] and xa.shape == shape and xb.shape == shape, (k, xa.shape, xb.shape)
+            res[k] = xa if in_place else np.empty(shape, dtype=np.float64)
+            keep += [xa, xb]
+            setattr(sa, k, xa.ctypes.data), setattr(sb, k, xb.ctypes.data), setattr(so, k, res[k].ctypes.data)
+        st = Stats()
+        self._check(self._lib.mcrt_frame_merge(self._h, int(np.prod(lead, dtype=np.int64)), C.byref(sa), int(n_a), C.byref(sb), int(n_b), C.byref(so),
+                                               C.byref(st)), "mcrt_frame_merge")
+        if stats is not None:
+            stats.update(st.as_dict())
+        return res
+
+    def frame_merge_device(self, pixels, a, n_a, b, n_b, out=None):
+        """mcrt_frame_merge_device: a, b, out = dicts channel -> raw device pointer of [pixels]... buffers that are complete when this is
+        called; out None = merged into a in place (the channels a and b both name). Synchronous; returns the stats dict."""
+        self._sync_env()
+        if out is None:
+            out = {k: v for k, v in a.items() if v and b.get(k)}
+        sums = []
+        for d in (a, b, out):
+            s = FrameSummary()
+            for name, ptr in d.items():
+                assert name in FRAME_SUMMARY_CHANNELS, name
+                setattr(s, name, int(ptr) if ptr else None)
+            sums.append(s)
+        st = Stats()
+        self._check(self._lib.mcrt_frame_merge_device(self._h, int(pixels), C.byref(sums[0]), int(n_a), C.byref(sums[1]), int(n_b), C.byref(sums[2]),
+                                                      C.byref(st)), "mcrt_frame_merge_device")
+        return st.as_dict()
+
+    def render_converged(self, cam, global_seed, target_relative_error=0.0, max_spp=0, integrator=INTEGRATOR_PATH_TRACER, min_batches=0,
+                         channels=("variance",), stats=None):
+        """mcrt_render_converged: batches of cam.sqrtspp^2 samples at the seeds global_seed, global_seed + 1, ... merged until the
+        frame's relative_error is at most target_relative_error (0 = no target) or one more batch would exceed max_spp (0 = the
+        default) -> dict "rgb" [H,W,3], the channels wanted (PIXEL_STATS_CHANNELS and HIGHLIGHT_CHANNELS) of the accumulated frame, and
+        "result": batches, spp, final (the frame_noise dict of the delivered frame), relative_error (a list, one per batch, the first 64).
+        stats: a dict that receives mcrt_stats, summed over the batches."""
+        self._sync_env()
+        frame = (cam.height, cam.width)
+        res, hl, ps = {}, HighlightBuffers(), PixelStatsBuffers()
+        for name in ["rgb"] + list(channels):
+            assert name == "rgb" or name in HIGHLIGHT_CHANNELS or name in PIXEL_STATS_CHANNELS, name
+            res[name] = np.zeros(frame + HIGHLIGHT_CHANNELS.get(name, (3,)), dtype=np.float64)
+            if name != "rgb":
+                setattr(hl if name in HIGHLIGHT_CHANNELS else ps, name, res[name].ctypes.data)
+        par = ConvergeParams(float(target_relative_error), int(max_spp), int(min_batches))
+        out, st = ConvergeResult(), Stats()
+        self._check(self._lib.mcrt_render_converged(self._h, C.byref(cam), int(global_seed) & 0xFFFFFFFF, int(integrator), C.byref(par), res["rgb"].ctypes.data,
+                                                    C.byref(ps), C.byref(hl), C.byref(out), C.byref(st)), "mcrt_render_converged")
+        if stats is not None:
+            stats.update(st.as_dict())
+        res["result"] = out.as_dict()
+        return res
+
+    def render_converged_device(self, cam, global_seed, integrator, rgb_ptr, target_relative_error=0.0, max_spp=0, min_batches=0, stats_pointers=None,
+                                pointers=None):
+        """mcrt_render_converged_device: rgb_ptr, stats_pointers = dict statistics channel -> raw device pointer and pointers = dict
+        highlight channel -> raw device pointer, all FULL frames; channels left out or None are not delivered. Synchronous; returns
+        (the result dict of render_converged, the stats dict)."""
+        self._sync_env()
+        hl, ps = HighlightBuffers(), PixelStatsBuffers()
+        for name, ptr in (pointers or {}).items():
+            assert name in HIGHLIGHT_CHANNELS, name
+            setattr(hl, name, int(ptr) if ptr else None)
+        for name, ptr in (stats_pointers or {}).items():
+            assert name in PIXEL_STATS_CHANNELS, name
+            setattr(ps, name, int(ptr) if ptr else None)
+        par = ConvergeParams(float(target_relative_error), int(max_spp), int(min_batches))
+        out, st = ConvergeResult(), Stats()
+        self._check(self._lib.mcrt_render_converged_device(self._h, C.byref(cam), int(global_seed) & 0xFFFFFFFF, int(integrator), C.byref(par),
+                                                           C.c_void_p(int(rgb_ptr)) if rgb_ptr else None, C.byref(ps), C.byref(hl), C.byref(out),
+                                                           C.byref(st)), "mcrt_render_converged_device")
+        return out.as_dict(), st.as_dict()
 
     def sampler(self, pixel, index, shuffles, global_seed):
         pixel = np.ascontiguousarray(pixel, dtype=np.uint32)

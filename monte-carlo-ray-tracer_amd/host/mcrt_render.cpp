@@ -5,6 +5,7 @@
 //   mcrt_render scene.mcrt out.f64 [--width W --height H --sqrtspp S] [--seed N] [--photon] [--device D | --devices D0,D1,...]
 //               [--tga out.tga [--tonemapper hable|aces] [--exposure EV] [--gain EV] [--plain]] [--aov PREFIX]
 //               [--denoise OUT.f64 [--denoise-iterations N]] [--denoise-variance OUT.f64 [--denoise-variance-out VAR.f64]] [--stats PREFIX] [--robust PREFIX [--robust-kappa X] [--robust-radius R]]
+//               [--converge TARGET [--max-spp N]]
 //
 // Writes the frame as raw FP64 RGB, row-major (what Image::operator() holds, camera/image.cpp:53-56),
 // and prints the statistics. --tga also develops it the way Image::save does (auto exposure / gain, tone map, sRGB bytes:
@@ -23,6 +24,10 @@
 // --robust renders the frame through mcrt_render_highlights (the same frame; with --stats the statistics come from the same render) and
 // also writes the robust frame of mcrt_robust_resolve, PREFIX.robust.f64 and PREFIX.removed.f64 (raw FP64 RGB) and PREFIX.clamped.u32,
 // and prints how many pixels and samples were clamped and the luminance removed next to the frame's (one device).
+// --converge renders the frame through mcrt_render_converged: batches of sqrtspp^2 samples at the seeds N, N + 1, ... merged until the
+// frame's relative error (mcrt_frame_noise) is at most TARGET or one more batch would exceed --max-spp (default 1024); --stats, --robust
+// and --denoise-variance then read the accumulated buffers at the accumulated sample count. Prints batches, spp and the final relative
+// error (one device).
 // --devices renders the frame on several GPUs from this one process (mcrt_render_multi: one host thread per GPU).
 #include <cstdio>
 #include <cstdlib>
@@ -54,6 +59,8 @@ int main(int argc, char** argv) {
     std::string tga, aov, denoise, dvar, dvar_out, pstats, robust;
     mcrt_robust_params rparams{};
     mcrt_denoise_params dparams{};
+    mcrt_converge_params cparams{};
+    bool converge = false;
     std::vector<int> devices;
     for (int i = 3; i < argc; i++) {
         std::string k = argv[i];
@@ -79,6 +86,8 @@ int main(int argc, char** argv) {
         else if (k == "--robust" && i + 1 < argc) robust = argv[++i];
         else if (k == "--robust-kappa" && i + 1 < argc) rparams.kappa = std::strtod(argv[++i], nullptr);
         else if (k == "--robust-radius") rparams.radius = (uint32_t)val();
+        else if (k == "--converge" && i + 1 < argc) converge = true, cparams.target_relative_error = std::strtod(argv[++i], nullptr);
+        else if (k == "--max-spp") cparams.max_spp = (uint32_t)val();
         else if (k == "--denoise-iterations") dparams.iterations = (uint32_t)val();
         else if (k == "--tonemapper" && i + 1 < argc) image.tonemapper = (argv[++i][0] | 0x20) == 'a' ? MCRT_TONEMAP_ACES : MCRT_TONEMAP_HABLE;
         else if (k == "--exposure" && i + 1 < argc) image.exposure_compensation = std::strtod(argv[++i], nullptr);
@@ -111,9 +120,10 @@ int main(int argc, char** argv) {
     const int mode = photon ? MCRT_INTEGRATOR_PHOTON_MAPPER : MCRT_INTEGRATOR_PATH_TRACER;
     std::vector<double> variance, half_a, half_b;
     std::vector<double> tops, level;
-    if (rc == MCRT_OK && (!pstats.empty() || !robust.empty() || !dvar.empty())) {
+    uint32_t spp = cam.sqrtspp * cam.sqrtspp;  // of the delivered frame: --converge accumulates batches of that many
+    if (rc == MCRT_OK && (converge || !pstats.empty() || !robust.empty() || !dvar.empty())) {
         if (ctxs.size() > 1) {
-            std::fprintf(stderr, "--stats, --robust and --denoise-variance take one device\n");
+            std::fprintf(stderr, "--stats, --robust, --denoise-variance and --converge take one device\n");
             return 2;
         }
         if (!dvar.empty()) variance.resize(rgb.size());
@@ -127,9 +137,19 @@ int main(int argc, char** argv) {
         if (!robust.empty()) {
             tops.resize(rgb.size() * MCRT_ROBUST_TOPS);
             level.resize(rgb.size() / 3);
-            const mcrt_highlight_buffers h{tops.data(), level.data()};
+        }
+        const mcrt_highlight_buffers h{robust.empty() ? nullptr : tops.data(), robust.empty() ? nullptr : level.data()};
+        if (converge) {
+            mcrt_converge_result cr;
+            rc = mcrt_render_converged(ctx, &cam, seed, mode, &cparams, rgb.data(), &b, &h, &cr, &st);
+            if (rc == MCRT_OK) {
+                spp = cr.spp;
+                std::printf("{\"converge\":%.17g,\"batches\":%u,\"spp\":%u,\"relative_error\":%.17g,\"noise\":%.17g,\"signal\":%.17g}\n",
+                            cparams.target_relative_error, cr.batches, cr.spp, cr.final.relative_error, cr.final.noise, cr.final.signal);
+            }
+        } else if (!robust.empty())
             rc = mcrt_render_highlights(ctx, &cam, seed, mode, rgb.data(), &h, &b, &st);
-        } else
+        else
             rc = mcrt_render_pixel_stats(ctx, &cam, seed, mode, rgb.data(), &b, &st);
     } else if (rc == MCRT_OK)
         rc = ctxs.size() > 1 ? mcrt_render_multi(ctxs.data(), (uint32_t)ctxs.size(), &cam, seed, mode, rgb.data(), &st)
@@ -160,7 +180,7 @@ int main(int argc, char** argv) {
             }
         }
         mcrt_frame_noise_result fn;
-        rc = mcrt_frame_noise(ctx, (uint64_t)cam.width * cam.height, cam.sqrtspp * cam.sqrtspp, rgb.data(), variance.data(), &fn);
+        rc = mcrt_frame_noise(ctx, (uint64_t)cam.width * cam.height, spp, rgb.data(), variance.data(), &fn);
         if (rc != MCRT_OK) {
             std::fprintf(stderr, "mcrt error %d: %s\n", rc, mcrt_last_error(ctx));
             return 1;
@@ -174,7 +194,7 @@ int main(int argc, char** argv) {
         std::vector<uint32_t> clamped(px);
         const mcrt_robust_buffers b{removed.data(), clamped.data()};
         mcrt_stats rst;
-        rc = mcrt_robust_resolve(ctx, cam.width, cam.height, cam.sqrtspp * cam.sqrtspp, rgb.data(), tops.data(), level.data(), &rparams, out.data(), &b, &rst);
+        rc = mcrt_robust_resolve(ctx, cam.width, cam.height, spp, rgb.data(), tops.data(), level.data(), &rparams, out.data(), &b, &rst);
         if (rc != MCRT_OK) {
             std::fprintf(stderr, "mcrt error %d: %s\n", rc, mcrt_last_error(ctx));
             return 1;
@@ -266,7 +286,6 @@ int main(int argc, char** argv) {
             }
         }
         if (!dvar.empty()) {
-            const uint32_t spp = cam.sqrtspp * cam.sqrtspp;
             std::vector<double> filtered(px * 3), filtered_var(px * 3);
             mcrt_denoise_variance_params vparams{};
             vparams.iterations = dparams.iterations;
@@ -292,7 +311,7 @@ int main(int argc, char** argv) {
         }
     }
     std::printf("{\"width\":%u,\"height\":%u,\"spp\":%u,\"paths\":%llu,\"rays\":%llu,\"kernel_ms\":%.3f,\"total_ms\":%.3f,\"Mray_s\":%.1f}\n",
-                cam.width, cam.height, cam.sqrtspp * cam.sqrtspp, (unsigned long long)st.paths, (unsigned long long)st.rays,
+                cam.width, cam.height, spp, (unsigned long long)st.paths, (unsigned long long)st.rays,
                 st.kernel_ms, st.total_ms, st.rays / st.kernel_ms / 1e3);
     for (mcrt_ctx* c : ctxs) mcrt_destroy(c);
     mcrt_image_free(img);
