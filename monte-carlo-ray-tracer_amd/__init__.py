@@ -405,6 +405,29 @@ def _ptr(arr, ctype):
     return arr.ctypes.data_as(C.POINTER(ctype))
 
 
+def _pointer_struct(cls, pointers, allowed):
+    """The ctypes struct cls of a dict channel -> raw pointer (None = no dict): a channel left out, None or 0 stays NULL = not wanted."""
+    s = cls()
+    for name, ptr in (pointers or {}).items():
+        assert name in allowed, name
+        setattr(s, name, int(ptr) if ptr else None)
+    return s
+
+
+def _guide_buffers(aov, height, width):
+    """The filters' guide channels of render_aov's dict as (AovBuffers of host pointers, the contiguous arrays they point into, to keep
+    alive over the call). A channel left out or None stays NULL: the library names a channel it misses."""
+    bufs, keep = AovBuffers(), []
+    for name in DENOISE_GUIDES:
+        if aov.get(name) is None:
+            continue
+        a = np.ascontiguousarray(aov[name], dtype=np.float64)
+        assert a.shape == (height, width) + ((3,) if AOV_CHANNELS[name][1] == 3 else ()), (name, a.shape)
+        keep.append(a)
+        setattr(bufs, name, a.ctypes.data)
+    return bufs, keep
+
+
 class SceneImage:
     """A scene image (*.mcrt) loaded through mcrt_image_load: flattened Scene/BVH/Camera (+ photon
     maps) as written by the flattener inside the reference host."""
@@ -788,10 +811,7 @@ class Context:
         """mcrt_render_aov_device: pointers = dict channel -> raw device pointer (owned rows only, packed like render_device's
         output); channels left out are not computed. Synchronous; returns the stats dict."""
         self._sync_env()
-        bufs = AovBuffers()
-        for name, ptr in pointers.items():
-            assert name in AOV_CHANNELS, name
-            setattr(bufs, name, int(ptr))
+        bufs = _pointer_struct(AovBuffers, pointers, AOV_CHANNELS)
         st = Stats()
         self._check(self._lib.mcrt_render_aov_device(self._h, C.byref(cam), int(global_seed), C.byref(bufs), C.byref(st)), "mcrt_render_aov_device")
         return st.as_dict()
@@ -806,14 +826,7 @@ class Context:
         assert rgb.ndim == 3 and rgb.shape[2] == 3, rgb.shape
         height, width = rgb.shape[:2]
         par = DenoiseParams(**params)
-        bufs, keep = AovBuffers(), []
-        for name in DENOISE_GUIDES:
-            if name not in aov or aov[name] is None:
-                continue  # (the library names a channel it misses)
-            a = np.ascontiguousarray(aov[name], dtype=np.float64)
-            assert a.shape == (height, width) + ((3,) if AOV_CHANNELS[name][1] == 3 else ()), (name, a.shape)
-            keep.append(a)
-            setattr(bufs, name, a.ctypes.data)
+        bufs, keep = _guide_buffers(aov, height, width)
         out = np.empty_like(rgb)
         st = Stats()
         self._check(self._lib.mcrt_denoise(self._h, width, height, rgb.ctypes.data, C.byref(bufs), C.byref(par), out.ctypes.data, C.byref(st)), "mcrt_denoise")
@@ -825,10 +838,7 @@ class Context:
         """mcrt_denoise_device: rgb_ptr / out_ptr (may be the same) and pointers = dict guide channel -> raw device pointer, all full
         frames that are complete when this is called. Synchronous; returns the stats dict."""
         self._sync_env()
-        bufs = AovBuffers()
-        for name, ptr in pointers.items():
-            assert name in AOV_CHANNELS, name
-            setattr(bufs, name, int(ptr) if ptr else None)
+        bufs = _pointer_struct(AovBuffers, pointers, AOV_CHANNELS)
         par = DenoiseParams(**params)
         st = Stats()
         self._check(self._lib.mcrt_denoise_device(self._h, int(width), int(height), C.c_void_p(int(rgb_ptr)) if rgb_ptr else None, C.byref(bufs), C.byref(par),
@@ -847,14 +857,7 @@ class Context:
         assert rgb.ndim == 3 and rgb.shape[2] == 3 and variance.shape == rgb.shape, (rgb.shape, variance.shape)
         height, width = rgb.shape[:2]
         par = DenoiseVarianceParams(**params)
-        bufs, keep = AovBuffers(), []
-        for name in DENOISE_GUIDES:
-            if name not in aov or aov[name] is None:
-                continue  # (the library names a channel it misses)
-            a = np.ascontiguousarray(aov[name], dtype=np.float64)
-            assert a.shape == (height, width) + ((3,) if AOV_CHANNELS[name][1] == 3 else ()), (name, a.shape)
-            keep.append(a)
-            setattr(bufs, name, a.ctypes.data)
+        bufs, keep = _guide_buffers(aov, height, width)
         out, out_var = np.empty_like(rgb), (np.empty_like(rgb) if want_variance else None)
         st = Stats()
         self._check(self._lib.mcrt_denoise_variance(self._h, width, height, int(spp), rgb.ctypes.data, variance.ctypes.data, C.byref(bufs), C.byref(par),
@@ -868,10 +871,7 @@ class Context:
         None = not wanted) and pointers = dict guide channel -> raw device pointer, all full frames that are complete when this is called.
         Synchronous; returns the stats dict."""
         self._sync_env()
-        bufs = AovBuffers()
-        for name, ptr in pointers.items():
-            assert name in AOV_CHANNELS, name
-            setattr(bufs, name, int(ptr) if ptr else None)
+        bufs = _pointer_struct(AovBuffers, pointers, AOV_CHANNELS)
         par = DenoiseVarianceParams(**params)
         st = Stats()
         p = lambda x: C.c_void_p(int(x)) if x else None
@@ -918,10 +918,7 @@ class Context:
         """mcrt_render_pixel_stats_device: rgb_ptr and pointers = dict channel -> raw device pointer (owned rows only, packed like
         render_device's output); channels left out or None are not computed. Synchronous; returns the stats dict."""
         self._sync_env()
-        bufs = PixelStatsBuffers()
-        for name, ptr in (pointers or {}).items():
-            assert name in PIXEL_STATS_CHANNELS, name
-            setattr(bufs, name, int(ptr) if ptr else None)
+        bufs = _pointer_struct(PixelStatsBuffers, pointers, PIXEL_STATS_CHANNELS)
         st = Stats()
         self._check(self._lib.mcrt_render_pixel_stats_device(self._h, C.byref(cam), int(global_seed), int(integrator),
                                                              C.c_void_p(int(rgb_ptr)) if rgb_ptr else None, C.byref(bufs) if pointers is not None else None,
@@ -973,13 +970,8 @@ class Context:
         statistics channel -> raw device pointer (owned rows only, packed like render_device's output); channels left out or None are
         not computed. Synchronous; returns the stats dict."""
         self._sync_env()
-        hl, ps = HighlightBuffers(), PixelStatsBuffers()
-        for name, ptr in (pointers or {}).items():
-            assert name in HIGHLIGHT_CHANNELS, name
-            setattr(hl, name, int(ptr) if ptr else None)
-        for name, ptr in (stats_pointers or {}).items():
-            assert name in PIXEL_STATS_CHANNELS, name
-            setattr(ps, name, int(ptr) if ptr else None)
+        hl = _pointer_struct(HighlightBuffers, pointers, HIGHLIGHT_CHANNELS)
+        ps = _pointer_struct(PixelStatsBuffers, stats_pointers, PIXEL_STATS_CHANNELS)
         st = Stats()
         self._check(self._lib.mcrt_render_highlights_device(self._h, C.byref(cam), int(global_seed), int(integrator),
                                                             C.c_void_p(int(rgb_ptr)) if rgb_ptr else None, C.byref(hl) if pointers is not None else None,
@@ -1063,13 +1055,7 @@ class Context:
         self._sync_env()
         if out is None:
             out = {k: v for k, v in a.items() if v and b.get(k)}
-        sums = []
-        for d in (a, b, out):
-            s = FrameSummary()
-            for name, ptr in d.items():
-                assert name in FRAME_SUMMARY_CHANNELS, name
-                setattr(s, name, int(ptr) if ptr else None)
-            sums.append(s)
+        sums = [_pointer_struct(FrameSummary, d, FRAME_SUMMARY_CHANNELS) for d in (a, b, out)]
         st = Stats()
         self._check(self._lib.mcrt_frame_merge_device(self._h, int(pixels), C.byref(sums[0]), int(n_a), C.byref(sums[1]), int(n_b), C.byref(sums[2]),
                                                       C.byref(st)), "mcrt_frame_merge_device")
@@ -1105,13 +1091,8 @@ class Context:
         highlight channel -> raw device pointer, all FULL frames; channels left out or None are not delivered. Synchronous; returns
         (the result dict of render_converged, the stats dict)."""
         self._sync_env()
-        hl, ps = HighlightBuffers(), PixelStatsBuffers()
-        for name, ptr in (pointers or {}).items():
-            assert name in HIGHLIGHT_CHANNELS, name
-            setattr(hl, name, int(ptr) if ptr else None)
-        for name, ptr in (stats_pointers or {}).items():
-            assert name in PIXEL_STATS_CHANNELS, name
-            setattr(ps, name, int(ptr) if ptr else None)
+        hl = _pointer_struct(HighlightBuffers, pointers, HIGHLIGHT_CHANNELS)
+        ps = _pointer_struct(PixelStatsBuffers, stats_pointers, PIXEL_STATS_CHANNELS)
         par = ConvergeParams(float(target_relative_error), int(max_spp), int(min_batches))
         out, st = ConvergeResult(), Stats()
         self._check(self._lib.mcrt_render_converged_device(self._h, C.byref(cam), int(global_seed) & 0xFFFFFFFF, int(integrator), C.byref(par),

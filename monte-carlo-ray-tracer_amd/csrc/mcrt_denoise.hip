@@ -8,6 +8,7 @@
 #include <hip/hip_runtime.h>
 
 #include "mcrt_denoise.hpp"
+#include "mcrt_atrous_launch.hpp"
 #include "mcrt_denoise_launch.hpp"
 
 using namespace mcrt;
@@ -29,21 +30,14 @@ __global__ void __launch_bounds__(kDenoiseBlock) denoiseTileKernel(DenoiseStep s
     denoiseTileBlock(st, blockIdx.x, threadIdx.x, tile);
 }
 
-uint32_t pixelBlocks(uint32_t width, uint32_t height) { return (uint32_t)(((uint64_t)width * height + kDenoiseBlock - 1) / kDenoiseBlock); }
-
 }  // namespace
 
 namespace mcrt {
 int launchDenoisePrep(void* stream, const DenoiseFrame& f) {
-    hipLaunchKernelGGL(denoisePrepKernel, dim3(pixelBlocks(f.width, f.height)), dim3(kDenoiseBlock), 0, (hipStream_t)stream, f);
+    hipLaunchKernelGGL(denoisePrepKernel, dim3(denoisePixelBlocks(f.width, f.height)), dim3(kDenoiseBlock), 0, (hipStream_t)stream, f);
     return (int)hipGetLastError();
 }
 int launchDenoiseStep(void* stream, const DenoiseStep& st, bool tile) {
-    const uint64_t tiles = denoiseTileBlocks(denoiseTiling(st.width, st.height, st.step));
-    if (tile && tiles <= 0x7FFFFFFFull)  // (a grid the runtime takes; frames of a few rows and billions of columns go the plain way)
-        hipLaunchKernelGGL(denoiseTileKernel, dim3((uint32_t)tiles), dim3(kDenoiseBlock), 0, (hipStream_t)stream, st);
-    else
-        hipLaunchKernelGGL(denoisePlainKernel, dim3(pixelBlocks(st.width, st.height)), dim3(kDenoiseBlock), 0, (hipStream_t)stream, st);
-    return (int)hipGetLastError();
+    return launchAtrousStep<DenoiseStep, denoiseTileKernel, denoisePlainKernel>(stream, st, tile);
 }
 }  // namespace mcrt

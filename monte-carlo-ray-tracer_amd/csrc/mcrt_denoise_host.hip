@@ -5,7 +5,7 @@
 // form stages its six input frames in another 128 B per pixel and filters the beauty frame in place.
 #include "mcrt_denoise.hpp"
 #include "mcrt_denoise_launch.hpp"
-#include "mcrt_pass_host.hpp"
+#include "mcrt_denoise_guides.hpp"
 
 using namespace mcrt;
 
@@ -17,18 +17,7 @@ int validate(mcrt_ctx* ctx, uint32_t width, uint32_t height, const double* rgb, 
     if ((uint64_t)width * height == 0 || (uint64_t)width * height > 0xFFFFFFFFull)
         return ctxFail(ctx, MCRT_ERR_INVALID, w + ": width * height must be non-zero and below 2^32");
     if (!rgb || !out) return ctxFail(ctx, MCRT_ERR_INVALID, w + ": the beauty frame or the output frame is NULL");
-    if (!guides) return ctxFail(ctx, MCRT_ERR_INVALID, w + ": guides is NULL");
-    const struct {
-        const double* p;
-        const char* name;
-        bool needed;
-    } ch[5] = {{guides->shading_normal, "shading_normal", true},
-               {guides->normal, "normal", true},
-               {guides->position, "position", true},
-               {guides->coverage, "coverage", true},
-               {guides->albedo, "albedo", !(s.flags & MCRT_DENOISE_NO_ALBEDO)}};
-    for (const auto& c : ch)
-        if (c.needed && !c.p) return ctxFail(ctx, MCRT_ERR_INVALID, w + ": guide channel " + c.name + " is NULL");
+    if (int rc = denoiseCheckGuides(ctx, w, guides, !(s.flags & MCRT_DENOISE_NO_ALBEDO))) return rc;
     if (s.iterations > kDenoiseMaxIterations)
         return ctxFail(ctx, MCRT_ERR_INVALID, w + ": " + std::to_string(s.iterations) + " iterations, at most " + std::to_string(kDenoiseMaxIterations));
     if (s.normal_power_log2 > kDenoiseMaxNormalPowerLog2)
@@ -104,20 +93,11 @@ extern "C" int mcrt_denoise(mcrt_ctx* ctx, uint32_t width, uint32_t height, cons
     const size_t pixels = (size_t)width * height;
     // the six input frames as one device allocation of 128 B per pixel: beauty (filtered in place), Ns, N, P, albedo, coverage
     const bool with_albedo = !(s.flags & MCRT_DENOISE_NO_ALBEDO);
-    FrameChannel ch[6] = {{rgb, out_rgb, 24},
-                          {guides->shading_normal, nullptr, 24},
-                          {guides->normal, nullptr, 24},
-                          {guides->position, nullptr, 24},
-                          {with_albedo ? guides->albedo : nullptr, nullptr, 24},
-                          {guides->coverage, nullptr, 8}};
-    StagedFrames frames{{ctx, "mcrt_denoise", kPassDenoise, 3, kPackedAll, ch, 6}};
+    FrameChannel ch[1 + kDenoiseGuides] = {{rgb, out_rgb, 24}};
+    denoiseGuideChannels(*guides, with_albedo, ch + 1);
+    StagedFrames frames{{ctx, "mcrt_denoise", kPassDenoise, 3, kPackedAll, ch, 1 + kDenoiseGuides}};
     if (int rc = frames.up(pixels)) return rc;
-    mcrt_aov_buffers d{};
-    d.shading_normal = (double*)ch[1].dev;
-    d.normal = (double*)ch[2].dev;
-    d.position = (double*)ch[3].dev;
-    d.albedo = (double*)ch[4].dev;
-    d.coverage = (double*)ch[5].dev;
+    const mcrt_aov_buffers d = denoiseDeviceGuides(ch + 1);
     mcrt_stats st;
     if (int rc = mcrt_denoise_device(ctx, width, height, (double*)ch[0].dev, &d, params, (double*)ch[0].dev, &st)) return rc;
     if (int rc = frames.down(pixels)) return rc;

@@ -10,6 +10,7 @@
 #include <hip/hip_runtime.h>
 
 #include "mcrt_denoise_var.hpp"
+#include "mcrt_atrous_launch.hpp"
 #include "mcrt_denoise_var_launch.hpp"
 
 using namespace mcrt;
@@ -31,21 +32,14 @@ __global__ void __launch_bounds__(kDenoiseBlock) denoiseVarTileKernel(DenoiseVar
     denoiseVarTileBlock(st, blockIdx.x, threadIdx.x, tile);
 }
 
-uint32_t pixelBlocks(uint32_t width, uint32_t height) { return (uint32_t)(((uint64_t)width * height + kDenoiseBlock - 1) / kDenoiseBlock); }
-
 }  // namespace
 
 namespace mcrt {
 int launchDenoiseVarPrep(void* stream, const DenoiseVarFrame& f) {
-    hipLaunchKernelGGL(denoiseVarPrepKernel, dim3(pixelBlocks(f.width, f.height)), dim3(kDenoiseBlock), 0, (hipStream_t)stream, f);
+    hipLaunchKernelGGL(denoiseVarPrepKernel, dim3(denoisePixelBlocks(f.width, f.height)), dim3(kDenoiseBlock), 0, (hipStream_t)stream, f);
     return (int)hipGetLastError();
 }
 int launchDenoiseVarStep(void* stream, const DenoiseVarStep& st, bool tile) {
-    const uint64_t tiles = denoiseTileBlocks(denoiseTiling(st.width, st.height, st.step));
-    if (tile && tiles <= 0x7FFFFFFFull)  // (a grid the runtime takes; frames of a few rows and billions of columns go the plain way)
-        hipLaunchKernelGGL(denoiseVarTileKernel, dim3((uint32_t)tiles), dim3(kDenoiseBlock), 0, (hipStream_t)stream, st);
-    else
-        hipLaunchKernelGGL(denoiseVarPlainKernel, dim3(pixelBlocks(st.width, st.height)), dim3(kDenoiseBlock), 0, (hipStream_t)stream, st);
-    return (int)hipGetLastError();
+    return launchAtrousStep<DenoiseVarStep, denoiseVarTileKernel, denoiseVarPlainKernel>(stream, st, tile);
 }
 }  // namespace mcrt

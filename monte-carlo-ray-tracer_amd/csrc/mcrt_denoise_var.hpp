@@ -1,27 +1,20 @@
-// Variance-guided denoised output (include/mcrt.h mcrt_denoise_variance*): the a-trous filter of mcrt_denoise.hpp with a colour weight in
-// units of the pixels' estimated variance, and that variance carried through the iterations. The per-pixel text, shared by the three
-// gfx950 kernels of mcrt_denoise_var.hip and the host emulation of the CPU tests (tests/emu/denoise_var_emu.cpp): both run this file.
-// Only FP64 + - * /, compare and select, in the order include/mcrt.h states, built uncontracted - both outputs are functions of the
-// inputs bit for bit. dot, max0, the albedo factor, the geometric weights and the tiling of a step are mcrt_denoise.hpp's own.
+// Variance-guided denoised output (include/mcrt.h mcrt_denoise_variance*): the a-trous filter of mcrt_atrous.hpp with a colour weight in
+// units of the pixels' estimated variance, and that variance carried through the iterations. What is this filter's own - settings, the
+// prep pixel, the colour weight, the sums and the store; the 25-tap loop, the tap sources and the tile form are mcrt_atrous.hpp's. The
+// per-pixel text, shared by the three gfx950 kernels of mcrt_denoise_var.hip and the host emulation of the CPU tests
+// (tests/emu/denoise_var_emu.cpp): both run this file. Only FP64 + - * /, compare and select, in the order include/mcrt.h states, built
+// uncontracted - both outputs are functions of the inputs bit for bit.
 //
-// Memory (device scratch, per pixel): the GUIDE record of mcrt_denoise.hpp (10 doubles, packed once by the prep pass) and one record of
+// Memory (device scratch, per pixel): the GUIDE record of mcrt_atrous.hpp (10 doubles, packed once by the prep pass) and one record of
 // 6 doubles {I.xyz, V.xyz} (48 B) in each of two frames that the iterations ping-pong: a tap reads irradiance and variance together.
-//
-// Two forms of an iteration, the same denoiseVarPixel behind two tap sources, as in mcrt_denoise.hpp:
-//   plain  one lane per pixel, taps from memory
-//   tile   a workgroup of 256 lanes takes a 16 x 16 tile of ONE residue class of the step and stages its 20 x 20 records (field-major)
-//          in LDS - 16 x 400 doubles = 51 200 B, three workgroups in a CU's 160 KB - and runs the 25 taps from there after one barrier
+// The tile form's LDS is 16 x 400 doubles = 51 200 B, three workgroups in a CU's 160 KB.
 #pragma once
 
-#include "mcrt_denoise.hpp"
+#include "mcrt_atrous.hpp"
 
 namespace mcrt {
 
-constexpr uint32_t kDenoiseVarIvWords = 6;                                            // I.xyz, V.xyz
-constexpr uint32_t kDenoiseVarRecWords = kDenoiseGuideWords + kDenoiseVarIvWords;      // 16 doubles per record in LDS
-constexpr uint32_t kDenoiseVarTileWords = kDenoiseVarRecWords * kDenoiseTileRecs;      // 6400 doubles
-constexpr uint32_t kDenoiseVarTileLdsBytes = kDenoiseVarTileWords * 8;                 // 51 200 B (tests/test_denoise_var_library.py)
-static_assert(3 * kDenoiseVarTileLdsBytes <= 160 * 1024, "three workgroups per CU by LDS");
+constexpr uint32_t kDenoiseVarIvWords = 6;  // I.xyz, V.xyz
 
 // mcrt_denoise_variance_params with its defaults filled in (NULL or a zero field = the default).
 struct DenoiseVarSettings {
@@ -100,7 +93,8 @@ MCRT_HD d3 denoiseVarOfMean(const DenoiseVarFrame& f, uint64_t q) {
 }
 
 MCRT_HD void denoiseVarPrepPixel(const DenoiseVarFrame& f, uint64_t p) {
-    // every load before the first store, as in denoisePrepPixel; the 3 x 3 neighbours' v, albedo and coverage come from the input frames
+    // every load before the first store, as in denoisePrepPixel (mcrt_denoise.hpp): the frames may alias as far as the compiler knows; the
+    // 3 x 3 neighbours' v, albedo and coverage come from the input frames
     const d3 ns = denoiseLd3(f.shading_normal + 3 * p), n = denoiseLd3(f.normal + 3 * p), pos = denoiseLd3(f.position + 3 * p);
     const d3 c = denoiseLd3(f.rgb + 3 * p), a = denoiseVarAlbedoFactor(f.albedo, p, f.albedo_floor);
     const double cov = f.coverage[p];
@@ -148,37 +142,6 @@ MCRT_HD double denoiseVarWeight(const DenoiseVarStep& st, const DenoiseVarRec& c
     return wg * wc;
 }
 
-// I_{i+1} and V_{i+1} of a covered pixel whose own record is c. src.tap(dx, dy, q): the record of tap (dx, dy) into q, false when the tap
-// is outside the frame or has coverage 0.
-template <class Src>
-MCRT_HD void denoiseVarPixel(const DenoiseVarStep& st, const Src& src, const DenoiseVarRec& c, d3& irr, d3& var) {
-    const double h[5] = {1.0 / 16.0, 1.0 / 4.0, 3.0 / 8.0, 1.0 / 4.0, 1.0 / 16.0};
-    d3 sum = splat(0.0), vsum = splat(0.0);
-    double wsum = 0.0;
-#pragma unroll
-    for (int dy = -2; dy <= 2; dy++) {
-#pragma unroll
-        for (int dx = -2; dx <= 2; dx++) {
-            double w;
-            DenoiseVarRec q;
-            if (dx == 0 && dy == 0) {
-                w = 9.0 / 64.0;
-                q.irr = c.irr;
-                q.var = c.var;
-            } else {
-                if (!src.tap(dx, dy, q)) continue;
-                w = denoiseVarWeight(st, c, q, h[dy + 2] * h[dx + 2]);
-            }
-            sum = sum + w * q.irr;
-            vsum = vsum + (w * w) * q.var;
-            wsum += w;
-        }
-    }
-    const double r = 1.0 / wsum;
-    irr = sum * r;
-    var = vsum * (r * r);
-}
-
 // The pixel's new record into st.out; the last iteration multiplies the albedo factor back in and writes the caller's frames.
 MCRT_HD void denoiseVarStore(const DenoiseVarStep& st, uint64_t p, d3 irr, d3 var) {
     if (st.out) {
@@ -199,101 +162,45 @@ MCRT_HD void denoiseVarStore(const DenoiseVarStep& st, uint64_t p, d3 irr, d3 va
     }
 }
 
-// ---- plain form ------------------------------------------------------------------------------------------------------------------
-struct DenoiseVarGlobalTaps {
-    const DenoiseVarStep& st;
-    uint32_t x, y;
-    MCRT_HD bool tap(int dx, int dy, DenoiseVarRec& q) const {
-        const int64_t qx = (int64_t)x + (int64_t)st.step * dx, qy = (int64_t)y + (int64_t)st.step * dy;
-        if (qx < 0 || qy < 0 || qx >= (int64_t)st.width || qy >= (int64_t)st.height) return false;
-        const uint64_t r = (uint64_t)qy * st.width + (uint64_t)qx;
-        const double* g = st.guide + r * kDenoiseGuideWords;
-        if (g[9] == 0.0) return false;
-        q.ns = denoiseLd3(g);
-        q.p = denoiseLd3(g + 6);
-        q.irr = denoiseLd3(st.in + r * kDenoiseVarIvWords);
-        q.var = denoiseLd3(st.in + r * kDenoiseVarIvWords + 3);
-        return true;
+// What mcrt_atrous.hpp's skeleton asks of a filter.
+struct DenoiseVarFilter {
+    using Step = DenoiseVarStep;
+    using Rec = DenoiseVarRec;
+    static constexpr uint32_t kValueWords = kDenoiseVarIvWords;
+    template <class Ld>
+    static MCRT_HD void loadValue(Rec& q, const Ld& ld) {
+        q.irr = ld(0);
+        q.var = ld(3);
     }
-};
-
-MCRT_HD void denoiseVarPlainPixel(const DenoiseVarStep& st, uint64_t p) {
-    const uint32_t x = (uint32_t)(p % st.width), y = (uint32_t)(p / st.width);
-    const double* g = st.guide + p * kDenoiseGuideWords;
-    DenoiseVarRec c;
-    c.irr = denoiseLd3(st.in + p * kDenoiseVarIvWords);
-    c.var = denoiseLd3(st.in + p * kDenoiseVarIvWords + 3);
-    if (g[9] == 0.0) return denoiseVarStore(st, p, c.irr, c.var);
-    c.ns = denoiseLd3(g);
-    c.n = denoiseLd3(g + 3);
-    c.p = denoiseLd3(g + 6);
-    d3 irr, var;
-    denoiseVarPixel(st, DenoiseVarGlobalTaps{st, x, y}, c, irr, var);
-    denoiseVarStore(st, p, irr, var);
-}
-
-// ---- tile form -------------------------------------------------------------------------------------------------------------------
-// The workgroups of an iteration are denoiseTiling's (mcrt_denoise.hpp): the same tiles of the same residue classes.
-#if defined(__HIPCC__) || defined(MCRT_WAVE_EMU)
-
-MCRT_HD d3 denoiseVarLds3(const double* lds, uint32_t field, uint32_t t) {
-    return d3{lds[field * kDenoiseTileRecs + t], lds[(field + 1) * kDenoiseTileRecs + t], lds[(field + 2) * kDenoiseTileRecs + t]};
-}
-
-struct DenoiseVarLdsTaps {
-    const double* lds;  // [kDenoiseVarRecWords][kDenoiseTileRecs]
-    uint32_t r;         // the centre's record
-    MCRT_HD bool tap(int dx, int dy, DenoiseVarRec& q) const {
-        const uint32_t t = (uint32_t)((int)r + dy * (int)kDenoiseSide + dx);
-        if (lds[9 * kDenoiseTileRecs + t] == 0.0) return false;
-        q.ns = denoiseVarLds3(lds, 0, t);
-        q.p = denoiseVarLds3(lds, 6, t);
-        q.irr = denoiseVarLds3(lds, 10, t);
-        q.var = denoiseVarLds3(lds, 13, t);
-        return true;
-    }
-};
-
-// One workgroup (kDenoiseBlock lanes, `tid` of them this one) of the tile form; lds: kDenoiseVarTileWords doubles.
-__device__ __forceinline__ void denoiseVarTileBlock(const DenoiseVarStep& st, uint32_t block, uint32_t tid, double* lds) {
-    const DenoiseTiling tl = denoiseTiling(st.width, st.height, st.step);
-    const uint32_t per_row = tl.ncx * tl.tiles_x;
-    const uint32_t bx = block % per_row, by = block / per_row;
-    const uint32_t rx = bx % tl.ncx, ry = by % tl.ncy;
-    const int64_t cx0 = (int64_t)(bx / tl.ncx) * kDenoiseTile, cy0 = (int64_t)(by / tl.ncy) * kDenoiseTile;  // the tile's first class member
-    for (uint32_t r = tid; r < kDenoiseTileRecs; r += kDenoiseBlock) {
-        const int64_t x = (int64_t)rx + (int64_t)st.step * (cx0 - 2 + (int64_t)(r % kDenoiseSide));
-        const int64_t y = (int64_t)ry + (int64_t)st.step * (cy0 - 2 + (int64_t)(r / kDenoiseSide));
-        if (x >= 0 && y >= 0 && x < (int64_t)st.width && y < (int64_t)st.height) {
-            const uint64_t p = (uint64_t)y * st.width + (uint64_t)x;
-            const double* g = st.guide + p * kDenoiseGuideWords;
-            const double* iv = st.in + p * kDenoiseVarIvWords;
-#pragma unroll
-            for (uint32_t k = 0; k < kDenoiseGuideWords; k++) lds[k * kDenoiseTileRecs + r] = g[k];
-#pragma unroll
-            for (uint32_t k = 0; k < kDenoiseVarIvWords; k++) lds[(kDenoiseGuideWords + k) * kDenoiseTileRecs + r] = iv[k];
-        } else {
-            lds[9 * kDenoiseTileRecs + r] = 0.0;  // outside the frame: skipped like a tap without coverage (its other words are not read)
+    static MCRT_HD double weight(const Step& st, const Rec& c, const Rec& q, double h) { return denoiseVarWeight(st, c, q, h); }
+    struct Acc {
+        d3 sum = splat(0.0), vsum = splat(0.0);
+        double wsum = 0.0;
+        MCRT_HD void add(double w, const Rec& q) {
+            sum = sum + w * q.irr;
+            vsum = vsum + (w * w) * q.var;
+            wsum += w;
         }
-    }
-    __syncthreads();
-    const uint32_t lx = tid % kDenoiseTile, ly = tid / kDenoiseTile;
-    const int64_t x = (int64_t)rx + (int64_t)st.step * (cx0 + lx), y = (int64_t)ry + (int64_t)st.step * (cy0 + ly);
-    if (x >= (int64_t)st.width || y >= (int64_t)st.height) return;
-    const uint64_t p = (uint64_t)y * st.width + (uint64_t)x;
-    const uint32_t r = (ly + 2) * kDenoiseSide + lx + 2;
-    DenoiseVarRec c;
-    c.irr = denoiseVarLds3(lds, 10, r);
-    c.var = denoiseVarLds3(lds, 13, r);
-    if (lds[9 * kDenoiseTileRecs + r] == 0.0) return denoiseVarStore(st, p, c.irr, c.var);
-    c.ns = denoiseVarLds3(lds, 0, r);
-    c.n = denoiseVarLds3(lds, 3, r);
-    c.p = denoiseVarLds3(lds, 6, r);
-    d3 irr, var;
-    denoiseVarPixel(st, DenoiseVarLdsTaps{lds, r}, c, irr, var);
-    denoiseVarStore(st, p, irr, var);
-}
+        MCRT_HD Rec result() const {
+            const double r = 1.0 / wsum;
+            Rec o{};
+            o.irr = sum * r;
+            o.var = vsum * (r * r);
+            return o;
+        }
+    };
+    static MCRT_HD void store(const Step& st, uint64_t p, const Rec& rec) { denoiseVarStore(st, p, rec.irr, rec.var); }
+};
+constexpr uint32_t kDenoiseVarTileWords = kAtrousTileWords<DenoiseVarFilter>;  // 6400 doubles
+constexpr uint32_t kDenoiseVarTileLdsBytes = kDenoiseVarTileWords * 8;         // 51 200 B (tests/test_denoise_var_library.py)
+static_assert(3 * kDenoiseVarTileLdsBytes <= 160 * 1024, "three workgroups per CU by LDS");
 
-#endif  // __HIPCC__ || MCRT_WAVE_EMU
+// An iteration's pixel in the plain form, and one workgroup (lane `tid` of kDenoiseBlock) of the tile form; lds: kDenoiseVarTileWords doubles.
+MCRT_HD void denoiseVarPlainPixel(const DenoiseVarStep& st, uint64_t p) { atrousPlainPixel<DenoiseVarFilter>(st, p); }
+#if defined(__HIPCC__) || defined(MCRT_WAVE_EMU)
+__device__ __forceinline__ void denoiseVarTileBlock(const DenoiseVarStep& st, uint32_t block, uint32_t tid, double* lds) {
+    atrousTileBlock<DenoiseVarFilter>(st, block, tid, lds);
+}
+#endif
 
 }  // namespace mcrt

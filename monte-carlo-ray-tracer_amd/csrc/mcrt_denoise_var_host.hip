@@ -5,7 +5,7 @@
 // host-pointer form stages its seven input frames in another 152 B per pixel and filters the beauty and the variance frame in place.
 #include "mcrt_denoise_var.hpp"
 #include "mcrt_denoise_var_launch.hpp"
-#include "mcrt_pass_host.hpp"
+#include "mcrt_denoise_guides.hpp"
 
 using namespace mcrt;
 
@@ -19,18 +19,7 @@ int validate(mcrt_ctx* ctx, uint32_t width, uint32_t height, uint32_t spp, const
     if (spp == 0) return ctxFail(ctx, MCRT_ERR_INVALID, w + ": spp must not be 0");
     if (!rgb || !out) return ctxFail(ctx, MCRT_ERR_INVALID, w + ": the beauty frame or the output frame is NULL");
     if (!variance) return ctxFail(ctx, MCRT_ERR_INVALID, w + ": the variance frame is NULL");
-    if (!guides) return ctxFail(ctx, MCRT_ERR_INVALID, w + ": guides is NULL");
-    const struct {
-        const double* p;
-        const char* name;
-        bool needed;
-    } ch[5] = {{guides->shading_normal, "shading_normal", true},
-               {guides->normal, "normal", true},
-               {guides->position, "position", true},
-               {guides->coverage, "coverage", true},
-               {guides->albedo, "albedo", !(s.flags & MCRT_DENOISE_NO_ALBEDO)}};
-    for (const auto& c : ch)
-        if (c.needed && !c.p) return ctxFail(ctx, MCRT_ERR_INVALID, w + ": guide channel " + c.name + " is NULL");
+    if (int rc = denoiseCheckGuides(ctx, w, guides, !(s.flags & MCRT_DENOISE_NO_ALBEDO))) return rc;
     if (const char* why = denoiseVarSettingsError(s)) return ctxFail(ctx, MCRT_ERR_INVALID, w + ": " + why);
     return MCRT_OK;
 }
@@ -111,21 +100,11 @@ extern "C" int mcrt_denoise_variance(mcrt_ctx* ctx, uint32_t width, uint32_t hei
     // the seven input frames as one device allocation of 152 B per pixel: beauty and variance (both filtered in place), Ns, N, P, albedo,
     // coverage
     const bool with_albedo = !(s.flags & MCRT_DENOISE_NO_ALBEDO);
-    FrameChannel ch[7] = {{rgb, out_rgb, 24},
-                          {variance, out_variance, 24},
-                          {guides->shading_normal, nullptr, 24},
-                          {guides->normal, nullptr, 24},
-                          {guides->position, nullptr, 24},
-                          {with_albedo ? guides->albedo : nullptr, nullptr, 24},
-                          {guides->coverage, nullptr, 8}};
-    StagedFrames frames{{ctx, "mcrt_denoise_variance", kPassDenoiseVar, 3, kPackedAll, ch, 7}};
+    FrameChannel ch[2 + kDenoiseGuides] = {{rgb, out_rgb, 24}, {variance, out_variance, 24}};
+    denoiseGuideChannels(*guides, with_albedo, ch + 2);
+    StagedFrames frames{{ctx, "mcrt_denoise_variance", kPassDenoiseVar, 3, kPackedAll, ch, 2 + kDenoiseGuides}};
     if (int rc = frames.up(pixels)) return rc;
-    mcrt_aov_buffers d{};
-    d.shading_normal = (double*)ch[2].dev;
-    d.normal = (double*)ch[3].dev;
-    d.position = (double*)ch[4].dev;
-    d.albedo = (double*)ch[5].dev;
-    d.coverage = (double*)ch[6].dev;
+    const mcrt_aov_buffers d = denoiseDeviceGuides(ch + 2);
     mcrt_stats st;
     if (int rc = mcrt_denoise_variance_device(ctx, width, height, spp, (double*)ch[0].dev, (double*)ch[1].dev, &d, params, (double*)ch[0].dev,
                                               out_variance ? (double*)ch[1].dev : nullptr, &st))
