@@ -183,12 +183,17 @@ class DenoiseVarianceParams(C.Structure):
                 ("sigma_plane", C.c_double), ("albedo_floor", C.c_double), ("flags", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+ROBUST_TOPS = 4
+# The per-sample summary of a render: channel -> the shape of a pixel, in mcrt_frame_summary order (csrc/mcrt_summary_channels.hpp is the
+# same table for the library); mcrt_pixel_stats_buffers is its members 1..3, mcrt_highlight_buffers its members 4..5.
+FRAME_SUMMARY_CHANNELS = {"rgb": (3,), "variance": (3,), "half_a": (3,), "half_b": (3,), "tops": (ROBUST_TOPS, 3), "level": ()}
+PIXEL_STATS_CHANNELS = tuple(FRAME_SUMMARY_CHANNELS)[1:4]
+HIGHLIGHT_CHANNELS = {k: FRAME_SUMMARY_CHANNELS[k] for k in tuple(FRAME_SUMMARY_CHANNELS)[4:6]}
+
+
 class PixelStatsBuffers(C.Structure):
     """mcrt_pixel_stats_buffers: a null pointer = channel not wanted."""
     _fields_ = [("variance", C.c_void_p), ("half_a", C.c_void_p), ("half_b", C.c_void_p)]
-
-
-PIXEL_STATS_CHANNELS = ("variance", "half_a", "half_b")
 
 
 class FrameNoise(C.Structure):
@@ -202,11 +207,6 @@ class FrameNoise(C.Structure):
 class HighlightBuffers(C.Structure):
     """mcrt_highlight_buffers: a null pointer = channel not wanted."""
     _fields_ = [("tops", C.c_void_p), ("level", C.c_void_p)]
-
-
-ROBUST_TOPS = 4
-# channel -> the shape of a pixel, in mcrt_highlight_buffers order
-HIGHLIGHT_CHANNELS = {"tops": (ROBUST_TOPS, 3), "level": ()}
 
 
 class RobustParams(C.Structure):
@@ -224,9 +224,26 @@ class FrameSummary(C.Structure):
     _fields_ = [("rgb", C.c_void_p), ("variance", C.c_void_p), ("half_a", C.c_void_p), ("half_b", C.c_void_p), ("tops", C.c_void_p), ("level", C.c_void_p)]
 
 
-# channel -> the shape of a pixel, in mcrt_frame_summary order; the groups that mcrt_frame_merge takes or leaves as a whole
-FRAME_SUMMARY_CHANNELS = {"rgb": (3,), "variance": (3,), "half_a": (3,), "half_b": (3,), "tops": (ROBUST_TOPS, 3), "level": ()}
-FRAME_SUMMARY_GROUPS = (("rgb", "variance"), ("half_a", "half_b"), ("tops", "level"))
+def _summary_arrays(names, lead, out=None, allowed=FRAME_SUMMARY_CHANNELS):
+    """The arrays of the summary channels `names` ("rgb" always allowed) for frames of the leading shape `lead`, from the dict `out` where
+    it holds them, otherwise fresh zeros -> dict channel -> array."""
+    res = {}
+    for name in names:
+        assert name == "rgb" or name in allowed, name
+        shape = tuple(lead) + FRAME_SUMMARY_CHANNELS[name]
+        a = out[name] if out is not None and name in out else np.zeros(shape, dtype=np.float64)
+        assert a.dtype == np.float64 and a.shape == shape and a.flags["C_CONTIGUOUS"], name
+        res[name] = a
+    return res
+
+
+def _addresses(struct, arrays):
+    """The FrameSummary, PixelStatsBuffers or HighlightBuffers of the arrays that are channels of it."""
+    return struct(**{k: arrays[k].ctypes.data for k, _ in struct._fields_ if k in arrays})
+
+
+# the groups that mcrt_frame_merge takes or leaves as a whole
+FRAME_SUMMARY_GROUPS = tuple(tuple(FRAME_SUMMARY_CHANNELS)[i:i + 2] for i in (0, 2, 4))
 CONVERGE_TRACE = 64
 
 
@@ -898,18 +915,10 @@ class Context:
         the call only writes the rows cam's shard owns. stats: a dict that receives mcrt_stats."""
         self._sync_env()
         names = list(PIXEL_STATS_CHANNELS) if channels is None else list(channels)
-        shape = (cam.height, cam.width, 3)
-        res, bufs = {}, PixelStatsBuffers()
-        for name in ["rgb"] + names:
-            assert name == "rgb" or name in PIXEL_STATS_CHANNELS, name
-            a = out[name] if out is not None and name in out else np.zeros(shape, dtype=np.float64)
-            assert a.dtype == np.float64 and a.shape == shape and a.flags["C_CONTIGUOUS"], name
-            res[name] = a
-            if name != "rgb":
-                setattr(bufs, name, a.ctypes.data)
+        res = _summary_arrays(["rgb"] + names, (cam.height, cam.width), out, PIXEL_STATS_CHANNELS)
         st = Stats()
-        self._check(self._lib.mcrt_render_pixel_stats(self._h, C.byref(cam), int(global_seed), int(integrator), res["rgb"].ctypes.data, C.byref(bufs),
-                                                      C.byref(st)), "mcrt_render_pixel_stats")
+        self._check(self._lib.mcrt_render_pixel_stats(self._h, C.byref(cam), int(global_seed), int(integrator), res["rgb"].ctypes.data,
+                                                      C.byref(_addresses(PixelStatsBuffers, res)), C.byref(st)), "mcrt_render_pixel_stats")
         if stats is not None:
             stats.update(st.as_dict())
         return res
@@ -948,19 +957,11 @@ class Context:
         the call only writes the rows cam's shard owns. stats: a dict that receives mcrt_stats."""
         self._sync_env()
         names = list(HIGHLIGHT_CHANNELS) if channels is None else list(channels)
-        frame = (cam.height, cam.width)
-        res, hl, ps = {}, HighlightBuffers(), PixelStatsBuffers()
-        for name in ["rgb"] + names + list(stats_channels):
-            assert name == "rgb" or name in HIGHLIGHT_CHANNELS or name in PIXEL_STATS_CHANNELS, name
-            shape = frame + HIGHLIGHT_CHANNELS.get(name, (3,))
-            a = out[name] if out is not None and name in out else np.zeros(shape, dtype=np.float64)
-            assert a.dtype == np.float64 and a.shape == shape and a.flags["C_CONTIGUOUS"], name
-            res[name] = a
-            if name != "rgb":
-                setattr(hl if name in HIGHLIGHT_CHANNELS else ps, name, a.ctypes.data)
+        res = _summary_arrays(["rgb"] + names + list(stats_channels), (cam.height, cam.width), out)
         st = Stats()
-        self._check(self._lib.mcrt_render_highlights(self._h, C.byref(cam), int(global_seed), int(integrator), res["rgb"].ctypes.data, C.byref(hl),
-                                                     C.byref(ps) if stats_channels else None, C.byref(st)), "mcrt_render_highlights")
+        self._check(self._lib.mcrt_render_highlights(self._h, C.byref(cam), int(global_seed), int(integrator), res["rgb"].ctypes.data,
+                                                     C.byref(_addresses(HighlightBuffers, res)),
+                                                     C.byref(_addresses(PixelStatsBuffers, res)) if stats_channels else None, C.byref(st)), "mcrt_render_highlights")
         if stats is not None:
             stats.update(st.as_dict())
         return res
@@ -1025,7 +1026,7 @@ class Context:
 
     def frame_merge(self, a, n_a, b, n_b, stats=None, in_place=False):
         """mcrt_frame_merge: the summary of a's n_a samples followed by b's n_b. a and b are dicts channel -> array
-        (FRAME_SUMMARY_CHANNELS: "rgb", "variance", "half_a", "half_b" [.., 3], "tops" [.., 4, 3], "level" [..]); the channels both hold
+        (FRAME_SUMMARY_CHANNELS gives the names and the shape of a pixel: [.., 3], "tops" [.., 4, 3], "level" [..]); the channels both hold
         are merged (whole groups, FRAME_SUMMARY_GROUPS; "rgb" alone gives the mean only) -> dict of the same channels. in_place: the
         outputs are a's own arrays (which must then be contiguous float64). stats: a dict that receives mcrt_stats."""
         self._sync_env()
@@ -1033,15 +1034,12 @@ class Context:
         assert "rgb" in names or "half_a" in names or "tops" in names, names
         first = names[0]
         lead = np.shape(a[first])[:np.ndim(a[first]) - len(FRAME_SUMMARY_CHANNELS[first])]
-        sa, sb, so, res, keep = FrameSummary(), FrameSummary(), FrameSummary(), {}, []
+        res = _summary_arrays(names, lead, a if in_place else None)
+        xa = res if in_place else {k: np.ascontiguousarray(a[k], dtype=np.float64) for k in names}
+        xb = {k: np.ascontiguousarray(b[k], dtype=np.float64) for k in names}
         for k in names:
-            shape = tuple(lead) + FRAME_SUMMARY_CHANNELS[k]
-            xa = a[k] if in_place else np.ascontiguousarray(a[k], dtype=np.float64)
-            xb = np.ascontiguousarray(b[k], dtype=np.float64)
-            assert xa.dtype == np.float64 and xa.flags["C_CONTIGUOUS"] and xa.shape == shape and xb.shape == shape, (k, xa.shape, xb.shape)
-            res[k] = xa if in_place else np.empty(shape, dtype=np.float64)
-            keep += [xa, xb]
-            setattr(sa, k, xa.ctypes.data), setattr(sb, k, xb.ctypes.data), setattr(so, k, res[k].ctypes.data)
+            assert xa[k].shape == res[k].shape and xb[k].shape == res[k].shape, (k, xa[k].shape, xb[k].shape)
+        sa, sb, so = (_addresses(FrameSummary, d) for d in (xa, xb, res))
         st = Stats()
         self._check(self._lib.mcrt_frame_merge(self._h, int(np.prod(lead, dtype=np.int64)), C.byref(sa), int(n_a), C.byref(sb), int(n_b), C.byref(so),
                                                C.byref(st)), "mcrt_frame_merge")
@@ -1069,17 +1067,12 @@ class Context:
         "result": batches, spp, final (the frame_noise dict of the delivered frame), relative_error (a list, one per batch, the first 64).
         stats: a dict that receives mcrt_stats, summed over the batches."""
         self._sync_env()
-        frame = (cam.height, cam.width)
-        res, hl, ps = {}, HighlightBuffers(), PixelStatsBuffers()
-        for name in ["rgb"] + list(channels):
-            assert name == "rgb" or name in HIGHLIGHT_CHANNELS or name in PIXEL_STATS_CHANNELS, name
-            res[name] = np.zeros(frame + HIGHLIGHT_CHANNELS.get(name, (3,)), dtype=np.float64)
-            if name != "rgb":
-                setattr(hl if name in HIGHLIGHT_CHANNELS else ps, name, res[name].ctypes.data)
+        res = _summary_arrays(["rgb"] + list(channels), (cam.height, cam.width))
         par = ConvergeParams(float(target_relative_error), int(max_spp), int(min_batches))
         out, st = ConvergeResult(), Stats()
         self._check(self._lib.mcrt_render_converged(self._h, C.byref(cam), int(global_seed) & 0xFFFFFFFF, int(integrator), C.byref(par), res["rgb"].ctypes.data,
-                                                    C.byref(ps), C.byref(hl), C.byref(out), C.byref(st)), "mcrt_render_converged")
+                                                    C.byref(_addresses(PixelStatsBuffers, res)), C.byref(_addresses(HighlightBuffers, res)), C.byref(out), C.byref(st)),
+                    "mcrt_render_converged")
         if stats is not None:
             stats.update(st.as_dict())
         res["result"] = out.as_dict()

@@ -2,27 +2,18 @@
 // the host-pointer forms, scratch and the stopping loop. No kernel here: the merge is libmcrt_accumulate.so (csrc/mcrt_accumulate.hip;
 // DESIGN.md "Image passes" says why, and what mcrt_pass_host.hpp shares). The loop is built from the library's own calls - a batch is a
 // mcrt_render_highlights_device or mcrt_render_pixel_stats_device, the summary a mcrt_frame_noise_device - so no render kernel knows of it.
+// Everything here works on mcrt_frame_summary, by the channel table and the conversions of mcrt_summary_channels.hpp.
 // Scratch slots of the family: 0 the host form of the merge, 1 the accumulators and the batch, 2 the host form of the converged render.
 #include <cmath>
 
 #include "mcrt_accumulate.hpp"
 #include "mcrt_accumulate_launch.hpp"
 #include "mcrt_pass_host.hpp"
+#include "mcrt_summary_channels.hpp"
 
 using namespace mcrt;
 
 namespace {
-
-constexpr int kChannels = 6;
-constexpr size_t kChannelBytes[kChannels] = {24, 24, 24, 24, MCRT_ROBUST_TOPS * 24, 8};  // rgb, variance, half_a, half_b, tops, level
-
-double** channelsOf(mcrt_frame_summary& s, double** p) {
-    p[0] = s.rgb, p[1] = s.variance, p[2] = s.half_a, p[3] = s.half_b, p[4] = s.tops, p[5] = s.level;
-    return p;
-}
-mcrt_frame_summary summaryOf(void* const* p) {
-    return mcrt_frame_summary{(double*)p[0], (double*)p[1], (double*)p[2], (double*)p[3], (double*)p[4], (double*)p[5]};
-}
 
 int mergeCheck(mcrt_ctx* ctx, const char* what, uint64_t pixels, const mcrt_frame_summary* a, uint32_t n_a, const mcrt_frame_summary* b,
                uint32_t n_b, const mcrt_frame_summary* out) {
@@ -75,19 +66,15 @@ extern "C" int mcrt_frame_merge(mcrt_ctx* ctx, uint64_t pixels, const mcrt_frame
     if (int rc = mergeCheck(ctx, "mcrt_frame_merge", pixels, a, n_a, b, n_b, out)) return rc;
     PassTimer whole(ctx);
     // A's device copies are merged into in place and come back as the outputs; only the channels of wanted groups travel
-    mcrt_frame_summary sa = *a, sb = *b, so = *out;
-    double *pa[kChannels], *pb[kChannels], *po[kChannels];
-    channelsOf(sa, pa), channelsOf(sb, pb), channelsOf(so, po);
-    FrameChannel ch[2 * kChannels];
-    for (int i = 0; i < kChannels; i++) {
-        ch[i] = FrameChannel{po[i] ? pa[i] : nullptr, po[i], kChannelBytes[i]};
-        ch[kChannels + i] = FrameChannel{po[i] ? pb[i] : nullptr, nullptr, kChannelBytes[i]};
+    FrameChannel ch[2 * kSummaryChannels];
+    for (int i = 0; i < kSummaryChannels; i++) {
+        double* po = summaryChannel(*out, i);
+        ch[i] = FrameChannel{po ? summaryChannel(*a, i) : nullptr, po, kSummaryChannel[i].pixel_bytes};
+        ch[kSummaryChannels + i] = FrameChannel{po ? summaryChannel(*b, i) : nullptr, nullptr, kSummaryChannel[i].pixel_bytes};
     }
-    StagedFrames frames{{ctx, "mcrt_frame_merge", kPassAccumulate, 0, kPackedWanted, ch, 2 * kChannels}};
+    StagedFrames frames{{ctx, "mcrt_frame_merge", kPassAccumulate, 0, kPackedWanted, ch, 2 * kSummaryChannels}};
     if (int rc = frames.up((size_t)pixels)) return rc;
-    void *da[kChannels], *db[kChannels];
-    for (int i = 0; i < kChannels; i++) da[i] = ch[i].dev, db[i] = ch[kChannels + i].dev;
-    const mcrt_frame_summary d_a = summaryOf(da), d_b = summaryOf(db);
+    const mcrt_frame_summary d_a = summaryOfDevice(ch), d_b = summaryOfDevice(ch + kSummaryChannels);
     mcrt_stats st;
     if (int rc = mcrt_frame_merge_device(ctx, pixels, &d_a, n_a, &d_b, n_b, &d_a, &st)) return rc;
     if (int rc = frames.down((size_t)pixels)) return rc;
@@ -121,35 +108,32 @@ extern "C" int mcrt_render_converged_device(mcrt_ctx* ctx, const mcrt_camera_des
     if (!std::isfinite(s.target) || s.target < 0.0) return ctxFail(ctx, MCRT_ERR_INVALID, std::string(what) + ": target_relative_error must be finite and not negative");
     if (s.max_spp < batch) return ctxFail(ctx, MCRT_ERR_INVALID, std::string(what) + ": max_spp is less than one batch");
     if (cam->sqrtspp == 1 && s.min_batches < 2) s.min_batches = 2;  // a 1-sample batch has variance 0
-    const bool want_halves = d_stats_buffers && (d_stats_buffers->half_a || d_stats_buffers->half_b);
-    const bool want_tops = d_highlights && (d_highlights->tops || d_highlights->level);
+    const mcrt_frame_summary dst = summaryOf(d_out_rgb, d_stats_buffers, d_highlights);
+    const bool want_halves = dst.half_a || dst.half_b, want_tops = summaryWantsHighlights(dst);
     if (want_tops && batch < kFrameMergeTopsMin)
         return ctxFail(ctx, MCRT_ERR_UNSUPPORTED, std::string(what) + ": highlights need 16 samples per batch");
 
     PassTimer whole(ctx);
     // the accumulators [0 .. 5] and the batch [6 .. 11], whole groups, in one allocation
-    const bool want[kChannels] = {true, true, want_halves, want_halves, want_tops, want_tops};
-    size_t at[2 * kChannels], total = 0;
-    for (int i = 0; i < 2 * kChannels; i++) {
+    const bool want[kSummaryChannels] = {true, true, want_halves, want_halves, want_tops, want_tops};
+    size_t at[2 * kSummaryChannels], total = 0;
+    for (int i = 0; i < 2 * kSummaryChannels; i++) {
         at[i] = total;
-        if (want[i % kChannels]) total += (size_t)pixels * kChannelBytes[i % kChannels];
+        if (want[i % kSummaryChannels]) total += (size_t)pixels * kSummaryChannel[i % kSummaryChannels].pixel_bytes;
     }
     unsigned char* base = (unsigned char*)ctxPassScratch(ctx, kPassAccumulate, 1, total);
     if (!base) return ctxFail(ctx, MCRT_ERR_HIP, std::string(what) + ": the accumulators could not be allocated");
-    void *pacc[kChannels], *pbatch[kChannels];
-    for (int i = 0; i < kChannels; i++) {
-        pacc[i] = want[i] ? base + at[i] : nullptr;
-        pbatch[i] = want[i] ? base + at[kChannels + i] : nullptr;
-    }
-    const mcrt_frame_summary acc = summaryOf(pacc), bat = summaryOf(pbatch);
+    mcrt_frame_summary acc{}, bat{};
+    for (int i = 0; i < kSummaryChannels; i++)
+        if (want[i]) summaryChannel(acc, i) = (double*)(base + at[i]), summaryChannel(bat, i) = (double*)(base + at[kSummaryChannels + i]);
 
     mcrt_converge_result res{};
     mcrt_stats sum{};
     uint32_t spp = 0;
     for (uint32_t j = 0;; j++) {
         const mcrt_frame_summary& to = j == 0 ? acc : bat;  // (batch 0 is the accumulators' first content)
-        const mcrt_pixel_stats_buffers ds{to.variance, to.half_a, to.half_b};
-        const mcrt_highlight_buffers dh{to.tops, to.level};
+        const mcrt_pixel_stats_buffers ds = summaryStats(to);
+        const mcrt_highlight_buffers dh = summaryHighlights(to);
         mcrt_stats st;
         const int rc = want_tops ? mcrt_render_highlights_device(ctx, cam, global_seed + j, integrator, to.rgb, &dh, &ds, &st)
                                  : mcrt_render_pixel_stats_device(ctx, cam, global_seed + j, integrator, to.rgb, &ds, &st);
@@ -170,14 +154,9 @@ extern "C" int mcrt_render_converged_device(mcrt_ctx* ctx, const mcrt_camera_des
     }
 
     hipStream_t stream = (hipStream_t)ctxStream(ctx);
-    double* dst[kChannels] = {d_out_rgb,
-                              d_stats_buffers ? d_stats_buffers->variance : nullptr,
-                              d_stats_buffers ? d_stats_buffers->half_a : nullptr,
-                              d_stats_buffers ? d_stats_buffers->half_b : nullptr,
-                              d_highlights ? d_highlights->tops : nullptr,
-                              d_highlights ? d_highlights->level : nullptr};
-    for (int i = 0; i < kChannels; i++)
-        if (dst[i]) MCRT_HIP_TRY(ctx, hipMemcpyAsync(dst[i], pacc[i], (size_t)pixels * kChannelBytes[i], hipMemcpyDeviceToDevice, stream));
+    for (int i = 0; i < kSummaryChannels; i++)
+        if (summaryChannel(dst, i))
+            MCRT_HIP_TRY(ctx, hipMemcpyAsync(summaryChannel(dst, i), summaryChannel(acc, i), (size_t)pixels * kSummaryChannel[i].pixel_bytes, hipMemcpyDeviceToDevice, stream));
     MCRT_HIP_TRY(ctx, hipStreamSynchronize(stream));
     sum.total_ms = whole.hostMs();
     if (result) *result = res;
@@ -193,20 +172,17 @@ extern "C" int mcrt_render_converged(mcrt_ctx* ctx, const mcrt_camera_desc* cam,
     if (!cam) return ctxFail(ctx, MCRT_ERR_INVALID, "mcrt_render_converged: camera is NULL");
     if (!out_rgb) return ctxFail(ctx, MCRT_ERR_INVALID, "mcrt_render_converged: out_rgb is NULL");
     PassTimer whole(ctx);
-    FrameChannel ch[kChannels] = {{nullptr, out_rgb, 24},
-                                  {nullptr, stats_buffers ? stats_buffers->variance : nullptr, 24},
-                                  {nullptr, stats_buffers ? stats_buffers->half_a : nullptr, 24},
-                                  {nullptr, stats_buffers ? stats_buffers->half_b : nullptr, 24},
-                                  {nullptr, highlights ? highlights->tops : nullptr, MCRT_ROBUST_TOPS * 24},
-                                  {nullptr, highlights ? highlights->level : nullptr, 8}};
+    FrameChannel ch[kSummaryChannels];
+    summaryFrameChannels(summaryOf(out_rgb, stats_buffers, highlights), ch);
     const size_t pixels = (size_t)cam->width * cam->height;
     if (pixels == 0 || pixels > 0xFFFFFFFFull) return ctxFail(ctx, MCRT_ERR_INVALID, "mcrt_render_converged: width * height must be non-zero and below 2^32");
-    StagedFrames frames{{ctx, "mcrt_render_converged", kPassAccumulate, 2, kPackedWanted, ch, kChannels}};
+    StagedFrames frames{{ctx, "mcrt_render_converged", kPassAccumulate, 2, kPackedWanted, ch, kSummaryChannels}};
     if (int rc = frames.place(pixels)) return rc;
-    const mcrt_pixel_stats_buffers ds{(double*)ch[1].dev, (double*)ch[2].dev, (double*)ch[3].dev};
-    const mcrt_highlight_buffers dh{(double*)ch[4].dev, (double*)ch[5].dev};
+    const mcrt_frame_summary d = summaryOfDevice(ch);
+    const mcrt_pixel_stats_buffers ds = summaryStats(d);
+    const mcrt_highlight_buffers dh = summaryHighlights(d);
     mcrt_stats st;
-    if (int rc = mcrt_render_converged_device(ctx, cam, global_seed, integrator, params, (double*)ch[0].dev, &ds, &dh, result, &st)) return rc;
+    if (int rc = mcrt_render_converged_device(ctx, cam, global_seed, integrator, params, d.rgb, &ds, &dh, result, &st)) return rc;
     if (int rc = frames.down(pixels)) return rc;
     st.total_ms = whole.hostMs();
     if (stats) *stats = st;

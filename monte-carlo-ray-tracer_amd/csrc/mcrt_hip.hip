@@ -30,6 +30,7 @@
 #include "mcrt_lean.hpp"
 #include "mcrt_pixel_stats_launch.hpp"
 #include "mcrt_robust_launch.hpp"
+#include "mcrt_summary_channels.hpp"
 
 #include <hipcub/hipcub.hpp>
 
@@ -125,11 +126,9 @@ struct mcrt_ctx {
     // scratch of the image passes (mcrt_pass_host.hpp: AOV, a-trous filter, sample statistics, firefly suppression), grown on demand too:
     // every (family, slot) a buffer of its own (ctxPassScratch)
     DevBuf pass_buf[mcrt::kPassFamilies][mcrt::kPassSlots];
-    // per-pixel sample statistics wanted from the renders of this context (set for the length of a mcrt_render_pixel_stats* call, so that a
-    // frame mcrt_render_finish renders again fills them again): packed like the frame; all nullptr = none, nothing in a render changes
-    mcrt_pixel_stats_buffers stats_targets{nullptr, nullptr, nullptr};
-    // the highlights wanted from the renders of this context (set for the length of a mcrt_render_highlights* call, like stats_targets)
-    mcrt_highlight_buffers highlight_targets{nullptr, nullptr};
+    // the channels of the per-sample summary wanted from the renders of this context (ctxSampleTargetsBegin: set for the length of a call, so that
+    // a frame mcrt_render_finish renders again fills them again): packed like the frame, rgb not used; all nullptr = none, nothing in a render changes
+    mcrt_frame_summary sample_targets{};
     std::map<std::string, std::string> options;  // mcrt_set_option; seeded from the MCRT_* environment variables at mcrt_create
     DevBuf pm_iors;  // refraction histories of the 1024-lane photon-mapping kernel
     // the frame in flight, kept so that mcrt_render_finish can run it again through the wavefront pipeline (deep refraction histories)
@@ -530,38 +529,39 @@ int runWavefrontPass(mcrt_ctx* ctx, const WfFrame& fr, uint64_t slots, hipStream
     return MCRT_OK;
 }
 
-// The statistics of a pass whose samples are complete in the store (include/mcrt.h "Per-pixel sample statistics"), when the context
-// holds targets: one launch of libmcrt_pixel_stats.so's kernel, the outputs offset to the pass's first row.
-int launchPassStats(mcrt_ctx* ctx, hipStream_t stream, const double* samples, uint64_t pass_pixels, uint32_t spp, size_t first_word) {
-    const mcrt_pixel_stats_buffers& t = ctx->stats_targets;
-    if (!t.variance && !t.half_a && !t.half_b) return MCRT_OK;
-    PixelStatsPass ps;
-    ps.samples = samples;
-    ps.words = pass_pixels * 3;
-    ps.spp = spp;
-    ps.vec = pixelStatsVec(samples, ps.words);
-    ps.variance = t.variance ? t.variance + first_word : nullptr;
-    ps.half_a = t.half_a ? t.half_a + first_word : nullptr;
-    ps.half_b = t.half_b ? t.half_b + first_word : nullptr;
-    HIP_TRY(ctx, (hipError_t)launchPixelStats(stream, ps));
+// The end of a pass whose samples are complete in the store, for both pass loops: the samples added up in sample order into the frame's rows
+// from row_base on; then, for the sample targets that the context holds, their statistics (libmcrt_pixel_stats.so's kernel, include/mcrt.h
+// "Per-pixel sample statistics") and their highlights (libmcrt_robust.so's, "Firefly suppression"), a launch each, offset to the first pixel.
+int launchPassEpilogue(mcrt_ctx* ctx, hipStream_t stream, const double* samples, uint64_t pass_pixels, uint32_t spp, double* d_out, uint32_t row_base,
+                       uint32_t width) {
+    const mcrt_frame_summary& t = ctx->sample_targets;
+    const size_t first_pixel = (size_t)row_base * width, first_word = first_pixel * 3;
+    hipLaunchKernelGGL(sampleResolveKernel, dim3((uint32_t)((pass_pixels + 255) / 256)), dim3(256), 0, stream, samples, pass_pixels, spp, d_out + first_word);
+    HIP_TRY(ctx, hipGetLastError());
     ctx->launches++;
-    return MCRT_OK;
-}
-
-// The highlights of a pass likewise (include/mcrt.h "Firefly suppression"): one launch of libmcrt_robust.so's kernel when the context
-// holds targets, the outputs offset to the pass's first pixel.
-int launchPassHighlights(mcrt_ctx* ctx, hipStream_t stream, const double* samples, uint64_t pass_pixels, uint32_t spp, size_t first_pixel) {
-    const mcrt_highlight_buffers& t = ctx->highlight_targets;
-    if (!t.tops && !t.level) return MCRT_OK;
-    HighlightsPass hp;
-    hp.samples = samples;
-    hp.pixels = pass_pixels;
-    hp.spp = spp;
-    hp.reserved = 0;
-    hp.tops = t.tops ? t.tops + first_pixel * (MCRT_ROBUST_TOPS * 3) : nullptr;
-    hp.level = t.level ? t.level + first_pixel : nullptr;
-    HIP_TRY(ctx, (hipError_t)launchHighlights(stream, hp));
-    ctx->launches++;
+    if (summaryWantsStats(t)) {
+        PixelStatsPass ps;
+        ps.samples = samples;
+        ps.words = pass_pixels * 3;
+        ps.spp = spp;
+        ps.vec = pixelStatsVec(samples, ps.words);
+        ps.variance = t.variance ? t.variance + first_word : nullptr;
+        ps.half_a = t.half_a ? t.half_a + first_word : nullptr;
+        ps.half_b = t.half_b ? t.half_b + first_word : nullptr;
+        HIP_TRY(ctx, (hipError_t)launchPixelStats(stream, ps));
+        ctx->launches++;
+    }
+    if (summaryWantsHighlights(t)) {
+        HighlightsPass hp;
+        hp.samples = samples;
+        hp.pixels = pass_pixels;
+        hp.spp = spp;
+        hp.reserved = 0;
+        hp.tops = t.tops ? t.tops + first_pixel * (MCRT_ROBUST_TOPS * 3) : nullptr;
+        hp.level = t.level ? t.level + first_pixel : nullptr;
+        HIP_TRY(ctx, (hipError_t)launchHighlights(stream, hp));
+        ctx->launches++;
+    }
     return MCRT_OK;
 }
 
@@ -639,14 +639,8 @@ int launchWavefront(mcrt_ctx* ctx, const mcrt_camera_desc* cam, uint32_t global_
     for (uint32_t row = 0; row < owned_rows; row += (uint32_t)pass_rows) {
         setWfPass(fr, row, (uint32_t)std::min<uint64_t>(owned_rows, row + pass_rows));
         if (int rc = runWavefrontPass(ctx, fr, slots, stream, opt, choice)) return rc;
-        if (!splats) {  // the pass's samples, added up in sample order
-            hipLaunchKernelGGL(sampleResolveKernel, dim3((uint32_t)((fr.pass_pixels + 255) / 256)), dim3(256), 0, stream, fr.samples,
-                               (uint64_t)fr.pass_pixels, fr.spp, d_out + (size_t)fr.row_base * cam->width * 3);
-            HIP_TRY(ctx, hipGetLastError());
-            ctx->launches++;
-            if (int rc = launchPassStats(ctx, stream, fr.samples, fr.pass_pixels, fr.spp, (size_t)fr.row_base * cam->width * 3)) return rc;
-            if (int rc = launchPassHighlights(ctx, stream, fr.samples, fr.pass_pixels, fr.spp, (size_t)fr.row_base * cam->width)) return rc;
-        }
+        if (!splats)
+            if (int rc = launchPassEpilogue(ctx, stream, fr.samples, fr.pass_pixels, fr.spp, d_out, fr.row_base, cam->width)) return rc;
     }
     if (splats && !film_out) {
         const uint64_t all_pixels = (uint64_t)cam->width * cam->height;
@@ -787,11 +781,8 @@ int launchRenderImpl(mcrt_ctx* ctx, const mcrt_camera_desc* cam, uint32_t global
             hipLaunchKernelGGL(kernelAs<FlatKernelT>(kernel), dim3(grid), dim3(g.block), g.lds_bytes, stream, launch_scene, prm, pre);
         else
             hipLaunchKernelGGL(kernelAs<RenderKernelT>(kernel), dim3(grid), dim3(g.block), g.lds_bytes, stream, launch_scene, prm);
-        hipLaunchKernelGGL(sampleResolveKernel, dim3((uint32_t)((prm.pass_pixels + 255) / 256)), dim3(256), 0, stream, prm.samples,
-                           prm.pass_pixels, prm.spp, d_out + (size_t)prm.row_base * cam->width * 3);
-        ctx->launches += 2;
-        if (int rc = launchPassStats(ctx, stream, prm.samples, prm.pass_pixels, prm.spp, (size_t)prm.row_base * cam->width * 3)) return rc;
-        if (int rc = launchPassHighlights(ctx, stream, prm.samples, prm.pass_pixels, prm.spp, (size_t)prm.row_base * cam->width)) return rc;
+        ctx->launches++;
+        if (int rc = launchPassEpilogue(ctx, stream, prm.samples, prm.pass_pixels, prm.spp, d_out, prm.row_base, cam->width)) return rc;
     }
     return endFrame(ctx, stream);
 }
@@ -1783,30 +1774,18 @@ void ctxAovScene(const mcrt_ctx* ctx, AovScene* out, const uint32_t** sobol_tab)
     out->prim = d.prim;
     *sobol_tab = d.sobol_tab;
 }
-// what a render may take per-sample `noun` for: idle, a scene, a camera, and a film that keeps its samples when a channel is wanted
-static int sampleTargetsCheck(mcrt_ctx* ctx, const mcrt_camera_desc* cam, bool wanted, const char* what, const char* noun) {
+// what a render may take per-sample channels for: idle, a scene, a camera, and a film that keeps its samples when a channel is wanted
+int ctxSampleTargetsBegin(mcrt_ctx* ctx, const mcrt_camera_desc* cam, const mcrt_frame_summary* targets, const char* what) {
     if (int rc = ctxIdle(ctx, what)) return rc;
     if (int rc = ctxNeedScene(ctx, what)) return rc;
     if (!cam) return fail(ctx, MCRT_ERR_INVALID, std::string(what) + ": camera is NULL");
-    if (wanted && filmSplats(cam->film_filter, cam->film_radius))
+    const char* noun = summaryWantsHighlights(*targets) ? "highlights" : summaryWantsStats(*targets) ? "statistics" : nullptr;
+    if (noun && filmSplats(cam->film_filter, cam->film_radius))
         return fail(ctx, MCRT_ERR_UNSUPPORTED, std::string(what) + ": a frame whose film splats (a reconstruction filter, or a box of another radius) keeps no "
                                                "samples: there is nothing to take the " + noun + " of");
+    ctx->sample_targets = *targets;
+    ctx->sample_targets.rgb = nullptr;
     return MCRT_OK;
 }
-int ctxPixelStatsBegin(mcrt_ctx* ctx, const mcrt_camera_desc* cam, const mcrt_pixel_stats_buffers* targets, const char* what) {
-    const bool wanted = targets && (targets->variance || targets->half_a || targets->half_b);
-    if (int rc = sampleTargetsCheck(ctx, cam, wanted, what, "statistics")) return rc;
-    ctx->stats_targets = wanted ? *targets : mcrt_pixel_stats_buffers{nullptr, nullptr, nullptr};
-    return MCRT_OK;
-}
-int ctxHighlightsBegin(mcrt_ctx* ctx, const mcrt_camera_desc* cam, const mcrt_highlight_buffers* targets, const char* what) {
-    const bool wanted = targets && (targets->tops || targets->level);
-    if (int rc = sampleTargetsCheck(ctx, cam, wanted, what, "highlights")) return rc;
-    ctx->highlight_targets = wanted ? *targets : mcrt_highlight_buffers{nullptr, nullptr};
-    return MCRT_OK;
-}
-void ctxSampleTargetsEnd(mcrt_ctx* ctx) {
-    ctx->stats_targets = mcrt_pixel_stats_buffers{nullptr, nullptr, nullptr};
-    ctx->highlight_targets = mcrt_highlight_buffers{nullptr, nullptr};
-}
+void ctxSampleTargetsEnd(mcrt_ctx* ctx) { ctx->sample_targets = mcrt_frame_summary{}; }
 }  // namespace mcrt

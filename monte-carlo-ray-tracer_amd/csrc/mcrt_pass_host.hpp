@@ -57,7 +57,7 @@ struct PassTimer {
     }
 };
 
-// Clears the sample targets of ctxPixelStatsBegin / ctxHighlightsBegin when the call that set them returns, whichever way.
+// Clears the sample targets of ctxSampleTargetsBegin when the call that set them returns, whichever way.
 struct SampleTargetsScope {
     mcrt_ctx* ctx;
     ~SampleTargetsScope() { ctxSampleTargetsEnd(ctx); }

@@ -1,43 +1,24 @@
 // Per-pixel sample statistics and the frame summary (include/mcrt.h mcrt_render_pixel_stats*, mcrt_frame_noise*), host side: the
 // entry points, validation, the host-pointer forms and scratch. No kernel here: they are libmcrt_pixel_stats.so (csrc/mcrt_pixel_stats.hip;
 // DESIGN.md "Image passes" says why, and what mcrt_pass_host.hpp shares). A render's statistics are launched by the pass loops of
-// csrc/mcrt_hip.hip, which find their targets in the context: this file sets them for the length of a call (ctxPixelStatsBegin,
-// SampleTargetsScope), so a frame that mcrt_render_finish renders again fills them again.
+// csrc/mcrt_hip.hip, which find their targets in the context: the render's two forms (mcrt_summary_host.hpp, shared with the firefly
+// suppression) set them for the length of a call. Scratch slots: 0 .. 3 the host forms (the summary's channels in order), 4 and 5 the noise levels.
 #include <cmath>
 
-#include "mcrt_pass_host.hpp"
 #include "mcrt_pixel_stats.hpp"
 #include "mcrt_pixel_stats_launch.hpp"
+#include "mcrt_summary_host.hpp"
 
 using namespace mcrt;
 
 extern "C" int mcrt_render_pixel_stats_device(mcrt_ctx* ctx, const mcrt_camera_desc* cam, uint32_t global_seed, int integrator, double* d_out_rgb,
                                               const mcrt_pixel_stats_buffers* d_buffers, mcrt_stats* stats) {
-    if (!ctx) return MCRT_ERR_INVALID;
-    if (!d_out_rgb) return ctxFail(ctx, MCRT_ERR_INVALID, "d_out_rgb is NULL");
-    if (int rc = ctxPixelStatsBegin(ctx, cam, d_buffers, "mcrt_render_pixel_stats_device")) return rc;
-    SampleTargetsScope targets{ctx};
-    if (int rc = mcrt_render_device(ctx, cam, global_seed, integrator, d_out_rgb, nullptr)) return rc;
-    return mcrt_render_finish(ctx, stats);  // (renders again when it has to: the targets are still set)
+    return renderSummaryDevice(ctx, "mcrt_render_pixel_stats_device", cam, global_seed, integrator, summaryOf(d_out_rgb, d_buffers, nullptr), stats);
 }
 
 extern "C" int mcrt_render_pixel_stats(mcrt_ctx* ctx, const mcrt_camera_desc* cam, uint32_t global_seed, int integrator, double* out_rgb,
                                        const mcrt_pixel_stats_buffers* buffers, mcrt_stats* stats) {
-    if (!ctx) return MCRT_ERR_INVALID;
-    if (!out_rgb) return ctxFail(ctx, MCRT_ERR_INVALID, "out_rgb is NULL");
-    if (int rc = ctxIdle(ctx, "mcrt_render_pixel_stats")) return rc;
-    FrameChannel ch[4] = {{nullptr, out_rgb, 24},
-                          {nullptr, buffers ? buffers->variance : nullptr, 24},
-                          {nullptr, buffers ? buffers->half_a : nullptr, 24},
-                          {nullptr, buffers ? buffers->half_b : nullptr, 24}};
-    ShardFrames frames{{ctx, "mcrt_render_pixel_stats", kPassPixelStats, 0, kSlotEach, ch, 4}};
-    if (int rc = frames.place(cam)) return rc;
-    const mcrt_pixel_stats_buffers d{(double*)ch[1].dev, (double*)ch[2].dev, (double*)ch[3].dev};
-    mcrt_stats st;
-    if (int rc = mcrt_render_pixel_stats_device(ctx, cam, global_seed, integrator, (double*)ch[0].dev, &d, &st)) return rc;
-    if (int rc = frames.down(cam)) return rc;
-    if (stats) *stats = st;
-    return MCRT_OK;
+    return renderSummaryHost(ctx, "mcrt_render_pixel_stats", kPassPixelStats, cam, global_seed, integrator, summaryOf(out_rgb, buffers, nullptr), stats);
 }
 
 extern "C" int mcrt_frame_noise_device(mcrt_ctx* ctx, uint64_t pixels, uint32_t spp, const double* d_rgb, const double* d_variance,

@@ -1,13 +1,13 @@
 // Firefly suppression (include/mcrt.h mcrt_render_highlights*, mcrt_robust_resolve*), host side: the entry points, validation, defaults,
 // the host-pointer forms and scratch. No kernel here: they are libmcrt_robust.so (csrc/mcrt_robust.hip; DESIGN.md "Image passes" says
 // why, and what mcrt_pass_host.hpp shares). A render's highlights are launched by the pass loops of csrc/mcrt_hip.hip, which find their
-// targets in the context: this file sets them for the length of a call (ctxHighlightsBegin, SampleTargetsScope), so a frame that
-// mcrt_render_finish renders again fills them again.
+// targets in the context: the render's two forms (mcrt_summary_host.hpp, shared with the sample statistics) set them for the length of
+// a call, so a frame that mcrt_render_finish renders again fills them again.
 #include <cmath>
 
-#include "mcrt_pass_host.hpp"
 #include "mcrt_robust.hpp"
 #include "mcrt_robust_launch.hpp"
+#include "mcrt_summary_host.hpp"
 
 using namespace mcrt;
 
@@ -46,35 +46,12 @@ int validate(mcrt_ctx* ctx, uint32_t width, uint32_t height, uint32_t spp, const
 extern "C" int mcrt_render_highlights_device(mcrt_ctx* ctx, const mcrt_camera_desc* cam, uint32_t global_seed, int integrator, double* d_out_rgb,
                                              const mcrt_highlight_buffers* d_highlights, const mcrt_pixel_stats_buffers* d_stats_buffers,
                                              mcrt_stats* stats) {
-    if (!ctx) return MCRT_ERR_INVALID;
-    if (!d_out_rgb) return ctxFail(ctx, MCRT_ERR_INVALID, "d_out_rgb is NULL");
-    if (int rc = ctxHighlightsBegin(ctx, cam, d_highlights, "mcrt_render_highlights_device")) return rc;
-    SampleTargetsScope targets{ctx};
-    if (int rc = ctxPixelStatsBegin(ctx, cam, d_stats_buffers, "mcrt_render_highlights_device")) return rc;
-    if (int rc = mcrt_render_device(ctx, cam, global_seed, integrator, d_out_rgb, nullptr)) return rc;
-    return mcrt_render_finish(ctx, stats);  // (renders again when it has to: the targets are still set)
+    return renderSummaryDevice(ctx, "mcrt_render_highlights_device", cam, global_seed, integrator, summaryOf(d_out_rgb, d_stats_buffers, d_highlights), stats);
 }
 
 extern "C" int mcrt_render_highlights(mcrt_ctx* ctx, const mcrt_camera_desc* cam, uint32_t global_seed, int integrator, double* out_rgb,
                                       const mcrt_highlight_buffers* highlights, const mcrt_pixel_stats_buffers* stats_buffers, mcrt_stats* stats) {
-    if (!ctx) return MCRT_ERR_INVALID;
-    if (!out_rgb) return ctxFail(ctx, MCRT_ERR_INVALID, "out_rgb is NULL");
-    if (int rc = ctxIdle(ctx, "mcrt_render_highlights")) return rc;
-    FrameChannel ch[6] = {{nullptr, out_rgb, 24},
-                          {nullptr, highlights ? highlights->tops : nullptr, MCRT_ROBUST_TOPS * 24},
-                          {nullptr, highlights ? highlights->level : nullptr, 8},
-                          {nullptr, stats_buffers ? stats_buffers->variance : nullptr, 24},
-                          {nullptr, stats_buffers ? stats_buffers->half_a : nullptr, 24},
-                          {nullptr, stats_buffers ? stats_buffers->half_b : nullptr, 24}};
-    ShardFrames frames{{ctx, "mcrt_render_highlights", kPassRobust, 0, kSlotEach, ch, 6}};
-    if (int rc = frames.place(cam)) return rc;
-    const mcrt_highlight_buffers dh{(double*)ch[1].dev, (double*)ch[2].dev};
-    const mcrt_pixel_stats_buffers ds{(double*)ch[3].dev, (double*)ch[4].dev, (double*)ch[5].dev};
-    mcrt_stats st;
-    if (int rc = mcrt_render_highlights_device(ctx, cam, global_seed, integrator, (double*)ch[0].dev, &dh, &ds, &st)) return rc;
-    if (int rc = frames.down(cam)) return rc;
-    if (stats) *stats = st;
-    return MCRT_OK;
+    return renderSummaryHost(ctx, "mcrt_render_highlights", kPassRobust, cam, global_seed, integrator, summaryOf(out_rgb, stats_buffers, highlights), stats);
 }
 
 extern "C" int mcrt_robust_resolve_device(mcrt_ctx* ctx, uint32_t width, uint32_t height, uint32_t spp, const double* d_rgb, const double* d_tops,

@@ -7,6 +7,8 @@ those frames, a target inside the trace stops where the trace says -; refusals; 
 Bounds: bits everywhere. The kernel and the emulation run one text (csrc/mcrt_accumulate.hpp), FP64 + - * / compare select in one
 order, uncontracted on both sides; the loop is compared with the library's own calls made by hand, which run the same kernels on the
 same inputs."""
+import re
+
 import numpy as np
 import pytest
 
@@ -21,6 +23,14 @@ WIDTH, HEIGHT, SEED = ps.WIDTH, ps.HEIGHT, ps.SEED
 EVERY = tuple(acc.CHANNELS)  # rgb, variance, half_a, half_b, tops, level
 SCENE = "hexagon_room_diffuse"
 _state = {}
+
+SPLATS = (": a frame whose film splats (a reconstruction filter, or a box of another radius) keeps no samples: there is nothing to take "
+          "the %s of")
+
+
+def refused(pkg, code, text):
+    """The call fails with `code` and, as the whole message of the library, `text`."""
+    return pytest.raises(pkg.McrtError, match=r"\(%d\): %s$" % (code, re.escape(text)))
 
 
 @pytest.fixture(scope="module", autouse=True)
@@ -244,15 +254,16 @@ def test_one_sample_batches_run_twice_at_least(pkg):
 
 def test_render_converged_refusals(pkg, manifest):
     ctx = context(pkg)
-    with pytest.raises(pkg.McrtError, match=r"\(-7\).*shard"):
+    what = "mcrt_render_converged_device"
+    with refused(pkg, -7, what + ": a sharded camera - the summary needs the whole frame: merge per shard with mcrt_frame_merge_device"):
         ctx.render_converged(camera(shard=(0, 3, 5)), SEED, 0.0, 48)
-    with pytest.raises(pkg.McrtError, match=r"\(-7\).*16 samples"):
+    with refused(pkg, -7, what + ": highlights need 16 samples per batch"):
         ctx.render_converged(camera(sqrtspp=3), SEED, 0.0, 48, channels=("variance", "tops"))
     assert ctx.render_converged(camera(sqrtspp=3), SEED, 0.0, 18)["result"]["spp"] == 18  # (without highlights 9 spp batches are fine)
-    with pytest.raises(pkg.McrtError, match=r"\(-1\).*max_spp"):
+    with refused(pkg, -1, what + ": max_spp is less than one batch"):
         ctx.render_converged(camera(), SEED, 0.0, 15)
     for bad in (-1.0, float("nan"), float("inf")):
-        with pytest.raises(pkg.McrtError, match=r"\(-1\).*target"):
+        with refused(pkg, -1, what + ": target_relative_error must be finite and not negative"):
             ctx.render_converged(camera(), SEED, bad, 48)
     film = pkg.SceneImage(golden_path(manifest["cases"]["film_mitchell"]["image"]))
     fctx = pkg.Context(0)
@@ -260,13 +271,15 @@ def test_render_converged_refusals(pkg, manifest):
         fctx.upload_image(film)
         fcam = film.camera
         fcam.width, fcam.height, fcam.sqrtspp = WIDTH, HEIGHT, 4
-        with pytest.raises(pkg.McrtError, match=r"\(-7\).*keeps no\s+samples"):
+        with refused(pkg, -7, "mcrt_render_pixel_stats_device" + SPLATS % "statistics"):  # (the batch's own entry point names itself)
             fctx.render_converged(fcam, SEED, 0.0, 48)
+        with refused(pkg, -7, "mcrt_render_highlights_device" + SPLATS % "highlights"):
+            fctx.render_converged(fcam, SEED, 0.0, 48, channels=("variance", "level"))
     finally:
         fctx.close()
     fresh = pkg.Context(0)
     try:
-        with pytest.raises(pkg.McrtError, match=r"\(-4\)"):
+        with refused(pkg, -4, what + " before mcrt_upload_scene"):
             fresh.render_converged(camera(), SEED, 0.0, 48)
     finally:
         fresh.close()

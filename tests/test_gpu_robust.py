@@ -14,6 +14,7 @@ S / n itself is taken from the half-buffers, (5 half_a + 4 half_b) / 9, three ro
 The two error ratios are the issue's: summed squared error of the robust frame against a 256-spp frame of seed 12345, over the plain
 frame's: <= 0.8 on hexagon_room_diffuse (0.577 on the oracle's samples, whose bits the frame is), < 1.0 on coffee_maker_qsah (0.885)."""
 import json
+import re
 import subprocess
 
 import numpy as np
@@ -30,6 +31,14 @@ WIDTH, HEIGHT, SEED = ps.WIDTH, ps.HEIGHT, ps.SEED
 CHANNELS = ("tops", "level")
 SHAPES = {"rgb": (3,), "tops": (4, 3), "level": ()}
 _state = {}
+
+SPLATS = (": a frame whose film splats (a reconstruction filter, or a box of another radius) keeps no samples: there is nothing to take "
+          "the %s of")
+
+
+def refused(pkg, code, text):
+    """The call fails with `code` and, as the whole message of the library, `text`."""
+    return pytest.raises(pkg.McrtError, match=r"\(%d\): %s$" % (code, re.escape(text)))
 
 
 @pytest.fixture(scope="module", autouse=True)
@@ -221,6 +230,28 @@ def test_statistics_and_highlights_together_equal_each_alone(pkg):
     same_bits(both, alone, ("rgb",) + CHANNELS)
     same_bits(both, stats_alone, ("rgb",) + tuple(pkg.PIXEL_STATS_CHANNELS))
     assert (both["variance"] > 0).any()
+    # the three ways to the statistics on device buffers, 16 x 12 at 16 spp (every list of tops full): the same bits, and one launch more
+    # than the plain render for each kind of summary wanted
+    import torch
+    cam = camera(scene, sqrtspp=4, width=16, height=12)
+    launches = ctx.sample_image(cam, SEED)[1]["kernel_launches"]
+    runs = []
+    for entry, kinds in (("stats", 1), ("highlights", 1), ("highlights", 2)):
+        dev = {k: torch.full((12, 16) + shape, -9.0, dtype=torch.float64, device="cuda:0") for k, shape in pkg.FRAME_SUMMARY_CHANNELS.items()}
+        torch.cuda.synchronize()
+        sp = {k: dev[k].data_ptr() for k in pkg.PIXEL_STATS_CHANNELS}
+        hp = {k: dev[k].data_ptr() for k in CHANNELS} if kinds == 2 else None
+        if entry == "stats":
+            st = ctx.render_pixel_stats_device(cam, SEED, pkg.INTEGRATOR_PATH_TRACER, dev["rgb"].data_ptr(), sp)
+        else:
+            st = ctx.render_highlights_device(cam, SEED, pkg.INTEGRATOR_PATH_TRACER, dev["rgb"].data_ptr(), hp, sp)
+        assert st["kernel_launches"] == launches + kinds, (entry, kinds)
+        runs.append({k: v.cpu().numpy() for k, v in dev.items()})
+        for k in CHANNELS:
+            assert (runs[-1][k] != -9.0).all() if kinds == 2 else (runs[-1][k] == -9.0).all(), (entry, kinds, k)
+    for other in runs[1:]:
+        same_bits(other, runs[0], ("rgb",) + tuple(pkg.PIXEL_STATS_CHANNELS))
+    assert (runs[0]["variance"] > 0).any()
 
 
 def test_channels_left_out_are_left_alone(pkg):
@@ -260,9 +291,9 @@ def test_refusals_name_their_cause_and_leave_the_context_usable(pkg, manifest):
     # a render in flight
     ctx.render_device(cam, SEED, pkg.INTEGRATOR_PATH_TRACER, p)
     try:
-        with pytest.raises(pkg.McrtError, match=r"\(-1\).*in flight"):
+        with refused(pkg, -1, "mcrt_render_highlights: a render is in flight, call mcrt_render_finish first"):
             ctx.render_highlights(cam, SEED)
-        with pytest.raises(pkg.McrtError, match=r"\(-1\).*in flight"):
+        with refused(pkg, -1, "mcrt_render_highlights_device: a render is in flight, call mcrt_render_finish first"):
             ctx.render_highlights_device(cam, SEED, pkg.INTEGRATOR_PATH_TRACER, p, {"level": p})
         with pytest.raises(pkg.McrtError, match=r"\(-1\).*in flight"):
             ctx.robust_resolve(whole["rgb"], whole["tops"], whole["level"], 9)
@@ -271,7 +302,7 @@ def test_refusals_name_their_cause_and_leave_the_context_usable(pkg, manifest):
     finally:
         ctx.render_finish()
     still_renders(ctx)
-    with pytest.raises(pkg.McrtError, match=r"\(-1\).*NULL"):
+    with refused(pkg, -1, "d_out_rgb is NULL"):
         ctx.render_highlights_device(cam, SEED, pkg.INTEGRATOR_PATH_TRACER, None, {"level": p})
     for missing in range(4):  # the frame, its tops, its level, the output
         ptrs = [p, p, p, p]
@@ -297,9 +328,11 @@ def test_refusals_name_their_cause_and_leave_the_context_usable(pkg, manifest):
         fctx.upload_image(film)
         fcam = film.camera
         fcam.width, fcam.height, fcam.sqrtspp = WIDTH, HEIGHT, 2
-        with pytest.raises(pkg.McrtError, match=r"\(-7\).*keeps no\s+samples"):
+        with refused(pkg, -7, "mcrt_render_highlights_device" + SPLATS % "highlights"):
             fctx.render_highlights(fcam, SEED)
-        with pytest.raises(pkg.McrtError, match=r"\(-7\).*keeps no\s+samples"):
+        with refused(pkg, -7, "mcrt_render_highlights_device" + SPLATS % "highlights"):  # (the noun when both kinds are wanted)
+            fctx.render_highlights(fcam, SEED, stats_channels=("variance",))
+        with refused(pkg, -7, "mcrt_render_highlights_device" + SPLATS % "statistics"):
             fctx.render_highlights(fcam, SEED, channels=(), stats_channels=("variance",))
         box = fcam.copy()
         box.film_filter, box.film_radius, box.film_cache_size = 0, 0.0, 0
@@ -310,9 +343,9 @@ def test_refusals_name_their_cause_and_leave_the_context_usable(pkg, manifest):
     # no scene: the render is refused, the resolve needs none
     fresh = pkg.Context(0)
     try:
-        with pytest.raises(pkg.McrtError, match=r"\(-4\)"):
+        with refused(pkg, -4, "mcrt_render_highlights_device before mcrt_upload_scene"):
             fresh.render_highlights(cam, SEED)
-        with pytest.raises(pkg.McrtError, match=r"\(-4\)"):
+        with refused(pkg, -4, "mcrt_render_highlights_device before mcrt_upload_scene"):
             fresh.render_highlights_device(cam, SEED, pkg.INTEGRATOR_PATH_TRACER, p, {"level": p})
         a = fresh.robust_resolve(whole["rgb"], whole["tops"], whole["level"], 9)
         same_bits(a, ctx.robust_resolve(whole["rgb"], whole["tops"], whole["level"], 9), ("robust", "removed", "clamped"))
