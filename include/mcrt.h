@@ -428,6 +428,90 @@ int mcrt_denoise_variance(mcrt_ctx* ctx, uint32_t width, uint32_t height, uint32
                           double* out_variance /* may be NULL */, mcrt_stats* stats /* may be NULL */);
 
 /* ------------------------------------------------------------------------------------------
+ * Dual-buffer denoised output: the non-local-means filter of Rousselle, Knaus and Zwicker 2012 on the two half-buffers of a render
+ * (half_a, half_b of mcrt_render_pixel_stats*, mcrt_frame_merge* or mcrt_render_converged*: the means of the even and of the odd
+ * samples). Each half is filtered with weights computed from the OTHER half, so the weights are independent of the noise they
+ * average, and the squared difference of the two filtered halves estimates the filtered frame's error, the filter's bias
+ * included. No AOV pass is read: it works where first-hit guides say little (glass, mirrors, depth of field, the sky). The
+ * reference has no such output. Only FP64 + - * /, compare and select, in the order written here, uncontracted, no libm routine:
+ * a function of its inputs bit for bit, whatever the form, tiling or stream.
+ *
+ * Inputs are FULL frames [height][width][3]: the halves A, B and the per-pixel sample variance v of the same render of n = spp
+ * samples per pixel. max0 is mcrt_denoise's (x < 0 ? 0 : x).
+ * Constants, computed once on the host: n_a = (n + 1) / 2 and n_b = n / 2 as integers (the counts the halves are means of, for a
+ * render and for any merge of renders); ia = 1.0 / (double)n_a, ib = 1.0 / (double)n_b; fa = (double)n_a / (double)n,
+ * fb = (double)n_b / (double)n; k2 = k * k.
+ * Prefilter the variance, as mcrt_denoise_variance does but without coverage: the taps q = p + (dx, dy) are visited with
+ * dy = -1..1 as the outer and dx = -1..1 as the inner loop, kk = {1/4, 1/2, 1/4}, kw = kk[dy] * kk[dx]; taps outside the frame are
+ * skipped; s_ch += kw * v_ch(q), ks += kw (both from 0.0, in tap order); V0(p)_ch = s_ch * (1.0 / ks). The variance of half X's
+ * pixel is VX = V0 * ix: VA = V0 * ia, VB = V0 * ib.
+ * Weights from half X, applied to the other half Y, for (X, Y) = (B, A) and (A, B). For pixel p the window taps q = p + (dx, dy)
+ * are visited with dy = -R..R as the outer and dx = -R..R as the inner loop; taps outside the frame are skipped; the centre tap has
+ * w = 1.0 exactly (the weight sum is never below 1); every other tap:
+ *   S = 0.0; cnt = 0
+ *   for j = -F..F:                      (patch rows, ascending)
+ *     row = 0.0
+ *     for i = -F..F:                    (ascending)
+ *       p' = p + (i, j); q' = q + (i, j); if p' or q' is outside the frame: skip the element
+ *       cnt += 1
+ *       for ch = r, g, b:
+ *         vp = VX_ch(p'); vq = VX_ch(q'); delta = X_ch(p') - X_ch(q'); vm = vq < vp ? vq : vp
+ *         num = delta * delta - alpha * (vp + vm); den = epsilon + k2 * (vp + vq)
+ *         row = row + num / den
+ *     S = S + row                       (for every j, a row without elements adds its 0.0)
+ *   D = S / (double)(3 * cnt); x = max0(D); w = max0(1.0 - x); w = w * w
+ * then sumY_ch += w * Y_ch(q), wsumX += w (both from 0.0, in tap order), and Y_f(p)_ch = sumY_ch * (1.0 / wsumX).
+ * Outputs: rgb_ch = (fa * A_f) + (fb * B_f); with dl = A_f - B_f, variance_ch = ((dl * dl) * (fa * fb)) * (double)n;
+ * half_a = A_f, half_b = B_f. For independent halves E(A - B)^2 = sigma^2 n / (n_a n_b), so (A_f - B_f)^2 fa fb estimates the
+ * variance of the combined pixel; times n it is the sample-variance equivalent that mcrt_frame_noise(rgb, variance, n) reads with
+ * no new call, as after mcrt_denoise_variance.
+ * The row-then-column order of the patch sum is deliberate: a row sum depends only on (x, y + j, offset), so an implementation
+ * that sums the rows of a tile once and then adds 2F+1 of them per pixel (the tile form does) gives these bits. A sliding or
+ * running sum does not, and is not allowed. The weight is not symmetric in p and q (vm is the centre side's variance clamped by
+ * the tap's), so the half-window trick that reuses w(p, q) for w(q, p) would change the result and is not used.
+ * NaN, Inf and negative variances are not filtered out. A NaN in X at pixel z reaches Y_f(p) for every p within Chebyshev
+ * distance R + F of z (through a patch that holds z, as p' or as q'; a frame of one pixel has no such patch) and no other pixel; a NaN in Y at z reaches Y_f(p) for those
+ * within R; one in v spreads one pixel further, through the prefilter: R + F + 1. A negative variance enters num and den as it is.
+ * The two halves of one Owen-scrambled Sobol pixel are NOT independent samples (the even and the odd points of one stratified
+ * sequence), and one squared difference per pixel is a noisy estimate of a variance: how far the estimate is off is a measurement,
+ * not a promise. Measured (four scenes, 192 x 108, the defaults; profiles/NOTES_denoise_dual.md): the mean of g(variance) / n over
+ * the covered pixels is 0.10 - 1.4 times the filtered frame's mean squared error to a 1024-spp render at 4 and 16 spp on seven of
+ * the eight frames - below 1 on the diffuse and the specular room, where the stratified halves agree better than independent
+ * samples would and the filter's bias is shared by both halves - and 18.6 times on the eighth (coffee_maker_qsah at 16 spp, a
+ * few firefly pixels): a guide, not a bound, and not a closer one than mcrt_denoise_variance's 0.59 - 3.2.
+ * Every output may alias the corresponding input (rgb any input): a prep pass copies what the filter reads into scratch first,
+ * one packed record {A.rgb, B.rgb, V0.rgb} per pixel - 72 B per pixel, per context, kept between calls (the host-pointer form
+ * stages its frames in another 96 B per pixel). The call needs no uploaded scene, is synchronous on the context's stream, and is
+ * refused (MCRT_ERR_INVALID, the cause in mcrt_last_error) while a render is in flight, with spp < 2 (half_b of one sample is not
+ * a mean), width * height 0 or >= 2^32, a NULL input, out or out->rgb NULL, window_radius > 8, patch_radius > 3, or a k, alpha or
+ * epsilon that is negative or not finite (epsilon must end up > 0).
+ * stats: kernel_ms, total_ms, kernel_launches = 2 (prep + filter).
+ * Option MCRT_DENOISE_DUAL_FORM: "tile" (a workgroup per 16 x 16 tile, records and per-offset patch terms in LDS) / "plain" (one
+ * lane per pixel, the text above as written) / unset = the measured choice, the tile form; MCRT_DENOISE_DUAL_LANES: 256 / 512 /
+ * 1024 lanes in the tile form's workgroup / unset = the measured choice per (R, F). The same bits all of them. */
+typedef struct mcrt_denoise_dual_params {   /* NULL or a zero field = the default */
+    uint32_t window_radius;   /* R, default 5; more than 8: MCRT_ERR_INVALID */
+    uint32_t patch_radius;    /* F, default 2; more than 3: MCRT_ERR_INVALID */
+    double   k;               /* default 0.45 (Rousselle et al.'s; profiles/NOTES_denoise_dual.md); negative or not finite: INVALID */
+    double   alpha;           /* variance cancellation, default 1.0 */
+    double   epsilon;         /* default 1e-10; must end up > 0 */
+    uint32_t flags, reserved; /* none yet */
+} mcrt_denoise_dual_params;                  /* 40 bytes */
+typedef struct mcrt_denoise_dual_buffers {  /* DEVICE (or HOST) full frames [height][width][3]; NULL = not wanted */
+    double* rgb;        /* required */
+    double* variance;   /* filtered frame's error, sample-variance equivalent */
+    double* half_a;     /* the filtered halves */
+    double* half_b;
+} mcrt_denoise_dual_buffers;
+int mcrt_denoise_dual_device(mcrt_ctx* ctx, uint32_t width, uint32_t height, uint32_t spp, const double* d_half_a,
+                             const double* d_half_b, const double* d_variance, const mcrt_denoise_dual_params* params,
+                             const mcrt_denoise_dual_buffers* d_out, mcrt_stats* stats /* may be NULL */);
+/* Same with HOST pointers. */
+int mcrt_denoise_dual(mcrt_ctx* ctx, uint32_t width, uint32_t height, uint32_t spp, const double* half_a, const double* half_b,
+                      const double* variance, const mcrt_denoise_dual_params* params, const mcrt_denoise_dual_buffers* out,
+                      mcrt_stats* stats /* may be NULL */);
+
+/* ------------------------------------------------------------------------------------------
  * Per-pixel sample statistics: the spread of a pixel's samples next to their mean - the sample variance and the two half-buffers
  * (the means of the even and of the odd samples) that error estimators, stopping rules and denoisers start from. The reference
  * has no such output. Every box-filter frame keeps the radiance of every sample until its pass is resolved; the statistics are

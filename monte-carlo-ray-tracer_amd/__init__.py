@@ -183,6 +183,18 @@ class DenoiseVarianceParams(C.Structure):
                 ("sigma_plane", C.c_double), ("albedo_floor", C.c_double), ("flags", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+class DenoiseDualParams(C.Structure):
+    """mcrt_denoise_dual_params: a zero field = the default (include/mcrt.h)."""
+    _fields_ = [("window_radius", C.c_uint32), ("patch_radius", C.c_uint32), ("k", C.c_double), ("alpha", C.c_double), ("epsilon", C.c_double),
+                ("flags", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class DenoiseDualBuffers(C.Structure):
+    """mcrt_denoise_dual_buffers: a null pointer = not wanted (rgb is required)."""
+    _fields_ = [("rgb", C.c_void_p), ("variance", C.c_void_p), ("half_a", C.c_void_p), ("half_b", C.c_void_p)]
+
+
+DENOISE_DUAL_OUTPUTS = tuple(k for k, _ in DenoiseDualBuffers._fields_)
 ROBUST_TOPS = 4
 # The per-sample summary of a render: channel -> the shape of a pixel, in mcrt_frame_summary order (csrc/mcrt_summary_channels.hpp is the
 # same table for the library); mcrt_pixel_stats_buffers is its members 1..3, mcrt_highlight_buffers its members 4..5.
@@ -356,6 +368,10 @@ def lib():
         L.mcrt_denoise_variance.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, C.POINTER(AovBuffers), C.POINTER(DenoiseVarianceParams), vp, vp,
                                             C.POINTER(Stats)]
         L.mcrt_denoise_variance_device.argtypes = L.mcrt_denoise_variance.argtypes
+    if hasattr(L, "mcrt_denoise_dual"):  # (likewise)
+        L.mcrt_denoise_dual.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, C.POINTER(DenoiseDualParams), C.POINTER(DenoiseDualBuffers),
+                                        C.POINTER(Stats)]
+        L.mcrt_denoise_dual_device.argtypes = L.mcrt_denoise_dual.argtypes
     if hasattr(L, "mcrt_render_pixel_stats"):  # (likewise)
         L.mcrt_render_pixel_stats.argtypes = [vp, C.POINTER(CameraDesc), C.c_uint32, C.c_int, vp, C.POINTER(PixelStatsBuffers), C.POINTER(Stats)]
         L.mcrt_render_pixel_stats_device.argtypes = [vp, C.POINTER(CameraDesc), C.c_uint32, C.c_int, vp, C.POINTER(PixelStatsBuffers), C.POINTER(Stats)]
@@ -907,6 +923,59 @@ class Context:
         aov = self.render_aov(cam, global_seed, channels=DENOISE_GUIDES)
         rgb, variance = self.denoise_variance(raw["rgb"], raw["variance"], aov, spp, **params)
         return {"rgb": rgb, "variance": variance, "raw": raw["rgb"], "noise": self.frame_noise(rgb, variance, spp),
+                "raw_noise": self.frame_noise(raw["rgb"], raw["variance"], spp)}
+
+    def denoise_dual(self, half_a, half_b=None, variance=None, spp=None, want=("rgb", "variance"), stats=None, **params):
+        """mcrt_denoise_dual: the dual-buffer non-local-means filter on the half-buffers half_a, half_b [H,W,3] of a render of spp samples
+        per pixel and its per-pixel sample variance [H,W,3] (render_pixel_stats' channels) -> dict of the outputs in `want`
+        (DENOISE_DUAL_OUTPUTS: "rgb" the filtered frame, always there; "variance" its error in the form frame_noise reads; "half_a",
+        "half_b" the filtered halves). half_a may be the dict a render_converged or render_pixel_stats returned instead: its "half_a",
+        "half_b" and "variance" are read, and spp from its "result" unless given. params: the fields of mcrt_denoise_dual_params
+        (window_radius, patch_radius, k, alpha, epsilon); left out = the default. stats: a dict that receives mcrt_stats."""
+        self._sync_env()
+        if isinstance(half_a, dict):
+            summary = half_a
+            half_a, half_b, variance = summary["half_a"], summary["half_b"], summary["variance"]
+            if spp is None:
+                spp = summary["result"]["spp"]
+        half_a, half_b, variance = (np.ascontiguousarray(a, dtype=np.float64) for a in (half_a, half_b, variance))
+        assert half_a.ndim == 3 and half_a.shape[2] == 3 and half_b.shape == half_a.shape and variance.shape == half_a.shape, (half_a.shape, half_b.shape, variance.shape)
+        height, width = half_a.shape[:2]
+        names = ["rgb"] + [k for k in want if k != "rgb"]
+        assert all(k in DENOISE_DUAL_OUTPUTS for k in names), names
+        res = {k: np.empty_like(half_a) for k in names}
+        bufs = DenoiseDualBuffers(**{k: a.ctypes.data for k, a in res.items()})
+        par = DenoiseDualParams(**params)
+        st = Stats()
+        self._check(self._lib.mcrt_denoise_dual(self._h, width, height, int(spp), half_a.ctypes.data, half_b.ctypes.data, variance.ctypes.data, C.byref(par),
+                                                C.byref(bufs), C.byref(st)), "mcrt_denoise_dual")
+        if stats is not None:
+            stats.update(st.as_dict())
+        return res
+
+    def denoise_dual_device(self, width, height, spp, half_a_ptr, half_b_ptr, variance_ptr, pointers, **params):
+        """mcrt_denoise_dual_device: the three input frames and pointers = dict output (DENOISE_DUAL_OUTPUTS) -> raw device pointer, all full
+        frames; an output may be the corresponding input, "rgb" any of them; outputs left out or None are not written. Synchronous; returns
+        the stats dict."""
+        self._sync_env()
+        bufs = _pointer_struct(DenoiseDualBuffers, pointers, DENOISE_DUAL_OUTPUTS)
+        par = DenoiseDualParams(**params)
+        st = Stats()
+        p = lambda x: C.c_void_p(int(x)) if x else None
+        self._check(self._lib.mcrt_denoise_dual_device(self._h, int(width), int(height), int(spp), p(half_a_ptr), p(half_b_ptr), p(variance_ptr), C.byref(par),
+                                                       C.byref(bufs) if pointers is not None else None, C.byref(st)), "mcrt_denoise_dual_device")
+        return st.as_dict()
+
+    def render_denoised_dual(self, cam, global_seed, integrator=INTEGRATOR_PATH_TRACER, **params):
+        """A frame with its half-buffers and the dual-buffer filter in one call: render_pixel_stats (variance, half_a, half_b), denoise_dual
+        and frame_noise of both frames -> dict "rgb" (the filtered frame), "variance" (its error estimate), "raw" (the unfiltered frame),
+        "noise" and "raw_noise" (frame_noise of the filtered and of the unfiltered frame). No AOV pass is rendered. cam is one whole frame
+        (no shard: the filter reads neighbouring rows)."""
+        assert cam.shard_count <= 1, "render_denoised_dual filters a whole frame: gather the shards first"
+        spp = cam.sqrtspp * cam.sqrtspp
+        raw = self.render_pixel_stats(cam, global_seed, integrator)
+        out = self.denoise_dual(raw["half_a"], raw["half_b"], raw["variance"], spp, **params)
+        return {"rgb": out["rgb"], "variance": out["variance"], "raw": raw["rgb"], "noise": self.frame_noise(out["rgb"], out["variance"], spp),
                 "raw_noise": self.frame_noise(raw["rgb"], raw["variance"], spp)}
 
     def render_pixel_stats(self, cam, global_seed, integrator=INTEGRATOR_PATH_TRACER, channels=None, stats=None, out=None):

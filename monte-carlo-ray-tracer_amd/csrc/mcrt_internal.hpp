@@ -26,7 +26,7 @@ int launchPowKat(void* stream, uint64_t n, const double* a, const double* b, dou
 // kernel fed from the arrays, otherwise the intersect kernel). d_uv must not be null. Synchronous on the context's stream.
 int intersectDeviceArrays(mcrt_ctx* ctx, uint64_t n, const double* d_start, const double* d_dir, double* d_t, uint32_t* d_surf, double* d_uv);
 // The hooks of the image passes' host toolkit (mcrt_pass_host.hpp; DESIGN.md "Image passes"), which mcrt_aov_host.hip, mcrt_denoise_host.hip,
-// mcrt_pixel_stats_host.hip and mcrt_robust_host.hip reach the context through (mcrt_denoise_var_host.hip and mcrt_accumulate_host.hip too).
+// mcrt_pixel_stats_host.hip and mcrt_robust_host.hip reach the context through (mcrt_denoise_var_host.hip, mcrt_accumulate_host.hip and mcrt_denoise_dual_host.hip too).
 // ctxIdle: no render in flight (MCRT_ERR_INVALID recorded under `what`), device selected. ctxNeedScene: MCRT_ERR_NO_SCENE under `what`.
 // ctxPassScratch: buffer `which` (0..kPassSlots-1) of a family's scratch - every (family, slot) a buffer of its own, kept in the context
 // and grown on demand like the operators'; at least 8 bytes; nullptr, the HIP error cleared, when the allocation fails.
@@ -35,7 +35,7 @@ int intersectDeviceArrays(mcrt_ctx* ctx, uint64_t n, const double* d_start, cons
 // a channel is wanted - then the channels of `targets` other than rgb (mcrt_summary_channels.hpp; nullptr: not wanted) are what the pass
 // loops of the next renders of this context fill (their epilogue's launches), until ctxSampleTargetsEnd clears them (SampleTargetsScope does).
 struct AovScene;
-enum PassFamily { kPassAov, kPassDenoise, kPassPixelStats, kPassRobust, kPassDenoiseVar, kPassAccumulate, kPassFamilies };
+enum PassFamily { kPassAov, kPassDenoise, kPassPixelStats, kPassRobust, kPassDenoiseVar, kPassAccumulate, kPassDenoiseDual, kPassFamilies };
 constexpr int kPassSlots = 6;
 int ctxIdle(mcrt_ctx* ctx, const char* what);
 int ctxNeedScene(mcrt_ctx* ctx, const char* what);

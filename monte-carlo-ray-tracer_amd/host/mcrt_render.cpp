@@ -4,7 +4,8 @@
 //
 //   mcrt_render scene.mcrt out.f64 [--width W --height H --sqrtspp S] [--seed N] [--photon] [--device D | --devices D0,D1,...]
 //               [--tga out.tga [--tonemapper hable|aces] [--exposure EV] [--gain EV] [--plain]] [--aov PREFIX]
-//               [--denoise OUT.f64 [--denoise-iterations N]] [--denoise-variance OUT.f64 [--denoise-variance-out VAR.f64]] [--stats PREFIX] [--robust PREFIX [--robust-kappa X] [--robust-radius R]]
+//               [--denoise OUT.f64 [--denoise-iterations N]] [--denoise-variance OUT.f64 [--denoise-variance-out VAR.f64]]
+//               [--denoise-dual OUT.f64 [--denoise-dual-out VAR.f64]] [--stats PREFIX] [--robust PREFIX [--robust-kappa X] [--robust-radius R]]
 //               [--converge TARGET [--max-spp N]]
 //
 // Writes the frame as raw FP64 RGB, row-major (what Image::operator() holds, camera/image.cpp:53-56),
@@ -19,14 +20,18 @@
 // mcrt_denoise_variance (the a-trous filter steered by the per-pixel sample variance; default parameters, --denoise-iterations N as above)
 // as raw FP64 RGB - with --tga developed too, to OUT's stem + ".tga" -, and with --denoise-variance-out (refused without
 // --denoise-variance) the filtered frame's variance, in the form mcrt_frame_noise reads; prints that summary for the unfiltered and the filtered frame (one device).
+// --denoise-dual renders the frame through mcrt_render_pixel_stats (the same frame) and also writes the frame filtered by mcrt_denoise_dual
+// (the dual-buffer non-local-means filter on the render's half-buffers; default parameters, no AOV pass) as raw FP64 RGB - with --tga
+// developed too, to OUT's stem + ".tga" -, and with --denoise-dual-out (refused without --denoise-dual) the filtered frame's error
+// estimate, in the form mcrt_frame_noise reads; prints that summary for the unfiltered and the filtered frame (one device).
 // --stats renders the frame through mcrt_render_pixel_stats (the same frame) and also writes the per-pixel sample statistics,
 // PREFIX.variance.f64, .half_a.f64 and .half_b.f64 (raw FP64 RGB, row-major), and prints the frame summary of mcrt_frame_noise (one device).
 // --robust renders the frame through mcrt_render_highlights (the same frame; with --stats the statistics come from the same render) and
 // also writes the robust frame of mcrt_robust_resolve, PREFIX.robust.f64 and PREFIX.removed.f64 (raw FP64 RGB) and PREFIX.clamped.u32,
 // and prints how many pixels and samples were clamped and the luminance removed next to the frame's (one device).
 // --converge renders the frame through mcrt_render_converged: batches of sqrtspp^2 samples at the seeds N, N + 1, ... merged until the
-// frame's relative error (mcrt_frame_noise) is at most TARGET or one more batch would exceed --max-spp (default 1024); --stats, --robust
-// and --denoise-variance then read the accumulated buffers at the accumulated sample count. Prints batches, spp and the final relative
+// frame's relative error (mcrt_frame_noise) is at most TARGET or one more batch would exceed --max-spp (default 1024); --stats, --robust,
+// --denoise-variance and --denoise-dual then read the accumulated buffers at the accumulated sample count. Prints batches, spp and the final relative
 // error (one device).
 // --devices renders the frame on several GPUs from this one process (mcrt_render_multi: one host thread per GPU).
 #include <cstdio>
@@ -56,7 +61,7 @@ int main(int argc, char** argv) {
     image.plain = (uint32_t)mcrt_image_param(img, "image_plain");
     image.exposure_compensation = from_bits(mcrt_image_param(img, "image_exposure_ev_bits"));
     image.gain_compensation = from_bits(mcrt_image_param(img, "image_gain_ev_bits"));
-    std::string tga, aov, denoise, dvar, dvar_out, pstats, robust;
+    std::string tga, aov, denoise, dvar, dvar_out, ddual, ddual_out, pstats, robust;
     mcrt_robust_params rparams{};
     mcrt_denoise_params dparams{};
     mcrt_converge_params cparams{};
@@ -82,6 +87,8 @@ int main(int argc, char** argv) {
         else if (k == "--denoise" && i + 1 < argc) denoise = argv[++i];
         else if (k == "--denoise-variance" && i + 1 < argc) dvar = argv[++i];
         else if (k == "--denoise-variance-out" && i + 1 < argc) dvar_out = argv[++i];
+        else if (k == "--denoise-dual" && i + 1 < argc) ddual = argv[++i];
+        else if (k == "--denoise-dual-out" && i + 1 < argc) ddual_out = argv[++i];
         else if (k == "--stats" && i + 1 < argc) pstats = argv[++i];
         else if (k == "--robust" && i + 1 < argc) robust = argv[++i];
         else if (k == "--robust-kappa" && i + 1 < argc) rparams.kappa = std::strtod(argv[++i], nullptr);
@@ -96,6 +103,10 @@ int main(int argc, char** argv) {
     }
     if (!dvar_out.empty() && dvar.empty()) {
         std::fprintf(stderr, "--denoise-variance-out needs --denoise-variance\n");
+        return 2;
+    }
+    if (!ddual_out.empty() && ddual.empty()) {
+        std::fprintf(stderr, "--denoise-dual-out needs --denoise-dual\n");
         return 2;
     }
     cam.shard_index = 0;
@@ -121,18 +132,18 @@ int main(int argc, char** argv) {
     std::vector<double> variance, half_a, half_b;
     std::vector<double> tops, level;
     uint32_t spp = cam.sqrtspp * cam.sqrtspp;  // of the delivered frame: --converge accumulates batches of that many
-    if (rc == MCRT_OK && (converge || !pstats.empty() || !robust.empty() || !dvar.empty())) {
+    if (rc == MCRT_OK && (converge || !pstats.empty() || !robust.empty() || !dvar.empty() || !ddual.empty())) {
         if (ctxs.size() > 1) {
-            std::fprintf(stderr, "--stats, --robust, --denoise-variance and --converge take one device\n");
+            std::fprintf(stderr, "--stats, --robust, --denoise-variance, --denoise-dual and --converge take one device\n");
             return 2;
         }
         if (!dvar.empty()) variance.resize(rgb.size());
-        if (!pstats.empty()) {
+        const bool ps = !pstats.empty() || !ddual.empty();  // the three statistics
+        if (ps) {
             variance.resize(rgb.size());
             half_a.resize(rgb.size());
             half_b.resize(rgb.size());
         }
-        const bool ps = !pstats.empty();
         const mcrt_pixel_stats_buffers b{ps || !dvar.empty() ? variance.data() : nullptr, ps ? half_a.data() : nullptr, ps ? half_b.data() : nullptr};
         if (!robust.empty()) {
             tops.resize(rgb.size() * MCRT_ROBUST_TOPS);
@@ -241,6 +252,42 @@ int main(int argc, char** argv) {
         return true;
     };
     if (!tga.empty() && !develop(rgb, tga)) return 1;
+    if (!ddual.empty()) {
+        const size_t px = (size_t)cam.width * cam.height;
+        std::vector<double> filtered(px * 3), filtered_var(px * 3);
+        const mcrt_denoise_dual_buffers out{filtered.data(), filtered_var.data(), nullptr, nullptr};
+        mcrt_stats dst;
+        mcrt_frame_noise_result raw, fn;
+        rc = mcrt_denoise_dual(ctx, cam.width, cam.height, spp, half_a.data(), half_b.data(), variance.data(), nullptr, &out, &dst);
+        if (rc == MCRT_OK) rc = mcrt_frame_noise(ctx, px, spp, rgb.data(), variance.data(), &raw);
+        if (rc == MCRT_OK) rc = mcrt_frame_noise(ctx, px, spp, filtered.data(), filtered_var.data(), &fn);
+        if (rc != MCRT_OK) {
+            std::fprintf(stderr, "mcrt error %d: %s\n", rc, mcrt_last_error(ctx));
+            return 1;
+        }
+        const struct {
+            const std::string* path;
+            const std::vector<double>* data;
+        } files[2] = {{&ddual, &filtered}, {&ddual_out, &filtered_var}};
+        for (const auto& c : files) {
+            if (c.path->empty()) continue;
+            FILE* o = std::fopen(c.path->c_str(), "wb");
+            const bool ok = o && std::fwrite(c.data->data(), sizeof(double), c.data->size(), o) == c.data->size();
+            if (o) std::fclose(o);
+            if (!ok) {
+                std::fprintf(stderr, "cannot write %s\n", c.path->c_str());
+                return 1;
+            }
+        }
+        std::printf("{\"denoise_dual\":\"%s\",\"kernel_launches\":%u,\"kernel_ms\":%.3f,\"total_ms\":%.3f,\"relative_error_raw\":%.17g,"
+                    "\"relative_error\":%.17g}\n",
+                    ddual.c_str(), dst.kernel_launches, dst.kernel_ms, dst.total_ms, raw.relative_error, fn.relative_error);
+        if (!tga.empty()) {
+            const size_t dot = ddual.find_last_of('.'), slash = ddual.find_last_of('/');
+            const bool has_ext = dot != std::string::npos && (slash == std::string::npos || dot > slash);
+            if (!develop(filtered, (has_ext ? ddual.substr(0, dot) : ddual) + ".tga")) return 1;
+        }
+    }
     if (!aov.empty() || !denoise.empty() || !dvar.empty()) {
         const size_t px = (size_t)cam.width * cam.height;
         std::vector<double> depth(px), position(px * 3), normal(px * 3), shading_normal(px * 3), albedo(px * 3), coverage(px);

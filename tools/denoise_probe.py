@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""The a-trous filters (mcrt_denoise_device and the variance-guided mcrt_denoise_variance_device) measured on the same frames in one
+"""The denoise filters (mcrt_denoise_device, the variance-guided mcrt_denoise_variance_device and the dual-buffer mcrt_denoise_dual_device) measured on the same frames in one
 session: their time next to the beauty frame and the AOV pass of the same camera, and what they do to the error of a low-sample frame.
 
   python tools/denoise_probe.py [--width 1920 --height 1080 --sqrtspp 4] [--runs 5] [--scenes hexagon_room]
@@ -13,7 +13,20 @@ session: their time next to the beauty frame and the AOV pass of the same camera
       filtered frame (default parameters) against a render at --truth-sqrtspp with another seed. The guided filter (default parameters) runs on the same frame with the variance of
       render_pixel_stats: "mse_variance_guided", and "calibration" = the mean over those pixels of g(out_variance) / spp over the mean of
       the filtered frame's squared error (channels added). --grid adds a small grid of parameters for each filter ("grid", "variance_grid":
-      [sigma_variance, sigma_floor, ratio]). One JSON line per (scene, sqrtspp)."""
+      [sigma_variance, sigma_floor, ratio]). One JSON line per (scene, sqrtspp).
+
+  python tools/denoise_probe.py --dual [--width 1920 --height 1080 --sqrtspp 4] [--runs 5] [--scenes hexagon_room] [--radii 5,2:8,3]
+      The dual-buffer filter (mcrt_denoise_dual_device) on the half-buffers of one render: HIP-event milliseconds (one warm-up, then the
+      median of --runs runs) of the tile form, the plain form (--plain-runs of it, default 1: it is slow on purpose) and the default choice
+      per (window_radius, patch_radius) of --radii ("0,0" = the defaults), and the variance-guided filter's at its defaults on the same
+      frame in the same session as the yardstick. One JSON line per scene.
+
+  python tools/denoise_probe.py --dual --errors [--width 192 --height 108] [--truth-sqrtspp 32] [--scenes a,b,...] [--grid]
+      Per scene and sqrtspp 2, 4: the mean squared error (all channels, pixels with coverage > 0) of the unfiltered frame and of the frames
+      filtered by mcrt_denoise_dual, mcrt_denoise_variance and mcrt_denoise (default parameters) against a render at --truth-sqrtspp with
+      another seed, and "calibration" / "calibration_variance_guided" = the mean of g(variance) / spp over the mean of the filtered
+      frame's squared error (channels added) for the two filters that estimate their error. --grid adds "dual_grid":
+      [window_radius, patch_radius, k, ratio, calibration]. One JSON line per (scene, sqrtspp)."""
 import argparse
 import importlib
 import itertools
@@ -111,9 +124,82 @@ def errors(m, args):
         img.close()
 
 
+DUAL_GRID = dict(radii=((3, 1), (5, 2), (8, 3)), k=(0.3, 0.45, 0.6, 0.8, 1.0))
+
+
+def dual_timing(m, args):
+    import torch
+    radii = [tuple(int(x) for x in r.split(",")) for r in args.radii.split(":")]
+    for name in args.scenes.split(","):
+        img, cam, ctx = setup(m, name, args.width, args.height, args.sqrtspp)
+        spp = cam.sqrtspp ** 2
+        frame = lambda: torch.empty((cam.height, cam.width, 3), dtype=torch.float64, device="cuda:0")
+        rgb, var, half_a, half_b, out, out_var = (frame() for _ in range(6))
+        bufs = {k: torch.empty((cam.height, cam.width) + ((3,) if m.AOV_CHANNELS[k][1] == 3 else ()), dtype=torch.float64, device="cuda:0") for k in GUIDES}
+        torch.cuda.synchronize()
+        ptrs = {k: v.data_ptr() for k, v in bufs.items()}
+        ctx.render_pixel_stats_device(cam, args.seed, m.INTEGRATOR_PATH_TRACER, rgb.data_ptr(), {"variance": var.data_ptr(), "half_a": half_a.data_ptr(), "half_b": half_b.data_ptr()})
+        ctx.render_aov_device(cam, args.seed, ptrs)
+        rec = {"scene": name, "width": cam.width, "height": cam.height, "spp": spp, "pixels": cam.width * cam.height}
+        dual = lambda R, F: ctx.denoise_dual_device(cam.width, cam.height, spp, half_a.data_ptr(), half_b.data_ptr(), var.data_ptr(),
+                                                    {"rgb": out.data_ptr(), "variance": out_var.data_ptr()}, window_radius=R, patch_radius=F)["kernel_ms"]
+        for R, F in radii:
+            for lanes in (256, 512, 1024):  # the tile form's workgroup
+                ctx.set_option("MCRT_DENOISE_DUAL_FORM", "tile")
+                ctx.set_option("MCRT_DENOISE_DUAL_LANES", str(lanes))
+                dual(R, F)
+                rec["dual_%d_%d_tile_%d" % (R, F, lanes)] = round(statistics.median([dual(R, F) for _ in range(max(args.runs, 1))]), 4)
+            ctx.set_option("MCRT_DENOISE_DUAL_LANES", None)
+            for form in ("tile", "plain", None):
+                ctx.set_option("MCRT_DENOISE_DUAL_FORM", form)
+                if form != "plain":
+                    dual(R, F)  # warm-up
+                runs = [dual(R, F) for _ in range(max(args.plain_runs if form == "plain" else args.runs, 1))]
+                rec["dual_%d_%d_%s" % (R, F, form or "default")] = round(statistics.median(runs), 4)
+        ctx.set_option("MCRT_DENOISE_DUAL_FORM", None)
+        guided = lambda: ctx.denoise_variance_device(cam.width, cam.height, spp, rgb.data_ptr(), var.data_ptr(), ptrs, out.data_ptr(), out_var.data_ptr())["kernel_ms"]
+        guided()
+        rec["variance_guided_default"] = round(statistics.median([guided() for _ in range(max(args.runs, 1))]), 4)
+        print(json.dumps(rec), flush=True)
+        ctx.close()
+        img.close()
+
+
+def dual_errors(m, args):
+    import numpy as np
+    for name in args.scenes.split(","):
+        img, cam, ctx = setup(m, name, args.width, args.height, args.truth_sqrtspp)
+        truth, _ = ctx.sample_image(cam, args.seed ^ 0x00ABCDEF, m.INTEGRATOR_PATH_TRACER)
+        for sqrtspp in (2, 4):
+            cam.sqrtspp = sqrtspp
+            raw, spp = ctx.render_pixel_stats(cam, args.seed, m.INTEGRATOR_PATH_TRACER), sqrtspp ** 2
+            guides = ctx.render_aov(cam, args.seed, channels=GUIDES)
+            covered = guides["coverage"] > 0
+            mse = lambda frame: float(((frame - truth)[covered] ** 2).mean())
+            calibration = lambda frame, variance: float((variance[covered].sum(axis=-1) / spp).mean()) / float((((frame - truth)[covered]) ** 2).sum(axis=-1).mean())
+            before = mse(raw["rgb"])
+            dual = ctx.denoise_dual(raw["half_a"], raw["half_b"], raw["variance"], spp)
+            guided, guided_var = ctx.denoise_variance(raw["rgb"], raw["variance"], guides, spp)
+            rec = {"scene": name, "width": cam.width, "height": cam.height, "spp": spp, "truth_spp": args.truth_sqrtspp ** 2, "mse_unfiltered": before,
+                   "ratio_dual": round(mse(dual["rgb"]) / before, 4), "ratio_variance_guided": round(mse(guided) / before, 4),
+                   "ratio_denoise": round(mse(ctx.denoise(raw["rgb"], guides)) / before, 4),
+                   "calibration": round(calibration(dual["rgb"], dual["variance"]), 4), "calibration_variance_guided": round(calibration(guided, guided_var), 4)}
+            if args.grid:
+                rec["dual_grid"] = []
+                for (R, F), k in itertools.product(DUAL_GRID["radii"], DUAL_GRID["k"]):
+                    d = ctx.denoise_dual(raw["half_a"], raw["half_b"], raw["variance"], spp, window_radius=R, patch_radius=F, k=k)
+                    rec["dual_grid"].append([R, F, k, round(mse(d["rgb"]) / before, 4), round(calibration(d["rgb"], d["variance"]), 4)])
+            print(json.dumps(rec), flush=True)
+        ctx.close()
+        img.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--errors", action="store_true")
+    ap.add_argument("--dual", action="store_true")
+    ap.add_argument("--radii", default="0,0:8,3")
+    ap.add_argument("--plain-runs", type=int, default=1)
     ap.add_argument("--grid", action="store_true")
     ap.add_argument("--width", type=int)
     ap.add_argument("--height", type=int)
@@ -128,7 +214,10 @@ def main():
     args.height = args.height or (108 if args.errors else 1080)
     args.scenes = args.scenes or ("hexagon_room_diffuse,hexagon_room,hexagon_room_ggx,coffee_maker_qsah" if args.errors else "hexagon_room")
     m = importlib.import_module("monte-carlo-ray-tracer_amd")
-    (errors if args.errors else timing)(m, args)
+    if args.dual:
+        (dual_errors if args.errors else dual_timing)(m, args)
+    else:
+        (errors if args.errors else timing)(m, args)
 
 
 if __name__ == "__main__":
