@@ -207,7 +207,8 @@ const char* mcrt_last_error(const mcrt_ctx* ctx); /* ctx may be NULL: last creat
  * environment SEEDS the options once, in mcrt_create (so `MCRT_KERNEL=wf ./host` still works); after that the library never
  * reads the environment: a host changes behaviour with mcrt_set_option, between frames (value NULL = back to the default).
  * Options that shape the uploaded scene (MCRT_FLAT_MAX) take effect at the next mcrt_upload_scene.
- * The reference has no counterpart (its knobs are compile-time constants); mcrt_get_option returns the value or NULL. */
+ * The reference has no counterpart (its knobs are compile-time constants); mcrt_get_option returns the value or NULL.
+ * Read-only: MCRT_LEAN_USED, and MCRT_INSTANCES_USED = the kernel instances of the last launch as "frame,trace,knn" ("-": none). */
 int mcrt_set_option(mcrt_ctx* ctx, const char* key, const char* value);
 const char* mcrt_get_option(const mcrt_ctx* ctx, const char* key);
 

@@ -140,6 +140,10 @@ struct mcrt_ctx {
     hipStream_t last_stream = nullptr;
     bool force_wf = false;
     bool lean_used = false;  // the last launch (frame, photon pass) ran a lean instance: mcrt_get_option("MCRT_LEAN_USED")
+    // ... and which instances (mcrt_select.hpp: RenderInstance) it ran - the frame's (pipeline: its shade kernel; photon pass: the emission
+    // kernel), the pipeline's trace and kNN kernels: mcrt_get_option("MCRT_INSTANCES_USED"), and what mcrt_render_finish reads out
+    int used_instance = mcrt::kInstNone, used_trace = mcrt::kInstNone, used_knn = mcrt::kInstNone;
+    std::string used_text = "-,-,-";
     uint32_t iors_depth = kMaxIorsDeep;  // RefractionHistory entries per pipeline slot (8 in LDS + deep rows); grows when a frame nests deeper
     DevBuf wf_iors_deep;
     DevPool pass_pool;  // work buffers of the device photon pass (mcrt_photon_device.hpp)
@@ -431,6 +435,16 @@ int planTrace(mcrt_ctx* ctx, K kernel, uint64_t max_items, int leaf_lanes, Trace
     return MCRT_OK;
 }
 
+// What the launch that follows runs, for MCRT_LEAN_USED / MCRT_INSTANCES_USED and the readouts of mcrt_render_finish: "frame,trace,knn" by
+// RenderInstance name, "/lean" behind a lean twin, "-" where there is none.
+void noteInstances(mcrt_ctx* ctx, int instance, bool lean, int trace = kInstNone, int knn = kInstNone, bool knn_lean = false) {
+    ctx->lean_used = lean || knn_lean;
+    ctx->used_instance = instance;
+    ctx->used_trace = trace;
+    ctx->used_knn = knn;
+    ctx->used_text = std::string(instanceName(instance)) + (lean ? "/lean," : ",") + instanceName(trace) + "," + instanceName(knn) + (knn_lean ? "/lean" : "");
+}
+
 // The start of every frame: the statistics cleared, the clocks started, ev0 recorded (each pass clears the work counter itself).
 int beginFrame(mcrt_ctx* ctx, hipStream_t stream, uint32_t kernel_id) {
     if (!ctx->work_counter.p) HIP_TRY(ctx, ctx->work_counter.alloc(sizeof(unsigned long long)));
@@ -594,7 +608,7 @@ int launchWavefront(mcrt_ctx* ctx, const mcrt_camera_desc* cam, uint32_t global_
 
     if (int rc = beginFrame(ctx, stream, owned_rows == 0 ? (uint32_t)MCRT_KERNEL_NONE : choice.form)) return rc;
     if (owned_rows == 0) return endFrame(ctx, stream);
-    ctx->lean_used = choice.lean || choice.knn_lean;
+    noteInstances(ctx, choice.instance, choice.lean, choice.trace_instance, choice.knn_instance, choice.knn_lean);
 
     // Passes: as many rows as the per-sample store holds (box filter; splat frames keep no samples and are one pass).
     uint64_t pass_rows = owned_rows;
@@ -710,7 +724,7 @@ int launchRenderImpl(mcrt_ctx* ctx, const mcrt_camera_desc* cam, uint32_t global
     if (photon && !ctx->has_photons) return fail(ctx, MCRT_ERR_NO_PHOTONS, "photon mapping render before mcrt_upload_photons");
     if (ctx->pending) return fail(ctx, MCRT_ERR_INVALID, "a render is already in flight: call mcrt_render_finish");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    ctx->lean_used = false;
+    noteInstances(ctx, kInstNone, false);
 
     const uint32_t owned_rows = mcrt_shard_rows(cam, nullptr);
     FrameFacts frame;
@@ -741,7 +755,7 @@ int launchRenderImpl(mcrt_ctx* ctx, const mcrt_camera_desc* cam, uint32_t global
     if (int rc = ensureSpill(ctx, megaSpillEntries(ctx->scene, choice, g.total_lanes) * sizeof(StackEntry))) return rc;
     if (int rc = beginFrame(ctx, stream, owned_rows == 0 ? (uint32_t)MCRT_KERNEL_NONE : choice.form)) return rc;
     if (owned_rows == 0) return endFrame(ctx, stream);
-    ctx->lean_used = choice.lean;
+    noteInstances(ctx, choice.instance, choice.lean);
 
     // Sample-chunked work units (RenderParams): the frame goes through in passes of as many rows as the per-sample store holds
     // (MCRT_SAMPLE_STORE_GB, default 64: mcrt_plan.hpp), each pass = one integrator launch + the in-order resolve.
@@ -954,6 +968,7 @@ int mcrt_set_option(mcrt_ctx* ctx, const char* key, const char* value) {
 const char* mcrt_get_option(const mcrt_ctx* ctx, const char* key) {
     if (!ctx || !key) return nullptr;
     if (strcmp(key, "MCRT_LEAN_USED") == 0) return ctx->lean_used ? "1" : "0";  // (read-only: did the last frame / photon pass run a lean kernel instance)
+    if (strcmp(key, "MCRT_INSTANCES_USED") == 0) return ctx->used_text.c_str();  // (read-only: ... and which instances, noteInstances)
     return mcrt::ctxOpt(ctx, key);
 }
 
@@ -1142,24 +1157,32 @@ int mcrt_render_finish(mcrt_ctx* ctx, mcrt_stats* stats) {
     HIP_TRY(ctx, hipEventSynchronize(ctx->ev1));
     unsigned long long h[kStatsWords];
     HIP_TRY(ctx, hipMemcpy(h, ctx->stats.p, sizeof(h), hipMemcpyDeviceToHost));
-    if (ctxOptOn(ctx, "MCRT_PROFILE_PHASES")) {
+    // Readouts of the words 8.. - only of what the instances that ran measured (noteInstances). The phase clocks, the trace kernel's step
+    // counters and the photon-mapping kernel's estimate clocks share those words: a line is printed for the kernel that wrote them and never
+    // from the option alone (MCRT_PROFILE_PHASES on a form without a profiling instance - pipeline, photon kernels - or next to
+    // MCRT_COUNT_TESTS, which a profiling instance does not carry, used to print another kernel's words as phases), and never with a zero
+    // divisor (a frame whose launches found no work leaves every clock at 0).
+    if (instanceProfiles(ctx->used_instance)) {
         static const char* names[kNumPhases] = {"regen", "trav/inner", "shade", "shadow/leaf", "sample", "loop"};
         unsigned long long tw = 0;
         for (int i = 0; i < kNumPhases; i++) tw += h[8 + i];
-        for (int i = 0; i < kNumPhases; i++)
-            fprintf(stderr, "[mcrt phase] %-9s wave-cycles %6.2f%%  lane utilisation %5.1f%%\n", names[i], 100.0 * h[8 + i] / (double)(tw ? tw : 1),
+        for (int i = 0; tw && i < kNumPhases; i++)
+            fprintf(stderr, "[mcrt phase] %-9s wave-cycles %6.2f%%  lane utilisation %5.1f%%\n", names[i], 100.0 * h[8 + i] / (double)tw,
                     h[8 + i] ? 100.0 * h[8 + kNumPhases + i] / (64.0 * h[8 + i]) : 0.0);
     }
-    if (ctx->kernel_id == MCRT_KERNEL_WAVEFRONT && h[8] && ctxOptOn(ctx, "MCRT_COUNT_TESTS"))
+    if (ctx->kernel_id == MCRT_KERNEL_WAVEFRONT && ctx->used_trace == kInstTrace_Count && h[8] && h[17]) {
+        const double iters = (double)h[8], cyc = (double)h[17], rays = (double)(h[1] ? h[1] : 1);
+        const unsigned long long stepped = std::min(h[15] + h[16], h[17]);
         fprintf(stderr, "[mcrt trace] per wave iteration: %.1f lanes hold a ray; inner step in %.1f%% of the iterations with %.1f lanes, leaf step in %.1f%% with %.1f lanes, "
-                        "%.1f leaf lanes wait; wave cycles: inner %.1f%%, leaf %.1f%%, rest %.1f%% (of the kernel: refills %.1f%%, pop site %.1f%%); per ray: %.2f inner steps, %.2f leaf steps\n",
-                (double)h[9] / h[8], 100.0 * h[10] / h[8], h[10] ? (double)h[11] / h[10] : 0.0, 100.0 * h[12] / h[8], h[12] ? (double)h[13] / h[12] : 0.0,
-                (double)h[14] / h[8], 100.0 * h[15] / (double)h[17], 100.0 * h[16] / (double)h[17], 100.0 * (h[17] - h[15] - h[16]) / (double)h[17],
-                100.0 * h[18] / (double)h[17], 100.0 * h[19] / (double)h[17],
-                (double)h[11] / (double)(h[1] ? h[1] : 1), (double)h[13] / (double)(h[1] ? h[1] : 1));
-    if (ctx->kernel_id == MCRT_KERNEL_PM_WAVE && h[9] && ctxOptOn(ctx, "MCRT_COUNT_TESTS"))
+                        "%.1f leaf lanes wait; wave cycles: inner %.1f%%, leaf %.1f%%, rest %.1f%% (of the kernel: refills %.1f%%, pop site %.1f%%); per ray: %.2f inner steps, %.2f leaf steps "
+                        "(%llu inner and %llu leaf lane steps of %llu rays)\n",
+                (double)h[9] / iters, 100.0 * h[10] / iters, h[10] ? (double)h[11] / h[10] : 0.0, 100.0 * h[12] / iters, h[12] ? (double)h[13] / h[12] : 0.0,
+                (double)h[14] / iters, 100.0 * h[15] / cyc, 100.0 * h[16] / cyc, 100.0 * (h[17] - stepped) / cyc, 100.0 * h[18] / cyc, 100.0 * h[19] / cyc,
+                (double)h[11] / rays, (double)h[13] / rays, h[11], h[13], h[1]);
+    }
+    if (ctx->kernel_id == MCRT_KERNEL_PM_WAVE && instanceClocksEstimates(ctx->used_instance) && h[9])
         fprintf(stderr, "[mcrt pm] wave cycles inside the radiance estimates: %.1f%% of the kernel (%llu searches, %.1f octants per search)\n",
-                100.0 * (double)h[8] / (double)h[9], h[4], h[4] ? (double)h[6] / (double)h[4] : 0.0);
+                100.0 * (double)std::min(h[8], h[9]) / (double)h[9], h[4], h[4] ? (double)h[6] / (double)h[4] : 0.0);
     float ms = 0.f;
     HIP_TRY(ctx, hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
     if (stats) {
@@ -1264,7 +1287,7 @@ int emitOnDevice(mcrt_ctx* ctx, double emissions, double caustic_factor, uint32_
     if (int rc = uploadArray(ctx, ctx->emit_flux, pflux.data(), pflux.size())) return rc;
     if (!ctx->emit_counters.p) HIP_TRY(ctx, ctx->emit_counters.alloc(8 * sizeof(unsigned long long)));
 
-    ctx->lean_used = leanScene(ctx->facts, parseRenderOptions(ctx->options));
+    noteInstances(ctx, ctx->scene.stage_all ? kInstEmit_All : kInstEmit, leanScene(ctx->facts, parseRenderOptions(ctx->options)));
     auto kernel = kernelAs<void (*)(const DeviceScene, const EmitParams)>(instanceAddress(ctx->scene.stage_all ? kInstEmit_All : kInstEmit, ctx->lean_used));
     if (!kernel) return fail(ctx, MCRT_ERR_INVALID, "internal error: no such lean kernel instance");
     DeviceScene scene = ctx->scene;

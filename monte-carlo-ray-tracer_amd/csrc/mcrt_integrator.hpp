@@ -48,13 +48,18 @@ struct PhaseProf<true> {
         if (participated) lane_cycles[p] += dt;
         if (__lane_id() == 0) wave_cycles[p] += dt;
     }
-    // called by every active lane when it enters phase p
+    // called by every active lane when it enters phase p. The phase it leaves is charged by the first of the lanes that arrive together:
+    // its cycles as the wave's, and those cycles once per arriving lane as the lanes'. (Each lane charging its OWN cycles counted the time
+    // it sat masked off - no pixel left, the other side of a branch - as work in the phase it waited in: the loop phase of a 70 x 21 frame
+    // read 122 to 167 per cent lane utilisation, profiles/NOTES_diagnostic_kernels.md.)
     __device__ void mark(int p) {
         const unsigned long long t = clock64();
         const unsigned long long dt = t - t0;
         const unsigned long long mask = waveBallot(1);
-        lane_cycles[cur] += dt;
-        if ((int)__lane_id() == __ffsll((long long)mask) - 1) wave_cycles[cur] += dt;
+        if ((int)__lane_id() == __ffsll((long long)mask) - 1) {
+            wave_cycles[cur] += dt;
+            lane_cycles[cur] += dt * (unsigned long long)__popcll(mask);
+        }
         t0 = t;
         cur = p;
     }

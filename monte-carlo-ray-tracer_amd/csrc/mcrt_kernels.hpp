@@ -1265,6 +1265,7 @@ __global__ void __launch_bounds__(256) MCRT_KNN_OCC wfKnnKernel(const WfKnnArgs 
                 }
                 continue;
             }
+            MCRT_LOCKSTEP();  // (the result was compacted by other lanes, as in waveEvalPhotons)
             if (lane == 0) {
                 a.res_n[(size_t)map * slots + slot] = c;
                 a.res_r2[(size_t)map * slots + slot] = r2;

@@ -142,6 +142,34 @@ enum RenderInstance : int {
     kInstCount
 };
 
+// The enumerator's name without its prefix ("-" for kInstNone): what the read-only option MCRT_INSTANCES_USED reports.
+inline const char* instanceName(int id) {
+    static const char* const names[] = {
+        "PT", "PT_All", "PT_Count", "PT_CountAll", "PT_Prof", "PT_ProfAll",
+        "PMLane", "PMLane_All", "PMLane_Count", "PMLane_CountAll",
+        "Flat512", "FlatK512", "FlatK768",
+        "SM", "SM_All", "SM_Count", "SM_CountAll", "SM_Prof", "SM_ProfAll",
+        "PM512", "PM512_All", "PM512_Count", "PM512_CountAll",
+        "PM1024", "PM1024_All", "PM1024_Count", "PM1024_CountAll",
+        "PMWide", "PMWide_All", "PMWide_Count", "PMWide_CountAll",
+        "ShadePT", "ShadePM",
+        "Trace", "Trace_Count", "TraceLean", "TraceLeanSingle",
+        "KnnEval", "KnnEvalWide", "KnnRaw", "KnnRawWide",
+        "Emit", "Emit_All"};
+    static_assert(sizeof(names) / sizeof(names[0]) == kInstCount && kInstFlat512 == 10 && kInstSM == 13 && kInstPM512 == 19 && kInstShadePT == 31 &&
+                      kInstTrace == 33 && kInstKnnEval == 37 && kInstEmit == 41,
+                  "names follow the enumeration");
+    return id >= 0 && id < kInstCount ? names[id] : "-";
+}
+
+// Which words 8.. of a frame's statistics the instance wrote: the phase clocks (MCRT_PROFILE_PHASES), the trace kernel's step counters
+// and the photon-mapping kernel's estimate clocks (MCRT_COUNT_TESTS). mcrt_render_finish prints a readout only for what was measured.
+inline bool instanceProfiles(int id) { return id == kInstPT_Prof || id == kInstPT_ProfAll || id == kInstSM_Prof || id == kInstSM_ProfAll; }
+inline bool instanceClocksEstimates(int id) {
+    return id == kInstPM512_Count || id == kInstPM512_CountAll || id == kInstPM1024_Count || id == kInstPM1024_CountAll || id == kInstPMWide_Count ||
+           id == kInstPMWide_CountAll;
+}
+
 // The inner visit of the pipeline's trace kernel (wfTraceKernel's third template argument; launchWavefront and mcrt_intersect):
 // MCRT_WF_LEAN (default 1) 1: travInnerStepQLean - with one block per visit (3) when the tree has no node with more than four children
 // (every quaternary tree); 0 (and MCRT_COUNT_TESTS): the earlier visit; 2: the block loop kept on a quaternary tree.

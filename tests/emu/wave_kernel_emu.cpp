@@ -167,6 +167,13 @@ int wemu_trace_kernel(const mcrt_scene_desc* scene, uint64_t n, const double* st
 // out_rgb [h][w][3]; stats_out [kStatsWords]. Returns 0, or a negative code (-100 stack overflow, -202 LDS plan too large, -203 an
 // instance this library does not hold, ...).
 enum : int { kForceWaveSync = 2, kForceFlatKarg = 6 };
+// MCRT_COUNT_TESTS / MCRT_WF_PM_EVAL of the frames that follow (wemu_set_count_tests, wemu_set_pm_eval). count_tests -1, the default:
+// wemu_render runs the instances without counters and wemu_render_pipeline the trace kernel WITH them, as both did before the switch existed.
+static int g_count_tests = -1, g_pm_eval = 1;
+static uint32_t g_flat_max = 64u;  // MCRT_FLAT_MAX of the scenes that follow (wemu_set_flat_max; 0: a small scene's BVH is walked)
+void wemu_set_flat_max(uint32_t n) { g_flat_max = n; }
+void wemu_set_count_tests(int on) { g_count_tests = on; }
+void wemu_set_pm_eval(int on) { g_pm_eval = on; }
 static uint64_t g_last_launch[4];  // of the last wemu_render call: {instance, workgroup size, stack entries per lane in LDS, dynamic LDS bytes}
 void wemu_last_launch(uint64_t* out) { std::copy(g_last_launch, g_last_launch + 4, out); }
 // What selectKernel reads of a scene as wemu_render derives it (sceneFacts), in emu_select_kernel's layout; out[25]: the LDS budget
@@ -174,7 +181,7 @@ int wemu_scene_facts(const mcrt_scene_desc* scene, uint64_t* out) {
     Emu E;
     if (int rc = setup(E, scene, 0)) return rc;
     DeviceScene d;
-    fillDeviceScene(scene, E, d, 64u);
+    fillDeviceScene(scene, E, d, g_flat_max);
     const SceneFacts f = sceneFacts(d, E.L, *scene);
     const uint64_t o[9] = {f.flat, f.cull, f.cull_floats, f.stage_all, f.num_nodes, f.q_nodes, f.q_single, f.material_flags, f.pm_lds_full};
     std::copy(o, o + 9, out);
@@ -188,15 +195,18 @@ int wemu_render(const mcrt_scene_desc* scene, const mcrt_photon_map_desc* gmap, 
     Emu E;
     if (int rc = setup(E, scene, 0)) return rc;
     DeviceScene d;
-    fillDeviceScene(scene, E, d, 64u);
+    fillDeviceScene(scene, E, d, g_flat_max);
     const bool photon = integrator == MCRT_INTEGRATOR_PHOTON_MAPPER;
     if (grid == 0) grid = 1;
     RenderOptions opt;
     opt.lean_kernels = MCRT_MAT_FEATURES_OFF != 0u;  // (csrc/mcrt_shade.hpp: 0 unless the build strips material features)
     SceneFacts facts = sceneFacts(d, E.L, *scene);
+    opt.count_tests = g_count_tests > 0;
     if (force == kForceWaveSync && !photon) {
         opt.kernel = kKernelLegacy;
         facts.cull = false;
+    } else if (force == kForceWaveSync) {  // photon-mapped: MCRT_KERNEL=legacy is the per-lane kernel
+        opt.kernel = kKernelLegacy;
     } else if (!d.flat) {
         opt.kernel = kKernelSm;
     } else if (force == 0) {
@@ -235,13 +245,29 @@ int wemu_render(const mcrt_scene_desc* scene, const mcrt_photon_map_desc* gmap, 
         if (pmIorsInMemory(choice)) pm_iors.resize(pmIorsBytes(total_lanes) / sizeof(double));
         fillPmExtra(pmx, wg.view, wc.view, choice, stage.data(), knn_spill.data(), pm_iors.data());
     }
+    std::vector<double> knn_res_d2, knn_visit_d2;
+    std::vector<uint32_t> knn_res_idx, knn_visit_oct;
+    if (choice.form == MCRT_KERNEL_PM_LANE) {  // the per-lane searches' scratch (ensureScratch, mcrt_hip.hip)
+        if (wg.init(gmap, k_nearest) || wc.init(cmap, k_nearest)) return -301;
+        setRenderMaps(prm, wg.view.base, wc.view.base, k_nearest, direct_visualization);
+        const uint32_t k = std::max<uint32_t>(k_nearest, 1u);
+        knn_res_d2.resize((size_t)total_lanes * k);
+        knn_res_idx.resize((size_t)total_lanes * k);
+        knn_visit_d2.resize((size_t)total_lanes * kMaxVisit);
+        knn_visit_oct.resize((size_t)total_lanes * kMaxVisit);
+        prm.knn_res_d2 = knn_res_d2.data();
+        prm.knn_res_idx = knn_res_idx.data();
+        prm.knn_visit_d2 = knn_visit_d2.data();
+        prm.knn_visit_oct = knn_visit_oct.data();
+        prm.knn_max_visit = kMaxVisit;
+    }
     setRenderPass(prm, 0, prm.owned_rows, photon);
     FlatPreArg pre;
     if (flat_karg) {  // the cull records as a kernel argument (renderKernelFlatK, MCRT_FLAT_KARG)
         memset(&pre, 0, sizeof(pre));
         memcpy(pre.v, E.L.flat_pre.data(), E.L.flat_pre.size() * sizeof(float));
     }
-    constexpr int PT = MCRT_INTEGRATOR_PATH_TRACER;
+    constexpr int PT = MCRT_INTEGRATOR_PATH_TRACER, PM = MCRT_INTEGRATOR_PHOTON_MAPPER;
     switch (choice.instance) {  // the instance -> the template it names (instanceTable, mcrt_hip.hip)
         case kInstPM1024_All: launchGrid(grid, block, [&] { renderKernelPM<false, true, 1024>(launch_scene, prm, pmx); }); break;
         case kInstPM1024: launchGrid(grid, block, [&] { renderKernelPM<false, false, 1024>(launch_scene, prm, pmx); }); break;
@@ -254,7 +280,24 @@ int wemu_render(const mcrt_scene_desc* scene, const mcrt_photon_map_desc* gmap, 
         case kInstFlat512: launchGrid(grid, block, [&] { renderKernel<PT, false, true, false, 1>(launch_scene, prm); }); break;
         case kInstPT_All: launchGrid(grid, block, [&] { renderKernel<PT, false, true>(launch_scene, prm); }); break;
         case kInstPT: launchGrid(grid, block, [&] { renderKernel<PT, false, false>(launch_scene, prm); }); break;
-        default: return -203;  // (the per-lane and the wide photon-mapping instances are not built into this library)
+        // MCRT_COUNT_TESTS (wemu_set_count_tests), the per-lane photon-mapping kernel and the wide candidate buffer
+        case kInstPT_CountAll: launchGrid(grid, block, [&] { renderKernel<PT, true, true>(launch_scene, prm); }); break;
+        case kInstPT_Count: launchGrid(grid, block, [&] { renderKernel<PT, true, false>(launch_scene, prm); }); break;
+        case kInstSM_CountAll: launchGrid(grid, block, [&] { renderKernelSM<true, true>(launch_scene, prm); }); break;
+        case kInstSM_Count: launchGrid(grid, block, [&] { renderKernelSM<true, false>(launch_scene, prm); }); break;
+        case kInstPM1024_CountAll: launchGrid(grid, block, [&] { renderKernelPM<true, true, 1024>(launch_scene, prm, pmx); }); break;
+        case kInstPM1024_Count: launchGrid(grid, block, [&] { renderKernelPM<true, false, 1024>(launch_scene, prm, pmx); }); break;
+        case kInstPM512_CountAll: launchGrid(grid, block, [&] { renderKernelPM<true, true>(launch_scene, prm, pmx); }); break;
+        case kInstPM512_Count: launchGrid(grid, block, [&] { renderKernelPM<true, false>(launch_scene, prm, pmx); }); break;
+        case kInstPMWide_All: launchGrid(grid, block, [&] { renderKernelPM<false, true, (int)kBlock, kWaveRowsLarge>(launch_scene, prm, pmx); }); break;
+        case kInstPMWide: launchGrid(grid, block, [&] { renderKernelPM<false, false, (int)kBlock, kWaveRowsLarge>(launch_scene, prm, pmx); }); break;
+        case kInstPMWide_CountAll: launchGrid(grid, block, [&] { renderKernelPM<true, true, (int)kBlock, kWaveRowsLarge>(launch_scene, prm, pmx); }); break;
+        case kInstPMWide_Count: launchGrid(grid, block, [&] { renderKernelPM<true, false, (int)kBlock, kWaveRowsLarge>(launch_scene, prm, pmx); }); break;
+        case kInstPMLane_All: launchGrid(grid, block, [&] { renderKernel<PM, false, true>(launch_scene, prm); }); break;
+        case kInstPMLane: launchGrid(grid, block, [&] { renderKernel<PM, false, false>(launch_scene, prm); }); break;
+        case kInstPMLane_CountAll: launchGrid(grid, block, [&] { renderKernel<PM, true, true>(launch_scene, prm); }); break;
+        case kInstPMLane_Count: launchGrid(grid, block, [&] { renderKernel<PM, true, false>(launch_scene, prm); }); break;
+        default: return -203;  // (an instance this library does not hold: the profiling ones)
     }
     const int kernel_id = flat_karg ? 16 : (int)choice.form;
     launchGrid((uint32_t)((prm.pass_pixels + 255) / 256), 256, [&] { sampleResolveKernel(prm.samples, prm.pass_pixels, prm.spp, out_rgb); });
@@ -275,10 +318,11 @@ int wemu_render_pipeline(const mcrt_scene_desc* scene, const mcrt_photon_map_des
     Emu E;
     if (int rc = setup(E, scene, 0)) return rc;
     DeviceScene d;
-    fillDeviceScene(scene, E, d, 64u);
+    fillDeviceScene(scene, E, d, g_flat_max);
     if (d.q_nodes == 0 || trace_grid == 0 || trace_waves == 0 || trace_waves > 16) return -200;
     const bool photon = integrator == MCRT_INTEGRATOR_PHOTON_MAPPER;
-    if (photon && k_nearest > waveMaxK(kWaveRows)) return -203;
+    const bool large_k = photon && k_nearest > waveMaxK(kWaveRows), knn_eval = g_pm_eval != 0, trace_counts = g_count_tests != 0;
+    if (photon && k_nearest > waveMaxK(kWaveRowsLarge)) return -203;
     const uint32_t spp = cam->sqrtspp * cam->sqrtspp, owned_rows = cam->height;
     const uint64_t pixels = (uint64_t)cam->width * owned_rows;
     const uint64_t slots = std::max<uint64_t>((slots_wanted + kWfBlock - 1) / kWfBlock * kWfBlock, kWfBlock);
@@ -310,15 +354,25 @@ int wemu_render_pipeline(const mcrt_scene_desc* scene, const mcrt_photon_map_des
     WfKnnArgs ka;
     memset(&ka, 0, sizeof(ka));
     std::vector<uint32_t> requests, knn_spill;
-    std::vector<double> stage, est;
+    std::vector<double> stage, est, res_r2, res_d2;
+    std::vector<uint32_t> res_n, res_idx;
     const uint32_t knn_grid = 2;
     if (photon) {
         if (wg.init(gmap, k_nearest) || wc.init(cmap, k_nearest)) return -301;
         requests.resize(slots);
-        stage.resize((size_t)slots * kStageDoubles);
-        est.resize((size_t)slots * 6);
         knn_spill.resize(wfKnnSpillBytes(knn_grid) / sizeof(uint32_t));
-        fillKnnArgs(ka, sa, ctrl, wg.view, wc.view, k_nearest, direct_visualization, requests.data(), stage.data(), est.data(), knn_spill.data());
+        if (knn_eval) {
+            stage.resize((size_t)slots * kStageDoubles);
+            est.resize((size_t)slots * 6);
+            fillKnnArgs(ka, sa, ctrl, wg.view, wc.view, k_nearest, direct_visualization, requests.data(), stage.data(), est.data(), knn_spill.data());
+        } else {  // MCRT_WF_PM_EVAL=0: the k photons handed back, summed per lane by the shade launch (runWavefrontPass's buffers)
+            res_n.resize((size_t)2 * slots, 0xA5A5A5A5u);
+            res_r2.resize((size_t)2 * slots, -1.0);
+            res_idx.resize((size_t)2 * k_nearest * slots, 0xA5A5A5A5u);
+            res_d2.resize((size_t)2 * k_nearest * slots, -1.0);
+            fillKnnArgs(ka, sa, ctrl, wg.view, wc.view, k_nearest, direct_visualization, requests.data(), nullptr, nullptr, knn_spill.data(), res_n.data(),
+                        res_r2.data(), res_idx.data(), res_d2.data());
+        }
     }
     uint32_t launches = 0;
     for (uint64_t it = 0;; it++) {
@@ -335,12 +389,16 @@ int wemu_render_pipeline(const mcrt_scene_desc* scene, const mcrt_photon_map_des
             wemu::runGroup((int)trace_waves, [&](int) {
                 if (trace_form == 11) wfTraceKernel<PoolRays, true, 1>(ta, pr);
                 else if (trace_form == 27) wfTraceKernel<PoolRays, true, 3>(ta, pr);
-                else wfTraceKernel<PoolRays, true, 0>(ta, pr);
+                else if (trace_counts) wfTraceKernel<PoolRays, true, 0>(ta, pr);  // Trace_Count
+                else wfTraceKernel<PoolRays, false, 0>(ta, pr);                   // Trace (MCRT_WF_LEAN=0 without counters)
             });
         }
         launches++;
         if (photon) {
-            launchGrid(knn_grid, 256, [&] { wfKnnKernel<true>(ka); });
+            if (knn_eval && !large_k) launchGrid(knn_grid, 256, [&] { wfKnnKernel<true>(ka); });
+            else if (knn_eval) launchGrid(knn_grid, 256, [&] { wfKnnKernel<true, kWaveRowsLarge>(ka); });
+            else if (!large_k) launchGrid(knn_grid, 256, [&] { wfKnnKernel<false>(ka); });
+            else launchGrid(knn_grid, 256, [&] { wfKnnKernel<false, kWaveRowsLarge>(ka); });
             launches++;
         }
     }

@@ -511,3 +511,253 @@ def test_emulated_frames_run_the_instance_the_host_selects(pkg, wave_kernel_emu,
     assert kid == (16 if force == 6 and form == 1 else form)
     if force == 6 and form == 1:
         assert block == 768  # the full instance with its records as an argument: the shape the host launches
+
+
+# ---- the counting instances (MCRT_COUNT_TESTS), the per-lane and the wide photon-mapping kernels, the raw kNN launch --------------------
+# RenderInstance of csrc/mcrt_select.hpp by value (instanceName gives the same words: test_instance_names_follow_the_enumeration)
+INSTANCE_NAMES = ["PT", "PT_All", "PT_Count", "PT_CountAll", "PT_Prof", "PT_ProfAll", "PMLane", "PMLane_All", "PMLane_Count", "PMLane_CountAll",
+                  "Flat512", "FlatK512", "FlatK768", "SM", "SM_All", "SM_Count", "SM_CountAll", "SM_Prof", "SM_ProfAll",
+                  "PM512", "PM512_All", "PM512_Count", "PM512_CountAll", "PM1024", "PM1024_All", "PM1024_Count", "PM1024_CountAll",
+                  "PMWide", "PMWide_All", "PMWide_Count", "PMWide_CountAll", "ShadePT", "ShadePM", "Trace", "Trace_Count", "TraceLean", "TraceLeanSingle",
+                  "KnnEval", "KnnEvalWide", "KnnRaw", "KnnRawWide", "Emit", "Emit_All"]
+
+
+def test_instance_names_follow_the_enumeration():
+    import re
+    from conftest import ROOT
+    text = open(os.path.join(ROOT, "monte-carlo-ray-tracer_amd", "csrc", "mcrt_select.hpp")).read()
+    body = re.sub(r"//[^\n]*", "", text[text.index("enum RenderInstance"):text.index("kInstCount\n")])
+    enum = [m for m in re.findall(r"kInst(\w+)", body) if m != "None"]
+    assert enum == INSTANCE_NAMES
+    names = re.findall(r'"([A-Za-z0-9_]+)"', text[text.index("inline const char* instanceName"):text.index("static_assert(sizeof(names)")])
+    assert names == INSTANCE_NAMES
+
+
+class SceneWithMaps:
+    """A SceneImage's scene with photon maps of the test's own making (oracle_lib and the emulation read .scene, .photons() and .param())."""
+
+    def __init__(self, img, maps, k):
+        self.img, self.maps, self.k, self.scene = img, maps, k, img.scene
+
+    def photons(self, which):
+        return self.maps[which].desc
+
+    def param(self, key):
+        return self.k if key == "k_nearest_photons" else 0
+
+
+def coffee_maker_with_photons(pkg, oracle, manifest, k=50):
+    """coffee_maker_qsah - a tree that stays in memory - with maps from the oracle's own emission pass: the scene of the photon-mapping
+    instances for trees in memory (golden photon-mapped scenes are all LDS-resident)."""
+    img = pkg.SceneImage(golden_path(manifest["cases"]["coffee_maker_qsah"]["image"]))
+    em = oracle.emit_photons(img, 4000, 10.0, manifest["seed"])
+    assert len(em["global_"][1]) > 1000 and len(em["caustic"][1]) > 100
+    s = img.scene
+    maps = [pkg.PhotonMap(em[key][0], s.bb_min[:], s.bb_max[:], 200) for key in ("global_", "caustic")]
+    return SceneWithMaps(img, maps, k)
+
+
+class emu_options:
+    """MCRT_COUNT_TESTS / MCRT_WF_PM_EVAL / MCRT_FLAT_MAX of the emulated frames inside the block (wave_kernel_emu.cpp's switches)."""
+
+    def __init__(self, lib, count=None, pm_eval=1, flat_max=64):
+        self.lib, self.values = lib, (-1 if count is None else int(count), int(pm_eval), int(flat_max))
+        for f, t in ((lib.wemu_set_count_tests, C.c_int), (lib.wemu_set_pm_eval, C.c_int), (lib.wemu_set_flat_max, C.c_uint32)):
+            f.argtypes, f.restype = [t], None
+        lib.wemu_last_launch.argtypes, lib.wemu_last_launch.restype = [C.c_void_p], None
+
+    def _set(self, count, pm_eval, flat_max):
+        self.lib.wemu_set_count_tests(count)
+        self.lib.wemu_set_pm_eval(pm_eval)
+        self.lib.wemu_set_flat_max(flat_max)
+
+    def __enter__(self):
+        self._set(*self.values)
+
+    def __exit__(self, *exc):
+        self._set(-1, 1, 64)
+
+
+def emulated_megakernel_frame(pkg, lib, img, cam, seed, integrator, count, legacy=False, flat_max=64, k=None, grid=1):
+    """-> (frame, stats words, the RenderInstance name wemu_render ran)"""
+    out = np.zeros((cam.height, cam.width, 3))
+    stats = np.zeros(64, dtype=np.uint64)
+    kid = C.c_int(0)
+    g, c = img.photons(0), img.photons(1)
+    with emu_options(lib, count=count, flat_max=flat_max):
+        rc = lib.wemu_render(C.byref(img.scene), C.byref(g) if g is not None else None, C.byref(c) if c is not None else None,
+                             k or img.param("k_nearest_photons") or 50, 0, C.byref(cam), seed, integrator, 2 if legacy else 0, grid, out.ctypes.data,
+                             stats.ctypes.data, C.byref(kid))
+    launch = (C.c_uint64 * 4)()
+    lib.wemu_last_launch(launch)
+    assert rc == 0, "wemu_render: %d (instance %s)" % (rc, INSTANCE_NAMES[int(launch[0])])
+    return out, [int(x) for x in stats[:20]], INSTANCE_NAMES[int(launch[0])]
+
+
+def emulated_pipeline_frame(lib, img, cam, seed, integrator, count, pm_eval=1, k=None, slots=512, grid=2, waves=2):
+    """... through the pipeline with the trace kernel's earlier visit (form 3: Trace / Trace_Count) -> (frame, stats words)"""
+    out = np.zeros((cam.height, cam.width, 3))
+    stats = np.zeros(64, dtype=np.uint64)
+    launches = C.c_uint32(0)
+    g, c = img.photons(0), img.photons(1)
+    with emu_options(lib, count=count, pm_eval=pm_eval):
+        rc = lib.wemu_render_pipeline(C.byref(img.scene), C.byref(g) if g is not None else None, C.byref(c) if c is not None else None,
+                                      k or img.param("k_nearest_photons") or 50, 0, C.byref(cam), seed, integrator, slots, grid, waves, 3, out.ctypes.data,
+                                      stats.ctypes.data, C.byref(launches))
+    assert rc == 0, "wemu_render_pipeline: %d" % rc
+    return out, [int(x) for x in stats[:20]]
+
+
+def check_counter_bounds(img, stats, frame, flat):
+    """What include/mcrt.h says of node_tests / prim_tests, as far as it can be said without walking the tree again: a flat scene tests no
+    node and at most every primitive per ray - with cull records what the FP32 cull leaves (the bound of test_device_code_host_emulation.py) -
+    a tree tests at least its root per ray that is walked; and a ray that hit something passed at least one primitive test. Rays that hit
+    are not counted by any kernel: at least one per pixel that is not black."""
+    paths, rays, node_tests, prim_tests = stats[:4]
+    ns = img.scene.num_surfaces
+    assert prim_tests > 0 and prim_tests >= int((frame != 0).any(axis=2).sum())
+    if flat:
+        assert node_tests == 0 and prim_tests <= ns * rays
+        assert prim_tests < (0.15 if ns >= 20 else 0.6) * ns * rays
+    else:
+        assert node_tests > 0 and node_tests >= paths
+
+
+FRAME = (70, 21, 2)       # ragged against the 8 x 8 tiles in both directions, four samples per pixel
+SMALL_FRAME = (22, 9, 1)  # ... for the wave-cooperative searches, whose emulation takes 4 ms each
+
+# (scene, photon-mapped, MCRT_KERNEL=legacy, MCRT_FLAT_MAX, k, frame, the instance without / with MCRT_COUNT_TESTS, counters are sums of per-ray quantities)
+COUNTING_CASES = [
+    ("hexagon_room_diffuse", False, False, 64, None, FRAME, "Flat512", "PT_CountAll", True),
+    ("hexagon_room_diffuse", False, True, 64, None, FRAME, "PT_All", "PT_CountAll", True),
+    ("hexagon_room_diffuse", False, False, 0, None, FRAME, "SM_All", "SM_CountAll", True),
+    ("hexagon_room_diffuse", False, True, 0, None, FRAME, "PT_All", "PT_CountAll", True),
+    ("coffee_maker_qsah", False, False, 64, None, FRAME, "SM", "SM_Count", True),
+    ("coffee_maker_qsah", False, True, 64, None, FRAME, "PT", "PT_Count", True),
+    ("quadric", False, False, 64, None, FRAME, "SM", "SM_Count", True),
+    ("quadric", False, True, 64, None, FRAME, "PT", "PT_Count", True),
+    ("hexagon_room_pm", True, False, 64, None, SMALL_FRAME, "PM1024_All", "PM1024_CountAll", True),
+    ("hexagon_room_pm", True, True, 64, None, FRAME, "PMLane_All", "PMLane_CountAll", True),
+    ("hexagon_room_pm", True, False, 64, 129, SMALL_FRAME, "PMWide_All", "PMWide_CountAll", True),
+    ("coffee_maker_qsah+photons", True, False, 64, None, SMALL_FRAME, "PM1024", "PM1024_Count", False),
+    ("coffee_maker_qsah+photons", True, True, 64, None, SMALL_FRAME, "PMLane", "PMLane_Count", True),
+    ("coffee_maker_qsah+photons", True, False, 64, 129, SMALL_FRAME, "PMWide", "PMWide_Count", False),
+]
+
+
+def diagnostic_scene(pkg, oracle, manifest, name):
+    if name == "coffee_maker_qsah+photons":
+        img = coffee_maker_with_photons(pkg, oracle, manifest)
+        return img, pkg.SceneImage(golden_path(manifest["cases"]["coffee_maker_qsah"]["image"])).camera.copy()
+    from conftest import camera_for
+    case = manifest["cases"][name]
+    img = pkg.SceneImage(golden_path(case["image"]))
+    return img, camera_for(img, case["renders"][0])
+
+
+@pytest.mark.parametrize("name,photon,legacy,flat_max,k,frame,plain,counting,per_ray", COUNTING_CASES)
+def test_counting_instances_on_the_host_render_the_plain_instances_bits(pkg, wave_kernel_emu, oracle, manifest, name, photon, legacy, flat_max, k, frame, plain,
+                                                                         counting, per_ray):
+    """MCRT_COUNT_TESTS selects another kernel instance (csrc/mcrt_select.hpp) - for a flat scene another FORM, the wave-synchronous kernel -
+    and every decision of DESIGN.md that quotes node or primitive tests per ray was measured on such a frame: it has to be the frame that
+    was being studied. Each counting instance on emulated workgroups against the instance the same call runs without the option: the same
+    bits, paths, rays and searches (the ray count the oracle's, as in the cases above); words 2 and 3 zero without the option and within
+    the bounds of check_counter_bounds with it; and, for the instances whose counters are sums of per-ray quantities (per_ray: every walk but
+    the shared leaf step of trees in memory, whose deferred leaves are tested when OTHER lanes of the wave are ready), the same counters from
+    one workgroup and from two whose waves are visited in a shuffled order."""
+    img, cam = diagnostic_scene(pkg, oracle, manifest, name)
+    cam.width, cam.height, cam.sqrtspp = frame
+    integ = pkg.INTEGRATOR_PHOTON_MAPPER if photon else pkg.INTEGRATOR_PATH_TRACER
+    seed = manifest["seed"]
+    out0, st0, inst0 = emulated_megakernel_frame(pkg, wave_kernel_emu, img, cam, seed, integ, False, legacy, flat_max, k)
+    out1, st1, inst1 = emulated_megakernel_frame(pkg, wave_kernel_emu, img, cam, seed, integ, True, legacy, flat_max, k)
+    assert (inst0, inst1) == (plain, counting)
+    np.testing.assert_array_equal(out1, out0)
+    assert st1[0] == st0[0] == cam.width * cam.height * cam.sqrtspp ** 2 and st1[1] == st0[1] and st1[4] == st0[4] and (st0[4] > 0) == photon
+    assert st0[2] == st0[3] == 0
+    _, info = oracle.render(img, cam, seed, integ, k=k)
+    if counting.startswith("SM"):  # (shadow rays whose BSDF term is zero are not traced by the state machine)
+        assert 0 <= info["rays"] - st1[1] <= 0.03 * info["rays"]
+    else:
+        assert st1[1] == info["rays"]
+    flat = name.startswith("hexagon_room") and flat_max != 0
+    check_counter_bounds(img, st1, out1, flat)
+    print("%s: %s = the bits of %s; %d rays, %.2f node and %.2f primitive tests per ray" % (name, inst1, inst0, st1[1], st1[2] / st1[1], st1[3] / st1[1]))
+    if per_ray:
+        try:
+            wave_kernel_emu.wemu_set_shuffle(5)
+            out2, st2, _ = emulated_megakernel_frame(pkg, wave_kernel_emu, img, cam, seed, integ, True, legacy, flat_max, k, grid=2)
+        finally:
+            wave_kernel_emu.wemu_set_shuffle(0)
+        np.testing.assert_array_equal(out2, out0)
+        assert st2[:5] == st1[:5]
+
+
+def test_photon_mapping_instances_count_the_same_tests_per_ray_on_the_host(pkg, wave_kernel_emu, manifest):
+    """The photon-mapping kernels of an LDS-resident scene - wave-cooperative at 1024 lanes, with the wide candidate buffer, per lane - trace
+    the same rays through the same sceneIntersect: words 1 to 4 of the three counting instances are the same numbers."""
+    img, cam = diagnostic_scene(pkg, None, manifest, "hexagon_room_pm")
+    cam.width, cam.height, cam.sqrtspp = SMALL_FRAME
+    seen = {}
+    for legacy, k in ((False, None), (True, None), (False, 129), (True, 129)):
+        _, st, inst = emulated_megakernel_frame(pkg, wave_kernel_emu, img, cam, manifest["seed"], pkg.INTEGRATOR_PHOTON_MAPPER, True, legacy, 64, k)
+        seen[inst] = st[1:5]
+    assert set(seen) == {"PM1024_CountAll", "PMLane_CountAll", "PMWide_CountAll"}
+    assert len(set(map(tuple, seen.values()))) == 1, seen
+
+
+@pytest.mark.parametrize("name", ["coffee_maker_qsah", "quadric"])
+def test_counting_trace_kernel_on_the_host_renders_the_plain_kernels_bits(pkg, wave_kernel_emu, oracle, manifest, name):
+    """Trace_Count (wfTraceKernel<PoolRays, true>: what MCRT_COUNT_TESTS runs in the pipeline) against Trace (MCRT_WF_LEAN=0): the oracle's
+    frame from both, the same rays; the counters only from the first, with the step counters of the [mcrt trace] line consistent among
+    themselves (an iteration holds at most 64 rays, steps at most one per iteration, lane steps at most 64 per step)."""
+    img, cam = diagnostic_scene(pkg, oracle, manifest, name)
+    cam.width, cam.height, cam.sqrtspp = FRAME
+    want, info = oracle.render(img, cam, manifest["seed"], pkg.INTEGRATOR_PATH_TRACER)
+    out0, st0 = emulated_pipeline_frame(wave_kernel_emu, img, cam, manifest["seed"], pkg.INTEGRATOR_PATH_TRACER, False)
+    out1, st1 = emulated_pipeline_frame(wave_kernel_emu, img, cam, manifest["seed"], pkg.INTEGRATOR_PATH_TRACER, True)
+    np.testing.assert_array_equal(out0, want)
+    np.testing.assert_array_equal(out1, want)
+    assert st0[:2] == st1[:2] and 0 <= info["rays"] - st1[1] <= 0.03 * info["rays"]
+    assert st0[2] == st0[3] == 0 and not any(st0[8:20])
+    check_counter_bounds(img, st1, out1, False)
+    iters, have, in_steps, in_lanes, lf_steps, lf_lanes = st1[8:14]
+    assert 0 < in_steps <= iters and 0 < lf_steps <= iters and in_steps <= in_lanes <= 64 * in_steps and lf_steps <= lf_lanes <= 64 * lf_steps
+    assert in_lanes <= have <= 64 * iters
+    # an inner lane step tests the children of one node: between one and eight boxes
+    assert in_lanes <= st1[2] <= 8 * in_lanes + st1[1]
+
+
+@pytest.mark.parametrize("k", [50, 129])
+def test_raw_knn_launch_on_the_host(pkg, wave_kernel_emu, oracle, manifest, k):
+    """MCRT_WF_PM_EVAL=0: wfKnnKernel<false> (k = 129: with the wide candidate buffer) hands the k photons of a search back and the next
+    shade launch sums them per lane (wfPhotonEstimate) - in the order of the candidate buffer, one after the other, where the evaluating
+    launch adds them by a wave reduction: the same photons, another order of the FP64 sum, so the oracle's frame to 1e-12 and not the
+    evaluating launch's bits. (Until the raw branch met its lanes at MCRT_LOCKSTEP before reading the compacted result this frame was off by
+    per cent here: nothing in the memory model ordered those LDS reads behind the other lanes' writes.)"""
+    img, cam = diagnostic_scene(pkg, oracle, manifest, "hexagon_room_pm")
+    cam.width, cam.height, cam.sqrtspp = SMALL_FRAME
+    want, info = oracle.render(img, cam, manifest["seed"], pkg.INTEGRATOR_PHOTON_MAPPER, k=k)
+    ev, st_ev = emulated_pipeline_frame(wave_kernel_emu, img, cam, manifest["seed"], pkg.INTEGRATOR_PHOTON_MAPPER, None, 1, k)
+    raw, st_raw = emulated_pipeline_frame(wave_kernel_emu, img, cam, manifest["seed"], pkg.INTEGRATOR_PHOTON_MAPPER, None, 0, k)
+    assert st_raw[:2] == st_ev[:2] and st_raw[4] == st_ev[4] > 0
+    rel_raw, rel_ev = np.abs(raw - want) / np.maximum(np.abs(want), 1e-3), np.abs(ev - want) / np.maximum(np.abs(want), 1e-3)
+    print("k = %d: max rel %.3e raw, %.3e evaluating" % (k, rel_raw.max(), rel_ev.max()))
+    assert rel_raw.max() <= 1e-12 and rel_ev.max() <= 1e-12
+
+
+def test_both_walks_of_a_staged_tree_test_the_same_boxes_on_the_host(pkg, wave_kernel_emu, oracle, manifest):
+    """Two implementations of one walk: sceneIntersect (csrc/mcrt_scene.hpp, the wave-synchronous kernel) and the state machine's steps
+    (csrc/mcrt_lanesm.hpp) both go depth first over the exact boxes of an LDS-resident tree, the nearest child first, a leaf tested whole
+    before the next node, and drop a pending node that starts behind the closest hit so far. In a scene without specular materials they
+    trace the same rays (no shadow ray is skipped for a zero BSDF term), so they test the same boxes: PT_CountAll and SM_CountAll agree on
+    node_tests to the last one - each counted in its own source file. (Primitive tests differ: the state machine tests a leaf two
+    primitives at a time.)"""
+    img, cam = diagnostic_scene(pkg, oracle, manifest, "hexagon_room_diffuse")
+    cam.width, cam.height, cam.sqrtspp = FRAME
+    _, sm, inst_sm = emulated_megakernel_frame(pkg, wave_kernel_emu, img, cam, manifest["seed"], pkg.INTEGRATOR_PATH_TRACER, True, False, 0)
+    _, pt, inst_pt = emulated_megakernel_frame(pkg, wave_kernel_emu, img, cam, manifest["seed"], pkg.INTEGRATOR_PATH_TRACER, True, True, 0)
+    assert (inst_sm, inst_pt) == ("SM_CountAll", "PT_CountAll")
+    assert sm[:2] == pt[:2]
+    assert sm[2] == pt[2] > 0, "node tests: state machine %d, wave-synchronous kernel %d" % (sm[2], pt[2])
+    assert 0 < pt[3] <= sm[3] <= 2 * pt[3]
