@@ -25,6 +25,7 @@
 #include "mcrt_aov.hpp"
 #include "mcrt_plan.hpp"
 #include "mcrt_select.hpp"
+#include "mcrt_stats_readout.hpp"
 #include "mcrt_launch.hpp"
 #include "mcrt_octree_shared.hpp"
 #include "mcrt_lean.hpp"
@@ -1153,45 +1154,18 @@ int mcrt_render_finish(mcrt_ctx* ctx, mcrt_stats* stats) {
     if (!ctx) return MCRT_ERR_INVALID;
     if (!ctx->pending) return fail(ctx, MCRT_ERR_INVALID, "no render in flight");
     ctx->pending = false;
+    // (a) wait for the frame, read its statistics words back
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     HIP_TRY(ctx, hipEventSynchronize(ctx->ev1));
     unsigned long long h[kStatsWords];
     HIP_TRY(ctx, hipMemcpy(h, ctx->stats.p, sizeof(h), hipMemcpyDeviceToHost));
-    // Readouts of the words 8.. - only of what the instances that ran measured (noteInstances). The phase clocks, the trace kernel's step
-    // counters and the photon-mapping kernel's estimate clocks share those words: a line is printed for the kernel that wrote them and never
-    // from the option alone (MCRT_PROFILE_PHASES on a form without a profiling instance - pipeline, photon kernels - or next to
-    // MCRT_COUNT_TESTS, which a profiling instance does not carry, used to print another kernel's words as phases), and never with a zero
-    // divisor (a frame whose launches found no work leaves every clock at 0).
-    if (instanceProfiles(ctx->used_instance)) {
-        static const char* names[kNumPhases] = {"regen", "trav/inner", "shade", "shadow/leaf", "sample", "loop"};
-        unsigned long long tw = 0;
-        for (int i = 0; i < kNumPhases; i++) tw += h[8 + i];
-        for (int i = 0; tw && i < kNumPhases; i++)
-            fprintf(stderr, "[mcrt phase] %-9s wave-cycles %6.2f%%  lane utilisation %5.1f%%\n", names[i], 100.0 * h[8 + i] / (double)tw,
-                    h[8 + i] ? 100.0 * h[8 + kNumPhases + i] / (64.0 * h[8 + i]) : 0.0);
-    }
-    if (ctx->kernel_id == MCRT_KERNEL_WAVEFRONT && ctx->used_trace == kInstTrace_Count && h[8] && h[17]) {
-        const double iters = (double)h[8], cyc = (double)h[17], rays = (double)(h[1] ? h[1] : 1);
-        const unsigned long long stepped = std::min(h[15] + h[16], h[17]);
-        fprintf(stderr, "[mcrt trace] per wave iteration: %.1f lanes hold a ray; inner step in %.1f%% of the iterations with %.1f lanes, leaf step in %.1f%% with %.1f lanes, "
-                        "%.1f leaf lanes wait; wave cycles: inner %.1f%%, leaf %.1f%%, rest %.1f%% (of the kernel: refills %.1f%%, pop site %.1f%%); per ray: %.2f inner steps, %.2f leaf steps "
-                        "(%llu inner and %llu leaf lane steps of %llu rays)\n",
-                (double)h[9] / iters, 100.0 * h[10] / iters, h[10] ? (double)h[11] / h[10] : 0.0, 100.0 * h[12] / iters, h[12] ? (double)h[13] / h[12] : 0.0,
-                (double)h[14] / iters, 100.0 * h[15] / cyc, 100.0 * h[16] / cyc, 100.0 * (h[17] - stepped) / cyc, 100.0 * h[18] / cyc, 100.0 * h[19] / cyc,
-                (double)h[11] / rays, (double)h[13] / rays, h[11], h[13], h[1]);
-    }
-    if (ctx->kernel_id == MCRT_KERNEL_PM_WAVE && instanceClocksEstimates(ctx->used_instance) && h[9])
-        fprintf(stderr, "[mcrt pm] wave cycles inside the radiance estimates: %.1f%% of the kernel (%llu searches, %.1f octants per search)\n",
-                100.0 * (double)std::min(h[8], h[9]) / (double)h[9], h[4], h[4] ? (double)h[6] / (double)h[4] : 0.0);
+    // (b) the words -> readouts, counters, outcome: pure functions of them (mcrt_stats_readout.hpp)
+    fputs(statsReadout(h, ctx->used_instance, ctx->used_trace, ctx->kernel_id).c_str(), stderr);
     float ms = 0.f;
     HIP_TRY(ctx, hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
     if (stats) {
         memset(stats, 0, sizeof(*stats));
-        stats->paths = h[0];
-        stats->rays = h[1];
-        stats->node_tests = h[2];
-        stats->prim_tests = h[3];
-        stats->knn_searches = h[4];
+        statsCounters(h, *stats);
         stats->kernel_ms = ms;
         stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - ctx->t_begin).count();
         stats->kernel_launches = ctx->launches;
@@ -1201,18 +1175,15 @@ int mcrt_render_finish(mcrt_ctx* ctx, mcrt_stats* stats) {
     // no tree the tests can build in reasonable time fills 128 + 1 024 frontier entries through the render path, whose record lists
     // are made for the k it searches with)
     const bool pm_wave_frame = ctx->kernel_id == MCRT_KERNEL_PM_WAVE || ctx->kernel_id == MCRT_KERNEL_WAVEFRONT_PM;
-    if (pm_wave_frame && !ctx->force_pm_lane && ctxOptOn(ctx, "MCRT_TEST_KNN_OVERFLOW")) h[5] |= kKnnOverflowFlag;
-    // Done, refused, or rendered again with a flag raised or a capacity grown: nextRender (mcrt_select.hpp) decides. The flags hold
+    if (pm_wave_frame && !ctx->force_pm_lane && ctxOptOn(ctx, "MCRT_TEST_KNN_OVERFLOW")) h[kStatOverflow] |= kKnnOverflowFlag;
+    // (c) Done, refused, or rendered again with a flag raised or a capacity grown: nextRender (mcrt_select.hpp) decides. The flags hold
     // until this frame is delivered or refused; the capacities a scene needed stay with the context.
     RetryState state;
     state.force_wf = ctx->force_wf;
     state.force_pm_lane = ctx->force_pm_lane;
     state.knn_visit_cap = ctx->knn_visit_cap;
     state.iors_depth = ctx->iors_depth;
-    FrameOutcome frame;
-    frame.kernel_id = ctx->kernel_id;
-    frame.overflow = h[5];
-    frame.iors_overflow = h[7] != 0;
+    FrameOutcome frame = statsOutcome(h, ctx->kernel_id);
     frame.splats = filmSplats(ctx->last_cam.film_filter, ctx->last_cam.film_radius);
     frame.can_pipeline = ctx->scene.q_nodes > 0 && (ctx->last_integrator != MCRT_INTEGRATOR_PHOTON_MAPPER || ctx->k_nearest <= waveMaxK(kWaveRowsLarge));
     const RetryStep step = nextRender(state, frame);
@@ -1261,11 +1232,10 @@ int mcrt_emit_photons(mcrt_ctx* ctx, double emissions, double caustic_factor, ui
 }  // extern "C"
 
 namespace {
-// The emission pass; the lists stay in ctx->emit_photons / emit_keys. h = the kernel's counters ([1] global, [2] caustic
-// photons, [3] paths, [4] rays).
+// The emission pass; the lists stay in ctx->emit_photons / emit_keys. h = the kernel's counters (kEmit*, mcrt_stats_words.hpp).
 int emitOnDevice(mcrt_ctx* ctx, double emissions, double caustic_factor, uint32_t global_seed, uint32_t shard_index, uint32_t shard_count,
-                 unsigned long long h[8], float& ms) {
-    for (int i = 0; i < 8; i++) h[i] = 0ull;
+                 unsigned long long h[kEmitWords], float& ms) {
+    for (int i = 0; i < kEmitWords; i++) h[i] = 0ull;
     ms = 0.f;
     if (shard_count == 0 || shard_index >= shard_count) return fail(ctx, MCRT_ERR_INVALID, "shard_index >= shard_count");
     if (!ctx->has_scene) return fail(ctx, MCRT_ERR_NO_SCENE, "mcrt_emit_photons before mcrt_upload_scene");
@@ -1285,7 +1255,7 @@ int emitOnDevice(mcrt_ctx* ctx, double emissions, double caustic_factor, uint32_
     const unsigned long long total = shard_end - shard_begin;  // paths of this shard
     if (int rc = uploadArray(ctx, ctx->emit_first, first.data(), first.size())) return rc;
     if (int rc = uploadArray(ctx, ctx->emit_flux, pflux.data(), pflux.size())) return rc;
-    if (!ctx->emit_counters.p) HIP_TRY(ctx, ctx->emit_counters.alloc(8 * sizeof(unsigned long long)));
+    if (!ctx->emit_counters.p) HIP_TRY(ctx, ctx->emit_counters.alloc(kEmitWords * sizeof(unsigned long long)));
 
     noteInstances(ctx, ctx->scene.stage_all ? kInstEmit_All : kInstEmit, leanScene(ctx->facts, parseRenderOptions(ctx->options)));
     auto kernel = kernelAs<void (*)(const DeviceScene, const EmitParams)>(instanceAddress(ctx->scene.stage_all ? kInstEmit_All : kInstEmit, ctx->lean_used));
@@ -1319,25 +1289,25 @@ int emitOnDevice(mcrt_ctx* ctx, double emissions, double caustic_factor, uint32_
                        global_seed, caustic_factor, lists, keys, counting ? none : cap, ctx->emit_counters.as<unsigned long long>(),
                        ctx->spill.as<StackEntry>(), g.total_lanes);
         const uint32_t grid = (uint32_t)std::min<unsigned long long>(g.grid, (total + kBlock - 1) / kBlock + 1);
-        HIP_TRY(ctx, hipMemsetAsync(ctx->emit_counters.p, 0, 8 * sizeof(unsigned long long), ctx->stream));
+        HIP_TRY(ctx, hipMemsetAsync(ctx->emit_counters.p, 0, kEmitWords * sizeof(unsigned long long), ctx->stream));
         HIP_TRY(ctx, hipEventRecord(ctx->ev0, ctx->stream));
         hipLaunchKernelGGL(kernel, dim3(grid), dim3(kBlock), g.lds_bytes, ctx->stream, scene, prm);
         HIP_TRY(ctx, hipGetLastError());
         HIP_TRY(ctx, hipEventRecord(ctx->ev1, ctx->stream));
         HIP_TRY(ctx, hipEventSynchronize(ctx->ev1));
-        HIP_TRY(ctx, hipMemcpy(h, ctx->emit_counters.p, 8 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+        HIP_TRY(ctx, hipMemcpy(h, ctx->emit_counters.p, kEmitWords * sizeof(unsigned long long), hipMemcpyDeviceToHost));
         HIP_TRY(ctx, hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
-        if (h[5]) return fail(ctx, MCRT_ERR_UNSUPPORTED, "traversal stack overflow in the emission pass");
+        if (h[kEmitOverflow]) return fail(ctx, MCRT_ERR_UNSUPPORTED, "traversal stack overflow in the emission pass");
         // RefractionHistory (ray.cpp:74-98) is unbounded in the reference; the emission kernel keeps kMaxIors (8) entries per lane. The eye
         // pass of such a scene retries through the 32-entry pool or fails (mcrt_render_finish); the photon pass must not be the silent one.
-        if (h[6]) return fail(ctx, MCRT_ERR_UNSUPPORTED, "a photon path entered more than 8 nested dielectric media (RefractionHistory, ray.cpp:74-98, is kept to 8 entries per lane in the emission pass)");
+        if (h[kEmitIorsOverflow]) return fail(ctx, MCRT_ERR_UNSUPPORTED, "a photon path entered more than 8 nested dielectric media (RefractionHistory, ray.cpp:74-98, is kept to 8 entries per lane in the emission pass)");
         if (counting) {
-            for (int w = 0; w < 2; w++) cap[w] = (unsigned long long)((double)h[1 + w] * kPilotStride * 1.05) + (1ull << 16);
+            for (int w = 0; w < 2; w++) cap[w] = (unsigned long long)((double)h[kEmitGlobalCount + w] * kPilotStride * 1.05) + (1ull << 16);
             continue;
         }
-        if (h[1] <= cap[0] && h[2] <= cap[1]) break;
-        cap[0] = std::max(cap[0], h[1]);  // a list was too small: size it exactly and emit again
-        cap[1] = std::max(cap[1], h[2]);
+        if (h[kEmitGlobalCount] <= cap[0] && h[kEmitCausticCount] <= cap[1]) break;
+        cap[0] = std::max(cap[0], h[kEmitGlobalCount]);  // a list was too small: size it exactly and emit again
+        cap[1] = std::max(cap[1], h[kEmitCausticCount]);
         if (attempt == 2) return fail(ctx, MCRT_ERR_HIP, "photon lists kept overflowing");
     }
     return MCRT_OK;
@@ -1351,11 +1321,11 @@ int mcrt_emit_photons_shard(mcrt_ctx* ctx, double emissions, double caustic_fact
     if (!ctx) return MCRT_ERR_INVALID;
     if (!out) return fail(ctx, MCRT_ERR_INVALID, "out is NULL");
     memset(out, 0, sizeof(*out));
-    unsigned long long h[8];
+    unsigned long long h[kEmitWords];
     float ms = 0.f;
     if (int rc = emitOnDevice(ctx, emissions, caustic_factor, global_seed, shard_index, shard_count, h, ms)) return rc;
     for (int w = 0; w < 2; w++) {
-        const size_t n = (size_t)h[1 + w];
+        const size_t n = (size_t)h[kEmitGlobalCount + w];
         ctx->host_photons[w].resize(n * 8);
         ctx->host_keys[w].resize(n);
         if (n) {
@@ -1363,14 +1333,14 @@ int mcrt_emit_photons_shard(mcrt_ctx* ctx, double emissions, double caustic_fact
             HIP_TRY(ctx, hipMemcpy(ctx->host_keys[w].data(), ctx->emit_keys[w].p, n * 8, hipMemcpyDeviceToHost));
         }
     }
-    out->global_count = h[1];
-    out->caustic_count = h[2];
+    out->global_count = h[kEmitGlobalCount];
+    out->caustic_count = h[kEmitCausticCount];
     out->global_photons = ctx->host_photons[0].data();
     out->caustic_photons = ctx->host_photons[1].data();
     out->global_keys = ctx->host_keys[0].data();
     out->caustic_keys = ctx->host_keys[1].data();
-    out->emission_paths = h[3];
-    out->rays = h[4];
+    out->emission_paths = h[kEmitPaths];
+    out->rays = h[kEmitRays];
     out->kernel_ms = ms;
     return MCRT_OK;
 }
@@ -1380,15 +1350,15 @@ int mcrt_emit_photons_device(mcrt_ctx* ctx, double emissions, double caustic_fac
     if (!ctx) return MCRT_ERR_INVALID;
     if (!out) return fail(ctx, MCRT_ERR_INVALID, "out is NULL");
     memset(out, 0, sizeof(*out));
-    unsigned long long h[8];
+    unsigned long long h[kEmitWords];
     float ms = 0.f;
     if (int rc = emitOnDevice(ctx, emissions, caustic_factor, global_seed, shard_index, shard_count, h, ms)) return rc;
-    out->global_count = h[1];
-    out->caustic_count = h[2];
+    out->global_count = h[kEmitGlobalCount];
+    out->caustic_count = h[kEmitCausticCount];
     out->d_global_photons = ctx->emit_photons[0].as<float>();
     out->d_caustic_photons = ctx->emit_photons[1].as<float>();
-    out->emission_paths = h[3];
-    out->rays = h[4];
+    out->emission_paths = h[kEmitPaths];
+    out->rays = h[kEmitRays];
     out->kernel_ms = ms;
     return MCRT_OK;
 }
@@ -1536,7 +1506,7 @@ int intersectDeviceArrays(mcrt_ctx* ctx, uint64_t n, const double* d_start, cons
         }
         unsigned long long h[kStatsWords];
         HIP_TRY(ctx, hipMemcpy(h, ctx->stats.p, sizeof(h), hipMemcpyDeviceToHost));
-        if (h[5]) return fail(ctx, MCRT_ERR_UNSUPPORTED, "traversal stack overflow (internal error: the stacks are sized to the tree's own bound, HostLayout::stack_bound)");
+        if (h[kStatOverflow]) return fail(ctx, MCRT_ERR_UNSUPPORTED, "traversal stack overflow (internal error: the stacks are sized to the tree's own bound, HostLayout::stack_bound)");
         return MCRT_OK;
     }
     LaunchGeom g;

@@ -9,6 +9,7 @@
 #pragma once
 
 #include "mcrt_shade.hpp"
+#include "mcrt_stats_words.hpp"
 
 namespace mcrt {
 
@@ -21,8 +22,7 @@ struct PathState {
 
 // Optional phase profiler (MCRT_PROFILE_PHASES=1 selects the instrumented kernel): per phase, the
 // wave-cycles spent (accumulated by the first active lane) and the lane-cycles spent (every active
-// lane), whose ratio is the SIMD lane utilisation of that phase.
-enum : int { kPhRegen = 0, kPhTraverse = 1, kPhShade = 2, kPhShadow = 3, kPhSample = 4, kPhLoop = 5, kNumPhases = 6 };
+// lane), whose ratio is the SIMD lane utilisation of that phase. The phases, kPhRegen .. kPhLoop, are named in mcrt_stats_words.hpp.
 template <bool kProf>
 struct PhaseProf {
     MCRT_HD void mark(int) {}

@@ -65,7 +65,7 @@ struct RenderParams {
     uint32_t tiles_x, tiles_y;
     uint64_t work_items;  // tiles_x * tiles_y * 64
     unsigned long long* work_counter;
-    unsigned long long* stats;  // paths, rays, node_tests, prim_tests, knn_searches, overflow, knn_octants
+    unsigned long long* stats;  // [kStatsWords], mcrt_stats_words.hpp: paths, rays, node_tests, prim_tests, knn_searches, overflow, knn_octants, iors_overflow; then the overlays
     StackEntry* spill;
     uint32_t total_lanes;
     uint32_t knn_max_visit;  // per-lane photon search: frontier entries per lane (KnnScratch::max_visit; in the padding before the maps)
@@ -114,10 +114,6 @@ __device__ inline void storeSample(const RenderParams& prm, uint32_t sample, uin
 // ------------------------------------------------------------------------------------------------
 // LDS carving
 // ------------------------------------------------------------------------------------------------
-constexpr uint32_t kStatsWords = 8 + 2 * kNumPhases;
-// stats[5] counts two things the host tells apart: lanes whose traversal stack overflowed (one each; cannot happen - the stacks are sized
-// to the tree's own bound) and searches whose kNN frontier did (kKnnOverflowFlag and above: octrees with leaves far smaller than k)
-constexpr unsigned long long kKnnOverflowUnit = 1ull << 32;
 constexpr uint32_t kBlock = 512;  // 8 waves per workgroup, one workgroup per CU (LDS-bound, see planLds)
 
 constexpr uint32_t kPmLdsIors = 2;  // refraction-history entries per lane the 1024-lane photon-mapping kernel keeps in LDS
@@ -171,6 +167,54 @@ __device__ inline MCRT_LDS_AS T* ldsAt(unsigned char* base, uint32_t off) {
 template <class T>
 __device__ inline void stageCopy(MCRT_LDS_AS T* dst, const T* src, uint32_t count) {
     for (uint32_t i = threadIdx.x; i < count; i += blockDim.x) dst[i] = src[i];
+}
+
+// The shading arrays of an LDS-resident scene, staged at the offsets of the workgroup's plan (LdsPlan / SmLdsPlan: the same member names);
+// the caller ends its staging with __syncthreads().
+template <class Plan>
+__device__ __forceinline__ void stageShading(const DeviceScene& s, unsigned char* lds, const Plan& p, ShadeViewT<true>& sh) {
+    const uint32_t ns = s.num_surfaces;
+    MCRT_LDS_AS double* lv = ldsAt<double>(lds, p.surf_v);
+    stageCopy(lv, s.surf_v, ns * 9);
+    sh.surf_v = lv;
+    MCRT_LDS_AS double* ln = ldsAt<double>(lds, p.surf_normal);
+    stageCopy(ln, s.surf_normal, ns * 3);
+    sh.surf_normal = ln;
+    sh.surf_rec = nullptr;
+    MCRT_LDS_AS double* lvn = ldsAt<double>(lds, p.surf_vn);
+    if (s.surf_vn) stageCopy(lvn, s.surf_vn, ns * 9);
+    sh.surf_vn = lvn;
+    MCRT_LDS_AS double* la = ldsAt<double>(lds, p.surf_area);
+    stageCopy(la, s.surf_area, ns);
+    sh.surf_area = la;
+    MCRT_LDS_AS uint32_t* lm = ldsAt<uint32_t>(lds, p.surf_material);
+    stageCopy(lm, s.surf_material, ns);
+    sh.surf_material = lm;
+    MCRT_LDS_AS uint8_t* lk = ldsAt<uint8_t>(lds, p.surf_kind);
+    stageCopy(lk, s.surf_kind, ns);
+    sh.surf_kind = lk;
+    MCRT_LDS_AS uint64_t* lmat = ldsAt<uint64_t>(lds, p.materials);
+    stageCopy(lmat, reinterpret_cast<const uint64_t*>(s.materials), s.num_materials * (uint32_t)(sizeof(mcrt_material) / 8));
+    sh.materials = (MCRT_LDS_AS const mcrt_material*)lmat;
+    MCRT_LDS_AS double* lc = ldsAt<double>(lds, p.light_cdf);
+    stageCopy(lc, s.light_cdf, s.num_lights);
+    sh.light_cdf = lc;
+    MCRT_LDS_AS uint32_t* ll = ldsAt<uint32_t>(lds, p.light_surface);
+    stageCopy(ll, s.light_surface, s.num_lights);
+    sh.light_surface = ll;
+}
+// ... of a scene whose shading arrays stay in memory
+__device__ __forceinline__ void shadeFromMemory(const DeviceScene& s, ShadeViewT<false>& sh) {
+    sh.surf_v = s.surf_v;
+    sh.surf_normal = s.surf_normal;
+    sh.surf_rec = s.surf_rec;
+    sh.surf_vn = s.surf_vn;
+    sh.surf_area = s.surf_area;
+    sh.surf_material = s.surf_material;
+    sh.surf_kind = s.surf_kind;
+    sh.materials = s.materials;
+    sh.light_surface = s.light_surface;
+    sh.light_cdf = s.light_cdf;
 }
 
 // Builds the per-lane views; stages the scene into LDS (ends with __syncthreads()).
@@ -244,34 +288,7 @@ __device__ inline void setupViews(const DeviceScene& s, unsigned char* lds, Scen
             stageCopy(lfi, s.flat_index, ns);
             sv.flat_index = lfi;
         }
-        MCRT_LDS_AS double* lv = ldsAt<double>(lds, p.surf_v);
-        stageCopy(lv, s.surf_v, ns * 9);
-        sh.surf_v = lv;
-        MCRT_LDS_AS double* ln = ldsAt<double>(lds, p.surf_normal);
-        stageCopy(ln, s.surf_normal, ns * 3);
-        sh.surf_normal = ln;
-        sh.surf_rec = nullptr;
-        MCRT_LDS_AS double* lvn = ldsAt<double>(lds, p.surf_vn);
-        if (s.surf_vn) stageCopy(lvn, s.surf_vn, ns * 9);
-        sh.surf_vn = lvn;
-        MCRT_LDS_AS double* la = ldsAt<double>(lds, p.surf_area);
-        stageCopy(la, s.surf_area, ns);
-        sh.surf_area = la;
-        MCRT_LDS_AS uint32_t* lm = ldsAt<uint32_t>(lds, p.surf_material);
-        stageCopy(lm, s.surf_material, ns);
-        sh.surf_material = lm;
-        MCRT_LDS_AS uint8_t* lk = ldsAt<uint8_t>(lds, p.surf_kind);
-        stageCopy(lk, s.surf_kind, ns);
-        sh.surf_kind = lk;
-        MCRT_LDS_AS uint64_t* lmat = ldsAt<uint64_t>(lds, p.materials);
-        stageCopy(lmat, reinterpret_cast<const uint64_t*>(s.materials), s.num_materials * (uint32_t)(sizeof(mcrt_material) / 8));
-        sh.materials = (MCRT_LDS_AS const mcrt_material*)lmat;
-        MCRT_LDS_AS double* lc = ldsAt<double>(lds, p.light_cdf);
-        stageCopy(lc, s.light_cdf, s.num_lights);
-        sh.light_cdf = lc;
-        MCRT_LDS_AS uint32_t* ll = ldsAt<uint32_t>(lds, p.light_surface);
-        stageCopy(ll, s.light_surface, s.num_lights);
-        sh.light_surface = ll;
+        stageShading(s, lds, p, sh);
     } else {
         sv.node_bounds = s.node_bounds;
         sv.node_meta = s.node_meta;
@@ -282,16 +299,7 @@ __device__ inline void setupViews(const DeviceScene& s, unsigned char* lds, Scen
         sv.flat_pre = nullptr;
         sv.pre_tri_pairs = sv.pre_sph_pairs = 0;
         sv.pre_cx = sv.pre_cy = sv.pre_cz = sv.pre_bound = 0.0;
-        sh.surf_v = s.surf_v;
-        sh.surf_normal = s.surf_normal;
-        sh.surf_rec = s.surf_rec;
-        sh.surf_vn = s.surf_vn;
-        sh.surf_area = s.surf_area;
-        sh.surf_material = s.surf_material;
-        sh.surf_kind = s.surf_kind;
-        sh.materials = s.materials;
-        sh.light_surface = s.light_surface;
-        sh.light_cdf = s.light_cdf;
+        shadeFromMemory(s, sh);
     }
     __syncthreads();
 }
@@ -375,6 +383,9 @@ __device__ __forceinline__ void renderKernelBody(const DeviceScene& scene, const
 
     for (;;) {
         if (kProf) prof.mark(kPhLoop);
+        // The work claim (wavePop -> decodeUnit -> arm the pixel) is written out in renderKernelSM and renderKernelPM too, like the
+        // epilogues, ON PURPOSE: folded into a helper - early return or the out-of-work action as a lambda - all 31 megakernel instances
+        // get other code (order, registers, the photon-mapping kernels' spills: profiles/NOTES_stats_words.md).
         const bool need = !have_pixel && !exhausted;
         if (waveBallot(need)) {
             const unsigned long long w = wavePop(need, prm.work_counter);
@@ -421,22 +432,22 @@ __device__ __forceinline__ void renderKernelBody(const DeviceScene& scene, const
         }
     }
 
-    waveAccumulate(prm.stats + 0, paths);
-    waveAccumulate(prm.stats + 1, cnt.rays);
+    waveAccumulate(prm.stats + kStatPaths, paths);
+    waveAccumulate(prm.stats + kStatRays, cnt.rays);
     if (kCount) {
-        waveAccumulate(prm.stats + 2, cnt.node_tests);
-        waveAccumulate(prm.stats + 3, cnt.prim_tests);
+        waveAccumulate(prm.stats + kStatNodeTests, cnt.node_tests);
+        waveAccumulate(prm.stats + kStatPrimTests, cnt.prim_tests);
     }
-    waveAccumulate(prm.stats + 4, searches);
-    if constexpr (kIntegrator == MCRT_INTEGRATOR_PHOTON_MAPPER) waveAccumulate(prm.stats + 5, cnt.overflow | ks.overflowed);  // (a search that ran out of frontier)
-    else waveAccumulate(prm.stats + 5, cnt.overflow);
-    waveAccumulate(prm.stats + 7, rh.overflow ? 1u : 0u);
-    waveAccumulate(prm.stats + 6, octant_visits);
+    waveAccumulate(prm.stats + kStatKnnSearches, searches);
+    if constexpr (kIntegrator == MCRT_INTEGRATOR_PHOTON_MAPPER) waveAccumulate(prm.stats + kStatOverflow, cnt.overflow | ks.overflowed);  // (a search that ran out of frontier)
+    else waveAccumulate(prm.stats + kStatOverflow, cnt.overflow);
+    waveAccumulate(prm.stats + kStatIorsOverflow, rh.overflow ? 1u : 0u);
+    waveAccumulate(prm.stats + kStatKnnOctants, octant_visits);
     if constexpr (kProf) {
         prof.mark(kPhLoop);
         for (int i = 0; i < kNumPhases; i++) {
-            atomicAdd(prm.stats + 8 + i, prof.wave_cycles[i]);
-            atomicAdd(prm.stats + 8 + kNumPhases + i, prof.lane_cycles[i]);
+            atomicAdd(prm.stats + kStatPhaseWave + i, prof.wave_cycles[i]);
+            atomicAdd(prm.stats + kStatPhaseLane + i, prof.lane_cycles[i]);
         }
     }
 }
@@ -549,47 +560,11 @@ __global__ void __launch_bounds__(kLanes) renderKernelSM(const DeviceScene scene
         MCRT_LDS_AS double* lp = ldsAt<double>(lds, p.prim);
         stageCopy(lp, scene.prim, ns * kPrimStride);
         sv.prim = lp;
-        MCRT_LDS_AS double* lv = ldsAt<double>(lds, p.surf_v);
-        stageCopy(lv, scene.surf_v, ns * 9);
-        sh.surf_v = lv;
-        MCRT_LDS_AS double* ln = ldsAt<double>(lds, p.surf_normal);
-        stageCopy(ln, scene.surf_normal, ns * 3);
-        sh.surf_normal = ln;
-        sh.surf_rec = nullptr;
-        MCRT_LDS_AS double* lvn = ldsAt<double>(lds, p.surf_vn);
-        if (scene.surf_vn) stageCopy(lvn, scene.surf_vn, ns * 9);
-        sh.surf_vn = lvn;
-        MCRT_LDS_AS double* la = ldsAt<double>(lds, p.surf_area);
-        stageCopy(la, scene.surf_area, ns);
-        sh.surf_area = la;
-        MCRT_LDS_AS uint32_t* lm = ldsAt<uint32_t>(lds, p.surf_material);
-        stageCopy(lm, scene.surf_material, ns);
-        sh.surf_material = lm;
-        MCRT_LDS_AS uint8_t* lk = ldsAt<uint8_t>(lds, p.surf_kind);
-        stageCopy(lk, scene.surf_kind, ns);
-        sh.surf_kind = lk;
-        MCRT_LDS_AS uint64_t* lmat = ldsAt<uint64_t>(lds, p.materials);
-        stageCopy(lmat, reinterpret_cast<const uint64_t*>(scene.materials), scene.num_materials * (uint32_t)(sizeof(mcrt_material) / 8));
-        sh.materials = (MCRT_LDS_AS const mcrt_material*)lmat;
-        MCRT_LDS_AS double* lc = ldsAt<double>(lds, p.light_cdf);
-        stageCopy(lc, scene.light_cdf, scene.num_lights);
-        sh.light_cdf = lc;
-        MCRT_LDS_AS uint32_t* ll = ldsAt<uint32_t>(lds, p.light_surface);
-        stageCopy(ll, scene.light_surface, scene.num_lights);
-        sh.light_surface = ll;
+        stageShading(scene, lds, p, sh);
     } else {
         sv.nodes = scene.nodes64;
         sv.prim = scene.prim;
-        sh.surf_v = scene.surf_v;
-        sh.surf_normal = scene.surf_normal;
-        sh.surf_rec = scene.surf_rec;
-        sh.surf_vn = scene.surf_vn;
-        sh.surf_area = scene.surf_area;
-        sh.surf_material = scene.surf_material;
-        sh.surf_kind = scene.surf_kind;
-        sh.materials = scene.materials;
-        sh.light_surface = scene.light_surface;
-        sh.light_cdf = scene.light_cdf;
+        shadeFromMemory(scene, sh);
     }
     __syncthreads();
 
@@ -721,18 +696,18 @@ __global__ void __launch_bounds__(kLanes) renderKernelSM(const DeviceScene scene
         }
     }
 
-    waveAccumulate(prm.stats + 0, paths);
-    waveAccumulate(prm.stats + 1, cnt.rays);
+    waveAccumulate(prm.stats + kStatPaths, paths);
+    waveAccumulate(prm.stats + kStatRays, cnt.rays);
     if (kCount) {
-        waveAccumulate(prm.stats + 2, cnt.node_tests);
-        waveAccumulate(prm.stats + 3, cnt.prim_tests);
+        waveAccumulate(prm.stats + kStatNodeTests, cnt.node_tests);
+        waveAccumulate(prm.stats + kStatPrimTests, cnt.prim_tests);
     }
-    waveAccumulate(prm.stats + 5, cnt.overflow);
-    waveAccumulate(prm.stats + 7, rh.overflow ? 1u : 0u);
+    waveAccumulate(prm.stats + kStatOverflow, cnt.overflow);
+    waveAccumulate(prm.stats + kStatIorsOverflow, rh.overflow ? 1u : 0u);
     if constexpr (kProf) {
         for (int i = 0; i < kNumPhases; i++) {
-            atomicAdd(prm.stats + 8 + i, prof.wave_cycles[i]);
-            atomicAdd(prm.stats + 8 + kNumPhases + i, prof.lane_cycles[i]);
+            atomicAdd(prm.stats + kStatPhaseWave + i, prof.wave_cycles[i]);
+            atomicAdd(prm.stats + kStatPhaseLane + i, prof.lane_cycles[i]);
         }
     }
 }
@@ -970,25 +945,25 @@ __global__ void __launch_bounds__(kTraceMaxBlock) wfTraceKernel(const WfTraceArg
         }
     }
     if (kCount && laneId() == 0) {
-        atomicAdd(a.stats + 8, ph_iter);
-        atomicAdd(a.stats + 9, ph_have);
-        atomicAdd(a.stats + 10, ph_in_steps);
-        atomicAdd(a.stats + 11, ph_in_lanes);
-        atomicAdd(a.stats + 12, ph_lf_steps);
-        atomicAdd(a.stats + 13, ph_lf_lanes);
-        atomicAdd(a.stats + 14, ph_lf_wait);
-        atomicAdd(a.stats + 15, ph_in_cyc);
-        atomicAdd(a.stats + 16, ph_lf_cyc);
-        atomicAdd(a.stats + 17, (unsigned long long)(clock64() - ph_begin));
-        atomicAdd(a.stats + 18, ph_refill_cyc);
-        atomicAdd(a.stats + 19, ph_pop_cyc);
+        atomicAdd(a.stats + kStatTraceIters, ph_iter);
+        atomicAdd(a.stats + kStatTraceHave, ph_have);
+        atomicAdd(a.stats + kStatTraceInnerSteps, ph_in_steps);
+        atomicAdd(a.stats + kStatTraceInnerLanes, ph_in_lanes);
+        atomicAdd(a.stats + kStatTraceLeafSteps, ph_lf_steps);
+        atomicAdd(a.stats + kStatTraceLeafLanes, ph_lf_lanes);
+        atomicAdd(a.stats + kStatTraceLeafWait, ph_lf_wait);
+        atomicAdd(a.stats + kStatTraceInnerCycles, ph_in_cyc);
+        atomicAdd(a.stats + kStatTraceLeafCycles, ph_lf_cyc);
+        atomicAdd(a.stats + kStatTraceKernelCycles, (unsigned long long)(clock64() - ph_begin));
+        atomicAdd(a.stats + kStatTraceRefillCycles, ph_refill_cyc);
+        atomicAdd(a.stats + kStatTracePopCycles, ph_pop_cyc);
     }
-    waveAccumulate(a.stats + 1, cnt.rays);
+    waveAccumulate(a.stats + kStatRays, cnt.rays);
     if (kCount) {
-        waveAccumulate(a.stats + 2, cnt.node_tests);
-        waveAccumulate(a.stats + 3, cnt.prim_tests);
+        waveAccumulate(a.stats + kStatNodeTests, cnt.node_tests);
+        waveAccumulate(a.stats + kStatPrimTests, cnt.prim_tests);
     }
-    waveAccumulate(a.stats + 5, cnt.overflow);
+    waveAccumulate(a.stats + kStatOverflow, cnt.overflow);
 }
 
 struct WfShadeArgs {
@@ -1151,8 +1126,8 @@ __global__ void __launch_bounds__(kWfBlock) __attribute__((amdgpu_waves_per_eu(3
     DevWfEnv env{a.work, a.queue, a.count_out, a.requests, a.rcount_out, a.stage, sh.materials, scene.materials};
     uint32_t paths = 0;
     wfShadeSlot<false, kPhoton>(env, a.pool, slot, fw, a.fr, sh, rh, (SobolTab)ltab, paths, &a.pm);
-    waveAccumulate(a.stats + 0, paths);
-    waveAccumulate(a.stats + 7, rh.overflow ? 1u : 0u);
+    waveAccumulate(a.stats + kStatPaths, paths);
+    waveAccumulate(a.stats + kStatIorsOverflow, rh.overflow ? 1u : 0u);
 }
 
 // The per-sample store of renderKernel / renderKernelSM -> image: rgb_sum += radiance * 1 in sample order (Film::deposit /
@@ -1279,9 +1254,9 @@ __global__ void __launch_bounds__(256) MCRT_KNN_OCC wfKnnKernel(const WfKnnArgs 
         }
     }
     if (lane == 0) {
-        if (searches) atomicAdd(a.stats + 4, (unsigned long long)searches);
-        if (visits) atomicAdd(a.stats + 6, (unsigned long long)visits);
-        if (overflow) atomicAdd(a.stats + 5, kKnnOverflowUnit);
+        if (searches) atomicAdd(a.stats + kStatKnnSearches, (unsigned long long)searches);
+        if (visits) atomicAdd(a.stats + kStatKnnOctants, (unsigned long long)visits);
+        if (overflow) atomicAdd(a.stats + kStatOverflow, kKnnOverflowUnit);
     }
 }
 
@@ -1484,22 +1459,22 @@ __global__ void __launch_bounds__(kLanes) renderKernelPM(const DeviceScene scene
             if (++sample == sample_end) have_pixel = false;
         }
     }
-    waveAccumulate(prm.stats + 0, paths);
-    waveAccumulate(prm.stats + 1, cnt.rays);
+    waveAccumulate(prm.stats + kStatPaths, paths);
+    waveAccumulate(prm.stats + kStatRays, cnt.rays);
     if (kCount) {
-        waveAccumulate(prm.stats + 2, cnt.node_tests);
-        waveAccumulate(prm.stats + 3, cnt.prim_tests);
+        waveAccumulate(prm.stats + kStatNodeTests, cnt.node_tests);
+        waveAccumulate(prm.stats + kStatPrimTests, cnt.prim_tests);
     }
-    waveAccumulate(prm.stats + 4, searches);
+    waveAccumulate(prm.stats + kStatKnnSearches, searches);
     // (one word for both overflows, as in round 4: lanes whose traversal stack overflowed count 1 each, a search whose frontier overflowed
     // sets kKnnOverflowFlag - the host reads the bits above 15. Two separate additions here cost C5 9 % of a frame: this kernel's
     // register allocation - 128 VGPRs, ~700 spilled - turns on such things, profiles/r05_ab_c5_bisect.log)
-    waveAccumulate(prm.stats + 5, cnt.overflow | knn_overflow);
-    waveAccumulate(prm.stats + 7, rh.overflow ? 1u : 0u);
-    waveAccumulate(prm.stats + 6, octant_visits);
+    waveAccumulate(prm.stats + kStatOverflow, cnt.overflow | knn_overflow);
+    waveAccumulate(prm.stats + kStatIorsOverflow, rh.overflow ? 1u : 0u);
+    waveAccumulate(prm.stats + kStatKnnOctants, octant_visits);
     if (kCount && __lane_id() == 0) {
-        atomicAdd(prm.stats + 8, cyc_est);
-        atomicAdd(prm.stats + 9, (unsigned long long)(clock64() - cyc_begin));
+        atomicAdd(prm.stats + kStatPmEstimateCycles, cyc_est);
+        atomicAdd(prm.stats + kStatPmKernelCycles, (unsigned long long)(clock64() - cyc_begin));
     }
 }
 
@@ -1619,7 +1594,7 @@ struct EmitParams {
     float* photons[2];                      // 0 global, 1 caustic: [capacity][8]
     unsigned long long* keys[2];
     unsigned long long capacity[2];
-    unsigned long long* counters;           // [0] work, [1] global count, [2] caustic count, [3] paths, [4] rays, [5] overflow
+    unsigned long long* counters;           // [kEmitWords], mcrt_stats_words.hpp: work, global count, caustic count, paths, rays, stack overflow, refraction-history overflow
     StackEntry* spill;
     uint32_t total_lanes;
 };
@@ -1646,7 +1621,7 @@ __global__ void __launch_bounds__(kBlock) emitKernel(const DeviceScene scene, co
     for (;;) {
         const bool need = !active && !exhausted;
         if (waveBallot(need)) {
-            const unsigned long long e = prm.first_emission + wavePop(need, prm.counters + 0) * prm.stride;
+            const unsigned long long e = prm.first_emission + wavePop(need, prm.counters + kEmitWork) * prm.stride;
             if (need) {
                 if (e >= prm.total_emissions) {
                     exhausted = true;
@@ -1686,7 +1661,7 @@ __global__ void __launch_bounds__(kBlock) emitKernel(const DeviceScene scene, co
         for (int which = 0; which < 2; which++) {
             const bool mine = out.store && (out.caustic == (which == 1));
             if (waveBallot(mine)) {
-                const unsigned long long slot = waveAppend(mine, prm.counters + 1 + which);
+                const unsigned long long slot = waveAppend(mine, prm.counters + kEmitGlobalCount + which);
                 if (mine && slot < prm.capacity[which]) {
                     float* o = prm.photons[which] + slot * 8ull;
                     for (int k = 0; k < 8; k++) o[k] = out.rec[k];
@@ -1695,10 +1670,10 @@ __global__ void __launch_bounds__(kBlock) emitKernel(const DeviceScene scene, co
             }
         }
     }
-    waveAccumulate(prm.counters + 3, paths);
-    waveAccumulate(prm.counters + 4, cnt.rays);
-    waveAccumulate(prm.counters + 5, cnt.overflow);
-    waveAccumulate(prm.counters + 6, rh.overflow ? 1u : 0u);  // a photon path nested deeper than the kMaxIors media a lane keeps (mcrt_emit_photons*: an error, not a silent wrong medium)
+    waveAccumulate(prm.counters + kEmitPaths, paths);
+    waveAccumulate(prm.counters + kEmitRays, cnt.rays);
+    waveAccumulate(prm.counters + kEmitOverflow, cnt.overflow);
+    waveAccumulate(prm.counters + kEmitIorsOverflow, rh.overflow ? 1u : 0u);  // a photon path nested deeper than the kMaxIors media a lane keeps (mcrt_emit_photons*: an error, not a silent wrong medium)
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -12,6 +12,7 @@
 
 #include "../../include/mcrt.h"
 #include "mcrt_plan.hpp"
+#include "mcrt_stats_words.hpp"
 
 namespace mcrt {
 
@@ -30,6 +31,7 @@ constexpr uint32_t kSelFlatArgFloats = 704;   // kFlatPreArgFloats
 constexpr uint32_t kSelVisit = 160;           // kMaxVisit
 constexpr uint32_t kSelVisitLimit = 1u << 15; // kMaxVisitLimit
 constexpr uint64_t kSelKnnOverflow = 0x10000u;  // kKnnOverflowFlag
+static_assert(kSelKnnOverflow == kStatKnnOverflowBit && kKnnOverflowUnit >= kSelKnnOverflow, "the overflow word, mcrt_stats_words.hpp");
 constexpr uint32_t kSelLeanFeaturesOff = (1u << 0) | (1u << 1) | (1u << 6);  // MCRT_LEAN_FEATURES_OFF
 
 // ------------------------------------------------------------------------------------------------
@@ -357,8 +359,8 @@ struct RetryState {  // what of the context decides how the frame is rendered ag
 
 struct FrameOutcome {
     uint32_t kernel_id = MCRT_KERNEL_NONE;  // the form that rendered the frame
-    uint64_t overflow = 0;       // stats word 5: traversal-stack overflows, kSelKnnOverflow and above: a kNN frontier overflowed
-    bool iors_overflow = false;  // stats word 7: a path nested deeper than its refraction history holds
+    uint64_t overflow = 0;       // the word kStatOverflow: statsStackOverflows / statsKnnOverflowed (mcrt_stats_words.hpp)
+    bool iors_overflow = false;  // the word kStatIorsOverflow: a path nested deeper than its refraction history holds
     bool splats = false;         // (only the pipeline splats: no second kernel for such a frame)
     bool can_pipeline = false;   // the scene has a tree and, photon-mapped, k fits the widest per-wave buffer
 };
@@ -384,7 +386,7 @@ inline RetryStep nextRender(const RetryState& st, const FrameOutcome& r) {
     const bool pm_wave_frame = r.kernel_id == MCRT_KERNEL_PM_WAVE || r.kernel_id == MCRT_KERNEL_WAVEFRONT_PM;
     const bool lane_frame = r.kernel_id == MCRT_KERNEL_PM_LANE;
     const bool was_pipeline = r.kernel_id == MCRT_KERNEL_WAVEFRONT || r.kernel_id == MCRT_KERNEL_WAVEFRONT_PM;
-    if (r.overflow >= kSelKnnOverflow) {
+    if (statsKnnOverflowed(r.overflow)) {
         // The reference's frontier is an unbounded priority queue (linear-octree.cpp:33). A wave-cooperative search keeps 128 entries
         // in registers and 1 024 in a list in memory; a frame in which one of them ran out is rendered AGAIN by the per-lane kernel (the
         // reference's two queues per lane, in memory), whose own frontier - 160 entries per lane to begin with - grows eightfold per
@@ -401,7 +403,7 @@ inline RetryStep nextRender(const RetryState& st, const FrameOutcome& r) {
         return refuse("kNN frontier overflow: a search had more than " + std::to_string(kSelVisitLimit) + " octants pending at once in the per-lane "
                       "kernel's frontier (the reference's queue is unbounded, linear-octree.cpp:33)");
     }
-    if (r.overflow) return refuse("traversal stack overflow (internal error: the stacks are sized to the tree's own bound, HostLayout::stack_bound)");
+    if (statsStackOverflows(r.overflow)) return refuse("traversal stack overflow (internal error: the stacks are sized to the tree's own bound, HostLayout::stack_bound)");
     if (r.iors_overflow) {
         // RefractionHistory (ray.cpp:74-98) is an unbounded vector. The megakernels keep kMaxIors (8) entries per lane, the pipeline
         // iors_depth per slot (32 to begin with). A frame that nested deeper is rendered AGAIN: a megakernel frame through the

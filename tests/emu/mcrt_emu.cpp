@@ -1220,8 +1220,8 @@ int emu_select_kernel(const uint64_t* scene, const uint64_t* frame, int n_option
     return c.err;
 }
 
-// nextRender (mcrt_select.hpp). state = {force_wf, force_pm_lane, knn_visit_cap, iors_depth}; outcome = {kernel_id, stats word 5, stats
-// word 7, splats, can_pipeline}; next = the state to render again with. Returns the action (0 done, 1 error, 2 again); err / msg: the error.
+// nextRender (mcrt_select.hpp). state = {force_wf, force_pm_lane, knn_visit_cap, iors_depth}; outcome = {kernel_id, the words kStatOverflow and
+// kStatIorsOverflow (csrc/mcrt_stats_words.hpp), splats, can_pipeline}; next = the state to render again with. Returns the action (0 done, 1 error, 2 again); err / msg: the error.
 int emu_next_render(const uint64_t* state, const uint64_t* outcome, uint64_t* next, int* err, char* msg, int msg_cap) {
     RetryState st;
     st.force_wf = state[0] != 0;

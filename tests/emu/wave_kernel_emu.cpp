@@ -10,6 +10,7 @@
 
 #include "../../monte-carlo-ray-tracer_amd/csrc/mcrt_groupknn.hpp"
 #include "../../monte-carlo-ray-tracer_amd/csrc/mcrt_widerec.hpp"
+#include "../../monte-carlo-ray-tracer_amd/csrc/mcrt_stats_readout.hpp"
 
 namespace {
 alignas(64) unsigned char lds[160 * 1024];  // what `extern __shared__ unsigned char lds[]` of the kernels refers to here
@@ -121,7 +122,7 @@ extern "C" {
 // Closest hits of n rays through wfTraceKernel<ArrayRays, count, lean> (form: 3 = round 4's visit, 11 = the lean visit, 27 = the lean visit
 // with one block per visit; the forms 0 / 1 / 2 of rounds 2-3 were removed in round 6: -201). grid workgroups of `waves` wavefronts; lds_blocks / lds_stack / refill /
 // leaf_lanes / deal_shift: fillTraceArgs's parameters (lds_blocks 0xFFFFFFFF = as many as the tree has, up to 512). stats: the kernel's
-// counters [kStatsWords] (rays at [1], node / primitive tests at [2] / [3], overflow at [5]). Returns 0, -100 on stack overflow.
+// counters [kStatsWords] (csrc/mcrt_stats_words.hpp: kStatRays, kStatNodeTests / kStatPrimTests, kStatOverflow). Returns 0, -100 on stack overflow.
 int wemu_trace_kernel(const mcrt_scene_desc* scene, uint64_t n, const double* start, const double* direction, int form, uint32_t grid, uint32_t waves,
                       uint32_t lds_blocks, int lds_stack, int refill_lanes, int leaf_lanes, uint32_t deal_shift, double* out_t, uint32_t* out_surface,
                       double* out_uv, unsigned long long* stats_out) {
@@ -147,7 +148,7 @@ int wemu_trace_kernel(const mcrt_scene_desc* scene, uint64_t n, const double* st
         launchTrace<3>(a, rays, grid, waves);
     } else launchTrace<0>(a, rays, grid, waves);
     if (stats_out) memcpy(stats_out, stats.data(), kStatsWords * sizeof(unsigned long long));
-    return stats[5] ? -100 : 0;
+    return stats[kStatOverflow] ? -100 : 0;
 }
 
 // ---- whole frames ------------------------------------------------------------------------------------------------------------------
@@ -303,7 +304,7 @@ int wemu_render(const mcrt_scene_desc* scene, const mcrt_photon_map_desc* gmap, 
     launchGrid((uint32_t)((prm.pass_pixels + 255) / 256), 256, [&] { sampleResolveKernel(prm.samples, prm.pass_pixels, prm.spp, out_rgb); });
     if (stats_out) memcpy(stats_out, stats.data(), kStatsWords * sizeof(unsigned long long));
     if (kernel_out) *kernel_out = kernel_id;
-    return stats[5] ? -100 : stats[7] ? -101 : 0;
+    return stats[kStatOverflow] ? -100 : stats[kStatIorsOverflow] ? -101 : 0;
 }
 
 // The wavefront pipeline - wfShadeKernel, wfTraceKernel<PoolRays>, for photon-mapped frames wfKnnKernel<eval>, then sampleResolveKernel -
@@ -406,7 +407,7 @@ int wemu_render_pipeline(const mcrt_scene_desc* scene, const mcrt_photon_map_des
     launches++;
     if (stats_out) memcpy(stats_out, stats.data(), kStatsWords * sizeof(unsigned long long));
     if (launches_out) *launches_out = launches;
-    return stats[5] ? -100 : stats[7] ? -101 : 0;
+    return stats[kStatOverflow] ? -100 : stats[kStatIorsOverflow] ? -101 : 0;
 }
 
 // emitKernel (the photon pass: PhotonMapper's emission loop, photon-mapper.cpp:96-110 / 225-277) on emulated workgroups, its arguments
@@ -429,7 +430,7 @@ int wemu_emit(const mcrt_scene_desc* scene, double emissions, double caustic_fac
     const uint32_t block = kBlock;
     const uint32_t lds_bytes = planLds(d, block).total;
     if (lds_bytes > kEmuMaxLds || lds_bytes > sizeof(lds)) return -202;
-    unsigned long long counters[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    unsigned long long counters[kEmitWords] = {};
     std::vector<StackEntry> spill((size_t)grid * block * (d.stack_depth - kLdsStackDepth) + 16);
     float* const lists[2] = {out_global, out_caustic};
     unsigned long long* const keys[2] = {keys_global, keys_caustic};
@@ -438,11 +439,49 @@ int wemu_emit(const mcrt_scene_desc* scene, double emissions, double caustic_fac
     fillEmitParams(prm, nl, first.data(), pflux.data(), 0, first[nl], stride, global_seed, caustic_factor, lists, keys, cap, counters, spill.data(), grid * block);
     if (d.stage_all) launchGrid(grid, block, [&] { emitKernel<true>(d, prm); });
     else launchGrid(grid, block, [&] { emitKernel<false>(d, prm); });
-    counts[0] = counters[1];
-    counts[1] = counters[2];
-    counts[2] = counters[3];
-    counts[3] = counters[4];
-    return counters[5] ? -100 : counters[6] ? -101 : 0;
+    counts[0] = counters[kEmitGlobalCount];
+    counts[1] = counters[kEmitCausticCount];
+    counts[2] = counters[kEmitPaths];
+    counts[3] = counters[kEmitRays];
+    return counters[kEmitOverflow] ? -100 : counters[kEmitIorsOverflow] ? -101 : 0;
+}
+
+// ---- the statistics words (csrc/mcrt_stats_words.hpp) and what mcrt_render_finish makes of them (csrc/mcrt_stats_readout.hpp) ----------
+// The numbering, in the order tests/test_stats_words.py names it: the eight common words, the overlays' base, the phase clocks (wave,
+// lane, how many phases), the trace kernel's twelve words, the photon-mapping kernel's two, kStatsWords; then the emission counters
+// and kEmitWords; then kStatKnnOverflowBit and kKnnOverflowUnit. Returns how many values that is (out may be null).
+int wemu_stats_layout(uint64_t* out) {
+    const uint64_t v[] = {kStatPaths, kStatRays, kStatNodeTests, kStatPrimTests, kStatKnnSearches, kStatOverflow, kStatKnnOctants, kStatIorsOverflow,
+                          kStatOverlay, kStatPhaseWave, kStatPhaseLane, kNumPhases,
+                          kStatTraceIters, kStatTraceHave, kStatTraceInnerSteps, kStatTraceInnerLanes, kStatTraceLeafSteps, kStatTraceLeafLanes, kStatTraceLeafWait,
+                          kStatTraceInnerCycles, kStatTraceLeafCycles, kStatTraceKernelCycles, kStatTraceRefillCycles, kStatTracePopCycles,
+                          kStatPmEstimateCycles, kStatPmKernelCycles, kStatsWords,
+                          kEmitWork, kEmitGlobalCount, kEmitCausticCount, kEmitPaths, kEmitRays, kEmitOverflow, kEmitIorsOverflow, kEmitWords,
+                          kStatKnnOverflowBit, kKnnOverflowUnit};
+    const int n = (int)(sizeof(v) / sizeof(v[0]));
+    if (out) std::copy(v, v + n, out);
+    return n;
+}
+// statsReadout: the text mcrt_render_finish prints for a frame with these words [kStatsWords], rendered by these instances (RenderInstance
+// values, -1 none) in this form. Returns the text's length; out holds as much of it as fits cap, zero-terminated.
+int wemu_stats_readout(const unsigned long long* words, int used_instance, int used_trace, uint32_t kernel_id, char* out, uint32_t cap) {
+    const std::string text = statsReadout(words, used_instance, used_trace, kernel_id);
+    if (out && cap) {
+        const size_t n = std::min<size_t>(text.size(), cap - 1);
+        memcpy(out, text.data(), n);
+        out[n] = 0;
+    }
+    return (int)text.size();
+}
+// statsCounters and statsOutcome of the words, and what nextRender makes of that outcome for a context that has not rendered the frame
+// again: out = {paths, rays, node_tests, prim_tests, knn_searches, overflow, iors_overflow, RetryAction}
+void wemu_stats_outcome(const unsigned long long* words, uint32_t kernel_id, uint64_t* out) {
+    mcrt_stats s;
+    memset(&s, 0, sizeof(s));
+    statsCounters(words, s);
+    const FrameOutcome frame = statsOutcome(words, kernel_id);
+    const uint64_t v[8] = {s.paths, s.rays, s.node_tests, s.prim_tests, s.knn_searches, frame.overflow, frame.iors_overflow, (uint64_t)nextRender(RetryState{}, frame).action};
+    std::copy(v, v + 8, out);
 }
 
 // 0: the waves of a workgroup take turns; otherwise the seed of a random visiting order (wave_emu.hpp)

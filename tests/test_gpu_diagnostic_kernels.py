@@ -184,10 +184,14 @@ def test_counting_instance_renders_the_frame_and_counts_what_the_header_says(pkg
 
 
 PHASES = ["regen", "trav/inner", "shade", "shadow/leaf", "sample", "loop"]
+# the readouts' lines (tests/test_stats_words.py matches hand-made words with the same expressions, without a GPU)
+PHASE_LINE = r"^\[mcrt phase\] (\S+)\s+wave-cycles\s+([0-9.naif-]+)%\s+lane utilisation\s+([0-9.naif-]+)%$"
+TRACE_PER_RAY = r"per ray: ([0-9.]+) inner steps, ([0-9.]+) leaf steps \((\d+) inner and (\d+) leaf lane steps of (\d+) rays\)"
+PM_LINE = r"^\[mcrt pm\] wave cycles inside the radiance estimates: ([0-9.]+)% of the kernel \((\d+) searches, ([0-9.]+) octants per search\)$"
 
 
 def _phase_lines(err):
-    rows = re.findall(r"^\[mcrt phase\] (\S+)\s+wave-cycles\s+([0-9.naif-]+)%\s+lane utilisation\s+([0-9.naif-]+)%$", err, re.M)
+    rows = re.findall(PHASE_LINE, err, re.M)
     return [(n, float(a), float(b)) for n, a, b in rows]
 
 
@@ -259,7 +263,7 @@ def test_trace_readout_is_well_formed(pkg, oracle, manifest, env, capfd, name):
             print(line)
             assert all(0.0 <= float(p) <= 100.0 for p in re.findall(r"(-?[0-9.]+)%", line)) and len(re.findall(r"%", line)) == 7
             assert all(0.0 <= float(x) <= 64.0 for x in re.findall(r"(-?[0-9.]+) (?:leaf )?lanes", line))
-            m = re.search(r"per ray: ([0-9.]+) inner steps, ([0-9.]+) leaf steps \((\d+) inner and (\d+) leaf lane steps of (\d+) rays\)", line)
+            m = re.search(TRACE_PER_RAY, line)
             assert m, line
             inner_per_ray, leaf_per_ray, inner, leaf, rays = float(m.group(1)), float(m.group(2)), int(m.group(3)), int(m.group(4)), int(m.group(5))
             assert rays == st["rays"] and inner > 0 and leaf > 0
@@ -286,7 +290,7 @@ def test_photon_mapping_readout_is_well_formed(pkg, oracle, manifest, env, capfd
             assert st["instances"] == ["PM1024_CountAll", "-", "-"]
             _no_nan(err)
             assert "[mcrt phase]" not in err and "[mcrt trace]" not in err
-            m = re.findall(r"^\[mcrt pm\] wave cycles inside the radiance estimates: ([0-9.]+)% of the kernel \((\d+) searches, ([0-9.]+) octants per search\)$", err, re.M)
+            m = re.findall(PM_LINE, err, re.M)
             assert len(m) == 1, err
             print(err.rstrip())
             assert 0.0 < float(m[0][0]) <= 100.0 and int(m[0][1]) == st["knn_searches"] and float(m[0][2]) >= 1.0
