@@ -735,6 +735,87 @@ int mcrt_render_converged(mcrt_ctx* ctx, const mcrt_camera_desc* cam, uint32_t g
                           const mcrt_pixel_stats_buffers* stats_buffers /* may be NULL */, const mcrt_highlight_buffers* highlights /* may be NULL */,
                           mcrt_converge_result* result /* may be NULL */, mcrt_stats* stats /* may be NULL */);
 
+/* ------------------------------------------------------------------------------------------
+ * OpenEXR output: one scan-line OpenEXR 2 file that holds a frame and any number of its passes as named channels. The reference
+ * has no such output. Nothing here links an OpenEXR or zlib library: the file is written from the format's public specification
+ * ("OpenEXR File Layout"), and deflate is the system's libz.so.1, looked up (dlopen) at the first ZIP save. The values are
+ * converted, and the bytes of every chunk laid out in file order (NONE) or in ZIP's pre-deflate order, on the device: the packed
+ * buffer is the only thing that crosses to the host.
+ *
+ * A channel is a strided view of a frame: its value at pixel p = y * width + x is data[p * stride + offset], data being double
+ * (MCRT_EXR_SRC_F64) or uint32_t (MCRT_EXR_SRC_U32) elements. An [H][W][3] frame gives R, G, B with stride 3 and offsets 0, 1, 2;
+ * tops [H][W][4][3] twelve channels of stride 12; level [H][W] one of stride 1. One data pointer may serve many channels.
+ *
+ * Conversions, per value, all of them on the bits in integer arithmetic (no floating-point mode of the device takes part):
+ *   F64 -> HALF   ONE rounding from binary64 to binary16, to nearest, ties to even, subnormal results kept; never through binary32
+ *                 (1 + 2^-11 + 2^-30 becomes 0x3c01; through float it would be 0x3c00). A finite input whose rounding is infinite
+ *                 becomes +-65504 (0x7bff / 0xfbff) unless MCRT_EXR_HALF_INF is set; +-Inf stays; NaN becomes 0x7e00 with the
+ *                 input's sign bit; -0 stays -0.
+ *   F64 -> FLOAT  one rounding to nearest, ties to even, subnormal results kept, overflow to +-Inf; NaN becomes
+ *                 sign | 0x7fc00000 | (the top 22 bits below the quiet bit of the input's fraction), what (float)x gives on x86-64.
+ *   U32 -> UINT   the bits.
+ * Any other pair is refused.
+ *
+ * The file, little-endian throughout:
+ *   magic 76 2f 31 01, version 02 00 00 00 (single-part scan line, short names)
+ *   attributes, each name\0 type\0 int32 size, value, in this order:
+ *     channels (chlist): per channel name\0, int32 pixelType, uint8 pLinear 0, three 0 bytes, int32 xSampling 1, int32 ySampling 1;
+ *       one \0 closes the list      compression (compression): 1 byte      dataWindow, displayWindow (box2i): 0, 0, W-1, H-1
+ *     lineOrder (lineOrder): 1 byte, 0      pixelAspectRatio (float): 1      screenWindowCenter (v2f): 0, 0
+ *     screenWindowWidth (float): 1      the caller's attributes in the order given, type string (size = length, no terminator)
+ *   one \0 ends the header
+ *   the offset table: one uint64 per chunk, its absolute file position
+ *   the chunks in ascending y, each int32 y, int32 size, data. NONE: a chunk is one scan line; ZIP: 16 scan lines, the last may
+ *   hold fewer.
+ * Channels are sorted by name as bytes, in the header and in the pixel data, whatever the caller's order. A chunk's raw bytes:
+ * per scan line ascending, per channel in sorted order, W values. ZIP, with n raw bytes (always even) and h = n / 2:
+ *   t[i] = raw[2i] for i < h, t[h + i] = raw[2i + 1];   u[0] = t[0], u[i] = (t[i] - t[i-1] + 128) mod 256;
+ *   data = zlib-deflate(u) at zip_level, with the zlib wrapper. When the deflated size is >= n the chunk stores the untransformed
+ *   raw bytes and size = n (the format's own rule; counted in raw_chunks).
+ * A NONE file is therefore a function of the inputs byte for byte; a ZIP file is one up to the bytes deflate chooses, which depend
+ * on the zlib version - what a reader decodes from it is a function of the inputs.
+ *
+ * Refused with MCRT_ERR_INVALID: a render in flight; path, the channel array or a data pointer NULL; count 0 or > 1024;
+ * width * height 0 or >= 2^32; a name that is empty, longer than 31 bytes or not printable ASCII (0x20 .. 0x7e); duplicate
+ * names; stride 0 or offset >= stride; a source / pixel type pair not listed; a compression not listed; zip_level > 9; an
+ * attribute without a name or value, or whose name is one of the standard ones above. With MCRT_ERR_IO: the file cannot be
+ * created or written (a partial file is removed). With MCRT_ERR_UNSUPPORTED: ZIP is asked for and libz.so.1 cannot be loaded
+ * (NONE still works). The call needs no scene and is synchronous on the context's stream.
+ * stats: kernel_ms (HIP events of the call's own around its launch), total_ms, kernel_launches (1). */
+enum { MCRT_EXR_SRC_F64 = 0, MCRT_EXR_SRC_U32 = 1 };
+enum { MCRT_EXR_UINT = 0, MCRT_EXR_HALF = 1, MCRT_EXR_FLOAT = 2 };     /* OpenEXR's pixelType numbers */
+enum { MCRT_EXR_COMPRESSION_NONE = 0, MCRT_EXR_COMPRESSION_ZIP = 3 };   /* OpenEXR's compression numbers */
+/* mcrt_exr_params.compression: 0 = the default (ZIP); otherwise MCRT_EXR_COMPRESSION_SET | one of the numbers above. */
+#define MCRT_EXR_COMPRESSION_SET 0x100u
+#define MCRT_EXR_HALF_INF 1u            /* mcrt_exr_params.flags: a finite value past the half range becomes +-Inf, not +-65504 */
+#define MCRT_EXR_MAX_CHANNELS 1024u
+typedef struct mcrt_exr_channel {
+    const char* name;       /* 1..31 bytes, printable ASCII, e.g. "R", "albedo.G", "denoise_dual.error.B" */
+    const void* data;       /* element (pixel p) is data[p * stride + offset] of the source type; row-major, full frame */
+    uint32_t source_type, pixel_type, stride, offset;
+} mcrt_exr_channel;
+typedef struct mcrt_exr_attribute { const char* name; const char* value; } mcrt_exr_attribute;   /* written as type "string" */
+typedef struct mcrt_exr_params {    /* NULL or a zero field = the default */
+    uint32_t compression;           /* default ZIP; MCRT_EXR_COMPRESSION_SET | MCRT_EXR_COMPRESSION_NONE or _ZIP */
+    uint32_t zip_level;             /* default 4; 1..9 */
+    uint32_t threads;               /* deflate threads, default min(16, the host's hardware threads); never more than 16 */
+    uint32_t flags;                 /* MCRT_EXR_HALF_INF */
+} mcrt_exr_params;
+typedef struct mcrt_exr_result {
+    uint64_t file_bytes;     /* the size of the file written */
+    uint64_t packed_bytes;   /* what crossed from the device to the host: the sum over the channels of W * H * bytes per value */
+    uint32_t chunks, raw_chunks;
+} mcrt_exr_result;
+/* channels: a HOST array of structs whose data point to DEVICE memory (complete when the call is made: the stream contract below).
+ * No FP64 source leaves the device. */
+int mcrt_exr_save_device(mcrt_ctx* ctx, const char* path, uint32_t width, uint32_t height, const mcrt_exr_channel* d_channels, uint32_t count,
+                         const mcrt_exr_attribute* attributes /* may be NULL */, uint32_t attribute_count, const mcrt_exr_params* params /* may be NULL */,
+                         mcrt_exr_result* result /* may be NULL */, mcrt_stats* stats /* may be NULL */);
+/* Same with HOST data pointers: every distinct source buffer is copied to the device once, whatever the number of its channels. */
+int mcrt_exr_save(mcrt_ctx* ctx, const char* path, uint32_t width, uint32_t height, const mcrt_exr_channel* channels, uint32_t count,
+                  const mcrt_exr_attribute* attributes /* may be NULL */, uint32_t attribute_count, const mcrt_exr_params* params /* may be NULL */,
+                  mcrt_exr_result* result /* may be NULL */, mcrt_stats* stats /* may be NULL */);
+
 /* Photon emission pass on the GPU. Replaces the thread fan-out of
  * PhotonMapper::PhotonMapper (integrator/photon-mapper/photon-mapper.cpp:80-115: per emission
  * Sampler::initiate(light), setIndex(offset+i), light point + cosine direction, emitPhoton :225-277) for

@@ -273,6 +273,128 @@ class ConvergeResult(C.Structure):
                 "relative_error": [self.relative_error[i] for i in range(min(self.batches, CONVERGE_TRACE))]}
 
 
+# OpenEXR output (include/mcrt.h "OpenEXR output")
+EXR_SRC_F64, EXR_SRC_U32 = 0, 1
+EXR_PIXEL_TYPES = {"uint": 0, "half": 1, "float": 2}
+EXR_COMPRESSION = {"none": 0x100 | 0, "zip": 0x100 | 3}  # MCRT_EXR_COMPRESSION_SET | OpenEXR's number
+EXR_HALF_INF = 1
+
+
+class ExrChannel(C.Structure):
+    """mcrt_exr_channel: a strided view of a frame under a name."""
+    _fields_ = [("name", C.c_char_p), ("data", C.c_void_p), ("source_type", C.c_uint32), ("pixel_type", C.c_uint32), ("stride", C.c_uint32), ("offset", C.c_uint32)]
+
+
+class ExrAttribute(C.Structure):
+    """mcrt_exr_attribute: written as type "string"."""
+    _fields_ = [("name", C.c_char_p), ("value", C.c_char_p)]
+
+
+class ExrParams(C.Structure):
+    """mcrt_exr_params: a zero field = the default (include/mcrt.h)."""
+    _fields_ = [("compression", C.c_uint32), ("zip_level", C.c_uint32), ("threads", C.c_uint32), ("flags", C.c_uint32)]
+
+
+class ExrResult(C.Structure):
+    """mcrt_exr_result."""
+    _fields_ = [("file_bytes", C.c_uint64), ("packed_bytes", C.c_uint64), ("chunks", C.c_uint32), ("raw_chunks", C.c_uint32)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+def _is_tensor(a):
+    return hasattr(a, "data_ptr") and hasattr(a, "storage_offset")
+
+
+def _exr_source(a):
+    """A frame view [H,W] of float64 or (u)int32 elements, numpy or torch -> (the array to keep alive, base pointer, source type, stride,
+    offset) with element (pixel p) = base[p * stride + offset]. A last-axis view of a packed [H,W,k] buffer keeps the buffer's pointer,
+    so that its k channels name one source; a view that is no such thing is copied."""
+    tensor = _is_tensor(a)
+    if not tensor:
+        a = np.asarray(a)
+    assert a.ndim == 2, "a channel is a [H,W] view, not %r" % (tuple(a.shape),)
+    kind = str(a.dtype).replace("torch.", "")
+    assert kind in ("float64", "uint32", "int32"), "a channel is float64 or uint32, not %s" % kind
+    item = 8 if kind == "float64" else 4
+    height, width = int(a.shape[0]), int(a.shape[1])
+    strides = [int(x) for x in a.stride()] if tensor else [int(x) // item if int(x) % item == 0 else -1 for x in a.strides]
+    step = strides[1] if width > 1 else (strides[0] if height > 1 else 1)
+    packed = step >= 1 and step < (1 << 32) and (height == 1 or width == 1 or strides[0] == width * step)
+    if not packed:
+        a = a.contiguous() if tensor else np.ascontiguousarray(a)
+        step = 1
+    if tensor:
+        ptr, first = int(a.data_ptr()), int(a.storage_offset())
+    else:
+        root = a
+        while isinstance(root.base, np.ndarray):
+            root = root.base
+        ptr = int(a.ctypes.data)
+        first = (ptr - int(root.ctypes.data)) // item if step > 1 else 0
+    offset = first % step
+    return a, ptr - offset * item, EXR_SRC_F64 if kind == "float64" else EXR_SRC_U32, step, offset
+
+
+_EXR_FLOAT_LAYERS = ("depth", "position", "variance", "error", "level")
+
+
+def exr_layers(rgb=None, aov=None, stats=None, highlights=None, robust=None, denoised=None, pixel_types=None):
+    """The channel dict Context.exr_save takes, from what the render_* and denoise_* methods return, under fixed names:
+      rgb [H,W,3]                       R, G, B
+      aov (render_aov's dict)           depth.Z, position.X/Y/Z, normal.X/Y/Z, shading_normal.X/Y/Z, albedo.R/G/B, coverage.A, surface.id, material.id
+      stats (render_pixel_stats')       variance.R/G/B, half_a.R/G/B, half_b.R/G/B          (its "rgb" is not taken: pass it as rgb)
+      highlights (render_highlights')   tops0.R .. tops3.B, level.Y
+      robust (robust_resolve's)         robust.R/G/B, removed.R/G/B, clamped.count
+      denoised {name: frame | (frame, variance) | dict with "rgb" and "variance" / "error"}   name.R/G/B, name.variance.R/G/B, name.error.R/G/B
+    -> dict name -> (view [H,W], "half" | "float" | "uint"). Colour is HALF; depth, position, variance, error and level FLOAT; ids and
+    counts UINT. pixel_types: {channel or layer name: type} overrides that (a layer is a name without its last component). The views
+    are of the arrays and tensors given, numpy or torch alike: nothing is copied."""
+    out = {}
+
+    def put(layer, parts, frame, kind=None):
+        if kind is None:
+            kind = "float" if layer.split(".")[-1] in _EXR_FLOAT_LAYERS else "half"
+        for i, part in enumerate(parts):
+            name = part if layer == "" else "%s.%s" % (layer, part)
+            view = frame if len(parts) == 1 and frame.ndim == 2 else frame[..., i]
+            assert view.ndim == 2, (name, tuple(frame.shape))
+            out[name] = (view, (pixel_types or {}).get(name, (pixel_types or {}).get(layer, kind)))
+
+    if rgb is not None:
+        put("", "RGB", rgb)
+    for layer, parts in (("depth", "Z"), ("position", "XYZ"), ("normal", "XYZ"), ("shading_normal", "XYZ"), ("albedo", "RGB"), ("coverage", "A")):
+        if aov is not None and aov.get(layer) is not None:
+            put(layer, parts, aov[layer])
+    for layer in ("surface", "material"):
+        if aov is not None and aov.get(layer) is not None:
+            put(layer, ("id",), aov[layer], "uint")
+    for layer in PIXEL_STATS_CHANNELS:
+        if stats is not None and stats.get(layer) is not None:
+            put(layer, "RGB", stats[layer])
+    if highlights is not None and highlights.get("tops") is not None:
+        for k in range(ROBUST_TOPS):
+            put("tops%d" % k, "RGB", highlights["tops"][:, :, k, :])
+    if highlights is not None and highlights.get("level") is not None:
+        put("level", "Y", highlights["level"])
+    for layer in ("robust", "removed"):
+        if robust is not None and robust.get(layer) is not None:
+            put(layer, "RGB", robust[layer])
+    if robust is not None and robust.get("clamped") is not None:
+        put("clamped", ("count",), robust["clamped"], "uint")
+    for name, value in (denoised or {}).items():
+        if isinstance(value, dict):
+            frames = {k: value[k] for k in ("rgb", "variance", "error") if value.get(k) is not None}
+        elif isinstance(value, (tuple, list)):
+            frames = {k: v for k, v in zip(("rgb", "variance"), value) if v is not None}
+        else:
+            frames = {"rgb": value}
+        for k, frame in frames.items():
+            put(name if k == "rgb" else "%s.%s" % (name, k), "RGB", frame)
+    return out
+
+
 class PhotonEmissionDevice(C.Structure):
     _fields_ = [("global_count", C.c_uint64), ("caustic_count", C.c_uint64), ("d_global_photons", C.c_void_p), ("d_caustic_photons", C.c_void_p),
                 ("emission_paths", C.c_uint64), ("rays", C.c_uint64), ("kernel_ms", C.c_double)]
@@ -388,6 +510,10 @@ def lib():
         L.mcrt_render_converged.argtypes = [vp, C.POINTER(CameraDesc), C.c_uint32, C.c_int, C.POINTER(ConvergeParams), vp, C.POINTER(PixelStatsBuffers),
                                             C.POINTER(HighlightBuffers), C.POINTER(ConvergeResult), C.POINTER(Stats)]
         L.mcrt_render_converged_device.argtypes = L.mcrt_render_converged.argtypes
+    if hasattr(L, "mcrt_exr_save"):  # (likewise)
+        L.mcrt_exr_save.argtypes = [vp, C.c_char_p, C.c_uint32, C.c_uint32, C.POINTER(ExrChannel), C.c_uint32, C.POINTER(ExrAttribute), C.c_uint32,
+                                    C.POINTER(ExrParams), C.POINTER(ExrResult), C.POINTER(Stats)]
+        L.mcrt_exr_save_device.argtypes = L.mcrt_exr_save.argtypes
     L.mcrt_sampler.argtypes = [vp, C.c_uint64, _u32p, _u32p, C.c_uint32, C.c_uint32, _dp]
     L.mcrt_knn.argtypes = [vp, C.c_int, C.c_uint64, _dp, C.c_uint32, _u32p, _u32p, _dp]
     L.mcrt_bsdf.argtypes = [vp, C.c_uint64, _dp, _dp, _dp]
@@ -1127,6 +1253,44 @@ class Context:
         self._check(self._lib.mcrt_frame_merge_device(self._h, int(pixels), C.byref(sums[0]), int(n_a), C.byref(sums[1]), int(n_b), C.byref(sums[2]),
                                                       C.byref(st)), "mcrt_frame_merge_device")
         return st.as_dict()
+
+    def exr_save(self, path, channels, attributes=None, compression="zip", zip_level=0, threads=0, half_inf=False, stats=None):
+        """mcrt_exr_save / mcrt_exr_save_device: one OpenEXR file of the named channels. channels: dict name -> frame view [H,W] or
+        (view, "half" | "float" | "uint") - exr_layers builds it; float64 goes to HALF unless told otherwise, (u)int32 to UINT. The
+        views are numpy arrays (the host form: every distinct buffer crosses to the device once) or torch device tensors (the device
+        form: only the packed buffer crosses back; all channels must then be tensors of this context's device, complete: the
+        producing streams are synchronised here). Last-axis views of one packed buffer become stride / offset of that buffer.
+        attributes: dict name -> str, written as strings. compression: "zip" or "none". -> dict file_bytes, packed_bytes, chunks,
+        raw_chunks. stats: a dict that receives mcrt_stats."""
+        self._sync_env()
+        assert len(channels) >= 1, "no channel"
+        keep, recs, shape, on_device = [], [], None, None
+        for name, value in channels.items():
+            view, kind = value if isinstance(value, (tuple, list)) else (value, None)
+            arr, ptr, source, stride, offset = _exr_source(view)
+            if kind is None:
+                kind = "half" if source == EXR_SRC_F64 else "uint"
+            tensor = _is_tensor(arr)
+            if tensor:
+                assert arr.is_cuda, "%s: a torch channel lives on the device (numpy arrays take the host form)" % name
+            assert on_device in (None, tensor), "channels are all numpy arrays or all torch device tensors"
+            assert shape in (None, tuple(arr.shape)), (name, tuple(arr.shape), shape)
+            on_device, shape = tensor, tuple(arr.shape)
+            keep.append(arr)
+            recs.append(ExrChannel(name.encode("ascii"), ptr, source, EXR_PIXEL_TYPES[kind], stride, offset))
+        if on_device:
+            import torch
+            torch.cuda.synchronize()
+        attrs = [ExrAttribute(str(k).encode("ascii"), str(v).encode("ascii")) for k, v in (attributes or {}).items()]
+        par = ExrParams(EXR_COMPRESSION[compression], int(zip_level), int(threads), EXR_HALF_INF if half_inf else 0)
+        res, st = ExrResult(), Stats()
+        call = self._lib.mcrt_exr_save_device if on_device else self._lib.mcrt_exr_save
+        self._check(call(self._h, os.fsencode(path), shape[1], shape[0], (ExrChannel * len(recs))(*recs), len(recs),
+                         (ExrAttribute * len(attrs))(*attrs) if attrs else None, len(attrs), C.byref(par), C.byref(res), C.byref(st)),
+                    "mcrt_exr_save_device" if on_device else "mcrt_exr_save")
+        if stats is not None:
+            stats.update(st.as_dict())
+        return res.as_dict()
 
     def render_converged(self, cam, global_seed, target_relative_error=0.0, max_spp=0, integrator=INTEGRATOR_PATH_TRACER, min_batches=0,
                          channels=("variance",), stats=None):

@@ -6,7 +6,7 @@
 //               [--tga out.tga [--tonemapper hable|aces] [--exposure EV] [--gain EV] [--plain]] [--aov PREFIX]
 //               [--denoise OUT.f64 [--denoise-iterations N]] [--denoise-variance OUT.f64 [--denoise-variance-out VAR.f64]]
 //               [--denoise-dual OUT.f64 [--denoise-dual-out VAR.f64]] [--stats PREFIX] [--robust PREFIX [--robust-kappa X] [--robust-radius R]]
-//               [--converge TARGET [--max-spp N]]
+//               [--converge TARGET [--max-spp N]] [--exr OUT.exr [--exr-compression none|zip]]
 //
 // Writes the frame as raw FP64 RGB, row-major (what Image::operator() holds, camera/image.cpp:53-56),
 // and prints the statistics. --tga also develops it the way Image::save does (auto exposure / gain, tone map, sRGB bytes:
@@ -33,10 +33,17 @@
 // frame's relative error (mcrt_frame_noise) is at most TARGET or one more batch would exceed --max-spp (default 1024); --stats, --robust,
 // --denoise-variance and --denoise-dual then read the accumulated buffers at the accumulated sample count. Prints batches, spp and the final relative
 // error (one device).
+// --exr also writes everything the run produced - the frame and the buffers of --aov, --stats, --robust and the --denoise options - into
+// one OpenEXR file (mcrt_exr_save) as named channels: R, G, B; depth.Z, position.X/Y/Z, normal.X/Y/Z, shading_normal.X/Y/Z, albedo.R/G/B,
+// coverage.A, surface.id, material.id; variance.R/G/B, half_a.*, half_b.*; tops0.R .. tops3.B, level.Y; robust.*, removed.*, clamped.count;
+// denoise.*, denoise_variance.*, denoise_variance.variance.*, denoise_dual.*, denoise_dual.variance.*. Colour is HALF; depth, position,
+// variances and level FLOAT; ids and counts UINT. The attributes mcrt:spp, mcrt:seed, mcrt:integrator and mcrt:kernel say what was
+// rendered. --exr-compression: zip (the default) or none. The .f64 outputs stay as they are (one device).
 // --devices renders the frame on several GPUs from this one process (mcrt_render_multi: one host thread per GPU).
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <deque>
 #include <string>
 #include <vector>
 
@@ -61,7 +68,23 @@ int main(int argc, char** argv) {
     image.plain = (uint32_t)mcrt_image_param(img, "image_plain");
     image.exposure_compensation = from_bits(mcrt_image_param(img, "image_exposure_ev_bits"));
     image.gain_compensation = from_bits(mcrt_image_param(img, "image_gain_ev_bits"));
-    std::string tga, aov, denoise, dvar, dvar_out, ddual, ddual_out, pstats, robust;
+    std::string tga, aov, denoise, dvar, dvar_out, ddual, ddual_out, pstats, robust, exr;
+    mcrt_exr_params eparams{};
+    // what --exr writes: the channels, their names and the buffers that outlive the block that filled them
+    std::vector<mcrt_exr_channel> exr_channels;
+    std::deque<std::string> exr_names;
+    std::deque<std::vector<double>> exr_f64;
+    std::deque<std::vector<uint32_t>> exr_u32;
+    auto exr_one = [&](const std::string& name, const void* data, uint32_t pixel_type, uint32_t stride, uint32_t offset) {
+        if (exr.empty()) return;
+        exr_names.push_back(name);
+        exr_channels.push_back({exr_names.back().c_str(), data, pixel_type == MCRT_EXR_UINT ? (uint32_t)MCRT_EXR_SRC_U32 : (uint32_t)MCRT_EXR_SRC_F64, pixel_type, stride, offset});
+    };
+    auto exr_layer = [&](const std::string& layer, const char* parts, const void* data, uint32_t pixel_type, uint32_t stride = 3, uint32_t first = 0) {
+        for (uint32_t i = 0; parts[i]; i++) exr_one(layer.empty() ? std::string(1, parts[i]) : layer + "." + parts[i], data, pixel_type, stride, first + i);
+    };
+    auto exr_keep = [&](std::vector<double>& v) { exr_f64.push_back(std::move(v)); return exr_f64.back().data(); };
+    auto exr_keep_u32 = [&](std::vector<uint32_t>& v) { exr_u32.push_back(std::move(v)); return exr_u32.back().data(); };
     mcrt_robust_params rparams{};
     mcrt_denoise_params dparams{};
     mcrt_converge_params cparams{};
@@ -91,6 +114,8 @@ int main(int argc, char** argv) {
         else if (k == "--denoise-dual-out" && i + 1 < argc) ddual_out = argv[++i];
         else if (k == "--stats" && i + 1 < argc) pstats = argv[++i];
         else if (k == "--robust" && i + 1 < argc) robust = argv[++i];
+        else if (k == "--exr" && i + 1 < argc) exr = argv[++i];
+        else if (k == "--exr-compression" && i + 1 < argc) eparams.compression = MCRT_EXR_COMPRESSION_SET | ((argv[++i][0] | 0x20) == 'n' ? MCRT_EXR_COMPRESSION_NONE : MCRT_EXR_COMPRESSION_ZIP);
         else if (k == "--robust-kappa" && i + 1 < argc) rparams.kappa = std::strtod(argv[++i], nullptr);
         else if (k == "--robust-radius") rparams.radius = (uint32_t)val();
         else if (k == "--converge" && i + 1 < argc) converge = true, cparams.target_relative_error = std::strtod(argv[++i], nullptr);
@@ -112,6 +137,10 @@ int main(int argc, char** argv) {
     cam.shard_index = 0;
     cam.shard_count = 1;
     if (devices.empty()) devices.push_back(device);
+    if (!exr.empty() && devices.size() > 1) {
+        std::fprintf(stderr, "--exr takes one device\n");
+        return 2;
+    }
     std::vector<mcrt_ctx*> ctxs(devices.size(), nullptr);
     int rc = MCRT_OK;
     for (size_t d = 0; d < devices.size() && rc == MCRT_OK; d++) {
@@ -175,6 +204,14 @@ int main(int argc, char** argv) {
         return 1;
     }
     std::fclose(f);
+    exr_layer("", "RGB", rgb.data(), MCRT_EXR_HALF);
+    if (!variance.empty()) exr_layer("variance", "RGB", variance.data(), MCRT_EXR_FLOAT);
+    if (!half_a.empty()) exr_layer("half_a", "RGB", half_a.data(), MCRT_EXR_HALF);
+    if (!half_b.empty()) exr_layer("half_b", "RGB", half_b.data(), MCRT_EXR_HALF);
+    if (!tops.empty()) {
+        for (uint32_t k = 0; k < MCRT_ROBUST_TOPS; k++) exr_layer("tops" + std::to_string(k), "RGB", tops.data(), MCRT_EXR_HALF, 3 * MCRT_ROBUST_TOPS, 3 * k);
+        exr_layer("level", "Y", level.data(), MCRT_EXR_FLOAT, 1);
+    }
     if (!pstats.empty()) {
         const struct {
             const char* ext;
@@ -236,6 +273,11 @@ int main(int argc, char** argv) {
         std::printf("{\"robust\":\"%s\",\"clamped_pixels\":%llu,\"clamped_samples\":%llu,\"removed_energy\":%.17g,\"frame_energy\":%.17g,"
                     "\"removed_fraction\":%.17g,\"kernel_ms\":%.3f}\n",
                     robust.c_str(), pixels, samples, gone, all, all > 0.0 ? gone / all : 0.0, rst.kernel_ms);
+        if (!exr.empty()) {
+            exr_layer("robust", "RGB", exr_keep(out), MCRT_EXR_HALF);
+            exr_layer("removed", "RGB", exr_keep(removed), MCRT_EXR_HALF);
+            exr_one("clamped.count", exr_keep_u32(clamped), MCRT_EXR_UINT, 1, 0);
+        }
     }
     auto develop = [&](const std::vector<double>& frame, const std::string& path) {
         image.width = cam.width;
@@ -287,6 +329,10 @@ int main(int argc, char** argv) {
             const bool has_ext = dot != std::string::npos && (slash == std::string::npos || dot > slash);
             if (!develop(filtered, (has_ext ? ddual.substr(0, dot) : ddual) + ".tga")) return 1;
         }
+        if (!exr.empty()) {
+            exr_layer("denoise_dual", "RGB", exr_keep(filtered), MCRT_EXR_HALF);
+            exr_layer("denoise_dual.variance", "RGB", exr_keep(filtered_var), MCRT_EXR_FLOAT);
+        }
     }
     if (!aov.empty() || !denoise.empty() || !dvar.empty()) {
         const size_t px = (size_t)cam.width * cam.height;
@@ -331,6 +377,7 @@ int main(int argc, char** argv) {
                 const bool has_ext = dot != std::string::npos && (slash == std::string::npos || dot > slash);
                 if (!develop(filtered, (has_ext ? denoise.substr(0, dot) : denoise) + ".tga")) return 1;
             }
+            if (!exr.empty()) exr_layer("denoise", "RGB", exr_keep(filtered), MCRT_EXR_HALF);
         }
         if (!dvar.empty()) {
             std::vector<double> filtered(px * 3), filtered_var(px * 3);
@@ -355,7 +402,36 @@ int main(int argc, char** argv) {
                 const bool has_ext = dot != std::string::npos && (slash == std::string::npos || dot > slash);
                 if (!develop(filtered, (has_ext ? dvar.substr(0, dot) : dvar) + ".tga")) return 1;
             }
+            if (!exr.empty()) {
+                exr_layer("denoise_variance", "RGB", exr_keep(filtered), MCRT_EXR_HALF);
+                exr_layer("denoise_variance.variance", "RGB", exr_keep(filtered_var), MCRT_EXR_FLOAT);
+            }
         }
+        if (!exr.empty()) {
+            exr_layer("depth", "Z", exr_keep(depth), MCRT_EXR_FLOAT, 1);
+            exr_layer("position", "XYZ", exr_keep(position), MCRT_EXR_FLOAT);
+            exr_layer("normal", "XYZ", exr_keep(normal), MCRT_EXR_HALF);
+            exr_layer("shading_normal", "XYZ", exr_keep(shading_normal), MCRT_EXR_HALF);
+            exr_layer("albedo", "RGB", exr_keep(albedo), MCRT_EXR_HALF);
+            exr_layer("coverage", "A", exr_keep(coverage), MCRT_EXR_HALF, 1);
+            exr_one("surface.id", exr_keep_u32(surface), MCRT_EXR_UINT, 1, 0);
+            exr_one("material.id", exr_keep_u32(material), MCRT_EXR_UINT, 1, 0);
+        }
+    }
+    if (!exr.empty()) {
+        const std::string a_spp = std::to_string(spp), a_seed = std::to_string(seed), a_kernel = std::to_string(st.kernel_id);
+        const mcrt_exr_attribute attributes[4] = {{"mcrt:spp", a_spp.c_str()}, {"mcrt:seed", a_seed.c_str()},
+                                                  {"mcrt:integrator", photon ? "photon_mapper" : "path_tracer"}, {"mcrt:kernel", a_kernel.c_str()}};
+        mcrt_exr_result er;
+        mcrt_stats est;
+        rc = mcrt_exr_save(ctx, exr.c_str(), cam.width, cam.height, exr_channels.data(), (uint32_t)exr_channels.size(), attributes, 4, &eparams, &er, &est);
+        if (rc != MCRT_OK) {
+            std::fprintf(stderr, "mcrt error %d: %s\n", rc, mcrt_last_error(ctx));
+            return 1;
+        }
+        std::printf("{\"exr\":\"%s\",\"channels\":%zu,\"file_bytes\":%llu,\"packed_bytes\":%llu,\"chunks\":%u,\"raw_chunks\":%u,\"kernel_ms\":%.3f,\"total_ms\":%.3f}\n",
+                    exr.c_str(), exr_channels.size(), (unsigned long long)er.file_bytes, (unsigned long long)er.packed_bytes, er.chunks, er.raw_chunks, est.kernel_ms,
+                    est.total_ms);
     }
     std::printf("{\"width\":%u,\"height\":%u,\"spp\":%u,\"paths\":%llu,\"rays\":%llu,\"kernel_ms\":%.3f,\"total_ms\":%.3f,\"Mray_s\":%.1f}\n",
                 cam.width, cam.height, spp, (unsigned long long)st.paths, (unsigned long long)st.rays,
