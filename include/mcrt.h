@@ -816,6 +816,80 @@ int mcrt_exr_save(mcrt_ctx* ctx, const char* path, uint32_t width, uint32_t heig
                   const mcrt_exr_attribute* attributes /* may be NULL */, uint32_t attribute_count, const mcrt_exr_params* params /* may be NULL */,
                   mcrt_exr_result* result /* may be NULL */, mcrt_stats* stats /* may be NULL */);
 
+/* ------------------------------------------------------------------------------------------
+ * ID mattes: per pixel, the `ranks` keys (material, surface or a caller's object index) that cover most of it, each with its
+ * coverage, in the Cryptomatte layout compositors decode from the FLOAT channels and string attributes mcrt_exr_save writes. The
+ * reference has no such output. The surface / material channels of the AOV pass are "the hit of sample 0": one id per pixel,
+ * aliased at every silhouette; a matte counts every sample.
+ *
+ * Samples and keys. The samples are the AOV pass's: sample i of pixel (x, y) is its ray (above), s_i its closest hit. With
+ * n = sqrtspp^2, the key of a hit sample is key_i = map[s_i]; a miss has no key. params->key chooses map:
+ *   MCRT_MATTE_MATERIAL (0, default)  map = surf_material, num_keys = num_materials
+ *   MCRT_MATTE_SURFACE  (1)           the identity, num_keys = num_surfaces
+ *   MCRT_MATTE_CUSTOM   (2)           params->surface_key, a HOST array [num_surfaces] (a flattener's mesh / object index);
+ *                                     params->num_keys must be greater than every entry
+ * 0xFFFFFFFF is never a key.
+ *
+ * Ranking, per pixel. For every distinct key k: c_k = #{i : key_i = k}, f_k = min{i : key_i = k}. The keys are ordered by c
+ * descending, then f ascending - a total order, there are no ties. For r = 0 .. ranks-1, where a rank exists:
+ *   id[r] = k_r · coverage[r] = (double)c / (double)n · layer[r] = { (double)float_with_bits(code[k_r]), coverage[r] }
+ * and past the last distinct key id = 0xFFFFFFFF, coverage = 0.0, layer = {0.0, 0.0}. distinct = the number of distinct keys, NOT
+ * capped by ranks: a caller sees truncation. ranks: default 6; even, 2 .. 16. Integer work and one exact FP64 division: the
+ * outputs are a function of the hits bit for bit, whatever the chunking (option MCRT_AOV_CHUNK_RAYS), sharding, launch shape or
+ * form of the kernel (option MCRT_MATTE_FORM: "tile" pins the form that stages a tile of pixels' keys in LDS - refused with
+ * MCRT_ERR_UNSUPPORTED past 2048 samples per pixel -, "memory" the form that reads them from memory; unset: the measured choice,
+ * the first up to 512 samples per pixel, the second past it).
+ *
+ * Codes. code[k] is the Cryptomatte code of key k's name: h = MurmurHash3_x86_32(name bytes, seed 0) - blocks of 4 little-endian
+ * bytes: k *= 0xcc9e2d51, k = rotl(k, 15), k *= 0x1b873593, h ^= k, h = rotl(h, 13), h = h * 5 + 0xe6546b64; the tail bytes xor-ed in
+ * at shifts 16 / 8 / 0, then the same k-mix without the h-mix; h ^= len; h ^= h >> 16, h *= 0x85ebca6b, h ^= h >> 13,
+ * h *= 0xc2b2ae35, h ^= h >> 16 - then e = (h >> 23) & 255, and h ^= 1 << 23 when e is 0 or 255: as a float32 no zero, denormal,
+ * Inf or NaN (a hash of 0, the empty name's, becomes 0x00800000). Names: params->names, num_keys C strings of 1 .. 255 bytes of
+ * printable ASCII (anything else: MCRT_ERR_INVALID); NULL: "material%u", "surface%u" or "key%u".
+ *
+ * layer is double because a float32 as a double passes mcrt_exr_save's F64 -> FLOAT conversion unchanged: viewed as
+ * [H][W][2 * ranks] with stride 2 * ranks, offsets 0 .. 3 are NAME00.R (id), .G (coverage), .B (id), .A (coverage), offsets 4 .. 7
+ * NAME01.*, and so on. Mattes are box means like the AOVs: cam->film_* is ignored (no filter-weighted coverage). The optional preview
+ * layer NAME.R/G/B and sidecar manifests are not written.
+ *
+ * mcrt_render_matte*: shards, chunks, refusals and stats as mcrt_render_aov*. d_aov (may be NULL): the same rays and hits also
+ * fill the AOV channels - one closest-hit search for both, the bits mcrt_render_aov_device gives.
+ * mcrt_matte_rank_device: the ranking on a caller's own ids, no scene needed - d_keys [spp][pixels] sample-major, 0xFFFFFFFF = none;
+ * d_codes [greater than every key] or NULL = layer not wanted; the buffers hold `pixels` pixels. Synchronous on the context's
+ * stream. Refused with MCRT_ERR_INVALID: a render in flight, pixels 0 or >= 2^32, spp 0, pixels * spp above 0xFFF00000, d_keys or
+ * d_buffers NULL, ranks odd or outside 2 .. 16 (0 = the default), layer wanted without d_codes; with MCRT_ERR_HIP when the form that
+ * reads from memory cannot allocate its 8 bytes per sample.
+ * mcrt_matte_code: a name's code. mcrt_matte_manifest: the JSON object {"name":"%08x",...} of the num_keys names (params->names
+ * or the defaults of params->key; params may be NULL) in key order, '"' and '\' escaped, into buf (cap bytes, NUL-terminated when
+ * it fits); returns the bytes needed with the NUL, or a negative MCRT_ERR_* for a bad name - so that a C++ host and Python write
+ * the same manifest. */
+enum { MCRT_MATTE_MATERIAL = 0, MCRT_MATTE_SURFACE = 1, MCRT_MATTE_CUSTOM = 2 };
+#define MCRT_MATTE_DEFAULT_RANKS 6u
+#define MCRT_MATTE_MAX_RANKS 16u
+typedef struct mcrt_matte_params {  /* NULL or a zero field = the default */
+    uint32_t key;                   /* MCRT_MATTE_* */
+    uint32_t ranks;                 /* default 6; even, 2 .. 16 */
+    uint32_t num_keys;              /* MCRT_MATTE_CUSTOM only */
+    const uint32_t* surface_key;    /* MCRT_MATTE_CUSTOM only: HOST [num_surfaces] */
+    const char* const* names;       /* HOST [num_keys] or NULL = the default names */
+    uint64_t reserved;
+} mcrt_matte_params;
+typedef struct mcrt_matte_buffers {  /* every pointer may be NULL = not wanted; owned rows only, packed like d_out_rgb */
+    uint32_t* id;         /* [rows][width][ranks]    */
+    double*   coverage;   /* [rows][width][ranks]    */
+    double*   layer;      /* [rows][width][ranks][2] */
+    uint32_t* distinct;   /* [rows][width]           */
+} mcrt_matte_buffers;
+int mcrt_render_matte_device(mcrt_ctx* ctx, const mcrt_camera_desc* cam, uint32_t global_seed, const mcrt_matte_params* params /* may be NULL */,
+                             const mcrt_matte_buffers* d_buffers, const mcrt_aov_buffers* d_aov /* may be NULL */, mcrt_stats* stats /* may be NULL */);
+/* Same with HOST pointers to FULL frames: rows this shard does not own are left untouched. */
+int mcrt_render_matte(mcrt_ctx* ctx, const mcrt_camera_desc* cam, uint32_t global_seed, const mcrt_matte_params* params /* may be NULL */,
+                      const mcrt_matte_buffers* buffers, const mcrt_aov_buffers* aov /* may be NULL */, mcrt_stats* stats /* may be NULL */);
+int mcrt_matte_rank_device(mcrt_ctx* ctx, uint64_t pixels, uint32_t spp, const uint32_t* d_keys, uint32_t ranks, const uint32_t* d_codes /* may be NULL */,
+                           const mcrt_matte_buffers* d_buffers, mcrt_stats* stats /* may be NULL */);
+uint32_t mcrt_matte_code(const char* name);
+int64_t mcrt_matte_manifest(const mcrt_matte_params* params /* may be NULL */, uint32_t num_keys, char* buf /* may be NULL when cap is 0 */, uint64_t cap);
+
 /* Photon emission pass on the GPU. Replaces the thread fan-out of
  * PhotonMapper::PhotonMapper (integrator/photon-mapper/photon-mapper.cpp:80-115: per emission
  * Sampler::initiate(light), setIndex(offset+i), light point + cosine direction, emitPhoton :225-277) for

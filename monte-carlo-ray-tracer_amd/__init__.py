@@ -303,6 +303,66 @@ class ExrResult(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+# ID mattes (include/mcrt.h "ID mattes")
+MATTE_KEYS = {"material": 0, "surface": 1, "custom": 2}
+MATTE_DEFAULT_NAMES = {"material": "material%u", "surface": "surface%u", "custom": "key%u"}
+MATTE_DEFAULT_RANKS, MATTE_MAX_RANKS = 6, 16
+MATTE_CHANNELS = {"id": (np.uint32, ("ranks",)), "coverage": (np.float64, ("ranks",)), "layer": (np.float64, ("ranks", 2)), "distinct": (np.uint32, ())}
+NO_KEY = 0xFFFFFFFF
+
+
+class MatteParams(C.Structure):
+    """mcrt_matte_params: a zero field = the default (include/mcrt.h)."""
+    _fields_ = [("key", C.c_uint32), ("ranks", C.c_uint32), ("num_keys", C.c_uint32), ("surface_key", C.c_void_p), ("names", C.POINTER(C.c_char_p)),
+                ("reserved", C.c_uint64)]
+
+
+class MatteBuffers(C.Structure):
+    """mcrt_matte_buffers: every pointer may be NULL = not wanted."""
+    _fields_ = [("id", C.c_void_p), ("coverage", C.c_void_p), ("layer", C.c_void_p), ("distinct", C.c_void_p)]
+
+
+def matte_code(name):
+    """mcrt_matte_code: the Cryptomatte code of a name (str or bytes)."""
+    return int(lib().mcrt_matte_code(name if isinstance(name, bytes) else str(name).encode("ascii")))
+
+
+def _matte_params(key, ranks, names, surface_key, num_keys):
+    """(MatteParams, what it points into) of render_matte's arguments. num_keys only matters for key "custom"."""
+    par, keep = MatteParams(MATTE_KEYS[key], int(ranks), 0, None, None, 0), []
+    if surface_key is not None:
+        sk = np.ascontiguousarray(surface_key, dtype=np.uint32)
+        keep.append(sk)
+        par.surface_key = sk.ctypes.data
+    if names is not None:
+        arr = (C.c_char_p * max(len(names), 1))(*[n if isinstance(n, bytes) else str(n).encode("latin-1") for n in names])
+        keep.append(arr)
+        par.names = arr
+    if key == "custom":
+        par.num_keys = int(num_keys) if num_keys is not None else len(names) if names is not None else int(np.max(surface_key)) + 1
+    return par, keep
+
+
+def matte_manifest(key="material", num_keys=0, names=None):
+    """mcrt_matte_manifest: the JSON text {"name":"%08x",...} of the num_keys names (names, or the defaults of `key`) in key order."""
+    par, keep = _matte_params(key, 0, names, None, num_keys)
+    n = len(names) if names is not None else int(num_keys)
+    need = lib().mcrt_matte_manifest(C.byref(par), n, None, 0)
+    if need < 0:
+        raise McrtError("mcrt_matte_manifest failed (%d): a name is not 1 .. 255 bytes of printable ASCII" % need)
+    buf = C.create_string_buffer(need)
+    assert lib().mcrt_matte_manifest(C.byref(par), n, buf, need) == need
+    return buf.value.decode("ascii")
+
+
+def matte_attributes(layer_name, result):
+    """The string attributes that make the channels exr_layers(mattes={layer_name: result}) writes a Cryptomatte layer: cryptomatte/<K>/name,
+    /hash, /conversion and /manifest, <K> the first 7 of the 8 hex digits of matte_code(layer_name) (readers match on /name; the key only
+    has to be unique). result: render_matte's dict (its "manifest")."""
+    k = "cryptomatte/%s/" % ("%08x" % matte_code(layer_name))[:7]
+    return {k + "name": layer_name, k + "hash": "MurmurHash3_32", k + "conversion": "uint32_to_float32", k + "manifest": result["manifest"]}
+
+
 def _is_tensor(a):
     return hasattr(a, "data_ptr") and hasattr(a, "storage_offset")
 
@@ -340,7 +400,7 @@ def _exr_source(a):
 _EXR_FLOAT_LAYERS = ("depth", "position", "variance", "error", "level")
 
 
-def exr_layers(rgb=None, aov=None, stats=None, highlights=None, robust=None, denoised=None, pixel_types=None):
+def exr_layers(rgb=None, aov=None, stats=None, highlights=None, robust=None, denoised=None, pixel_types=None, mattes=None):
     """The channel dict Context.exr_save takes, from what the render_* and denoise_* methods return, under fixed names:
       rgb [H,W,3]                       R, G, B
       aov (render_aov's dict)           depth.Z, position.X/Y/Z, normal.X/Y/Z, shading_normal.X/Y/Z, albedo.R/G/B, coverage.A, surface.id, material.id
@@ -348,6 +408,9 @@ def exr_layers(rgb=None, aov=None, stats=None, highlights=None, robust=None, den
       highlights (render_highlights')   tops0.R .. tops3.B, level.Y
       robust (robust_resolve's)         robust.R/G/B, removed.R/G/B, clamped.count
       denoised {name: frame | (frame, variance) | dict with "rgb" and "variance" / "error"}   name.R/G/B, name.variance.R/G/B, name.error.R/G/B
+      mattes {name: render_matte's dict}  name00.R/G/B/A, name01.R/G/B/A, ...: views of its "layer" [H,W,ranks,2] - (id, coverage) of
+                                        ranks 2 l and 2 l + 1 -, always FLOAT whatever pixel_types says (HALF would destroy the ids);
+                                        matte_attributes gives the attributes that go with them
     -> dict name -> (view [H,W], "half" | "float" | "uint"). Colour is HALF; depth, position, variance, error and level FLOAT; ids and
     counts UINT. pixel_types: {channel or layer name: type} overrides that (a layer is a name without its last component). The views
     are of the arrays and tensors given, numpy or torch alike: nothing is copied."""
@@ -392,6 +455,12 @@ def exr_layers(rgb=None, aov=None, stats=None, highlights=None, robust=None, den
             frames = {"rgb": value}
         for k, frame in frames.items():
             put(name if k == "rgb" else "%s.%s" % (name, k), "RGB", frame)
+    for name, result in (mattes or {}).items():
+        layer = result["layer"]
+        assert layer.ndim == 4 and layer.shape[3] == 2 and layer.shape[2] % 2 == 0, tuple(layer.shape)
+        flat = layer.reshape(layer.shape[0], layer.shape[1], 2 * layer.shape[2])
+        for i in range(flat.shape[2]):
+            out["%s%02d.%s" % (name, i // 4, "RGBA"[i % 4])] = (flat[..., i], "float")
     return out
 
 
@@ -514,6 +583,14 @@ def lib():
         L.mcrt_exr_save.argtypes = [vp, C.c_char_p, C.c_uint32, C.c_uint32, C.POINTER(ExrChannel), C.c_uint32, C.POINTER(ExrAttribute), C.c_uint32,
                                     C.POINTER(ExrParams), C.POINTER(ExrResult), C.POINTER(Stats)]
         L.mcrt_exr_save_device.argtypes = L.mcrt_exr_save.argtypes
+    if hasattr(L, "mcrt_render_matte"):  # (likewise)
+        L.mcrt_render_matte.argtypes = [vp, C.POINTER(CameraDesc), C.c_uint32, C.POINTER(MatteParams), C.POINTER(MatteBuffers), C.POINTER(AovBuffers), C.POINTER(Stats)]
+        L.mcrt_render_matte_device.argtypes = L.mcrt_render_matte.argtypes
+        L.mcrt_matte_rank_device.argtypes = [vp, C.c_uint64, C.c_uint32, vp, C.c_uint32, vp, C.POINTER(MatteBuffers), C.POINTER(Stats)]
+        L.mcrt_matte_code.argtypes = [C.c_char_p]
+        L.mcrt_matte_code.restype = C.c_uint32
+        L.mcrt_matte_manifest.argtypes = [C.POINTER(MatteParams), C.c_uint32, C.c_char_p, C.c_uint64]
+        L.mcrt_matte_manifest.restype = C.c_int64
     L.mcrt_sampler.argtypes = [vp, C.c_uint64, _u32p, _u32p, C.c_uint32, C.c_uint32, _dp]
     L.mcrt_knn.argtypes = [vp, C.c_int, C.c_uint64, _dp, C.c_uint32, _u32p, _u32p, _dp]
     L.mcrt_bsdf.argtypes = [vp, C.c_uint64, _dp, _dp, _dp]
@@ -770,6 +847,7 @@ class Context:
     def __init__(self, device_id=0):
         self._lib = lib()
         self._h = C.c_void_p()
+        self._device_id = int(device_id)
         rc = self._lib.mcrt_create(C.byref(self._h), int(device_id))
         if rc != 0:
             msg = self._lib.mcrt_last_error(None)
@@ -805,6 +883,7 @@ class Context:
     def upload_scene(self, scene_desc):
         self._sync_env()
         self._check(self._lib.mcrt_upload_scene(self._h, C.byref(scene_desc)), "mcrt_upload_scene")
+        self._scene_counts = {"surface": int(scene_desc.num_surfaces), "material": int(scene_desc.num_materials)}  # (render_matte's default names)
 
     def upload_photons(self, global_map, caustic_map, k_nearest, direct_visualization=False):
         self._sync_env()
@@ -974,6 +1053,101 @@ class Context:
         st = Stats()
         self._check(self._lib.mcrt_render_aov_device(self._h, C.byref(cam), int(global_seed), C.byref(bufs), C.byref(st)), "mcrt_render_aov_device")
         return st.as_dict()
+
+    def render_matte(self, cam, global_seed, key="material", ranks=MATTE_DEFAULT_RANKS, names=None, surface_key=None, aov=None, out=None, stats=None,
+                     num_keys=None):
+        """mcrt_render_matte: the ranked id / coverage mattes of the frame -> dict "id" [H,W,ranks] uint32, "coverage" [H,W,ranks],
+        "layer" [H,W,ranks,2] (the Cryptomatte channels: exr_layers(mattes=...)), "distinct" [H,W] uint32, plus "names", "codes", "manifest"
+        (the JSON text), "key", "ranks". key: "material", "surface" or "custom" (surface_key: [num_surfaces] key per surface; num_keys:
+        default len(names), else max(surface_key) + 1). names: a name per key, default "material%u" / "surface%u" / "key%u". aov: AOV
+        channel names (True = all) rendered from the same rays and hits -> result["aov"], render_aov's bits. out: a dict of arrays to write
+        into instead of fresh ones (the rows cam's shard owns are written). stats: a dict that receives mcrt_stats."""
+        self._sync_env()
+        ranks = int(ranks) or MATTE_DEFAULT_RANKS
+        par, keep = _matte_params(key, ranks, names, surface_key, num_keys)
+        n_keys = par.num_keys if key == "custom" else getattr(self, "_scene_counts", {}).get(key, 0)
+        res, bufs = {}, MatteBuffers()
+        for name, (dtype, tail) in MATTE_CHANNELS.items():
+            shape = (cam.height, cam.width) + tuple(int(ranks) if t == "ranks" else t for t in tail)
+            a = out[name] if out is not None and name in out else np.zeros(shape, dtype=dtype)
+            if not (out is not None and name in out) and name == "id":
+                a.fill(NO_KEY)
+            assert a.dtype == dtype and a.shape == shape and a.flags["C_CONTIGUOUS"], name
+            res[name] = a
+            setattr(bufs, name, a.ctypes.data)
+        aov_res, aov_bufs = {}, AovBuffers()
+        for name in (list(AOV_CHANNELS) if aov is True else list(aov or ())):
+            dtype, k = AOV_CHANNELS[name]
+            shape = (cam.height, cam.width) + ((k,) if k > 1 else ())
+            a = out["aov"][name] if out is not None and name in out.get("aov", {}) else np.zeros(shape, dtype=dtype)
+            assert a.dtype == dtype and a.shape == shape and a.flags["C_CONTIGUOUS"], name
+            aov_res[name] = a
+            setattr(aov_bufs, name, a.ctypes.data)
+        st = Stats()
+        self._check(self._lib.mcrt_render_matte(self._h, C.byref(cam), int(global_seed), C.byref(par), C.byref(bufs), C.byref(aov_bufs) if aov_res else None,
+                                                C.byref(st)), "mcrt_render_matte")
+        if stats is not None:
+            stats.update(st.as_dict())
+        res["names"] = [n.decode("latin-1") if isinstance(n, bytes) else str(n) for n in names] if names is not None else \
+            [MATTE_DEFAULT_NAMES[key].replace("%u", "%d") % k for k in range(n_keys)]
+        res["codes"] = np.array([matte_code(n) for n in res["names"]], dtype=np.uint32)
+        res["manifest"] = matte_manifest(key, n_keys, names)
+        res["key"], res["ranks"] = key, int(ranks)
+        if aov_res:
+            res["aov"] = aov_res
+        return res
+
+    def render_matte_device(self, cam, global_seed, pointers, key="material", ranks=MATTE_DEFAULT_RANKS, names=None, surface_key=None, aov_pointers=None,
+                            num_keys=None):
+        """mcrt_render_matte_device: pointers = dict "id" / "coverage" / "layer" / "distinct" -> raw device pointer (owned rows only, packed
+        like render_device's output); aov_pointers likewise for the AOV channels. Synchronous; returns the stats dict."""
+        self._sync_env()
+        par, keep = _matte_params(key, ranks, names, surface_key, num_keys)
+        bufs = _pointer_struct(MatteBuffers, pointers, MATTE_CHANNELS)
+        aov_bufs = _pointer_struct(AovBuffers, aov_pointers, AOV_CHANNELS)
+        st = Stats()
+        self._check(self._lib.mcrt_render_matte_device(self._h, C.byref(cam), int(global_seed), C.byref(par), C.byref(bufs),
+                                                       C.byref(aov_bufs) if aov_pointers else None, C.byref(st)), "mcrt_render_matte_device")
+        return st.as_dict()
+
+    def matte_rank_device(self, pixels, spp, keys_ptr, ranks, codes_ptr, pointers):
+        """mcrt_matte_rank_device on raw device pointers: keys [spp][pixels] uint32 (0xFFFFFFFF = none), codes [greater than every key] or
+        None, pointers = dict "id" / "coverage" / "layer" / "distinct" -> buffers of `pixels` pixels. The inputs must be complete when
+        this is called. Synchronous; returns the stats dict."""
+        self._sync_env()
+        bufs = _pointer_struct(MatteBuffers, pointers, MATTE_CHANNELS)
+        st = Stats()
+        self._check(self._lib.mcrt_matte_rank_device(self._h, int(pixels), int(spp), C.c_void_p(int(keys_ptr)) if keys_ptr else None, int(ranks),
+                                                     C.c_void_p(int(codes_ptr)) if codes_ptr else None, C.byref(bufs), C.byref(st)), "mcrt_matte_rank_device")
+        return st.as_dict()
+
+    def matte_rank(self, keys, ranks=MATTE_DEFAULT_RANKS, codes=None, stats=None):
+        """The ranking of mcrt_render_matte on a caller's own ids: keys [spp, pixels] uint32 (numpy; 0xFFFFFFFF = none), codes [num_keys]
+        uint32 or None (then no "layer") -> dict "id" [pixels, ranks], "coverage", "layer" [pixels, ranks, 2], "distinct" [pixels]. The
+        arrays cross to this context's device and back through torch."""
+        import torch
+        keys = np.ascontiguousarray(keys, dtype=np.uint32)
+        assert keys.ndim == 2, keys.shape
+        spp, pixels = keys.shape
+        if codes is not None:
+            codes = np.ascontiguousarray(codes, dtype=np.uint32)
+            assert not (keys != NO_KEY).any() or int(keys[keys != NO_KEY].max()) < codes.shape[0], "a key without a code"
+        dev = torch.device("cuda", self._device_id)
+        up = lambda a: torch.from_numpy((a if a.flags.writeable else a.copy()).view(np.int32)).to(dev)
+        d_keys, d_codes = up(keys.reshape(-1)), up(codes) if codes is not None else None
+        r = max(int(ranks), 0) or MATTE_DEFAULT_RANKS
+        outs = {"id": torch.full((pixels, r), -1, dtype=torch.int32, device=dev), "coverage": torch.zeros((pixels, r), dtype=torch.float64, device=dev),
+                "distinct": torch.zeros((pixels,), dtype=torch.int32, device=dev)}
+        if codes is not None:
+            outs["layer"] = torch.zeros((pixels, r, 2), dtype=torch.float64, device=dev)
+        torch.cuda.synchronize()
+        st = self.matte_rank_device(pixels, spp, d_keys.data_ptr(), ranks, d_codes.data_ptr() if d_codes is not None else None,
+                                    {k: v.data_ptr() for k, v in outs.items()})
+        if stats is not None:
+            stats.update(st)
+        res = {k: v.cpu().numpy() for k, v in outs.items()}
+        res["id"], res["distinct"] = res["id"].view(np.uint32), res["distinct"].view(np.uint32)
+        return res
 
     def denoise(self, rgb, aov, stats=None, **params):
         """mcrt_denoise: the edge-avoiding a-trous filter on the beauty frame rgb [H,W,3], guided by aov - render_aov's dict of the same

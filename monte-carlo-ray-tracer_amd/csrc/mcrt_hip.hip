@@ -1767,6 +1767,10 @@ void ctxAovScene(const mcrt_ctx* ctx, AovScene* out, const uint32_t** sobol_tab)
     out->prim = d.prim;
     *sobol_tab = d.sobol_tab;
 }
+void ctxSceneCounts(const mcrt_ctx* ctx, uint32_t* num_surfaces, uint32_t* num_materials) {
+    *num_surfaces = (uint32_t)ctx->scene.num_surfaces;
+    *num_materials = (uint32_t)ctx->scene.num_materials;
+}
 // what a render may take per-sample channels for: idle, a scene, a camera, and a film that keeps its samples when a channel is wanted
 int ctxSampleTargetsBegin(mcrt_ctx* ctx, const mcrt_camera_desc* cam, const mcrt_frame_summary* targets, const char* what) {
     if (int rc = ctxIdle(ctx, what)) return rc;

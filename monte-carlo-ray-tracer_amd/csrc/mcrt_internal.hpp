@@ -30,17 +30,18 @@ int intersectDeviceArrays(mcrt_ctx* ctx, uint64_t n, const double* d_start, cons
 // ctxIdle: no render in flight (MCRT_ERR_INVALID recorded under `what`), device selected. ctxNeedScene: MCRT_ERR_NO_SCENE under `what`.
 // ctxPassScratch: buffer `which` (0..kPassSlots-1) of a family's scratch - every (family, slot) a buffer of its own, kept in the context
 // and grown on demand like the operators'; at least 8 bytes; nullptr, the HIP error cleared, when the allocation fails.
-// ctxAovScene: the uploaded scene's arrays in device memory.
+// ctxAovScene: the uploaded scene's arrays in device memory. ctxSceneCounts: its numbers of surfaces and materials.
 // ctxSampleTargetsBegin: ctxIdle, ctxNeedScene, MCRT_ERR_INVALID for no camera, MCRT_ERR_UNSUPPORTED for a camera whose film splats when
 // a channel is wanted - then the channels of `targets` other than rgb (mcrt_summary_channels.hpp; nullptr: not wanted) are what the pass
 // loops of the next renders of this context fill (their epilogue's launches), until ctxSampleTargetsEnd clears them (SampleTargetsScope does).
 struct AovScene;
-enum PassFamily { kPassAov, kPassDenoise, kPassPixelStats, kPassRobust, kPassDenoiseVar, kPassAccumulate, kPassDenoiseDual, kPassExr, kPassFamilies };
+enum PassFamily { kPassAov, kPassDenoise, kPassPixelStats, kPassRobust, kPassDenoiseVar, kPassAccumulate, kPassDenoiseDual, kPassExr, kPassMatte, kPassFamilies };
 constexpr int kPassSlots = 6;
 int ctxIdle(mcrt_ctx* ctx, const char* what);
 int ctxNeedScene(mcrt_ctx* ctx, const char* what);
 void* ctxPassScratch(mcrt_ctx* ctx, PassFamily family, int which, size_t bytes);
 void ctxAovScene(const mcrt_ctx* ctx, AovScene* out, const uint32_t** sobol_tab);
+void ctxSceneCounts(const mcrt_ctx* ctx, uint32_t* num_surfaces, uint32_t* num_materials);
 int ctxSampleTargetsBegin(mcrt_ctx* ctx, const mcrt_camera_desc* cam, const mcrt_frame_summary* targets, const char* what);
 void ctxSampleTargetsEnd(mcrt_ctx* ctx);
 }  // namespace mcrt

@@ -7,6 +7,7 @@
 //               [--denoise OUT.f64 [--denoise-iterations N]] [--denoise-variance OUT.f64 [--denoise-variance-out VAR.f64]]
 //               [--denoise-dual OUT.f64 [--denoise-dual-out VAR.f64]] [--stats PREFIX] [--robust PREFIX [--robust-kappa X] [--robust-radius R]]
 //               [--converge TARGET [--max-spp N]] [--exr OUT.exr [--exr-compression none|zip]]
+//               [--matte PREFIX [--matte-key material|surface] [--matte-ranks N]]
 //
 // Writes the frame as raw FP64 RGB, row-major (what Image::operator() holds, camera/image.cpp:53-56),
 // and prints the statistics. --tga also develops it the way Image::save does (auto exposure / gain, tone map, sRGB bytes:
@@ -39,6 +40,11 @@
 // denoise.*, denoise_variance.*, denoise_variance.variance.*, denoise_dual.*, denoise_dual.variance.*. Colour is HALF; depth, position,
 // variances and level FLOAT; ids and counts UINT. The attributes mcrt:spp, mcrt:seed, mcrt:integrator and mcrt:kernel say what was
 // rendered. --exr-compression: zip (the default) or none. The .f64 outputs stay as they are (one device).
+// --matte also writes the ranked id / coverage mattes of the same camera and seed (mcrt_render_matte, device 0; --matte-key material, the
+// default, or surface; --matte-ranks N, default 6): PREFIX.id.u32 and PREFIX.coverage.f64 ([H][W][ranks]) and PREFIX.distinct.u32. With --exr
+// the file also holds them as the Cryptomatte layer CryptoMaterial or CryptoSurface - FLOAT channels CryptoMaterial00.R/G/B/A, 01.*, ... -
+// with the attributes cryptomatte/<key>/name, /hash, /conversion and /manifest (mcrt_matte_manifest); a manifest past 1 MiB (the surface
+// key on large meshes) is left out, with a message: the ids then still separate the surfaces, without names.
 // --devices renders the frame on several GPUs from this one process (mcrt_render_multi: one host thread per GPU).
 #include <cstdio>
 #include <cstdlib>
@@ -68,7 +74,9 @@ int main(int argc, char** argv) {
     image.plain = (uint32_t)mcrt_image_param(img, "image_plain");
     image.exposure_compensation = from_bits(mcrt_image_param(img, "image_exposure_ev_bits"));
     image.gain_compensation = from_bits(mcrt_image_param(img, "image_gain_ev_bits"));
-    std::string tga, aov, denoise, dvar, dvar_out, ddual, ddual_out, pstats, robust, exr;
+    std::string tga, aov, denoise, dvar, dvar_out, ddual, ddual_out, pstats, robust, exr, matte;
+    mcrt_matte_params mparams{};
+    std::deque<std::string> exr_attr_text;  // the attributes --matte adds to --exr's: name, value, name, value, ...
     mcrt_exr_params eparams{};
     // what --exr writes: the channels, their names and the buffers that outlive the block that filled them
     std::vector<mcrt_exr_channel> exr_channels;
@@ -115,6 +123,9 @@ int main(int argc, char** argv) {
         else if (k == "--stats" && i + 1 < argc) pstats = argv[++i];
         else if (k == "--robust" && i + 1 < argc) robust = argv[++i];
         else if (k == "--exr" && i + 1 < argc) exr = argv[++i];
+        else if (k == "--matte" && i + 1 < argc) matte = argv[++i];
+        else if (k == "--matte-key" && i + 1 < argc) mparams.key = (argv[++i][0] | 0x20) == 's' ? MCRT_MATTE_SURFACE : MCRT_MATTE_MATERIAL;
+        else if (k == "--matte-ranks") mparams.ranks = (uint32_t)val();
         else if (k == "--exr-compression" && i + 1 < argc) eparams.compression = MCRT_EXR_COMPRESSION_SET | ((argv[++i][0] | 0x20) == 'n' ? MCRT_EXR_COMPRESSION_NONE : MCRT_EXR_COMPRESSION_ZIP);
         else if (k == "--robust-kappa" && i + 1 < argc) rparams.kappa = std::strtod(argv[++i], nullptr);
         else if (k == "--robust-radius") rparams.radius = (uint32_t)val();
@@ -418,13 +429,74 @@ int main(int argc, char** argv) {
             exr_one("material.id", exr_keep_u32(material), MCRT_EXR_UINT, 1, 0);
         }
     }
+    if (!matte.empty()) {
+        const size_t px = (size_t)cam.width * cam.height;
+        const uint32_t ranks = mparams.ranks ? mparams.ranks : MCRT_MATTE_DEFAULT_RANKS;
+        if (ranks > MCRT_MATTE_MAX_RANKS) {
+            std::fprintf(stderr, "--matte-ranks: %u at most\n", MCRT_MATTE_MAX_RANKS);
+            return 2;
+        }
+        std::vector<uint32_t> id(px * ranks), distinct(px);
+        std::vector<double> coverage(px * ranks), layer(exr.empty() ? 0 : px * ranks * 2);
+        const mcrt_matte_buffers mb{id.data(), coverage.data(), exr.empty() ? nullptr : layer.data(), distinct.data()};
+        mcrt_stats mst;
+        rc = mcrt_render_matte(ctx, &cam, seed, &mparams, &mb, nullptr, &mst);
+        if (rc != MCRT_OK) {
+            std::fprintf(stderr, "mcrt error %d: %s\n", rc, mcrt_last_error(ctx));
+            return 1;
+        }
+        auto dump = [&](const std::string& path, const void* data, size_t bytes) {
+            FILE* o = std::fopen(path.c_str(), "wb");
+            const bool ok = o && std::fwrite(data, 1, bytes, o) == bytes;
+            if (o) std::fclose(o);
+            if (!ok) std::fprintf(stderr, "cannot write %s\n", path.c_str());
+            return ok;
+        };
+        if (!(dump(matte + ".id.u32", id.data(), px * ranks * 4) && dump(matte + ".coverage.f64", coverage.data(), px * ranks * 8) &&
+              dump(matte + ".distinct.u32", distinct.data(), px * 4)))
+            return 1;
+        uint32_t most = 0;
+        for (uint32_t d : distinct) most = d > most ? d : most;
+        std::printf("{\"matte\":\"%s\",\"key\":\"%s\",\"ranks\":%u,\"max_distinct\":%u,\"rays\":%llu,\"kernel_ms\":%.3f,\"total_ms\":%.3f}\n", matte.c_str(),
+                    mparams.key == MCRT_MATTE_SURFACE ? "surface" : "material", ranks, most, (unsigned long long)mst.rays, mst.kernel_ms, mst.total_ms);
+        if (!exr.empty()) {
+            const std::string name = mparams.key == MCRT_MATTE_SURFACE ? "CryptoSurface" : "CryptoMaterial";
+            const double* data = exr_keep(layer);
+            for (uint32_t i = 0; i < 2 * ranks; i++) {
+                char level[8];
+                std::snprintf(level, sizeof level, "%02u", i / 4);
+                exr_one(name + level + "." + "RGBA"[i % 4], data, MCRT_EXR_FLOAT, 2 * ranks, i);
+            }
+            char code[12];
+            std::snprintf(code, sizeof code, "%08x", mcrt_matte_code(name.c_str()));
+            const std::string key = "cryptomatte/" + std::string(code, 7) + "/";
+            const char* said[3][2] = {{"name", name.c_str()}, {"hash", "MurmurHash3_32"}, {"conversion", "uint32_to_float32"}};
+            for (const auto& kv : said) {
+                exr_attr_text.push_back(key + kv[0]);
+                exr_attr_text.push_back(kv[1]);
+            }
+            const mcrt_scene_desc* sd = mcrt_image_scene(img);
+            const uint32_t num_keys = mparams.key == MCRT_MATTE_SURFACE ? sd->num_surfaces : sd->num_materials;
+            const int64_t need = mcrt_matte_manifest(&mparams, num_keys, nullptr, 0);
+            if (need > 0 && need <= (1 << 20)) {
+                std::string text((size_t)need, '\0');
+                mcrt_matte_manifest(&mparams, num_keys, &text[0], (uint64_t)need);
+                text.resize((size_t)need - 1);
+                exr_attr_text.push_back(key + "manifest");
+                exr_attr_text.push_back(text);
+            } else {
+                std::fprintf(stderr, "--matte: the manifest of %u names would take %lld bytes: left out of %s\n", num_keys, (long long)need, exr.c_str());
+            }
+        }
+    }
     if (!exr.empty()) {
         const std::string a_spp = std::to_string(spp), a_seed = std::to_string(seed), a_kernel = std::to_string(st.kernel_id);
-        const mcrt_exr_attribute attributes[4] = {{"mcrt:spp", a_spp.c_str()}, {"mcrt:seed", a_seed.c_str()},
-                                                  {"mcrt:integrator", photon ? "photon_mapper" : "path_tracer"}, {"mcrt:kernel", a_kernel.c_str()}};
+        std::vector<mcrt_exr_attribute> attributes = {{"mcrt:spp", a_spp.c_str()}, {"mcrt:seed", a_seed.c_str()},
+                                                      {"mcrt:integrator", photon ? "photon_mapper" : "path_tracer"}, {"mcrt:kernel", a_kernel.c_str()}};
+        for (size_t i = 0; i + 1 < exr_attr_text.size(); i += 2) attributes.push_back({exr_attr_text[i].c_str(), exr_attr_text[i + 1].c_str()});
         mcrt_exr_result er;
         mcrt_stats est;
-        rc = mcrt_exr_save(ctx, exr.c_str(), cam.width, cam.height, exr_channels.data(), (uint32_t)exr_channels.size(), attributes, 4, &eparams, &er, &est);
+        rc = mcrt_exr_save(ctx, exr.c_str(), cam.width, cam.height, exr_channels.data(), (uint32_t)exr_channels.size(), attributes.data(), (uint32_t)attributes.size(), &eparams, &er, &est);
         if (rc != MCRT_OK) {
             std::fprintf(stderr, "mcrt error %d: %s\n", rc, mcrt_last_error(ctx));
             return 1;
