@@ -890,6 +890,91 @@ int mcrt_matte_rank_device(mcrt_ctx* ctx, uint64_t pixels, uint32_t spp, const u
 uint32_t mcrt_matte_code(const char* name);
 int64_t mcrt_matte_manifest(const mcrt_matte_params* params /* may be NULL */, uint32_t num_keys, char* buf /* may be NULL when cap is 0 */, uint64_t cap);
 
+/* ------------------------------------------------------------------------------------------
+ * Frame comparison: error metrics and error maps between two frames of one camera - a frame under test rgb and a reference ref,
+ * both [height][width][3] FP64 - computed on the device, so that only the results cross PCIe. The reference has no such
+ * output. Only FP64 + - * /, compare and select, in the order written here, uncontracted, no libm routine on the device: a
+ * function of the two frames (and the mask) bit for bit. sqrt and log10 of the final scalars run on the host.
+ *
+ *   finite(v) = (v - v == 0.0);   eps, peak, ssim_range: mcrt_compare_params
+ *
+ * 1. Per pixel p (row-major, p = y * width + x), with x_c, r_c the channels of rgb and ref and d_c = x_c - r_c:
+ *   p is masked when a mask [height][width] is given and !(mask_p > 0) (a NaN is not > 0); otherwise p is nonfinite when any
+ *   of its six values is not finite; otherwise it is compared. A masked or nonfinite pixel is excluded: it adds 0.0 at its
+ *   own position to every sum and holds 0.0 in the maps, so the reduction tree depends on width * height alone.
+ *   a_c   = d_c < 0 ? 0.0 - d_c : d_c
+ *   se_p  = (d_r * d_r + d_g * d_g) + d_b * d_b
+ *   ae_p  = (a_r + a_g) + a_b
+ *   rel_p = ((d_r * d_r) / (r_r * r_r + eps) + (d_g * d_g) / (r_g * r_g + eps)) + (d_b * d_b) / (r_b * r_b + eps)
+ *   differs_p = any channel's 64-bit pattern differs between rgb and ref (+0 and -0 differ, equal NaN patterns do not); it
+ *   is evaluated for every pixel that is not masked, the nonfinite ones included: the count of pixels off the reference's bits.
+ * sum_se, sum_ae, sum_rel = treesum over the pixels in row-major order, treesum being the one defined for mcrt_frame_noise
+ * above (blocks of 256 consecutive values, stride 128 .. 1, again on the block values): not another one.
+ * compared, nonfinite, masked, differing are exact counts (compared + nonfinite + masked == pixels). max_abs is the largest a_c
+ * over the compared pixels and channels, max_abs_pixel the lowest pixel that holds it and max_abs_channel the lowest channel
+ * of that pixel that does; with nothing compared they are 0.0, UINT64_MAX and UINT32_MAX.
+ * On the host, with n = (double)(3 * compared): mse = sum_se / n, mae = sum_ae / n, relmse = sum_rel / n, rmse = sqrt(mse),
+ * psnr = 10 * log10(peak * peak / mse), +inf at mse == 0; all five are 0.0 when compared == 0.
+ *
+ * 2. SSIM (Wang, Bovik, Sheikh, Simoncelli 2004) on the luminance L(x) = (0.2126 * x.r + 0.7152 * x.g) + 0.0722 * x.b - the L of
+ * "Firefly suppression" - with the separable 11 x 11 Gaussian window of sigma 1.5. The mask is ignored. The eleven 1-D weights
+ * g[-5 .. 5] are g[i] = MCRT_SSIM_G<|i|> below - exp(-i * i / 4.5) normalised to sum 1, computed once in float64; the
+ * hexadecimal literals are the definition. With Lx = L(rgb), Lr = L(ref) and the five fields f = {Lx, Lr, Lx * Lx, Lr * Lr, Lx * Lr}:
+ *   h_k(x, y) = (((0.0 + g[-5] * f_k(x - 5, y)) + g[-4] * f_k(x - 4, y)) + ... + g[5] * f_k(x + 5, y))     (ascending dx)
+ *   w_k(x, y) = (((0.0 + g[-5] * h_k(x, y - 5)) + g[-4] * h_k(x, y - 4)) + ... + g[5] * h_k(x, y + 5))     (ascending dy)
+ * Only the centres whose window lies inside the frame exist: 5 <= x < width - 5, 5 <= y < height - 5. At a centre:
+ *   mx = w_0, mr = w_1, sxx = w_2 - mx * mx, srr = w_3 - mr * mr, sxr = w_4 - mx * mr
+ *   C1 = (0.01 * ssim_range) * (0.01 * ssim_range), C2 = (0.03 * ssim_range) * (0.03 * ssim_range)
+ *   ssim = ((2.0 * (mx * mr) + C1) * (2.0 * sxr + C2)) / (((mx * mx + mr * mr) + C1) * ((sxx + srr) + C2))
+ * A centre whose ssim is not finite adds 0.0 and is counted in ssim_excluded. sum_ssim = treesum over the centres in row-major
+ * order of the (width - 10) x (height - 10) grid, ssim_centres their number, and on the host
+ * mean_ssim = sum_ssim / (double)(ssim_centres - ssim_excluded), 0.0 when that count is 0. A frame narrower or lower than 11
+ * has no centre: ssim_centres == 0, mean_ssim == 0.0, no error. In this order a frame compared with itself has ssim == 1.0
+ * exactly at every finite centre. The constants 0.01 and 0.03 presume display-referred values in [0, ssim_range]: for HDR
+ * frames set ssim_range to the frames' white level or compare tone-mapped frames. want_ssim == 0 skips all of part 2.
+ *
+ * 3. Maps (mcrt_compare_maps; every pointer may be NULL, the buffers are [height][width] FP64, separate from each other and
+ * from the inputs): squared_error = se_p, relative = rel_p, ssim = the centre's ssim (0.0 outside the centres and at an
+ * excluded centre; not written when want_ssim == 0).
+ *
+ * The call needs no scene, is synchronous on the context's stream (device inputs must be complete when it is called) and, in
+ * the device form, moves only the result across PCIe. Refused (MCRT_ERR_INVALID): a render in flight; rgb, ref or result NULL;
+ * width * height 0 or >= 2^32; eps, peak or ssim_range not finite or negative (0 = the default). stats: kernel_ms (HIP events
+ * around the call's own launches), total_ms, kernel_launches. */
+#define MCRT_SSIM_G0 0x1.106560aa892c0p-2
+#define MCRT_SSIM_G1 0x1.b43c3f52b19f2p-3
+#define MCRT_SSIM_G2 0x1.bff0fe8e98418p-4
+#define MCRT_SSIM_G3 0x1.26eb175d83f67p-5
+#define MCRT_SSIM_G4 0x1.f1fe01ae5a5b8p-8
+#define MCRT_SSIM_G5 0x1.0d956b52a1d70p-10
+typedef struct mcrt_compare_params {   /* params NULL: every default. 0 = the default for the three doubles */
+    double eps;          /* relMSE's constant; default 0.01 */
+    double peak;         /* PSNR's peak value; default 1.0 */
+    double ssim_range;   /* SSIM's dynamic range; default 1.0 */
+    int32_t want_ssim;   /* taken as it is: 0 skips SSIM (params NULL: 1) */
+    uint32_t reserved;   /* 0 */
+} mcrt_compare_params;                 /* 32 bytes */
+typedef struct mcrt_compare_maps {     /* DEVICE (or HOST) [height][width] FP64; NULL = not wanted */
+    double* squared_error;
+    double* relative;
+    double* ssim;
+} mcrt_compare_maps;
+typedef struct mcrt_compare_result {
+    double sum_se, sum_ae, sum_rel, sum_ssim;
+    double max_abs;
+    uint64_t max_abs_pixel;
+    uint32_t max_abs_channel, reserved;
+    uint64_t pixels, compared, nonfinite, masked, differing, ssim_centres, ssim_excluded;
+    double mse, mae, relmse, rmse, psnr, mean_ssim;   /* computed on the host */
+} mcrt_compare_result;                 /* 160 bytes */
+int mcrt_frame_compare_device(mcrt_ctx* ctx, uint32_t width, uint32_t height, const double* d_rgb, const double* d_ref,
+                              const double* d_mask /* may be NULL */, const mcrt_compare_params* params /* may be NULL */,
+                              const mcrt_compare_maps* d_maps /* may be NULL */, mcrt_compare_result* result, mcrt_stats* stats /* may be NULL */);
+/* Same with HOST pointers. */
+int mcrt_frame_compare(mcrt_ctx* ctx, uint32_t width, uint32_t height, const double* rgb, const double* ref,
+                       const double* mask /* may be NULL */, const mcrt_compare_params* params /* may be NULL */,
+                       const mcrt_compare_maps* maps /* may be NULL */, mcrt_compare_result* result, mcrt_stats* stats /* may be NULL */);
+
 /* Photon emission pass on the GPU. Replaces the thread fan-out of
  * PhotonMapper::PhotonMapper (integrator/photon-mapper/photon-mapper.cpp:80-115: per emission
  * Sampler::initiate(light), setIndex(offset+i), light point + cosine direction, emitPhoton :225-277) for

@@ -216,6 +216,31 @@ class FrameNoise(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+# Frame comparison (include/mcrt.h "Frame comparison")
+COMPARE_MAPS = ("squared_error", "relative", "ssim")
+COMPARE_ERROR_CHANNELS = {"squared_error": "se", "relative": "rel", "ssim": "ssim"}  # exr_layers(errors=): error.se, error.rel, error.ssim
+
+
+class CompareParams(C.Structure):
+    """mcrt_compare_params: a zero double = the default; want_ssim is taken as it is."""
+    _fields_ = [("eps", C.c_double), ("peak", C.c_double), ("ssim_range", C.c_double), ("want_ssim", C.c_int32), ("reserved", C.c_uint32)]
+
+
+class CompareMaps(C.Structure):
+    """mcrt_compare_maps: a null pointer = not wanted."""
+    _fields_ = [("squared_error", C.c_void_p), ("relative", C.c_void_p), ("ssim", C.c_void_p)]
+
+
+class CompareResult(C.Structure):
+    """mcrt_compare_result."""
+    _fields_ = ([(k, C.c_double) for k in ("sum_se", "sum_ae", "sum_rel", "sum_ssim", "max_abs")] + [("max_abs_pixel", C.c_uint64), ("max_abs_channel", C.c_uint32),
+                ("reserved", C.c_uint32)] + [(k, C.c_uint64) for k in ("pixels", "compared", "nonfinite", "masked", "differing", "ssim_centres", "ssim_excluded")] +
+                [(k, C.c_double) for k in ("mse", "mae", "relmse", "rmse", "psnr", "mean_ssim")])
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved"}
+
+
 class HighlightBuffers(C.Structure):
     """mcrt_highlight_buffers: a null pointer = channel not wanted."""
     _fields_ = [("tops", C.c_void_p), ("level", C.c_void_p)]
@@ -400,7 +425,7 @@ def _exr_source(a):
 _EXR_FLOAT_LAYERS = ("depth", "position", "variance", "error", "level")
 
 
-def exr_layers(rgb=None, aov=None, stats=None, highlights=None, robust=None, denoised=None, pixel_types=None, mattes=None):
+def exr_layers(rgb=None, aov=None, stats=None, highlights=None, robust=None, denoised=None, pixel_types=None, mattes=None, errors=None):
     """The channel dict Context.exr_save takes, from what the render_* and denoise_* methods return, under fixed names:
       rgb [H,W,3]                       R, G, B
       aov (render_aov's dict)           depth.Z, position.X/Y/Z, normal.X/Y/Z, shading_normal.X/Y/Z, albedo.R/G/B, coverage.A, surface.id, material.id
@@ -411,6 +436,8 @@ def exr_layers(rgb=None, aov=None, stats=None, highlights=None, robust=None, den
       mattes {name: render_matte's dict}  name00.R/G/B/A, name01.R/G/B/A, ...: views of its "layer" [H,W,ranks,2] - (id, coverage) of
                                         ranks 2 l and 2 l + 1 -, always FLOAT whatever pixel_types says (HALF would destroy the ids);
                                         matte_attributes gives the attributes that go with them
+      errors (frame_compare's maps)     error.se, error.rel, error.ssim: "squared_error", "relative", "ssim" [H,W] of the dict (those
+                                        that are there), always FLOAT
     -> dict name -> (view [H,W], "half" | "float" | "uint"). Colour is HALF; depth, position, variance, error and level FLOAT; ids and
     counts UINT. pixel_types: {channel or layer name: type} overrides that (a layer is a name without its last component). The views
     are of the arrays and tensors given, numpy or torch alike: nothing is copied."""
@@ -461,6 +488,10 @@ def exr_layers(rgb=None, aov=None, stats=None, highlights=None, robust=None, den
         flat = layer.reshape(layer.shape[0], layer.shape[1], 2 * layer.shape[2])
         for i in range(flat.shape[2]):
             out["%s%02d.%s" % (name, i // 4, "RGBA"[i % 4])] = (flat[..., i], "float")
+    for key, part in COMPARE_ERROR_CHANNELS.items():
+        if errors is not None and errors.get(key) is not None:
+            assert errors[key].ndim == 2, (key, tuple(errors[key].shape))
+            out["error." + part] = (errors[key], "float")
     return out
 
 
@@ -591,6 +622,9 @@ def lib():
         L.mcrt_matte_code.restype = C.c_uint32
         L.mcrt_matte_manifest.argtypes = [C.POINTER(MatteParams), C.c_uint32, C.c_char_p, C.c_uint64]
         L.mcrt_matte_manifest.restype = C.c_int64
+    if hasattr(L, "mcrt_frame_compare"):  # (likewise)
+        L.mcrt_frame_compare.argtypes = [vp, C.c_uint32, C.c_uint32, vp, vp, vp, C.POINTER(CompareParams), C.POINTER(CompareMaps), C.POINTER(CompareResult), C.POINTER(Stats)]
+        L.mcrt_frame_compare_device.argtypes = L.mcrt_frame_compare.argtypes
     L.mcrt_sampler.argtypes = [vp, C.c_uint64, _u32p, _u32p, C.c_uint32, C.c_uint32, _dp]
     L.mcrt_knn.argtypes = [vp, C.c_int, C.c_uint64, _dp, C.c_uint32, _u32p, _u32p, _dp]
     L.mcrt_bsdf.argtypes = [vp, C.c_uint64, _dp, _dp, _dp]
@@ -1318,6 +1352,59 @@ class Context:
         self._check(self._lib.mcrt_frame_noise_device(self._h, int(pixels), int(spp), C.c_void_p(int(rgb_ptr)) if rgb_ptr else None,
                                                       C.c_void_p(int(variance_ptr)) if variance_ptr else None, C.byref(r)), "mcrt_frame_noise_device")
         return r.as_dict()
+
+    def frame_compare(self, rgb, ref, mask=None, eps=None, peak=None, ssim_range=None, ssim=True, maps=False, stats=None):
+        """mcrt_frame_compare: the frame rgb [H,W,3] against the reference ref [H,W,3], mask [H,W] or None (a pixel takes part where
+        mask > 0) -> dict of mcrt_compare_result's fields; with maps=True also "squared_error", "relative" and - with ssim - "ssim",
+        [H,W] each (maps may also name the ones wanted). numpy arrays go through the host-pointer form; torch tensors on this context's
+        device (float64, contiguous) through mcrt_frame_compare_device, and the maps come back as tensors of that device. eps, peak,
+        ssim_range: None = the default. stats: a dict that receives mcrt_stats."""
+        self._sync_env()
+        tensors = _is_tensor(rgb)
+        wanted = [k for k in COMPARE_MAPS if (maps is True or (maps and k in maps)) and (ssim or k != "ssim")]
+        par = CompareParams(eps or 0.0, peak or 0.0, ssim_range or 0.0, 1 if ssim else 0, 0)
+        for name, v in (("eps", eps), ("peak", peak), ("ssim_range", ssim_range)):
+            if v is not None and not v > 0:  # (0 would mean the default to the library: the caller gave a value)
+                raise McrtError("frame_compare: %s must be finite and > 0, not %r" % (name, v))
+        res, st, out = CompareResult(), Stats(), {}
+        if tensors:
+            import torch
+            assert _is_tensor(ref) and (mask is None or _is_tensor(mask)), "device tensors and numpy arrays are not mixed"
+            frames = [rgb, ref] + ([mask] if mask is not None else [])
+            assert all(str(t.dtype) == "torch.float64" and t.is_contiguous() and t.is_cuda for t in frames), "float64, contiguous, on the device"
+            height, width = int(rgb.shape[0]), int(rgb.shape[1])
+            out = {k: torch.empty((height, width), dtype=torch.float64, device=rgb.device) for k in wanted}
+            ptr = lambda t: C.c_void_p(int(t.data_ptr()))
+            torch.cuda.synchronize(rgb.device)
+            call = self._lib.mcrt_frame_compare_device
+        else:
+            rgb, ref = np.ascontiguousarray(rgb, dtype=np.float64), np.ascontiguousarray(ref, dtype=np.float64)
+            mask = None if mask is None else np.ascontiguousarray(mask, dtype=np.float64)
+            height, width = rgb.shape[:2]
+            out = {k: np.empty((height, width)) for k in wanted}
+            ptr = lambda a: C.c_void_p(a.ctypes.data)
+            call = self._lib.mcrt_frame_compare
+        assert rgb.ndim == 3 and rgb.shape[2] == 3 and tuple(ref.shape) == tuple(rgb.shape), (tuple(rgb.shape), tuple(ref.shape))
+        assert mask is None or tuple(mask.shape) == (height, width), tuple(mask.shape)
+        bufs = CompareMaps(**{k: ptr(a) for k, a in out.items()})
+        self._check(call(self._h, width, height, ptr(rgb), ptr(ref), ptr(mask) if mask is not None else None, C.byref(par), C.byref(bufs), C.byref(res),
+                         C.byref(st)), "mcrt_frame_compare")
+        if stats is not None:
+            stats.update(st.as_dict())
+        r = res.as_dict()
+        r.update(out)
+        return r
+
+    def frame_compare_device(self, width, height, rgb_ptr, ref_ptr, mask_ptr=None, pointers=None, params=None):
+        """mcrt_frame_compare_device on raw device pointers of frames that are complete when this is called; pointers = dict map
+        (COMPARE_MAPS) -> raw device pointer, params a CompareParams or None. Synchronous -> (result dict, stats dict)."""
+        self._sync_env()
+        bufs = _pointer_struct(CompareMaps, pointers, COMPARE_MAPS)
+        res, st = CompareResult(), Stats()
+        p = lambda x: C.c_void_p(int(x)) if x else None
+        self._check(self._lib.mcrt_frame_compare_device(self._h, int(width), int(height), p(rgb_ptr), p(ref_ptr), p(mask_ptr), C.byref(params) if params is not None else None,
+                                                        C.byref(bufs) if pointers is not None else None, C.byref(res), C.byref(st)), "mcrt_frame_compare_device")
+        return res.as_dict(), st.as_dict()
 
     def render_highlights(self, cam, global_seed, integrator=INTEGRATOR_PATH_TRACER, channels=None, stats_channels=(), stats=None, out=None):
         """mcrt_render_highlights: the frame of sample_image plus the highlights of its samples -> dict "rgb" [H,W,3] and the channels

@@ -7,7 +7,7 @@
 //               [--denoise OUT.f64 [--denoise-iterations N]] [--denoise-variance OUT.f64 [--denoise-variance-out VAR.f64]]
 //               [--denoise-dual OUT.f64 [--denoise-dual-out VAR.f64]] [--stats PREFIX] [--robust PREFIX [--robust-kappa X] [--robust-radius R]]
 //               [--converge TARGET [--max-spp N]] [--exr OUT.exr [--exr-compression none|zip]]
-//               [--matte PREFIX [--matte-key material|surface] [--matte-ranks N]]
+//               [--matte PREFIX [--matte-key material|surface] [--matte-ranks N]] [--compare REF]
 //
 // Writes the frame as raw FP64 RGB, row-major (what Image::operator() holds, camera/image.cpp:53-56),
 // and prints the statistics. --tga also develops it the way Image::save does (auto exposure / gain, tone map, sRGB bytes:
@@ -45,6 +45,11 @@
 // the file also holds them as the Cryptomatte layer CryptoMaterial or CryptoSurface - FLOAT channels CryptoMaterial00.R/G/B/A, 01.*, ... -
 // with the attributes cryptomatte/<key>/name, /hash, /conversion and /manifest (mcrt_matte_manifest); a manifest past 1 MiB (the surface
 // key on large meshes) is left out, with a message: the ids then still separate the surfaces, without names.
+// --compare compares the delivered frame with the reference frame REF (mcrt_frame_compare; default parameters, no mask) and prints one
+// JSON line of the result; with --robust, --denoise, --denoise-variance or --denoise-dual each of those frames is compared too, a line
+// each ("frame" names it). REF is raw little-endian binary64 of exactly width * height * 3 * 8 bytes, or a .npy file - version 1.0, '<f8',
+// C order, shape (height, width, 3): what bench.py --dump-outputs writes. With --exr the file also holds the error maps of the delivered
+// frame as FLOAT channels error.se, error.rel and error.ssim (device 0).
 // --devices renders the frame on several GPUs from this one process (mcrt_render_multi: one host thread per GPU).
 #include <cstdio>
 #include <cstdlib>
@@ -74,7 +79,7 @@ int main(int argc, char** argv) {
     image.plain = (uint32_t)mcrt_image_param(img, "image_plain");
     image.exposure_compensation = from_bits(mcrt_image_param(img, "image_exposure_ev_bits"));
     image.gain_compensation = from_bits(mcrt_image_param(img, "image_gain_ev_bits"));
-    std::string tga, aov, denoise, dvar, dvar_out, ddual, ddual_out, pstats, robust, exr, matte;
+    std::string tga, aov, denoise, dvar, dvar_out, ddual, ddual_out, pstats, robust, exr, matte, compare;
     mcrt_matte_params mparams{};
     std::deque<std::string> exr_attr_text;  // the attributes --matte adds to --exr's: name, value, name, value, ...
     mcrt_exr_params eparams{};
@@ -124,6 +129,7 @@ int main(int argc, char** argv) {
         else if (k == "--robust" && i + 1 < argc) robust = argv[++i];
         else if (k == "--exr" && i + 1 < argc) exr = argv[++i];
         else if (k == "--matte" && i + 1 < argc) matte = argv[++i];
+        else if (k == "--compare" && i + 1 < argc) compare = argv[++i];
         else if (k == "--matte-key" && i + 1 < argc) mparams.key = (argv[++i][0] | 0x20) == 's' ? MCRT_MATTE_SURFACE : MCRT_MATTE_MATERIAL;
         else if (k == "--matte-ranks") mparams.ranks = (uint32_t)val();
         else if (k == "--exr-compression" && i + 1 < argc) eparams.compression = MCRT_EXR_COMPRESSION_SET | ((argv[++i][0] | 0x20) == 'n' ? MCRT_EXR_COMPRESSION_NONE : MCRT_EXR_COMPRESSION_ZIP);
@@ -147,6 +153,41 @@ int main(int argc, char** argv) {
     }
     cam.shard_index = 0;
     cam.shard_count = 1;
+    // --compare's reference, read before anything is rendered: raw binary64, or .npy 1.0 of '<f8' in C order and shape (height, width, 3)
+    std::vector<double> reference;
+    if (!compare.empty()) {
+        const size_t want = (size_t)cam.width * cam.height * 3 * 8;
+        std::string bytes;
+        if (FILE* in = std::fopen(compare.c_str(), "rb")) {
+            char chunk[1 << 16];
+            for (size_t got; (got = std::fread(chunk, 1, sizeof chunk, in)) > 0;) bytes.append(chunk, got);
+            std::fclose(in);
+        } else {
+            std::fprintf(stderr, "--compare: cannot read %s\n", compare.c_str());
+            return 1;
+        }
+        size_t at = 0;
+        if (bytes.size() >= 10 && bytes.compare(0, 6, "\x93NUMPY") == 0) {
+            const size_t len = (unsigned char)bytes[8] | (size_t)(unsigned char)bytes[9] << 8;
+            const std::string head = bytes.size() >= 10 + len ? bytes.substr(10, len) : std::string();
+            std::string h;  // the header's dict without blanks and quotes
+            for (char c : head)
+                if (c != ' ' && c != '"' && c != '\'') h += c;
+            const std::string shape = "shape:(" + std::to_string(cam.height) + "," + std::to_string(cam.width) + ",3)";
+            if (bytes[6] != 1 || bytes[7] != 0 || h.find("descr:<f8") == std::string::npos || h.find("fortran_order:False") == std::string::npos ||
+                h.find(shape) == std::string::npos) {
+                std::fprintf(stderr, "--compare: %s is not .npy 1.0 of '<f8' in C order with %s: %s\n", compare.c_str(), shape.c_str(), head.c_str());
+                return 2;
+            }
+            at = 10 + len;
+        }
+        if (bytes.size() - at != want) {
+            std::fprintf(stderr, "--compare: %s holds %zu bytes of frame, %u x %u x 3 binary64 are %zu\n", compare.c_str(), bytes.size() - at, cam.width, cam.height, want);
+            return 2;
+        }
+        reference.resize(want / 8);
+        std::memcpy(reference.data(), bytes.data() + at, want);
+    }
     if (devices.empty()) devices.push_back(device);
     if (!exr.empty() && devices.size() > 1) {
         std::fprintf(stderr, "--exr takes one device\n");
@@ -216,6 +257,35 @@ int main(int argc, char** argv) {
     }
     std::fclose(f);
     exr_layer("", "RGB", rgb.data(), MCRT_EXR_HALF);
+    // --compare: one JSON line per frame; with_maps (the delivered frame under --exr): its error maps become channels
+    auto compare_frame = [&](const char* label, const std::vector<double>& frame, bool with_maps) {
+        if (compare.empty()) return true;
+        const size_t px = (size_t)cam.width * cam.height;
+        std::vector<double> se(with_maps ? px : 0), rel(with_maps ? px : 0), ssim(with_maps ? px : 0);
+        const mcrt_compare_maps maps{with_maps ? se.data() : nullptr, with_maps ? rel.data() : nullptr, with_maps ? ssim.data() : nullptr};
+        mcrt_compare_result r;
+        mcrt_stats cst;
+        const int crc = mcrt_frame_compare(ctx, cam.width, cam.height, frame.data(), reference.data(), nullptr, nullptr, &maps, &r, &cst);
+        if (crc != MCRT_OK) {
+            std::fprintf(stderr, "mcrt error %d: %s\n", crc, mcrt_last_error(ctx));
+            return false;
+        }
+        char psnr[40];
+        std::snprintf(psnr, sizeof psnr, r.mse == 0.0 && r.compared ? "\"inf\"" : "%.17g", r.psnr);
+        std::printf("{\"compare\":\"%s\",\"frame\":\"%s\",\"mse\":%.17g,\"rmse\":%.17g,\"mae\":%.17g,\"relmse\":%.17g,\"psnr\":%s,\"mean_ssim\":%.17g,"
+                    "\"max_abs\":%.17g,\"max_abs_pixel\":%lld,\"max_abs_channel\":%d,\"compared\":%llu,\"nonfinite\":%llu,\"differing\":%llu,"
+                    "\"ssim_centres\":%llu,\"ssim_excluded\":%llu,\"sum_se\":%.17g,\"sum_ae\":%.17g,\"sum_rel\":%.17g,\"sum_ssim\":%.17g,\"kernel_ms\":%.3f,\"total_ms\":%.3f}\n",
+                    compare.c_str(), label, r.mse, r.rmse, r.mae, r.relmse, psnr, r.mean_ssim, r.max_abs, r.compared ? (long long)r.max_abs_pixel : -1ll,
+                    r.compared ? (int)r.max_abs_channel : -1, (unsigned long long)r.compared, (unsigned long long)r.nonfinite, (unsigned long long)r.differing,
+                    (unsigned long long)r.ssim_centres, (unsigned long long)r.ssim_excluded, r.sum_se, r.sum_ae, r.sum_rel, r.sum_ssim, cst.kernel_ms, cst.total_ms);
+        if (with_maps) {
+            exr_one("error.se", exr_keep(se), MCRT_EXR_FLOAT, 1, 0);
+            exr_one("error.rel", exr_keep(rel), MCRT_EXR_FLOAT, 1, 0);
+            exr_one("error.ssim", exr_keep(ssim), MCRT_EXR_FLOAT, 1, 0);
+        }
+        return true;
+    };
+    if (!compare_frame("rgb", rgb, !exr.empty())) return 1;
     if (!variance.empty()) exr_layer("variance", "RGB", variance.data(), MCRT_EXR_FLOAT);
     if (!half_a.empty()) exr_layer("half_a", "RGB", half_a.data(), MCRT_EXR_HALF);
     if (!half_b.empty()) exr_layer("half_b", "RGB", half_b.data(), MCRT_EXR_HALF);
@@ -284,6 +354,7 @@ int main(int argc, char** argv) {
         std::printf("{\"robust\":\"%s\",\"clamped_pixels\":%llu,\"clamped_samples\":%llu,\"removed_energy\":%.17g,\"frame_energy\":%.17g,"
                     "\"removed_fraction\":%.17g,\"kernel_ms\":%.3f}\n",
                     robust.c_str(), pixels, samples, gone, all, all > 0.0 ? gone / all : 0.0, rst.kernel_ms);
+        if (!compare_frame("robust", out, false)) return 1;
         if (!exr.empty()) {
             exr_layer("robust", "RGB", exr_keep(out), MCRT_EXR_HALF);
             exr_layer("removed", "RGB", exr_keep(removed), MCRT_EXR_HALF);
@@ -335,6 +406,7 @@ int main(int argc, char** argv) {
         std::printf("{\"denoise_dual\":\"%s\",\"kernel_launches\":%u,\"kernel_ms\":%.3f,\"total_ms\":%.3f,\"relative_error_raw\":%.17g,"
                     "\"relative_error\":%.17g}\n",
                     ddual.c_str(), dst.kernel_launches, dst.kernel_ms, dst.total_ms, raw.relative_error, fn.relative_error);
+        if (!compare_frame("denoise_dual", filtered, false)) return 1;
         if (!tga.empty()) {
             const size_t dot = ddual.find_last_of('.'), slash = ddual.find_last_of('/');
             const bool has_ext = dot != std::string::npos && (slash == std::string::npos || dot > slash);
@@ -383,6 +455,7 @@ int main(int argc, char** argv) {
             if (!dump(denoise, filtered.data(), px * 24)) return 1;
             std::printf("{\"denoise\":\"%s\",\"kernel_launches\":%u,\"kernel_ms\":%.3f,\"total_ms\":%.3f}\n", denoise.c_str(), dst.kernel_launches,
                         dst.kernel_ms, dst.total_ms);
+            if (!compare_frame("denoise", filtered, false)) return 1;
             if (!tga.empty()) {
                 const size_t dot = denoise.find_last_of('.'), slash = denoise.find_last_of('/');
                 const bool has_ext = dot != std::string::npos && (slash == std::string::npos || dot > slash);
@@ -408,6 +481,7 @@ int main(int argc, char** argv) {
             std::printf("{\"denoise_variance\":\"%s\",\"kernel_launches\":%u,\"kernel_ms\":%.3f,\"total_ms\":%.3f,\"relative_error_raw\":%.17g,"
                         "\"relative_error\":%.17g}\n",
                         dvar.c_str(), dst.kernel_launches, dst.kernel_ms, dst.total_ms, raw.relative_error, fn.relative_error);
+            if (!compare_frame("denoise_variance", filtered, false)) return 1;
             if (!tga.empty()) {
                 const size_t dot = dvar.find_last_of('.'), slash = dvar.find_last_of('/');
                 const bool has_ext = dot != std::string::npos && (slash == std::string::npos || dot > slash);
