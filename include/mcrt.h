@@ -817,6 +817,94 @@ int mcrt_exr_save(mcrt_ctx* ctx, const char* path, uint32_t width, uint32_t heig
                   mcrt_exr_result* result /* may be NULL */, mcrt_stats* stats /* may be NULL */);
 
 /* ------------------------------------------------------------------------------------------
+ * OpenEXR input: the mirror of the output above. A file is opened once (header and offset table, no GPU work), asked what it holds,
+ * and any subset of its channels is then loaded into strided destinations. Written from the format's specification like the output:
+ * no OpenEXR or zlib library is linked; inflate is the system's libz.so.1 (uncompress), looked up at the first load that needs it - a
+ * lookup of its own, the save's is untouched. The host reads the chunks and inflates the deflated ones, chunk by chunk on at most 16
+ * threads, into ONE pinned payload buffer (chunk k at k * chunk_bytes, still in ZIP's transformed order u) which crosses to the device
+ * in one copy together with a flag per chunk (transformed or raw); payload_bytes counts the payloads. A chunk is inflated whole, so a
+ * channel the caller does not ask for still rides along in it. The inverse of ZIP's transform (t[0] = u[0],
+ * t[i] = (t[i-1] + u[i] - 128) mod 256: a prefix sum of bytes) and the widening to the destination's type are done on the device,
+ * on the bits; no FP64 value is made on the host. What a load returns is a function of the file, bit for bit.
+ *
+ * Accepted: single-part scan-line OpenEXR 2 files - version 2, optionally with the long-names bit 0x400 (names up to 255 bytes);
+ * compression NONE (0), ZIPS (2: one line per chunk, ZIP's transform) and ZIP (3: 16 lines); any data window with xMax >= xMin,
+ * yMax >= yMin and width * height < 2^32 (the display window is reported, not used); lineOrder 0, 1 or 2 - entry k of the offset
+ * table is the chunk whose first line is yMin + k * lines_per_chunk whatever the line order says, and every chunk's own y is checked
+ * against its slot; channels of pixelType UINT / HALF / FLOAT with xSampling == ySampling == 1 (pLinear is ignored); attributes of
+ * any type, known or not.
+ * Refused with MCRT_ERR_UNSUPPORTED (the message names the cause): the tiled (0x200), deep (0x800) or multi-part (0x1000) bit; any
+ * other version number; any other compression (the message gives its number); a subsampled channel; a chunk that needs inflating
+ * when libz.so.1 cannot be loaded (NONE files and raw chunks still load); a load of more lanes than one launch holds.
+ * Refused with MCRT_ERR_IO (the message says what and where; never a crash, never a read outside the file's bytes): the file cannot
+ * be opened or read; a wrong magic number; a header, channel list or attribute cut short or not ending where its size says; a
+ * negative or oversized attribute size; one of channels, compression, dataWindow, displayWindow, lineOrder missing or of the wrong
+ * type or size; an unknown pixelType; no channel or more than 65 536; duplicate channel names; an empty data window or one of 2^32
+ * pixels or more; an offset table cut short or an offset outside the file; a chunk whose y is not its slot's, whose size is
+ * negative, larger than its raw size (or, in a NONE file, not its raw size) or runs past the end of the file, or whose inflated
+ * size is not its raw size.
+ * Refused with MCRT_ERR_INVALID: a render in flight; NULL arguments; count 0 or > MCRT_EXR_MAX_CHANNELS; a target name the file does
+ * not hold (the message names it); two targets writing one element; stride 0 or offset >= stride; reserved or flags not 0; a type
+ * pair other than HALF -> F64, FLOAT -> F64, UINT -> U32.
+ *
+ * Widening, per value, on the bits in integer arithmetic (no floating-point mode of the device takes part); sign = the source's sign
+ * bit moved to bit 63:
+ *   HALF -> F64   s = h >> 15, e = (h >> 10) & 31, f = h & 1023.  e == 0, f == 0: sign.  e == 0, f != 0 (subnormal), k the index of
+ *                 f's top set bit (0..9): sign | (999 + k) << 52 | (f ^ (1 << k)) << (52 - k).  1 <= e <= 30:
+ *                 sign | (e + 1008) << 52 | f << 42.  e == 31, f == 0: sign | 0x7FF0000000000000.  e == 31, f != 0:
+ *                 sign | 0x7FF8000000000000 | f << 42 - the payload kept, the quiet bit set: what (double)x gives on x86-64.
+ *   FLOAT -> F64  the same with 8 / 23 bits: subnormal sign | (874 + k) << 52 | (f ^ (1 << k)) << (52 - k), k = 0..22; normal
+ *                 sign | (e + 896) << 52 | f << 29; NaN sign | 0x7FF8000000000000 | f << 29.
+ *   UINT -> U32   the bits.
+ * These are the exact left inverses of the save's roundings: saving a loaded HALF channel as HALF, or a loaded FLOAT channel as
+ * FLOAT, gives back the file's bits for every pattern that is not a NaN, for 0x7e00 / 0xfe00, and for every binary32 NaN whose quiet
+ * bit is set.
+ *
+ * A target is the mirror of mcrt_exr_channel: the value of the file's channel `name` at pixel p = y * width + x (x, y relative to
+ * the data window's corner) goes to data[p * stride + offset], data being double (MCRT_EXR_SRC_F64) or uint32_t (MCRT_EXR_SRC_U32)
+ * elements. Elements of a destination that no target names keep their bytes, in both forms. The calls are synchronous on the
+ * context's stream and need no scene. stats: kernel_ms (HIP events of the call's own around its launches), total_ms,
+ * kernel_launches (1 for a file without transformed chunks, 4 otherwise). */
+enum { MCRT_EXR_COMPRESSION_ZIPS = 2 };
+typedef struct mcrt_exr_file mcrt_exr_file;   /* opaque: a parsed header, the offset table, the open file */
+typedef struct mcrt_exr_info {
+    uint32_t width, height;                       /* of the data window */
+    int32_t data_window[4], display_window[4];    /* xMin, yMin, xMax, yMax as the file gives them */
+    uint32_t channels, attributes;                /* counts */
+    uint32_t compression, line_order, lines_per_chunk, chunks;
+    uint64_t file_bytes;
+} mcrt_exr_info;
+typedef struct mcrt_exr_target {
+    const char* name;       /* the channel's name in the file */
+    void* data;             /* element of pixel p is data[p * stride + offset] of the destination type */
+    uint32_t dest_type, stride, offset, reserved;   /* dest_type: MCRT_EXR_SRC_F64 or MCRT_EXR_SRC_U32; reserved 0 */
+} mcrt_exr_target;
+typedef struct mcrt_exr_load_params {   /* NULL or a zero field = the default */
+    uint32_t threads;       /* inflate threads, default min(16, the host's hardware threads); never more than 16 */
+    uint32_t flags;         /* 0 */
+} mcrt_exr_load_params;
+typedef struct mcrt_exr_load_result {
+    uint64_t file_bytes;
+    uint64_t payload_bytes;   /* what crossed from the host to the device as pixel data: height * the bytes of a scan line */
+    uint32_t chunks, raw_chunks;
+} mcrt_exr_load_result;
+/* Header and offset table only. *out is NULL unless MCRT_OK. ctx takes the refusal's message (mcrt_last_error). */
+int mcrt_exr_open(mcrt_ctx* ctx, const char* path, mcrt_exr_file** out);
+void mcrt_exr_close(mcrt_exr_file* f /* may be NULL */);
+int mcrt_exr_file_info(const mcrt_exr_file* f, mcrt_exr_info* info);
+/* Channel i in file (= sorted) order; the name lives as long as f. MCRT_ERR_INVALID past the last. */
+int mcrt_exr_file_channel(const mcrt_exr_file* f, uint32_t i, const char** name, uint32_t* pixel_type);
+/* Header attribute i in file order, standard and custom: its name, type name and raw bytes (they live as long as f). */
+int mcrt_exr_file_attribute(const mcrt_exr_file* f, uint32_t i, const char** name, const char** type, const void** value, uint32_t* size);
+/* targets: a HOST array of structs whose data point to DEVICE memory. */
+int mcrt_exr_load_device(mcrt_ctx* ctx, mcrt_exr_file* f, const mcrt_exr_target* d_targets, uint32_t count, const mcrt_exr_load_params* params /* may be NULL */,
+                         mcrt_exr_load_result* result /* may be NULL */, mcrt_stats* stats /* may be NULL */);
+/* Same with HOST data pointers: every distinct destination buffer is staged on the device with its present bytes and copied back
+ * once, however many channels land in it. */
+int mcrt_exr_load(mcrt_ctx* ctx, mcrt_exr_file* f, const mcrt_exr_target* targets, uint32_t count, const mcrt_exr_load_params* params /* may be NULL */,
+                  mcrt_exr_load_result* result /* may be NULL */, mcrt_stats* stats /* may be NULL */);
+
+/* ------------------------------------------------------------------------------------------
  * ID mattes: per pixel, the `ranks` keys (material, surface or a caller's object index) that cover most of it, each with its
  * coverage, in the Cryptomatte layout compositors decode from the FLOAT channels and string attributes mcrt_exr_save writes. The
  * reference has no such output. The surface / material channels of the AOV pass are "the hit of sample 0": one id per pixel,

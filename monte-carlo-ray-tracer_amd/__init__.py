@@ -12,6 +12,7 @@ Python identifier).
 """
 import ctypes as C
 import os
+import struct
 
 import numpy as np
 
@@ -328,6 +329,52 @@ class ExrResult(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+# OpenEXR input (include/mcrt.h "OpenEXR input")
+EXR_PIXEL_TYPE_NAMES = {v: k for k, v in EXR_PIXEL_TYPES.items()}
+
+
+class ExrInfo(C.Structure):
+    """mcrt_exr_info."""
+    _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("data_window", C.c_int32 * 4), ("display_window", C.c_int32 * 4), ("channels", C.c_uint32),
+                ("attributes", C.c_uint32), ("compression", C.c_uint32), ("line_order", C.c_uint32), ("lines_per_chunk", C.c_uint32), ("chunks", C.c_uint32),
+                ("file_bytes", C.c_uint64)]
+
+
+class ExrTarget(C.Structure):
+    """mcrt_exr_target: where one channel of a file goes, a strided view of a destination."""
+    _fields_ = [("name", C.c_char_p), ("data", C.c_void_p), ("dest_type", C.c_uint32), ("stride", C.c_uint32), ("offset", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class ExrLoadParams(C.Structure):
+    """mcrt_exr_load_params: a zero field = the default (include/mcrt.h)."""
+    _fields_ = [("threads", C.c_uint32), ("flags", C.c_uint32)]
+
+
+class ExrLoadResult(C.Structure):
+    """mcrt_exr_load_result."""
+    _fields_ = [("file_bytes", C.c_uint64), ("payload_bytes", C.c_uint64), ("chunks", C.c_uint32), ("raw_chunks", C.c_uint32)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+def _exr_attribute_value(typ, value, channels):
+    """A header attribute's bytes as tools/exr_probe.py read() decodes them; types it does not know stay bytes."""
+    if typ == "string":
+        return value.decode("ascii", "replace")
+    if typ == "float":
+        return struct.unpack("<f", value)[0]
+    if typ == "v2f":
+        return struct.unpack("<2f", value)
+    if typ == "box2i":
+        return struct.unpack("<4i", value)
+    if typ in ("compression", "lineOrder"):
+        return value[0]
+    if typ == "chlist":
+        return [(n, t.upper()) for n, t in channels]
+    return value
+
+
 # ID mattes (include/mcrt.h "ID mattes")
 MATTE_KEYS = {"material": 0, "surface": 1, "custom": 2}
 MATTE_DEFAULT_NAMES = {"material": "material%u", "surface": "surface%u", "custom": "key%u"}
@@ -495,6 +542,78 @@ def exr_layers(rgb=None, aov=None, stats=None, highlights=None, robust=None, den
     return out
 
 
+def exr_unlayer(channels):
+    """The inverse of exr_layers: from a dict name -> frame [H,W] (Context.exr_load's, numpy arrays or torch tensors) the keyword dict
+    exr_layers takes, for the names documented there - rgb [H,W,3]; aov with its [H,W,3] and [H,W] members; stats; highlights with tops
+    [H,W,4,3] and level; robust; denoised {name: {"rgb", "variance", "error"}} for every other layer that has R, G and B but no A (R, G,
+    B, A are a matte's layer); errors. A layer is taken when all its parts are there; every other name comes back under "other".
+    Frames are stacked where they live."""
+    left = dict(channels)
+
+    def stack(frames, axis=-1):
+        if _is_tensor(frames[0]):
+            import torch
+            return torch.stack(list(frames), dim=axis)
+        return np.stack(frames, axis=axis)
+
+    def take(layer, parts):
+        names = [part if layer == "" else "%s.%s" % (layer, part) for part in parts]
+        if not all(n in left for n in names):
+            return None
+        frames = [left.pop(n) for n in names]
+        return frames[0] if len(frames) == 1 else stack(frames)
+
+    out = {}
+    rgb = take("", "RGB")
+    if rgb is not None:
+        out["rgb"] = rgb
+    groups = {"aov": [(l, p) for l, p in (("depth", "Z"), ("position", "XYZ"), ("normal", "XYZ"), ("shading_normal", "XYZ"), ("albedo", "RGB"), ("coverage", "A"),
+                                          ("surface", ("id",)), ("material", ("id",)))],
+              "stats": [(l, "RGB") for l in PIXEL_STATS_CHANNELS],
+              "robust": [("robust", "RGB"), ("removed", "RGB"), ("clamped", ("count",))]}
+    for key, layers in groups.items():
+        found = {}
+        for layer, parts in layers:
+            frame = take(layer, parts)
+            if frame is not None:
+                found[layer] = frame
+        if found:
+            out[key] = found
+    highlights = {}
+    tops = [take("tops%d" % k, "RGB") if all("tops%d.%s" % (j, c) in channels for j in range(ROBUST_TOPS) for c in "RGB") else None for k in range(ROBUST_TOPS)]
+    if all(t is not None for t in tops):
+        highlights["tops"] = stack(tops, axis=2)
+    level = take("level", "Y")
+    if level is not None:
+        highlights["level"] = level
+    if highlights:
+        out["highlights"] = highlights
+    errors = {}
+    for key, part in COMPARE_ERROR_CHANNELS.items():
+        frame = take("error", (part,))
+        if frame is not None:
+            errors[key] = frame
+    if errors:
+        out["errors"] = errors
+    denoised = {}
+    for name in [n[:-2] for n in channels if n.endswith(".R") and n in left]:
+        if name.endswith((".variance", ".error")) or name + ".A" in left:  # (R, G, B, A: a matte's layer, not a frame)
+            continue
+        frame = take(name, "RGB")
+        if frame is None:
+            continue
+        denoised[name] = {"rgb": frame}
+        for k in ("variance", "error"):
+            extra = take("%s.%s" % (name, k), "RGB")
+            if extra is not None:
+                denoised[name][k] = extra
+    if denoised:
+        out["denoised"] = denoised
+    if left:
+        out["other"] = left
+    return out
+
+
 class PhotonEmissionDevice(C.Structure):
     _fields_ = [("global_count", C.c_uint64), ("caustic_count", C.c_uint64), ("d_global_photons", C.c_void_p), ("d_caustic_photons", C.c_void_p),
                 ("emission_paths", C.c_uint64), ("rays", C.c_uint64), ("kernel_ms", C.c_double)]
@@ -614,6 +733,15 @@ def lib():
         L.mcrt_exr_save.argtypes = [vp, C.c_char_p, C.c_uint32, C.c_uint32, C.POINTER(ExrChannel), C.c_uint32, C.POINTER(ExrAttribute), C.c_uint32,
                                     C.POINTER(ExrParams), C.POINTER(ExrResult), C.POINTER(Stats)]
         L.mcrt_exr_save_device.argtypes = L.mcrt_exr_save.argtypes
+    if hasattr(L, "mcrt_exr_open"):  # (likewise)
+        L.mcrt_exr_open.argtypes = [vp, C.c_char_p, C.POINTER(vp)]
+        L.mcrt_exr_close.argtypes = [vp]
+        L.mcrt_exr_close.restype = None
+        L.mcrt_exr_file_info.argtypes = [vp, C.POINTER(ExrInfo)]
+        L.mcrt_exr_file_channel.argtypes = [vp, C.c_uint32, C.POINTER(C.c_char_p), C.POINTER(C.c_uint32)]
+        L.mcrt_exr_file_attribute.argtypes = [vp, C.c_uint32, C.POINTER(C.c_char_p), C.POINTER(C.c_char_p), C.POINTER(vp), C.POINTER(C.c_uint32)]
+        L.mcrt_exr_load.argtypes = [vp, vp, C.POINTER(ExrTarget), C.c_uint32, C.POINTER(ExrLoadParams), C.POINTER(ExrLoadResult), C.POINTER(Stats)]
+        L.mcrt_exr_load_device.argtypes = L.mcrt_exr_load.argtypes
     if hasattr(L, "mcrt_render_matte"):  # (likewise)
         L.mcrt_render_matte.argtypes = [vp, C.POINTER(CameraDesc), C.c_uint32, C.POINTER(MatteParams), C.POINTER(MatteBuffers), C.POINTER(AovBuffers), C.POINTER(Stats)]
         L.mcrt_render_matte_device.argtypes = L.mcrt_render_matte.argtypes
@@ -1552,6 +1680,63 @@ class Context:
         if stats is not None:
             stats.update(st.as_dict())
         return res.as_dict()
+
+    def exr_load(self, path, channels=None, device=False, threads=0, stats=None):
+        """mcrt_exr_open .. mcrt_exr_load / mcrt_exr_load_device: the channels of an OpenEXR file -> (channels, attributes, info).
+        channels: dict name -> [H,W] float64 (the file's HALF and FLOAT channels, widened exactly) or uint32 (UINT) numpy array, in the
+        file's order; device=True: torch tensors on this context's device instead (float64, and int32 holding the uint32 bits, as
+        exr_save takes them), born there - only the file's own bytes cross. channels= selects a subset, in the order given.
+        attributes: dict name -> (type, value) of every header attribute in file order, decoded as tools/exr_probe.py read() does
+        (unknown types stay bytes). info: width, height, data_window, display_window, compression, line_order, chunks, raw_chunks,
+        file_bytes, payload_bytes. stats: a dict that receives mcrt_stats."""
+        self._sync_env()
+        f = C.c_void_p()
+        self._check(self._lib.mcrt_exr_open(self._h, os.fsencode(path), C.byref(f)), "mcrt_exr_open")
+        try:
+            fi = ExrInfo()
+            self._check(self._lib.mcrt_exr_file_info(f, C.byref(fi)), "mcrt_exr_file_info")
+            in_file = []
+            for i in range(fi.channels):
+                name, ptype = C.c_char_p(), C.c_uint32()
+                self._check(self._lib.mcrt_exr_file_channel(f, i, C.byref(name), C.byref(ptype)), "mcrt_exr_file_channel")
+                in_file.append((name.value.decode("latin-1"), EXR_PIXEL_TYPE_NAMES[ptype.value]))
+            attributes = {}
+            for i in range(fi.attributes):
+                name, typ, value, size = C.c_char_p(), C.c_char_p(), C.c_void_p(), C.c_uint32()
+                self._check(self._lib.mcrt_exr_file_attribute(f, i, C.byref(name), C.byref(typ), C.byref(value), C.byref(size)), "mcrt_exr_file_attribute")
+                raw = C.string_at(value.value, size.value) if size.value else b""
+                attributes[name.value.decode("latin-1")] = (typ.value.decode("latin-1"), _exr_attribute_value(typ.value.decode("latin-1"), raw, in_file))
+            types = dict(in_file)
+            wanted = [n for n, _ in in_file] if channels is None else [str(n) for n in channels]
+            assert len(wanted) >= 1, "no channel"
+            shape = (fi.height, fi.width)
+            out, recs = {}, []
+            if device:
+                import torch
+                dev = torch.device("cuda", self._device_id)
+            for n in wanted:
+                uint = types.get(n) == "uint"  # (a name the file does not hold: the library refuses it, and names it)
+                if device:
+                    a = torch.empty(shape, dtype=torch.int32 if uint else torch.float64, device=dev)
+                    ptr = int(a.data_ptr())
+                else:
+                    a = np.empty(shape, dtype=np.uint32 if uint else np.float64)
+                    ptr = int(a.ctypes.data)
+                out[n] = a
+                recs.append(ExrTarget(n.encode("latin-1"), ptr, EXR_SRC_U32 if uint else EXR_SRC_F64, 1, 0, 0))
+            if device:
+                torch.cuda.synchronize()
+            par, res, st = ExrLoadParams(int(threads), 0), ExrLoadResult(), Stats()
+            call = self._lib.mcrt_exr_load_device if device else self._lib.mcrt_exr_load
+            self._check(call(self._h, f, (ExrTarget * len(recs))(*recs), len(recs), C.byref(par), C.byref(res), C.byref(st)),
+                        "mcrt_exr_load_device" if device else "mcrt_exr_load")
+        finally:
+            self._lib.mcrt_exr_close(f)
+        if stats is not None:
+            stats.update(st.as_dict())
+        info = {"width": fi.width, "height": fi.height, "data_window": tuple(fi.data_window), "display_window": tuple(fi.display_window), "compression": fi.compression,
+                "line_order": fi.line_order, "chunks": res.chunks, "raw_chunks": res.raw_chunks, "file_bytes": res.file_bytes, "payload_bytes": res.payload_bytes}
+        return out, attributes, info
 
     def render_converged(self, cam, global_seed, target_relative_error=0.0, max_spp=0, integrator=INTEGRATOR_PATH_TRACER, min_batches=0,
                          channels=("variance",), stats=None):

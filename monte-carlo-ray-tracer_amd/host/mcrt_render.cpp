@@ -7,7 +7,7 @@
 //               [--denoise OUT.f64 [--denoise-iterations N]] [--denoise-variance OUT.f64 [--denoise-variance-out VAR.f64]]
 //               [--denoise-dual OUT.f64 [--denoise-dual-out VAR.f64]] [--stats PREFIX] [--robust PREFIX [--robust-kappa X] [--robust-radius R]]
 //               [--converge TARGET [--max-spp N]] [--exr OUT.exr [--exr-compression none|zip]]
-//               [--matte PREFIX [--matte-key material|surface] [--matte-ranks N]] [--compare REF]
+//               [--matte PREFIX [--matte-key material|surface] [--matte-ranks N]] [--compare REF [--compare-layer PREFIX]]
 //
 // Writes the frame as raw FP64 RGB, row-major (what Image::operator() holds, camera/image.cpp:53-56),
 // and prints the statistics. --tga also develops it the way Image::save does (auto exposure / gain, tone map, sRGB bytes:
@@ -48,8 +48,10 @@
 // --compare compares the delivered frame with the reference frame REF (mcrt_frame_compare; default parameters, no mask) and prints one
 // JSON line of the result; with --robust, --denoise, --denoise-variance or --denoise-dual each of those frames is compared too, a line
 // each ("frame" names it). REF is raw little-endian binary64 of exactly width * height * 3 * 8 bytes, or a .npy file - version 1.0, '<f8',
-// C order, shape (height, width, 3): what bench.py --dump-outputs writes. With --exr the file also holds the error maps of the delivered
-// frame as FLOAT channels error.se, error.rel and error.ssim (device 0).
+// C order, shape (height, width, 3): what bench.py --dump-outputs writes - or a file that starts with the OpenEXR magic number (what --exr
+// writes, or another renderer's scan-line file: mcrt_exr_open, mcrt_exr_load on device 0), of which the channels R, G, B - with
+// --compare-layer PREFIX the channels PREFIX.R, PREFIX.G, PREFIX.B - are the reference; its data window must be width x height. With --exr
+// the file also holds the error maps of the delivered frame as FLOAT channels error.se, error.rel and error.ssim (device 0).
 // --devices renders the frame on several GPUs from this one process (mcrt_render_multi: one host thread per GPU).
 #include <cstdio>
 #include <cstdlib>
@@ -79,7 +81,8 @@ int main(int argc, char** argv) {
     image.plain = (uint32_t)mcrt_image_param(img, "image_plain");
     image.exposure_compensation = from_bits(mcrt_image_param(img, "image_exposure_ev_bits"));
     image.gain_compensation = from_bits(mcrt_image_param(img, "image_gain_ev_bits"));
-    std::string tga, aov, denoise, dvar, dvar_out, ddual, ddual_out, pstats, robust, exr, matte, compare;
+    std::string tga, aov, denoise, dvar, dvar_out, ddual, ddual_out, pstats, robust, exr, matte, compare, compare_layer;
+    bool compare_exr = false;
     mcrt_matte_params mparams{};
     std::deque<std::string> exr_attr_text;  // the attributes --matte adds to --exr's: name, value, name, value, ...
     mcrt_exr_params eparams{};
@@ -130,6 +133,7 @@ int main(int argc, char** argv) {
         else if (k == "--exr" && i + 1 < argc) exr = argv[++i];
         else if (k == "--matte" && i + 1 < argc) matte = argv[++i];
         else if (k == "--compare" && i + 1 < argc) compare = argv[++i];
+        else if (k == "--compare-layer" && i + 1 < argc) compare_layer = argv[++i];
         else if (k == "--matte-key" && i + 1 < argc) mparams.key = (argv[++i][0] | 0x20) == 's' ? MCRT_MATTE_SURFACE : MCRT_MATTE_MATERIAL;
         else if (k == "--matte-ranks") mparams.ranks = (uint32_t)val();
         else if (k == "--exr-compression" && i + 1 < argc) eparams.compression = MCRT_EXR_COMPRESSION_SET | ((argv[++i][0] | 0x20) == 'n' ? MCRT_EXR_COMPRESSION_NONE : MCRT_EXR_COMPRESSION_ZIP);
@@ -167,6 +171,7 @@ int main(int argc, char** argv) {
             return 1;
         }
         size_t at = 0;
+        compare_exr = bytes.size() >= 4 && bytes.compare(0, 4, "\x76\x2f\x31\x01") == 0;  // (read once a context is there)
         if (bytes.size() >= 10 && bytes.compare(0, 6, "\x93NUMPY") == 0) {
             const size_t len = (unsigned char)bytes[8] | (size_t)(unsigned char)bytes[9] << 8;
             const std::string head = bytes.size() >= 10 + len ? bytes.substr(10, len) : std::string();
@@ -181,12 +186,12 @@ int main(int argc, char** argv) {
             }
             at = 10 + len;
         }
-        if (bytes.size() - at != want) {
+        if (!compare_exr && bytes.size() - at != want) {
             std::fprintf(stderr, "--compare: %s holds %zu bytes of frame, %u x %u x 3 binary64 are %zu\n", compare.c_str(), bytes.size() - at, cam.width, cam.height, want);
             return 2;
         }
         reference.resize(want / 8);
-        std::memcpy(reference.data(), bytes.data() + at, want);
+        if (!compare_exr) std::memcpy(reference.data(), bytes.data() + at, want);
     }
     if (devices.empty()) devices.push_back(device);
     if (!exr.empty() && devices.size() > 1) {
@@ -207,6 +212,31 @@ int main(int argc, char** argv) {
         if (rc != MCRT_OK) std::fprintf(stderr, "device %d: %s\n", devices[d], mcrt_last_error(ctxs[d]));
     }
     mcrt_ctx* ctx = ctxs[0];
+    if (compare_exr && rc == MCRT_OK) {  // the reference's channels, widened on the device into the [H][W][3] frame
+        mcrt_exr_file* ref = nullptr;
+        mcrt_exr_info info{};
+        if (mcrt_exr_open(ctx, compare.c_str(), &ref) != MCRT_OK || mcrt_exr_file_info(ref, &info) != MCRT_OK) {
+            std::fprintf(stderr, "--compare: %s\n", mcrt_last_error(ctx));
+            return 1;
+        }
+        if (info.width != cam.width || info.height != cam.height) {
+            std::fprintf(stderr, "--compare: %s is %u x %u, the frame %u x %u\n", compare.c_str(), info.width, info.height, cam.width, cam.height);
+            mcrt_exr_close(ref);
+            return 2;
+        }
+        std::string names[3];
+        mcrt_exr_target targets[3];
+        for (uint32_t c = 0; c < 3; c++) {
+            names[c] = (compare_layer.empty() ? std::string() : compare_layer + ".") + "RGB"[c];
+            targets[c] = mcrt_exr_target{names[c].c_str(), reference.data(), MCRT_EXR_SRC_F64, 3, c, 0};
+        }
+        const int lrc = mcrt_exr_load(ctx, ref, targets, 3, nullptr, nullptr, nullptr);
+        mcrt_exr_close(ref);
+        if (lrc != MCRT_OK) {
+            std::fprintf(stderr, "--compare: %s\n", mcrt_last_error(ctx));
+            return lrc == MCRT_ERR_INVALID ? 2 : 1;
+        }
+    }
     std::vector<double> rgb((size_t)cam.width * cam.height * 3);
     mcrt_stats st;
     const int mode = photon ? MCRT_INTEGRATOR_PHOTON_MAPPER : MCRT_INTEGRATOR_PATH_TRACER;
