@@ -1063,6 +1063,54 @@ int mcrt_frame_compare(mcrt_ctx* ctx, uint32_t width, uint32_t height, const dou
                        const double* mask /* may be NULL */, const mcrt_compare_params* params /* may be NULL */,
                        const mcrt_compare_maps* maps /* may be NULL */, mcrt_compare_result* result, mcrt_stats* stats /* may be NULL */);
 
+/* ------------------------------------------------------------------------------------------
+ * Occlusion pass: how open the surface under every pixel is - ambient occlusion, sky visibility and the bent normal, the passes
+ * compositors and look development read next to the AOVs, and the cheapest "clay" look at a scene: the cosine-weighted visibility
+ * estimate `ao` is the irradiance under a white sky, over pi. The reference has no such output; every ray is one its path tracer
+ * would draw. The camera samples are the AOV pass's: sample i in 0..sqrtspp^2-1 of pixel (x, y) is Camera::samplePixel's ray
+ * (camera/camera.cpp:79-95) with the sampler at initiate(y*width+x), setIndex(i) and Sampler::global_seed = global_seed. A sample
+ * that misses contributes nothing. For a sample that hits, with P, N and Ns of the first hit as the AOV pass defines them (P = ray(t),
+ * N the geometric normal, Ns the shading normal with its fall-back, both on the ray's side: ray/interaction.cpp:12-36), occlusion
+ * ray (i, j), j in 0..rays-1, is
+ *   sampler   restore(global_seed, y*width+x, i, 1 + j): initiate, setIndex(i), then the state after 1 + j calls of shuffle()
+ *             (sampling/sampler.hpp:32-52) - with j = 0 the state of the path tracer's first bounce (path-tracer.cpp:23)
+ *   numbers   u0 = get<DIM_BSDF>(), u1 = get<DIM_BSDF + 1>(): the pair the diffuse bounce draws (ray/ray.cpp, the last branch)
+ *   direction w = CoordinateSystem(Ns).from(cosWeightedHemi(u0, u1)) (common/coordinate-system.cpp:7-35, sampling/sampling.hpp:35-44,
+ *             sin and cos of the azimuth glibc's sincos); with MCRT_OCCLUSION_GEOMETRIC the basis is CoordinateSystem(N)
+ *   start     P + N * 1e-9 (C::EPSILON), whatever the sign of dot(w, N)
+ * and goes through the closest-hit search behind mcrt_intersect, unchanged: (t, surface). The ray SEES THE SKY when nothing is hit,
+ * and is OPEN when nothing is hit or t > max_distance; max_distance == 0 means unbounded: any hit occludes. Materials play no
+ * part: glass occludes. Per pixel every word is summed by ONE FP64 accumulator in ascending (i, j) - the frame does not depend on
+ * chunking (option MCRT_AOV_CHUNK_RAYS: here the OCCLUSION rays per launch group, always whole pixels, one at least), sharding or
+ * launch shape, bit for bit. With hits = the camera samples that hit and n = (double)(hits * rays):
+ *   ao             (number of open rays) / n                    1.0 at hits == 0
+ *   sky            (number of rays that see the sky) / n        1.0 at hits == 0
+ *   bent_normal    (sum of w over the open rays) / n            zeros at hits == 0; NOT normalised: + - * / only, like the AOV means
+ * so ao >= sky everywhere, and a bounded ao >= the unbounded one. cam->shard_* is honoured exactly as in mcrt_render_aov_device;
+ * cam->film_* is IGNORED. Both calls are synchronous on the context's stream. Refused with a message (mcrt_last_error): before
+ * mcrt_upload_scene (MCRT_ERR_NO_SCENE), and with MCRT_ERR_INVALID a render in flight, rays > 64, max_distance negative or not
+ * finite, flag bits other than MCRT_OCCLUSION_GEOMETRIC, and ao, sky and bent_normal all NULL.
+ * stats: paths = camera samples; rays = paths * (1 + rays): the camera rays and EVERY occlusion slot traced - the slots of a camera
+ * sample that missed hold its camera ray and go through the search too, their results unread (misses are not compacted) -;
+ * kernel_ms (HIP events around the pass's launches), total_ms, kernel_launches (5 per chunk). */
+#define MCRT_OCCLUSION_GEOMETRIC 1u     /* flags: directions around the geometric normal N instead of the shading normal Ns */
+#define MCRT_OCCLUSION_MAX_RAYS 64u
+typedef struct mcrt_occlusion_params {  /* NULL = the defaults */
+    uint32_t rays;          /* occlusion rays per camera sample that hits: 1 .. 64; 0 = 1 */
+    uint32_t flags;         /* MCRT_OCCLUSION_* */
+    double max_distance;    /* hits farther than this do not occlude; 0 = unbounded; finite, >= 0 */
+} mcrt_occlusion_params;                /* 16 bytes */
+typedef struct mcrt_occlusion_buffers { /* every pointer may be NULL = channel not wanted (not all); DEVICE memory, owned rows only, packed like d_out_rgb */
+    double* ao;            /* [rows][width]    */
+    double* sky;           /* [rows][width]    */
+    double* bent_normal;   /* [rows][width][3] */
+} mcrt_occlusion_buffers;
+int mcrt_render_occlusion_device(mcrt_ctx* ctx, const mcrt_camera_desc* cam, uint32_t global_seed, const mcrt_occlusion_params* params /* may be NULL */,
+                                 const mcrt_occlusion_buffers* d_buffers, mcrt_stats* stats /* may be NULL */);
+/* Same with HOST pointers to FULL frames: rows this shard does not own are left untouched. */
+int mcrt_render_occlusion(mcrt_ctx* ctx, const mcrt_camera_desc* cam, uint32_t global_seed, const mcrt_occlusion_params* params /* may be NULL */,
+                          const mcrt_occlusion_buffers* buffers, mcrt_stats* stats /* may be NULL */);
+
 /* Photon emission pass on the GPU. Replaces the thread fan-out of
  * PhotonMapper::PhotonMapper (integrator/photon-mapper/photon-mapper.cpp:80-115: per emission
  * Sampler::initiate(light), setIndex(offset+i), light point + cosine direction, emitPhoton :225-277) for

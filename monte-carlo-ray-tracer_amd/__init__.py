@@ -167,6 +167,22 @@ AOV_CHANNELS = {"depth": (np.float64, 1), "position": (np.float64, 3), "normal":
                 "albedo": (np.float64, 3), "coverage": (np.float64, 1), "surface": (np.uint32, 1), "material": (np.uint32, 1)}
 
 
+class OcclusionParams(C.Structure):
+    """mcrt_occlusion_params: rays per camera sample that hits (0 = 1), MCRT_OCCLUSION_* flags, max_distance (0 = unbounded)."""
+    _fields_ = [("rays", C.c_uint32), ("flags", C.c_uint32), ("max_distance", C.c_double)]
+
+
+class OcclusionBuffers(C.Structure):
+    """mcrt_occlusion_buffers: one pointer per channel of the occlusion pass, NULL = channel not wanted."""
+    _fields_ = [("ao", C.c_void_p), ("sky", C.c_void_p), ("bent_normal", C.c_void_p)]
+
+
+OCCLUSION_GEOMETRIC = 1
+OCCLUSION_MAX_RAYS = 64
+# channel -> (dtype, values per pixel), in mcrt_occlusion_buffers order
+OCCLUSION_CHANNELS = {"ao": (np.float64, 1), "sky": (np.float64, 1), "bent_normal": (np.float64, 3)}
+
+
 class DenoiseParams(C.Structure):
     """mcrt_denoise_params: a zero field = the default (include/mcrt.h)."""
     _fields_ = [("iterations", C.c_uint32), ("normal_power_log2", C.c_uint32), ("sigma_color", C.c_double), ("sigma_plane", C.c_double),
@@ -472,7 +488,7 @@ def _exr_source(a):
 _EXR_FLOAT_LAYERS = ("depth", "position", "variance", "error", "level")
 
 
-def exr_layers(rgb=None, aov=None, stats=None, highlights=None, robust=None, denoised=None, pixel_types=None, mattes=None, errors=None):
+def exr_layers(rgb=None, aov=None, stats=None, highlights=None, robust=None, denoised=None, pixel_types=None, mattes=None, errors=None, occlusion=None):
     """The channel dict Context.exr_save takes, from what the render_* and denoise_* methods return, under fixed names:
       rgb [H,W,3]                       R, G, B
       aov (render_aov's dict)           depth.Z, position.X/Y/Z, normal.X/Y/Z, shading_normal.X/Y/Z, albedo.R/G/B, coverage.A, surface.id, material.id
@@ -485,6 +501,8 @@ def exr_layers(rgb=None, aov=None, stats=None, highlights=None, robust=None, den
                                         matte_attributes gives the attributes that go with them
       errors (frame_compare's maps)     error.se, error.rel, error.ssim: "squared_error", "relative", "ssim" [H,W] of the dict (those
                                         that are there), always FLOAT
+      occlusion (render_occlusion's)    occlusion.ao, occlusion.sky, occlusion.bent.X/Y/Z (those that are there): HALF like the AOV
+                                        pass's coverage and normals
     -> dict name -> (view [H,W], "half" | "float" | "uint"). Colour is HALF; depth, position, variance, error and level FLOAT; ids and
     counts UINT. pixel_types: {channel or layer name: type} overrides that (a layer is a name without its last component). The views
     are of the arrays and tensors given, numpy or torch alike: nothing is copied."""
@@ -539,6 +557,11 @@ def exr_layers(rgb=None, aov=None, stats=None, highlights=None, robust=None, den
         if errors is not None and errors.get(key) is not None:
             assert errors[key].ndim == 2, (key, tuple(errors[key].shape))
             out["error." + part] = (errors[key], "float")
+    for key in ("ao", "sky"):
+        if occlusion is not None and occlusion.get(key) is not None:
+            put("occlusion", (key,), occlusion[key])
+    if occlusion is not None and occlusion.get("bent_normal") is not None:
+        put("occlusion.bent", "XYZ", occlusion["bent_normal"])
     return out
 
 
@@ -546,7 +569,7 @@ def exr_unlayer(channels):
     """The inverse of exr_layers: from a dict name -> frame [H,W] (Context.exr_load's, numpy arrays or torch tensors) the keyword dict
     exr_layers takes, for the names documented there - rgb [H,W,3]; aov with its [H,W,3] and [H,W] members; stats; highlights with tops
     [H,W,4,3] and level; robust; denoised {name: {"rgb", "variance", "error"}} for every other layer that has R, G and B but no A (R, G,
-    B, A are a matte's layer); errors. A layer is taken when all its parts are there; every other name comes back under "other".
+    B, A are a matte's layer); occlusion with ao, sky and bent_normal [H,W,3]; errors. A layer is taken when all its parts are there; every other name comes back under "other".
     Frames are stacked where they live."""
     left = dict(channels)
 
@@ -588,6 +611,13 @@ def exr_unlayer(channels):
         highlights["level"] = level
     if highlights:
         out["highlights"] = highlights
+    occlusion = {}
+    for key, layer, parts in (("ao", "occlusion", ("ao",)), ("sky", "occlusion", ("sky",)), ("bent_normal", "occlusion.bent", "XYZ")):
+        frame = take(layer, parts)
+        if frame is not None:
+            occlusion[key] = frame
+    if occlusion:
+        out["occlusion"] = occlusion
     errors = {}
     for key, part in COMPARE_ERROR_CHANNELS.items():
         frame = take("error", (part,))
@@ -750,6 +780,9 @@ def lib():
         L.mcrt_matte_code.restype = C.c_uint32
         L.mcrt_matte_manifest.argtypes = [C.POINTER(MatteParams), C.c_uint32, C.c_char_p, C.c_uint64]
         L.mcrt_matte_manifest.restype = C.c_int64
+    if hasattr(L, "mcrt_render_occlusion"):  # (likewise)
+        L.mcrt_render_occlusion.argtypes = [vp, C.POINTER(CameraDesc), C.c_uint32, C.POINTER(OcclusionParams), C.POINTER(OcclusionBuffers), C.POINTER(Stats)]
+        L.mcrt_render_occlusion_device.argtypes = L.mcrt_render_occlusion.argtypes
     if hasattr(L, "mcrt_frame_compare"):  # (likewise)
         L.mcrt_frame_compare.argtypes = [vp, C.c_uint32, C.c_uint32, vp, vp, vp, C.POINTER(CompareParams), C.POINTER(CompareMaps), C.POINTER(CompareResult), C.POINTER(Stats)]
         L.mcrt_frame_compare_device.argtypes = L.mcrt_frame_compare.argtypes
@@ -1214,6 +1247,40 @@ class Context:
         bufs = _pointer_struct(AovBuffers, pointers, AOV_CHANNELS)
         st = Stats()
         self._check(self._lib.mcrt_render_aov_device(self._h, C.byref(cam), int(global_seed), C.byref(bufs), C.byref(st)), "mcrt_render_aov_device")
+        return st.as_dict()
+
+    def render_occlusion(self, cam, global_seed, rays=1, max_distance=0.0, geometric=False, channels=None, out=None, stats=None):
+        """mcrt_render_occlusion: the occlusion frame -> dict "ao" [H,W], "sky" [H,W], "bent_normal" [H,W,3] (not normalised). rays:
+        occlusion rays per camera sample that hits, 1 .. 64; max_distance: hits farther away do not occlude, 0 = unbounded; geometric:
+        directions around the geometric instead of the shading normal. channels: the names wanted (OCCLUSION_CHANNELS; None = all). out:
+        a dict of arrays to write into instead of fresh zeros - the call only writes the rows cam's shard owns. stats: a dict that
+        receives mcrt_stats."""
+        self._sync_env()
+        names = list(OCCLUSION_CHANNELS) if channels is None else list(channels)
+        res, bufs = {}, OcclusionBuffers()
+        for name in names:
+            dtype, k = OCCLUSION_CHANNELS[name]
+            shape = (cam.height, cam.width) + ((k,) if k > 1 else ())
+            a = out[name] if out is not None and name in out else np.zeros(shape, dtype=dtype)
+            assert a.dtype == dtype and a.shape == shape and a.flags["C_CONTIGUOUS"], name
+            res[name] = a
+            setattr(bufs, name, a.ctypes.data)
+        par = OcclusionParams(int(rays), OCCLUSION_GEOMETRIC if geometric else 0, float(max_distance))
+        st = Stats()
+        self._check(self._lib.mcrt_render_occlusion(self._h, C.byref(cam), int(global_seed), C.byref(par), C.byref(bufs), C.byref(st)), "mcrt_render_occlusion")
+        if stats is not None:
+            stats.update(st.as_dict())
+        return res
+
+    def render_occlusion_device(self, cam, global_seed, pointers, rays=1, max_distance=0.0, geometric=False):
+        """mcrt_render_occlusion_device: pointers = dict channel -> raw device pointer (owned rows only, packed like render_device's
+        output); channels left out are not computed. Synchronous; returns the stats dict."""
+        self._sync_env()
+        bufs = _pointer_struct(OcclusionBuffers, pointers, OCCLUSION_CHANNELS)
+        par = OcclusionParams(int(rays), OCCLUSION_GEOMETRIC if geometric else 0, float(max_distance))
+        st = Stats()
+        self._check(self._lib.mcrt_render_occlusion_device(self._h, C.byref(cam), int(global_seed), C.byref(par), C.byref(bufs), C.byref(st)),
+                    "mcrt_render_occlusion_device")
         return st.as_dict()
 
     def render_matte(self, cam, global_seed, key="material", ranks=MATTE_DEFAULT_RANKS, names=None, surface_key=None, aov=None, out=None, stats=None,

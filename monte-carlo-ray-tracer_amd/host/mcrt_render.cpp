@@ -8,6 +8,7 @@
 //               [--denoise-dual OUT.f64 [--denoise-dual-out VAR.f64]] [--stats PREFIX] [--robust PREFIX [--robust-kappa X] [--robust-radius R]]
 //               [--converge TARGET [--max-spp N]] [--exr OUT.exr [--exr-compression none|zip]]
 //               [--matte PREFIX [--matte-key material|surface] [--matte-ranks N]] [--compare REF [--compare-layer PREFIX]]
+//               [--occlusion PREFIX [--occlusion-rays N] [--occlusion-distance D]]
 //
 // Writes the frame as raw FP64 RGB, row-major (what Image::operator() holds, camera/image.cpp:53-56),
 // and prints the statistics. --tga also develops it the way Image::save does (auto exposure / gain, tone map, sRGB bytes:
@@ -52,6 +53,10 @@
 // writes, or another renderer's scan-line file: mcrt_exr_open, mcrt_exr_load on device 0), of which the channels R, G, B - with
 // --compare-layer PREFIX the channels PREFIX.R, PREFIX.G, PREFIX.B - are the reference; its data window must be width x height. With --exr
 // the file also holds the error maps of the delivered frame as FLOAT channels error.se, error.rel and error.ssim (device 0).
+// --occlusion also writes the occlusion pass of the same camera and seed (mcrt_render_occlusion, device 0; --occlusion-rays N rays per
+// camera sample that hits, default 1, 64 at most; --occlusion-distance D: hits farther away do not occlude, default 0 = unbounded):
+// PREFIX.ao.f64, PREFIX.sky.f64 ([H][W]) and PREFIX.bent_normal.f64 ([H][W][3], not normalised), raw FP64. With --exr the file also holds
+// them as the HALF channels occlusion.ao, occlusion.sky and occlusion.bent.X/Y/Z.
 // --devices renders the frame on several GPUs from this one process (mcrt_render_multi: one host thread per GPU).
 #include <cstdio>
 #include <cstdlib>
@@ -81,7 +86,8 @@ int main(int argc, char** argv) {
     image.plain = (uint32_t)mcrt_image_param(img, "image_plain");
     image.exposure_compensation = from_bits(mcrt_image_param(img, "image_exposure_ev_bits"));
     image.gain_compensation = from_bits(mcrt_image_param(img, "image_gain_ev_bits"));
-    std::string tga, aov, denoise, dvar, dvar_out, ddual, ddual_out, pstats, robust, exr, matte, compare, compare_layer;
+    std::string tga, aov, denoise, dvar, dvar_out, ddual, ddual_out, pstats, robust, exr, matte, compare, compare_layer, occlusion;
+    mcrt_occlusion_params oparams{};
     bool compare_exr = false;
     mcrt_matte_params mparams{};
     std::deque<std::string> exr_attr_text;  // the attributes --matte adds to --exr's: name, value, name, value, ...
@@ -133,6 +139,9 @@ int main(int argc, char** argv) {
         else if (k == "--exr" && i + 1 < argc) exr = argv[++i];
         else if (k == "--matte" && i + 1 < argc) matte = argv[++i];
         else if (k == "--compare" && i + 1 < argc) compare = argv[++i];
+        else if (k == "--occlusion" && i + 1 < argc) occlusion = argv[++i];
+        else if (k == "--occlusion-rays") oparams.rays = (uint32_t)val();
+        else if (k == "--occlusion-distance" && i + 1 < argc) oparams.max_distance = std::strtod(argv[++i], nullptr);
         else if (k == "--compare-layer" && i + 1 < argc) compare_layer = argv[++i];
         else if (k == "--matte-key" && i + 1 < argc) mparams.key = (argv[++i][0] | 0x20) == 's' ? MCRT_MATTE_SURFACE : MCRT_MATTE_MATERIAL;
         else if (k == "--matte-ranks") mparams.ranks = (uint32_t)val();
@@ -591,6 +600,36 @@ int main(int argc, char** argv) {
             } else {
                 std::fprintf(stderr, "--matte: the manifest of %u names would take %lld bytes: left out of %s\n", num_keys, (long long)need, exr.c_str());
             }
+        }
+    }
+    if (!occlusion.empty()) {
+        const size_t px = (size_t)cam.width * cam.height;
+        std::vector<double> ao(px), sky(px), bent(px * 3);
+        const mcrt_occlusion_buffers ob{ao.data(), sky.data(), bent.data()};
+        mcrt_stats ost;
+        rc = mcrt_render_occlusion(ctx, &cam, seed, &oparams, &ob, &ost);
+        if (rc != MCRT_OK) {
+            std::fprintf(stderr, "mcrt error %d: %s\n", rc, mcrt_last_error(ctx));
+            return 1;
+        }
+        auto dump = [&](const std::string& path, const void* data, size_t bytes) {
+            FILE* o = std::fopen(path.c_str(), "wb");
+            const bool ok = o && std::fwrite(data, 1, bytes, o) == bytes;
+            if (o) std::fclose(o);
+            if (!ok) std::fprintf(stderr, "cannot write %s\n", path.c_str());
+            return ok;
+        };
+        if (!(dump(occlusion + ".ao.f64", ao.data(), px * 8) && dump(occlusion + ".sky.f64", sky.data(), px * 8) && dump(occlusion + ".bent_normal.f64", bent.data(), px * 24)))
+            return 1;
+        double mean_ao = 0.0;
+        for (double a : ao) mean_ao += a;
+        std::printf("{\"occlusion\":\"%s\",\"occlusion_rays\":%u,\"max_distance\":%.17g,\"mean_ao\":%.6f,\"rays\":%llu,\"kernel_ms\":%.3f,\"total_ms\":%.3f,\"Mray_s\":%.1f}\n",
+                    occlusion.c_str(), oparams.rays ? oparams.rays : 1u, oparams.max_distance, px ? mean_ao / (double)px : 0.0, (unsigned long long)ost.rays, ost.kernel_ms,
+                    ost.total_ms, ost.rays / ost.kernel_ms / 1e3);
+        if (!exr.empty()) {
+            exr_one("occlusion.ao", exr_keep(ao), MCRT_EXR_HALF, 1, 0);
+            exr_one("occlusion.sky", exr_keep(sky), MCRT_EXR_HALF, 1, 0);
+            exr_layer("occlusion.bent", "XYZ", exr_keep(bent), MCRT_EXR_HALF);
         }
     }
     if (!exr.empty()) {

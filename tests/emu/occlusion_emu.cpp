@@ -1,0 +1,122 @@
+// tests/emu/occlusion_emu.cpp — TEST HARNESS ONLY (built by tests/test_occlusion_emulation.py into tests/emu/_build/).
+//
+// The occlusion pass on the host: csrc/mcrt_occlusion.hpp (and csrc/mcrt_aov.hpp below it) unchanged - the text the two kernels of
+// csrc/mcrt_occlusion.hip run - driven chunk by chunk the way mcrt_render_occlusion_device drives them, with the closest hits from the
+// emulation's sceneIntersect (mcrt_emu.cpp's emu_intersect). Not a CPU fallback: nothing in the product links or loads it.
+#include "mcrt_emu.cpp"
+
+#include "../../monte-carlo-ray-tracer_amd/csrc/mcrt_occlusion.hpp"
+
+namespace {
+
+uint32_t ownedRows(const mcrt_camera_desc* cam) {
+    uint32_t rows = 0;
+    for (uint32_t ly = 0; localToGlobalRow(*cam, ly) < cam->height; ly++) rows++;
+    return rows;
+}
+
+}  // namespace
+
+extern "C" {
+
+// Owned rows of the camera's shard (what mcrt_shard_rows counts).
+uint32_t occlusion_emu_rows(const mcrt_camera_desc* cam) { return ownedRows(cam); }
+
+// Why `params` is refused (the text mcrt_render_occlusion* records), or NULL; *rays: the number of rays they mean.
+const char* occlusion_emu_settings(const mcrt_occlusion_params* params, uint32_t* rays) {
+    OcclusionSettings s;
+    const char* why = occlusionSettingsOf(params, s);
+    if (rays) *rays = s.rays;
+    return why;
+}
+
+// What the frame's records hold, every pointer optional, over the packed owned rows: the camera samples [pixel][sample] and the
+// occlusion rays [pixel][sample][j] (the slots of a missed camera sample hold what the kernel put there).
+struct OcclusionEmuRecords {
+    double* cam_start;      // [P][S][3]
+    double* cam_direction;  // [P][S][3]
+    double* cam_t;          // [P][S]
+    uint32_t* cam_surface;  // [P][S]
+    double* cam_uv;         // [P][S][2]
+    double* start;          // [P][S][R][3]
+    double* direction;      // [P][S][R][3]
+    double* t;              // [P][S][R]
+    uint32_t* surface;      // [P][S][R]
+    uint32_t* hits;         // [P]
+};
+
+// The occlusion frame into `out` (host arrays over the packed owned rows, null = channel not wanted), in chunks of chunk_rays occlusion
+// rays (0 = one chunk). stage_lds: emu_intersect's flavour of the walk.
+int occlusion_emu_frame(const mcrt_scene_desc* scene, const mcrt_camera_desc* cam, uint32_t global_seed, int stage_lds, uint64_t chunk_rays,
+                        const mcrt_occlusion_params* params, const mcrt_occlusion_buffers* out, const OcclusionEmuRecords* rec) {
+    OcclusionSettings o;
+    if (occlusionSettingsOf(params, o)) return MCRT_ERR_INVALID;
+    Emu E;
+    if (int rc = setup(E, scene, 0)) return rc;
+    AovScene as;
+    as.sh = E.sh_top;
+    as.prim = E.L.prim.data();
+    const uint32_t spp = cam->sqrtspp * cam->sqrtspp;
+    const uint64_t per_pixel = (uint64_t)spp * o.rays;
+    const uint64_t total = (uint64_t)ownedRows(cam) * cam->width;
+    const uint64_t chunk_pixels = std::min<uint64_t>(std::max<uint64_t>((chunk_rays ? chunk_rays : total * per_pixel) / per_pixel, 1), std::max<uint64_t>(total, 1));
+    const uint64_t max_cam = chunk_pixels * spp, max_occ = chunk_pixels * per_pixel;
+    std::vector<double> c_start(max_cam * 3), c_dir(max_cam * 3), c_t(max_cam), c_uv(max_cam * 2);
+    std::vector<uint32_t> c_surf(max_cam);
+    std::vector<double> o_start(max_occ * 3), o_dir(max_occ * 3), o_t(max_occ), o_uv(max_occ * 2);
+    std::vector<uint32_t> o_surf(max_occ);
+    const OcclusionEmuRecords none{};
+    const OcclusionEmuRecords& k = rec ? *rec : none;
+    for (uint64_t first = 0; first < total; first += chunk_pixels) {
+        AovChunk c;
+        c.cam = *cam;
+        c.global_seed = global_seed;
+        c.spp = spp;
+        c.first_pixel = first;
+        c.pixels = (uint32_t)std::min<uint64_t>(chunk_pixels, total - first);
+        const uint64_t n = (uint64_t)c.pixels * spp;
+        for (uint64_t r = 0; r < n; r++) {  // aovRayKernel
+            const Ray ray = aovCameraRay<true>(c, as.sh.scene_ior, (uint32_t)(r % c.pixels), (uint32_t)(r / c.pixels), E.tab.data());
+            aovStore3(c_start.data(), r, ray.start);
+            aovStore3(c_dir.data(), r, ray.direction);
+        }
+        if (int rc = emu_intersect(scene, n, c_start.data(), c_dir.data(), stage_lds, c_t.data(), c_surf.data(), c_uv.data())) return rc;
+        const AovRays cam_rays{c_start.data(), c_dir.data(), c_t.data(), c_surf.data(), c_uv.data()};
+        const AovRays occ{o_start.data(), o_dir.data(), o_t.data(), o_surf.data(), o_uv.data()};
+        for (uint64_t r = 0; r < n * o.rays; r++) {  // occlusionRayKernel
+            d3 start, direction;
+            occlusionChunkRay<true>(c, as, o, cam_rays, r, E.tab.data(), start, direction);
+            aovStore3(occ.start, r, start);
+            aovStore3(occ.direction, r, direction);
+        }
+        if (int rc = emu_intersect(scene, n * o.rays, occ.start, occ.direction, stage_lds, occ.t, occ.surface, occ.uv)) return rc;
+        for (uint32_t p = 0; p < c.pixels; p++) {  // occlusionResolveKernel
+            OcclusionAccum acc;
+            occlusionPixel(acc, c, o, cam_rays, occ, p);
+            occlusionFinish(acc, o.rays, *out, first + p);
+            const uint64_t q = first + p;
+            if (k.hits) k.hits[q] = acc.hits;
+            for (uint32_t i = 0; i < spp; i++) {
+                const uint64_t cr = (uint64_t)i * c.pixels + p, cq = q * spp + i;
+                if (k.cam_start) aovStore3(k.cam_start, cq, ld3(c_start.data() + 3 * cr));
+                if (k.cam_direction) aovStore3(k.cam_direction, cq, ld3(c_dir.data() + 3 * cr));
+                if (k.cam_t) k.cam_t[cq] = c_t[cr];
+                if (k.cam_surface) k.cam_surface[cq] = c_surf[cr];
+                if (k.cam_uv) {
+                    k.cam_uv[2 * cq] = c_uv[2 * cr];
+                    k.cam_uv[2 * cq + 1] = c_uv[2 * cr + 1];
+                }
+                for (uint32_t j = 0; j < o.rays; j++) {
+                    const uint64_t r = ((uint64_t)i * o.rays + j) * c.pixels + p, oq = cq * o.rays + j;
+                    if (k.start) aovStore3(k.start, oq, ld3(occ.start + 3 * r));
+                    if (k.direction) aovStore3(k.direction, oq, ld3(occ.direction + 3 * r));
+                    if (k.t) k.t[oq] = occ.t[r];
+                    if (k.surface) k.surface[oq] = occ.surface[r];
+                }
+            }
+        }
+    }
+    return 0;
+}
+
+}  // extern "C"
