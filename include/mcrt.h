@@ -1111,6 +1111,61 @@ int mcrt_render_occlusion_device(mcrt_ctx* ctx, const mcrt_camera_desc* cam, uin
 int mcrt_render_occlusion(mcrt_ctx* ctx, const mcrt_camera_desc* cam, uint32_t global_seed, const mcrt_occlusion_params* params /* may be NULL */,
                           const mcrt_occlusion_buffers* buffers, mcrt_stats* stats /* may be NULL */);
 
+/* ------------------------------------------------------------------------------------------
+ * Lighting passes: the light of a path-traced frame split up per pixel - what the camera sees of emitters (`emission`) and of the sky
+ * (`sky`), what the first hit receives straight from the emitters and the sky (`direct`), the sampled half of that alone (`light`) and
+ * the same with nothing in its way (`unoccluded`), so that light / unoccluded is the shadow matte and beauty - emission - sky - direct
+ * is what arrives after more bounces. Path tracer only. For every camera sample the pass evaluates PathTracer::sampleRay's own path
+ * (path-tracer.cpp:16-50) CUT AFTER ITS SECOND VERTEX, with that function's operations in its order.
+ * The sample and its interaction: sample i in 0..sqrtspp^2-1 of pixel (x, y) is the AOV pass's camera ray (Camera::samplePixel,
+ * camera/camera.cpp:79-95, sampler at initiate(y*width+x), setIndex(i), Sampler::global_seed = global_seed), and goes through the
+ * closest-hit search behind mcrt_intersect. The sampler is then at restore(global_seed, y*width+x, i, 1): the state after the one
+ * shuffle() of the loop's first iteration (path-tracer.cpp:23). `ia` is Interaction(hit, ray, external_ior) of the first hit
+ * (ray/interaction.cpp:12-54) with external_ior what RefractionHistory(camera_ray) gives (the scene's IOR), the sampler in that state
+ * (selectType draws DIM_INTERACTION from it) and the ray at depth 0.
+ * The camera sample misses:
+ *   sky_i = Scene::skyColor(ray) (scene.cpp:219-223); everything else is 0.
+ * Otherwise, with throughput (1, 1, 1) - the products with it are exact and not written out:
+ *   emission_i   = Integrator::sampleEmissive(ia, ls0) (integrator.cpp:93-110), ls0 the LightSample sampleRay starts with
+ *   sampled half   Integrator::sampleDirect (integrator.cpp:31-86) in two halves around its shadow ray. When the first half (:31-66)
+ *                  builds a shadow ray, that ray goes through the unchanged closest-hit search and light_i is the second half (:68-86)
+ *                  with that hit; otherwise light_i = 0. The first half leaves ls.light and ls.select_probability as sampleDirect does.
+ *   unoccluded_i = light_i when the search returned the selected light; otherwise the second half with the hit {surface = ls.light,
+ *                  t = dist}, dist = length(light point - shadow ray's start) - the light as if nothing stood before it; 0 when no
+ *                  shadow ray was built. So light_i <= unoccluded_i word for word, and light / unoccluded is the shadow matte.
+ *   bounce half    ia.sampleBSDF(f, ls.bsdf_pdf, ray1) (interaction.cpp:56-72), T = f / ls.bsdf_pdf. The bounce is cut when it returns
+ *                  false or when compMax(T) * ray1.refraction_scale == 0 (Integrator::absorb's first test, integrator.cpp:112-116; at
+ *                  depth 1 its roulette does not play): bounce_i = 0. Otherwise ray1 goes through the search; on a miss
+ *                  bounce_i = skyColor(ray1) * T, on a hit bounce_i = sampleEmissive(ia1, ls) * T with ia1 what Interaction's
+ *                  constructor derives for that hit at depth 1 (position, material, geometric normal, inside, t, out; dirac_delta as
+ *                  ray1 carries it) and ls the light sample of vertex 1: light and select_probability from the sampled half, bsdf_pdf
+ *                  from the bounce half. So a lamp the bounce finds is weighted against the sampled half exactly as the path tracer
+ *                  weights it, and light + bounce is the whole direct light, once.
+ *   direct_i     = light_i + bounce_i, in this order
+ * Both rays of a sample go through the search in one launch of 2 rays per sample. Per pixel every channel word is
+ * (sum over i, ascending, in ONE FP64 accumulator) / spp: box means like the AOVs, every sample one addend (zeros included). At
+ * sqrtspp 1, in a scene whose paths all end by their second vertex, (emission + direct) + sky is the path tracer's frame bit for bit.
+ * The frame does not depend on chunking (option MCRT_AOV_CHUNK_RAYS: here the shadow and bounce slots per launch group, always whole
+ * pixels, one at least; default: what 2^17 pixels take, at least 2^24 and at most 2^26 slots), sharding or launch shape, bit for bit. cam->shard_* is honoured exactly as in mcrt_render_aov_device;
+ * cam->film_* is IGNORED. Both calls are synchronous on the context's stream. Refused with a message (mcrt_last_error): before
+ * mcrt_upload_scene (MCRT_ERR_NO_SCENE), and with MCRT_ERR_INVALID a render in flight, a bad shard, and all five channels NULL.
+ * stats: paths = camera samples; rays = 3 * paths: the camera ray and BOTH slots of every sample traced - the slots of a sample without
+ * a shadow or a bounce ray hold its camera ray and go through the search too, their results unread (dead slots are not compacted) -;
+ * kernel_ms (HIP events around the pass's launches), total_ms, kernel_launches (5 per chunk).
+ * Not done: photon-mapped frames, deeper path classes (diffuse / specular indirect), per-light groups, filter-weighted means. */
+typedef struct mcrt_lighting_buffers { /* every pointer may be NULL = channel not wanted (not all); DEVICE memory, owned rows only, packed like d_out_rgb */
+    double* emission;     /* [rows][width][3] */
+    double* sky;          /* [rows][width][3] */
+    double* direct;       /* [rows][width][3] */
+    double* light;        /* [rows][width][3] */
+    double* unoccluded;   /* [rows][width][3] */
+} mcrt_lighting_buffers;
+int mcrt_render_lighting_device(mcrt_ctx* ctx, const mcrt_camera_desc* cam, uint32_t global_seed, const mcrt_lighting_buffers* d_buffers,
+                                mcrt_stats* stats /* may be NULL */);
+/* Same with HOST pointers to FULL frames: rows this shard does not own are left untouched. */
+int mcrt_render_lighting(mcrt_ctx* ctx, const mcrt_camera_desc* cam, uint32_t global_seed, const mcrt_lighting_buffers* buffers,
+                         mcrt_stats* stats /* may be NULL */);
+
 /* Photon emission pass on the GPU. Replaces the thread fan-out of
  * PhotonMapper::PhotonMapper (integrator/photon-mapper/photon-mapper.cpp:80-115: per emission
  * Sampler::initiate(light), setIndex(offset+i), light point + cosine direction, emitPhoton :225-277) for

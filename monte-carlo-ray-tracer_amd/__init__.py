@@ -183,6 +183,15 @@ OCCLUSION_MAX_RAYS = 64
 OCCLUSION_CHANNELS = {"ao": (np.float64, 1), "sky": (np.float64, 1), "bent_normal": (np.float64, 3)}
 
 
+class LightingBuffers(C.Structure):
+    """mcrt_lighting_buffers: one pointer per channel of the lighting passes, NULL = channel not wanted."""
+    _fields_ = [("emission", C.c_void_p), ("sky", C.c_void_p), ("direct", C.c_void_p), ("light", C.c_void_p), ("unoccluded", C.c_void_p)]
+
+
+# channel -> (dtype, values per pixel), in mcrt_lighting_buffers order
+LIGHTING_CHANNELS = {"emission": (np.float64, 3), "sky": (np.float64, 3), "direct": (np.float64, 3), "light": (np.float64, 3), "unoccluded": (np.float64, 3)}
+
+
 class DenoiseParams(C.Structure):
     """mcrt_denoise_params: a zero field = the default (include/mcrt.h)."""
     _fields_ = [("iterations", C.c_uint32), ("normal_power_log2", C.c_uint32), ("sigma_color", C.c_double), ("sigma_plane", C.c_double),
@@ -488,7 +497,7 @@ def _exr_source(a):
 _EXR_FLOAT_LAYERS = ("depth", "position", "variance", "error", "level")
 
 
-def exr_layers(rgb=None, aov=None, stats=None, highlights=None, robust=None, denoised=None, pixel_types=None, mattes=None, errors=None, occlusion=None):
+def exr_layers(rgb=None, aov=None, stats=None, highlights=None, robust=None, denoised=None, pixel_types=None, mattes=None, errors=None, occlusion=None, lighting=None):
     """The channel dict Context.exr_save takes, from what the render_* and denoise_* methods return, under fixed names:
       rgb [H,W,3]                       R, G, B
       aov (render_aov's dict)           depth.Z, position.X/Y/Z, normal.X/Y/Z, shading_normal.X/Y/Z, albedo.R/G/B, coverage.A, surface.id, material.id
@@ -503,6 +512,8 @@ def exr_layers(rgb=None, aov=None, stats=None, highlights=None, robust=None, den
                                         that are there), always FLOAT
       occlusion (render_occlusion's)    occlusion.ao, occlusion.sky, occlusion.bent.X/Y/Z (those that are there): HALF like the AOV
                                         pass's coverage and normals
+      lighting (render_lighting's)      lighting.emission.R/G/B, lighting.sky.R/G/B, lighting.direct.R/G/B, lighting.light.R/G/B,
+                                        lighting.unoccluded.R/G/B (those that are there): colour, HALF
     -> dict name -> (view [H,W], "half" | "float" | "uint"). Colour is HALF; depth, position, variance, error and level FLOAT; ids and
     counts UINT. pixel_types: {channel or layer name: type} overrides that (a layer is a name without its last component). The views
     are of the arrays and tensors given, numpy or torch alike: nothing is copied."""
@@ -562,6 +573,9 @@ def exr_layers(rgb=None, aov=None, stats=None, highlights=None, robust=None, den
             put("occlusion", (key,), occlusion[key])
     if occlusion is not None and occlusion.get("bent_normal") is not None:
         put("occlusion.bent", "XYZ", occlusion["bent_normal"])
+    for key in LIGHTING_CHANNELS:
+        if lighting is not None and lighting.get(key) is not None:
+            put("lighting." + key, "RGB", lighting[key])
     return out
 
 
@@ -569,7 +583,7 @@ def exr_unlayer(channels):
     """The inverse of exr_layers: from a dict name -> frame [H,W] (Context.exr_load's, numpy arrays or torch tensors) the keyword dict
     exr_layers takes, for the names documented there - rgb [H,W,3]; aov with its [H,W,3] and [H,W] members; stats; highlights with tops
     [H,W,4,3] and level; robust; denoised {name: {"rgb", "variance", "error"}} for every other layer that has R, G and B but no A (R, G,
-    B, A are a matte's layer); occlusion with ao, sky and bent_normal [H,W,3]; errors. A layer is taken when all its parts are there; every other name comes back under "other".
+    B, A are a matte's layer); occlusion with ao, sky and bent_normal [H,W,3]; lighting with its [H,W,3] channels; errors. A layer is taken when all its parts are there; every other name comes back under "other".
     Frames are stacked where they live."""
     left = dict(channels)
 
@@ -618,6 +632,13 @@ def exr_unlayer(channels):
             occlusion[key] = frame
     if occlusion:
         out["occlusion"] = occlusion
+    lighting = {}
+    for key in LIGHTING_CHANNELS:
+        frame = take("lighting." + key, "RGB")
+        if frame is not None:
+            lighting[key] = frame
+    if lighting:
+        out["lighting"] = lighting
     errors = {}
     for key, part in COMPARE_ERROR_CHANNELS.items():
         frame = take("error", (part,))
@@ -783,6 +804,9 @@ def lib():
     if hasattr(L, "mcrt_render_occlusion"):  # (likewise)
         L.mcrt_render_occlusion.argtypes = [vp, C.POINTER(CameraDesc), C.c_uint32, C.POINTER(OcclusionParams), C.POINTER(OcclusionBuffers), C.POINTER(Stats)]
         L.mcrt_render_occlusion_device.argtypes = L.mcrt_render_occlusion.argtypes
+    if hasattr(L, "mcrt_render_lighting"):  # (likewise)
+        L.mcrt_render_lighting.argtypes = [vp, C.POINTER(CameraDesc), C.c_uint32, C.POINTER(LightingBuffers), C.POINTER(Stats)]
+        L.mcrt_render_lighting_device.argtypes = L.mcrt_render_lighting.argtypes
     if hasattr(L, "mcrt_frame_compare"):  # (likewise)
         L.mcrt_frame_compare.argtypes = [vp, C.c_uint32, C.c_uint32, vp, vp, vp, C.POINTER(CompareParams), C.POINTER(CompareMaps), C.POINTER(CompareResult), C.POINTER(Stats)]
         L.mcrt_frame_compare_device.argtypes = L.mcrt_frame_compare.argtypes
@@ -1281,6 +1305,37 @@ class Context:
         st = Stats()
         self._check(self._lib.mcrt_render_occlusion_device(self._h, C.byref(cam), int(global_seed), C.byref(par), C.byref(bufs), C.byref(st)),
                     "mcrt_render_occlusion_device")
+        return st.as_dict()
+
+    def render_lighting(self, cam, global_seed, channels=None, out=None, stats=None):
+        """mcrt_render_lighting: the lighting frame of a path-traced render of cam and global_seed -> dict "emission", "sky", "direct",
+        "light", "unoccluded", each [H,W,3]: the path tracer's path cut after its second vertex, split up (include/mcrt.h "Lighting
+        passes"); light / unoccluded is the shadow matte. channels: the names wanted (LIGHTING_CHANNELS; None = all). out: a dict of
+        arrays to write into instead of fresh zeros - the call only writes the rows cam's shard owns. stats: a dict that receives
+        mcrt_stats."""
+        self._sync_env()
+        names = list(LIGHTING_CHANNELS) if channels is None else list(channels)
+        res, bufs = {}, LightingBuffers()
+        for name in names:
+            dtype, k = LIGHTING_CHANNELS[name]
+            shape = (cam.height, cam.width, k)
+            a = out[name] if out is not None and name in out else np.zeros(shape, dtype=dtype)
+            assert a.dtype == dtype and a.shape == shape and a.flags["C_CONTIGUOUS"], name
+            res[name] = a
+            setattr(bufs, name, a.ctypes.data)
+        st = Stats()
+        self._check(self._lib.mcrt_render_lighting(self._h, C.byref(cam), int(global_seed), C.byref(bufs), C.byref(st)), "mcrt_render_lighting")
+        if stats is not None:
+            stats.update(st.as_dict())
+        return res
+
+    def render_lighting_device(self, cam, global_seed, pointers):
+        """mcrt_render_lighting_device: pointers = dict channel -> raw device pointer (owned rows only, packed like render_device's
+        output); channels left out are not computed. Synchronous; returns the stats dict."""
+        self._sync_env()
+        bufs = _pointer_struct(LightingBuffers, pointers, LIGHTING_CHANNELS)
+        st = Stats()
+        self._check(self._lib.mcrt_render_lighting_device(self._h, C.byref(cam), int(global_seed), C.byref(bufs), C.byref(st)), "mcrt_render_lighting_device")
         return st.as_dict()
 
     def render_matte(self, cam, global_seed, key="material", ranks=MATTE_DEFAULT_RANKS, names=None, surface_key=None, aov=None, out=None, stats=None,

@@ -8,7 +8,7 @@
 //               [--denoise-dual OUT.f64 [--denoise-dual-out VAR.f64]] [--stats PREFIX] [--robust PREFIX [--robust-kappa X] [--robust-radius R]]
 //               [--converge TARGET [--max-spp N]] [--exr OUT.exr [--exr-compression none|zip]]
 //               [--matte PREFIX [--matte-key material|surface] [--matte-ranks N]] [--compare REF [--compare-layer PREFIX]]
-//               [--occlusion PREFIX [--occlusion-rays N] [--occlusion-distance D]]
+//               [--occlusion PREFIX [--occlusion-rays N] [--occlusion-distance D]] [--lighting PREFIX]
 //
 // Writes the frame as raw FP64 RGB, row-major (what Image::operator() holds, camera/image.cpp:53-56),
 // and prints the statistics. --tga also develops it the way Image::save does (auto exposure / gain, tone map, sRGB bytes:
@@ -57,6 +57,9 @@
 // camera sample that hits, default 1, 64 at most; --occlusion-distance D: hits farther away do not occlude, default 0 = unbounded):
 // PREFIX.ao.f64, PREFIX.sky.f64 ([H][W]) and PREFIX.bent_normal.f64 ([H][W][3], not normalised), raw FP64. With --exr the file also holds
 // them as the HALF channels occlusion.ao, occlusion.sky and occlusion.bent.X/Y/Z.
+// --lighting also writes the lighting passes of the same camera and seed (mcrt_render_lighting, device 0; path tracer only): PREFIX.emission.f64,
+// .sky.f64, .direct.f64, .light.f64 and .unoccluded.f64 ([H][W][3], raw FP64). With --exr the file also holds them as the HALF channels
+// lighting.emission.R/G/B ... lighting.unoccluded.R/G/B.
 // --devices renders the frame on several GPUs from this one process (mcrt_render_multi: one host thread per GPU).
 #include <cstdio>
 #include <cstdlib>
@@ -86,7 +89,7 @@ int main(int argc, char** argv) {
     image.plain = (uint32_t)mcrt_image_param(img, "image_plain");
     image.exposure_compensation = from_bits(mcrt_image_param(img, "image_exposure_ev_bits"));
     image.gain_compensation = from_bits(mcrt_image_param(img, "image_gain_ev_bits"));
-    std::string tga, aov, denoise, dvar, dvar_out, ddual, ddual_out, pstats, robust, exr, matte, compare, compare_layer, occlusion;
+    std::string tga, aov, denoise, dvar, dvar_out, ddual, ddual_out, pstats, robust, exr, matte, compare, compare_layer, occlusion, lighting;
     mcrt_occlusion_params oparams{};
     bool compare_exr = false;
     mcrt_matte_params mparams{};
@@ -140,6 +143,7 @@ int main(int argc, char** argv) {
         else if (k == "--matte" && i + 1 < argc) matte = argv[++i];
         else if (k == "--compare" && i + 1 < argc) compare = argv[++i];
         else if (k == "--occlusion" && i + 1 < argc) occlusion = argv[++i];
+        else if (k == "--lighting" && i + 1 < argc) lighting = argv[++i];
         else if (k == "--occlusion-rays") oparams.rays = (uint32_t)val();
         else if (k == "--occlusion-distance" && i + 1 < argc) oparams.max_distance = std::strtod(argv[++i], nullptr);
         else if (k == "--compare-layer" && i + 1 < argc) compare_layer = argv[++i];
@@ -631,6 +635,41 @@ int main(int argc, char** argv) {
             exr_one("occlusion.sky", exr_keep(sky), MCRT_EXR_HALF, 1, 0);
             exr_layer("occlusion.bent", "XYZ", exr_keep(bent), MCRT_EXR_HALF);
         }
+    }
+    if (!lighting.empty()) {
+        if (photon) {
+            std::fprintf(stderr, "--lighting: the lighting passes are the path tracer's (not with --photon)\n");
+            return 1;
+        }
+        const size_t px = (size_t)cam.width * cam.height;
+        static const char* const names[5] = {"emission", "sky", "direct", "light", "unoccluded"};
+        std::vector<double> frames[5];
+        for (auto& f : frames) f.resize(px * 3);
+        const mcrt_lighting_buffers lb{frames[0].data(), frames[1].data(), frames[2].data(), frames[3].data(), frames[4].data()};
+        mcrt_stats lst;
+        rc = mcrt_render_lighting(ctx, &cam, seed, &lb, &lst);
+        if (rc != MCRT_OK) {
+            std::fprintf(stderr, "mcrt error %d: %s\n", rc, mcrt_last_error(ctx));
+            return 1;
+        }
+        double mean[5] = {0, 0, 0, 0, 0};
+        for (int c = 0; c < 5; c++) {
+            const std::string path = lighting + "." + names[c] + ".f64";
+            FILE* o = std::fopen(path.c_str(), "wb");
+            const bool ok = o && std::fwrite(frames[c].data(), 1, px * 24, o) == px * 24;
+            if (o) std::fclose(o);
+            if (!ok) {
+                std::fprintf(stderr, "cannot write %s\n", path.c_str());
+                return 1;
+            }
+            for (double w : frames[c]) mean[c] += w;
+            mean[c] = px ? mean[c] / (double)(px * 3) : 0.0;
+        }
+        std::printf("{\"lighting\":\"%s\",\"mean_emission\":%.6g,\"mean_sky\":%.6g,\"mean_direct\":%.6g,\"mean_light\":%.6g,\"mean_unoccluded\":%.6g,\"rays\":%llu,"
+                    "\"kernel_ms\":%.3f,\"total_ms\":%.3f,\"Mray_s\":%.1f}\n",
+                    lighting.c_str(), mean[0], mean[1], mean[2], mean[3], mean[4], (unsigned long long)lst.rays, lst.kernel_ms, lst.total_ms, lst.rays / lst.kernel_ms / 1e3);
+        if (!exr.empty())
+            for (int c = 0; c < 5; c++) exr_layer(std::string("lighting.") + names[c], "RGB", exr_keep(frames[c]), MCRT_EXR_HALF);
     }
     if (!exr.empty()) {
         const std::string a_spp = std::to_string(spp), a_seed = std::to_string(seed), a_kernel = std::to_string(st.kernel_id);

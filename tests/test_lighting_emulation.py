@@ -1,0 +1,358 @@
+"""Lighting passes, CPU tier: csrc/mcrt_lighting.hpp - the text the two kernels of csrc/mcrt_lighting.hip run - driven on the host
+(tests/emu/lighting_emu.cpp) against the reference's own arithmetic: the oracle's path-traced frame (oracle_lib.render).
+
+1. A scene built HERE in which every path ends by its second vertex: a planar floor of two coplanar triangles, above it an emissive
+   triangle pair whose material reflects nothing, between them an opaque occluder that reflects nothing, nothing else, the camera above
+   the floor looking down at it. A ray that leaves a plane cannot meet the plane again; a black surface ends the path through absorb's
+   survive == 0; a miss ends it. So the oracle's full path IS the cut path, and at sqrtspp 1 (emission + direct) + sky equals the oracle's
+   frame bit for bit: in every pixel at most one of the three is non-zero, or emission and sky are zero and direct = light + bounce is the
+   oracle's own order of additions. Six floor materials, each flat and under a quaternary SAH tree.
+2. The four scene images of test_aov_emulation.SCENES at sqrtspp 1: the cut path is a lower bound of the beauty frame, the sky is the
+   oracle's where nothing is hit.
+3. Chunks and shards give the same bits; channels that were not asked for are left alone.
+
+Frames are 70 x 13 pixels (width no multiple of 64, 910 pixels no multiple of 256) at sqrtspp 1 and 2.
+
+Bounds: bit equality at sqrtspp 1 (read off pathTracerBounce, see above); at sqrtspp 2 conftest.rel_error <= 1e-12, include/mcrt.h's
+bound for sums that agree to rounding (the oracle adds whole samples, the pass adds each channel and then the channels); against the
+beauty frame of a scene with longer paths (emission + direct) + sky <= beauty * (1 + 1e-12): every term the path adds later is
+non-negative, and the two sums of the same leading terms differ by roundings only."""
+import ctypes as C
+import functools
+import importlib
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+import test_aov_emulation as aov
+from conftest import ROOT, TESTS, rel_error
+
+WIDTH, HEIGHT, SEED, SCENES = aov.WIDTH, aov.HEIGHT, aov.SEED, aov.SCENES
+PIXELS = WIDTH * HEIGHT
+CHANNELS = ("emission", "sky", "direct", "light", "unoccluded")
+
+# mcrt_material flag bits (include/mcrt.h)
+ROUGH, ROUGH_SPECULAR, OPAQUE, EMISSIVE, DIRAC_DELTA, PERFECT_MIRROR, COMPLEX_IOR = (1 << i for i in range(7))
+# floor material -> the fields that differ from the default record (reflectance (0.8, 0.6, 0.4), everything else white, A = 1);
+# the numbers are those the scene images under tests/golden carry for materials of these kinds
+FLOORS = {
+    "lambertian": dict(flags=OPAQUE, ior=1.5),
+    "oren_nayar": dict(flags=OPAQUE | ROUGH, ior=-1.0, roughness=10.0, A=0.501645, B=0.449595),
+    "ggx": dict(flags=OPAQUE | ROUGH_SPECULAR, ior=1.333, specular_roughness=0.25, a=(0.25, 0.25)),
+    "conductor": dict(flags=OPAQUE | ROUGH_SPECULAR | COMPLEX_IOR, ior=-1.0, specular_roughness=0.1, a=(0.1, 0.1), reflectance=(1.0, 1.0, 1.0),
+                      ior_real=(0.19786621768539725, 0.5848289090087098, 1.0273623525293878), ior_imag=(3.3329151319093153, 2.3746219186140376, 1.884681468047541)),
+    "mirror": dict(flags=OPAQUE | DIRAC_DELTA | PERFECT_MIRROR, ior=-1.0, reflectance=(1.0, 1.0, 1.0)),
+    "glass": dict(flags=DIRAC_DELTA, ior=1.5, transparency=1.0, reflectance=(1.0, 1.0, 1.0)),
+}
+CONSTRUCTED = [(floor, bvh) for floor in FLOORS for bvh in (False, True)]
+
+
+def load_lighting_emu():
+    """Host build of the lighting passes (tests/emu/lighting_emu.cpp = mcrt_emu.cpp + csrc/mcrt_lighting.hpp), the way
+    test_occlusion_emulation.load_occlusion_emu builds its library."""
+    src = os.path.join(TESTS, "emu", "lighting_emu.cpp")
+    out = os.path.join(TESTS, "emu", "_build", "liblighting_emu.so")
+    csrc = os.path.join(ROOT, "monte-carlo-ray-tracer_amd", "csrc")
+    deps = [src, os.path.join(TESTS, "emu", "mcrt_emu.cpp"), os.path.join(ROOT, "include", "mcrt.h")] + [os.path.join(csrc, f) for f in os.listdir(csrc) if f.endswith(".hpp")]
+    if not os.path.exists(out) or any(os.path.getmtime(d) > os.path.getmtime(out) for d in deps):
+        os.makedirs(os.path.dirname(out), exist_ok=True)
+        tmp = "%s.%d.tmp" % (out, os.getpid())
+        subprocess.check_call(["g++", "-std=c++17", "-O2", "-ffp-contract=off", "-fPIC", "-shared", "-o", tmp, src])
+        os.replace(tmp, out)
+    L = C.CDLL(out)
+    vp = C.c_void_p
+    L.lighting_emu_rows.argtypes = [vp]
+    L.lighting_emu_rows.restype = C.c_uint32
+    L.lighting_emu_frame.argtypes = [vp, vp, C.c_uint32, C.c_int, C.c_uint64, vp]
+    return L
+
+
+@functools.lru_cache(maxsize=None)
+def _emu():
+    return load_lighting_emu()
+
+
+def _pkg():
+    return importlib.import_module("monte-carlo-ray-tracer_amd")
+
+
+def _material(pkg, **fields):
+    m = pkg.Material()
+    base = dict(reflectance=(0.8, 0.6, 0.4), specular_reflectance=(1.0, 1.0, 1.0), transmittance=(1.0, 1.0, 1.0), emittance=(0.0, 0.0, 0.0), A=1.0, ior=-1.0)
+    base.update(fields)
+    for k, v in base.items():
+        setattr(m, k, (C.c_double * len(v))(*v) if isinstance(v, tuple) else v)
+    return m
+
+
+def _quad(y, x0, x1, z0, z1, up):
+    """Two coplanar triangles of the rectangle [x0, x1] x [z0, z1] at height y whose normal cross(E1, E2) points up or down."""
+    a, b, c, d = (x0, y, z0), (x0, y, z1), (x1, y, z1), (x1, y, z0)
+    return [(a, b, c), (a, c, d)] if up else [(a, c, b), (a, d, c)]
+
+
+class ConstructedScene:
+    """What oracle_lib.render, the emulation and Context.upload_scene need of an image: a scene descriptor and the arrays it points into.
+    Surfaces 0, 1 the floor (8 x 8 at y = 0, facing up), 2, 3 the lamp (1 x 1 at y = 3, facing down, beside the camera's axis), 4, 5 the
+    occluder (1.2 x 1.2 at y = 1.5, partly between them); materials 0 floor, 1 lamp, 2 occluder."""
+
+    def __init__(self, pkg, floor):
+        tris = _quad(0.0, -4.0, 4.0, -4.0, 4.0, True) + _quad(3.0, 1.5, 2.5, -0.5, 0.5, False) + _quad(1.5, 2.0, 3.2, -0.6, 0.6, True)
+        n = len(tris)
+        v = np.array(tris, dtype=np.float64).reshape(n, 9)
+        e1, e2 = v[:, 3:6] - v[:, 0:3], v[:, 6:9] - v[:, 0:3]
+        cross = np.cross(e1, e2)
+        length = np.sqrt((cross * cross).sum(axis=1))
+        e = np.concatenate([e1, e2, cross / length[:, None]], axis=1)
+        mats = (pkg.Material * 3)(_material(pkg, **FLOORS[floor]),
+                                  _material(pkg, flags=OPAQUE | EMISSIVE, reflectance=(0.0, 0.0, 0.0), specular_reflectance=(0.0, 0.0, 0.0), emittance=(30.0, 24.0, 18.0)),
+                                  _material(pkg, flags=OPAQUE, reflectance=(0.0, 0.0, 0.0), specular_reflectance=(0.0, 0.0, 0.0)))
+        self.keep = [mats]
+
+        def arr(a, ctype):
+            a = np.ascontiguousarray(a)
+            self.keep.append(a)
+            return a.ctypes.data_as(C.POINTER(ctype))
+
+        d = pkg.SceneDesc()
+        d.abi_version = pkg.ABI_VERSION
+        d.num_nodes = 0
+        d.num_surfaces = n
+        d.surf_kind = arr(np.zeros(n, dtype=np.uint8), C.c_uint8)
+        d.surf_interpolate = arr(np.zeros(n, dtype=np.uint8), C.c_uint8)
+        d.surf_material = arr(np.array([0, 0, 1, 1, 2, 2], dtype=np.uint32), C.c_uint32)
+        d.surf_area = arr(0.5 * length, C.c_double)
+        d.surf_v = arr(v, C.c_double)
+        d.surf_e = arr(e, C.c_double)
+        d.num_materials = 3
+        d.materials = C.cast(mats, C.POINTER(pkg.Material))
+        d.num_lights = 2
+        d.light_surface = arr(np.array([2, 3], dtype=np.uint32), C.c_uint32)
+        d.light_cdf = arr(np.array([0.5, 1.0]), C.c_double)
+        d.scene_ior = 1.0
+        d.bb_min = (C.c_double * 3)(*v.reshape(-1, 3).min(axis=0))
+        d.bb_max = (C.c_double * 3)(*v.reshape(-1, 3).max(axis=0))
+        self.scene = d
+
+    def photons(self, which):
+        return None
+
+    def param(self, key):
+        return 0
+
+
+class WithBvh:
+    """The same scene under a quaternary SAH tree (surfaces in the tree's order, lights re-indexed)."""
+
+    def __init__(self, pkg, flat):
+        self.bvh = pkg.Bvh(flat.scene, kind="quaternary_sah", threads=1)
+        self.owned = self.bvh.apply(flat.scene)
+        self.scene = self.owned.desc
+        self.flat = flat
+
+    def photons(self, which):
+        return None
+
+    def param(self, key):
+        return 0
+
+
+@functools.lru_cache(maxsize=None)
+def constructed(floor, bvh):
+    pkg = _pkg()
+    pkg.lib()
+    flat = ConstructedScene(pkg, floor)
+    return WithBvh(pkg, flat) if bvh else flat
+
+
+def constructed_camera(sqrtspp, shard=None, under_the_lamp=False):
+    """Above the floor, looking down at it a little off the vertical: the view is wider than the floor, so columns at both ends see the sky.
+    under_the_lamp: just above the floor instead, looking up at the lamp's emitting side, the occluder's underside and the sky."""
+    cam = _pkg().CameraDesc()
+    forward = np.array([0.02, 1.0, 0.03]) if under_the_lamp else np.array([0.02, -1.0, 0.03])
+    forward /= np.sqrt((forward * forward).sum())
+    left = np.cross(np.array([0.0, 0.0, -1.0]), forward)
+    left /= np.sqrt((left * left).sum())
+    up = np.cross(forward, left)
+    for k, val in (("eye", (1.6, 0.25, 0.1) if under_the_lamp else (0.0, 8.0, 0.5)), ("forward", forward), ("left", left), ("up", up)):
+        setattr(cam, k, (C.c_double * 3)(*val))
+    cam.focal_length, cam.sensor_width = 1.0, 2.0
+    cam.width, cam.height, cam.sqrtspp = WIDTH, HEIGHT, sqrtspp
+    cam.shard_index, cam.shard_count, cam.shard_rows = shard if shard else (0, 1, 0)
+    cam.film_radius = 0.5
+    return cam
+
+
+def emu_frame(scene_desc, cam, flavour, chunk_rays=0, channels=CHANNELS):
+    """The emulation's frame over the camera's packed owned rows: dict channel -> [P,3]; every channel is allocated and filled with 0xAB
+    bytes, only `channels` are handed over."""
+    pkg, L = _pkg(), _emu()
+    P = L.lighting_emu_rows(C.byref(cam)) * cam.width
+    res = {k: np.empty((P, 3)) for k in CHANNELS}
+    bufs = pkg.LightingBuffers()
+    for k, a in res.items():
+        a.view(np.uint8).fill(0xAB)  # (whatever is not written shows)
+        if k in channels:
+            setattr(bufs, k, a.ctypes.data)
+    rc = L.lighting_emu_frame(C.byref(scene_desc), C.byref(cam), SEED, flavour, chunk_rays, C.byref(bufs))
+    assert rc == 0, "lighting_emu_frame: %d" % rc
+    return res
+
+
+@functools.lru_cache(maxsize=None)
+def constructed_case(floor, bvh, sqrtspp):
+    """The emulation's default frame of the constructed scene, computed once: flat scenes through the brute-force loop (flavour 1), trees
+    through the trace kernel's walk (3)."""
+    return emu_frame(constructed(floor, bvh).scene, constructed_camera(sqrtspp), 3 if bvh else 1)
+
+
+@functools.lru_cache(maxsize=None)
+def constructed_oracle(floor, bvh, sqrtspp):
+    import oracle_lib
+    frame, _ = oracle_lib.render(constructed(floor, bvh), constructed_camera(sqrtspp), SEED, _pkg().INTEGRATOR_PATH_TRACER)
+    return frame.reshape(PIXELS, 3)
+
+
+@functools.lru_cache(maxsize=None)
+def image_case(scene):
+    return emu_frame(aov._image(scene).scene, aov.camera(scene, 1), SCENES[scene])
+
+
+def recombined(f):
+    return (f["emission"] + f["direct"]) + f["sky"]
+
+
+def check_constructed(frame, floor, bvh, sqrtspp, ref, what):
+    """The checks of part 1 on a frame dict of [P,3] channels against the path-traced frame `ref` [P,3]."""
+    total = recombined(frame)
+    if sqrtspp == 1:
+        diff = np.nonzero((total.view(np.uint64) != ref.view(np.uint64)).any(axis=1))[0]
+        print("%s: %d of %d pixels differ from the path tracer's bits" % (what, diff.size, PIXELS))
+        for q in diff[:5]:
+            print("   pixel %d: emission %r direct %r (light %r) sky %r, path tracer %r" % (q, frame["emission"][q], frame["direct"][q], frame["light"][q], frame["sky"][q], ref[q]))
+        assert diff.size == 0, what
+    else:
+        err = rel_error(total, ref).max()
+        print("%s: max rel error %.3e" % (what, err))
+        assert err <= 1e-12, what
+    for k in CHANNELS:
+        assert np.isfinite(frame[k]).all() and (frame[k] >= 0.0).all(), "%s %s" % (what, k)
+    assert (frame["light"] <= frame["unoccluded"]).all() and (frame["light"] <= frame["direct"]).all(), what
+    covered = (frame["sky"] == 0.0).all(axis=1)
+    assert covered.any() and not covered.all(), what  # the floor, and the sky beside it
+    assert (frame["emission"] == 0.0).all(), what  # (the lamp shows the camera its back)
+    if floor in ("mirror", "glass"):  # dirac-delta materials take no light sample
+        assert (frame["light"] == 0.0).all() and (frame["unoccluded"] == 0.0).all(), what
+        assert (frame["direct"] > 0.0).any(), what  # the lamp in the mirror, the sky through and in the glass
+    else:
+        shadowed = (frame["unoccluded"] > frame["light"]).all(axis=1)
+        lit = (frame["light"] > 0.0).all(axis=1)
+        print("%s: %d pixels lit, %d behind the occluder" % (what, lit.sum(), shadowed.sum()))
+        assert shadowed.any() and lit.any(), what
+        if sqrtspp == 1:  # one sample: the occluder hides the light point or it does not
+            assert ((frame["light"][shadowed] == 0.0).all()), what
+
+
+@pytest.mark.parametrize("sqrtspp", [1, 2])
+@pytest.mark.parametrize("floor,bvh", CONSTRUCTED)
+def test_cut_path_is_the_whole_path_where_paths_end_by_their_second_vertex(floor, bvh, sqrtspp, oracle):
+    check_constructed(constructed_case(floor, bvh, sqrtspp), floor, bvh, sqrtspp, constructed_oracle(floor, bvh, sqrtspp),
+                      "%s floor, %s, sqrtspp %d" % (floor, "quaternary SAH" if bvh else "flat", sqrtspp))
+
+
+@pytest.mark.parametrize("sqrtspp", [1, 2])
+def test_lamp_seen_from_below_is_emission(sqrtspp, oracle):
+    """The camera under the lamp: where a sample meets the emitting side, emission is the emittance and nothing else is added (a light
+    point on the lamp's own plane is not lit by it, a black surface does not bounce); the occluder's underside is black; the rest is sky."""
+    scene, cam = constructed("lambertian", False), constructed_camera(sqrtspp, under_the_lamp=True)
+    f = emu_frame(scene.scene, cam, 1)
+    ref, _ = oracle.render(scene, cam, SEED, _pkg().INTEGRATOR_PATH_TRACER)
+    ref = ref.reshape(PIXELS, 3)
+    total = recombined(f)
+    if sqrtspp == 1:
+        assert total.tobytes() == ref.tobytes()
+    else:
+        assert rel_error(total, ref).max() <= 1e-12
+    lamp = (f["emission"] == np.array([30.0, 24.0, 18.0])).all(axis=1)
+    print("sqrtspp %d: %d pixels all lamp, %d some lamp, %d some sky" % (sqrtspp, lamp.sum(), (f["emission"] > 0).any(axis=1).sum(), (f["sky"] > 0).any(axis=1).sum()))
+    assert lamp.any() and (f["sky"] > 0).any()
+    if sqrtspp == 1:  # one sample: the lamp or the sky, never both
+        assert not ((f["emission"] > 0).any(axis=1) & (f["sky"] > 0).any(axis=1)).any()
+    assert (f["direct"] == 0.0).all() and (f["light"] == 0.0).all() and (f["unoccluded"] == 0.0).all()
+    black = (total == 0.0).all(axis=1)
+    assert black.any()  # the occluder's underside
+
+
+def test_mirror_floor_shows_the_lamp_and_glass_the_sky():
+    """What the constructed scene is there for beyond the sums: the lamp reflected in the mirror with its full emittance (a bounce that
+    carries dirac_delta is not weighted), light sampling and bounce sharing the lamp on the diffuse floors (both halves non-zero in one
+    pixel, the bounce half weighted down)."""
+    mirror = constructed_case("mirror", False, 1)
+    lamp = (np.abs(mirror["direct"] / np.array([30.0, 24.0, 18.0]) - 1.0) <= 1e-12).all(axis=1)  # (f / pdf of a mirror is 1 to rounding)
+    assert lamp.any()
+    for floor in ("lambertian", "oren_nayar", "ggx"):
+        f = constructed_case(floor, False, 2)
+        both = ((f["light"] > 0.0) & (f["direct"] > f["light"])).all(axis=1)
+        assert both.any(), floor
+    tree = constructed_case("ggx", True, 2)
+    flat = constructed_case("ggx", False, 2)
+    for k in CHANNELS:  # the tree reorders the surfaces and re-indexes the lights: the frame is the same
+        assert tree[k].tobytes() == flat[k].tobytes(), k
+
+
+@pytest.mark.parametrize("scene", list(SCENES))
+def test_cut_path_is_below_the_beauty_frame_and_the_sky_is_the_oracles(scene, oracle):
+    f = image_case(scene)
+    beauty, _ = oracle.render(aov._image(scene), aov.camera(scene, 1), SEED, _pkg().INTEGRATOR_PATH_TRACER)
+    beauty = beauty.reshape(PIXELS, 3)
+    for k in CHANNELS:
+        assert np.isfinite(f[k]).all(), k
+    total = recombined(f)
+    over = total > beauty * (1.0 + 1e-12)
+    print("%s: cut path / beauty = %.4f of the frame's sum, %d words over" % (scene, total.sum() / beauty.sum(), over.sum()))
+    assert not over.any()
+    coverage = aov.emu_frame(scene, 1)[0]["coverage"]
+    empty = coverage == 0.0
+    if scene == "quadric":
+        assert empty.any()
+    assert f["sky"][empty].tobytes() == beauty[empty].tobytes()
+    assert (f["sky"][~empty] == 0.0).all() and (f["emission"][empty] == 0.0).all() and (f["direct"][empty] == 0.0).all()
+    assert (f["light"] <= f["unoccluded"]).all() and (f["light"] <= f["direct"]).all()
+
+
+def test_frame_does_not_depend_on_chunks_or_shards():
+    """One pixel per chunk, 64 K slots per chunk, the default (one chunk); 1, 2 and 3 shards of 2-row groups dealt round robin (13 rows:
+    the last group ragged). coffee_maker_qsah at sqrtspp 2: vertex normals, the trace kernel's walk, 8 slots a pixel."""
+    scene, sqrtspp = "coffee_maker_qsah", 2
+    desc = aov._image(scene).scene
+    whole = emu_frame(desc, aov.camera(scene, sqrtspp), SCENES[scene])
+    assert all((whole[k] != 0.0).any() for k in ("direct", "light", "unoccluded"))
+    for chunk_rays in (1, 65536 // 16, 100):
+        chunked = emu_frame(desc, aov.camera(scene, sqrtspp), SCENES[scene], chunk_rays=chunk_rays)
+        for k in CHANNELS:
+            assert whole[k].tobytes() == chunked[k].tobytes(), "chunk_rays %d: %s" % (chunk_rays, k)
+    for count in (1, 2, 3):
+        seen = 0
+        for index in range(count):
+            cam = aov.camera(scene, sqrtspp, (index, count, 2))
+            rows = _pkg().shard_rows(cam)
+            part = emu_frame(desc, cam, SCENES[scene])
+            for k in CHANNELS:
+                full = whole[k].reshape(HEIGHT, WIDTH, 3)
+                assert full[rows].tobytes() == part[k].tobytes(), "shard %d of %d: %s" % (index, count, k)
+            seen += len(rows)
+        assert seen == HEIGHT
+
+
+def test_unrequested_channels_keep_their_fill():
+    whole = constructed_case("ggx", True, 2)
+    scene, cam = constructed("ggx", True).scene, constructed_camera(2)
+    for asked in (("light",), ("sky", "unoccluded"), ("emission", "direct")):
+        part = emu_frame(scene, cam, 3, channels=asked)
+        for k in CHANNELS:
+            if k in asked:
+                assert part[k].tobytes() == whole[k].tobytes(), k
+            else:
+                assert (part[k].view(np.uint8) == 0xAB).all(), k
