@@ -1152,7 +1152,8 @@ int mcrt_render_occlusion(mcrt_ctx* ctx, const mcrt_camera_desc* cam, uint32_t g
  * stats: paths = camera samples; rays = 3 * paths: the camera ray and BOTH slots of every sample traced - the slots of a sample without
  * a shadow or a bounce ray hold its camera ray and go through the search too, their results unread (dead slots are not compacted) -;
  * kernel_ms (HIP events around the pass's launches), total_ms, kernel_launches (5 per chunk).
- * Not done: photon-mapped frames, deeper path classes (diffuse / specular indirect), per-light groups, filter-weighted means. */
+ * Not done: photon-mapped frames, deeper path classes (diffuse / specular indirect), filter-weighted means. (Per-light frames of the
+ * whole path: "Light groups" below.) */
 typedef struct mcrt_lighting_buffers { /* every pointer may be NULL = channel not wanted (not all); DEVICE memory, owned rows only, packed like d_out_rgb */
     double* emission;     /* [rows][width][3] */
     double* sky;          /* [rows][width][3] */
@@ -1165,6 +1166,84 @@ int mcrt_render_lighting_device(mcrt_ctx* ctx, const mcrt_camera_desc* cam, uint
 /* Same with HOST pointers to FULL frames: rows this shard does not own are left untouched. */
 int mcrt_render_lighting(mcrt_ctx* ctx, const mcrt_camera_desc* cam, uint32_t global_seed, const mcrt_lighting_buffers* buffers,
                          mcrt_stats* stats /* may be NULL */);
+
+/* ------------------------------------------------------------------------------------------
+ * Light groups: the path-traced frame split by emitter, EVERY bounce - one frame ("plane") per group of emitters and one for the sky,
+ * which add up to the beauty frame, so that dimming a lamp, recolouring another or turning the sky down is a weighted sum of planes.
+ * Path tracer only. The lighting passes above are iteration 0 of what is defined here.
+ * The sample: sample i in 0..sqrtspp^2-1 of pixel (x, y) is the AOV pass's camera ray (Camera::samplePixel, camera/camera.cpp:79-95,
+ * sampler at initiate(y*width+x), setIndex(i), Sampler::global_seed = global_seed).
+ * The path is the while (true) of PathTracer::sampleRay (path-tracer.cpp:14-51) with the same functions in the same order and the same
+ * throughput: ray = the camera ray, throughput = (1, 1, 1), ls = {0, 0, none}, RefractionHistory(ray). Iteration k = 0, 1, ... begins
+ * with one shuffle(), so its sampler is restore(global_seed, y*width+x, i, k + 1). Then, as :25-49 have it:
+ *   the ray goes through the closest-hit search behind mcrt_intersect. On a miss c = Scene::skyColor(ray) (scene.cpp:219-223) is added
+ *     and the path ends.
+ *   ia = Interaction(hit, ray, history.externalIOR(ray)) (ray/interaction.cpp:12-54)
+ *   c = Integrator::sampleEmissive(ia, ls) (integrator.cpp:93-110) is added
+ *   c = Integrator::sampleDirect(ia, ls) (integrator.cpp:31-86) is added: its first half (:31-66) chooses the light point, leaves
+ *     ls.light and ls.select_probability and builds the shadow ray or returns zeros; the shadow ray goes through the same search; the
+ *     second half (:68-86) is evaluated with that hit
+ *   ia.sampleBSDF(f, ls.bsdf_pdf, ray) (interaction.cpp:56-72); false ends the path
+ *   throughput = throughput * (f / ls.bsdf_pdf)
+ *   Integrator::absorb(ray, throughput) (integrator.cpp:112-129, its roulette drawing DIM_ABSORB of this iteration's sampler); true
+ *     ends the path
+ *   history.update(ray)
+ * The sample keeps one radiance R_p per plane p, all starting at (0, 0, 0). Where the path tracer executes radiance = radiance +
+ * c * throughput, the pass executes R_p = R_p + c * throughput for exactly ONE plane p:
+ *   c = skyColor(ray):           p = sky_plane
+ *   c = sampleEmissive(ia, ls):  p = plane[ia.surface]
+ *   c = sampleDirect(ia, ls):    p = plane[ls.light]
+ * with plane[s] = surface_group[s] for an emitter s (a surface whose material carries MCRT_MAT_EMISSIVE). The operands and their order
+ * are the path tracer's: the direct light of vertex k is added with the throughput of vertex k, before anything of vertex k + 1. A term
+ * that the functions return as zeros is skipped: all values are >= +0.0, so the bits are the same. Per pixel and plane every word of the
+ * frame is (((0.0 + R_p(0)) + R_p(1)) + ...) / (double)spp: ascending i, one FP64 accumulator per word, not clamped - box means.
+ * Parameters (params NULL, or a field zero: the default):
+ *   num_groups     G, 1 .. MCRT_LIGHT_GROUPS_MAX (0 = 1)
+ *   surface_group  HOST [num_surfaces of the uploaded scene]: the group of every surface. Entries of surfaces that are not emitters are
+ *                  ignored; an emitter's entry must be < G. NULL: every emitter in group 0.
+ *   sky_plane      read when flags carries MCRT_LIGHT_GROUPS_SKY_PLANE (0 is a plane like any other): the plane that takes the sky, any
+ *                  value <= G. Otherwise G: a plane of its own after the groups. The number of planes is P = max(G, sky_plane + 1)
+ *                  (mcrt_light_group_planes; at most MCRT_LIGHT_GROUPS_MAX + 1 = 16).
+ *   max_depth      D; 0 = the whole path. With D > 0 iteration k == D takes only its miss or its sampleEmissive term and the path ends
+ *                  there: no light sample, no bounce. D = 1 is the lighting passes' cut - planes of direct light only -, and the
+ *                  indirect light per group is the full planes minus these.
+ * Output: d_planes, [P][rows][width][3] doubles, the rows this shard owns packed like d_out_rgb. cam->shard_* is honoured exactly as in
+ * mcrt_render_aov_device; cam->film_* is IGNORED. Both calls are synchronous on the context's stream.
+ * What holds, bit for bit unless said otherwise:
+ *   - The planes are a function of scene, camera, seed and parameters. They do not depend on chunking (option MCRT_AOV_CHUNK_RAYS: here
+ *     the shadow and bounce slots of iteration 0 per chunk - 2 per sample, whole pixels, one at least; default: what 2^17 pixels take, at least
+ *     2^25 and at most 2^26 slots, cut down to what 8 GiB of path state hold), sharding, launch shape, or the order in which live samples are queued.
+ *   - A group's plane does not depend on how the OTHER emitters are grouped.
+ *   - With G = 1, surface_group NULL, sky_plane = 0 and D = 0, plane 0 is the box-film frame of mcrt_render (path tracer, same camera
+ *     and seed), in the exact library, wherever that frame's mean is neither negative nor NaN.
+ *   - With more planes their sum agrees with that frame to rounding: relative error <= 1e-12, this header's bound for sums of
+ *     non-negative terms taken in another order.
+ * Refused with a message (mcrt_last_error): before mcrt_upload_scene (MCRT_ERR_NO_SCENE); with MCRT_ERR_INVALID a render in flight, a bad
+ * camera or shard, d_planes NULL, G > MCRT_LIGHT_GROUPS_MAX, sky_plane > G, an emitter whose surface_group entry is >= G (the surface is
+ * named); with MCRT_ERR_UNSUPPORTED a path that nests more dielectric media than the history's 8 entries in registers' reach (mcrt_render
+ * renders such frames again through the wavefront pipeline's deep rows; this pass says so and stops), and a frame whose paths are still
+ * alive after 4096 iterations (the host loop is bounded).
+ * stats: paths = camera samples; rays = the rays handed to the search: the camera rays and 2 per sample alive at every iteration that
+ * traces (a sample without a shadow or a bounce ray has a finite dummy traced in that slot; a sample whose ray missed is not alive: its
+ * sky was added where the miss was found); kernel_ms (HIP events around the pass's
+ * launches), total_ms, kernel_launches.
+ * Not done: photon-mapped frames, a split by lobe (diffuse / glossy / transmission), filter-weighted means, nesting deeper than 8 media. */
+#define MCRT_LIGHT_GROUPS_MAX 15u
+enum { MCRT_LIGHT_GROUPS_SKY_PLANE = 1u }; /* mcrt_light_group_params.flags: sky_plane is given */
+typedef struct mcrt_light_group_params {
+    uint32_t num_groups;           /* G; 0 = 1 */
+    uint32_t flags;                /* MCRT_LIGHT_GROUPS_* */
+    uint32_t sky_plane;            /* with MCRT_LIGHT_GROUPS_SKY_PLANE: <= G; otherwise ignored (the sky's plane is G) */
+    uint32_t max_depth;            /* D; 0 = the whole path */
+    const uint32_t* surface_group; /* HOST [num_surfaces], or NULL = every emitter in group 0 */
+} mcrt_light_group_params;         /* 24 bytes */
+/* P of these parameters (NULL: 2, one group and the sky); 0 when num_groups or sky_plane is out of range. */
+uint32_t mcrt_light_group_planes(const mcrt_light_group_params* params);
+int mcrt_render_light_groups_device(mcrt_ctx* ctx, const mcrt_camera_desc* cam, uint32_t global_seed, const mcrt_light_group_params* params /* may be NULL */,
+                                    double* d_planes, mcrt_stats* stats /* may be NULL */);
+/* Same with a HOST pointer to P FULL frames, [P][height][width][3]: rows this shard does not own are left untouched. */
+int mcrt_render_light_groups(mcrt_ctx* ctx, const mcrt_camera_desc* cam, uint32_t global_seed, const mcrt_light_group_params* params /* may be NULL */,
+                             double* planes, mcrt_stats* stats /* may be NULL */);
 
 /* Photon emission pass on the GPU. Replaces the thread fan-out of
  * PhotonMapper::PhotonMapper (integrator/photon-mapper/photon-mapper.cpp:80-115: per emission

@@ -192,6 +192,48 @@ class LightingBuffers(C.Structure):
 LIGHTING_CHANNELS = {"emission": (np.float64, 3), "sky": (np.float64, 3), "direct": (np.float64, 3), "light": (np.float64, 3), "unoccluded": (np.float64, 3)}
 
 
+class LightGroupParams(C.Structure):
+    """mcrt_light_group_params: num_groups (0 = 1), MCRT_LIGHT_GROUPS_* flags, sky_plane (read with LIGHT_GROUPS_SKY_PLANE), max_depth
+    (0 = the whole path), surface_group (host uint32 per surface, NULL = every emitter in group 0)."""
+    _fields_ = [("num_groups", C.c_uint32), ("flags", C.c_uint32), ("sky_plane", C.c_uint32), ("max_depth", C.c_uint32), ("surface_group", C.c_void_p)]
+
+
+LIGHT_GROUPS_MAX = 15
+LIGHT_GROUPS_SKY_PLANE = 1
+MAT_EMISSIVE = 1 << 3
+
+
+def light_group_map(scene, by="material"):
+    """surface_group and plane names for Context.render_light_groups from a scene descriptor (SceneDesc): -> (groups [num_surfaces]
+    uint32, names). by="material": one group per emissive material, in the order of the materials, named "material%u" by the material's
+    index; by="light": one group per emitter surface, in the order of the surfaces, named "light%u" by the surface's index; by="one":
+    every emitter in group 0, named "lights". names ends with "sky", the plane the sky takes by default. More than LIGHT_GROUPS_MAX
+    groups are a ValueError."""
+    n = int(scene.num_surfaces)
+    material = np.ctypeslib.as_array(scene.surf_material, shape=(n,)) if n else np.zeros(0, dtype=np.uint32)
+    emissive = np.array([bool(scene.materials[i].flags & MAT_EMISSIVE) for i in range(int(scene.num_materials))], dtype=bool)
+    emitter = emissive[material] if n else np.zeros(0, dtype=bool)
+    groups = np.zeros(n, dtype=np.uint32)
+    if by == "material":
+        ids = [int(m) for m in np.nonzero(emissive)[0] if (material[emitter] == m).any()]
+        for g, m in enumerate(ids):
+            groups[emitter & (material == m)] = g
+        names = ["material%u" % m for m in ids]
+    elif by == "light":
+        ids = [int(i) for i in np.nonzero(emitter)[0]]
+        groups[ids] = np.arange(len(ids), dtype=np.uint32)
+        names = ["light%u" % i for i in ids]
+    elif by == "one":
+        names = ["lights"]
+    else:
+        raise ValueError("light_group_map: by must be \"material\", \"light\" or \"one\", not %r" % (by,))
+    if not names:
+        names = ["lights"]  # (a scene without emitters: one empty group)
+    if len(names) > LIGHT_GROUPS_MAX:
+        raise ValueError("light_group_map: %d groups by %s, at most %d can be rendered" % (len(names), by, LIGHT_GROUPS_MAX))
+    return groups, names + ["sky"]
+
+
 class DenoiseParams(C.Structure):
     """mcrt_denoise_params: a zero field = the default (include/mcrt.h)."""
     _fields_ = [("iterations", C.c_uint32), ("normal_power_log2", C.c_uint32), ("sigma_color", C.c_double), ("sigma_plane", C.c_double),
@@ -497,7 +539,7 @@ def _exr_source(a):
 _EXR_FLOAT_LAYERS = ("depth", "position", "variance", "error", "level")
 
 
-def exr_layers(rgb=None, aov=None, stats=None, highlights=None, robust=None, denoised=None, pixel_types=None, mattes=None, errors=None, occlusion=None, lighting=None):
+def exr_layers(rgb=None, aov=None, stats=None, highlights=None, robust=None, denoised=None, pixel_types=None, mattes=None, errors=None, occlusion=None, lighting=None, light_groups=None):
     """The channel dict Context.exr_save takes, from what the render_* and denoise_* methods return, under fixed names:
       rgb [H,W,3]                       R, G, B
       aov (render_aov's dict)           depth.Z, position.X/Y/Z, normal.X/Y/Z, shading_normal.X/Y/Z, albedo.R/G/B, coverage.A, surface.id, material.id
@@ -514,6 +556,8 @@ def exr_layers(rgb=None, aov=None, stats=None, highlights=None, robust=None, den
                                         pass's coverage and normals
       lighting (render_lighting's)      lighting.emission.R/G/B, lighting.sky.R/G/B, lighting.direct.R/G/B, lighting.light.R/G/B,
                                         lighting.unoccluded.R/G/B (those that are there): colour, HALF
+      light_groups (planes, names)      lightgroup.<name>.R/G/B for every plane of render_light_groups' [P,H,W,3] and its name
+                                        (light_group_map's): colour, HALF
     -> dict name -> (view [H,W], "half" | "float" | "uint"). Colour is HALF; depth, position, variance, error and level FLOAT; ids and
     counts UINT. pixel_types: {channel or layer name: type} overrides that (a layer is a name without its last component). The views
     are of the arrays and tensors given, numpy or torch alike: nothing is copied."""
@@ -576,6 +620,11 @@ def exr_layers(rgb=None, aov=None, stats=None, highlights=None, robust=None, den
     for key in LIGHTING_CHANNELS:
         if lighting is not None and lighting.get(key) is not None:
             put("lighting." + key, "RGB", lighting[key])
+    if light_groups is not None:
+        planes, names = light_groups
+        assert len(planes) == len(names) and len(set(names)) == len(names), (len(planes), names)
+        for plane, name in zip(planes, names):
+            put("lightgroup." + name, "RGB", plane)
     return out
 
 
@@ -583,7 +632,7 @@ def exr_unlayer(channels):
     """The inverse of exr_layers: from a dict name -> frame [H,W] (Context.exr_load's, numpy arrays or torch tensors) the keyword dict
     exr_layers takes, for the names documented there - rgb [H,W,3]; aov with its [H,W,3] and [H,W] members; stats; highlights with tops
     [H,W,4,3] and level; robust; denoised {name: {"rgb", "variance", "error"}} for every other layer that has R, G and B but no A (R, G,
-    B, A are a matte's layer); occlusion with ao, sky and bent_normal [H,W,3]; lighting with its [H,W,3] channels; errors. A layer is taken when all its parts are there; every other name comes back under "other".
+    B, A are a matte's layer); occlusion with ao, sky and bent_normal [H,W,3]; lighting with its [H,W,3] channels; light_groups (planes [P,H,W,3], names) from the lightgroup.<name> layers; errors. A layer is taken when all its parts are there; every other name comes back under "other".
     Frames are stacked where they live."""
     left = dict(channels)
 
@@ -639,6 +688,10 @@ def exr_unlayer(channels):
             lighting[key] = frame
     if lighting:
         out["lighting"] = lighting
+    group_names = [n[len("lightgroup."):-2] for n in channels if n.startswith("lightgroup.") and n.endswith(".R")]
+    group_planes = [(name, take("lightgroup." + name, "RGB")) for name in group_names]
+    if any(frame is not None for _, frame in group_planes):
+        out["light_groups"] = (stack([frame for _, frame in group_planes if frame is not None], axis=0), [name for name, frame in group_planes if frame is not None])
     errors = {}
     for key, part in COMPARE_ERROR_CHANNELS.items():
         frame = take("error", (part,))
@@ -807,6 +860,11 @@ def lib():
     if hasattr(L, "mcrt_render_lighting"):  # (likewise)
         L.mcrt_render_lighting.argtypes = [vp, C.POINTER(CameraDesc), C.c_uint32, C.POINTER(LightingBuffers), C.POINTER(Stats)]
         L.mcrt_render_lighting_device.argtypes = L.mcrt_render_lighting.argtypes
+    if hasattr(L, "mcrt_render_light_groups"):  # (likewise)
+        L.mcrt_render_light_groups.argtypes = [vp, C.POINTER(CameraDesc), C.c_uint32, C.POINTER(LightGroupParams), vp, C.POINTER(Stats)]
+        L.mcrt_render_light_groups_device.argtypes = L.mcrt_render_light_groups.argtypes
+        L.mcrt_light_group_planes.argtypes = [C.POINTER(LightGroupParams)]
+        L.mcrt_light_group_planes.restype = C.c_uint32
     if hasattr(L, "mcrt_frame_compare"):  # (likewise)
         L.mcrt_frame_compare.argtypes = [vp, C.c_uint32, C.c_uint32, vp, vp, vp, C.POINTER(CompareParams), C.POINTER(CompareMaps), C.POINTER(CompareResult), C.POINTER(Stats)]
         L.mcrt_frame_compare_device.argtypes = L.mcrt_frame_compare.argtypes
@@ -1336,6 +1394,45 @@ class Context:
         bufs = _pointer_struct(LightingBuffers, pointers, LIGHTING_CHANNELS)
         st = Stats()
         self._check(self._lib.mcrt_render_lighting_device(self._h, C.byref(cam), int(global_seed), C.byref(bufs), C.byref(st)), "mcrt_render_lighting_device")
+        return st.as_dict()
+
+    @staticmethod
+    def _light_group_params(groups, sky_plane, max_depth, num_groups):
+        """-> (LightGroupParams, the array it points into). groups: [num_surfaces] group per surface, or None."""
+        keep = None if groups is None else np.ascontiguousarray(groups, dtype=np.uint32)
+        if num_groups is None:
+            num_groups = 1 if keep is None or keep.size == 0 else int(keep.max()) + 1
+        par = LightGroupParams(int(num_groups), 0 if sky_plane is None else LIGHT_GROUPS_SKY_PLANE, 0 if sky_plane is None else int(sky_plane), int(max_depth),
+                               None if keep is None else keep.ctypes.data)
+        return par, keep
+
+    def render_light_groups(self, cam, global_seed, groups=None, sky_plane=None, max_depth=0, stats=None, num_groups=None, out=None):
+        """mcrt_render_light_groups: the path-traced frame of cam and global_seed split by emitter, every bounce -> [P,H,W,3]: one plane
+        per group and the sky's, which add up to the frame (include/mcrt.h "Light groups"). groups: [num_surfaces] the group of every
+        surface (light_group_map builds it; entries of surfaces that emit nothing are ignored), None = every emitter in group 0.
+        num_groups: default max(groups) + 1. sky_plane: the plane that takes the sky, default a plane of its own after the groups.
+        max_depth: 0 = the whole path, 1 = direct light only. out: an array to write into instead of fresh zeros - the call only writes
+        the rows cam's shard owns. stats: a dict that receives mcrt_stats."""
+        self._sync_env()
+        par, keep = self._light_group_params(groups, sky_plane, max_depth, num_groups)
+        planes = int(self._lib.mcrt_light_group_planes(C.byref(par)))
+        shape = (max(planes, 1), cam.height, cam.width, 3)  # (out of range: the call below says what is)
+        a = out if out is not None else np.zeros(shape)
+        assert a.dtype == np.float64 and a.shape == shape and a.flags["C_CONTIGUOUS"]
+        st = Stats()
+        self._check(self._lib.mcrt_render_light_groups(self._h, C.byref(cam), int(global_seed), C.byref(par), a.ctypes.data, C.byref(st)), "mcrt_render_light_groups")
+        if stats is not None:
+            stats.update(st.as_dict())
+        return a
+
+    def render_light_groups_device(self, cam, global_seed, pointer, groups=None, sky_plane=None, max_depth=0, num_groups=None):
+        """mcrt_render_light_groups_device: pointer = raw device pointer to [P][owned rows][W][3] doubles (packed like render_device's
+        output). Synchronous; returns the stats dict."""
+        self._sync_env()
+        par, keep = self._light_group_params(groups, sky_plane, max_depth, num_groups)
+        st = Stats()
+        self._check(self._lib.mcrt_render_light_groups_device(self._h, C.byref(cam), int(global_seed), C.byref(par), int(pointer) if pointer else None, C.byref(st)),
+                    "mcrt_render_light_groups_device")
         return st.as_dict()
 
     def render_matte(self, cam, global_seed, key="material", ranks=MATTE_DEFAULT_RANKS, names=None, surface_key=None, aov=None, out=None, stats=None,

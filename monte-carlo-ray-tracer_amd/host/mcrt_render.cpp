@@ -9,6 +9,7 @@
 //               [--converge TARGET [--max-spp N]] [--exr OUT.exr [--exr-compression none|zip]]
 //               [--matte PREFIX [--matte-key material|surface] [--matte-ranks N]] [--compare REF [--compare-layer PREFIX]]
 //               [--occlusion PREFIX [--occlusion-rays N] [--occlusion-distance D]] [--lighting PREFIX]
+//               [--light-groups PREFIX [--light-groups-by material|light|one] [--light-groups-depth D]]
 //
 // Writes the frame as raw FP64 RGB, row-major (what Image::operator() holds, camera/image.cpp:53-56),
 // and prints the statistics. --tga also develops it the way Image::save does (auto exposure / gain, tone map, sRGB bytes:
@@ -60,6 +61,10 @@
 // --lighting also writes the lighting passes of the same camera and seed (mcrt_render_lighting, device 0; path tracer only): PREFIX.emission.f64,
 // .sky.f64, .direct.f64, .light.f64 and .unoccluded.f64 ([H][W][3], raw FP64). With --exr the file also holds them as the HALF channels
 // lighting.emission.R/G/B ... lighting.unoccluded.R/G/B.
+// --light-groups also writes the light groups of the same camera and seed (mcrt_render_light_groups, device 0; path tracer only): one plane
+// per group of emitters and one for the sky, PREFIX.<name>.f64 ([height][width][3] FP64) and, with --exr, lightgroup.<name>.R/G/B (HALF).
+// --light-groups-by material (default): a group per emissive material, named material<index>; light: a group per emitter surface,
+// light<index>; one: every emitter in one group, lights. --light-groups-depth D cuts the paths (1 = direct light only; default 0 = whole).
 // --devices renders the frame on several GPUs from this one process (mcrt_render_multi: one host thread per GPU).
 #include <cstdio>
 #include <cstdlib>
@@ -89,7 +94,8 @@ int main(int argc, char** argv) {
     image.plain = (uint32_t)mcrt_image_param(img, "image_plain");
     image.exposure_compensation = from_bits(mcrt_image_param(img, "image_exposure_ev_bits"));
     image.gain_compensation = from_bits(mcrt_image_param(img, "image_gain_ev_bits"));
-    std::string tga, aov, denoise, dvar, dvar_out, ddual, ddual_out, pstats, robust, exr, matte, compare, compare_layer, occlusion, lighting;
+    std::string tga, aov, denoise, dvar, dvar_out, ddual, ddual_out, pstats, robust, exr, matte, compare, compare_layer, occlusion, lighting, light_groups, light_groups_by = "material";
+    uint32_t light_groups_depth = 0;
     mcrt_occlusion_params oparams{};
     bool compare_exr = false;
     mcrt_matte_params mparams{};
@@ -144,6 +150,9 @@ int main(int argc, char** argv) {
         else if (k == "--compare" && i + 1 < argc) compare = argv[++i];
         else if (k == "--occlusion" && i + 1 < argc) occlusion = argv[++i];
         else if (k == "--lighting" && i + 1 < argc) lighting = argv[++i];
+        else if (k == "--light-groups" && i + 1 < argc) light_groups = argv[++i];
+        else if (k == "--light-groups-by" && i + 1 < argc) light_groups_by = argv[++i];
+        else if (k == "--light-groups-depth" && i + 1 < argc) light_groups_depth = (uint32_t)std::strtoul(argv[++i], nullptr, 10);
         else if (k == "--occlusion-rays") oparams.rays = (uint32_t)val();
         else if (k == "--occlusion-distance" && i + 1 < argc) oparams.max_distance = std::strtod(argv[++i], nullptr);
         else if (k == "--compare-layer" && i + 1 < argc) compare_layer = argv[++i];
@@ -670,6 +679,80 @@ int main(int argc, char** argv) {
                     lighting.c_str(), mean[0], mean[1], mean[2], mean[3], mean[4], (unsigned long long)lst.rays, lst.kernel_ms, lst.total_ms, lst.rays / lst.kernel_ms / 1e3);
         if (!exr.empty())
             for (int c = 0; c < 5; c++) exr_layer(std::string("lighting.") + names[c], "RGB", exr_keep(frames[c]), MCRT_EXR_HALF);
+    }
+    if (!light_groups.empty()) {
+        if (photon) {
+            std::fprintf(stderr, "--light-groups: the light groups are the path tracer's (not with --photon)\n");
+            return 1;
+        }
+        // the groups of light_group_map (the Python binding): emitters are the surfaces whose material carries MCRT_MAT_EMISSIVE
+        const mcrt_scene_desc* sd = mcrt_image_scene(img);
+        std::vector<uint32_t> group(sd->num_surfaces, 0u);
+        std::vector<std::string> names;
+        if (light_groups_by == "material") {
+            std::vector<int> group_of(sd->num_materials, -1);
+            for (uint32_t m = 0; m < sd->num_materials; m++) {
+                if (!(sd->materials[m].flags & MCRT_MAT_EMISSIVE)) continue;
+                bool used = false;
+                for (uint32_t i = 0; i < sd->num_surfaces && !used; i++) used = sd->surf_material[i] == m;
+                if (!used) continue;
+                group_of[m] = (int)names.size();
+                names.push_back("material" + std::to_string(m));
+            }
+            for (uint32_t i = 0; i < sd->num_surfaces; i++)
+                if (group_of[sd->surf_material[i]] >= 0) group[i] = (uint32_t)group_of[sd->surf_material[i]];
+        } else if (light_groups_by == "light") {
+            for (uint32_t i = 0; i < sd->num_surfaces; i++)
+                if (sd->materials[sd->surf_material[i]].flags & MCRT_MAT_EMISSIVE) {
+                    group[i] = (uint32_t)names.size();
+                    names.push_back("light" + std::to_string(i));
+                }
+        } else if (light_groups_by != "one") {
+            std::fprintf(stderr, "--light-groups-by: material, light or one, not %s\n", light_groups_by.c_str());
+            return 1;
+        }
+        if (names.empty()) names.push_back("lights");
+        if (names.size() > MCRT_LIGHT_GROUPS_MAX) {
+            std::fprintf(stderr, "--light-groups-by %s: %zu groups, at most %u can be rendered\n", light_groups_by.c_str(), names.size(), MCRT_LIGHT_GROUPS_MAX);
+            return 1;
+        }
+        mcrt_light_group_params gp{};
+        gp.num_groups = (uint32_t)names.size();
+        gp.max_depth = light_groups_depth;
+        gp.surface_group = group.data();
+        names.push_back("sky");
+        const size_t px = (size_t)cam.width * cam.height;
+        std::vector<double> planes(names.size() * px * 3);
+        mcrt_stats gst;
+        rc = mcrt_render_light_groups(ctx, &cam, seed, &gp, planes.data(), &gst);
+        if (rc != MCRT_OK) {
+            std::fprintf(stderr, "mcrt error %d: %s\n", rc, mcrt_last_error(ctx));
+            return 1;
+        }
+        std::string means;
+        for (size_t p = 0; p < names.size(); p++) {
+            const double* plane = planes.data() + p * px * 3;
+            const std::string path = light_groups + "." + names[p] + ".f64";
+            FILE* o = std::fopen(path.c_str(), "wb");
+            const bool ok = o && std::fwrite(plane, 1, px * 24, o) == px * 24;
+            if (o) std::fclose(o);
+            if (!ok) {
+                std::fprintf(stderr, "cannot write %s\n", path.c_str());
+                return 1;
+            }
+            double mean = 0.0;
+            for (size_t w = 0; w < px * 3; w++) mean += plane[w];
+            char text[96];
+            std::snprintf(text, sizeof text, "%s\"%s\":%.6g", p ? "," : "", names[p].c_str(), px ? mean / (double)(px * 3) : 0.0);
+            means += text;
+            if (!exr.empty()) {
+                std::vector<double> copy(plane, plane + px * 3);
+                exr_layer("lightgroup." + names[p], "RGB", exr_keep(copy), MCRT_EXR_HALF);
+            }
+        }
+        std::printf("{\"light_groups\":\"%s\",\"by\":\"%s\",\"max_depth\":%u,\"means\":{%s},\"rays\":%llu,\"kernel_ms\":%.3f,\"total_ms\":%.3f,\"Mray_s\":%.1f}\n",
+                    light_groups.c_str(), light_groups_by.c_str(), light_groups_depth, means.c_str(), (unsigned long long)gst.rays, gst.kernel_ms, gst.total_ms,
+                    gst.rays / gst.kernel_ms / 1e3);
     }
     if (!exr.empty()) {
         const std::string a_spp = std::to_string(spp), a_seed = std::to_string(seed), a_kernel = std::to_string(st.kernel_id);

@@ -1,0 +1,144 @@
+// tests/emu/light_groups_emu.cpp — TEST HARNESS ONLY (built by tests/test_light_groups_emulation.py into tests/emu/_build/).
+//
+// The light groups on the host: csrc/mcrt_light_groups.hpp (and csrc/mcrt_aov.hpp, csrc/mcrt_shade.hpp below it) unchanged - the text the
+// kernels of csrc/mcrt_light_groups.hip run - driven chunk by chunk and iteration by iteration the way mcrt_render_light_groups_device
+// drives them, live lists included, with the closest hits from the emulation's sceneIntersect (mcrt_emu.cpp's emu_intersect). Not a CPU
+// fallback: nothing in the product links or loads it.
+#include "mcrt_emu.cpp"
+
+#include "../../monte-carlo-ray-tracer_amd/csrc/mcrt_light_groups.hpp"
+
+namespace {
+
+uint32_t ownedRows(const mcrt_camera_desc* cam) {
+    uint32_t rows = 0;
+    for (uint32_t ly = 0; localToGlobalRow(*cam, ly) < cam->height; ly++) rows++;
+    return rows;
+}
+
+}  // namespace
+
+extern "C" {
+
+// Owned rows of the camera's shard (what mcrt_shard_rows counts).
+uint32_t light_groups_emu_rows(const mcrt_camera_desc* cam) { return ownedRows(cam); }
+
+// The surface every camera sample meets first (0xFFFFFFFF: none), [owned pixels][spp].
+int light_groups_emu_first_hits(const mcrt_scene_desc* scene, const mcrt_camera_desc* cam, uint32_t global_seed, int stage_lds, uint32_t* surface) {
+    Emu E;
+    if (int rc = setup(E, scene, 0)) return rc;
+    AovChunk c;
+    c.cam = *cam;
+    c.global_seed = global_seed;
+    c.spp = cam->sqrtspp * cam->sqrtspp;
+    c.first_pixel = 0;
+    c.pixels = ownedRows(cam) * cam->width;
+    const uint64_t n = (uint64_t)c.pixels * c.spp;
+    std::vector<double> start(3 * n), direction(3 * n), t(n), uv(2 * n);
+    for (uint64_t r = 0; r < n; r++) {
+        const Ray ray = aovCameraRay<true>(c, E.sh_top.scene_ior, (uint32_t)(r / c.spp), (uint32_t)(r % c.spp), E.tab.data());
+        aovStore3(start.data(), r, ray.start);
+        aovStore3(direction.data(), r, ray.direction);
+    }
+    return emu_intersect(scene, n, start.data(), direction.data(), stage_lds, t.data(), surface, uv.data());
+}
+
+// The planes into `out` (host array [planes][owned pixels][3]), in chunks of chunk_rays shadow and bounce slots of iteration 0 (0 = one
+// chunk). stage_lds: emu_intersect's flavour of the walk. list_order: what happens to a live list between the step that appended it
+// and the iteration that reads it - 0 nothing, 1 reversed, 2 shuffled (a fixed generator). info: [0] rays handed to the search,
+// [1] the most iterations a chunk took, [2] live samples summed over all iterations. Returns mcrt_status values for what the call refuses.
+int light_groups_emu_frame(const mcrt_scene_desc* scene, const mcrt_camera_desc* cam, uint32_t global_seed, int stage_lds, uint64_t chunk_rays,
+                           const mcrt_light_group_params* params, int list_order, double* out, uint64_t* info) {
+    Emu E;
+    if (int rc = setup(E, scene, 0)) return rc;
+    AovScene as;
+    as.sh = E.sh_top;
+    as.prim = E.L.prim.data();
+    const uint32_t groups = params && params->num_groups ? params->num_groups : 1u;
+    if (groups > MCRT_LIGHT_GROUPS_MAX) return MCRT_ERR_INVALID;
+    LgParams par;
+    par.sky_plane = params && (params->flags & MCRT_LIGHT_GROUPS_SKY_PLANE) ? params->sky_plane : groups;
+    if (par.sky_plane > groups) return MCRT_ERR_INVALID;
+    par.planes = std::max(groups, par.sky_plane + 1u);
+    par.max_depth = params ? params->max_depth : 0u;
+    std::vector<uint8_t> plane(scene->num_surfaces, 0);
+    for (uint32_t i = 0; i < scene->num_surfaces; i++) {
+        if (!(scene->materials[scene->surf_material[i]].flags & MCRT_MAT_EMISSIVE)) continue;
+        const uint32_t g = params && params->surface_group ? params->surface_group[i] : 0u;
+        if (g >= groups) return MCRT_ERR_INVALID;
+        plane[i] = (uint8_t)g;
+    }
+    par.plane = plane.data();
+
+    const uint32_t spp = cam->sqrtspp * cam->sqrtspp;
+    const uint64_t per_pixel = (uint64_t)spp * 2;
+    const uint64_t total = (uint64_t)ownedRows(cam) * cam->width;
+    const uint64_t chunk_pixels = std::min<uint64_t>(std::max<uint64_t>((chunk_rays ? chunk_rays : total * per_pixel) / per_pixel, 1), std::max<uint64_t>(total, 1));
+    const uint64_t max_n = chunk_pixels * spp;
+    std::vector<double> state((max_n * kLgStateBytes + 7) / 8), radiance(max_n * 3 * par.planes);
+    LgState st;
+    lgPlaceState(st, state.data(), max_n);
+    st.radiance = radiance.data();
+    std::vector<double> l_start(2 * max_n * 3), l_dir(2 * max_n * 3), l_t(2 * max_n), l_uv(2 * max_n * 2);
+    std::vector<uint32_t> l_surf(2 * max_n), list[2];
+    const AovRays lit{l_start.data(), l_dir.data(), l_t.data(), l_surf.data(), l_uv.data()};
+    double iors[kMaxIors];
+    RefractionHistory rh;
+    rh.iors = iors;
+    rh.stride = 1;
+    rh.size = 0;
+    uint64_t lcg = 0x9E3779B97F4A7C15ull;
+    if (info) info[0] = info[1] = info[2] = 0;
+    for (uint64_t first = 0; first < total; first += chunk_pixels) {
+        AovChunk c;
+        c.cam = *cam;
+        c.global_seed = global_seed;
+        c.spp = spp;
+        c.first_pixel = first;
+        c.pixels = (uint32_t)std::min<uint64_t>(chunk_pixels, total - first);
+        const uint64_t n = (uint64_t)c.pixels * spp;
+        for (uint64_t r = 0; r < n; r++) {  // aovRayKernel
+            const Ray ray = aovCameraRay<true>(c, as.sh.scene_ior, (uint32_t)(r % c.pixels), (uint32_t)(r / c.pixels), E.tab.data());
+            aovStore3(st.ray.start, r, ray.start);
+            aovStore3(st.ray.direction, r, ray.direction);
+        }
+        if (int rc = emu_intersect(scene, n, st.ray.start, st.ray.direction, stage_lds, st.ray.t, st.ray.surface, st.ray.uv)) return rc;
+        list[0].clear();
+        list[1].clear();
+        for (uint64_t s = 0; s < n; s++)  // lightGroupsBeginKernel
+            if (lgBegin(st, s, as.sh.scene_ior, par)) list[0].push_back((uint32_t)s);
+        if (info) info[0] += n;
+        uint32_t k = 0;
+        for (; !list[k & 1u].empty(); k++) {
+            if (k >= kLgMaxIterations) return MCRT_ERR_UNSUPPORTED;
+            std::vector<uint32_t>& cur = list[k & 1u];
+            std::vector<uint32_t>& next = list[(k & 1u) ^ 1u];
+            if (list_order == 1) std::reverse(cur.begin(), cur.end());
+            if (list_order == 2)
+                for (size_t a = cur.size(); a > 1; a--) {
+                    lcg = lcg * 6364136223846793005ull + 1442695040888963407ull;
+                    std::swap(cur[a - 1], cur[(size_t)((lcg >> 33) % a)]);
+                }
+            const uint32_t live = (uint32_t)cur.size();
+            const bool last = par.max_depth != 0u && k == par.max_depth;
+            if (info) info[2] += live;
+            if (!last) {
+                for (uint32_t j = 0; j < live; j++) lgRays(c, as, st, cur.data(), live, j, k, lit, rh, E.tab.data());  // lightGroupsRayKernel
+                if (int rc = emu_intersect(scene, 2ull * live, lit.start, lit.direction, stage_lds, lit.t, lit.surface, lit.uv)) return rc;
+                if (info) info[0] += 2ull * live;
+            }
+            next.clear();
+            for (uint32_t j = 0; j < live; j++) {  // lightGroupsStepKernel
+                bool too_deep = false;
+                if (lgStep(c, as, st, par, cur.data(), live, j, k, last, lit, rh, too_deep, E.tab.data())) next.push_back(cur[j]);
+                if (too_deep) return MCRT_ERR_UNSUPPORTED;
+            }
+            cur.clear();
+        }
+        if (info) info[1] = std::max<uint64_t>(info[1], k);
+        for (uint32_t p = 0; p < c.pixels; p++) lgResolvePixel(c, st, par.planes, p, out, total);  // lightGroupsResolveKernel
+    }
+    return 0;
+}
+
+}  // extern "C"
