@@ -927,6 +927,20 @@ def _pointer_struct(cls, pointers, allowed):
     return s
 
 
+def _channel_arrays(cls, names, table, cam, out):
+    """The host arrays of the channels `names` of `table` (name -> (dtype, elements per pixel)) for cam's frame, from the dict `out` where
+    it holds them, otherwise fresh zeros -> (dict channel -> array, the ctypes struct cls pointing into them)."""
+    res, bufs = {}, cls()
+    for name in names:
+        dtype, k = table[name]
+        shape = (cam.height, cam.width) + ((k,) if k > 1 else ())
+        a = out[name] if out is not None and name in out else np.zeros(shape, dtype=dtype)
+        assert a.dtype == dtype and a.shape == shape and a.flags["C_CONTIGUOUS"], name
+        res[name] = a
+        setattr(bufs, name, a.ctypes.data)
+    return res, bufs
+
+
 def _guide_buffers(aov, height, width):
     """The filters' guide channels of render_aov's dict as (AovBuffers of host pointers, the contiguous arrays they point into, to keep
     alive over the call). A channel left out or None stays NULL: the library names a channel it misses."""
@@ -1308,14 +1322,7 @@ class Context:
         others keep their contents. stats: a dict that receives mcrt_stats."""
         self._sync_env()
         names = list(AOV_CHANNELS) if channels is None else list(channels)
-        res, bufs = {}, AovBuffers()
-        for name in names:
-            dtype, k = AOV_CHANNELS[name]
-            shape = (cam.height, cam.width) + ((k,) if k > 1 else ())
-            a = out[name] if out is not None and name in out else np.zeros(shape, dtype=dtype)
-            assert a.dtype == dtype and a.shape == shape and a.flags["C_CONTIGUOUS"], name
-            res[name] = a
-            setattr(bufs, name, a.ctypes.data)
+        res, bufs = _channel_arrays(AovBuffers, names, AOV_CHANNELS, cam, out)
         st = Stats()
         self._check(self._lib.mcrt_render_aov(self._h, C.byref(cam), int(global_seed), C.byref(bufs), C.byref(st)), "mcrt_render_aov")
         if stats is not None:
@@ -1339,14 +1346,7 @@ class Context:
         receives mcrt_stats."""
         self._sync_env()
         names = list(OCCLUSION_CHANNELS) if channels is None else list(channels)
-        res, bufs = {}, OcclusionBuffers()
-        for name in names:
-            dtype, k = OCCLUSION_CHANNELS[name]
-            shape = (cam.height, cam.width) + ((k,) if k > 1 else ())
-            a = out[name] if out is not None and name in out else np.zeros(shape, dtype=dtype)
-            assert a.dtype == dtype and a.shape == shape and a.flags["C_CONTIGUOUS"], name
-            res[name] = a
-            setattr(bufs, name, a.ctypes.data)
+        res, bufs = _channel_arrays(OcclusionBuffers, names, OCCLUSION_CHANNELS, cam, out)
         par = OcclusionParams(int(rays), OCCLUSION_GEOMETRIC if geometric else 0, float(max_distance))
         st = Stats()
         self._check(self._lib.mcrt_render_occlusion(self._h, C.byref(cam), int(global_seed), C.byref(par), C.byref(bufs), C.byref(st)), "mcrt_render_occlusion")
@@ -1373,14 +1373,7 @@ class Context:
         mcrt_stats."""
         self._sync_env()
         names = list(LIGHTING_CHANNELS) if channels is None else list(channels)
-        res, bufs = {}, LightingBuffers()
-        for name in names:
-            dtype, k = LIGHTING_CHANNELS[name]
-            shape = (cam.height, cam.width, k)
-            a = out[name] if out is not None and name in out else np.zeros(shape, dtype=dtype)
-            assert a.dtype == dtype and a.shape == shape and a.flags["C_CONTIGUOUS"], name
-            res[name] = a
-            setattr(bufs, name, a.ctypes.data)
+        res, bufs = _channel_arrays(LightingBuffers, names, LIGHTING_CHANNELS, cam, out)
         st = Stats()
         self._check(self._lib.mcrt_render_lighting(self._h, C.byref(cam), int(global_seed), C.byref(bufs), C.byref(st)), "mcrt_render_lighting")
         if stats is not None:
@@ -1456,14 +1449,8 @@ class Context:
             assert a.dtype == dtype and a.shape == shape and a.flags["C_CONTIGUOUS"], name
             res[name] = a
             setattr(bufs, name, a.ctypes.data)
-        aov_res, aov_bufs = {}, AovBuffers()
-        for name in (list(AOV_CHANNELS) if aov is True else list(aov or ())):
-            dtype, k = AOV_CHANNELS[name]
-            shape = (cam.height, cam.width) + ((k,) if k > 1 else ())
-            a = out["aov"][name] if out is not None and name in out.get("aov", {}) else np.zeros(shape, dtype=dtype)
-            assert a.dtype == dtype and a.shape == shape and a.flags["C_CONTIGUOUS"], name
-            aov_res[name] = a
-            setattr(aov_bufs, name, a.ctypes.data)
+        aov_res, aov_bufs = _channel_arrays(AovBuffers, list(AOV_CHANNELS) if aov is True else list(aov or ()), AOV_CHANNELS, cam,
+                                            None if out is None else out.get("aov"))
         st = Stats()
         self._check(self._lib.mcrt_render_matte(self._h, C.byref(cam), int(global_seed), C.byref(par), C.byref(bufs), C.byref(aov_bufs) if aov_res else None,
                                                 C.byref(st)), "mcrt_render_matte")

@@ -25,8 +25,8 @@ int launchPowKat(void* stream, uint64_t n, const double* a, const double* b, dou
 // mcrt_hip.hip: Scene::intersect on n rays in DEVICE arrays - the body of mcrt_intersect behind its uploads (trees in memory: the trace
 // kernel fed from the arrays, otherwise the intersect kernel). d_uv must not be null. Synchronous on the context's stream.
 int intersectDeviceArrays(mcrt_ctx* ctx, uint64_t n, const double* d_start, const double* d_dir, double* d_t, uint32_t* d_surf, double* d_uv);
-// The hooks of the image passes' host toolkit (mcrt_pass_host.hpp; DESIGN.md "Image passes"), which mcrt_aov_host.hip, mcrt_denoise_host.hip,
-// mcrt_pixel_stats_host.hip and mcrt_robust_host.hip reach the context through (mcrt_denoise_var_host.hip, mcrt_accumulate_host.hip and mcrt_denoise_dual_host.hip too).
+// The hooks of the image passes' host toolkit (mcrt_pass_host.hpp, mcrt_camera_pass.hpp; DESIGN.md "Image passes"), which every
+// mcrt_*_host.hip reaches the context through - one PassFamily below each, but the OpenEXR output and input, which share kPassExr.
 // ctxIdle: no render in flight (MCRT_ERR_INVALID recorded under `what`), device selected. ctxNeedScene: MCRT_ERR_NO_SCENE under `what`.
 // ctxPassScratch: buffer `which` (0..kPassSlots-1) of a family's scratch - every (family, slot) a buffer of its own, kept in the context
 // and grown on demand like the operators'; at least 8 bytes; nullptr, the HIP error cleared, when the allocation fails.

@@ -1,50 +1,32 @@
-// Light groups (include/mcrt.h mcrt_render_light_groups*), host side: validation, the group map, the chunk and bounce loops, statistics
-// and the host-pointer form. No kernel here: they are libmcrt_light_groups.so (csrc/mcrt_light_groups.hip; DESIGN.md "Image passes" says
-// why, and what mcrt_pass_host.hpp shares). Per chunk: launchAovRays and intersectDeviceArrays write the camera rays and their hits
-// straight into the samples' state, launchLightGroupsBegin starts the paths, then per iteration launchLightGroupsRays ->
-// intersectDeviceArrays over 2 rays per LIVE sample -> launchLightGroupsStep, the host reading the next list's count (and the pass's
-// error word) after every step; launchLightGroupsResolve when no sample is alive. The family's scratch: slot 0 the samples' state, 1 the
-// planes' radiances, 2 the shadow and bounce records, 3 the two live lists and the counters, 4 the surfaces' planes, 5 the host-pointer
-// form's frames. Option MCRT_AOV_CHUNK_RAYS bounds the shadow and bounce SLOTS of iteration 0: pixels * spp * 2, whole pixels, one pixel
-// at least. Its default is sized like the lighting passes' - what 2^17 pixels take (the resolve is one lane per pixel
-// there and here), between 2^25 and 2^26 slots - and cut down to what 8 GiB of state, radiances and records hold: a sample takes 216 bytes
-// of state, 24 per plane and 152 of records where the lighting passes take 228 in all. Large chunks matter more here than there: every
-// chunk runs its own tail of iterations with a handful of live samples, each about 0.08 ms of launches and waits whatever it shades
-// (profiles/NOTES_light_groups.md: hexagon_room at 16 samples a pixel takes 98 ms in one chunk, 118 in four, 175 in sixteen).
+// Light groups (include/mcrt.h mcrt_render_light_groups*), host side: the group map, the samples' state, and behind the camera-ray
+// passes' chunk loop (mcrt_camera_pass.hpp), which writes the camera rays and their hits straight into that state, the bounce loop:
+// launchLightGroupsBegin starts the paths, then per iteration launchLightGroupsRays -> intersectDeviceArrays over 2 rays per LIVE sample
+// -> launchLightGroupsStep, the host reading the next list's count (and the pass's error word) after every step;
+// launchLightGroupsResolve when no sample is alive. No kernel here: they are libmcrt_light_groups.so (csrc/mcrt_light_groups.hip;
+// DESIGN.md "Image passes" says why). The family's scratch: slot 0 the samples' state, 1 the planes' radiances, 2 the shadow and bounce
+// records, 3 the two live lists and the counters, 4 the surfaces' planes, 5 the host-pointer form's frames. Option MCRT_AOV_CHUNK_RAYS
+// bounds the shadow and bounce SLOTS of iteration 0: pixels * spp * 2 (its default: lightGroupsDefaultChunkSlots).
 // Option MCRT_LIGHT_GROUPS_LOG (tools/light_groups_probe.py sets it): one JSON line per chunk on stderr - the live samples of every
-// iteration and the host-clock milliseconds of the chunk and of its searches, the stream drained before each search so that the kernels
-// queued before it are not counted as search. It changes no result.
-#include <algorithm>
+// iteration and the host-clock milliseconds of the chunk and of its searches, the stream drained before each bounce search so that the
+// kernels queued before it are not counted as search (the camera rays' kernel is counted with their search). It changes no result.
 #include <chrono>
 #include <cstdio>
 #include <vector>
 
-#include "mcrt_aov.hpp"
-#include "mcrt_aov_launch.hpp"
+#include "mcrt_camera_pass.hpp"
 #include "mcrt_light_groups.hpp"
 #include "mcrt_light_groups_launch.hpp"
-#include "mcrt_pass_host.hpp"
 
 using namespace mcrt;
 
 namespace {
 
-constexpr uint64_t kLgDefaultChunkRays = 1ull << 25;
-constexpr uint64_t kLgDefaultChunkRaysMost = 1ull << 26;
-constexpr uint64_t kLgDefaultChunkPixels = 1ull << 17;
-constexpr uint64_t kLgDefaultChunkBytes = 8ull << 30;
-constexpr uint64_t kLgMaxChunkRays = 0xFFF00000ull;  // mcrt_intersect's queue limit (32-bit cursors)
-constexpr uint64_t kLgRecordBytes = 76;              // start, direction, t, surface, uv of one ray
+constexpr uint64_t kLgRecordBytes = 76;  // start, direction, t, surface, uv of one ray
 
 struct Resolved {
     uint32_t groups, sky_plane, planes, max_depth;
     const uint32_t* surface_group;
 };
-
-int ready(mcrt_ctx* ctx, const char* what) {  // (the scene first: a context without one says so, whatever else is wrong)
-    if (int rc = ctxNeedScene(ctx, what)) return rc;
-    return ctxIdle(ctx, what);
-}
 
 // 0 when the numbers are out of range
 uint32_t resolveParams(const mcrt_light_group_params* p, Resolved& r) {
@@ -59,11 +41,8 @@ uint32_t resolveParams(const mcrt_light_group_params* p, Resolved& r) {
 }
 
 int validate(mcrt_ctx* ctx, const mcrt_camera_desc* cam, const mcrt_light_group_params* params, const void* planes, Resolved& r, const char* what) {
-    if (!cam) return ctxFail(ctx, MCRT_ERR_INVALID, std::string(what) + ": cam is NULL");
-    if (cam->width == 0 || cam->height == 0 || cam->sqrtspp == 0)
-        return ctxFail(ctx, MCRT_ERR_INVALID, "camera: width, height and sqrtspp must be non-zero");
-    if (cam->shard_count > 1 && cam->shard_index >= cam->shard_count) return ctxFail(ctx, MCRT_ERR_INVALID, "camera: shard_index >= shard_count");
-    if ((uint64_t)cam->width * cam->height > 0xFFFFFFFFull) return ctxFail(ctx, MCRT_ERR_INVALID, "camera: more than 2^32 pixels");
+    if (int rc = cameraPassReady(ctx, what)) return rc;
+    if (int rc = checkCamera(ctx, cam, true, what, "cam is NULL")) return rc;
     if (!planes) return ctxFail(ctx, MCRT_ERR_INVALID, std::string(what) + ": planes is NULL");
     if (params && params->num_groups > MCRT_LIGHT_GROUPS_MAX)
         return ctxFail(ctx, MCRT_ERR_INVALID, std::string(what) + ": num_groups " + std::to_string(params->num_groups) + " is more than MCRT_LIGHT_GROUPS_MAX (" +
@@ -71,9 +50,7 @@ int validate(mcrt_ctx* ctx, const mcrt_camera_desc* cam, const mcrt_light_group_
     if (!resolveParams(params, r))
         return ctxFail(ctx, MCRT_ERR_INVALID, std::string(what) + ": sky_plane " + std::to_string(params->sky_plane) + " is more than num_groups (" +
                                                   std::to_string(r.groups) + "): the sky takes a group's plane or the one after them");
-    if ((uint64_t)cam->sqrtspp * cam->sqrtspp * 2 > kLgMaxChunkRays)
-        return ctxFail(ctx, MCRT_ERR_UNSUPPORTED, std::string(what) + ": more rays per pixel than one closest-hit launch takes");
-    return MCRT_OK;
+    return checkPixelSlots(ctx, cam, 2, "rays", what);
 }
 
 // The plane of every surface of the uploaded scene into scratch slot 4: an emitter's (a surface whose material carries MCRT_MAT_EMISSIVE)
@@ -112,30 +89,22 @@ extern "C" int mcrt_render_light_groups_device(mcrt_ctx* ctx, const mcrt_camera_
                                                double* d_planes, mcrt_stats* stats) {
     const char* what = "mcrt_render_light_groups_device";
     if (!ctx) return MCRT_ERR_INVALID;
-    if (int rc = ready(ctx, what)) return rc;
     Resolved r;
     if (int rc = validate(ctx, cam, params, d_planes, r, what)) return rc;
     PassTimer timer(ctx);
-    hipStream_t stream = (hipStream_t)ctxStream(ctx);
-    AovScene scene;
-    const uint32_t* sobol_tab = nullptr;
-    ctxAovScene(ctx, &scene, &sobol_tab);
+    const CameraPass cp(ctx);
+    const hipStream_t stream = cp.stream;
+    const AovScene& scene = cp.scene;
+    const uint32_t* sobol_tab = cp.sobol_tab;
     LgParams par;
     par.planes = r.planes;
     par.sky_plane = r.sky_plane;
     par.max_depth = r.max_depth;
     if (int rc = uploadPlanes(ctx, scene, r, what, &par.plane)) return rc;
 
-    const uint32_t spp = cam->sqrtspp * cam->sqrtspp;
-    const uint64_t per_pixel = (uint64_t)spp * 2;
-    const uint64_t total_pixels = (uint64_t)mcrt_shard_rows(cam, nullptr) * cam->width;
-    // a chunk is a whole number of pixels, at least one, and never more slots than one closest-hit launch takes
     const uint64_t sample_bytes = kLgStateBytes + 24ull * r.planes + 2 * kLgRecordBytes + 8;
-    const uint64_t dflt = std::min(std::min(std::max(kLgDefaultChunkPixels * per_pixel, kLgDefaultChunkRays), kLgDefaultChunkRaysMost), kLgDefaultChunkBytes / sample_bytes * 2);
-    const long want = ctxOptL(ctx, "MCRT_AOV_CHUNK_RAYS", (long)dflt);
-    const uint64_t chunk_rays = std::min<uint64_t>(want > 0 ? (uint64_t)want : dflt, kLgMaxChunkRays);
-    const uint64_t chunk_pixels = std::min<uint64_t>(std::max<uint64_t>(chunk_rays / per_pixel, 1), std::max<uint64_t>(total_pixels, 1));
-    const uint64_t max_n = chunk_pixels * spp;
+    const PixelChunks plan = pixelChunksOf(ctx, cam, 2, lightGroupsDefaultChunkSlots((uint64_t)cam->sqrtspp * cam->sqrtspp * 2, sample_bytes));
+    const uint64_t max_n = plan.max_rays, total_pixels = plan.total_pixels;
 
     LgState st;
     void* state = ctxPassScratch(ctx, kPassLightGroups, 0, max_n * kLgStateBytes);
@@ -166,29 +135,17 @@ extern "C" int mcrt_render_light_groups_device(mcrt_ctx* ctx, const mcrt_camera_
         ms += clock_ms() - t0;
         return rc;
     };
-    if (int rc = timer.begin(stream)) return rc;
-    uint32_t launches = 0;
-    uint64_t rays = 0;
-    for (uint64_t first = 0; first < total_pixels; first += chunk_pixels) {
-        AovChunk c;
-        c.cam = *cam;
-        c.global_seed = global_seed;
-        c.spp = spp;
-        c.first_pixel = first;
-        c.pixels = (uint32_t)std::min<uint64_t>(chunk_pixels, total_pixels - first);
-        const uint64_t n = (uint64_t)c.pixels * spp;
-        const double chunk_t0 = log ? clock_ms() : 0.0;
-        double search_ms = 0.0;
+    double chunk_t0 = log ? clock_ms() : 0.0;  // (a chunk's clock starts where the one before it ended: the stream is drained there)
+    return runChunks(ctx, cp, timer, cam, global_seed, plan, st.ray, stats, [&](const AovChunk& c, uint32_t& launches, uint64_t& rays) {
+        const uint64_t n = (uint64_t)c.pixels * c.spp;
+        double search_ms = log ? clock_ms() - chunk_t0 : 0.0;  // the camera rays and their search
         std::string curve;
-        MCRT_HIP_TRY(ctx, (hipError_t)launchAovRays(stream, c, scene.sh.scene_ior, sobol_tab, st.ray));
-        if (int rc = search(n, st.ray, search_ms)) return rc;
         MCRT_HIP_TRY(ctx, hipMemsetAsync(counters, 0, sizeof(LgCounters), stream));
         MCRT_HIP_TRY(ctx, (hipError_t)launchLightGroupsBegin(stream, st, n, scene.sh.scene_ior, par, list[0], counters));
         LgCounters now;
         MCRT_HIP_TRY(ctx, hipMemcpyAsync(&now, counters, sizeof(now), hipMemcpyDeviceToHost, stream));
         MCRT_HIP_TRY(ctx, hipStreamSynchronize(stream));
-        launches += 3;
-        rays += n;
+        launches++;
         uint32_t live = now.live[0];
         for (uint32_t k = 0; live != 0u; k++) {
             if (k >= kLgMaxIterations)
@@ -218,36 +175,24 @@ extern "C" int mcrt_render_light_groups_device(mcrt_ctx* ctx, const mcrt_camera_
         launches++;
         if (log) {
             (void)hipStreamSynchronize(stream);
-            std::fprintf(stderr, "{\"light_groups_chunk\":%llu,\"samples\":%llu,\"live\":[%s],\"chunk_ms\":%.3f,\"search_ms\":%.3f}\n", (unsigned long long)first,
-                         (unsigned long long)n, curve.c_str(), clock_ms() - chunk_t0, search_ms);
+            const double now_ms = clock_ms();
+            std::fprintf(stderr, "{\"light_groups_chunk\":%llu,\"samples\":%llu,\"live\":[%s],\"chunk_ms\":%.3f,\"search_ms\":%.3f}\n",
+                         (unsigned long long)c.first_pixel, (unsigned long long)n, curve.c_str(), now_ms - chunk_t0, search_ms);
+            chunk_t0 = now_ms;
         }
-    }
-    if (int rc = timer.end(stream)) return rc;
-    if (int rc = timer.finish(stats, launches)) return rc;
-    if (stats) {
-        stats->paths = total_pixels * spp;
-        stats->rays = rays;
-    }
-    return MCRT_OK;
+        return (int)MCRT_OK;
+    });
 }
 
 extern "C" int mcrt_render_light_groups(mcrt_ctx* ctx, const mcrt_camera_desc* cam, uint32_t global_seed, const mcrt_light_group_params* params, double* planes,
                                         mcrt_stats* stats) {
     const char* what = "mcrt_render_light_groups";
     if (!ctx) return MCRT_ERR_INVALID;
-    if (int rc = ready(ctx, what)) return rc;
     Resolved r;
     if (int rc = validate(ctx, cam, params, planes, r, what)) return rc;
-    PassTimer whole(ctx);
-    FrameChannel ch[kLgPlanesMax];  // the planes as one device allocation, one behind the other
+    FrameChannel ch[kLgPlanesMax];  // the planes, one behind the other
     const size_t frame = (size_t)cam->width * cam->height * 3;
     for (uint32_t p = 0; p < r.planes; p++) ch[p] = FrameChannel{nullptr, planes + p * frame, 24};
-    ShardFrames frames{{ctx, what, kPassLightGroups, 5, kPackedWanted, ch, (int)r.planes}};
-    if (int rc = frames.place(cam, "planes'")) return rc;
-    mcrt_stats st;
-    if (int rc = mcrt_render_light_groups_device(ctx, cam, global_seed, params, (double*)ch[0].dev, &st)) return rc;
-    if (int rc = frames.down(cam)) return rc;
-    st.total_ms = whole.hostMs();
-    if (stats) *stats = st;
-    return MCRT_OK;
+    return hostPointerForm(ctx, what, cam, kPassLightGroups, 5, ch, (int)r.planes, "planes'", stats,
+                           [&](mcrt_stats* st) { return mcrt_render_light_groups_device(ctx, cam, global_seed, params, (double*)ch[0].dev, st); });
 }

@@ -1,27 +1,22 @@
-// ID mattes (include/mcrt.h mcrt_render_matte*, mcrt_matte_rank_device, mcrt_matte_code, mcrt_matte_manifest), host side: validation,
-// the key map and the code table, the chunk loop, statistics and the host-pointer form. No kernel here: the ranking is libmcrt_matte.so
-// (csrc/mcrt_matte.hip; DESIGN.md "Image passes" says why, and what mcrt_pass_host.hpp shares). The chunk loop is the AOV pass's with
-// the ranking in it: launchAovRays -> intersectDeviceArrays -> launchMatteRank (which maps surfaces to keys as it loads them)
-// [-> launchAovResolve when the AOV channels are wanted too], on the AOV pass's ray scratch (kPassAov slots 0 .. 4: the two passes of a
-// context run one after the other). Scratch slots of the family: 0 the uploaded key map (MCRT_MATTE_CUSTOM), 1 the code table, 2 the
-// memory form's work arrays, 3 the host-pointer form's frames. The map and the codes are made and uploaded by every call that needs them:
-// a snprintf and a hash per key, next to a closest-hit search per sample.
-#include <algorithm>
+// ID mattes (include/mcrt.h mcrt_render_matte*, mcrt_matte_rank_device, mcrt_matte_code, mcrt_matte_manifest), host side: the settings,
+// the key map and the code table, the ranking's form, the manifest, and behind the camera-ray passes' chunk loop (mcrt_camera_pass.hpp)
+// launchMatteRank (which maps surfaces to keys as it loads them) [-> launchAovResolve when the AOV channels are wanted too]. No kernel
+// here: the ranking is libmcrt_matte.so (csrc/mcrt_matte.hip; DESIGN.md "Image passes" says why). Scratch slots of the family: 0 the
+// uploaded key map (MCRT_MATTE_CUSTOM), 1 the code table, 2 the memory form's work arrays, 3 the host-pointer form's frames. The map and
+// the codes are made and uploaded by every call that needs them: a snprintf and a hash per key, next to a closest-hit search per sample.
 #include <cstdio>
 #include <cstring>
 #include <vector>
 
-#include "mcrt_aov.hpp"
-#include "mcrt_aov_launch.hpp"
+#include "mcrt_camera_pass.hpp"
 #include "mcrt_matte.hpp"
 #include "mcrt_matte_launch.hpp"
-#include "mcrt_pass_host.hpp"
 
 using namespace mcrt;
 
 namespace {
 
-constexpr uint64_t kMatteDefaultChunkRays = 1ull << 24;  // (the AOV pass's: the option is shared)
+static_assert(kMatteMaxSamples == kClosestHitMaxRays, "a ranking takes what one closest-hit search gives it");
 
 struct MatteSettings {
     uint32_t key, ranks, num_keys;
@@ -91,19 +86,9 @@ int rankLaunch(mcrt_ctx* ctx, hipStream_t stream, MatteRank& mr, int form, const
 }
 
 int validateCamera(mcrt_ctx* ctx, const mcrt_camera_desc* cam, const mcrt_matte_buffers* buffers, const char* what) {  // (as mcrt_render_aov*)
-    if (!cam || !buffers) return ctxFail(ctx, MCRT_ERR_INVALID, std::string(what) + ": cam or buffers is NULL");
-    if (cam->width == 0 || cam->height == 0 || cam->sqrtspp == 0)
-        return ctxFail(ctx, MCRT_ERR_INVALID, "camera: width, height and sqrtspp must be non-zero");
-    if (cam->shard_count > 1 && cam->shard_index >= cam->shard_count) return ctxFail(ctx, MCRT_ERR_INVALID, "camera: shard_index >= shard_count");
-    if ((uint64_t)cam->width * cam->height > 0xFFFFFFFFull) return ctxFail(ctx, MCRT_ERR_INVALID, "camera: more than 2^32 pixels");
-    if ((uint64_t)cam->sqrtspp * cam->sqrtspp > kMatteMaxSamples)
-        return ctxFail(ctx, MCRT_ERR_UNSUPPORTED, std::string(what) + ": more samples per pixel than one closest-hit launch takes");
-    return MCRT_OK;
-}
-
-int ready(mcrt_ctx* ctx, const char* what) {  // (the scene first: a context without one says so, whatever else is wrong)
-    if (int rc = ctxNeedScene(ctx, what)) return rc;
-    return ctxIdle(ctx, what);
+    if (int rc = cameraPassReady(ctx, what)) return rc;
+    if (int rc = checkCamera(ctx, cam, buffers != nullptr, what)) return rc;
+    return checkPixelSlots(ctx, cam, 1, "samples", what);
 }
 
 int settingsFor(mcrt_ctx* ctx, const mcrt_matte_params* params, MatteSettings& s, const char* what) {
@@ -180,7 +165,6 @@ extern "C" int mcrt_render_matte_device(mcrt_ctx* ctx, const mcrt_camera_desc* c
                                         const mcrt_matte_buffers* d_buffers, const mcrt_aov_buffers* d_aov, mcrt_stats* stats) {
     const char* what = "mcrt_render_matte_device";
     if (!ctx) return MCRT_ERR_INVALID;
-    if (int rc = ready(ctx, what)) return rc;
     if (int rc = validateCamera(ctx, cam, d_buffers, what)) return rc;
     MatteSettings s;
     if (int rc = settingsFor(ctx, params, s, what)) return rc;
@@ -188,31 +172,15 @@ extern "C" int mcrt_render_matte_device(mcrt_ctx* ctx, const mcrt_camera_desc* c
     const int form = formOf(ctx, spp);
     if (!form) return ctxFail(ctx, MCRT_ERR_UNSUPPORTED, std::string(what) + ": option MCRT_MATTE_FORM pins the tile form, which takes 2048 samples per pixel at most");
     PassTimer timer(ctx);
-    hipStream_t stream = (hipStream_t)ctxStream(ctx);
-    const uint64_t total_pixels = (uint64_t)mcrt_shard_rows(cam, nullptr) * cam->width;
-    // a chunk is a whole number of pixels, at least one, and never more rays than one closest-hit launch takes (as mcrt_render_aov_device)
-    const long want = ctxOptL(ctx, "MCRT_AOV_CHUNK_RAYS", (long)kMatteDefaultChunkRays);
-    const uint64_t chunk_rays = std::min<uint64_t>(want > 0 ? (uint64_t)want : kMatteDefaultChunkRays, kMatteMaxSamples);
-    const uint64_t chunk_pixels = std::min<uint64_t>(std::max<uint64_t>(chunk_rays / spp, 1), std::max<uint64_t>(total_pixels, 1));
-    const uint64_t max_rays = chunk_pixels * spp;
-
+    const PixelChunks plan = pixelChunksOf(ctx, cam, 1, defaultChunkSlots());
     AovRays rays;
-    rays.start = (double*)ctxPassScratch(ctx, kPassAov, 0, max_rays * 24);
-    rays.direction = (double*)ctxPassScratch(ctx, kPassAov, 1, max_rays * 24);
-    rays.t = (double*)ctxPassScratch(ctx, kPassAov, 2, max_rays * 8);
-    rays.surface = (uint32_t*)ctxPassScratch(ctx, kPassAov, 3, max_rays * 4);
-    rays.uv = (double*)ctxPassScratch(ctx, kPassAov, 4, max_rays * 16);
-    if (!rays.start || !rays.direction || !rays.t || !rays.surface || !rays.uv)
-        return ctxFail(ctx, MCRT_ERR_HIP, std::string(what) + ": " + std::to_string((max_rays * 76) >> 20) +
-                                              " MiB of ray scratch could not be allocated (option MCRT_AOV_CHUNK_RAYS sizes it)");
-    AovScene scene;
-    const uint32_t* sobol_tab = nullptr;
-    ctxAovScene(ctx, &scene, &sobol_tab);
+    if (int rc = rayScratch(ctx, what, kPassAov, plan.max_rays, plan.max_rays, rays)) return rc;
+    const CameraPass cp(ctx);
 
     // the key map and, when the layer is wanted, the code table
     const uint32_t* d_map = nullptr;
     const uint32_t* d_codes = nullptr;
-    if (s.key == MCRT_MATTE_MATERIAL) d_map = scene.sh.surf_material;
+    if (s.key == MCRT_MATTE_MATERIAL) d_map = cp.scene.sh.surf_material;
     if (s.key == MCRT_MATTE_CUSTOM) {
         uint32_t num_surfaces = 0, num_materials = 0;
         ctxSceneCounts(ctx, &num_surfaces, &num_materials);
@@ -231,65 +199,44 @@ extern "C" int mcrt_render_matte_device(mcrt_ctx* ctx, const mcrt_camera_desc* c
         d_codes = (const uint32_t*)up;
     }
 
-    if (int rc = timer.begin(stream)) return rc;
-    uint32_t launches = 0;
-    for (uint64_t first = 0; first < total_pixels; first += chunk_pixels) {
-        AovChunk c;
-        c.cam = *cam;
-        c.global_seed = global_seed;
-        c.spp = spp;
-        c.first_pixel = first;
-        c.pixels = (uint32_t)std::min<uint64_t>(chunk_pixels, total_pixels - first);
-        const uint64_t n = (uint64_t)c.pixels * spp;
-        MCRT_HIP_TRY(ctx, (hipError_t)launchAovRays(stream, c, scene.sh.scene_ior, sobol_tab, rays));
-        if (int rc = intersectDeviceArrays(ctx, n, rays.start, rays.direction, rays.t, rays.surface, rays.uv)) return rc;
+    return runChunks(ctx, cp, timer, cam, global_seed, plan, rays, stats, [&](const AovChunk& c, uint32_t& launches, uint64_t&) {
         MatteRank mr{};
         mr.keys = rays.surface;
         mr.map = d_map;
         mr.codes = d_codes;
         mr.out = *d_buffers;
-        mr.first_pixel = first;
+        mr.first_pixel = c.first_pixel;
         mr.pixels = c.pixels;
         mr.spp = spp;
         mr.ranks = s.ranks;
-        if (int rc = rankLaunch(ctx, stream, mr, form, what)) return rc;
-        launches += 3;
+        if (int rc = rankLaunch(ctx, cp.stream, mr, form, what)) return rc;
+        launches++;
         if (d_aov) {
-            MCRT_HIP_TRY(ctx, (hipError_t)launchAovResolve(stream, c, scene, rays, *d_aov));
+            MCRT_HIP_TRY(ctx, (hipError_t)launchAovResolve(cp.stream, c, cp.scene, rays, *d_aov));
             launches++;
         }
-    }
-    if (int rc = timer.end(stream)) return rc;
-    if (int rc = timer.finish(stats, launches)) return rc;
-    if (stats) stats->paths = stats->rays = total_pixels * spp;
-    return MCRT_OK;
+        return (int)MCRT_OK;
+    });
 }
 
 extern "C" int mcrt_render_matte(mcrt_ctx* ctx, const mcrt_camera_desc* cam, uint32_t global_seed, const mcrt_matte_params* params,
                                  const mcrt_matte_buffers* buffers, const mcrt_aov_buffers* aov, mcrt_stats* stats) {
     const char* what = "mcrt_render_matte";
     if (!ctx) return MCRT_ERR_INVALID;
-    if (int rc = ready(ctx, what)) return rc;
     if (int rc = validateCamera(ctx, cam, buffers, what)) return rc;
     MatteSettings s;
     if (int rc = settingsFor(ctx, params, s, what)) return rc;
-    PassTimer whole(ctx);
-    // the wanted buffers as one device allocation: the four of the mattes, then the AOV pass's eight
+    // the wanted buffers: the four of the mattes, then the AOV pass's eight
     const size_t r = s.ranks;
     const mcrt_aov_buffers none{};
     const mcrt_aov_buffers& a = aov ? *aov : none;
     FrameChannel ch[12] = {{nullptr, buffers->id, 4 * r}, {nullptr, buffers->coverage, 8 * r}, {nullptr, buffers->layer, 16 * r}, {nullptr, buffers->distinct, 4},
                            {nullptr, a.depth, 8},  {nullptr, a.position, 24}, {nullptr, a.normal, 24}, {nullptr, a.shading_normal, 24},
                            {nullptr, a.albedo, 24}, {nullptr, a.coverage, 8}, {nullptr, a.surface, 4}, {nullptr, a.material, 4}};
-    ShardFrames frames{{ctx, what, kPassMatte, 3, kPackedWanted, ch, 12}};
-    if (int rc = frames.place(cam, "buffers'")) return rc;
-    const mcrt_matte_buffers d{(uint32_t*)ch[0].dev, (double*)ch[1].dev, (double*)ch[2].dev, (uint32_t*)ch[3].dev};
-    const mcrt_aov_buffers da{(double*)ch[4].dev, (double*)ch[5].dev, (double*)ch[6].dev, (double*)ch[7].dev,
-                              (double*)ch[8].dev, (double*)ch[9].dev, (uint32_t*)ch[10].dev, (uint32_t*)ch[11].dev};
-    mcrt_stats st;
-    if (int rc = mcrt_render_matte_device(ctx, cam, global_seed, params, &d, aov ? &da : nullptr, &st)) return rc;
-    if (int rc = frames.down(cam)) return rc;
-    st.total_ms = whole.hostMs();
-    if (stats) *stats = st;
-    return MCRT_OK;
+    return hostPointerForm(ctx, what, cam, kPassMatte, 3, ch, 12, "buffers'", stats, [&](mcrt_stats* st) {
+        const mcrt_matte_buffers d{(uint32_t*)ch[0].dev, (double*)ch[1].dev, (double*)ch[2].dev, (uint32_t*)ch[3].dev};
+        const mcrt_aov_buffers da{(double*)ch[4].dev, (double*)ch[5].dev, (double*)ch[6].dev, (double*)ch[7].dev,
+                                  (double*)ch[8].dev, (double*)ch[9].dev, (uint32_t*)ch[10].dev, (uint32_t*)ch[11].dev};
+        return mcrt_render_matte_device(ctx, cam, global_seed, params, &d, aov ? &da : nullptr, st);
+    });
 }

@@ -1,6 +1,8 @@
-// The image passes' host toolkit (DESIGN.md "Image passes"): what the host sides of the first-hit AOV pass, the a-trous filter, the sample
-// statistics and the firefly suppression (mcrt_*_host.hip) share - the HIP-error macro, a call's event pair and statistics, the guard of a
-// render's sample targets, and the device copies of the host-pointer forms' frames. The context's side of it is in mcrt_internal.hpp.
+// The image passes' host toolkit (DESIGN.md "Image passes"): what the host sides of every image pass (mcrt_*_host.hip: the first-hit AOV
+// pass, the three filters, the sample statistics, the firefly suppression, accumulated rendering, the OpenEXR output and input, the ID
+// mattes, the frame comparison, the occlusion pass, the lighting passes, the light groups) share - the HIP-error macro, a call's event pair
+// and statistics, the guard of a render's sample targets, and the device copies of the host-pointer forms' frames. The context's side of
+// it is in mcrt_internal.hpp; what the passes that trace camera rays share beyond it is mcrt_camera_pass.hpp.
 #pragma once
 
 #include <hip/hip_runtime.h>

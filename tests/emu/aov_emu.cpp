@@ -1,50 +1,21 @@
 // tests/emu/aov_emu.cpp — TEST HARNESS ONLY (built by tests/test_aov_emulation.py into tests/emu/_build/).
 //
 // The first-hit AOV pass on the host: csrc/mcrt_aov.hpp unchanged - the text the two kernels of csrc/mcrt_aov.hip run - driven chunk by
-// chunk the way mcrt_render_aov_device drives them, with the closest hits from the emulation's sceneIntersect (mcrt_emu.cpp's
-// emu_intersect). Not a CPU fallback: nothing in the product links or loads it.
+// chunk the way mcrt_render_aov_device drives them (mcrt_emu.cpp's chunk plan and emuCameraRays), with the closest hits from the
+// emulation's sceneIntersect (emu_intersect). Not a CPU fallback: nothing in the product links or loads it.
 #include "mcrt_emu.cpp"
-
-#include "../../monte-carlo-ray-tracer_amd/csrc/mcrt_aov.hpp"
-
-namespace {
-
-AovScene aovSceneOf(const Emu& E) {
-    AovScene s;
-    s.sh = E.sh_top;
-    s.prim = E.L.prim.data();
-    return s;
-}
-
-AovChunk aovChunkOf(const mcrt_camera_desc* cam, uint32_t global_seed, uint64_t first, uint32_t pixels) {
-    AovChunk c;
-    c.cam = *cam;
-    c.global_seed = global_seed;
-    c.spp = cam->sqrtspp * cam->sqrtspp;
-    c.first_pixel = first;
-    c.pixels = pixels;
-    return c;
-}
-
-uint32_t ownedRows(const mcrt_camera_desc* cam) {
-    uint32_t rows = 0;
-    for (uint32_t ly = 0; localToGlobalRow(*cam, ly) < cam->height; ly++) rows++;
-    return rows;
-}
-
-}  // namespace
 
 extern "C" {
 
 // Owned rows of the camera's shard (what mcrt_shard_rows counts).
-uint32_t aov_emu_rows(const mcrt_camera_desc* cam) { return ownedRows(cam); }
+uint32_t aov_emu_rows(const mcrt_camera_desc* cam) { return ownedRows(*cam); }
 
 // The camera rays of the frame, [pixel][sample][3] over the packed owned rows.
 int aov_emu_rays(const mcrt_scene_desc* scene, const mcrt_camera_desc* cam, uint32_t global_seed, double* start, double* direction) {
     std::vector<uint32_t> tab(kSobolTableWords);
     buildSobolByteTables(tab.data());
-    const uint64_t pixels = (uint64_t)ownedRows(cam) * cam->width;
-    const AovChunk c = aovChunkOf(cam, global_seed, 0, (uint32_t)pixels);
+    const uint64_t pixels = (uint64_t)ownedRows(*cam) * cam->width;
+    const AovChunk c = chunkAt(*cam, global_seed, cam->sqrtspp * cam->sqrtspp, 0, pixels, pixels);
     for (uint64_t p = 0; p < pixels; p++)
         for (uint32_t i = 0; i < c.spp; i++) {
             const Ray ray = aovCameraRay<true>(c, scene->scene_ior, (uint32_t)p, i, tab.data());
@@ -61,32 +32,24 @@ int aov_emu_frame(const mcrt_scene_desc* scene, const mcrt_camera_desc* cam, uin
     Emu E;
     if (int rc = setup(E, scene, 0)) return rc;
     const AovScene as = aovSceneOf(E);
-    const uint32_t spp = cam->sqrtspp * cam->sqrtspp;
-    const uint64_t total = (uint64_t)ownedRows(cam) * cam->width;
-    const uint64_t chunk_pixels = std::min<uint64_t>(std::max<uint64_t>((chunk_rays ? chunk_rays : total * spp) / spp, 1), std::max<uint64_t>(total, 1));
-    std::vector<double> start(chunk_pixels * spp * 3), dir(chunk_pixels * spp * 3), t(chunk_pixels * spp), uv(chunk_pixels * spp * 2);
-    std::vector<uint32_t> surf(chunk_pixels * spp);
-    for (uint64_t first = 0; first < total; first += chunk_pixels) {
-        const AovChunk c = aovChunkOf(cam, global_seed, first, (uint32_t)std::min<uint64_t>(chunk_pixels, total - first));
-        const uint64_t n = (uint64_t)c.pixels * spp;
-        for (uint64_t r = 0; r < n; r++) {  // aovRayKernel
-            const Ray ray = aovCameraRay<true>(c, as.sh.scene_ior, (uint32_t)(r % c.pixels), (uint32_t)(r / c.pixels), E.tab.data());
-            aovStore3(start.data(), r, ray.start);
-            aovStore3(dir.data(), r, ray.direction);
-        }
-        if (int rc = emu_intersect(scene, n, start.data(), dir.data(), stage_lds, t.data(), surf.data(), uv.data())) return rc;
-        const AovRays rays{start.data(), dir.data(), t.data(), surf.data(), uv.data()};
+    const PixelChunks plan = emuPixelChunks(cam, 1, chunk_rays);
+    const uint32_t spp = plan.spp;
+    EmuRays records(plan.max_rays);
+    const AovRays rays = records.view();
+    for (uint64_t first = 0; first < plan.total_pixels; first += plan.chunk_pixels) {
+        const AovChunk c = chunkAt(*cam, global_seed, spp, first, plan.chunk_pixels, plan.total_pixels);
+        if (int rc = emuCameraRays(scene, E, c, stage_lds, rays)) return rc;
         for (uint32_t p = 0; p < c.pixels; p++) {  // aovResolveKernel
             AovAccum acc;
             aovBegin(acc);
             for (uint32_t i = 0; i < spp; i++) {
                 const uint64_t r = (uint64_t)i * c.pixels + p;
                 aovAddRay(acc, as, i, rays, r);
-                if (hit_t) hit_t[(first + p) * spp + i] = t[r];
-                if (hit_surface) hit_surface[(first + p) * spp + i] = surf[r];
+                if (hit_t) hit_t[(first + p) * spp + i] = rays.t[r];
+                if (hit_surface) hit_surface[(first + p) * spp + i] = rays.surface[r];
                 if (hit_uv) {
-                    hit_uv[((first + p) * spp + i) * 2] = uv[2 * r];
-                    hit_uv[((first + p) * spp + i) * 2 + 1] = uv[2 * r + 1];
+                    hit_uv[((first + p) * spp + i) * 2] = rays.uv[2 * r];
+                    hit_uv[((first + p) * spp + i) * 2 + 1] = rays.uv[2 * r + 1];
                 }
             }
             aovFinish(acc, spp, *out, first + p);

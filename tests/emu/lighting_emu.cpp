@@ -1,26 +1,17 @@
 // tests/emu/lighting_emu.cpp — TEST HARNESS ONLY (built by tests/test_lighting_emulation.py into tests/emu/_build/).
 //
 // The lighting passes on the host: csrc/mcrt_lighting.hpp (and csrc/mcrt_aov.hpp, csrc/mcrt_shade.hpp below it) unchanged - the text the
-// two kernels of csrc/mcrt_lighting.hip run - driven chunk by chunk the way mcrt_render_lighting_device drives them, with the closest hits
-// from the emulation's sceneIntersect (mcrt_emu.cpp's emu_intersect). Not a CPU fallback: nothing in the product links or loads it.
+// two kernels of csrc/mcrt_lighting.hip run - driven chunk by chunk the way mcrt_render_lighting_device drives them (mcrt_emu.cpp's chunk
+// plan and emuCameraRays), with the closest hits from the emulation's sceneIntersect (emu_intersect). Not a CPU fallback: nothing in the
+// product links or loads it.
 #include "mcrt_emu.cpp"
 
 #include "../../monte-carlo-ray-tracer_amd/csrc/mcrt_lighting.hpp"
 
-namespace {
-
-uint32_t ownedRows(const mcrt_camera_desc* cam) {
-    uint32_t rows = 0;
-    for (uint32_t ly = 0; localToGlobalRow(*cam, ly) < cam->height; ly++) rows++;
-    return rows;
-}
-
-}  // namespace
-
 extern "C" {
 
 // Owned rows of the camera's shard (what mcrt_shard_rows counts).
-uint32_t lighting_emu_rows(const mcrt_camera_desc* cam) { return ownedRows(cam); }
+uint32_t lighting_emu_rows(const mcrt_camera_desc* cam) { return ownedRows(*cam); }
 
 // The lighting frame into `out` (host arrays over the packed owned rows, null = channel not wanted), in chunks of chunk_rays shadow and
 // bounce slots (0 = one chunk). stage_lds: emu_intersect's flavour of the walk.
@@ -28,40 +19,20 @@ int lighting_emu_frame(const mcrt_scene_desc* scene, const mcrt_camera_desc* cam
                        const mcrt_lighting_buffers* out) {
     Emu E;
     if (int rc = setup(E, scene, 0)) return rc;
-    AovScene as;
-    as.sh = E.sh_top;
-    as.prim = E.L.prim.data();
-    const uint32_t spp = cam->sqrtspp * cam->sqrtspp;
-    const uint64_t per_pixel = (uint64_t)spp * 2;
-    const uint64_t total = (uint64_t)ownedRows(cam) * cam->width;
-    const uint64_t chunk_pixels = std::min<uint64_t>(std::max<uint64_t>((chunk_rays ? chunk_rays : total * per_pixel) / per_pixel, 1), std::max<uint64_t>(total, 1));
-    const uint64_t max_cam = chunk_pixels * spp, max_lit = chunk_pixels * per_pixel;
-    std::vector<double> c_start(max_cam * 3), c_dir(max_cam * 3), c_t(max_cam), c_uv(max_cam * 2);
-    std::vector<uint32_t> c_surf(max_cam);
-    std::vector<double> l_start(max_lit * 3), l_dir(max_lit * 3), l_t(max_lit), l_uv(max_lit * 2);
-    std::vector<uint32_t> l_surf(max_lit);
-    for (uint64_t first = 0; first < total; first += chunk_pixels) {
-        AovChunk c;
-        c.cam = *cam;
-        c.global_seed = global_seed;
-        c.spp = spp;
-        c.first_pixel = first;
-        c.pixels = (uint32_t)std::min<uint64_t>(chunk_pixels, total - first);
-        const uint64_t n = (uint64_t)c.pixels * spp;
-        for (uint64_t r = 0; r < n; r++) {  // aovRayKernel
-            const Ray ray = aovCameraRay<true>(c, as.sh.scene_ior, (uint32_t)(r % c.pixels), (uint32_t)(r / c.pixels), E.tab.data());
-            aovStore3(c_start.data(), r, ray.start);
-            aovStore3(c_dir.data(), r, ray.direction);
-        }
-        if (int rc = emu_intersect(scene, n, c_start.data(), c_dir.data(), stage_lds, c_t.data(), c_surf.data(), c_uv.data())) return rc;
-        const AovRays cam_rays{c_start.data(), c_dir.data(), c_t.data(), c_surf.data(), c_uv.data()};
-        const AovRays lit{l_start.data(), l_dir.data(), l_t.data(), l_surf.data(), l_uv.data()};
+    const AovScene as = aovSceneOf(E);
+    const PixelChunks plan = emuPixelChunks(cam, 2, chunk_rays);
+    EmuRays cam_records(plan.max_rays), lit_records(plan.max_slots);
+    const AovRays cam_rays = cam_records.view(), lit = lit_records.view();
+    for (uint64_t first = 0; first < plan.total_pixels; first += plan.chunk_pixels) {
+        const AovChunk c = chunkAt(*cam, global_seed, plan.spp, first, plan.chunk_pixels, plan.total_pixels);
+        const uint64_t n = (uint64_t)c.pixels * c.spp;
+        if (int rc = emuCameraRays(scene, E, c, stage_lds, cam_rays)) return rc;
         for (uint64_t r = 0; r < n; r++) lightingChunkRays(c, as, cam_rays, lit, r, E.tab.data());  // lightingRayKernel
         if (int rc = emu_intersect(scene, 2 * n, lit.start, lit.direction, stage_lds, lit.t, lit.surface, lit.uv)) return rc;
         for (uint32_t p = 0; p < c.pixels; p++) {  // lightingResolveKernel
             LightingAccum acc;
             lightingPixel(acc, c, as, cam_rays, lit, p, E.tab.data());
-            lightingFinish(acc, spp, *out, first + p);
+            lightingFinish(acc, c.spp, *out, first + p);
         }
     }
     return 0;

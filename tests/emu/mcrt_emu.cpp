@@ -1258,3 +1258,44 @@ void emu_instance_ids(int* out) {
 }
 
 }  // extern "C"
+
+// What the emulations of the camera-ray passes share ({aov,occlusion,lighting,light_groups}_emu.cpp, which include this file): the pure
+// layer of csrc/mcrt_camera_pass.hpp - the chunk plan, chunkAt, ownedRows, the text the host sides run - and the head of a chunk.
+#include "../../monte-carlo-ray-tracer_amd/csrc/mcrt_camera_pass.hpp"
+
+namespace {
+
+AovScene aovSceneOf(const Emu& E) {
+    AovScene s;
+    s.sh = E.sh_top;
+    s.prim = E.L.prim.data();
+    return s;
+}
+
+// The plan of a frame in chunks of chunk_slots slots (0 = one chunk), per_sample slots per camera sample.
+PixelChunks emuPixelChunks(const mcrt_camera_desc* cam, uint64_t per_sample, uint64_t chunk_slots) {
+    const uint32_t spp = cam->sqrtspp * cam->sqrtspp;
+    const uint64_t total = (uint64_t)ownedRows(*cam) * cam->width;
+    return pixelChunks(total, spp, spp * per_sample, chunk_slots, total * spp * per_sample);
+}
+
+// Host arrays for the records of n rays.
+struct EmuRays {
+    std::vector<double> start, direction, t, uv;
+    std::vector<uint32_t> surface;
+    explicit EmuRays(uint64_t n) : start(3 * n), direction(3 * n), t(n), uv(2 * n), surface(n) {}
+    AovRays view() { return AovRays{start.data(), direction.data(), t.data(), surface.data(), uv.data()}; }
+};
+
+// The head of a chunk as runChunks has it: aovRayKernel, then the closest hits.
+int emuCameraRays(const mcrt_scene_desc* scene, const Emu& E, const AovChunk& c, int stage_lds, const AovRays& rays) {
+    const uint64_t n = (uint64_t)c.pixels * c.spp;
+    for (uint64_t r = 0; r < n; r++) {
+        const Ray ray = aovCameraRay<true>(c, E.sh_top.scene_ior, (uint32_t)(r % c.pixels), (uint32_t)(r / c.pixels), E.tab.data());
+        aovStore3(rays.start, r, ray.start);
+        aovStore3(rays.direction, r, ray.direction);
+    }
+    return emu_intersect(scene, n, rays.start, rays.direction, stage_lds, rays.t, rays.surface, rays.uv);
+}
+
+}  // namespace

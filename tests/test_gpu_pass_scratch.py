@@ -124,3 +124,70 @@ def test_device_outputs_stay_what_they_were_across_host_calls_of_other_families(
     ctx.robust_resolve_device(width, height, SPP, d["rgb"].data_ptr(), d["tops"].data_ptr(), d["level"].data_ptr(), live["robust"].data_ptr(),
                               live["removed"].data_ptr(), live["clamped"].data_ptr())
     then(live, want["robust_resolve"], "render_aov", "denoise", "render_pixel_stats", "frame_noise")
+
+
+# The passes that trace camera rays (csrc/mcrt_camera_pass.hpp) all keep the camera-ray records in kPassAov slots 0 .. 4, each sized for
+# its own chunk - 76 B a ray - and the second search's rays in slots 0 .. 4 of their own family. So the five of them run in a row on ONE
+# context, in small chunks, at the three sizes above, and every array of every call must be, bit for bit, what the same call gives on a
+# context of its own that takes the frame in one chunk. Bounds: bits - neither the chunking nor a context's history is an input.
+CAMERA_CHUNK_RAYS = 40  # 10 pixels a chunk for the AOV pass and the mattes, 3 for the occlusion pass (12 rays a pixel), 5 for the lighting
+                        # passes and the light groups (8 slots a pixel): 20, 64 and 39 chunks at 16 x 12, the last one ragged every time
+_fresh_camera = {}
+
+
+def camera_calls(cam):
+    """The five camera-ray passes in the order they run: name -> function(ctx, stats) -> dict of arrays (or of numbers and texts). The
+    room is closed, so an unbounded occlusion ray always hits and that frame is all zeros; a sixth call bounds the rays at 2 units, where
+    the emulation's ao lies between 1/12 and 1."""
+    def matte(c, st):
+        res = c.render_matte(cam, SEED, aov=True, stats=st)
+        res.update({"aov." + k: v for k, v in res.pop("aov").items()})
+        return res
+    return [
+        ("render_aov", lambda c, st: c.render_aov(cam, SEED, stats=st)),
+        ("render_matte", matte),
+        ("render_occlusion", lambda c, st: c.render_occlusion(cam, SEED, rays=3, stats=st)),
+        ("render_lighting", lambda c, st: c.render_lighting(cam, SEED, stats=st)),
+        ("render_light_groups", lambda c, st: {"planes": c.render_light_groups(cam, SEED, stats=st)}),
+        ("render_occlusion_near", lambda c, st: c.render_occlusion(cam, SEED, rays=3, max_distance=2.0, stats=st)),
+    ]
+
+
+def fresh_camera(pkg, size):
+    """Every camera-ray pass on a context of its own, option MCRT_AOV_CHUNK_RAYS unset (one chunk), once per frame size."""
+    if size not in _fresh_camera:
+        res = {}
+        for name, call in camera_calls(camera(*size)):
+            ctx = pkg.Context(0)
+            try:
+                ctx.upload_image(aov._image(SCENE))
+                assert ctx.get_option("MCRT_AOV_CHUNK_RAYS") is None
+                res[name] = call(ctx, {})
+            finally:
+                ctx.close()
+        assert res["render_aov"]["coverage"].any() and res["render_matte"]["coverage"].any() and res["render_occlusion_near"]["ao"].any()
+        assert res["render_occlusion_near"]["bent_normal"].any() and not res["render_occlusion"]["ao"].any()
+        assert res["render_lighting"]["direct"].any() and res["render_light_groups"]["planes"].any()
+        _fresh_camera[size] = res
+    return _fresh_camera[size]
+
+
+def test_one_context_gives_every_camera_ray_pass_in_small_chunks_what_a_fresh_context_gives(pkg, ctx):
+    try:
+        ctx.set_option("MCRT_AOV_CHUNK_RAYS", CAMERA_CHUNK_RAYS)
+        for visit, size in enumerate(SIZES):
+            want, pixels = fresh_camera(pkg, size), size[0] * size[1]
+            # launches per chunk (include/mcrt.h): 3, 3 + 1 with the AOV channels, 5, 5; the light groups' depend on the paths
+            launches = {"render_aov": 3 * -(-pixels // 10), "render_matte": 4 * -(-pixels // 10), "render_occlusion": 5 * -(-pixels // 3),
+                        "render_occlusion_near": 5 * -(-pixels // 3),
+                        "render_lighting": 5 * -(-pixels // 5)}
+            for name, call in camera_calls(camera(*size)):
+                st = {}
+                assert_same(call(ctx, st), want[name], "visit %d, %d x %d: %s" % (visit, size[0], size[1], name))
+                assert st["paths"] == pixels * SPP, name
+                if name in launches:
+                    assert st["kernel_launches"] == launches[name], (name, size)
+                else:
+                    assert st["kernel_launches"] >= 4 * -(-pixels // 5), (name, size)  # rays, search, begin and resolve in every chunk
+    finally:
+        ctx.set_option("MCRT_AOV_CHUNK_RAYS", None)
