@@ -757,7 +757,7 @@ int mcrt_render_converged(mcrt_ctx* ctx, const mcrt_camera_desc* cam, uint32_t g
  * Any other pair is refused.
  *
  * The file, little-endian throughout:
- *   magic 76 2f 31 01, version 02 00 00 00 (single-part scan line, short names)
+ *   magic 76 2f 31 01, version 02 00 00 00 (single-part scan line, short names; with MCRT_EXR_LONG_NAMES 02 04 00 00: the long-names bit 0x400)
  *   attributes, each name\0 type\0 int32 size, value, in this order:
  *     channels (chlist): per channel name\0, int32 pixelType, uint8 pLinear 0, three 0 bytes, int32 xSampling 1, int32 ySampling 1;
  *       one \0 closes the list      compression (compression): 1 byte      dataWindow, displayWindow (box2i): 0, 0, W-1, H-1
@@ -776,7 +776,7 @@ int mcrt_render_converged(mcrt_ctx* ctx, const mcrt_camera_desc* cam, uint32_t g
  * on the zlib version - what a reader decodes from it is a function of the inputs.
  *
  * Refused with MCRT_ERR_INVALID: a render in flight; path, the channel array or a data pointer NULL; count 0 or > 1024;
- * width * height 0 or >= 2^32; a name that is empty, longer than 31 bytes or not printable ASCII (0x20 .. 0x7e); duplicate
+ * width * height 0 or >= 2^32; a name that is empty, longer than 31 bytes (channel names with MCRT_EXR_LONG_NAMES: 255) or not printable ASCII (0x20 .. 0x7e); duplicate
  * names; stride 0 or offset >= stride; a source / pixel type pair not listed; a compression not listed; zip_level > 9; an
  * attribute without a name or value, or whose name is one of the standard ones above. With MCRT_ERR_IO: the file cannot be
  * created or written (a partial file is removed). With MCRT_ERR_UNSUPPORTED: ZIP is asked for and libz.so.1 cannot be loaded
@@ -788,9 +788,10 @@ enum { MCRT_EXR_COMPRESSION_NONE = 0, MCRT_EXR_COMPRESSION_ZIP = 3 };   /* OpenE
 /* mcrt_exr_params.compression: 0 = the default (ZIP); otherwise MCRT_EXR_COMPRESSION_SET | one of the numbers above. */
 #define MCRT_EXR_COMPRESSION_SET 0x100u
 #define MCRT_EXR_HALF_INF 1u            /* mcrt_exr_params.flags: a finite value past the half range becomes +-Inf, not +-65504 */
+#define MCRT_EXR_LONG_NAMES 2u          /* mcrt_exr_params.flags: channel names of up to 255 bytes; the file carries the long-names version bit */
 #define MCRT_EXR_MAX_CHANNELS 1024u
 typedef struct mcrt_exr_channel {
-    const char* name;       /* 1..31 bytes, printable ASCII, e.g. "R", "albedo.G", "denoise_dual.error.B" */
+    const char* name;       /* 1..31 bytes (MCRT_EXR_LONG_NAMES: 255), printable ASCII, e.g. "R", "albedo.G", "denoise_dual.error.B" */
     const void* data;       /* element (pixel p) is data[p * stride + offset] of the source type; row-major, full frame */
     uint32_t source_type, pixel_type, stride, offset;
 } mcrt_exr_channel;
@@ -799,7 +800,7 @@ typedef struct mcrt_exr_params {    /* NULL or a zero field = the default */
     uint32_t compression;           /* default ZIP; MCRT_EXR_COMPRESSION_SET | MCRT_EXR_COMPRESSION_NONE or _ZIP */
     uint32_t zip_level;             /* default 4; 1..9 */
     uint32_t threads;               /* deflate threads, default min(16, the host's hardware threads); never more than 16 */
-    uint32_t flags;                 /* MCRT_EXR_HALF_INF */
+    uint32_t flags;                 /* MCRT_EXR_HALF_INF | MCRT_EXR_LONG_NAMES */
 } mcrt_exr_params;
 typedef struct mcrt_exr_result {
     uint64_t file_bytes;     /* the size of the file written */
@@ -1152,8 +1153,8 @@ int mcrt_render_occlusion(mcrt_ctx* ctx, const mcrt_camera_desc* cam, uint32_t g
  * stats: paths = camera samples; rays = 3 * paths: the camera ray and BOTH slots of every sample traced - the slots of a sample without
  * a shadow or a bounce ray hold its camera ray and go through the search too, their results unread (dead slots are not compacted) -;
  * kernel_ms (HIP events around the pass's launches), total_ms, kernel_launches (5 per chunk).
- * Not done: photon-mapped frames, deeper path classes (diffuse / specular indirect), filter-weighted means. (Per-light frames of the
- * whole path: "Light groups" below.) */
+ * Not done: photon-mapped frames, filter-weighted means. (Per-light frames of the whole path: "Light groups" below; the whole path
+ * split by lobe, direct and indirect: "Path classes" below.) */
 typedef struct mcrt_lighting_buffers { /* every pointer may be NULL = channel not wanted (not all); DEVICE memory, owned rows only, packed like d_out_rgb */
     double* emission;     /* [rows][width][3] */
     double* sky;          /* [rows][width][3] */
@@ -1227,7 +1228,8 @@ int mcrt_render_lighting(mcrt_ctx* ctx, const mcrt_camera_desc* cam, uint32_t gl
  * traces (a sample without a shadow or a bounce ray has a finite dummy traced in that slot; a sample whose ray missed is not alive: its
  * sky was added where the miss was found); kernel_ms (HIP events around the pass's
  * launches), total_ms, kernel_launches.
- * Not done: photon-mapped frames, a split by lobe (diffuse / glossy / transmission), filter-weighted means, nesting deeper than 8 media. */
+ * Not done: photon-mapped frames, filter-weighted means, nesting deeper than 8 media. (A split by lobe - diffuse / glossy /
+ * transmission -: "Path classes" below.) */
 #define MCRT_LIGHT_GROUPS_MAX 15u
 enum { MCRT_LIGHT_GROUPS_SKY_PLANE = 1u }; /* mcrt_light_group_params.flags: sky_plane is given */
 typedef struct mcrt_light_group_params {
@@ -1243,6 +1245,77 @@ int mcrt_render_light_groups_device(mcrt_ctx* ctx, const mcrt_camera_desc* cam, 
                                     double* d_planes, mcrt_stats* stats /* may be NULL */);
 /* Same with a HOST pointer to P FULL frames, [P][height][width][3]: rows this shard does not own are left untouched. */
 int mcrt_render_light_groups(mcrt_ctx* ctx, const mcrt_camera_desc* cam, uint32_t global_seed, const mcrt_light_group_params* params /* may be NULL */,
+                             double* planes, mcrt_stats* stats /* may be NULL */);
+
+/* ------------------------------------------------------------------------------------------
+ * Path classes: the path-traced frame split by what the FIRST surface did with the light - diffuse, glossy, transmission -, each into
+ * the light that arrived there directly and the light that arrived after further bounces, plus emission and background: the layers a
+ * compositor grades separately and a denoiser filters separately. Path tracer only.
+ * The sample, the path, the sampler positions, the closest-hit search and the order of all operations are exactly those of "Light
+ * groups" above: sample i of pixel (x, y) is the AOV pass's camera ray, iteration k of the while (true) of PathTracer::sampleRay has its
+ * sampler at restore(global_seed, y*width+x, i, k + 1), and every iteration runs the functions listed there in that order.
+ * The class: Interaction's selectType (ray/interaction.cpp:156-183) picks ONE lobe per vertex before any light is gathered. Let L be
+ * ia.type of iteration 0's interaction: DIFFUSE -> diffuse, REFLECT -> glossy (on a Dirac surface too), REFRACT -> transmission. Every
+ * term of the path's radiance has one class (MCRT_PATH_CLASSES = 8, in this order):
+ *   0 emission                c = sampleEmissive(ia, ls) of iteration 0
+ *   1 background              c = skyColor(ray) of a camera ray that misses (iteration 0's miss)
+ *   2, 4, 6 diffuse_direct, glossy_direct, transmission_direct (by L)
+ *                             c = sampleDirect(ia, ls) of iteration 0; c = sampleEmissive(ia, ls) of iteration 1; c = skyColor(ray) of
+ *                             iteration 1's miss: the light sample and the BSDF bounce of the first vertex, which the path tracer weights
+ *                             against each other
+ *   3, 5, 7 diffuse_indirect, glossy_indirect, transmission_indirect (by L)
+ *                             c = sampleDirect(ia, ls) of iteration 1; every term of the iterations >= 2
+ * The sample keeps one radiance R_p per plane p, all starting at (0, 0, 0). Where the path tracer executes radiance = radiance +
+ * c * throughput, the pass executes R_p = R_p + c * throughput for exactly ONE plane p = class_plane[class of the term]. The operands
+ * and their order are the path tracer's. A term that the functions return as zeros is skipped, as in the light groups. Per pixel,
+ * plane and word the frame is (((0.0 + R_p(0)) + R_p(1)) + ...) / (double)spp: ascending i, one FP64 accumulator per word, not clamped.
+ * Parameters (params NULL, or a field zero: the default):
+ *   flags        MCRT_PATH_CLASSES_MAP: class_plane is given. Otherwise it is the identity: 8 planes in the order above.
+ *   class_plane  the output plane of every class, each < MCRT_PATH_CLASSES. The number of planes is P = 1 + max(class_plane)
+ *                (mcrt_path_class_planes). Classes may share a plane; a plane that no class maps to comes back as zeros.
+ *   max_depth    D, with the light groups' meaning: 0 = the whole path; with D > 0 iteration k == D takes only its miss or its
+ *                sampleEmissive term and the path ends there.
+ * Output: d_planes, [P][rows][width][3] doubles, the rows this shard owns packed like d_out_rgb. cam->shard_* is honoured exactly as in
+ * mcrt_render_aov_device; cam->film_* is IGNORED. Both calls are synchronous on the context's stream.
+ * What holds, bit for bit unless said otherwise:
+ *   1. The planes are a function of scene, camera, seed and parameters. They do not depend on chunking (option MCRT_AOV_CHUNK_RAYS, with
+ *      the light groups' meaning and default), sharding, launch shape, or the order in which live samples are queued.
+ *   2. With all eight classes mapped to plane 0 and D = 0, plane 0 is the box-film frame of mcrt_render (path tracer, same camera and
+ *      seed), in the exact library, wherever that frame's mean is neither negative nor NaN - and so the light groups' single plane.
+ *   3. A plane does not depend on how the classes that do not map to it are mapped.
+ *   4. emission, background and the three *_direct planes are the same for every D >= 1 and for D = 0: they receive terms in iterations
+ *      0 and 1 only, in the same order. With D = 1 the *_indirect planes are zeros.
+ *   5. The planes add up to the beauty frame to rounding: relative error <= 1e-12, this header's bound for sums of non-negative terms
+ *      taken in another order.
+ * Refused with a message (mcrt_last_error): before mcrt_upload_scene (MCRT_ERR_NO_SCENE); with MCRT_ERR_INVALID a render in flight, a bad
+ * camera or shard, d_planes NULL, a class_plane entry >= MCRT_PATH_CLASSES (the class is named); with MCRT_ERR_UNSUPPORTED a path that
+ * nests more than 8 dielectric media and a frame whose paths are still alive after 4096 iterations, as in the light groups.
+ * stats: as in the light groups (rays = the camera rays and 2 per sample alive at every iteration that traces).
+ * Not done: photon-mapped frames, a split of glossy into Dirac and rough, classification by any vertex other than the first, classes x
+ * light groups in one call, albedo-divided planes, filter-weighted means, nesting deeper than 8 media. */
+#define MCRT_PATH_CLASSES 8u
+enum {
+    MCRT_PATH_CLASS_EMISSION = 0,
+    MCRT_PATH_CLASS_BACKGROUND = 1,
+    MCRT_PATH_CLASS_DIFFUSE_DIRECT = 2,
+    MCRT_PATH_CLASS_DIFFUSE_INDIRECT = 3,
+    MCRT_PATH_CLASS_GLOSSY_DIRECT = 4,
+    MCRT_PATH_CLASS_GLOSSY_INDIRECT = 5,
+    MCRT_PATH_CLASS_TRANSMISSION_DIRECT = 6,
+    MCRT_PATH_CLASS_TRANSMISSION_INDIRECT = 7
+};
+enum { MCRT_PATH_CLASSES_MAP = 1u }; /* mcrt_path_class_params.flags: class_plane is given */
+typedef struct mcrt_path_class_params {
+    uint32_t flags;                          /* MCRT_PATH_CLASSES_* */
+    uint32_t max_depth;                      /* D; 0 = the whole path */
+    uint8_t class_plane[MCRT_PATH_CLASSES];  /* with MCRT_PATH_CLASSES_MAP: the plane of every class, each < MCRT_PATH_CLASSES */
+} mcrt_path_class_params;                    /* 16 bytes */
+/* P of these parameters (NULL: 8); 0 when a class_plane entry is out of range. */
+uint32_t mcrt_path_class_planes(const mcrt_path_class_params* params);
+int mcrt_render_path_classes_device(mcrt_ctx* ctx, const mcrt_camera_desc* cam, uint32_t global_seed, const mcrt_path_class_params* params /* may be NULL */,
+                                    double* d_planes, mcrt_stats* stats /* may be NULL */);
+/* Same with a HOST pointer to P FULL frames, [P][height][width][3]: rows this shard does not own are left untouched. */
+int mcrt_render_path_classes(mcrt_ctx* ctx, const mcrt_camera_desc* cam, uint32_t global_seed, const mcrt_path_class_params* params /* may be NULL */,
                              double* planes, mcrt_stats* stats /* may be NULL */);
 
 /* Photon emission pass on the GPU. Replaces the thread fan-out of

@@ -234,6 +234,34 @@ def light_group_map(scene, by="material"):
     return groups, names + ["sky"]
 
 
+class PathClassParams(C.Structure):
+    """mcrt_path_class_params: MCRT_PATH_CLASSES_* flags, max_depth (0 = the whole path), class_plane (read with PATH_CLASSES_MAP: the
+    output plane of each of the eight classes, in the order of PATH_CLASS_NAMES)."""
+    _fields_ = [("flags", C.c_uint32), ("max_depth", C.c_uint32), ("class_plane", C.c_uint8 * 8)]
+
+
+PATH_CLASSES = 8
+PATH_CLASSES_MAP = 1
+PATH_CLASS_NAMES = ("emission", "background", "diffuse_direct", "diffuse_indirect", "glossy_direct", "glossy_indirect", "transmission_direct",
+                    "transmission_indirect")
+
+
+def path_class_map(merge="all"):
+    """class_plane and plane names for Context.render_path_classes: -> (class_plane [8] uint8, names). merge="all": the eight classes in
+    planes of their own, named by PATH_CLASS_NAMES; "lobes": direct and indirect of a lobe in one plane - emission, background, diffuse,
+    glossy, transmission; "one": everything in plane 0, named "beauty" (mcrt_render's frame bit for bit)."""
+    if merge == "all":
+        names = list(PATH_CLASS_NAMES)
+    elif merge == "lobes":
+        names = ["emission", "background", "diffuse", "glossy", "transmission"]
+    elif merge == "one":
+        names = ["beauty"]
+    else:
+        raise ValueError("path_class_map: merge must be \"all\", \"lobes\" or \"one\", not %r" % (merge,))
+    plane = {"all": lambda c: c, "lobes": lambda c: c if c < 2 else 2 + (c - 2) // 2, "one": lambda c: 0}[merge]
+    return np.array([plane(c) for c in range(PATH_CLASSES)], dtype=np.uint8), names
+
+
 class DenoiseParams(C.Structure):
     """mcrt_denoise_params: a zero field = the default (include/mcrt.h)."""
     _fields_ = [("iterations", C.c_uint32), ("normal_power_log2", C.c_uint32), ("sigma_color", C.c_double), ("sigma_plane", C.c_double),
@@ -371,6 +399,7 @@ EXR_SRC_F64, EXR_SRC_U32 = 0, 1
 EXR_PIXEL_TYPES = {"uint": 0, "half": 1, "float": 2}
 EXR_COMPRESSION = {"none": 0x100 | 0, "zip": 0x100 | 3}  # MCRT_EXR_COMPRESSION_SET | OpenEXR's number
 EXR_HALF_INF = 1
+EXR_LONG_NAMES = 2
 
 
 class ExrChannel(C.Structure):
@@ -539,7 +568,7 @@ def _exr_source(a):
 _EXR_FLOAT_LAYERS = ("depth", "position", "variance", "error", "level")
 
 
-def exr_layers(rgb=None, aov=None, stats=None, highlights=None, robust=None, denoised=None, pixel_types=None, mattes=None, errors=None, occlusion=None, lighting=None, light_groups=None):
+def exr_layers(rgb=None, aov=None, stats=None, highlights=None, robust=None, denoised=None, pixel_types=None, mattes=None, errors=None, occlusion=None, lighting=None, light_groups=None, path_classes=None):
     """The channel dict Context.exr_save takes, from what the render_* and denoise_* methods return, under fixed names:
       rgb [H,W,3]                       R, G, B
       aov (render_aov's dict)           depth.Z, position.X/Y/Z, normal.X/Y/Z, shading_normal.X/Y/Z, albedo.R/G/B, coverage.A, surface.id, material.id
@@ -558,6 +587,8 @@ def exr_layers(rgb=None, aov=None, stats=None, highlights=None, robust=None, den
                                         lighting.unoccluded.R/G/B (those that are there): colour, HALF
       light_groups (planes, names)      lightgroup.<name>.R/G/B for every plane of render_light_groups' [P,H,W,3] and its name
                                         (light_group_map's): colour, HALF
+      path_classes (planes, names)      pathclass.<name>.R/G/B for every plane of render_path_classes' [P,H,W,3] and its name
+                                        (path_class_map's): colour, HALF
     -> dict name -> (view [H,W], "half" | "float" | "uint"). Colour is HALF; depth, position, variance, error and level FLOAT; ids and
     counts UINT. pixel_types: {channel or layer name: type} overrides that (a layer is a name without its last component). The views
     are of the arrays and tensors given, numpy or torch alike: nothing is copied."""
@@ -625,6 +656,11 @@ def exr_layers(rgb=None, aov=None, stats=None, highlights=None, robust=None, den
         assert len(planes) == len(names) and len(set(names)) == len(names), (len(planes), names)
         for plane, name in zip(planes, names):
             put("lightgroup." + name, "RGB", plane)
+    if path_classes is not None:
+        planes, names = path_classes
+        assert len(planes) == len(names) and len(set(names)) == len(names), (len(planes), names)
+        for plane, name in zip(planes, names):
+            put("pathclass." + name, "RGB", plane)
     return out
 
 
@@ -632,7 +668,7 @@ def exr_unlayer(channels):
     """The inverse of exr_layers: from a dict name -> frame [H,W] (Context.exr_load's, numpy arrays or torch tensors) the keyword dict
     exr_layers takes, for the names documented there - rgb [H,W,3]; aov with its [H,W,3] and [H,W] members; stats; highlights with tops
     [H,W,4,3] and level; robust; denoised {name: {"rgb", "variance", "error"}} for every other layer that has R, G and B but no A (R, G,
-    B, A are a matte's layer); occlusion with ao, sky and bent_normal [H,W,3]; lighting with its [H,W,3] channels; light_groups (planes [P,H,W,3], names) from the lightgroup.<name> layers; errors. A layer is taken when all its parts are there; every other name comes back under "other".
+    B, A are a matte's layer); occlusion with ao, sky and bent_normal [H,W,3]; lighting with its [H,W,3] channels; light_groups (planes [P,H,W,3], names) from the lightgroup.<name> layers; path_classes likewise from the pathclass.<name> layers; errors. A layer is taken when all its parts are there; every other name comes back under "other".
     Frames are stacked where they live."""
     left = dict(channels)
 
@@ -692,6 +728,10 @@ def exr_unlayer(channels):
     group_planes = [(name, take("lightgroup." + name, "RGB")) for name in group_names]
     if any(frame is not None for _, frame in group_planes):
         out["light_groups"] = (stack([frame for _, frame in group_planes if frame is not None], axis=0), [name for name, frame in group_planes if frame is not None])
+    class_names = [n[len("pathclass."):-2] for n in channels if n.startswith("pathclass.") and n.endswith(".R")]
+    class_planes = [(name, take("pathclass." + name, "RGB")) for name in class_names]
+    if any(frame is not None for _, frame in class_planes):
+        out["path_classes"] = (stack([frame for _, frame in class_planes if frame is not None], axis=0), [name for name, frame in class_planes if frame is not None])
     errors = {}
     for key, part in COMPARE_ERROR_CHANNELS.items():
         frame = take("error", (part,))
@@ -865,6 +905,11 @@ def lib():
         L.mcrt_render_light_groups_device.argtypes = L.mcrt_render_light_groups.argtypes
         L.mcrt_light_group_planes.argtypes = [C.POINTER(LightGroupParams)]
         L.mcrt_light_group_planes.restype = C.c_uint32
+    if hasattr(L, "mcrt_render_path_classes"):  # (likewise)
+        L.mcrt_render_path_classes.argtypes = [vp, C.POINTER(CameraDesc), C.c_uint32, C.POINTER(PathClassParams), vp, C.POINTER(Stats)]
+        L.mcrt_render_path_classes_device.argtypes = L.mcrt_render_path_classes.argtypes
+        L.mcrt_path_class_planes.argtypes = [C.POINTER(PathClassParams)]
+        L.mcrt_path_class_planes.restype = C.c_uint32
     if hasattr(L, "mcrt_frame_compare"):  # (likewise)
         L.mcrt_frame_compare.argtypes = [vp, C.c_uint32, C.c_uint32, vp, vp, vp, C.POINTER(CompareParams), C.POINTER(CompareMaps), C.POINTER(CompareResult), C.POINTER(Stats)]
         L.mcrt_frame_compare_device.argtypes = L.mcrt_frame_compare.argtypes
@@ -1428,6 +1473,45 @@ class Context:
                     "mcrt_render_light_groups_device")
         return st.as_dict()
 
+    @staticmethod
+    def _path_class_params(class_plane, max_depth):
+        """-> PathClassParams. class_plane: the plane of each of the eight classes, or None = the identity."""
+        par = PathClassParams(0, int(max_depth))
+        if class_plane is not None:
+            entries = [int(p) for p in class_plane]
+            assert len(entries) == PATH_CLASSES and all(0 <= p < 256 for p in entries), entries
+            par.flags = PATH_CLASSES_MAP
+            par.class_plane[:] = entries
+        return par
+
+    def render_path_classes(self, cam, global_seed, class_plane=None, max_depth=0, stats=None, out=None):
+        """mcrt_render_path_classes: the path-traced frame of cam and global_seed split by what the first surface did with the light
+        -> [P,H,W,3]: emission, background, and direct and indirect of diffuse, glossy and transmission (PATH_CLASS_NAMES), which add up
+        to the frame (include/mcrt.h "Path classes"). class_plane: [8] the output plane of every class (path_class_map builds it),
+        None = a plane each. max_depth: 0 = the whole path, 1 = no indirect light. out: an array to write into instead of fresh zeros -
+        the call only writes the rows cam's shard owns. stats: a dict that receives mcrt_stats."""
+        self._sync_env()
+        par = self._path_class_params(class_plane, max_depth)
+        planes = int(self._lib.mcrt_path_class_planes(C.byref(par)))
+        shape = (max(planes, 1), cam.height, cam.width, 3)  # (out of range: the call below says what is)
+        a = out if out is not None else np.zeros(shape)
+        assert a.dtype == np.float64 and a.shape == shape and a.flags["C_CONTIGUOUS"]
+        st = Stats()
+        self._check(self._lib.mcrt_render_path_classes(self._h, C.byref(cam), int(global_seed), C.byref(par), a.ctypes.data, C.byref(st)), "mcrt_render_path_classes")
+        if stats is not None:
+            stats.update(st.as_dict())
+        return a
+
+    def render_path_classes_device(self, cam, global_seed, pointer, class_plane=None, max_depth=0):
+        """mcrt_render_path_classes_device: pointer = raw device pointer to [P][owned rows][W][3] doubles (packed like render_device's
+        output). Synchronous; returns the stats dict."""
+        self._sync_env()
+        par = self._path_class_params(class_plane, max_depth)
+        st = Stats()
+        self._check(self._lib.mcrt_render_path_classes_device(self._h, C.byref(cam), int(global_seed), C.byref(par), int(pointer) if pointer else None, C.byref(st)),
+                    "mcrt_render_path_classes_device")
+        return st.as_dict()
+
     def render_matte(self, cam, global_seed, key="material", ranks=MATTE_DEFAULT_RANKS, names=None, surface_key=None, aov=None, out=None, stats=None,
                      num_keys=None):
         """mcrt_render_matte: the ranked id / coverage mattes of the frame -> dict "id" [H,W,ranks] uint32, "coverage" [H,W,ranks],
@@ -1849,14 +1933,16 @@ class Context:
                                                       C.byref(st)), "mcrt_frame_merge_device")
         return st.as_dict()
 
-    def exr_save(self, path, channels, attributes=None, compression="zip", zip_level=0, threads=0, half_inf=False, stats=None):
+    def exr_save(self, path, channels, attributes=None, compression="zip", zip_level=0, threads=0, half_inf=False, stats=None, long_names=None):
         """mcrt_exr_save / mcrt_exr_save_device: one OpenEXR file of the named channels. channels: dict name -> frame view [H,W] or
         (view, "half" | "float" | "uint") - exr_layers builds it; float64 goes to HALF unless told otherwise, (u)int32 to UINT. The
         views are numpy arrays (the host form: every distinct buffer crosses to the device once) or torch device tensors (the device
         form: only the packed buffer crosses back; all channels must then be tensors of this context's device, complete: the
         producing streams are synchronised here). Last-axis views of one packed buffer become stride / offset of that buffer.
-        attributes: dict name -> str, written as strings. compression: "zip" or "none". -> dict file_bytes, packed_bytes, chunks,
-        raw_chunks. stats: a dict that receives mcrt_stats."""
+        attributes: dict name -> str, written as strings. compression: "zip" or "none". long_names: channel names of up to 255 bytes
+        instead of 31, in a file with OpenEXR's long-names bit (MCRT_EXR_LONG_NAMES); None = when a name needs it
+        (pathclass.transmission_indirect.R is 33 bytes). -> dict file_bytes, packed_bytes, chunks, raw_chunks. stats: a dict that
+        receives mcrt_stats."""
         self._sync_env()
         assert len(channels) >= 1, "no channel"
         keep, recs, shape, on_device = [], [], None, None
@@ -1877,7 +1963,9 @@ class Context:
             import torch
             torch.cuda.synchronize()
         attrs = [ExrAttribute(str(k).encode("ascii"), str(v).encode("ascii")) for k, v in (attributes or {}).items()]
-        par = ExrParams(EXR_COMPRESSION[compression], int(zip_level), int(threads), EXR_HALF_INF if half_inf else 0)
+        if long_names is None:
+            long_names = any(len(name) > 31 for name in channels)
+        par = ExrParams(EXR_COMPRESSION[compression], int(zip_level), int(threads), (EXR_HALF_INF if half_inf else 0) | (EXR_LONG_NAMES if long_names else 0))
         res, st = ExrResult(), Stats()
         call = self._lib.mcrt_exr_save_device if on_device else self._lib.mcrt_exr_save
         self._check(call(self._h, os.fsencode(path), shape[1], shape[0], (ExrChannel * len(recs))(*recs), len(recs),

@@ -1,12 +1,12 @@
 // What the passes that trace camera rays share (DESIGN.md "Image passes"): the first-hit AOV pass, the ID mattes, the occlusion pass, the
-// lighting passes and the light groups (mcrt_{aov,matte,occlusion,lighting,light_groups}_host.hip). Two layers. The PURE one - no HIP, no
+// lighting passes, the light groups and the path classes (mcrt_{aov,matte,occlusion,lighting,light_groups,path_classes}_host.hip). Two layers. The PURE one - no HIP, no
 // context - is the chunk plan, its defaults, a chunk's record and a shard's rows: the host sides and the emulations of the CPU tests
 // (tests/emu/*_emu.cpp, which include this file the way they include mcrt_aov.hpp) run the same text. The HOST one, on top of
 // mcrt_pass_host.hpp and compiled by hipcc only, is the calls' guard, the camera checks, the five arrays of a family's ray scratch, the
 // chunk loop around the camera rays and their closest hits, and the host-pointer form.
 //
 // Every such pass keeps its camera-ray records - 48 B of ray + 28 B of hit = 76 B per ray: start, direction, t, surface, uv - in
-// kPassAov slots 0 .. 4 (the light groups in their samples' state): the passes of a context run one after the other, and each sizes the
+// kPassAov slots 0 .. 4 (the light groups and the path classes in their samples' state): the passes of a context run one after the other, and each sizes the
 // slots for its own chunk. A pass with a second search keeps those rays in slots 0 .. 4 of its own family.
 #pragma once
 

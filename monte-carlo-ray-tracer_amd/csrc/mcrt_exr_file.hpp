@@ -65,11 +65,11 @@ inline void putAttr(std::vector<unsigned char>& b, const char* name, const char*
     putStr(b, type);
     put32(b, size);
 }
-inline bool shortName(const char* s) {
+inline bool shortName(const char* s, size_t most = 31) {
     if (!s) return false;
     size_t n = 0;
     for (; s[n]; n++)
-        if (n >= 31 || (unsigned char)s[n] < 0x20 || (unsigned char)s[n] > 0x7e) return false;
+        if (n >= most || (unsigned char)s[n] < 0x20 || (unsigned char)s[n] > 0x7e) return false;
     return n >= 1;
 }
 inline const char* const kStandardAttributes[] = {"channels", "compression", "dataWindow", "displayWindow", "lineOrder", "pixelAspectRatio", "screenWindowCenter", "screenWindowWidth"};
@@ -84,10 +84,13 @@ inline int exrPlan(const char* path, uint32_t width, uint32_t height, const mcrt
     if (count == 0 || count > MCRT_EXR_MAX_CHANNELS) return refuse(MCRT_ERR_INVALID, "1 .. 1024 channels");
     const uint64_t pixels = (uint64_t)width * height;
     if (pixels == 0 || pixels > 0xFFFFFFFFull) return refuse(MCRT_ERR_INVALID, "width * height must be non-zero and below 2^32");
+    // (the flags are read before the names they bound; they are checked with the other parameters below)
+    const bool long_names = params && (params->flags & MCRT_EXR_LONG_NAMES);
     for (uint32_t i = 0; i < count; i++) {
         const mcrt_exr_channel& c = channels[i];
         const std::string at = "channel " + std::to_string(i);
-        if (!shortName(c.name)) return refuse(MCRT_ERR_INVALID, at + ": a name is 1 .. 31 bytes of printable ASCII");
+        if (!shortName(c.name, long_names ? 255 : 31))
+            return refuse(MCRT_ERR_INVALID, at + (long_names ? ": a name is 1 .. 255 bytes of printable ASCII" : ": a name is 1 .. 31 bytes of printable ASCII"));
         if (!c.data) return refuse(MCRT_ERR_INVALID, at + " (" + c.name + "): data is NULL");
         if (c.stride == 0 || c.offset >= c.stride) return refuse(MCRT_ERR_INVALID, at + " (" + c.name + "): stride 0 or offset >= stride");
         const bool pair = (c.source_type == MCRT_EXR_SRC_F64 && (c.pixel_type == MCRT_EXR_HALF || c.pixel_type == MCRT_EXR_FLOAT)) ||
@@ -109,7 +112,7 @@ inline int exrPlan(const char* path, uint32_t width, uint32_t height, const mcrt
         }
         if (params->zip_level > 9) return refuse(MCRT_ERR_INVALID, "zip_level is 1 .. 9");
         if (params->zip_level) plan.zip_level = params->zip_level;
-        if (params->flags & ~MCRT_EXR_HALF_INF) return refuse(MCRT_ERR_INVALID, "unknown flags");
+        if (params->flags & ~(MCRT_EXR_HALF_INF | MCRT_EXR_LONG_NAMES)) return refuse(MCRT_ERR_INVALID, "unknown flags");
         plan.flags = params->flags;
     }
     if (attribute_count && !attributes) return refuse(MCRT_ERR_INVALID, "the attribute array is NULL");
@@ -145,6 +148,7 @@ inline int exrPlan(const char* path, uint32_t width, uint32_t height, const mcrt
     std::vector<unsigned char>& h = plan.header;
     const unsigned char magic[8] = {0x76, 0x2f, 0x31, 0x01, 0x02, 0x00, 0x00, 0x00};
     h.assign(magic, magic + 8);
+    if (long_names) h[5] = 0x04;  // version bit 0x400: names of up to 255 bytes
     uint32_t chlist = 1;
     for (uint32_t i = 0; i < count; i++) chlist += (uint32_t)strlen(channels[plan.order[i]].name) + 1 + 16;
     putAttr(h, "channels", "chlist", chlist);

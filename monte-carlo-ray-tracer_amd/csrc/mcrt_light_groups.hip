@@ -21,49 +21,18 @@
 // refraction history there ([entry][lane], loaded from the state at entry and written back at exit).
 #include <hip/hip_runtime.h>
 
-#include <algorithm>
-
-#include "mcrt_light_groups.hpp"
+#include "mcrt_light_groups_device.hpp"
 #include "mcrt_light_groups_launch.hpp"
 
 using namespace mcrt;
 
 namespace {
 
-constexpr uint32_t kLgBlock = 256;
-constexpr uint32_t kLgGridMost = 4096;  // (the shading kernels stage 28 KB per block: a block takes several rounds of lanes)
-
-__device__ __forceinline__ void stageTables(uint32_t* ltab, const uint32_t* sobol_tab) {
-    for (uint32_t i = threadIdx.x; i < (uint32_t)kSobolTableWords; i += blockDim.x) ltab[i] = sobol_tab[i];
-    glibc235::stageSinCosTab();
-    __syncthreads();
-}
-
-__device__ __forceinline__ RefractionHistory laneHistory(double* liors) {
-    RefractionHistory rh;
-    rh.iors = (MCRT_LDS_AS double*)liors + threadIdx.x;
-    rh.stride = kLgBlock;
-    rh.size = 0;
-    return rh;
-}
-
-// All lanes of the wave call this together. The survivors' samples go behind one another at the end of `list`.
-__device__ __forceinline__ void appendLive(uint32_t* list, uint32_t* count, bool alive, uint32_t sample) {
-    const unsigned long long m = waveBallot(alive);
-    if (m == 0ull) return;  // (the same for every lane)
-    const uint32_t behind = __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
-    const int leader = __ffsll((long long)m) - 1;
-    uint32_t base = 0u;
-    if ((int)__lane_id() == leader) base = atomicAdd(count, (uint32_t)__popcll(m));
-    base = (uint32_t)__shfl((int)base, leader);
-    if (alive) list[base + behind] = sample;
-}
-
 __global__ void __launch_bounds__(kLgBlock) lightGroupsBeginKernel(LgState st, uint64_t n, double scene_ior, LgParams par, uint32_t* list, LgCounters* counters) {
-    for (uint64_t base = (uint64_t)blockIdx.x * blockDim.x; base < n; base += (uint64_t)gridDim.x * blockDim.x) {  // (whole blocks: appendLive)
+    for (uint64_t base = (uint64_t)blockIdx.x * blockDim.x; base < n; base += (uint64_t)gridDim.x * blockDim.x) {  // (whole blocks: lgAppendLive)
         const uint64_t s = base + threadIdx.x;
         const bool alive = s < n && lgBegin(st, s, scene_ior, par);
-        appendLive(list, &counters->live[0], alive, (uint32_t)s);
+        lgAppendLive(list, &counters->live[0], alive, (uint32_t)s);
     }
 }
 
@@ -72,8 +41,8 @@ __global__ void __launch_bounds__(kLgBlock) lightGroupsRayKernel(AovChunk c, Aov
     __shared__ uint32_t ltab[kSobolTableWords];
     __shared__ double liors[kMaxIors * kLgBlock];
     if (blockIdx.x == 0 && threadIdx.x == 0) counters->live[next] = 0u;  // the list this iteration's step kernel appends to (one fill launch less per iteration)
-    stageTables(ltab, sobol_tab);
-    RefractionHistory rh = laneHistory(liors);
+    lgStageTables(ltab, sobol_tab);
+    RefractionHistory rh = lgLaneHistory(liors);
     for (uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; j < n_live; j += (uint64_t)gridDim.x * blockDim.x)
         lgRays(c, scene, st, list, n_live, (uint32_t)j, k, lit, rh, (SobolTab)ltab);
 }
@@ -83,9 +52,9 @@ __global__ void __launch_bounds__(kLgBlock) lightGroupsStepKernel(AovChunk c, Ao
                                                                   uint32_t next) {
     __shared__ uint32_t ltab[kSobolTableWords];
     __shared__ double liors[kMaxIors * kLgBlock];
-    stageTables(ltab, sobol_tab);
-    RefractionHistory rh = laneHistory(liors);
-    // whole blocks go round together, so that every lane of a wave reaches appendLive
+    lgStageTables(ltab, sobol_tab);
+    RefractionHistory rh = lgLaneHistory(liors);
+    // whole blocks go round together, so that every lane of a wave reaches lgAppendLive
     for (uint64_t base = (uint64_t)blockIdx.x * blockDim.x; base < n_live; base += (uint64_t)gridDim.x * blockDim.x) {
         const uint64_t j = base + threadIdx.x;
         bool alive = false, too_deep = false;
@@ -95,7 +64,7 @@ __global__ void __launch_bounds__(kLgBlock) lightGroupsStepKernel(AovChunk c, Ao
             alive = lgStep(c, scene, st, par, list, n_live, (uint32_t)j, k, last != 0u, lit, rh, too_deep, (SobolTab)ltab);
         }
         if (too_deep) counters->too_deep = 1u;
-        appendLive(next_list, &counters->live[next], alive, sample);
+        lgAppendLive(next_list, &counters->live[next], alive, sample);
     }
 }
 
@@ -105,23 +74,21 @@ __global__ void __launch_bounds__(kLgBlock) lightGroupsResolveKernel(AovChunk c,
     lgResolvePixel(c, st, planes, p, out, frame_pixels);
 }
 
-uint32_t gridFor(uint64_t n) { return (uint32_t)std::min<uint64_t>((n + kLgBlock - 1) / kLgBlock, kLgGridMost); }
-
 }  // namespace
 
 namespace mcrt {
 int launchLightGroupsBegin(void* stream, const LgState& st, uint64_t n, double scene_ior, const LgParams& par, uint32_t* list, LgCounters* counters) {
-    hipLaunchKernelGGL(lightGroupsBeginKernel, dim3(gridFor(n)), dim3(kLgBlock), 0, (hipStream_t)stream, st, n, scene_ior, par, list, counters);
+    hipLaunchKernelGGL(lightGroupsBeginKernel, dim3(lgGridFor(n)), dim3(kLgBlock), 0, (hipStream_t)stream, st, n, scene_ior, par, list, counters);
     return (int)hipGetLastError();
 }
 int launchLightGroupsRays(void* stream, const AovChunk& c, const AovScene& scene, const uint32_t* sobol_tab, const LgState& st, const uint32_t* list, uint32_t n_live,
                           uint32_t k, const AovRays& lit, LgCounters* counters, uint32_t next) {
-    hipLaunchKernelGGL(lightGroupsRayKernel, dim3(gridFor(n_live)), dim3(kLgBlock), 0, (hipStream_t)stream, c, scene, sobol_tab, st, list, n_live, k, lit, counters, next);
+    hipLaunchKernelGGL(lightGroupsRayKernel, dim3(lgGridFor(n_live)), dim3(kLgBlock), 0, (hipStream_t)stream, c, scene, sobol_tab, st, list, n_live, k, lit, counters, next);
     return (int)hipGetLastError();
 }
 int launchLightGroupsStep(void* stream, const AovChunk& c, const AovScene& scene, const uint32_t* sobol_tab, const LgState& st, const LgParams& par, const uint32_t* list,
                           uint32_t n_live, uint32_t k, bool last, const AovRays& lit, uint32_t* next_list, LgCounters* counters, uint32_t next) {
-    hipLaunchKernelGGL(lightGroupsStepKernel, dim3(gridFor(n_live)), dim3(kLgBlock), 0, (hipStream_t)stream, c, scene, sobol_tab, st, par, list, n_live, k,
+    hipLaunchKernelGGL(lightGroupsStepKernel, dim3(lgGridFor(n_live)), dim3(kLgBlock), 0, (hipStream_t)stream, c, scene, sobol_tab, st, par, list, n_live, k,
                        last ? 1u : 0u, lit, next_list, counters, next);
     return (int)hipGetLastError();
 }

@@ -176,6 +176,32 @@ MCRT_HD void lgRays(const AovChunk& c, const AovScene& s, const LgState& st, con
     aovStore3(lit.direction, (uint64_t)n_live + j, d1);
 }
 
+// What the step kernels (this pass's and the path classes', mcrt_path_classes.hpp) share around their additions: the shadow ray's closest
+// hit from record j, and the state of vertex k + 1 - the bounce ray, its hit from record b of `lit`, the throughput, the light sample and
+// the history `rh` after its update.
+MCRT_HD Hit lgShadowHit(const AovRays& lit, uint64_t j) {
+    Hit h;
+    h.surface = lit.surface[j];
+    h.t = lit.t[j];
+    h.u = h.v = 0.0;
+    h.interpolate = false;
+    return h;
+}
+MCRT_HD void lgStoreNext(const LgState& st, uint64_t sample, const LgVertex& v, const AovRays& lit, uint64_t b, const RefractionHistory& rh) {
+    lgStoreRay(st, sample, v.ray);
+    st.ray.t[sample] = lit.t[b];
+    st.ray.surface[sample] = lit.surface[b];
+    st.ray.uv[2 * sample] = lit.uv[2 * b];
+    st.ray.uv[2 * sample + 1] = lit.uv[2 * b + 1];
+    st.throughput[sample] = v.next.x;
+    st.throughput[st.n + sample] = v.next.y;
+    st.throughput[2 * st.n + sample] = v.next.z;
+    st.pdf[sample] = v.ls.bsdf_pdf;
+    st.pdf[st.n + sample] = v.ls.select_probability;
+    st.word[3 * st.n + sample] = v.ls.light;
+    lgStoreHistory(st, sample, rh);
+}
+
 // Step kernel, entry j: the terms of vertex k into their planes in the path tracer's order, then the state of vertex k + 1. `last`: this
 // is iteration max_depth, which takes its emission and ends (its miss was taken where the ray was found to miss; no rays were traced for
 // it, lit is not read). Returns true when
@@ -190,11 +216,7 @@ MCRT_HD bool lgStep(const AovChunk& c, const AovScene& s, const LgState& st, con
     if (v.ia.material->flags & MCRT_MAT_EMISSIVE) lgAdd(st, sample, par.plane[v.ia.surface], v.emission, v.throughput);  // :34 (zeros otherwise)
     if (last) return false;
     if (v.shadow) {  // :35
-        Hit h;
-        h.surface = lit.surface[j];
-        h.t = lit.t[j];
-        h.u = h.v = 0.0;
-        h.interpolate = false;
+        const Hit h = lgShadowHit(lit, j);
         if (h.surface == v.ls.light) lgAdd(st, sample, par.plane[v.ls.light], sampleDirectFinish(s.sh, v.ia, v.ls, v.dq, h), v.throughput);  // (zeros otherwise)
     }
     if (!v.bounce) return false;  // :37-47
@@ -209,18 +231,7 @@ MCRT_HD bool lgStep(const AovChunk& c, const AovScene& s, const LgState& st, con
         lgAdd(st, sample, par.sky_plane, skyColor(v.ray), v.next);
         return false;
     }
-    lgStoreRay(st, sample, v.ray);
-    st.ray.t[sample] = lit.t[b];
-    st.ray.surface[sample] = surface;
-    st.ray.uv[2 * sample] = lit.uv[2 * b];
-    st.ray.uv[2 * sample + 1] = lit.uv[2 * b + 1];
-    st.throughput[sample] = v.next.x;
-    st.throughput[st.n + sample] = v.next.y;
-    st.throughput[2 * st.n + sample] = v.next.z;
-    st.pdf[sample] = v.ls.bsdf_pdf;
-    st.pdf[st.n + sample] = v.ls.select_probability;
-    st.word[3 * st.n + sample] = v.ls.light;
-    lgStoreHistory(st, sample, rh);
+    lgStoreNext(st, sample, v, lit, b, rh);
     return true;
 }
 

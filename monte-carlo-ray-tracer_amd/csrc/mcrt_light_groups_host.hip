@@ -1,5 +1,6 @@
 // Light groups (include/mcrt.h mcrt_render_light_groups*), host side: the group map, the samples' state, and behind the camera-ray
-// passes' chunk loop (mcrt_camera_pass.hpp), which writes the camera rays and their hits straight into that state, the bounce loop:
+// passes' chunk loop (mcrt_camera_pass.hpp), which writes the camera rays and their hits straight into that state, the bounce loop
+// (runLivePaths, mcrt_live_paths_host.hpp, which the path classes run too):
 // launchLightGroupsBegin starts the paths, then per iteration launchLightGroupsRays -> intersectDeviceArrays over 2 rays per LIVE sample
 // -> launchLightGroupsStep, the host reading the next list's count (and the pass's error word) after every step;
 // launchLightGroupsResolve when no sample is alive. No kernel here: they are libmcrt_light_groups.so (csrc/mcrt_light_groups.hip;
@@ -9,19 +10,14 @@
 // Option MCRT_LIGHT_GROUPS_LOG (tools/light_groups_probe.py sets it): one JSON line per chunk on stderr - the live samples of every
 // iteration and the host-clock milliseconds of the chunk and of its searches, the stream drained before each bounce search so that the
 // kernels queued before it are not counted as search (the camera rays' kernel is counted with their search). It changes no result.
-#include <chrono>
-#include <cstdio>
 #include <vector>
 
-#include "mcrt_camera_pass.hpp"
-#include "mcrt_light_groups.hpp"
+#include "mcrt_live_paths_host.hpp"
 #include "mcrt_light_groups_launch.hpp"
 
 using namespace mcrt;
 
 namespace {
-
-constexpr uint64_t kLgRecordBytes = 76;  // start, direction, t, surface, uv of one ray
 
 struct Resolved {
     uint32_t groups, sky_plane, planes, max_depth;
@@ -102,86 +98,29 @@ extern "C" int mcrt_render_light_groups_device(mcrt_ctx* ctx, const mcrt_camera_
     par.max_depth = r.max_depth;
     if (int rc = uploadPlanes(ctx, scene, r, what, &par.plane)) return rc;
 
-    const uint64_t sample_bytes = kLgStateBytes + 24ull * r.planes + 2 * kLgRecordBytes + 8;
+    const uint64_t sample_bytes = kLgStateBytes + 24ull * r.planes + 2 * kLivePathRecordBytes + 8;
     const PixelChunks plan = pixelChunksOf(ctx, cam, 2, lightGroupsDefaultChunkSlots((uint64_t)cam->sqrtspp * cam->sqrtspp * 2, sample_bytes));
     const uint64_t max_n = plan.max_rays, total_pixels = plan.total_pixels;
 
     LgState st;
     void* state = ctxPassScratch(ctx, kPassLightGroups, 0, max_n * kLgStateBytes);
     double* radiance = (double*)ctxPassScratch(ctx, kPassLightGroups, 1, max_n * 24 * r.planes);
-    double* records = (double*)ctxPassScratch(ctx, kPassLightGroups, 2, 2 * max_n * kLgRecordBytes);
-    uint32_t* lists = (uint32_t*)ctxPassScratch(ctx, kPassLightGroups, 3, sizeof(LgCounters) + 2 * max_n * 4);
-    if (!state || !radiance || !records || !lists)
+    LivePathScratch sc;
+    if (!state || !radiance || !livePathScratch(ctx, kPassLightGroups, max_n, sc))
         return ctxFail(ctx, MCRT_ERR_HIP, std::string(what) + ": " + std::to_string((max_n * sample_bytes) >> 20) +
                                               " MiB of path state could not be allocated (option MCRT_AOV_CHUNK_RAYS sizes it)");
     lgPlaceState(st, state, max_n);
     st.radiance = radiance;
-    AovRays lit;  // 2 * max_n records
-    lit.start = records;
-    lit.direction = lit.start + 6 * max_n;
-    lit.t = lit.direction + 6 * max_n;
-    lit.uv = lit.t + 2 * max_n;
-    lit.surface = (uint32_t*)(lit.uv + 4 * max_n);
-    LgCounters* counters = (LgCounters*)lists;
-    uint32_t* list[2] = {lists + sizeof(LgCounters) / 4, lists + sizeof(LgCounters) / 4 + max_n};
-
-    const bool log = ctxOptOn(ctx, "MCRT_LIGHT_GROUPS_LOG");
-    auto clock_ms = [] { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-    auto search = [&](uint64_t count, const AovRays& rays_, double& ms) {
-        if (!log) return intersectDeviceArrays(ctx, count, rays_.start, rays_.direction, rays_.t, rays_.surface, rays_.uv);
-        (void)hipStreamSynchronize(stream);
-        const double t0 = clock_ms();
-        const int rc = intersectDeviceArrays(ctx, count, rays_.start, rays_.direction, rays_.t, rays_.surface, rays_.uv);
-        ms += clock_ms() - t0;
-        return rc;
-    };
-    double chunk_t0 = log ? clock_ms() : 0.0;  // (a chunk's clock starts where the one before it ended: the stream is drained there)
-    return runChunks(ctx, cp, timer, cam, global_seed, plan, st.ray, stats, [&](const AovChunk& c, uint32_t& launches, uint64_t& rays) {
-        const uint64_t n = (uint64_t)c.pixels * c.spp;
-        double search_ms = log ? clock_ms() - chunk_t0 : 0.0;  // the camera rays and their search
-        std::string curve;
-        MCRT_HIP_TRY(ctx, hipMemsetAsync(counters, 0, sizeof(LgCounters), stream));
-        MCRT_HIP_TRY(ctx, (hipError_t)launchLightGroupsBegin(stream, st, n, scene.sh.scene_ior, par, list[0], counters));
-        LgCounters now;
-        MCRT_HIP_TRY(ctx, hipMemcpyAsync(&now, counters, sizeof(now), hipMemcpyDeviceToHost, stream));
-        MCRT_HIP_TRY(ctx, hipStreamSynchronize(stream));
-        launches++;
-        uint32_t live = now.live[0];
-        for (uint32_t k = 0; live != 0u; k++) {
-            if (k >= kLgMaxIterations)
-                return ctxFail(ctx, MCRT_ERR_UNSUPPORTED, std::string(what) + ": " + std::to_string(live) + " paths are still alive after " +
-                                                              std::to_string(kLgMaxIterations) + " iterations (max_depth cuts them)");
-            const uint32_t cur = k & 1u, next = cur ^ 1u;
-            if (log) curve += (k ? "," : "") + std::to_string(live);
-            const bool last = r.max_depth != 0u && k == r.max_depth;
-            if (!last) {
-                MCRT_HIP_TRY(ctx, (hipError_t)launchLightGroupsRays(stream, c, scene, sobol_tab, st, list[cur], live, k, lit, counters, next));
-                if (int rc = search(2ull * live, lit, search_ms)) return rc;
-                launches += 2;
-                rays += 2ull * live;
-            }
-            if (last) MCRT_HIP_TRY(ctx, hipMemsetAsync(&counters->live[next], 0, 4, stream));  // (otherwise the ray kernel did)
-            MCRT_HIP_TRY(ctx, (hipError_t)launchLightGroupsStep(stream, c, scene, sobol_tab, st, par, list[cur], live, k, last, lit, list[next], counters, next));
-            launches++;
-            MCRT_HIP_TRY(ctx, hipMemcpyAsync(&now, counters, sizeof(now), hipMemcpyDeviceToHost, stream));
-            MCRT_HIP_TRY(ctx, hipStreamSynchronize(stream));
-            if (now.too_deep)
-                return ctxFail(ctx, MCRT_ERR_UNSUPPORTED, std::string(what) + ": a path nests more than " + std::to_string(kMaxIors) +
-                                                              " dielectric media (mcrt_render renders such frames through the pipeline's deep rows; this pass does not)");
-            if (now.live[next] > live) return ctxFail(ctx, MCRT_ERR_HIP, std::string(what) + ": the live list grew");  // (cannot happen: a sample is appended once)
-            live = now.live[next];
-        }
-        MCRT_HIP_TRY(ctx, (hipError_t)launchLightGroupsResolve(stream, c, st, r.planes, d_planes, total_pixels));
-        launches++;
-        if (log) {
-            (void)hipStreamSynchronize(stream);
-            const double now_ms = clock_ms();
-            std::fprintf(stderr, "{\"light_groups_chunk\":%llu,\"samples\":%llu,\"live\":[%s],\"chunk_ms\":%.3f,\"search_ms\":%.3f}\n",
-                         (unsigned long long)c.first_pixel, (unsigned long long)n, curve.c_str(), now_ms - chunk_t0, search_ms);
-            chunk_t0 = now_ms;
-        }
-        return (int)MCRT_OK;
-    });
+    return runLivePaths(
+        ctx, what, cp, timer, cam, global_seed, plan, st.ray, stats, sc, r.max_depth, ctxOptOn(ctx, "MCRT_LIGHT_GROUPS_LOG"), "light_groups_chunk",
+        [&](const AovChunk&, uint64_t n, uint32_t* list, LgCounters* counters) { return launchLightGroupsBegin(stream, st, n, scene.sh.scene_ior, par, list, counters); },
+        [&](const AovChunk& c, const uint32_t* list, uint32_t live, uint32_t k, const AovRays& lit, LgCounters* counters, uint32_t next) {
+            return launchLightGroupsRays(stream, c, scene, sobol_tab, st, list, live, k, lit, counters, next);
+        },
+        [&](const AovChunk& c, const uint32_t* list, uint32_t live, uint32_t k, bool last, const AovRays& lit, uint32_t* next_list, LgCounters* counters, uint32_t next) {
+            return launchLightGroupsStep(stream, c, scene, sobol_tab, st, par, list, live, k, last, lit, next_list, counters, next);
+        },
+        [&](const AovChunk& c) { return launchLightGroupsResolve(stream, c, st, r.planes, d_planes, total_pixels); });
 }
 
 extern "C" int mcrt_render_light_groups(mcrt_ctx* ctx, const mcrt_camera_desc* cam, uint32_t global_seed, const mcrt_light_group_params* params, double* planes,

@@ -10,6 +10,7 @@
 //               [--matte PREFIX [--matte-key material|surface] [--matte-ranks N]] [--compare REF [--compare-layer PREFIX]]
 //               [--occlusion PREFIX [--occlusion-rays N] [--occlusion-distance D]] [--lighting PREFIX]
 //               [--light-groups PREFIX [--light-groups-by material|light|one] [--light-groups-depth D]]
+//               [--path-classes PREFIX [--path-classes-depth D]]
 //
 // Writes the frame as raw FP64 RGB, row-major (what Image::operator() holds, camera/image.cpp:53-56),
 // and prints the statistics. --tga also develops it the way Image::save does (auto exposure / gain, tone map, sRGB bytes:
@@ -65,6 +66,11 @@
 // per group of emitters and one for the sky, PREFIX.<name>.f64 ([height][width][3] FP64) and, with --exr, lightgroup.<name>.R/G/B (HALF).
 // --light-groups-by material (default): a group per emissive material, named material<index>; light: a group per emitter surface,
 // light<index>; one: every emitter in one group, lights. --light-groups-depth D cuts the paths (1 = direct light only; default 0 = whole).
+// --path-classes also writes the path classes of the same camera and seed (mcrt_render_path_classes, device 0; path tracer only): the frame
+// split by what the first surface did with the light, eight planes - emission, background, diffuse_direct, diffuse_indirect, glossy_direct,
+// glossy_indirect, transmission_direct, transmission_indirect - as PREFIX.<name>.f64 ([height][width][3] FP64) and, with --exr,
+// pathclass.<name>.R/G/B (HALF; the file then carries OpenEXR's long-names bit: pathclass.transmission_indirect.R is 33 bytes).
+// --path-classes-depth D cuts the paths (1 = no indirect light; default 0 = whole).
 // --devices renders the frame on several GPUs from this one process (mcrt_render_multi: one host thread per GPU).
 #include <cstdio>
 #include <cstdlib>
@@ -94,8 +100,8 @@ int main(int argc, char** argv) {
     image.plain = (uint32_t)mcrt_image_param(img, "image_plain");
     image.exposure_compensation = from_bits(mcrt_image_param(img, "image_exposure_ev_bits"));
     image.gain_compensation = from_bits(mcrt_image_param(img, "image_gain_ev_bits"));
-    std::string tga, aov, denoise, dvar, dvar_out, ddual, ddual_out, pstats, robust, exr, matte, compare, compare_layer, occlusion, lighting, light_groups, light_groups_by = "material";
-    uint32_t light_groups_depth = 0;
+    std::string tga, aov, denoise, dvar, dvar_out, ddual, ddual_out, pstats, robust, exr, matte, compare, compare_layer, occlusion, lighting, light_groups, light_groups_by = "material", path_classes;
+    uint32_t light_groups_depth = 0, path_classes_depth = 0;
     mcrt_occlusion_params oparams{};
     bool compare_exr = false;
     mcrt_matte_params mparams{};
@@ -153,6 +159,8 @@ int main(int argc, char** argv) {
         else if (k == "--light-groups" && i + 1 < argc) light_groups = argv[++i];
         else if (k == "--light-groups-by" && i + 1 < argc) light_groups_by = argv[++i];
         else if (k == "--light-groups-depth" && i + 1 < argc) light_groups_depth = (uint32_t)std::strtoul(argv[++i], nullptr, 10);
+        else if (k == "--path-classes" && i + 1 < argc) path_classes = argv[++i];
+        else if (k == "--path-classes-depth" && i + 1 < argc) path_classes_depth = (uint32_t)std::strtoul(argv[++i], nullptr, 10);
         else if (k == "--occlusion-rays") oparams.rays = (uint32_t)val();
         else if (k == "--occlusion-distance" && i + 1 < argc) oparams.max_distance = std::strtod(argv[++i], nullptr);
         else if (k == "--compare-layer" && i + 1 < argc) compare_layer = argv[++i];
@@ -753,6 +761,48 @@ int main(int argc, char** argv) {
         std::printf("{\"light_groups\":\"%s\",\"by\":\"%s\",\"max_depth\":%u,\"means\":{%s},\"rays\":%llu,\"kernel_ms\":%.3f,\"total_ms\":%.3f,\"Mray_s\":%.1f}\n",
                     light_groups.c_str(), light_groups_by.c_str(), light_groups_depth, means.c_str(), (unsigned long long)gst.rays, gst.kernel_ms, gst.total_ms,
                     gst.rays / gst.kernel_ms / 1e3);
+    }
+    if (!path_classes.empty()) {
+        if (photon) {
+            std::fprintf(stderr, "--path-classes: the path classes are the path tracer's (not with --photon)\n");
+            return 1;
+        }
+        const char* const names[MCRT_PATH_CLASSES] = {"emission",      "background",      "diffuse_direct",      "diffuse_indirect",
+                                                      "glossy_direct", "glossy_indirect", "transmission_direct", "transmission_indirect"};
+        mcrt_path_class_params pp{};
+        pp.max_depth = path_classes_depth;
+        const size_t px = (size_t)cam.width * cam.height;
+        std::vector<double> planes(MCRT_PATH_CLASSES * px * 3);
+        mcrt_stats pst;
+        rc = mcrt_render_path_classes(ctx, &cam, seed, &pp, planes.data(), &pst);
+        if (rc != MCRT_OK) {
+            std::fprintf(stderr, "mcrt error %d: %s\n", rc, mcrt_last_error(ctx));
+            return 1;
+        }
+        std::string means;
+        for (size_t p = 0; p < MCRT_PATH_CLASSES; p++) {
+            const double* plane = planes.data() + p * px * 3;
+            const std::string path = path_classes + "." + names[p] + ".f64";
+            FILE* o = std::fopen(path.c_str(), "wb");
+            const bool ok = o && std::fwrite(plane, 1, px * 24, o) == px * 24;
+            if (o) std::fclose(o);
+            if (!ok) {
+                std::fprintf(stderr, "cannot write %s\n", path.c_str());
+                return 1;
+            }
+            double mean = 0.0;
+            for (size_t w = 0; w < px * 3; w++) mean += plane[w];
+            char text[96];
+            std::snprintf(text, sizeof text, "%s\"%s\":%.6g", p ? "," : "", names[p], px ? mean / (double)(px * 3) : 0.0);
+            means += text;
+            if (!exr.empty()) {
+                std::vector<double> copy(plane, plane + px * 3);
+                exr_layer(std::string("pathclass.") + names[p], "RGB", exr_keep(copy), MCRT_EXR_HALF);
+            }
+        }
+        eparams.flags |= MCRT_EXR_LONG_NAMES;  // (pathclass.transmission_indirect.R is 33 bytes)
+        std::printf("{\"path_classes\":\"%s\",\"max_depth\":%u,\"means\":{%s},\"rays\":%llu,\"kernel_ms\":%.3f,\"total_ms\":%.3f,\"Mray_s\":%.1f}\n", path_classes.c_str(),
+                    path_classes_depth, means.c_str(), (unsigned long long)pst.rays, pst.kernel_ms, pst.total_ms, pst.rays / pst.kernel_ms / 1e3);
     }
     if (!exr.empty()) {
         const std::string a_spp = std::to_string(spp), a_seed = std::to_string(seed), a_kernel = std::to_string(st.kernel_id);

@@ -1,0 +1,440 @@
+"""Path classes, CPU tier: csrc/mcrt_path_classes.hpp - the text the kernels of csrc/mcrt_path_classes.hip run - driven on the host
+(tests/emu/path_classes_emu.cpp: chunks, iterations and live lists as mcrt_render_path_classes_device drives them) against the
+reference's own arithmetic: the oracle's path-traced frame (oracle_lib.render).
+
+1. One plane is the path tracer: with all eight classes in plane 0 the plane is the oracle's frame BIT FOR BIT at sqrtspp 1 and 2 - on
+   the twelve constructed scenes of test_lighting_emulation and on the four scene images of test_aov_emulation.SCENES.
+2. The default map: eight planes, each finite and >= 0, which add up to the oracle's frame.
+3. Three lobes of pure colours (built here): a floor whose diffuse reflectance is red only, whose specular reflectance is green only and
+   whose transmittance is blue only, under a white lamp and the sky, beside a white wall. A sample that took another lobe contributes
+   +0.0 to a lobe's channel, so the diffuse planes have exactly zero green and blue (and so on), and a lobe's merged plane carries the
+   oracle's bits in its channel: x + 0.0 keeps x's bits, the other operands and their order are the path tracer's.
+   Which field a lobe multiplies (mcrt_shade.hpp interactionBSDFLocal): reflect brdf_s * F = specular_reflectance / |wi.z| * F, refract
+   btdf * T * (1 - F) with btdf = transmittance / |wi.z| from outside, diffuse brdf_d * (1 - F) * (1 - T) = reflectance / pi * ...
+   The floor carries MCRT_MAT_DIRAC_DELTA: sampleDirect (integrator.cpp:31-86) does not look at the lobe selectType chose - on a
+   material without that flag it evaluates the BSDF for a non-Dirac direction, which on a smooth material is the DIFFUSE term, whatever
+   ia.type is. By the header's definition that term belongs to the class of the lobe chosen, so on such a floor the glossy and
+   transmission DIRECT planes carry red: the reference's own estimator, not a misclassification. The second tricolour test pins that
+   down on the same floor without the flag. With the flag no light sample is taken, and every term of a path carries its lobe's colour.
+4. Zeros that the materials force on the constructed scenes, over the pixels whose every sample meets the floor first.
+5. Promises 3 and 4 of the header; emission, background and the merged direct planes against the lighting passes at D = 1.
+6. Chunks, shards and the order of the live lists do not reach the bits.
+7. Refusals; a camera that sees only sky.
+
+Frames are 70 x 13 pixels (width no multiple of 64, 910 pixels no multiple of 256) at sqrtspp 1 and 2.
+
+Bounds: bit equality where the header promises it; where planes are added up in another order than the path tracer adds its terms,
+conftest.rel_error <= 1e-12, include/mcrt.h's bound for sums of non-negative terms taken in another order."""
+import ctypes as C
+import functools
+import importlib
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+import test_aov_emulation as aov
+import test_lighting_emulation as lit
+from conftest import ROOT, TESTS, rel_error
+
+WIDTH, HEIGHT, SEED, SCENES = lit.WIDTH, lit.HEIGHT, lit.SEED, lit.SCENES
+PIXELS = WIDTH * HEIGHT
+NO_SURFACE = 0xFFFFFFFF
+EMISSION, BACKGROUND, DIFFUSE_DIRECT, DIFFUSE_INDIRECT, GLOSSY_DIRECT, GLOSSY_INDIRECT, TRANSMISSION_DIRECT, TRANSMISSION_INDIRECT = range(8)
+LOBES = {"diffuse": (DIFFUSE_DIRECT, DIFFUSE_INDIRECT), "glossy": (GLOSSY_DIRECT, GLOSSY_INDIRECT), "transmission": (TRANSMISSION_DIRECT, TRANSMISSION_INDIRECT)}
+ONE = (0,) * 8
+MERGED_LOBES = (0, 1, 2, 2, 3, 3, 4, 4)   # path_class_map("lobes")
+MERGED_DIRECT = (0, 1, 2, 3, 2, 4, 2, 5)  # the three direct planes in plane 2
+
+
+def load_path_classes_emu():
+    """Host build of the path classes (tests/emu/path_classes_emu.cpp = mcrt_emu.cpp + csrc/mcrt_path_classes.hpp), the way
+    test_light_groups_emulation.load_light_groups_emu builds its library."""
+    src = os.path.join(TESTS, "emu", "path_classes_emu.cpp")
+    out = os.path.join(TESTS, "emu", "_build", "libpath_classes_emu.so")
+    csrc = os.path.join(ROOT, "monte-carlo-ray-tracer_amd", "csrc")
+    deps = [src, os.path.join(TESTS, "emu", "mcrt_emu.cpp"), os.path.join(ROOT, "include", "mcrt.h")] + [os.path.join(csrc, f) for f in os.listdir(csrc) if f.endswith(".hpp")]
+    if not os.path.exists(out) or any(os.path.getmtime(d) > os.path.getmtime(out) for d in deps):
+        os.makedirs(os.path.dirname(out), exist_ok=True)
+        tmp = "%s.%d.tmp" % (out, os.getpid())
+        subprocess.check_call(["g++", "-std=c++17", "-O2", "-ffp-contract=off", "-fPIC", "-shared", "-o", tmp, src])
+        os.replace(tmp, out)
+    L = C.CDLL(out)
+    vp = C.c_void_p
+    L.path_classes_emu_rows.argtypes = [vp]
+    L.path_classes_emu_rows.restype = C.c_uint32
+    L.path_classes_emu_first_hits.argtypes = [vp, vp, C.c_uint32, C.c_int, vp]
+    L.path_classes_emu_frame.argtypes = [vp, vp, C.c_uint32, C.c_int, C.c_uint64, vp, C.c_int, vp, vp]
+    return L
+
+
+@functools.lru_cache(maxsize=None)
+def _emu():
+    return load_path_classes_emu()
+
+
+def _pkg():
+    return importlib.import_module("monte-carlo-ray-tracer_amd")
+
+
+def emu_planes(scene_desc, cam, flavour, class_plane=None, max_depth=0, chunk_rays=0, order=0, expect=0):
+    """The emulation's planes over the camera's packed owned rows: ([P, pixels, 3], info dict). The array is filled with 0xAB bytes
+    first (whatever is not written shows). expect: the status the call must return."""
+    L = _emu()
+    par = _pkg().Context._path_class_params(class_plane, max_depth)
+    planes = 8 if class_plane is None else min(max(class_plane) + 1, 8)
+    pixels = L.path_classes_emu_rows(C.byref(cam)) * cam.width
+    out = np.empty((planes, pixels, 3))
+    out.view(np.uint8).fill(0xAB)
+    info = np.zeros(3, dtype=np.uint64)
+    rc = L.path_classes_emu_frame(C.byref(scene_desc), C.byref(cam), SEED, flavour, chunk_rays, C.byref(par), order, out.ctypes.data, info.ctypes.data)
+    assert rc == expect, "path_classes_emu_frame: %d" % rc
+    return out, dict(rays=int(info[0]), iterations=int(info[1]), live=int(info[2]))
+
+
+def first_hits(scene_desc, cam, flavour):
+    """[pixels, spp] the surface every camera sample meets first."""
+    L = _emu()
+    surf = np.empty((L.path_classes_emu_rows(C.byref(cam)) * cam.width, cam.sqrtspp * cam.sqrtspp), dtype=np.uint32)
+    assert L.path_classes_emu_first_hits(C.byref(scene_desc), C.byref(cam), SEED, flavour, surf.ctypes.data) == 0
+    return surf
+
+
+def floor_first(scene_desc, cam, flavour):
+    """[pixels] bool: every sample of the pixel meets a surface of material 0 (the floor) first."""
+    surf = first_hits(scene_desc, cam, flavour)
+    material = np.ctypeslib.as_array(scene_desc.surf_material, shape=(int(scene_desc.num_surfaces),))
+    hit = surf != NO_SURFACE
+    on_floor = np.zeros(surf.shape, dtype=bool)
+    on_floor[hit] = material[surf[hit]] == 0
+    return on_floor.all(axis=1)
+
+
+def constructed_flavour(bvh):
+    return 3 if bvh else 1  # (test_lighting_emulation.constructed_case's)
+
+
+@functools.lru_cache(maxsize=None)
+def constructed_planes(floor, bvh, sqrtspp, class_plane=None, max_depth=0):
+    """A constructed scene's planes, computed once (the GPU tests compare with them): ([P, PIXELS, 3], info)."""
+    return emu_planes(lit.constructed(floor, bvh).scene, lit.constructed_camera(sqrtspp), constructed_flavour(bvh), class_plane, max_depth)
+
+
+@functools.lru_cache(maxsize=None)
+def image_planes(scene, sqrtspp, class_plane=None, max_depth=0):
+    return emu_planes(aov._image(scene).scene, aov.camera(scene, sqrtspp), SCENES[scene], class_plane, max_depth)
+
+
+@functools.lru_cache(maxsize=None)
+def image_oracle(scene, sqrtspp):
+    import oracle_lib
+    frame, _ = oracle_lib.render(aov._image(scene), aov.camera(scene, sqrtspp), SEED, _pkg().INTEGRATOR_PATH_TRACER)
+    return frame.reshape(PIXELS, 3)
+
+
+def assert_is_the_frame(plane, ref, what):
+    """plane == ref bit for bit in every word where ref is neither negative nor NaN (include/mcrt.h "Path classes", promise 2)."""
+    comparable = ~(np.isnan(ref) | (ref < 0.0))
+    differ = (plane.view(np.uint64) != ref.view(np.uint64)) & comparable
+    print("%s: %d of %d words differ from the path tracer's bits (%d not comparable)" % (what, differ.sum(), ref.size, (~comparable).sum()))
+    for q in np.nonzero(differ.any(axis=1))[0][:5]:
+        print("   pixel %d: plane %r, path tracer %r" % (q, plane[q], ref[q]))
+    assert comparable.sum() > ref.size // 2, what
+    assert not differ.any(), what
+
+
+def assert_planes_add_up(planes, ref, what):
+    assert planes.shape == (8, PIXELS, 3) and np.isfinite(planes).all() and (planes >= 0.0).all(), what
+    comparable = ~(np.isnan(ref) | (ref < 0.0)).any(axis=1)
+    err = rel_error(planes.sum(axis=0)[comparable], ref[comparable]).max()
+    print("%s: the eight planes against the oracle: max rel error %.3e; shares %s" % (what, err, ["%.3f" % (p.sum() / max(planes.sum(), 1e-300)) for p in planes]))
+    assert err <= 1e-12, what
+
+
+def zero_bits(a):
+    return (np.ascontiguousarray(a).view(np.uint64) == 0).all()
+
+
+# ------------------------------------------------------------------ three lobes of pure colours
+class TricolourScene:
+    """test_lighting_emulation's constructed floor (8 x 8 at y = 0) with all three lobes - not opaque, ior 1.5, transparency 0.5, diffuse
+    reflectance red, specular reflectance green, transmittance blue -, a white lamp (surfaces 2, 3: 1 x 1 at y = 3, facing down) and a
+    white diffuse wall (4, 5: the plane x = -3 from the floor to y = 6, which gives the paths a third vertex), under the sky.
+    Materials 0 floor, 1 lamp, 2 wall. dirac: the floor carries MCRT_MAT_DIRAC_DELTA (the module's docstring says why)."""
+
+    def __init__(self, pkg, dirac):
+        tris = lit._quad(0.0, -4.0, 4.0, -4.0, 4.0, True) + lit._quad(3.0, 1.5, 2.5, -0.5, 0.5, False)
+        a, b, c, d = (-3.0, 0.0, -4.0), (-3.0, 6.0, -4.0), (-3.0, 6.0, 4.0), (-3.0, 0.0, 4.0)
+        tris += [(a, b, c), (a, c, d)]  # (its side does not matter: opaque)
+        n = len(tris)
+        v = np.array(tris, dtype=np.float64).reshape(n, 9)
+        e1, e2 = v[:, 3:6] - v[:, 0:3], v[:, 6:9] - v[:, 0:3]
+        cross = np.cross(e1, e2)
+        length = np.sqrt((cross * cross).sum(axis=1))
+        e = np.concatenate([e1, e2, cross / length[:, None]], axis=1)
+        mats = (pkg.Material * 3)(lit._material(pkg, flags=lit.DIRAC_DELTA if dirac else 0, ior=1.5, transparency=0.5, reflectance=(0.8, 0.0, 0.0),
+                                                specular_reflectance=(0.0, 0.9, 0.0), transmittance=(0.0, 0.0, 0.7)),
+                                  lit._material(pkg, flags=lit.OPAQUE | lit.EMISSIVE, emittance=(30.0, 30.0, 30.0), reflectance=(0.0, 0.0, 0.0), specular_reflectance=(0.0, 0.0, 0.0)),
+                                  lit._material(pkg, flags=lit.OPAQUE, ior=-1.0, reflectance=(0.9, 0.9, 0.9)))
+        self.keep = [mats]
+
+        def arr(a, ctype):
+            a = np.ascontiguousarray(a)
+            self.keep.append(a)
+            return a.ctypes.data_as(C.POINTER(ctype))
+
+        desc = pkg.SceneDesc()
+        desc.abi_version = pkg.ABI_VERSION
+        desc.num_nodes = 0
+        desc.num_surfaces = n
+        desc.surf_kind = arr(np.zeros(n, dtype=np.uint8), C.c_uint8)
+        desc.surf_interpolate = arr(np.zeros(n, dtype=np.uint8), C.c_uint8)
+        desc.surf_material = arr(np.array([0, 0, 1, 1, 2, 2], dtype=np.uint32), C.c_uint32)
+        desc.surf_area = arr(0.5 * length, C.c_double)
+        desc.surf_v = arr(v, C.c_double)
+        desc.surf_e = arr(e, C.c_double)
+        desc.num_materials = 3
+        desc.materials = C.cast(mats, C.POINTER(pkg.Material))
+        desc.num_lights = 2
+        desc.light_surface = arr(np.array([2, 3], dtype=np.uint32), C.c_uint32)
+        desc.light_cdf = arr(np.array([0.5, 1.0]), C.c_double)
+        desc.scene_ior = 1.0
+        desc.bb_min = (C.c_double * 3)(*v.reshape(-1, 3).min(axis=0))
+        desc.bb_max = (C.c_double * 3)(*v.reshape(-1, 3).max(axis=0))
+        self.scene = desc
+
+    def photons(self, which):
+        return None
+
+    def param(self, key):
+        return 0
+
+
+@functools.lru_cache(maxsize=None)
+def tricolour(dirac=True):
+    pkg = _pkg()
+    pkg.lib()
+    return TricolourScene(pkg, dirac)
+
+
+@functools.lru_cache(maxsize=None)
+def tricolour_planes(sqrtspp, class_plane=None, max_depth=0, dirac=True):
+    return emu_planes(tricolour(dirac).scene, lit.constructed_camera(sqrtspp), 1, class_plane, max_depth)
+
+
+@functools.lru_cache(maxsize=None)
+def tricolour_oracle(sqrtspp, dirac=True):
+    import oracle_lib
+    frame, _ = oracle_lib.render(tricolour(dirac), lit.constructed_camera(sqrtspp), SEED, _pkg().INTEGRATOR_PATH_TRACER)
+    return frame.reshape(PIXELS, 3)
+
+
+# ------------------------------------------------------------------ 1. one plane is the path tracer
+@pytest.mark.parametrize("sqrtspp", [1, 2])
+@pytest.mark.parametrize("floor,bvh", lit.CONSTRUCTED)
+def test_one_plane_is_the_path_tracer_on_the_constructed_scenes(floor, bvh, sqrtspp, oracle):
+    planes, info = constructed_planes(floor, bvh, sqrtspp, ONE)
+    assert planes.shape == (1, PIXELS, 3)
+    assert_is_the_frame(planes[0], lit.constructed_oracle(floor, bvh, sqrtspp), "%s floor, bvh %s, sqrtspp %d" % (floor, bvh, sqrtspp))
+    assert info["iterations"] <= 3  # (the paths end by their second vertex; the iteration after it only finds the miss)
+
+
+@pytest.mark.parametrize("sqrtspp", [1, 2])
+@pytest.mark.parametrize("scene", list(SCENES))
+def test_one_plane_is_the_path_tracer_on_the_scene_images(scene, sqrtspp, oracle):
+    planes, info = image_planes(scene, sqrtspp, ONE)
+    samples = PIXELS * sqrtspp * sqrtspp
+    print("%s sqrtspp %d: %d iterations, %.2f rays a path, %.2f live iterations a path" % (scene, sqrtspp, info["iterations"], info["rays"] / samples, info["live"] / samples))
+    assert_is_the_frame(planes[0], image_oracle(scene, sqrtspp), "%s sqrtspp %d" % (scene, sqrtspp))
+    assert info["rays"] == samples + 2 * info["live"] and info["iterations"] > 3
+
+
+# ------------------------------------------------------------------ 2. the default map
+@pytest.mark.parametrize("sqrtspp", [1, 2])
+@pytest.mark.parametrize("floor,bvh", lit.CONSTRUCTED)
+def test_eight_planes_add_up_on_the_constructed_scenes(floor, bvh, sqrtspp, oracle):
+    planes, info = constructed_planes(floor, bvh, sqrtspp)
+    assert_planes_add_up(planes, lit.constructed_oracle(floor, bvh, sqrtspp), "%s floor, bvh %s, sqrtspp %d" % (floor, bvh, sqrtspp))
+    assert info == constructed_planes(floor, bvh, sqrtspp, ONE)[1]  # (the walk does not depend on the map)
+
+
+@pytest.mark.parametrize("sqrtspp", [1, 2])
+@pytest.mark.parametrize("scene", list(SCENES))
+def test_eight_planes_add_up_on_the_scene_images(scene, sqrtspp, oracle):
+    planes, info = image_planes(scene, sqrtspp)
+    assert_planes_add_up(planes, image_oracle(scene, sqrtspp), "%s sqrtspp %d" % (scene, sqrtspp))
+    assert info == image_planes(scene, sqrtspp, ONE)[1]
+    assert sum((p > 0).any() for p in planes) >= 4  # (every image has diffuse light of both kinds and more)
+
+
+# ------------------------------------------------------------------ 3. three lobes of pure colours
+@pytest.mark.parametrize("sqrtspp", [1, 2])
+def test_three_lobes_of_pure_colours_stay_apart_and_carry_the_oracles_bits(sqrtspp, oracle):
+    s, cam = tricolour(), lit.constructed_camera(sqrtspp)
+    (planes, info), ref = tricolour_planes(sqrtspp), tricolour_oracle(sqrtspp)
+    assert planes.shape == (8, PIXELS, 3) and np.isfinite(planes).all() and (planes >= 0.0).all()
+    floor = floor_first(s.scene, cam, 1)
+    print("sqrtspp %d: %d iterations, %d of %d pixels meet the floor first with every sample" % (sqrtspp, info["iterations"], floor.sum(), PIXELS))
+    assert floor.sum() > PIXELS // 4
+    on = planes[:, floor]
+    for lobe, channel in (("diffuse", 0), ("glossy", 1), ("transmission", 2)):
+        others = [c for c in range(3) if c != channel]
+        for p in LOBES[lobe]:
+            assert zero_bits(on[p][:, others]), (lobe, p)  # +0.0, every word
+        assert (on[LOBES[lobe][0]][:, channel] > 0.0).any(), lobe
+        print("   %s: direct sum %.6g, indirect sum %.6g" % (lobe, on[LOBES[lobe][0]].sum(), on[LOBES[lobe][1]].sum()))
+    assert (on[DIFFUSE_INDIRECT][:, 0] > 0.0).any()  # (the wall: light that reaches the floor's diffuse bounce after one more vertex)
+    assert zero_bits(on[EMISSION]) and zero_bits(on[BACKGROUND])
+    merged, _ = tricolour_planes(sqrtspp, MERGED_LOBES)
+    assert merged.shape == (5, PIXELS, 3)
+    for plane, channel, lobe in ((2, 0, "diffuse"), (3, 1, "glossy"), (4, 2, "transmission")):
+        got, want = np.ascontiguousarray(merged[plane][floor, channel]), np.ascontiguousarray(ref[floor, channel])
+        differ = got.view(np.uint64) != want.view(np.uint64)
+        print("   %s plane, channel %d: %d of %d words differ from the oracle's bits" % (lobe, channel, differ.sum(), differ.size))
+        assert not differ.any(), lobe
+    assert_planes_add_up(planes, ref, "tricolour sqrtspp %d" % sqrtspp)
+
+
+@pytest.mark.parametrize("sqrtspp", [1, 2])
+def test_without_the_dirac_flag_the_light_sample_is_diffuse_whatever_the_lobe(sqrtspp, oracle):
+    """The same floor as a scene file would give it (transparency 0.5: no MCRT_MAT_DIRAC_DELTA). sampleDirect is then taken at every first
+    vertex, with the diffuse term of the BSDF, whichever lobe selectType chose: the glossy and transmission DIRECT planes carry red and
+    nothing else beside their own colour; the indirect planes and everything green or blue stay as pure as with the flag; the three
+    lobes' red add up to the oracle's, green and blue are the oracle's bits."""
+    s, cam = tricolour(False), lit.constructed_camera(sqrtspp)
+    (planes, _), ref = tricolour_planes(sqrtspp, dirac=False), tricolour_oracle(sqrtspp, dirac=False)
+    floor = floor_first(s.scene, cam, 1)
+    on = planes[:, floor]
+    assert zero_bits(on[DIFFUSE_DIRECT][:, 1:]) and zero_bits(on[DIFFUSE_INDIRECT][:, 1:])
+    assert zero_bits(on[GLOSSY_DIRECT][:, 2]) and zero_bits(on[GLOSSY_INDIRECT][:, (0, 2)])
+    assert zero_bits(on[TRANSMISSION_DIRECT][:, 1]) and zero_bits(on[TRANSMISSION_INDIRECT][:, :2])
+    assert (on[GLOSSY_DIRECT][:, 0] > 0.0).any() and (on[TRANSMISSION_DIRECT][:, 0] > 0.0).any()  # the lamp's light sample, red
+    merged, _ = tricolour_planes(sqrtspp, MERGED_LOBES, dirac=False)
+    assert np.ascontiguousarray(merged[3][floor, 1]).tobytes() == np.ascontiguousarray(ref[floor, 1]).tobytes()
+    assert np.ascontiguousarray(merged[4][floor, 2]).tobytes() == np.ascontiguousarray(ref[floor, 2]).tobytes()
+    red = (merged[2] + merged[3] + merged[4])[floor, 0]
+    assert rel_error(red, ref[floor, 0]).max() <= 1e-12
+    assert_planes_add_up(planes, ref, "tricolour without the flag, sqrtspp %d" % sqrtspp)
+
+
+# ------------------------------------------------------------------ 4. zeros that the materials force
+ZERO_LOBES = {"oren_nayar": ("glossy", "transmission"), "mirror": ("diffuse", "transmission"), "conductor": ("diffuse", "transmission"), "glass": ("diffuse",),
+              "lambertian": ("transmission",), "ggx": ("transmission",)}
+
+
+@pytest.mark.parametrize("floor,bvh", lit.CONSTRUCTED)
+def test_lobes_a_material_does_not_have_are_zero_bits(floor, bvh):
+    for sqrtspp in (1, 2):
+        planes, _ = constructed_planes(floor, bvh, sqrtspp)
+        on = planes[:, floor_first(lit.constructed(floor, bvh).scene, lit.constructed_camera(sqrtspp), constructed_flavour(bvh))]
+        assert on.shape[1] > PIXELS // 4
+        for lobe, (direct, indirect) in LOBES.items():
+            if lobe in ZERO_LOBES[floor]:
+                assert zero_bits(on[direct]) and zero_bits(on[indirect]), (floor, lobe, sqrtspp)
+            else:
+                assert (on[direct] > 0.0).any(), (floor, lobe, sqrtspp)
+        assert zero_bits(on[EMISSION]) and zero_bits(on[BACKGROUND])
+        if sqrtspp == 1:  # one sample took one lobe
+            lit_lobes = sum(((on[d] > 0.0) | (on[i] > 0.0)).any(axis=1).astype(int) for d, i in LOBES.values())
+            assert lit_lobes.max() == 1, floor
+
+
+# ------------------------------------------------------------------ 5. promises 3 and 4
+def test_a_plane_does_not_depend_on_how_the_other_classes_are_mapped():
+    for (apart, _), planes_of in ((image_planes("coffee_maker_qsah", 2), lambda m: image_planes("coffee_maker_qsah", 2, m)[0]),
+                                  (tricolour_planes(2), lambda m: tricolour_planes(2, m)[0])):
+        lobes = planes_of(MERGED_LOBES)
+        assert lobes[0].tobytes() == apart[EMISSION].tobytes() and lobes[1].tobytes() == apart[BACKGROUND].tobytes()
+        direct = planes_of(MERGED_DIRECT)
+        for plane, cls in ((0, EMISSION), (1, BACKGROUND), (3, DIFFUSE_INDIRECT), (4, GLOSSY_INDIRECT), (5, TRANSMISSION_INDIRECT)):
+            assert direct[plane].tobytes() == apart[cls].tobytes(), cls
+        far = planes_of((7, 7, 7, 7, 7, 7, 7, 3))  # transmission_indirect alone in plane 3, the rest in 7, planes without a class between
+        assert far.shape[0] == 8 and far[3].tobytes() == apart[TRANSMISSION_INDIRECT].tobytes()
+        assert all(zero_bits(far[p]) for p in (0, 1, 2, 4, 5, 6))
+        swapped = planes_of((7, 6, 5, 4, 3, 2, 1, 0))
+        for cls in range(8):
+            assert swapped[7 - cls].tobytes() == apart[cls].tobytes(), cls
+
+
+@pytest.mark.parametrize("scene", list(SCENES) + ["tricolour"])
+def test_depth_cuts_leave_the_direct_planes_alone_and_depth_one_has_no_indirect_light(scene):
+    planes_of = (lambda d: tricolour_planes(1, None, d)) if scene == "tricolour" else (lambda d: image_planes(scene, 1, None, d))
+    (full, _), (one, info), (two, _) = planes_of(0), planes_of(1), planes_of(2)
+    assert info["iterations"] == 2 and PIXELS < info["rays"] <= 3 * PIXELS  # (only iteration 0 traces, for the samples that hit)
+    for cls in (EMISSION, BACKGROUND, DIFFUSE_DIRECT, GLOSSY_DIRECT, TRANSMISSION_DIRECT):
+        assert one[cls].tobytes() == full[cls].tobytes() and two[cls].tobytes() == full[cls].tobytes(), cls
+    for cls in (DIFFUSE_INDIRECT, GLOSSY_INDIRECT, TRANSMISSION_INDIRECT):
+        assert zero_bits(one[cls]), cls
+        assert not (two[cls] > full[cls] * (1.0 + 1e-12)).any(), cls  # (every term a longer path adds is non-negative)
+    assert any((two[cls] > 0).any() for cls in (DIFFUSE_INDIRECT, GLOSSY_INDIRECT, TRANSMISSION_INDIRECT))
+
+
+@pytest.mark.parametrize("scene", list(SCENES) + lit.CONSTRUCTED)
+def test_depth_one_is_the_lighting_passes(scene):
+    """At D = 1 and one sample a pixel: emission is the lighting passes' emission, background their sky, the three direct planes in one
+    their direct."""
+    if isinstance(scene, str):
+        (planes, _), lighting = image_planes(scene, 1, MERGED_DIRECT, 1), lit.image_case(scene)
+    else:
+        (planes, _), lighting = constructed_planes(*scene, 1, MERGED_DIRECT, 1), lit.constructed_case(*scene, 1)
+    assert rel_error(planes[0], lighting["emission"]).max() <= 1e-12
+    assert rel_error(planes[1], lighting["sky"]).max() <= 1e-12
+    if scene != "quadric":
+        # (the lighting passes take a quadric's hit for a triangle with vertex normals and shade it with a shading normal that is not the
+        # path tracer's - test_light_groups_emulation says where -; test 1 holds this pass to the oracle on that image too)
+        err = rel_error(planes[2], lighting["direct"]).max()
+        print("%s: merged direct planes against the lighting passes' direct: max rel error %.3e" % (scene, err))
+        assert err <= 1e-12
+    assert all(zero_bits(planes[p]) for p in (3, 4, 5))
+
+
+# ------------------------------------------------------------------ 6. chunks, shards, list order
+def test_planes_do_not_depend_on_chunks_shards_or_the_order_of_the_live_lists():
+    """coffee_maker_qsah at sqrtspp 2, the default map: chunks of one pixel (8 slots), of 97 pixels (which split rows), one chunk; 3 shards
+    of 2-row groups dealt round robin (13 rows: the last group ragged); live lists reversed and shuffled."""
+    scene, sqrtspp = "coffee_maker_qsah", 2
+    img = aov._image(scene)
+    whole, info = image_planes(scene, sqrtspp)
+    for chunk_rays in (8, 97 * 8, 910 * 8):
+        chunked, cinfo = emu_planes(img.scene, aov.camera(scene, sqrtspp), SCENES[scene], chunk_rays=chunk_rays)
+        assert chunked.tobytes() == whole.tobytes(), chunk_rays
+        assert cinfo["rays"] == info["rays"] and cinfo["live"] == info["live"]
+    for order in (1, 2):
+        other, oinfo = emu_planes(img.scene, aov.camera(scene, sqrtspp), SCENES[scene], order=order)
+        assert other.tobytes() == whole.tobytes() and oinfo == info, order
+    seen = 0
+    for index in range(3):
+        cam = aov.camera(scene, sqrtspp, (index, 3, 2))
+        rows = _pkg().shard_rows(cam)
+        part, _ = emu_planes(img.scene, cam, SCENES[scene])
+        assert whole.reshape(8, HEIGHT, WIDTH, 3)[:, rows].tobytes() == part.tobytes(), index
+        seen += len(rows)
+    assert seen == HEIGHT
+
+
+# ------------------------------------------------------------------ 7. refusals and edge cases
+def test_a_map_entry_of_eight_is_refused():
+    scene, cam = lit.constructed("lambertian", False), lit.constructed_camera(1)
+    emu_planes(scene.scene, cam, 1, class_plane=(0, 1, 2, 3, 4, 5, 6, 8), expect=-1)
+    emu_planes(scene.scene, cam, 1, class_plane=(255, 0, 0, 0, 0, 0, 0, 0), expect=-1)
+    assert _pkg().lib().mcrt_path_class_planes(C.byref(_pkg().Context._path_class_params((0, 1, 2, 3, 4, 5, 6, 8), 0))) == 0
+
+
+def test_nesting_deeper_than_the_history_is_refused(manifest):
+    """test_nested_media's twelve concentric shells with the fixture's own camera: MCRT_ERR_UNSUPPORTED, as the call on the GPU says."""
+    import test_nested_media as nested
+    scene, cam = nested._setup(_pkg(), manifest, 12)
+    emu_planes(scene.scene, cam, 1, expect=-7)
+    emu_planes(nested._setup(_pkg(), manifest, 4)[0].scene, cam, 1)  # four shells are within the eight entries
+
+
+def test_a_camera_that_sees_only_sky_ends_after_iteration_zero(oracle):
+    scene = lit.constructed("lambertian", False)
+    cam = lit.constructed_camera(2)
+    cam.eye = (C.c_double * 3)(0.0, 8.0, 40.0)  # beside the floor, looking down past it
+    planes, info = emu_planes(scene.scene, cam, 1)
+    ref, _ = oracle.render(scene, cam, SEED, _pkg().INTEGRATOR_PATH_TRACER)
+    assert info == dict(rays=PIXELS * 4, iterations=0, live=0)  # (the camera rays and nothing else: a miss is never queued)
+    assert all(zero_bits(planes[p]) for p in range(8) if p != BACKGROUND) and (planes[BACKGROUND] > 0).all()
+    assert planes[BACKGROUND].tobytes() == ref.reshape(PIXELS, 3).tobytes()
