@@ -1318,6 +1318,96 @@ int mcrt_render_path_classes_device(mcrt_ctx* ctx, const mcrt_camera_desc* cam, 
 int mcrt_render_path_classes(mcrt_ctx* ctx, const mcrt_camera_desc* cam, uint32_t global_seed, const mcrt_path_class_params* params /* may be NULL */,
                              double* planes, mcrt_stats* stats /* may be NULL */);
 
+/* ------------------------------------------------------------------------------------------
+ * Adaptive sampling: a per-pixel stopping rule. mcrt_render_converged stops when the whole FRAME is quiet enough and until then samples
+ * every pixel at full price; this pass renders batch 0 over the frame and every later batch over the LIST of pixels that are still
+ * noisy (or lie next to one), and delivers the accumulated summary of every pixel together with a sample-count map that shows where the
+ * samples went. The reference has no such output. Path tracer only (the walk over a list is the light groups', which supports no other
+ * integrator): there is no integrator argument. What decides anything - the batch summary, the merge, the criterion - is only FP64
+ * + - * /, compare and select, in the order written here, uncontracted, no libm routine: a function of scene, camera, seed and
+ * parameters bit for bit.
+ *
+ * Batches. Batch j (j = 0, 1, ...) has n = sqrtspp^2 samples per LISTED pixel. A pixel numbers its own batches: with count[p] = k n
+ * samples so far, its next batch is its batch k, whichever batch of the call lists it, and the sampler of pixel (x, y) is then
+ * initiate(global_seed + k (wrapping in uint32_t), y * width + x) with sample index i = 0 .. n-1: the samples a full render of cam at
+ * seed global_seed + k gives that pixel, whatever else is listed. As long as no batch has left a pixel out, k = j for every pixel. The
+ * batch summary of a listed pixel is what mcrt_render_pixel_stats delivers for it at that seed ("Per-pixel sample statistics"): rgb the
+ * frame value max(m, 0), variance two-pass about the unclamped mean m, half_a and half_b the means of the even and of the odd samples.
+ * Merge. Every pixel p has accumulators rgb, variance, half_a, half_b and a count[p], 0 before batch 0. A listed pixel takes its batch
+ * summary by mcrt_frame_merge's formulas ("Accumulated rendering" 1.) with n_a = count[p], n_b = n, accumulator = A, batch = B, in place,
+ * the halves' parity rule included; a pixel with count[p] = 0 takes the batch summary as it is. Then count[p] = count[p] + n. A pixel
+ * that is not listed is not touched. So a pixel's outputs depend on its count alone: with count[p] = k n they are the outputs of
+ * mcrt_render_converged (path tracer, same camera and seed, max_spp = k n, no target) at that pixel, bit for bit.
+ * Criterion. After the merge of each batch, on the accumulated rgb (r, g, b), variance (v_r, v_g, v_b) and n_p = count[p], with
+ * T2 = target * target and F2 = floor * floor computed once on the host:
+ *   e_p     = ((v_r + v_g) + v_b) / (double)n_p
+ *   g_p     = (r * r + g * g) + b * b
+ *   noisy_p = g_p == g_p  and  e_p > T2 * (g_p > F2 ? g_p : F2)      (false when a NaN takes part: a NaN pixel retires)
+ *   p is listed for the next batch when
+ *     count[p] + n <= max_spp
+ *     and ( batches so far < min_batches   or   target_relative_error == 0
+ *           or noisy_q for some q with |x_q - x_p| <= r and |y_q - y_p| <= r inside the frame )          (r = window)
+ * Before batch 0 no batch was rendered, so every pixel is listed. The list is rebuilt from scratch after every batch: a retired pixel
+ * comes back when a neighbour turns noisy. It holds the packed pixels y * width + x in ascending order. The loop ends when the list is
+ * empty; ending at max_spp is not an error. Nothing depends on how a list is cut into chunks (option MCRT_AOV_CHUNK_RAYS, with the
+ * light groups' meaning and default) or on the order in which live samples are queued.
+ * A batch whose list is the whole frame, while no batch before it has left a pixel out (every pixel is at its batch j), is one
+ * mcrt_render_pixel_stats_device at seed global_seed + j followed by the merge (option MCRT_ADAPTIVE_FULL_BATCH=render, the default:
+ * the render kernel is several times cheaper per sample than the walk) or a walk like every other batch (=walk); both give the same
+ * bytes. The first min_batches batches are such full ones.
+ * Parameters (params NULL, or a field zero: the default):
+ *   target_relative_error  per PIXEL: a pixel is quiet when the estimated standard error of its mean is at most this fraction of its
+ *                          radiance (sqrt(e_p) <= target * max(sqrt(g_p), floor)). 0 (the default): no pixel ever retires before max_spp.
+ *   floor                  the radiance below which a pixel's signal counts as `floor`: dark pixels are not chased for a RELATIVE
+ *                          error they cannot reach. Default: 0.01 * sqrt(signal / (double)pixels), signal being mcrt_frame_noise's
+ *                          of the frame after batch 0 (its treesum: a function of the bits; sqrt on the host) - a hundredth of the
+ *                          root mean square radiance -, or 0 when that is not finite. (For no floor pass the smallest positive double.)
+ *   max_spp                per pixel; default 1024, or one batch where that is more.
+ *   min_batches            default 1; with sqrtspp 1 it is at least 2 (a 1-sample batch has variance 0), as in mcrt_converge_params.
+ *   window                 the Chebyshev radius r of the dilation, 1 .. 4; default 1. MCRT_ADAPTIVE_WINDOW_NONE: r = 0, a pixel
+ *                          answers for itself alone.
+ * Outputs: d_out_rgb and the channels of d_stats that are not NULL are FULL frames [height][width][3]; d_count, when given, is
+ * [height][width] uint32_t, the samples every pixel received. result: the batches rendered, the smallest and largest count, the sum of
+ * count over the frame, and the length of the list of each of the first MCRT_CONVERGE_TRACE batches (0 past `batches`). The three
+ * numbers about the counts are computed on the host: both forms, the _device one too, read the count map back once at the end (4 bytes
+ * a pixel), next to the one word per batch that is the list's length.
+ * stats: paths, rays, node_tests, prim_tests, knn_searches, kernel_ms and kernel_launches summed over the batches (the rule and the
+ * list count 4 launches a batch, a merge 1), kernel_id of the last rendered full batch (MCRT_KERNEL_NONE when every batch was a walk),
+ * total_ms of the call. Both calls are synchronous on the context's stream.
+ * Refused with a message (mcrt_last_error): before mcrt_upload_scene (MCRT_ERR_NO_SCENE); with MCRT_ERR_UNSUPPORTED a camera whose film
+ * splats (a reconstruction filter, or a box of another radius), cam->shard_count > 1 - the window needs the neighbouring rows -, a path
+ * that nests more than 8 dielectric media and a list whose paths are still alive after 4096 iterations, as in the light groups; with
+ * MCRT_ERR_INVALID a render in flight, cam or the frame NULL, sqrtspp 0, a target or floor that is negative or not finite, window > 4,
+ * max_spp below one batch.
+ * Not done: photon-mapped frames, filtered (splatting) films, sharded cameras, highlights (tops / level) under per-pixel counts, a
+ * frame-level relative_error for non-uniform counts, continuing the Sobol sequence across batches instead of reseeding, compaction of
+ * the walk's tail iterations. */
+#define MCRT_ADAPTIVE_WINDOW_NONE 0xFFFFFFFFu
+typedef struct mcrt_adaptive_params {   /* NULL or a zero field = the default */
+    double   target_relative_error;     /* per PIXEL; finite, >= 0; 0 = no pixel ever retires before max_spp */
+    double   floor;                     /* radiance below which a pixel's signal counts as `floor`; finite, >= 0 */
+    uint32_t max_spp;                   /* per pixel; default 1024, or one batch where that is more */
+    uint32_t min_batches;               /* default 1; with sqrtspp 1 it is 2 (as in mcrt_converge_params) */
+    uint32_t window;                    /* Chebyshev radius r of the dilation, 1 .. 4; MCRT_ADAPTIVE_WINDOW_NONE = 0 */
+} mcrt_adaptive_params;                 /* 32 bytes */
+typedef struct mcrt_adaptive_result {
+    uint32_t batches, min_count, max_count;
+    uint64_t samples;                         /* sum of count over the frame */
+    uint32_t active[MCRT_CONVERGE_TRACE];     /* pixels listed for batch j, first 64 */
+} mcrt_adaptive_result;
+int mcrt_render_adaptive_device(mcrt_ctx* ctx, const mcrt_camera_desc* cam, uint32_t global_seed, const mcrt_adaptive_params* params /* may be NULL */,
+                                double* d_out_rgb, const mcrt_pixel_stats_buffers* d_stats /* may be NULL */, uint32_t* d_count /* may be NULL */,
+                                mcrt_adaptive_result* result /* may be NULL */, mcrt_stats* stats /* may be NULL */);
+/* The list alone. DIAGNOSTIC AND UNSTABLE: it exists so that the compaction can be tested by itself on the device, is no part of the
+ * interface a renderer builds on, and may change or go without a new ABI version. The pass's three list launches (count, scan, scatter) on `pixels` flags (HOST, one byte each, set =
+ * not zero) -> list (HOST, room for `pixels` words): the indices of the set flags in ascending order, *length of them. Needs no scene.
+ * Refused (MCRT_ERR_INVALID) while a render is in flight, with a NULL pointer, with pixels 0 or >= 2^32. */
+int mcrt_adaptive_list(mcrt_ctx* ctx, uint64_t pixels, const uint8_t* flags, uint32_t* list, uint32_t* length);
+/* Same with HOST pointers. */
+int mcrt_render_adaptive(mcrt_ctx* ctx, const mcrt_camera_desc* cam, uint32_t global_seed, const mcrt_adaptive_params* params /* may be NULL */,
+                         double* out_rgb, const mcrt_pixel_stats_buffers* stats_buffers /* may be NULL */, uint32_t* count /* may be NULL */,
+                         mcrt_adaptive_result* result /* may be NULL */, mcrt_stats* stats /* may be NULL */);
+
 /* Photon emission pass on the GPU. Replaces the thread fan-out of
  * PhotonMapper::PhotonMapper (integrator/photon-mapper/photon-mapper.cpp:80-115: per emission
  * Sampler::initiate(light), setIndex(offset+i), light point + cosine direction, emitPhoton :225-277) for

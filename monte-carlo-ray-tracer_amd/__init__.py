@@ -394,6 +394,24 @@ class ConvergeResult(C.Structure):
                 "relative_error": [self.relative_error[i] for i in range(min(self.batches, CONVERGE_TRACE))]}
 
 
+# Adaptive sampling (include/mcrt.h "Adaptive sampling")
+ADAPTIVE_WINDOW_NONE = 0xFFFFFFFF
+
+
+class AdaptiveParams(C.Structure):
+    """mcrt_adaptive_params: a zero field = the default (include/mcrt.h); window ADAPTIVE_WINDOW_NONE = radius 0."""
+    _fields_ = [("target_relative_error", C.c_double), ("floor", C.c_double), ("max_spp", C.c_uint32), ("min_batches", C.c_uint32), ("window", C.c_uint32)]
+
+
+class AdaptiveResult(C.Structure):
+    """mcrt_adaptive_result."""
+    _fields_ = [("batches", C.c_uint32), ("min_count", C.c_uint32), ("max_count", C.c_uint32), ("samples", C.c_uint64), ("active", C.c_uint32 * CONVERGE_TRACE)]
+
+    def as_dict(self):
+        return {"batches": self.batches, "min_count": self.min_count, "max_count": self.max_count, "samples": self.samples,
+                "active": [self.active[i] for i in range(min(self.batches, CONVERGE_TRACE))]}
+
+
 # OpenEXR output (include/mcrt.h "OpenEXR output")
 EXR_SRC_F64, EXR_SRC_U32 = 0, 1
 EXR_PIXEL_TYPES = {"uint": 0, "half": 1, "float": 2}
@@ -568,7 +586,7 @@ def _exr_source(a):
 _EXR_FLOAT_LAYERS = ("depth", "position", "variance", "error", "level")
 
 
-def exr_layers(rgb=None, aov=None, stats=None, highlights=None, robust=None, denoised=None, pixel_types=None, mattes=None, errors=None, occlusion=None, lighting=None, light_groups=None, path_classes=None):
+def exr_layers(rgb=None, aov=None, stats=None, highlights=None, robust=None, denoised=None, pixel_types=None, mattes=None, errors=None, occlusion=None, lighting=None, light_groups=None, path_classes=None, adaptive=None):
     """The channel dict Context.exr_save takes, from what the render_* and denoise_* methods return, under fixed names:
       rgb [H,W,3]                       R, G, B
       aov (render_aov's dict)           depth.Z, position.X/Y/Z, normal.X/Y/Z, shading_normal.X/Y/Z, albedo.R/G/B, coverage.A, surface.id, material.id
@@ -589,6 +607,8 @@ def exr_layers(rgb=None, aov=None, stats=None, highlights=None, robust=None, den
                                         (light_group_map's): colour, HALF
       path_classes (planes, names)      pathclass.<name>.R/G/B for every plane of render_path_classes' [P,H,W,3] and its name
                                         (path_class_map's): colour, HALF
+      adaptive (render_adaptive's)      samples.count (its "count" [H,W] uint32: UINT) and variance.R/G/B, half_a.R/G/B, half_b.R/G/B under
+                                        the statistics' names (those that are there; its "rgb" is not taken: pass it as rgb)
     -> dict name -> (view [H,W], "half" | "float" | "uint"). Colour is HALF; depth, position, variance, error and level FLOAT; ids and
     counts UINT. pixel_types: {channel or layer name: type} overrides that (a layer is a name without its last component). The views
     are of the arrays and tensors given, numpy or torch alike: nothing is copied."""
@@ -661,6 +681,13 @@ def exr_layers(rgb=None, aov=None, stats=None, highlights=None, robust=None, den
         assert len(planes) == len(names) and len(set(names)) == len(names), (len(planes), names)
         for plane, name in zip(planes, names):
             put("pathclass." + name, "RGB", plane)
+    if adaptive is not None:
+        assert stats is None, "adaptive and stats name the same channels"
+        if adaptive.get("count") is not None:
+            put("samples", ("count",), adaptive["count"], "uint")
+        for layer in PIXEL_STATS_CHANNELS:
+            if adaptive.get(layer) is not None:
+                put(layer, "RGB", adaptive[layer])
     return out
 
 
@@ -873,6 +900,11 @@ def lib():
         L.mcrt_render_converged.argtypes = [vp, C.POINTER(CameraDesc), C.c_uint32, C.c_int, C.POINTER(ConvergeParams), vp, C.POINTER(PixelStatsBuffers),
                                             C.POINTER(HighlightBuffers), C.POINTER(ConvergeResult), C.POINTER(Stats)]
         L.mcrt_render_converged_device.argtypes = L.mcrt_render_converged.argtypes
+    if hasattr(L, "mcrt_render_adaptive"):  # (likewise)
+        L.mcrt_render_adaptive.argtypes = [vp, C.POINTER(CameraDesc), C.c_uint32, C.POINTER(AdaptiveParams), vp, C.POINTER(PixelStatsBuffers), vp,
+                                           C.POINTER(AdaptiveResult), C.POINTER(Stats)]
+        L.mcrt_render_adaptive_device.argtypes = L.mcrt_render_adaptive.argtypes
+        L.mcrt_adaptive_list.argtypes = [vp, C.c_uint64, vp, vp, C.POINTER(C.c_uint32)]
     if hasattr(L, "mcrt_exr_save"):  # (likewise)
         L.mcrt_exr_save.argtypes = [vp, C.c_char_p, C.c_uint32, C.c_uint32, C.POINTER(ExrChannel), C.c_uint32, C.POINTER(ExrAttribute), C.c_uint32,
                                     C.POINTER(ExrParams), C.POINTER(ExrResult), C.POINTER(Stats)]
@@ -2050,6 +2082,56 @@ class Context:
             stats.update(st.as_dict())
         res["result"] = out.as_dict()
         return res
+
+    @staticmethod
+    def _adaptive_params(target_relative_error, max_spp=0, floor=0.0, window=None, min_batches=0):
+        w = 0 if window is None else ADAPTIVE_WINDOW_NONE if int(window) == 0 else int(window)
+        return AdaptiveParams(float(target_relative_error), float(floor), int(max_spp), int(min_batches), w)
+
+    def render_adaptive(self, cam, global_seed, target_relative_error, max_spp=0, floor=0.0, window=None, min_batches=0, channels=("variance",), stats=None):
+        """mcrt_render_adaptive: the per-pixel stopping rule. Batches of cam.sqrtspp^2 samples at the seeds global_seed, global_seed + 1,
+        ...: batch 0 over the frame, every later one over the list of the pixels that are still noisy - the estimated error of the
+        pixel's mean above target_relative_error times its radiance (or `floor`, where that is more; 0.0 = the default, derived from the
+        frame) - or have such a pixel within `window` pixels (None = the default, 1; 0 = the pixel alone), until the list is empty or
+        max_spp (0 = the default) is reached per pixel. Path tracer only. -> dict "rgb" [H,W,3], the channels wanted
+        (PIXEL_STATS_CHANNELS) of the accumulated frame, "count" [H,W] uint32 - the samples every pixel received - and "result": batches,
+        min_count, max_count, samples, active (the list's length per batch, the first 64). stats: a dict that receives mcrt_stats,
+        summed over the batches."""
+        self._sync_env()
+        res = _summary_arrays(["rgb"] + list(channels), (cam.height, cam.width), allowed=PIXEL_STATS_CHANNELS)
+        count = np.zeros((cam.height, cam.width), dtype=np.uint32)
+        par = self._adaptive_params(target_relative_error, max_spp, floor, window, min_batches)
+        out, st = AdaptiveResult(), Stats()
+        self._check(self._lib.mcrt_render_adaptive(self._h, C.byref(cam), int(global_seed) & 0xFFFFFFFF, C.byref(par), res["rgb"].ctypes.data,
+                                                   C.byref(_addresses(PixelStatsBuffers, res)), count.ctypes.data, C.byref(out), C.byref(st)), "mcrt_render_adaptive")
+        if stats is not None:
+            stats.update(st.as_dict())
+        res["count"] = count
+        res["result"] = out.as_dict()
+        return res
+
+    def adaptive_list(self, flags):
+        """mcrt_adaptive_list, a diagnostic for the tests (unstable: no part of the interface to build on): the indices of the flags that are set ([n] uint8), ascending, by the pass's three list
+        launches -> [length] uint32."""
+        flags = np.ascontiguousarray(flags, dtype=np.uint8).reshape(-1)
+        out, length = np.full(flags.size, 0xABABABAB, dtype=np.uint32), C.c_uint32(0)
+        self._check(self._lib.mcrt_adaptive_list(self._h, flags.size, flags.ctypes.data, out.ctypes.data, C.byref(length)), "mcrt_adaptive_list")
+        assert (out[length.value:] == 0xABABABAB).all()  # nothing behind the list is written
+        return out[:length.value]
+
+    def render_adaptive_device(self, cam, global_seed, rgb_ptr, target_relative_error, max_spp=0, floor=0.0, window=None, min_batches=0, stats_pointers=None,
+                               count_ptr=None):
+        """mcrt_render_adaptive_device: rgb_ptr, stats_pointers = dict statistics channel -> raw device pointer and count_ptr ([H][W]
+        uint32), all FULL frames; channels left out or None are not delivered. Synchronous; returns (the result dict of render_adaptive,
+        the stats dict)."""
+        self._sync_env()
+        ps = _pointer_struct(PixelStatsBuffers, stats_pointers, PIXEL_STATS_CHANNELS)
+        par = self._adaptive_params(target_relative_error, max_spp, floor, window, min_batches)
+        out, st = AdaptiveResult(), Stats()
+        self._check(self._lib.mcrt_render_adaptive_device(self._h, C.byref(cam), int(global_seed) & 0xFFFFFFFF, C.byref(par), C.c_void_p(int(rgb_ptr)) if rgb_ptr else None,
+                                                          C.byref(ps), C.c_void_p(int(count_ptr)) if count_ptr else None, C.byref(out), C.byref(st)),
+                    "mcrt_render_adaptive_device")
+        return out.as_dict(), st.as_dict()
 
     def render_converged_device(self, cam, global_seed, integrator, rgb_ptr, target_relative_error=0.0, max_spp=0, min_batches=0, stats_pointers=None,
                                 pointers=None):

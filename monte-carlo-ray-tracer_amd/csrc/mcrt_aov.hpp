@@ -30,19 +30,28 @@ struct AovChunk {
     uint32_t pixels;
 };
 
-MCRT_HD void aovPixelOf(const AovChunk& c, uint32_t p, uint32_t& x, uint32_t& y) {
-    const uint64_t q = c.first_pixel + p;
+// How a chunk names its pixels: pixel p of it is packed pixel chunkPixel(c, p) of the shard's rows. A chunk of the frame counts on
+// from its first one; the adaptive pass's chunk of a pixel LIST (mcrt_adaptive.hpp: AdaptiveChunk) overloads this with one indirection.
+// What follows - the camera rays here, the walk of mcrt_light_groups.hpp - takes the chunk's type as a parameter and asks this function.
+// chunkSeed(c, p) is the global seed of that pixel's samples: the chunk's for a chunk of the frame; the adaptive pass counts a pixel's own
+// batches.
+MCRT_HD uint64_t chunkPixel(const AovChunk& c, uint32_t p) { return c.first_pixel + p; }
+MCRT_HD uint32_t chunkSeed(const AovChunk& c, uint32_t) { return c.global_seed; }
+
+template <class Chunk>
+MCRT_HD void aovPixelOf(const Chunk& c, uint32_t p, uint32_t& x, uint32_t& y) {
+    const uint64_t q = chunkPixel(c, p);
     x = (uint32_t)(q % c.cam.width);
     y = localToGlobalRow(c.cam, (uint32_t)(q / c.cam.width));
 }
 
 // Camera ray of sample i of the chunk's pixel p (camera.cpp:73-95).
-template <bool kLdsTab>
-MCRT_HD Ray aovCameraRay(const AovChunk& c, double scene_ior, uint32_t p, uint32_t i, SobolTab tab) {
+template <bool kLdsTab, class Chunk>
+MCRT_HD Ray aovCameraRay(const Chunk& c, double scene_ior, uint32_t p, uint32_t i, SobolTab tab) {
     uint32_t x, y;
     aovPixelOf(c, p, x, y);
     Sampler smp;
-    smp.initiate(c.global_seed, y * c.cam.width + x);
+    smp.initiate(chunkSeed(c, p), y * c.cam.width + x);
     smp.setIndex(i);
     return cameraRay<kLdsTab>(c.cam, scene_ior, x, y, smp, tab);
 }

@@ -1,5 +1,5 @@
 // What the passes that trace camera rays share (DESIGN.md "Image passes"): the first-hit AOV pass, the ID mattes, the occlusion pass, the
-// lighting passes, the light groups and the path classes (mcrt_{aov,matte,occlusion,lighting,light_groups,path_classes}_host.hip). Two layers. The PURE one - no HIP, no
+// lighting passes, the light groups, the path classes and adaptive sampling (mcrt_{aov,matte,occlusion,lighting,light_groups,path_classes,adaptive}_host.hip). Two layers. The PURE one - no HIP, no
 // context - is the chunk plan, its defaults, a chunk's record and a shard's rows: the host sides and the emulations of the CPU tests
 // (tests/emu/*_emu.cpp, which include this file the way they include mcrt_aov.hpp) run the same text. The HOST one, on top of
 // mcrt_pass_host.hpp and compiled by hipcc only, is the calls' guard, the camera checks, the five arrays of a family's ray scratch, the
@@ -137,18 +137,30 @@ struct CameraPass {
     explicit CameraPass(mcrt_ctx* ctx) : stream((hipStream_t)ctxStream(ctx)) { ctxAovScene(ctx, &scene, &sobol_tab); }
 };
 
+// How the chunks of a call name their pixels, as the chunk loop needs it: chunk(...) is the record of a chunk, rays(...) queues the
+// kernel that writes its camera rays. Here the frame's own order - pixel p of a chunk is packed pixel first_pixel + p, the rays are
+// libmcrt_aov.so's -; the adaptive pass has a naming through a pixel list (mcrt_adaptive_host.hip).
+struct FramePixels {
+    AovChunk chunk(const mcrt_camera_desc& cam, uint32_t global_seed, uint32_t spp, uint64_t first, uint64_t chunk_pixels, uint64_t total_pixels) const {
+        return chunkAt(cam, global_seed, spp, first, chunk_pixels, total_pixels);
+    }
+    int rays(hipStream_t stream, const AovChunk& c, double scene_ior, const uint32_t* sobol_tab, const AovRays& rays_) const {
+        return launchAovRays(stream, c, scene_ior, sobol_tab, rays_);
+    }
+};
+
 // The chunk loop. Per chunk: the camera rays into `rays` and their closest hits (2 launches, n rays), then body(chunk, launches, traced)
 // -> rc, which adds its own launches and rays to the two counts. Around the loop the call's events; after it the statistics.
-template <class Body>
-int runChunks(mcrt_ctx* ctx, const CameraPass& cp, PassTimer& timer, const mcrt_camera_desc* cam, uint32_t global_seed, const PixelChunks& plan, const AovRays& rays,
-              mcrt_stats* stats, Body body) {
+template <class Naming, class Body>
+int runChunksOf(const Naming& naming, mcrt_ctx* ctx, const CameraPass& cp, PassTimer& timer, const mcrt_camera_desc* cam, uint32_t global_seed, const PixelChunks& plan,
+                const AovRays& rays, mcrt_stats* stats, Body body) {
     if (int rc = timer.begin(cp.stream)) return rc;
     uint32_t launches = 0;
     uint64_t traced = 0;
     for (uint64_t first = 0; first < plan.total_pixels; first += plan.chunk_pixels) {
-        const AovChunk c = chunkAt(*cam, global_seed, plan.spp, first, plan.chunk_pixels, plan.total_pixels);
+        const auto c = naming.chunk(*cam, global_seed, plan.spp, first, plan.chunk_pixels, plan.total_pixels);
         const uint64_t n = (uint64_t)c.pixels * plan.spp;
-        MCRT_HIP_TRY(ctx, (hipError_t)launchAovRays(cp.stream, c, cp.scene.sh.scene_ior, cp.sobol_tab, rays));
+        MCRT_HIP_TRY(ctx, (hipError_t)naming.rays(cp.stream, c, cp.scene.sh.scene_ior, cp.sobol_tab, rays));
         if (int rc = intersectDeviceArrays(ctx, n, rays.start, rays.direction, rays.t, rays.surface, rays.uv)) return rc;
         launches += 2;
         traced += n;
@@ -161,6 +173,11 @@ int runChunks(mcrt_ctx* ctx, const CameraPass& cp, PassTimer& timer, const mcrt_
         stats->rays = traced;
     }
     return MCRT_OK;
+}
+template <class Body>
+int runChunks(mcrt_ctx* ctx, const CameraPass& cp, PassTimer& timer, const mcrt_camera_desc* cam, uint32_t global_seed, const PixelChunks& plan, const AovRays& rays,
+              mcrt_stats* stats, Body body) {
+    return runChunksOf(FramePixels{}, ctx, cp, timer, cam, global_seed, plan, rays, stats, body);
 }
 
 // The host-pointer form of a pass: the frames of `ch` (n of them, the wanted ones one allocation in the family's `slot`) as device

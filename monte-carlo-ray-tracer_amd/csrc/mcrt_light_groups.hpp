@@ -110,7 +110,8 @@ MCRT_HD bool lgBegin(const LgState& st, uint64_t s, double scene_ior, const LgPa
 }
 
 // Vertex k of sample s, as iteration k of sampleRay's loop has it (path-tracer.cpp:23-47 without the additions to the radiance):
-// both kernels derive it from the stored ray and hit. `rh` holds the sample's history and is not changed.
+// both kernels derive it from the stored ray and hit. `rh` holds the sample's history and is not changed. (Chunk: how the chunk names
+// its pixels, mcrt_aov.hpp chunkPixel - the frame's chunks here and in the path classes, a pixel list in the adaptive pass.)
 struct LgVertex {
     InteractionT<false> ia;
     LightSample ls;   // in: as vertex k finds it; out: as vertex k + 1 finds it
@@ -123,11 +124,13 @@ struct LgVertex {
     bool bounce;      // the path goes on to vertex k + 1
 };
 
-MCRT_HD void lgVertex(LgVertex& v, const AovChunk& c, const AovScene& s, const LgState& st, uint64_t sample, uint32_t k, const RefractionHistory& rh, SobolTab tab) {
+template <class Chunk>
+MCRT_HD void lgVertex(LgVertex& v, const Chunk& c, const AovScene& s, const LgState& st, uint64_t sample, uint32_t k, const RefractionHistory& rh, SobolTab tab) {
     uint32_t x, y;
-    aovPixelOf(c, (uint32_t)(sample % c.pixels), x, y);
+    const uint32_t p = (uint32_t)(sample % c.pixels);
+    aovPixelOf(c, p, x, y);
     Sampler smp;
-    smp.restore(c.global_seed, y * c.cam.width + x, (uint32_t)(sample / c.pixels), k + 1u);  // iteration k begins with one shuffle (path-tracer.cpp:23)
+    smp.restore(chunkSeed(c, p), y * c.cam.width + x, (uint32_t)(sample / c.pixels), k + 1u);  // iteration k begins with one shuffle (path-tracer.cpp:23)
     v.ray = lgLoadRay(st, sample);
     Hit hit;
     hit.t = st.ray.t[sample];
@@ -154,7 +157,8 @@ MCRT_HD void lgVertex(LgVertex& v, const AovChunk& c, const AovScene& s, const L
 // Ray kernel, entry j of the n_live entries of `list`: the shadow ray of the sample's vertex k into record j of `lit`, its bounce ray
 // into record n_live + j. A slot without a ray - no shadow ray was built, the path ends here - gets the ray that
 // arrived: finite, traced, never read.
-MCRT_HD void lgRays(const AovChunk& c, const AovScene& s, const LgState& st, const uint32_t* list, uint32_t n_live, uint32_t j, uint32_t k, const AovRays& lit,
+template <class Chunk>
+MCRT_HD void lgRays(const Chunk& c, const AovScene& s, const LgState& st, const uint32_t* list, uint32_t n_live, uint32_t j, uint32_t k, const AovRays& lit,
                     RefractionHistory& rh, SobolTab tab) {
     const uint64_t sample = list[j];
     const d3 start = ld3(st.ray.start + 3 * sample), direction = ld3(st.ray.direction + 3 * sample);
@@ -206,7 +210,8 @@ MCRT_HD void lgStoreNext(const LgState& st, uint64_t sample, const LgVertex& v, 
 // is iteration max_depth, which takes its emission and ends (its miss was taken where the ray was found to miss; no rays were traced for
 // it, lit is not read). Returns true when
 // the path goes on; too_deep: the history would have needed a ninth entry (the sample is dropped, the host refuses the frame).
-MCRT_HD bool lgStep(const AovChunk& c, const AovScene& s, const LgState& st, const LgParams& par, const uint32_t* list, uint32_t n_live, uint32_t j, uint32_t k, bool last,
+template <class Chunk>
+MCRT_HD bool lgStep(const Chunk& c, const AovScene& s, const LgState& st, const LgParams& par, const uint32_t* list, uint32_t n_live, uint32_t j, uint32_t k, bool last,
                     const AovRays& lit, RefractionHistory& rh, bool& too_deep, SobolTab tab) {
     const uint64_t sample = list[j];
     too_deep = false;

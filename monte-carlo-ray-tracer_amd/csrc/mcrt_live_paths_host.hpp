@@ -1,5 +1,5 @@
-// The bounce loop of the passes that walk whole paths over live lists - the light groups and the path classes
-// (mcrt_{light_groups,path_classes}_host.hip) - behind the camera-ray passes' chunk loop (mcrt_camera_pass.hpp): per chunk begin, then
+// The bounce loop of the passes that walk whole paths over live lists - the light groups, the path classes and adaptive sampling
+// (mcrt_{light_groups,path_classes,adaptive}_host.hip) - behind the camera-ray passes' chunk loop (mcrt_camera_pass.hpp): per chunk begin, then
 // per iteration rays -> intersectDeviceArrays over 2 rays per LIVE sample -> step, the host reading the next list's count (and the
 // pass's error word) after every step; resolve when no sample is alive. Each pass hands in its own four launches. Scratch of the family:
 // slot 2 the shadow and bounce records, 3 the two live lists and the counters.
@@ -42,9 +42,9 @@ inline bool livePathScratch(mcrt_ctx* ctx, PassFamily family, uint64_t max_n, Li
 
 // begin(c, n, list, counters), rays(c, list, live, k, lit, counters, next), step(c, list, live, k, last, lit, next_list, counters, next)
 // and resolve(c) queue one kernel each and return its hipError_t as an int. camera_rays: where the chunk loop writes the camera rays
-// and their hits (the samples' state).
-template <class Begin, class Rays, class Step, class Resolve>
-int runLivePaths(mcrt_ctx* ctx, const char* what, const CameraPass& cp, PassTimer& timer, const mcrt_camera_desc* cam, uint32_t global_seed, const PixelChunks& plan,
+// and their hits (the samples' state). naming: how the chunks name their pixels (mcrt_camera_pass.hpp FramePixels; c is its chunk).
+template <class Naming, class Begin, class Rays, class Step, class Resolve>
+int runLivePathsOf(const Naming& naming, mcrt_ctx* ctx, const char* what, const CameraPass& cp, PassTimer& timer, const mcrt_camera_desc* cam, uint32_t global_seed, const PixelChunks& plan,
                  const AovRays& camera_rays, mcrt_stats* stats, const LivePathScratch& sc, uint32_t max_depth, bool log, const char* log_key, Begin begin, Rays rays_of,
                  Step step, Resolve resolve) {
     const hipStream_t stream = cp.stream;
@@ -60,7 +60,7 @@ int runLivePaths(mcrt_ctx* ctx, const char* what, const CameraPass& cp, PassTime
         return rc;
     };
     double chunk_t0 = log ? clock_ms() : 0.0;  // (a chunk's clock starts where the one before it ended: the stream is drained there)
-    return runChunks(ctx, cp, timer, cam, global_seed, plan, camera_rays, stats, [&](const AovChunk& c, uint32_t& launches, uint64_t& rays) {
+    return runChunksOf(naming, ctx, cp, timer, cam, global_seed, plan, camera_rays, stats, [&](const auto& c, uint32_t& launches, uint64_t& rays) {
         const uint64_t n = (uint64_t)c.pixels * c.spp;
         double search_ms = log ? clock_ms() - chunk_t0 : 0.0;  // the camera rays and their search
         std::string curve;
@@ -106,6 +106,13 @@ int runLivePaths(mcrt_ctx* ctx, const char* what, const CameraPass& cp, PassTime
         }
         return (int)MCRT_OK;
     });
+}
+
+template <class Begin, class Rays, class Step, class Resolve>
+int runLivePaths(mcrt_ctx* ctx, const char* what, const CameraPass& cp, PassTimer& timer, const mcrt_camera_desc* cam, uint32_t global_seed, const PixelChunks& plan,
+                 const AovRays& camera_rays, mcrt_stats* stats, const LivePathScratch& sc, uint32_t max_depth, bool log, const char* log_key, Begin begin, Rays rays_of,
+                 Step step, Resolve resolve) {
+    return runLivePathsOf(FramePixels{}, ctx, what, cp, timer, cam, global_seed, plan, camera_rays, stats, sc, max_depth, log, log_key, begin, rays_of, step, resolve);
 }
 
 }  // namespace mcrt

@@ -7,6 +7,7 @@
 //               [--denoise OUT.f64 [--denoise-iterations N]] [--denoise-variance OUT.f64 [--denoise-variance-out VAR.f64]]
 //               [--denoise-dual OUT.f64 [--denoise-dual-out VAR.f64]] [--stats PREFIX] [--robust PREFIX [--robust-kappa X] [--robust-radius R]]
 //               [--converge TARGET [--max-spp N]] [--exr OUT.exr [--exr-compression none|zip]]
+//               [--adaptive TARGET [--max-spp N] [--adaptive-window R] [--adaptive-floor F] [--adaptive-count OUT.u32]]
 //               [--matte PREFIX [--matte-key material|surface] [--matte-ranks N]] [--compare REF [--compare-layer PREFIX]]
 //               [--occlusion PREFIX [--occlusion-rays N] [--occlusion-distance D]] [--lighting PREFIX]
 //               [--light-groups PREFIX [--light-groups-by material|light|one] [--light-groups-depth D]]
@@ -37,6 +38,13 @@
 // frame's relative error (mcrt_frame_noise) is at most TARGET or one more batch would exceed --max-spp (default 1024); --stats, --robust,
 // --denoise-variance and --denoise-dual then read the accumulated buffers at the accumulated sample count. Prints batches, spp and the final relative
 // error (one device).
+// --adaptive renders the frame through mcrt_render_adaptive (path tracer): the per-pixel stopping rule - batch 0 over the frame, every later
+// batch over the list of the pixels whose own relative error is above TARGET (or that have such a pixel within --adaptive-window R pixels:
+// 1 .. 4, 0 = the pixel alone; the default 1), with --adaptive-floor F the radiance below which a pixel's signal counts as F (the default is
+// derived from the frame), until the list is empty or --max-spp (default 1024) is reached per pixel; --stats then writes the accumulated
+// statistics, --adaptive-count the samples every pixel received ([H][W] uint32), and with --exr the count map goes into the file as the
+// UINT channel samples.count. Prints batches, the number of samples, the smallest and largest count and the list's length per batch. Not
+// with --converge, --robust, --denoise-variance or --denoise-dual, which read a uniform sample count (one device).
 // --exr also writes everything the run produced - the frame and the buffers of --aov, --stats, --robust and the --denoise options - into
 // one OpenEXR file (mcrt_exr_save) as named channels: R, G, B; depth.Z, position.X/Y/Z, normal.X/Y/Z, shading_normal.X/Y/Z, albedo.R/G/B,
 // coverage.A, surface.id, material.id; variance.R/G/B, half_a.*, half_b.*; tops0.R .. tops3.B, level.Y; robust.*, removed.*, clamped.count;
@@ -125,7 +133,10 @@ int main(int argc, char** argv) {
     mcrt_robust_params rparams{};
     mcrt_denoise_params dparams{};
     mcrt_converge_params cparams{};
-    bool converge = false;
+    bool converge = false, adaptive = false;
+    mcrt_adaptive_params aparams{};
+    std::string adaptive_count;
+    std::vector<uint32_t> sample_count;
     std::vector<int> devices;
     for (int i = 3; i < argc; i++) {
         std::string k = argv[i];
@@ -170,7 +181,13 @@ int main(int argc, char** argv) {
         else if (k == "--robust-kappa" && i + 1 < argc) rparams.kappa = std::strtod(argv[++i], nullptr);
         else if (k == "--robust-radius") rparams.radius = (uint32_t)val();
         else if (k == "--converge" && i + 1 < argc) converge = true, cparams.target_relative_error = std::strtod(argv[++i], nullptr);
-        else if (k == "--max-spp") cparams.max_spp = (uint32_t)val();
+        else if (k == "--max-spp") cparams.max_spp = aparams.max_spp = (uint32_t)val();
+        else if (k == "--adaptive" && i + 1 < argc) adaptive = true, aparams.target_relative_error = std::strtod(argv[++i], nullptr);
+        else if (k == "--adaptive-window") {
+            const uint32_t r = (uint32_t)val();
+            aparams.window = r == 0 ? MCRT_ADAPTIVE_WINDOW_NONE : r;
+        } else if (k == "--adaptive-floor" && i + 1 < argc) aparams.floor = std::strtod(argv[++i], nullptr);
+        else if (k == "--adaptive-count" && i + 1 < argc) adaptive_count = argv[++i];
         else if (k == "--denoise-iterations") dparams.iterations = (uint32_t)val();
         else if (k == "--tonemapper" && i + 1 < argc) image.tonemapper = (argv[++i][0] | 0x20) == 'a' ? MCRT_TONEMAP_ACES : MCRT_TONEMAP_HABLE;
         else if (k == "--exposure" && i + 1 < argc) image.exposure_compensation = std::strtod(argv[++i], nullptr);
@@ -273,7 +290,36 @@ int main(int argc, char** argv) {
     std::vector<double> variance, half_a, half_b;
     std::vector<double> tops, level;
     uint32_t spp = cam.sqrtspp * cam.sqrtspp;  // of the delivered frame: --converge accumulates batches of that many
-    if (rc == MCRT_OK && (converge || !pstats.empty() || !robust.empty() || !dvar.empty() || !ddual.empty())) {
+    if (adaptive && (converge || photon || !robust.empty() || !dvar.empty() || !ddual.empty() || ctxs.size() > 1)) {
+        std::fprintf(stderr, "--adaptive is the path tracer on one device, and not with --converge, --robust, --denoise-variance or --denoise-dual\n");
+        return 2;
+    }
+    if (rc == MCRT_OK && adaptive) {
+        if (!pstats.empty()) {
+            variance.resize(rgb.size());
+            half_a.resize(rgb.size());
+            half_b.resize(rgb.size());
+        }
+        const mcrt_pixel_stats_buffers b{pstats.empty() ? nullptr : variance.data(), pstats.empty() ? nullptr : half_a.data(), pstats.empty() ? nullptr : half_b.data()};
+        sample_count.resize(rgb.size() / 3);
+        mcrt_adaptive_result ar;
+        rc = mcrt_render_adaptive(ctx, &cam, seed, &aparams, rgb.data(), &b, sample_count.data(), &ar, &st);
+        if (rc == MCRT_OK) {
+            spp = ar.max_count;
+            std::string active;
+            for (uint32_t j = 0; j < ar.batches && j < MCRT_CONVERGE_TRACE; j++) active += (j ? "," : "") + std::to_string(ar.active[j]);
+            std::printf("{\"adaptive\":%.17g,\"batches\":%u,\"samples\":%llu,\"min_count\":%u,\"max_count\":%u,\"active\":[%s]}\n", aparams.target_relative_error,
+                        ar.batches, (unsigned long long)ar.samples, ar.min_count, ar.max_count, active.c_str());
+            if (!adaptive_count.empty()) {
+                FILE* fc = std::fopen(adaptive_count.c_str(), "wb");
+                if (!fc || std::fwrite(sample_count.data(), 4, sample_count.size(), fc) != sample_count.size()) {
+                    std::fprintf(stderr, "cannot write %s\n", adaptive_count.c_str());
+                    return 1;
+                }
+                std::fclose(fc);
+            }
+        }
+    } else if (rc == MCRT_OK && (converge || !pstats.empty() || !robust.empty() || !dvar.empty() || !ddual.empty())) {
         if (ctxs.size() > 1) {
             std::fprintf(stderr, "--stats, --robust, --denoise-variance, --denoise-dual and --converge take one device\n");
             return 2;
@@ -317,6 +363,7 @@ int main(int argc, char** argv) {
     }
     std::fclose(f);
     exr_layer("", "RGB", rgb.data(), MCRT_EXR_HALF);
+    if (!sample_count.empty()) exr_one("samples.count", sample_count.data(), MCRT_EXR_UINT, 1, 0);
     // --compare: one JSON line per frame; with_maps (the delivered frame under --exr): its error maps become channels
     auto compare_frame = [&](const char* label, const std::vector<double>& frame, bool with_maps) {
         if (compare.empty()) return true;
@@ -368,13 +415,14 @@ int main(int argc, char** argv) {
                 return 1;
             }
         }
-        mcrt_frame_noise_result fn;
-        rc = mcrt_frame_noise(ctx, (uint64_t)cam.width * cam.height, spp, rgb.data(), variance.data(), &fn);
+        mcrt_frame_noise_result fn{};
+        if (!adaptive) rc = mcrt_frame_noise(ctx, (uint64_t)cam.width * cam.height, spp, rgb.data(), variance.data(), &fn);  // (one count for the frame)
         if (rc != MCRT_OK) {
             std::fprintf(stderr, "mcrt error %d: %s\n", rc, mcrt_last_error(ctx));
             return 1;
         }
-        std::printf("{\"stats\":\"%s\",\"noise\":%.17g,\"signal\":%.17g,\"relative_error\":%.17g,\"pixels\":%llu}\n", pstats.c_str(), fn.noise, fn.signal,
+        if (!adaptive)
+            std::printf("{\"stats\":\"%s\",\"noise\":%.17g,\"signal\":%.17g,\"relative_error\":%.17g,\"pixels\":%llu}\n", pstats.c_str(), fn.noise, fn.signal,
                     fn.relative_error, (unsigned long long)fn.pixels);
     }
     if (!robust.empty()) {

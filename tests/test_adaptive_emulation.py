@@ -1,0 +1,410 @@
+"""Adaptive sampling, CPU tier: csrc/mcrt_adaptive.hpp - the text the kernels of csrc/mcrt_adaptive.hip run - driven on the host
+(tests/emu/adaptive_emu.cpp: batches, the rule, the three launches of the list on emulated wavefronts, chunks of the list and the walk's
+iterations as mcrt_render_adaptive_device drives them) against an oracle made of what the project already has.
+
+The oracle (include/mcrt.h "Adaptive sampling"): a pixel's outputs depend on its count alone, and the criterion is elementwise IEEE
+arithmetic. So with C_k the frame mcrt_render_converged delivers at max_spp = k n - here: the oracle's per-sample radiances of the seeds
+SEED, SEED + 1, ... summarised by the header's text in numpy (test_pixel_stats_emulation) and merged by mcrt_frame_merge's text in numpy
+(test_accumulate_emulation) - the rule is replayed in numpy in the stated operation order, which gives the list of every batch and the
+count map, and the expected outputs are out[p] = C_{count[p] / n}[p]. Everything is compared BYTE FOR BYTE: rgb, variance, half_a, half_b,
+count, the lists' lengths, the number of samples.
+
+The replay asserts what makes a case worth running (REQUIRED below): at least three different counts, 20 % .. 80 % of the pixels stop below
+max_spp, a list shorter than 256, a list longer than 256 that is no multiple of 64, and a pixel that comes back after a batch it sat out.
+
+Which frames the replay runs on: on a host whose libm is the one csrc/mcrt_libm.hpp restates (x86-64 glibc 2.35 with FMA and AVX2: where
+this tier normally runs) oracle_converged takes the oracle's samples, and the reference is independent of everything under test. On any
+other host the oracle's samples differ from the device text's in last bits, which can flip a decision of the rule; there the C_k come from
+the emulation's own full batches (target 0), so only the rule and the list stay independently checked on this tier - the summary and the
+merge are then held to the oracle by test_the_degenerate_anchors within its tolerance, and bit for bit on the GPU tier, whose C_k are
+mcrt_render_converged's.
+
+Frames are 70 x 13 pixels (910: no multiple of 64 or 256) at sqrtspp 1 and 2, at most 6 batches."""
+import ctypes as C
+import functools
+import importlib
+import os
+import struct
+import subprocess
+
+import numpy as np
+import pytest
+
+import test_accumulate_emulation as acc
+import test_aov_emulation as aov
+import test_pixel_stats_emulation as ps
+from conftest import ROOT, TESTS, host_libm_is_the_restated_one
+
+WIDTH, HEIGHT, SEED, SCENES = aov.WIDTH, aov.HEIGHT, aov.SEED, aov.SCENES
+PIXELS = WIDTH * HEIGHT
+CHANNELS = ("rgb", "variance", "half_a", "half_b")
+TRACE = 64
+ERR_INVALID, ERR_UNSUPPORTED = -1, -7
+WINDOW_NONE = 0xFFFFFFFF
+bits = ps.bits
+
+# The cases: scene, sqrtspp -> target, max_spp, the window; the floor is the default. Tuned on this tier so that REQUIRED holds and the
+# schedule has at most 6 batches (a pixel that sits out and comes back makes it longer than max_spp / n): the lists of the first are
+# 910, 574, 375, 221, 9, 2 pixels, those of the second 910, 910, 612, 496, 5.
+CASES = {
+    ("coffee_maker_qsah", 2): dict(target=0.6, max_spp=16, window=1),
+    ("hexagon_room_dof", 1): dict(target=0.6, max_spp=4, window=1),
+}
+MAIN = ("coffee_maker_qsah", 2)
+
+
+def load_adaptive_emu():
+    """Host build of the pass (tests/emu/adaptive_emu.cpp = wave_emu.hpp + mcrt_emu.cpp + csrc/mcrt_adaptive.hpp), the way
+    test_light_groups_emulation.load_light_groups_emu builds its library."""
+    src = os.path.join(TESTS, "emu", "adaptive_emu.cpp")
+    out = os.path.join(TESTS, "emu", "_build", "libadaptive_emu.so")
+    csrc = os.path.join(ROOT, "monte-carlo-ray-tracer_amd", "csrc")
+    deps = [src, os.path.join(TESTS, "emu", "mcrt_emu.cpp"), os.path.join(TESTS, "emu", "wave_emu.hpp"), os.path.join(ROOT, "include", "mcrt.h")] + \
+           [os.path.join(csrc, f) for f in os.listdir(csrc) if f.endswith(".hpp")]
+    if not os.path.exists(out) or any(os.path.getmtime(d) > os.path.getmtime(out) for d in deps):
+        os.makedirs(os.path.dirname(out), exist_ok=True)
+        tmp = "%s.%d.tmp" % (out, os.getpid())
+        subprocess.check_call(["g++", "-std=c++17", "-O2", "-ffp-contract=off", "-fPIC", "-shared", "-o", tmp, src])
+        os.replace(tmp, out)
+    L = C.CDLL(out)
+    vp = C.c_void_p
+    L.adaptive_emu_compact.argtypes = [vp, C.c_uint64, vp]
+    L.adaptive_emu_compact.restype = C.c_uint32
+    L.adaptive_emu_flags.argtypes = [vp, vp, vp, C.c_uint32, C.c_uint32, C.c_double, C.c_double, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, vp]
+    L.adaptive_emu_flags.restype = None
+    L.adaptive_emu_settings.argtypes = [vp, C.c_uint32, vp]
+    L.adaptive_emu_render.argtypes = [vp, vp, C.c_uint32, vp, C.c_int, C.c_uint64, C.c_int, vp, vp, vp, vp, vp, vp, vp]
+    return L
+
+
+@functools.lru_cache(maxsize=None)
+def _emu():
+    return load_adaptive_emu()
+
+
+def _pkg():
+    return importlib.import_module("monte-carlo-ray-tracer_amd")
+
+
+def params(target, max_spp=0, floor=0.0, window=None, min_batches=0):
+    return _pkg().Context._adaptive_params(target, max_spp, floor, window, min_batches)
+
+
+@functools.lru_cache(maxsize=None)
+def emu_render(scene, sqrtspp, target, max_spp=0, floor=0.0, window=None, min_batches=0, chunk_rays=0, full_form=0, seed=SEED, expect=0):
+    """The emulation's call -> dict rgb, variance, half_a, half_b [PIXELS, 3], count [PIXELS], active (list), samples, batches, floor,
+    rays, chunks. The arrays are filled with 0xAB bytes first (whatever is not written shows). Computed once per set of arguments."""
+    L = _emu()
+    out = {k: np.empty((PIXELS, 3)) for k in CHANNELS}
+    count = np.empty(PIXELS, dtype=np.uint32)
+    for a in list(out.values()) + [count]:
+        a.view(np.uint8).fill(0xAB)
+    active, info = np.zeros(TRACE, dtype=np.uint32), np.zeros(4, dtype=np.uint64)
+    par = params(target, max_spp, floor, window, min_batches)
+    rc = L.adaptive_emu_render(C.byref(aov._image(scene).scene), C.byref(aov.camera(scene, sqrtspp)), seed, C.byref(par), SCENES[scene], chunk_rays, full_form,
+                               *[out[k].ctypes.data for k in CHANNELS], count.ctypes.data, active.ctypes.data, info.ctypes.data)
+    assert rc == expect, "adaptive_emu_render: %d" % rc
+    out.update(count=count, batches=int(info[2]), active=[int(a) for a in active[:int(info[2])]], samples=int(count.astype(np.uint64).sum()),
+               floor=struct.unpack("d", struct.pack("Q", int(info[3])))[0], rays=int(info[0]), chunks=int(info[1]))
+    for a in out.values():
+        if isinstance(a, np.ndarray):
+            a.setflags(write=False)
+    return out
+
+
+# ------------------------------------------------------------------ the oracle
+@functools.lru_cache(maxsize=None)
+def oracle_converged(scene, sqrtspp, batches, seed=SEED):
+    """C_1 .. C_batches as a list of dicts of [PIXELS, 3] arrays (index k - 1): what mcrt_render_converged delivers at max_spp = k n, from
+    the oracle's per-sample radiances. Batch j is the store of seed + j, summarised as mcrt_render_pixel_stats does (rgb: the frame,
+    max(mean, 0)); batch 0 is C_1, every later one is merged into the frame before it. Where the host's libm is not the one
+    csrc/mcrt_libm.hpp restates, the oracle's samples differ from the device text's in last bits, which may flip a decision of the rule:
+    there the frames come from the emulation's own full batches (target 0), which test_the_degenerate_anchors holds to the oracle."""
+    n = sqrtspp * sqrtspp
+    if not host_libm_is_the_restated_one():
+        return [{k: emu_render(scene, sqrtspp, 0.0, max_spp=k_ * n, seed=seed)[k] for k in CHANNELS} for k_ in range(1, batches + 1)]
+    frames = []
+    for j in range(batches):
+        frame, store, want = ps.oracle_case(scene, sqrtspp, seed=(seed + j) & 0xFFFFFFFF)
+        batch = {"rgb": frame.reshape(-1, 3), "variance": want["variance"].reshape(-1, 3), "half_a": want["half_a"].reshape(-1, 3), "half_b": want["half_b"].reshape(-1, 3)}
+        frames.append(batch if j == 0 else acc.numpy_frame_merge(frames[-1], j * n, batch, n, channels=list(CHANNELS)))
+    return frames
+
+
+def numpy_noisy(rgb, variance, count, t2, f2):
+    """include/mcrt.h's criterion on [P, 3] frames and [P] counts -> [P] bool."""
+    with np.errstate(all="ignore"):
+        e = ((variance[:, 0] + variance[:, 1]) + variance[:, 2]) / count.astype(np.float64)
+        g = (rgb[:, 0] * rgb[:, 0] + rgb[:, 1] * rgb[:, 1]) + rgb[:, 2] * rgb[:, 2]
+        return (g == g) & (e > t2 * np.where(g > f2, g, f2))
+
+
+def numpy_dilate(noisy, width, height, r):
+    """A pixel is set when one within Chebyshev distance r, inside the frame, is."""
+    m = noisy.reshape(height, width)
+    out = np.zeros_like(m)
+    for dy in range(-r, r + 1):
+        for dx in range(-r, r + 1):
+            ys, yd = slice(max(dy, 0), height + min(dy, 0)), slice(max(-dy, 0), height + min(-dy, 0))
+            xs, xd = slice(max(dx, 0), width + min(dx, 0)), slice(max(-dx, 0), width + min(-dx, 0))
+            out[yd, xd] |= m[ys, xs]
+    return out.reshape(-1)
+
+
+def numpy_default_floor(c1, n):
+    """0.01 * sqrt(signal / pixels) of the frame after batch 0, signal by mcrt_frame_noise's treesum."""
+    _, signal = ps.numpy_frame_noise(c1["rgb"], c1["variance"], n)[:2]
+    with np.errstate(all="ignore"):
+        f = 0.01 * np.sqrt(np.float64(signal) / np.float64(c1["rgb"].shape[0]))
+    return float(f) if np.isfinite(f) and f >= 0.0 else 0.0
+
+
+REQUIRED = ("three_counts", "stops_20_80", "short_list", "ragged_list", "relisted")
+
+
+def replay(frames, n, target, max_spp, floor=0.0, window=None, min_batches=0, width=WIDTH, height=HEIGHT):
+    """The rule replayed on the converged frames C_k (frames[k - 1]) -> dict count [P], listed (a [P] bool per batch), active, samples,
+    floor, the outputs selected per pixel, and `conditions`: which of REQUIRED hold."""
+    pixels = width * height
+    r = 1 if window is None else int(window)
+    min_batches = max(min_batches or 1, 2 if n == 1 else 1)
+    t2 = np.float64(target) * np.float64(target)
+    f2 = np.float64(floor) * np.float64(floor)
+    stack = {k: np.stack([f[k] for f in frames]) for k in CHANNELS}  # [K, P, 3]
+    count = np.zeros(pixels, dtype=np.uint32)
+    listed_per_batch, relisted, sat_out = [], False, np.zeros(pixels, dtype=bool)
+    at = np.arange(pixels)
+    for j in range(TRACE):  # (a pixel that sits a batch out and comes back makes the schedule longer than max_spp / n batches)
+        room = count.astype(np.uint64) + n <= max_spp
+        if j < min_batches or target == 0.0:
+            listed = room
+        else:
+            k = count // n - 1
+            listed = room & numpy_dilate(numpy_noisy(stack["rgb"][k, at], stack["variance"][k, at], count, t2, f2), width, height, r)
+        if not listed.any():
+            break
+        relisted = relisted or bool((listed & sat_out).any())  # back after a batch it was not listed for
+        sat_out = sat_out | ~listed
+        listed_per_batch.append(listed)
+        count = count + np.where(listed, n, 0).astype(np.uint32)
+        if j == 0 and floor == 0.0:
+            floor = numpy_default_floor(frames[0], n)
+            f2 = np.float64(floor) * np.float64(floor)
+    k = count // n - 1
+    out = {c: stack[c][k, at] for c in CHANNELS}
+    active = [int(l.sum()) for l in listed_per_batch]
+    stopped = float((count < (max_spp // n) * n).mean())
+    out.update(count=count, listed=listed_per_batch, active=active, samples=int(count.astype(np.uint64).sum()), floor=float(floor),
+               conditions={"three_counts": len(np.unique(count)) >= 3, "stops_20_80": 0.2 <= stopped <= 0.8, "short_list": any(a < 256 for a in active),
+                           "ragged_list": any(a > 256 and a % 64 for a in active), "relisted": relisted})
+    return out
+
+
+def assert_matches(got, want, what):
+    """The call's outputs against the replay's, byte for byte, with a report of where they part."""
+    print("%s: active %s (replay %s), samples %d (replay %d), counts %s" % (what, got["active"], want["active"], got["samples"], want["samples"],
+                                                                         dict(zip(*[x.tolist() for x in np.unique(got["count"], return_counts=True)]))))
+    assert got["active"] == want["active"], what
+    np.testing.assert_array_equal(got["count"].reshape(-1), want["count"], err_msg=what)
+    assert got["samples"] == want["samples"], what
+    for k in CHANNELS:
+        differ = (bits(np.ascontiguousarray(got[k]).reshape(-1, 3)) != bits(want[k])).any(axis=1)
+        for q in np.nonzero(differ)[0][:5]:
+            print("   %s pixel %d (count %d): %r, replay %r" % (k, q, want["count"][q], np.asarray(got[k]).reshape(-1, 3)[q], want[k][q]))
+        assert not differ.any(), (what, k, int(differ.sum()))
+
+
+def case(scene, sqrtspp, **change):
+    """(the arguments of a case of CASES with `change` applied, its replay)."""
+    args = dict(CASES[(scene, sqrtspp)], **change)
+    n = sqrtspp * sqrtspp
+    return args, replay(oracle_converged(scene, sqrtspp, args["max_spp"] // n), n, **args)
+
+
+# ------------------------------------------------------------------ the schedule against the replay
+@pytest.mark.parametrize("scene,sqrtspp", sorted(CASES))
+def test_the_schedule_is_the_replay_of_the_rule_on_converged_frames(scene, sqrtspp):
+    args, want = case(scene, sqrtspp)
+    print("%s sqrtspp %d: conditions %s, floor %.6g" % (scene, sqrtspp, want["conditions"], want["floor"]))
+    for name in REQUIRED:
+        assert want["conditions"][name], (name, want["active"], np.unique(want["count"], return_counts=True))
+    got = emu_render(scene, sqrtspp, **args)
+    assert got["batches"] == len(want["active"]) <= 6
+    assert bits(np.float64(got["floor"])) == bits(np.float64(want["floor"]))
+    assert_matches(got, want, "%s sqrtspp %d" % (scene, sqrtspp))
+
+
+@pytest.mark.parametrize("window", [0, 4])
+def test_the_window(window):
+    """Radius 0 and 4 match the replay as radius 1 does; with radius 0 no pixel is listed that is not noisy itself."""
+    scene, sqrtspp = MAIN
+    args, want = case(scene, sqrtspp, window=window)
+    assert len(np.unique(want["count"])) >= 2 and 0 < want["active"][-1] < PIXELS
+    assert_matches(emu_render(scene, sqrtspp, **args), want, "window %d" % window)
+    _, one = case(scene, sqrtspp)
+    assert want["samples"] != one["samples"]  # the radius reaches the schedule
+
+
+def test_chunks_of_the_list_and_the_form_of_a_full_batch_do_not_reach_the_bytes():
+    scene, sqrtspp = MAIN
+    args, want = case(scene, sqrtspp)
+    whole = emu_render(scene, sqrtspp, **args)
+    longest_partial = max(a for a in want["active"] if a < PIXELS)
+    chunk_rays = (longest_partial // 3) * 4 * 2  # slots: pixels * spp * 2 - at least three chunks for that list
+    cut = emu_render(scene, sqrtspp, chunk_rays=chunk_rays, **args)
+    assert whole["chunks"] == whole["batches"] and cut["chunks"] >= whole["chunks"] + 2 * sum(1 for a in want["active"] if a >= longest_partial)
+    merged = emu_render(scene, sqrtspp, full_form=1, **args)
+    for other, what in ((cut, "chunks"), (merged, "full batches through batch frames")):
+        assert other["active"] == whole["active"] and other["rays"] == whole["rays"], what
+        for k in CHANNELS + ("count",):
+            assert other[k].tobytes() == whole[k].tobytes(), (what, k)
+
+
+# ------------------------------------------------------------------ the degenerate anchors
+@pytest.mark.parametrize("scene,sqrtspp", sorted(CASES))
+def test_the_degenerate_anchors(scene, sqrtspp):
+    """Target 0: every batch is full, the count uniform, the outputs the converged frame's at max_spp - here against the oracle's samples
+    summarised and merged in numpy (the same bits where the host's libm is the restated one). A huge target with min_batches 1: one batch,
+    the frame and channels of mcrt_render_pixel_stats (sqrtspp 1: two, min_batches being 2 there)."""
+    from conftest import assert_oracle_bits
+    n = sqrtspp * sqrtspp
+    max_spp = CASES[(scene, sqrtspp)]["max_spp"]
+    got = emu_render(scene, sqrtspp, 0.0, max_spp=max_spp)
+    assert got["active"] == [PIXELS] * (max_spp // n) and (got["count"] == max_spp).all() and got["samples"] == PIXELS * max_spp
+    frames = []
+    for j in range(max_spp // n):
+        frame, store, want = ps.oracle_case(scene, sqrtspp, seed=SEED + j)
+        batch = {"rgb": frame.reshape(-1, 3), "variance": want["variance"].reshape(-1, 3), "half_a": want["half_a"].reshape(-1, 3), "half_b": want["half_b"].reshape(-1, 3)}
+        frames.append(batch if j == 0 else acc.numpy_frame_merge(frames[-1], j * n, batch, n, channels=list(CHANNELS)))
+    for k in CHANNELS:
+        assert_oracle_bits(got[k], frames[-1][k], "%s sqrtspp %d target 0: %s" % (scene, sqrtspp, k), rel=1e-9)
+    once = emu_render(scene, sqrtspp, 1e30, max_spp=max_spp, min_batches=1)
+    first = 2 if sqrtspp == 1 else 1
+    assert once["active"] == [PIXELS] * first and (once["count"] == first * n).all()
+    for k in CHANNELS:
+        assert_oracle_bits(once[k], frames[first - 1][k], "%s sqrtspp %d one batch: %s" % (scene, sqrtspp, k), rel=1e-9)
+
+
+# ------------------------------------------------------------------ the rule alone
+def emu_flags(rgb, variance, count, width, height, target, floor, n, max_spp, window, force=0):
+    flags = np.full(width * height, 0xAB, dtype=np.uint8)
+    rgb, variance, count = (np.ascontiguousarray(a) for a in (rgb, variance, count))
+    _emu().adaptive_emu_flags(rgb.ctypes.data, variance.ctypes.data, count.ctypes.data, width, height, np.float64(target) * np.float64(target),
+                              np.float64(floor) * np.float64(floor), n, max_spp, window, force, flags.ctypes.data)
+    return flags
+
+
+def quiet_frame(width, height, n=4):
+    pixels = width * height
+    return np.full((pixels, 3), 0.5), np.full((pixels, 3), 1e-8), np.full(pixels, n, dtype=np.uint32)
+
+
+@pytest.mark.parametrize("window", [0, 1, 4])
+def test_a_noisy_pixel_lists_exactly_its_clipped_neighbourhood(window):
+    """... at the four corners, on the four edges and inside a 70 x 13 frame."""
+    w, h = WIDTH, HEIGHT
+    for x, y in [(0, 0), (w - 1, 0), (0, h - 1), (w - 1, h - 1), (33, 0), (33, h - 1), (0, 6), (w - 1, 6), (33, 6), (2, 1)]:
+        rgb, variance, count = quiet_frame(w, h)
+        variance[y * w + x] = 1.0
+        flags = emu_flags(rgb, variance, count, w, h, 0.1, 0.0, 4, 64, window).reshape(h, w)
+        want = np.zeros((h, w), dtype=np.uint8)
+        want[max(y - window, 0):y + window + 1, max(x - window, 0):x + window + 1] = 1
+        np.testing.assert_array_equal(flags, want, err_msg="pixel (%d, %d), window %d" % (x, y, window))
+        np.testing.assert_array_equal(flags.reshape(-1), numpy_dilate(numpy_noisy(rgb, variance, count, 0.01, 0.0), w, h, window).astype(np.uint8))
+
+
+def test_a_nan_pixel_retires_and_does_not_spread():
+    w, h = WIDTH, HEIGHT
+    for channel in ("rgb", "variance"):
+        rgb, variance, count = quiet_frame(w, h)
+        (rgb if channel == "rgb" else variance)[5 * w + 17, 1] = np.nan
+        variance[5 * w + 40] = 1.0  # (a noisy pixel elsewhere: the rule is at work)
+        flags = emu_flags(rgb, variance, count, w, h, 0.1, 0.25, 4, 64, 1).reshape(h, w)
+        assert flags[4:7, 39:42].all() and flags.sum() == 9, channel
+        assert not flags[3:8, 15:20].any(), channel
+    # an infinite variance is noisy, not NaN: it stays listed
+    rgb, variance, count = quiet_frame(w, h)
+    variance[3, 0] = np.inf
+    assert emu_flags(rgb, variance, count, w, h, 0.1, 0.0, 4, 64, 0).sum() == 1
+
+
+def test_the_floor_the_room_and_the_forced_batches():
+    w, h = 9, 5
+    rgb, variance, count = quiet_frame(w, h)
+    rgb[:], variance[:] = 1e-3, 1e-6  # dark: relative to itself every pixel is noisy, relative to the floor none
+    assert emu_flags(rgb, variance, count, w, h, 0.1, 0.0, 4, 64, 0).all()
+    assert not emu_flags(rgb, variance, count, w, h, 0.1, 0.5, 4, 64, 0).any()
+    # a pixel without room for a batch is not listed, whatever its noise or the forcing
+    count[7] = 61
+    assert emu_flags(rgb, variance, count, w, h, 0.1, 0.0, 4, 64, 1).sum() == w * h - 1
+    assert emu_flags(rgb, variance, count, w, h, 0.1, 0.5, 4, 64, 1, force=1).sum() == w * h - 1
+    count[:] = 60
+    assert emu_flags(rgb, variance, count, w, h, 0.1, 0.0, 4, 64, 1).all()
+    count[:] = 0  # before batch 0: forced, nothing of the accumulators is read (NaN frames would not matter)
+    rgb[:] = np.nan
+    assert emu_flags(rgb, variance, count, w, h, 0.1, 0.0, 4, 64, 1, force=1).all()
+
+
+# ------------------------------------------------------------------ the list alone
+def emu_compact(flags):
+    flags = np.ascontiguousarray(flags, dtype=np.uint8)
+    out = np.full(flags.size, 0xABABABAB, dtype=np.uint32)
+    length = _emu().adaptive_emu_compact(flags.ctypes.data, flags.size, out.ctypes.data)
+    assert (out[length:] == 0xABABABAB).all()  # nothing is written behind the list
+    return out[:length]
+
+
+def compaction_cases():
+    """name -> flags: what the device test runs too."""
+    rng = np.random.default_rng(11)
+    cases = {"all set": np.ones(PIXELS, np.uint8), "none set": np.zeros(PIXELS, np.uint8), "the last pixel": np.zeros(PIXELS, np.uint8),
+             "across a workgroup boundary": np.zeros(PIXELS, np.uint8), "across a wave boundary": np.zeros(700, np.uint8), "one pixel": np.ones(1, np.uint8),
+             "random": (rng.random(PIXELS) < 0.3).astype(np.uint8), "values other than 1": (rng.integers(0, 4, 517) * 85).astype(np.uint8),
+             "more blocks than lanes of the scan": (rng.random(256 * 300 + 5) < 0.02).astype(np.uint8)}
+    cases["the last pixel"][-1] = 1
+    cases["across a workgroup boundary"][250:262] = 1
+    cases["across a workgroup boundary"][767:769] = 1
+    cases["across a wave boundary"][60:70] = 1
+    return cases
+
+
+@pytest.mark.parametrize("name", sorted(compaction_cases()))
+def test_the_list_is_the_ascending_indices_of_the_set_flags(name):
+    flags = compaction_cases()[name]
+    np.testing.assert_array_equal(emu_compact(flags), np.nonzero(flags)[0].astype(np.uint32), err_msg=name)
+
+
+# ------------------------------------------------------------------ the settings and what is refused
+def test_defaults_and_refusals():
+    L = _emu()
+
+    def settings(sqrtspp, *a, **k):
+        out = np.zeros(5)
+        rc = L.adaptive_emu_settings(C.byref(params(*a, **k)) if a or k else None, sqrtspp, out.ctypes.data)
+        return rc, list(out)
+    assert settings(2) == (0, [0.0, -1.0, 1024, 1, 1])
+    assert settings(1)[1][3] == 2 and settings(1, 0.1, min_batches=1)[1][3] == 2 and settings(1, 0.1, min_batches=3)[1][3] == 3
+    assert settings(40)[1][2] == 1600
+    assert settings(2, 0.25, 64, 0.5, 4, 3) == (0, [0.25, 0.5, 64, 3, 4])
+    assert settings(2, 0.25, window=0)[1][4] == 0 and settings(2, 0.25, window=None)[1][4] == 1
+    for bad in (dict(target=-0.1), dict(target=np.nan), dict(target=np.inf), dict(target=0.1, floor=-1.0),
+                dict(target=0.1, floor=np.inf), dict(target=0.1, floor=np.nan), dict(target=0.1, window=5),
+                dict(target=0.1, max_spp=3)):
+        assert settings(2, **bad)[0] == ERR_INVALID, bad
+    assert settings(0)[0] == ERR_INVALID
+    par = params(0.1)
+    par.window = WINDOW_NONE - 1
+    assert L.adaptive_emu_settings(C.byref(par), 2, None) == ERR_INVALID
+    # the camera: a shard, a film that splats
+    pkg = _pkg()
+    scene = "hexagon_room_dof"
+    cam = aov.camera(scene, 2, shard=(0, 2, 1))
+    out = [np.zeros((PIXELS, 3)) for _ in CHANNELS]
+    count = np.zeros(PIXELS, dtype=np.uint32)
+
+    def render(cam):
+        return L.adaptive_emu_render(C.byref(aov._image(scene).scene), C.byref(cam), SEED, None, SCENES[scene], 0, 0, *[a.ctypes.data for a in out], count.ctypes.data, None, None)
+    assert render(cam) == ERR_UNSUPPORTED
+    cam = aov.camera(scene, 2)
+    cam.film_filter = pkg.FILM_FILTERS["gaussian"]
+    assert render(cam) == ERR_UNSUPPORTED
