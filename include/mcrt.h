@@ -1578,7 +1578,9 @@ void mcrt_photon_map_free(mcrt_photon_map* map);
  * surfaces, one node per non-empty octant with the union of its surfaces' boxes — built by sorting per-surface octant
  * path codes instead of inserting one surface at a time. The result is the reference's tree
  * bit for bit: same LinearNode arrays, same surface order (tests/test_bvh_build.py rebuilds every golden octree BVH,
- * up to the 6.9 M-triangle C5 scene). `scene` needs its surface arrays, quadrics, bb_min/bb_max; its node arrays are
+ * up to the 6.9 M-triangle C5 scene; tests/test_bvh_awkward.py compares bytes, on centroids on octant mid-planes and on the
+ * cube's far faces among others). A box coordinate that is zero has the reference's sign: that of the first surface, in input
+ * order, of the first octant, in octant order, that attains it (BoundingBox::merge keeps the first). `scene` needs its surface arrays, quadrics, bb_min/bb_max; its node arrays are
  * ignored. ctx != NULL: boxes, codes and the radix sort run on the GPU of ctx; ctx == NULL: host only.
  * MCRT_ERR_UNSUPPORTED when more than 8 centroids share one 2^-21 cell of the root cube. */
 typedef struct mcrt_bvh_desc {
@@ -1594,13 +1596,18 @@ typedef struct mcrt_bvh mcrt_bvh;       /* opaque; owns the arrays its descripto
 int  mcrt_bvh_build_octree(mcrt_ctx* ctx /* may be NULL */, const mcrt_scene_desc* scene, mcrt_bvh** out);
 /* The reference's other two hierarchies, "binary_sah" (arity 2) and "quaternary_sah" (arity 4): its binned surface-area
  * builders (bvh/bvh.cpp:165-426) restated with the same arithmetic and tie rules — same tree — and run on `threads` host
- * threads (0 = all), one subtree per thread. bins_per_axis 0 = the reference's default (16 / 8). Host only. */
+ * threads (0 = all), one subtree per thread. bins_per_axis 0 = the reference's default (16 / 8). Host only.
+ * The tree depends on the ORDER of the input surfaces where the reference's does: a node that cannot be split by position is
+ * dealt round-robin (surface i of the node to part i % arity), and a box coordinate that is zero has the sign of the first
+ * surface of the node, in input order, whose own box coordinate is zero (-0.0 and +0.0 are different bytes in node_bounds). */
 int  mcrt_bvh_build_sah(const mcrt_scene_desc* scene, int arity, uint32_t bins_per_axis, uint32_t threads, mcrt_bvh** out);
 /* The same two hierarchies built LEVEL BY LEVEL — all open nodes of a depth at once: centroid bounds, binning and the
  * order-preserving partition are passes over the surfaces on the GPU of ctx (atomics on exact minima / maxima / counts, one
  * prefix sum per level), the split of every open node is decided by one thread with the reference's cost loop, the host
  * only strings the nodes together (csrc/mcrt_sah_shared.hpp, mcrt_sah_gpu.hip). Same tree as mcrt_bvh_build_sah and the
- * reference, bit for bit. ctx == NULL runs the same level loop on the host (one thread). bins_per_axis <= 16. */
+ * reference, bit for bit - the signs of zero box coordinates included, which the atomic reductions do not give and a host
+ * step over the zero coordinates alone restores. ctx == NULL runs the same level loop on the host (one thread). More than
+ * 16 bins per axis: built by mcrt_bvh_build_sah on all host threads, same tree. */
 int  mcrt_bvh_build_sah_gpu(mcrt_ctx* ctx /* may be NULL */, const mcrt_scene_desc* scene, int arity, uint32_t bins_per_axis, mcrt_bvh** out);
 const mcrt_bvh_desc* mcrt_bvh_get(const mcrt_bvh* bvh);
 void mcrt_bvh_free(mcrt_bvh* bvh);

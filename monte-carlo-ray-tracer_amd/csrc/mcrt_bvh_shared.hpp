@@ -103,16 +103,37 @@ inline bool assembleOctreeBvh(const unsigned long long* keys, const uint32_t* in
             bb[3 + c] = -1.7976931348623157e308;
         }
         const uint64_t lo = M.start[l], hi = lo + M.contained[l];
-        for (uint64_t i = lo; i < hi; i++) {  // BoundingBox::merge(BB), bounding-box.cpp:56-63
-            const double* sb = sorted_bb + i * 6;
+        // insertion order inside a leaf = input order, for the list and for the box: BoundingBox::merge (bounding-box.cpp:56-63) keeps the
+        // FIRST box that attains an extreme, which decides the sign of a coordinate that is zero (bvh.cpp:139-144)
+        uint64_t at[kBvhLeafSurfaces];
+        const uint64_t cnt = hi - lo;  // <= kBvhLeafSurfaces (a deeper cell was refused above)
+        for (uint64_t i = 0; i < cnt; i++) at[i] = lo + i;
+        std::sort(at, at + cnt, [&](uint64_t a, uint64_t b) { return index[a] < index[b]; });
+        for (uint64_t i = 0; i < cnt; i++) {
+            const double* sb = sorted_bb + at[i] * 6;
             for (int c = 0; c < 3; c++) {
                 if (bb[c] > sb[c]) bb[c] = sb[c];
                 if (bb[3 + c] < sb[3 + c]) bb[3 + c] = sb[3 + c];
             }
         }
-        std::sort(B->order.begin() + lo, B->order.begin() + hi);  // insertion order inside a leaf = input order
+        std::sort(B->order.begin() + lo, B->order.begin() + hi);
     }
-    A.mergeBounds();
+    // inner nodes: the children's boxes in octant order, first seen wins again (bvh.cpp:149-158); children have larger indices
+    for (uint32_t i = nodes; i-- > 0;) {
+        if (M.leaf[i]) continue;
+        double* p = &M.bounds[(size_t)i * 6];
+        for (int c = 0; c < 3; c++) {
+            p[c] = 1.7976931348623157e308;
+            p[3 + c] = -1.7976931348623157e308;
+        }
+        for (uint32_t ch = i + 1; ch != 0xFFFFFFFFu; ch = M.next[ch]) {
+            const double* b = &M.bounds[(size_t)ch * 6];
+            for (int c = 0; c < 3; c++) {
+                if (p[c] > b[c]) p[c] = b[c];
+                if (p[3 + c] < b[3 + c]) p[3 + c] = b[3 + c];
+            }
+        }
+    }
     B->bounds = M.bounds;
     finishBvhDesc(B);
     return true;

@@ -9,6 +9,8 @@
 //      64-bit words of two 32-bit counters each), new position = run start + child's offset + own rank; the parts of an
 //      arbitrary split are dealt in closed form; surfaces of closed nodes stay where they are
 //   7. (rare) boxes of round-robin parts: one more atomic pass over those runs
+//   8. (rare) the sign of box coordinates that are zero: the ordered keys put -0.0 below +0.0, the reference keeps the first surface's
+//      zero; the host settles those from a slice of the new order (sahZeroSigns, mcrt_sah_shared.hpp)
 // The host reads back the splits (a few hundred bytes per open node), appends the children to the node table and uploads
 // the next level's open nodes; the depth-first numbering (BVH::compact) is a host pass over the finished table.
 #include <hip/hip_runtime.h>
@@ -301,6 +303,7 @@ int mcrt::bvhSahGpu(mcrt_ctx* ctx, const mcrt_scene_desc* s, int arity, int bins
     std::vector<SahSplit> splits;
     std::vector<Run> runs;
     std::vector<double> arb_box;
+    std::vector<uint32_t> zero_order;
     uint32_t* order = d_order.as<uint32_t>();
     uint32_t* order_next = d_order2.as<uint32_t>();
     while (!segs.empty()) {
@@ -356,6 +359,23 @@ int mcrt::bvhSahGpu(mcrt_ctx* ctx, const mcrt_scene_desc* s, int arity, int bins
             hipLaunchKernelGGL(decodeKeysKernel, dim3(gridFor(runs.size() * 6)), dim3(256), 0, 0, d_run_box.as<unsigned long long>(), (uint64_t)runs.size() * 6);
             SAH_TRY(hipGetLastError());
             SAH_TRY(hipMemcpy(arb_box.data(), d_run_box.p, runs.size() * 48, hipMemcpyDeviceToHost));
+        }
+        {   // signs of zero box coordinates (sahForZeroCoords): rare, settled on the host from the slice of the new order that holds the runs
+            uint32_t lo = 0xFFFFFFFFu, hi = 0u;
+            sahForZeroCoords(segs, splits, arb_box.data(), true, [&](double*, int, uint32_t start, uint32_t size) {
+                lo = start < lo ? start : lo;
+                hi = start + size > hi ? start + size : hi;
+            });
+            if (lo < hi) {
+                zero_order.resize(hi - lo);
+                SAH_TRY(hipMemcpy(zero_order.data(), order + lo, (size_t)(hi - lo) * 4, hipMemcpyDeviceToHost));
+                sahZeroSigns(segs, splits, arb_box.data(), true, [&](uint32_t p, int c) {
+                    const uint32_t surf = zero_order[p - lo];
+                    double b[6];
+                    surfaceBounds(s->surf_kind[surf], s->surf_v + 9 * (size_t)surf, s->quadrics, b);  // the kernel's own expression: same bits
+                    return b[c];
+                });
+            }
         }
         sahGrow(T, segs, splits, arb_box.data(), next);
         segs.swap(next);

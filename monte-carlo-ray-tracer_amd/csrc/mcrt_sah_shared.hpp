@@ -307,6 +307,51 @@ inline void sahGrow(SahTree& T, const std::vector<SahSeg>& segs, const std::vect
     }
 }
 
+// The sign of a box coordinate that is zero. BoundingBox::merge keeps the FIRST box that attains an extreme (`if (min > b) min = b`,
+// bounding-box.cpp:56-63; -0.0 > +0.0 is false), and the reference merges a child's box over the child's surfaces in node order
+// (bvh.cpp:255-268, :396-411, :462-468): a zero coordinate of a child's box has the sign of the first surface of the child's run whose
+// own box coordinate is zero. The level loop gets the children's boxes otherwise - from the bins in bin order (sahEvaluate), on the GPU
+// from atomic minima / maxima on ordered keys, which put -0.0 below +0.0 - so the values are the reference's but a zero's sign need
+// not be. This visits every zero coordinate of the boxes that sahGrow is about to consume, with the child's run of the NEW working
+// order: visit(coordinate, c, start, size). `from_keys`: the boxes of round-robin parts were reduced on ordered keys alone, so a
+// minimum +0.0 (no contributor is -0.0) and a maximum -0.0 (none is +0.0) are right as they are and are not visited. (A binned
+// child's box is a first-seen merge of per-bin key reductions: nothing follows from its sign.)
+template <class Visit>
+inline void sahForZeroCoords(const std::vector<SahSeg>& segs, std::vector<SahSplit>& splits, double* arb_box, bool from_keys, Visit visit) {
+    size_t arb_at = 0;
+    for (size_t i = 0; i < segs.size(); i++) {
+        SahSplit& s = splits[i];
+        if (s.mode == kSahLeafMode) continue;
+        const uint32_t parts = s.mode == kSahBinary ? 2u : s.mode == kSahQuad ? 4u : s.arb;
+        uint32_t at = segs[i].start;
+        for (uint32_t k = 0; k < parts; k++) {
+            const uint32_t sz = s.child_size[k];
+            double* b = s.mode == kSahArb ? arb_box + 6 * (arb_at++) : s.child_box[k];
+            if (sz == 0) continue;
+            for (int c = 0; c < 6; c++) {
+                if (b[c] != 0.0) continue;
+                if (from_keys && s.mode == kSahArb && std::signbit(b[c]) != (c < 3)) continue;
+                visit(b + c, c, at, sz);
+            }
+            at += sz;
+        }
+    }
+}
+
+// ... and gives each the reference's sign. coord(p, c): box coordinate c of the surface at position p of the new working order.
+template <class Coord>
+inline void sahZeroSigns(const std::vector<SahSeg>& segs, std::vector<SahSplit>& splits, double* arb_box, bool from_keys, Coord coord) {
+    sahForZeroCoords(segs, splits, arb_box, from_keys, [&](double* x, int c, uint32_t start, uint32_t size) {
+        for (uint32_t p = start; p < start + size; p++) {
+            const double v = coord(p, c);
+            if (v == 0.0) {  // the first surface that attains the extreme
+                *x = v;
+                return;
+            }
+        }
+    });
+}
+
 inline void sahCompactInto(const SahTree& T, uint32_t node, uint32_t next_sibling, const uint32_t* subtree, mcrt_bvh* B) {
     // iterative depth-first walk (trees over coincident centroids get deep)
     struct Item { uint32_t node, next; };
@@ -443,6 +488,7 @@ inline int buildSahLevelsHost(const double* bb, const double* centroid, uint64_t
                 }
             }
         }
+        sahZeroSigns(segs, splits, arb_box.data(), false, [&](uint32_t p, int c) { return bb[(size_t)order[p] * 6 + c]; });
         sahGrow(T, segs, splits, arb_box.data(), next);
         segs.swap(next);
     }

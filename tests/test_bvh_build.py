@@ -55,10 +55,10 @@ def test_level_synchronous_sah_host(pkg, manifest, name, kind):
     assert _check_same_tree(pkg, img, kind=kind, levels=True) == img.scene.num_nodes > 0
 
 
-def test_level_synchronous_sah_equals_recursive_on_awkward_input(pkg):
+def _awkward_input(pkg):
     """Surfaces the split rules have trouble with: 700 triangles sharing one centroid (no usable axis, more than a leaf
     holds: arbitrarySplit, bvh.cpp:451-473), a line of centroids (the quaternary rule falls back to the binary one for the
-    whole subtree, bvh.cpp:313-318) and a cloud; the level-synchronous build against the recursive restatement."""
+    whole subtree, bvh.cpp:313-318) and a cloud. -> (scene descriptor, the arrays it points into)"""
     rng = np.random.default_rng(5)
     tris = []
     for i in range(700):  # same centroid, different sizes
@@ -94,6 +94,12 @@ def test_level_synchronous_sah_equals_recursive_on_awkward_input(pkg):
     pts = v.reshape(-1, 3)
     sc.bb_min[:] = pts.min(axis=0).tolist()
     sc.bb_max[:] = pts.max(axis=0).tolist()
+    return sc, (v, e, kind, interp, mat, area, m)
+
+
+def test_level_synchronous_sah_equals_recursive_on_awkward_input(pkg):
+    """The level-synchronous build against the recursive restatement on _awkward_input."""
+    sc, keep = _awkward_input(pkg)
     for kind_name in ("quaternary_sah", "binary_sah"):
         a = pkg.Bvh(sc, kind=kind_name, threads=1)
         b = pkg.Bvh(sc, kind=kind_name, levels=True)
@@ -103,6 +109,23 @@ def test_level_synchronous_sah_equals_recursive_on_awkward_input(pkg):
             np.testing.assert_array_equal(ra[k], rb[k], err_msg="%s %s" % (kind_name, k))
         a.close()
         b.close()
+
+
+@pytest.mark.gpu
+def test_gpu_level_synchronous_sah_equals_recursive_on_awkward_input(pkg):
+    """The same input through the kernels of csrc/mcrt_sah_gpu.hip, all five arrays compared as bytes (-0.0 is not +0.0)."""
+    sc, keep = _awkward_input(pkg)
+    ctx = pkg.Context(0)
+    for kind_name in ("quaternary_sah", "binary_sah"):
+        a = pkg.Bvh(sc, kind=kind_name, threads=1)
+        b = pkg.Bvh(sc, ctx=ctx, kind=kind_name)
+        ra, rb = a.arrays(), b.arrays()
+        assert len(ra["start"]) > 500
+        for k in ("bounds", "start", "count", "next", "order"):
+            assert ra[k].shape == rb[k].shape and ra[k].tobytes() == rb[k].tobytes(), "%s %s" % (kind_name, k)
+        a.close()
+        b.close()
+    ctx.close()
 
 
 @pytest.mark.parametrize("name,nodes", [("c3", 169162), ("c4", 153801), ("spaceship", 23187)])
