@@ -394,4 +394,23 @@ inline void bindIteration(uint64_t it, unsigned long long* ctrl, WfShadeArgs& sa
     }
 }
 
+// ---- mcrt_bsdf ---------------------------------------------------------------------------------------------------------------------
+// bsdfKernel's constants from the ABI's consts[10] = roughness, reflectance[3], complex IOR real[3], imaginary[3]: the Oren-Nayar
+// material as Material::computeProperties leaves it (material/material.cpp:99,106-108) - rough only above C::EPSILON, Lambertian below.
+inline void fillBsdfKatConsts(BsdfKatConsts& c, const double* consts) {
+    memset(&c, 0, sizeof(c));
+    c.rough.roughness = consts[0];
+    for (int k = 0; k < 3; k++) {
+        c.rough.reflectance[k] = consts[1 + k];
+        c.real[k] = consts[4 + k];
+        c.imag[k] = consts[7 + k];
+    }
+    const double variance = c.rough.roughness * c.rough.roughness;
+    c.rough.A = 1.0 - 0.5 * (variance / (variance + 0.33));
+    c.rough.B = 0.45 * (variance / (variance + 0.09));
+    c.rough.flags = c.rough.roughness > kEpsilon ? MCRT_MAT_ROUGH : 0u;
+}
+// bsdfKernel's workgroups of 256 lanes: past 2048 of them the lanes stride over the vectors
+inline uint32_t bsdfGrid(uint64_t n) { return (uint32_t)std::min<uint64_t>(2048, (n + 255) / 256); }
+
 #endif  // MCRT_LAUNCH_KERNEL_ARGS

@@ -1314,7 +1314,7 @@ void oracle_bsdf_kat(uint64_t n, const double* in, const double* consts, double*
     double variance = pow2(rough.roughness); /* material.cpp:106-108 */
     rough.A = 1.0 - 0.5 * (variance / (variance + 0.33));
     rough.B = 0.45 * (variance / (variance + 0.09));
-    rough.flags = MCRT_MAT_ROUGH;
+    rough.flags = rough.roughness > EPSILON ? MCRT_MAT_ROUGH : 0u; /* material.cpp:99 */
     v3 real = ld3(consts + 4), imag = ld3(consts + 7);
     for (uint64_t i = 0; i < n; i++) {
         const double* I = in + 11 * i; double* O = out + 18 * i;

@@ -10,7 +10,9 @@
 //      (the value Camera::sampleImage stores into camera.image, camera.cpp:138-144), timing only
 //      the worker section (the reference's own timer is quantised to 1 s, camera.cpp:131,224);
 //   3. "kat":     calls individual reference functions on seeded random inputs and dumps
-//      known-answer vectors (the reference has no tests of its own).
+//      known-answer vectors (the reference has no tests of its own);
+//   4. "bsdf":    the kat mode's lobe-function rows (Fresnel / GGX / Oren-Nayar) on inputs read from files:
+//      the edge vectors of tests/golden/make_bsdf_edges.py.
 //
 // Private members are reached with -fno-access-control (this TU only; layout is unaffected).
 #include <atomic>
@@ -51,7 +53,7 @@
 namespace {
 
 struct Args {
-    std::string mode, scene, out, out_samples, out_radiance, out_kat;
+    std::string mode, scene, out, out_samples, out_radiance, out_kat, consts, in;
     int camera = 0;
     bool photon = false;
     long width = -1, height = -1, sqrtspp = -1, threads = -1;
@@ -80,6 +82,7 @@ struct Args {
         "   [--specular-roughness material value]... [--n N]\n"
         "   [--save base key=value,...]... (render of the full frame: Image::save to base.tga; keys of the \"image\" object, \"-\" = none)\n"
         "   --out image.mcrt (flatten) --out-radiance file.f64 [--out-samples file.f64] (render) --out-kat dir (kat)\n"
+        "   mcrt_ref bsdf --consts consts.f64 --in in.f64 --out out.f64 (the kat mode's lobe-function rows on given inputs; no scene)\n"
         "   several modes in one run share ONE Camera/Scene/photon map (photon order is thread-dependent)\n");
     std::exit(2);
 }
@@ -96,6 +99,8 @@ Args parse(int argc, char** argv) {
         else if (k == "--out-samples") a.out_samples = next();
         else if (k == "--out-radiance") a.out_radiance = next();
         else if (k == "--out-kat") a.out_kat = next();
+        else if (k == "--consts") a.consts = next();
+        else if (k == "--in") a.in = next();
         else if (k == "--camera") a.camera = std::stoi(next());
         else if (k == "--photon") a.photon = true;
         else if (k == "--width") a.width = std::stol(next());
@@ -118,6 +123,7 @@ Args parse(int argc, char** argv) {
         else if (k == "--specular-roughness") { std::string m = next(); a.rough.push_back({m, std::stod(next())}); }
         else usage();
     }
+    if (a.mode == "bsdf") { if (a.consts.empty() || a.in.empty() || a.out.empty()) usage(); return a; }
     if (a.scene.empty()) usage();
     // single-mode shorthand: --out names that mode's output
     if (a.mode == "render" && a.out_radiance.empty()) a.out_radiance = a.out;
@@ -319,6 +325,61 @@ glm::dvec3 randDir(Rng& r) {
     return glm::dvec3(s * std::cos(phi), s * std::sin(phi), z);
 }
 
+// One row of the lobe-function vectors, for doKat's seeded inputs and for doBsdf's inputs from a file alike.
+// in: wi(3) wo(3) n1 n2 alpha u v | out: F_dielectric, conductor(3), GGX refl (f,pdf), GGX trans (f,pdf),
+//     visibleMicrofacet(3), D(m), Lambda(wo), OrenNayar-diffuse (rgb, pdf)
+// consts: roughness, reflectance(3) of the diffuse material (rough as Material::computeProperties decides), complex IOR real(3), imaginary(3)
+struct BsdfKat {
+    Material rough_mat;
+    ComplexIOR cior;
+    explicit BsdfKat(const double* c) : cior(glm::dvec3(c[4], c[5], c[6]), glm::dvec3(c[7], c[8], c[9])) {
+        rough_mat.roughness = c[0]; rough_mat.reflectance = glm::dvec3(c[1], c[2], c[3]);
+        rough_mat.computeProperties();
+    }
+    void row(const double* I, double* O) {
+        const glm::dvec3 wi(I[0], I[1], I[2]), wo(I[3], I[4], I[5]);
+        const double n1 = I[6], n2 = I[7], alpha = I[8], u = I[9], v = I[10];
+        glm::dvec2 al(alpha);
+        O[0] = Fresnel::dielectric(n1, n2, wo.z);
+        glm::dvec3 fc = Fresnel::conductor(n1, &cior, wo.z);
+        O[1] = fc.x; O[2] = fc.y; O[3] = fc.z;
+        glm::dvec3 wir = wi; wir.z = std::abs(wir.z) + 1e-3; wir = glm::normalize(wir);
+        double pdf;
+        O[4] = GGX::reflection(wir, wo, al, pdf); O[5] = pdf;
+        glm::dvec3 wit = -wir;
+        O[6] = GGX::transmission(wit, wo, n1, n2, al, pdf); O[7] = pdf;
+        glm::dvec3 m = GGX::visibleMicrofacet(u, v, wo, al);
+        O[8] = m.x; O[9] = m.y; O[10] = m.z;
+        O[11] = GGX::D(m, al);
+        O[12] = GGX::Lambda(wo, al);
+        glm::dvec3 d = rough_mat.diffuseReflection(wir, wo, pdf);
+        O[13] = d.x; O[14] = d.y; O[15] = d.z; O[16] = pdf;
+        O[17] = 0.0;
+    }
+};
+
+// bsdf: the same rows on inputs read from files (no scene): consts[10] and in[n][11] -> out[n][18], raw FP64
+std::vector<double> readDoubles(const std::string& path) {
+    std::ifstream f(path, std::ios::binary | std::ios::ate);
+    if (!f) { std::fprintf(stderr, "cannot open %s\n", path.c_str()); std::exit(1); }
+    std::vector<double> v((size_t)f.tellg() / sizeof(double));
+    f.seekg(0);
+    f.read(reinterpret_cast<char*>(v.data()), (std::streamsize)(v.size() * sizeof(double)));
+    return v;
+}
+
+int doBsdf(const Args& a) {
+    const std::vector<double> consts = readDoubles(a.consts), in = readDoubles(a.in);
+    if (consts.size() != 10 || in.empty() || in.size() % 11) { std::fprintf(stderr, "bsdf: --consts holds 10 doubles, --in 11 per row\n"); return 2; }
+    const size_t n = in.size() / 11;
+    std::vector<double> out(n * 18);
+    BsdfKat kat(consts.data());
+    for (size_t i = 0; i < n; i++) kat.row(&in[i * 11], &out[i * 18]);
+    writeRaw(a.out, out.data(), out.size() * 8);
+    std::printf("bsdf: %zu rows -> %s\n", n, a.out.c_str());
+    return 0;
+}
+
 int doKat(const Args& a, Camera& camera) {
     std::string dir = a.out_kat;
     std::filesystem::create_directories(dir);
@@ -373,11 +434,9 @@ int doKat(const Args& a, Camera& camera) {
         //     visibleMicrofacet(3), D(m), Lambda(wo), OrenNayar-diffuse (rgb, pdf)
         const size_t n = std::min<size_t>(N, 20000);
         std::vector<double> in(n * 11), out(n * 18);
-        Material rough_mat;
-        rough_mat.roughness = 0.7; rough_mat.reflectance = glm::dvec3(0.8, 0.6, 0.4);
-        rough_mat.computeProperties();
-        ComplexIOR cior(glm::dvec3(0.27, 0.68, 1.32), glm::dvec3(3.6, 2.6, 2.3));
-        writeRaw(dir + "/bsdf_consts.f64", (const double[]){0.7, 0.8, 0.6, 0.4, 0.27, 0.68, 1.32, 3.6, 2.6, 2.3}, 80);
+        const double consts[10] = {0.7, 0.8, 0.6, 0.4, 0.27, 0.68, 1.32, 3.6, 2.6, 2.3};
+        BsdfKat kat(consts);
+        writeRaw(dir + "/bsdf_consts.f64", consts, 80);
         for (size_t i = 0; i < n; i++) {
             glm::dvec3 wo = randDir(rng); wo.z = std::abs(wo.z) + 1e-3; wo = glm::normalize(wo);
             glm::dvec3 wi = randDir(rng);
@@ -386,23 +445,7 @@ int doKat(const Args& a, Camera& camera) {
             double* I = &in[i * 11];
             I[0] = wi.x; I[1] = wi.y; I[2] = wi.z; I[3] = wo.x; I[4] = wo.y; I[5] = wo.z;
             I[6] = n1; I[7] = n2; I[8] = alpha; I[9] = u; I[10] = v;
-            double* O = &out[i * 18];
-            glm::dvec2 al(alpha);
-            O[0] = Fresnel::dielectric(n1, n2, wo.z);
-            glm::dvec3 fc = Fresnel::conductor(n1, &cior, wo.z);
-            O[1] = fc.x; O[2] = fc.y; O[3] = fc.z;
-            glm::dvec3 wir = wi; wir.z = std::abs(wir.z) + 1e-3; wir = glm::normalize(wir);
-            double pdf;
-            O[4] = GGX::reflection(wir, wo, al, pdf); O[5] = pdf;
-            glm::dvec3 wit = -wir;
-            O[6] = GGX::transmission(wit, wo, n1, n2, al, pdf); O[7] = pdf;
-            glm::dvec3 m = GGX::visibleMicrofacet(u, v, wo, al);
-            O[8] = m.x; O[9] = m.y; O[10] = m.z;
-            O[11] = GGX::D(m, al);
-            O[12] = GGX::Lambda(wo, al);
-            glm::dvec3 d = rough_mat.diffuseReflection(wir, wo, pdf);
-            O[13] = d.x; O[14] = d.y; O[15] = d.z; O[16] = pdf;
-            O[17] = 0.0;
+            kat.row(I, &out[i * 18]);
         }
         writeRaw(dir + "/bsdf_in.f64", in.data(), in.size() * 8);
         writeRaw(dir + "/bsdf_out.f64", out.data(), out.size() * 8);
@@ -467,6 +510,7 @@ int doKat(const Args& a, Camera& camera) {
 int main(int argc, char** argv) {
     Args a = parse(argc, argv);
     try {
+        if (a.mode == "bsdf") return doBsdf(a);
         nlohmann::json j = loadScene(a);
         Camera camera(j, Option(a.scene, "", a.camera, a.photon));
         int rc = 0, did = 0;

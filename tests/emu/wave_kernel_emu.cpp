@@ -151,6 +151,18 @@ int wemu_trace_kernel(const mcrt_scene_desc* scene, uint64_t n, const double* st
     return stats[kStatOverflow] ? -100 : 0;
 }
 
+// bsdfKernel (mcrt_bsdf: the lobe functions on n local-frame vectors, include/mcrt.h) on emulated workgroups, its constants filled and
+// its grid sized by what mcrt_bsdf fills and sizes them with (fillBsdfKatConsts, bsdfGrid). grid_cap: 0 = that grid, else at most so many
+// workgroups, so that a few thousand vectors take the lanes' stride loop more than once. in[n][11], consts[10], out[n][18].
+int wemu_bsdf(uint64_t n, const double* in, const double* consts, double* out, uint32_t grid_cap) {
+    if (n == 0) return 0;
+    BsdfKatConsts c;
+    fillBsdfKatConsts(c, consts);
+    const uint32_t grid = grid_cap ? std::min(grid_cap, bsdfGrid(n)) : bsdfGrid(n);
+    launchGrid(grid, 256, [&] { bsdfKernel(n, in, c, out); });
+    return 0;
+}
+
 // ---- whole frames ------------------------------------------------------------------------------------------------------------------
 // The frame kernels of launchRender (mcrt_hip.hip) - renderKernel<path tracer, flat>, renderKernelSM, renderKernelPM - and
 // sampleResolveKernel on emulated workgroups: DeviceScene filled from the host layout the way mcrt_upload_scene fills it (same staging

@@ -18,6 +18,7 @@ import numpy as np
 import pytest
 
 from conftest import camera_for, check_hits_against_reference, golden_path, load_radiance, rel_error
+from kat_bits import BSDF_COLUMNS, assert_same_bits, edge_groups, load_edge_group
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-4
@@ -246,7 +247,7 @@ def test_sampler_bits_exact(pkg, ctx, manifest):
     for shuffles in range(5):
         sel = inp[:, 2] == shuffles
         out = ctx.sampler(inp[sel, 0].copy(), inp[sel, 1].copy(), shuffles, manifest["seed"])
-        np.testing.assert_array_equal(out, ref[sel])
+        assert_same_bits(out, ref[sel], inputs=inp[sel], what="sampler, %d shuffles" % shuffles)
 
 
 def test_bsdf_kat(pkg, ctx, manifest):
@@ -262,8 +263,71 @@ def test_bsdf_kat(pkg, ctx, manifest):
     out = ctx.bsdf(inp, consts)
     # every column: +,-,*,/ and sqrt are correctly rounded, contraction is off, and visibleMicrofacet's sin / cos pair (columns 8-10, which
     # D(m), column 11, inherits) is glibc's sincos restated (csrc/mcrt_libm.hpp) since round 3
-    np.testing.assert_array_equal(out, ref)
+    assert_same_bits(out, ref, inputs=inp, columns=BSDF_COLUMNS, what="mcrt_bsdf, kat_hexagon_room")
     print("bsdf KAT: %d vectors x 18 columns bit-equal" % len(inp))
+
+
+def _report_edges(group, out, ref):
+    """Per column, what the GPU returned on an edge group: how many values are not the reference's bits (NaN for NaN), and how many
+    of the reference's are NaN, -0.0, subnormal or infinite."""
+    from kat_bits import mismatches
+    bad = mismatches(out, ref)
+    for c in range(18):
+        r = ref[:, c]
+        print("%s column %2d %-20s mismatches %4d / %d   (reference: NaN %4d, -0.0 %3d, subnormal %3d, inf %4d)" % (
+            group, c, BSDF_COLUMNS[c], int(bad[:, c].sum()), len(r), int(np.isnan(r).sum()), int(((r == 0) & np.signbit(r)).sum()),
+            int(((r != 0) & (np.abs(r) < 2.2250738585072014e-308)).sum()), int(np.isinf(r).sum())))
+
+
+@pytest.mark.parametrize("group", edge_groups())
+def test_bsdf_edges(pkg, ctx, group):
+    """mcrt_bsdf at the edges of the lobe functions' domain (tests/golden/kat_bsdf_edges, the reference's own answers): the `len2 == 0`
+    branch and the clamps of GGX::visibleMicrofacet, `g2 < 0` of Fresnel::dielectric at the critical angle and to either side of it,
+    n1 == n2, the 0 / 0 of Oren-Nayar, a roughness on either side of C::EPSILON, quotients and roots with subnormal, infinite and huge
+    operands and results, phi at 0 and 2 pi. Every value the reference's bits, the sign of a zero included; NaN where it has NaN."""
+    consts, inp, ref = load_edge_group(group)
+    out = ctx.bsdf(inp, consts)
+    _report_edges(group, out, ref)
+    assert_same_bits(out, ref, inputs=inp, columns=BSDF_COLUMNS, what="mcrt_bsdf, " + group)
+
+
+@pytest.mark.parametrize("n", [1, 255, 256, 257])
+def test_bsdf_edges_small_counts(pkg, ctx, n):
+    """One lane, one workgroup short of a lane, a full one, and one lane of a second workgroup."""
+    consts, inp, ref = load_edge_group("g0")
+    assert_same_bits(ctx.bsdf(inp[:n], consts), ref[:n], inputs=inp, columns=BSDF_COLUMNS, what="mcrt_bsdf, g0[:%d]" % n)
+
+
+def _tiled(a, n):
+    return np.ascontiguousarray(np.resize(a, (n, a.shape[1])))  # row i = a[i mod m]
+
+
+def test_bsdf_edges_grid_stride(pkg, ctx):
+    """More vectors than the grid has lanes (2048 workgroups of 256): every lane takes the stride loop a second time, 257 of them a
+    third time. Row i must be the fixture's row i mod m."""
+    consts, inp, ref = load_edge_group("g0")
+    n = 2048 * 256 + 257
+    out = ctx.bsdf(_tiled(inp, n), consts)
+    assert out.shape == (n, 18)
+    assert_same_bits(out, _tiled(ref, n), columns=BSDF_COLUMNS, what="mcrt_bsdf, g0 tiled to %d rows" % n)
+    print("bsdf edges: %d vectors (%d passes over g0) x 18 columns bit-equal" % (n, -(-n // len(inp))))
+
+
+def test_bsdf_operator_scratch_reuse(pkg, ctx, manifest):
+    """The operators share one scratch (op_buf), grown and never shrunk: a large mcrt_bsdf, then mcrt_sampler on a few inputs, then
+    mcrt_bsdf on one vector, then on the group - the same bits each time, whatever the buffers held before."""
+    consts, inp, ref = load_edge_group("g0")
+    n = 2048 * 256 + 257
+    big_ref = _tiled(ref, n)
+    assert_same_bits(ctx.bsdf(_tiled(inp, n), consts), big_ref, columns=BSDF_COLUMNS, what="mcrt_bsdf, large call")
+    d = golden_path(manifest["cases"]["hexagon_room"]["kat"])
+    sin = np.fromfile(os.path.join(d, "sampler_in.u32"), dtype=np.uint32).reshape(-1, 3)
+    sref = np.fromfile(os.path.join(d, "sampler_out.f64")).reshape(-1, 7)
+    sel = np.nonzero(sin[:, 2] == 2)[0][:5]
+    assert_same_bits(ctx.sampler(sin[sel, 0].copy(), sin[sel, 1].copy(), 2, manifest["seed"]), sref[sel], inputs=sin[sel], what="mcrt_sampler after the large call")
+    last = len(inp) - 1
+    assert_same_bits(ctx.bsdf(inp[last:], consts), ref[last:], inputs=inp[last:], columns=BSDF_COLUMNS, what="mcrt_bsdf, one vector")
+    assert_same_bits(ctx.bsdf(inp, consts), ref, inputs=inp, columns=BSDF_COLUMNS, what="mcrt_bsdf, g0 after the others")
 
 
 @pytest.mark.parametrize("name", ["hexagon_room", "hexagon_room_diffuse", "coffee_maker_qsah", "ior_test", "quadric"])

@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 from conftest import camera_for, golden_path, load_radiance, rel_error
+from kat_bits import BSDF_COLUMNS, assert_same_bits, edge_groups, load_edge_group
 
 
 def _cases(manifest):
@@ -93,7 +94,15 @@ def test_bsdf_kat(oracle, manifest):
     ref = np.fromfile(os.path.join(d, "bsdf_out.f64")).reshape(-1, 18)
     consts = np.fromfile(os.path.join(d, "bsdf_consts.f64"))
     out = oracle.bsdf_kat(inp, consts)
-    np.testing.assert_array_equal(out, ref)
+    assert_same_bits(out, ref, inputs=inp, columns=BSDF_COLUMNS, what="oracle, kat_hexagon_room")
+
+
+@pytest.mark.parametrize("group", edge_groups())
+def test_bsdf_edges(oracle, group):
+    """The lobe functions at the edges of their domain (tests/golden/kat_bsdf_edges: every branch, NaN, -0.0, subnormal and infinite
+    operands and results, a roughness on either side of C::EPSILON), the sign of a zero included, NaN for NaN."""
+    consts, inp, ref = load_edge_group(group)
+    assert_same_bits(oracle.bsdf_kat(inp, consts), ref, inputs=inp, columns=BSDF_COLUMNS, what="oracle, " + group)
 
 
 def test_knn_kat(pkg, oracle, manifest):
