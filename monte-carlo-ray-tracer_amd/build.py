@@ -18,13 +18,15 @@ LIB = os.path.join(CSRC, "libmcrt_hip.so")
 LIB_TOL = os.path.join(CSRC, "libmcrt_hip_tol.so")
 TOL_FLAGS = ["-ffp-contract=fast", "-DMCRT_PLATFORM_LIBM", "-DMCRT_TOLERANCE_BUILD"]
 RENDER_BIN = os.path.join(HOST, "mcrt_render")
-# The kernels of the image passes are shared libraries of their own, one translation unit each, which both libraries above link (the
-# tolerance one too: the exact objects): the gfx950 functions of libmcrt_hip.so stay the render path's, the set
-# tests/golden/device_code_hashes.json lists; tests/test_{aov,denoise,pixel_stats,robust,denoise_var,accumulate,denoise_dual,exr,matte,compare,exr_read,occlusion,lighting,light_groups,path_classes,adaptive}_library.py hold what each library may contain.
-# They have to lie next to libmcrt_hip.so wherever that goes (RUNPATH $ORIGIN). In link order: the first-hit AOV pass, the a-trous filter,
-# the per-pixel sample statistics, the firefly suppression, the variance-guided a-trous filter, the frame merge of accumulated rendering, the dual-buffer filter, the pack of the OpenEXR output, the ranking of the ID mattes, the frame comparison, the occlusion pass, the lighting passes, the light groups, the path classes, the rule, the list and the walk of adaptive sampling, the kernels of the OpenEXR input.
-SIDE_LIBS = [(os.path.join(CSRC, "lib%s.so" % name), name + ".hip") for name in ("mcrt_aov", "mcrt_denoise", "mcrt_pixel_stats", "mcrt_robust", "mcrt_denoise_var", "mcrt_accumulate", "mcrt_denoise_dual", "mcrt_exr", "mcrt_matte", "mcrt_compare", "mcrt_occlusion", "mcrt_lighting", "mcrt_light_groups", "mcrt_path_classes", "mcrt_adaptive", "mcrt_exr_read")]
-LIB_AOV, LIB_DENOISE, LIB_PIXEL_STATS, LIB_ROBUST, LIB_DENOISE_VAR, LIB_ACCUMULATE, LIB_DENOISE_DUAL, LIB_EXR, LIB_MATTE, LIB_COMPARE, LIB_OCCLUSION, LIB_LIGHTING, LIB_LIGHT_GROUPS, LIB_PATH_CLASSES, LIB_ADAPTIVE, LIB_EXR_READ = (lib for lib, _ in SIDE_LIBS)
+# The image passes, one stem each, in link order. A stem stands for two files: the kernels in csrc/<stem>.hip become a shared library of
+# their own, lib<stem>.so (one translation unit, compiled and linked in one step), and the host side in csrc/<stem>_host.hip goes into
+# both main libraries above, which link every lib<stem>.so (the tolerance one too: the exact objects). So the gfx950 functions of
+# libmcrt_hip.so stay the render path's, the set tests/golden/device_code_hashes.json lists; tests/side_libraries.py holds what each
+# library may contain. The side libraries have to lie next to libmcrt_hip.so wherever that goes (RUNPATH $ORIGIN).
+PASSES = ("mcrt_aov", "mcrt_denoise", "mcrt_pixel_stats", "mcrt_robust", "mcrt_denoise_var", "mcrt_accumulate", "mcrt_denoise_dual",
+          "mcrt_exr", "mcrt_matte", "mcrt_compare", "mcrt_occlusion", "mcrt_lighting", "mcrt_light_groups", "mcrt_path_classes",
+          "mcrt_adaptive", "mcrt_exr_read")
+SIDE_LIBS = [(os.path.join(CSRC, "lib%s.so" % stem), stem + ".hip") for stem in PASSES]
 
 # -ffp-contract=off: the CPU reference is compiled by g++ for baseline x86-64 (no FMA contraction);
 # per-pixel FP64 parity needs the same rounding sequence on the GPU.
@@ -61,7 +63,9 @@ def sources():
 
 # the translation units that hold kernels of the render path: the tolerance library has its own objects of these
 KERNEL_TUS = ("mcrt_hip.hip", "mcrt_hip_lean.hip")
-TUS = ["mcrt_hip.hip", "mcrt_hip_lean.hip", "mcrt_octree_gpu.hip", "mcrt_sah_gpu.hip", "mcrt_output.hip", "mcrt_aov_host.hip", "mcrt_denoise_host.hip", "mcrt_pixel_stats_host.hip", "mcrt_robust_host.hip", "mcrt_denoise_var_host.hip", "mcrt_accumulate_host.hip", "mcrt_denoise_dual_host.hip", "mcrt_exr_host.hip", "mcrt_matte_host.hip", "mcrt_compare_host.hip", "mcrt_multi.hip", "mcrt_image.cpp", "mcrt_octree.cpp", "mcrt_bvh.cpp", "mcrt_exr_read_host.hip", "mcrt_occlusion_host.hip", "mcrt_lighting_host.hip", "mcrt_light_groups_host.hip", "mcrt_path_classes_host.hip", "mcrt_adaptive_host.hip"]
+CORE_TUS = ["mcrt_hip.hip", "mcrt_hip_lean.hip", "mcrt_octree_gpu.hip", "mcrt_sah_gpu.hip", "mcrt_output.hip", "mcrt_multi.hip", "mcrt_image.cpp",
+            "mcrt_octree.cpp", "mcrt_bvh.cpp"]
+TUS = CORE_TUS + [stem + "_host.hip" for stem in PASSES]
 OBJ = os.path.join(CSRC, "_obj")
 
 
@@ -141,7 +145,7 @@ def build_lib(force=False, verbose=True, tolerance=False, both=False):
     for tol in variants:
         lib, objs = (LIB_TOL if tol else LIB), _objects(tol)
         if jobs or not os.path.exists(lib) or any(os.path.getmtime(o) > os.path.getmtime(lib) for o in objs):
-            run([_hipcc(), "--offload-arch=gfx950", "-shared", "-fPIC", "-o", lib] + objs + ["-L" + CSRC] + ["-l" + os.path.basename(side_lib)[3:-3] for side_lib, _ in SIDE_LIBS] + ["-Wl,-rpath,$ORIGIN"])
+            run([_hipcc(), "--offload-arch=gfx950", "-shared", "-fPIC", "-o", lib] + objs + ["-L" + CSRC] + ["-l" + stem for stem in PASSES] + ["-Wl,-rpath,$ORIGIN"])
     return LIB_TOL if tolerance and not both else LIB
 
 

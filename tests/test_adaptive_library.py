@@ -1,101 +1,23 @@
-"""Adaptive sampling is a code object of its own, like the image passes before it. libmcrt_adaptive.so holds exactly the pass's ten
-kernels, without scratch and within the registers profiles/NOTES_adaptive.md records (its table is read here: the numbers are upper
-bounds); libmcrt_hip.so - the render path's device code, listed function by function in tests/golden/device_code_hashes.json - and the
-other side libraries hold no kernel of these names, and the main libraries find the new one next to themselves (RUNPATH $ORIGIN). What the
-calls refuse is checked here as far as no GPU is needed."""
+"""What only adaptive sampling has (tests/side_libraries.py holds what libmcrt_adaptive.so may contain, within the registers
+profiles/NOTES_adaptive.md records): the binding's struct layouts and parameters, and what the calls refuse as far as no GPU is needed."""
 import ctypes as C
-import importlib.util
-import os
-import re
-import subprocess
 
 import numpy as np
 
-from conftest import ROOT
+from side_libraries import c_values
 
-CSRC = os.path.join(ROOT, "monte-carlo-ray-tracer_amd", "csrc")
-KERNELS = ["adaptiveBeginKernel", "adaptiveCameraRayKernel", "adaptiveCountKernel", "adaptiveFlagKernel", "adaptiveMergeKernel", "adaptiveRayKernel",
-           "adaptiveResolveKernel", "adaptiveScanKernel", "adaptiveScatterKernel", "adaptiveStepKernel"]
-SHADING = ("adaptiveRayKernel", "adaptiveStepKernel")
-# LDS: the shading kernels stage the Sobol byte tables, the sine / cosine table and 8 history entries for each of 256 lanes; the camera
-# rays the Sobol tables; the list's kernels four wave sums, the scan two rows of 256 lane sums
-LDS = {"adaptiveRayKernel": 6 * 4 * 256 * 4 + 440 * 8 + 8 * 256 * 8, "adaptiveStepKernel": 6 * 4 * 256 * 4 + 440 * 8 + 8 * 256 * 8, "adaptiveCameraRayKernel": 6 * 4 * 256 * 4,
-       "adaptiveCountKernel": 16, "adaptiveScatterKernel": 16, "adaptiveScanKernel": 2 * 256 * 4}
 PARAM_FIELDS = ["target_relative_error", "floor", "max_spp", "min_batches", "window"]
 RESULT_FIELDS = ["batches", "min_count", "max_count", "samples", "active"]
 
 
-def _tool(name):
-    spec = importlib.util.spec_from_file_location(name, os.path.join(ROOT, "tools", name + ".py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return mod
-
-
-def recorded_resources():
-    """The table of profiles/NOTES_adaptive.md: kernel -> dict of vgpr, vgpr_spill, sgpr_spill, scratch, lds."""
-    rows = {}
-    for line in open(os.path.join(ROOT, "profiles", "NOTES_adaptive.md")):
-        m = re.match(r"\|\s*`(adaptive\w+Kernel)`\s*\|\s*(\d+)\s*\|\s*(\d+)\s*\|\s*(\d+)\s*\|\s*(\d+)\s*\|\s*(\d+)\s*\|", line)
-        if m:
-            rows[m.group(1)] = dict(zip(("vgpr", "vgpr_spill", "sgpr_spill", "scratch", "lds"), (int(x) for x in m.groups()[1:])))
-    return rows
-
-
-def test_the_adaptive_kernels_live_beside_the_render_path(pkg):
-    pkg.lib()
-    table = _tool("kernel_spill_table")
-    kernels = {k["name"]: k for k in table.kernels_of(os.path.join(CSRC, "libmcrt_adaptive.so"))}
-    assert sorted(kernels) == KERNELS
-    recorded = recorded_resources()
-    assert sorted(recorded) == KERNELS
-    for name, k in kernels.items():
-        assert k["scratch"] == 0 and k["vgpr_spill"] == 0, (name, k)  # (spilled SGPRs go to lanes of a VGPR, not to memory)
-        if name not in SHADING:
-            assert k["sgpr_spill"] == 0, (name, k)  # the rule, the list, the camera rays, begin, resolve and merge: no spill of any kind
-        assert k["max_wg"] == 256, name
-        for word, bound in recorded[name].items():
-            assert k[word] <= bound, (name, word, k[word], bound)
-        assert k["lds"] == LDS.get(name, 0), name
-    others = sorted(f for f in os.listdir(CSRC) if f.startswith("libmcrt_") and f.endswith(".so") and f != "libmcrt_adaptive.so")
-    assert len(others) >= 16, others
-    for lib in others:
-        names = [k["name"] for k in table.kernels_of(os.path.join(CSRC, lib))]
-        assert names and not [n for n in names if n in KERNELS or n.startswith("adaptive")], lib
-
-
-def test_the_libraries_find_the_adaptive_library_next_to_themselves():
-    assert os.path.exists(os.path.join(CSRC, "libmcrt_hip.so"))
-    for lib in ("libmcrt_hip.so", "libmcrt_hip_tol.so"):
-        path = os.path.join(CSRC, lib)
-        if lib.endswith("_tol.so") and not os.path.exists(path):
-            continue  # (MCRT_SKIP_TOLERANCE_BUILD=1 builds)
-        dyn = subprocess.run(["readelf", "-d", path], check=True, capture_output=True, text=True).stdout
-        assert "[libmcrt_adaptive.so]" in dyn, lib
-        assert any("$ORIGIN" in l for l in dyn.splitlines() if "RUNPATH" in l or "RPATH" in l), lib
-
-
-def test_the_calls_are_exported_and_the_abi_version_stays(pkg):
-    L = pkg.lib()
-    for name in ("mcrt_render_adaptive", "mcrt_render_adaptive_device", "mcrt_adaptive_list"):
-        assert hasattr(L, name), name
-    assert L.mcrt_abi_version() == 2
-    for name in ("AdaptiveParams", "AdaptiveResult", "ADAPTIVE_WINDOW_NONE"):
-        assert hasattr(pkg, name), name
-    for name in ("render_adaptive", "render_adaptive_device", "adaptive_list"):
-        assert hasattr(pkg.Context, name), name
+def test_the_structs_of_the_binding_have_the_header_s_fields(pkg):
     assert [k for k, _ in pkg.AdaptiveParams._fields_] == PARAM_FIELDS and [k for k, _ in pkg.AdaptiveResult._fields_] == RESULT_FIELDS
 
 
 def test_the_binding_lays_the_structs_out_as_the_header_does(pkg, tmp_path):
-    src = tmp_path / "sizes.c"
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "mcrt.h"\nint main(void){printf("%zu %zu %u %u ' + "%zu " * (len(PARAM_FIELDS) + len(RESULT_FIELDS))
-                   + '\\n",sizeof(mcrt_adaptive_params),sizeof(mcrt_adaptive_result),(unsigned)MCRT_CONVERGE_TRACE,(unsigned)MCRT_ADAPTIVE_WINDOW_NONE,'
-                   + ",".join("offsetof(mcrt_adaptive_params,%s)" % k for k in PARAM_FIELDS) + ","
-                   + ",".join("offsetof(mcrt_adaptive_result,%s)" % k for k in RESULT_FIELDS) + ');return 0;}\n')
-    exe = tmp_path / "sizes"
-    subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), "-o", str(exe), str(src)])
-    sizes = [int(x) for x in subprocess.check_output([str(exe)]).split()]
+    sizes = c_values(tmp_path, ["sizeof(mcrt_adaptive_params)", "sizeof(mcrt_adaptive_result)", "(unsigned)MCRT_CONVERGE_TRACE", "(unsigned)MCRT_ADAPTIVE_WINDOW_NONE"]
+                     + ["offsetof(mcrt_adaptive_params,%s)" % k for k in PARAM_FIELDS] + ["offsetof(mcrt_adaptive_result,%s)" % k for k in RESULT_FIELDS],
+                     "%zu %zu %u %u " + "%zu " * (len(PARAM_FIELDS) + len(RESULT_FIELDS)))
     assert sizes == [C.sizeof(pkg.AdaptiveParams), C.sizeof(pkg.AdaptiveResult), pkg.CONVERGE_TRACE, pkg.ADAPTIVE_WINDOW_NONE] + \
         [getattr(pkg.AdaptiveParams, k).offset for k in PARAM_FIELDS] + [getattr(pkg.AdaptiveResult, k).offset for k in RESULT_FIELDS]
     assert sizes[0] == 32

@@ -1,10 +1,7 @@
-"""The frame comparison is a code object of its own, like the image passes before it. libmcrt_compare.so holds exactly the three kernels -
-the pixel level, the upper levels of the tree sums, the SSIM tiles - without spills or scratch and without a call (so no libm routine: the
-device code is + - * /, compare and select); libmcrt_hip.so - the render path's device code, listed function by function in
-tests/golden/device_code_hashes.json - and the other side libraries hold no kernel of it, and the main libraries find the new one next to
-themselves (RUNPATH $ORIGIN)."""
+"""What only the frame comparison has (tests/side_libraries.py holds what libmcrt_compare.so may contain): the device code is without a
+call (so no libm routine: it is + - * /, compare and select), three SSIM workgroups fit a CU, the binding's struct layouts, exr_layers'
+names of the error maps."""
 import ctypes as C
-import importlib.util
 import os
 import re
 import shutil
@@ -12,34 +9,13 @@ import subprocess
 
 import numpy as np
 
-from conftest import ROOT
+from side_libraries import CSRC, TABLE, c_values, tool as _tool
 
-CSRC = os.path.join(ROOT, "monte-carlo-ray-tracer_amd", "csrc")
 LIB = os.path.join(CSRC, "libmcrt_compare.so")
 
 
-def _tool(name):
-    spec = importlib.util.spec_from_file_location(name, os.path.join(ROOT, "tools", name + ".py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return mod
-
-
-def test_the_three_kernels_live_beside_the_render_path(pkg):
-    pkg.lib()
-    table = _tool("kernel_spill_table")
-    kernels = {k["name"]: k for k in table.kernels_of(LIB)}
-    assert sorted(kernels) == ["compareLevelKernel", "comparePixelsKernel", "compareSsimKernel"]
-    for name, k in kernels.items():
-        assert k["vgpr_spill"] == 0 and k["sgpr_spill"] == 0 and k["scratch"] == 0, (name, k)
-    assert kernels["comparePixelsKernel"]["lds"] == 2 * 3 * 256 * 8   # the two frames' words of a block; the tree reuses them
-    assert kernels["compareLevelKernel"]["lds"] == 9 * 256 * 8        # four sums, the maximum's values and indices, three counts
-    assert kernels["compareSsimKernel"]["lds"] == 2 * 42 * 26 * 8 + 5 * 26 * 32 * 8 <= 160 * 1024 // 3  # three workgroups per CU
-    others = sorted(f for f in os.listdir(CSRC) if f.startswith("libmcrt_") and f.endswith(".so") and f != "libmcrt_compare.so")
-    assert len(others) >= 10, others
-    for lib in others:
-        names = [k["name"] for k in table.kernels_of(os.path.join(CSRC, lib))]
-        assert names and not [n for n in names if n.startswith("compare") or "ssim" in n.lower()], lib
+def test_three_ssim_workgroups_fit_a_cu():
+    assert TABLE["mcrt_compare"]["lds"]["compareSsimKernel"] == 2 * 42 * 26 * 8 + 5 * 26 * 32 * 8 <= 160 * 1024 // 3  # three workgroups per CU
 
 
 def test_the_device_code_calls_nothing(pkg, tmp_path):
@@ -66,41 +42,15 @@ def test_the_device_code_calls_nothing(pkg, tmp_path):
     assert len(table.kernels_of(LIB)) == 3
 
 
-def test_the_libraries_find_the_compare_library_next_to_themselves():
-    assert os.path.exists(os.path.join(CSRC, "libmcrt_hip.so"))
-    for lib in ("libmcrt_hip.so", "libmcrt_hip_tol.so"):
-        path = os.path.join(CSRC, lib)
-        if lib.endswith("_tol.so") and not os.path.exists(path):
-            continue  # (MCRT_SKIP_TOLERANCE_BUILD=1 builds)
-        dyn = subprocess.run(["readelf", "-d", path], check=True, capture_output=True, text=True).stdout
-        assert "[libmcrt_compare.so]" in dyn, lib
-        assert any("$ORIGIN" in l for l in dyn.splitlines() if "RUNPATH" in l or "RPATH" in l), lib
-
-
-def test_the_calls_are_exported_and_the_abi_version_stays(pkg):
-    L = pkg.lib()
-    for name in ("mcrt_frame_compare", "mcrt_frame_compare_device"):
-        assert hasattr(L, name), name
-    assert L.mcrt_abi_version() == 2
-    for name in ("CompareParams", "CompareMaps", "CompareResult", "COMPARE_MAPS", "exr_layers"):
-        assert hasattr(pkg, name), name
-    for name in ("frame_compare", "frame_compare_device"):
-        assert hasattr(pkg.Context, name), name
-
-
 def test_the_binding_lays_the_structs_out_as_the_header_does(pkg, tmp_path):
-    src = tmp_path / "sizes.c"
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "mcrt.h"\nint main(void){printf("%zu %zu %zu %zu %zu %zu %zu %zu %a\\n",sizeof(mcrt_compare_params),'
-                   'sizeof(mcrt_compare_maps),sizeof(mcrt_compare_result),offsetof(mcrt_compare_params,want_ssim),offsetof(mcrt_compare_result,max_abs_pixel),'
-                   'offsetof(mcrt_compare_result,pixels),offsetof(mcrt_compare_result,ssim_excluded),offsetof(mcrt_compare_result,mean_ssim),(double)MCRT_SSIM_G0);return 0;}\n')
-    exe = tmp_path / "sizes"
-    subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), "-o", str(exe), str(src)])
-    out = subprocess.check_output([str(exe)]).split()
-    assert [int(x) for x in out[:8]] == [C.sizeof(pkg.CompareParams), C.sizeof(pkg.CompareMaps), C.sizeof(pkg.CompareResult), pkg.CompareParams.want_ssim.offset,
-                                         pkg.CompareResult.max_abs_pixel.offset, pkg.CompareResult.pixels.offset, pkg.CompareResult.ssim_excluded.offset,
-                                         pkg.CompareResult.mean_ssim.offset]
+    sizes = c_values(tmp_path, ["sizeof(mcrt_compare_params)", "sizeof(mcrt_compare_maps)", "sizeof(mcrt_compare_result)", "offsetof(mcrt_compare_params,want_ssim)",
+                                "offsetof(mcrt_compare_result,max_abs_pixel)", "offsetof(mcrt_compare_result,pixels)", "offsetof(mcrt_compare_result,ssim_excluded)",
+                                "offsetof(mcrt_compare_result,mean_ssim)"], "%zu %zu %zu %zu %zu %zu %zu %zu")
+    assert sizes == [C.sizeof(pkg.CompareParams), C.sizeof(pkg.CompareMaps), C.sizeof(pkg.CompareResult), pkg.CompareParams.want_ssim.offset,
+                     pkg.CompareResult.max_abs_pixel.offset, pkg.CompareResult.pixels.offset, pkg.CompareResult.ssim_excluded.offset,
+                     pkg.CompareResult.mean_ssim.offset]
     assert C.sizeof(pkg.CompareParams) == 32 and C.sizeof(pkg.CompareResult) == 160
-    assert float.fromhex(out[8].decode()) == 0.26601172486179436
+    assert c_values(tmp_path, ["(double)MCRT_SSIM_G0"], "%a", parse=float.fromhex) == [0.26601172486179436]
 
 
 def test_exr_layers_of_errors_names_types_and_views(pkg):

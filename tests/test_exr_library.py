@@ -1,70 +1,13 @@
-"""The pack of the OpenEXR output is a code object of its own, like the seven image passes before it. libmcrt_exr.so holds exactly
-exrPackKernel, without spills or scratch (its channel table is dynamic LDS, sized per launch); libmcrt_hip.so - the render path's device
-code, listed function by function in tests/golden/device_code_hashes.json - and the other side libraries hold no kernel of it, the main
-libraries find the new one next to themselves (RUNPATH $ORIGIN), and zlib is not linked: it is looked up when a ZIP file is first saved."""
-import importlib.util
-import os
-import subprocess
+"""What only the pack of the OpenEXR output has (tests/side_libraries.py holds what libmcrt_exr.so may contain, and that zlib is not
+linked: it is looked up when a ZIP file is first saved): the binding's struct layouts, exr_layers' names and types, the views."""
+import ctypes as C
 
-from conftest import ROOT
-
-CSRC = os.path.join(ROOT, "monte-carlo-ray-tracer_amd", "csrc")
-OTHER_LIBS = ("libmcrt_hip.so", "libmcrt_aov.so", "libmcrt_denoise.so", "libmcrt_pixel_stats.so", "libmcrt_robust.so", "libmcrt_denoise_var.so",
-              "libmcrt_accumulate.so", "libmcrt_denoise_dual.so")
-
-
-def _tool(name):
-    spec = importlib.util.spec_from_file_location(name, os.path.join(ROOT, "tools", name + ".py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return mod
-
-
-def test_the_pack_kernel_lives_beside_the_render_path(pkg):
-    pkg.lib()
-    table = _tool("kernel_spill_table")
-    kernels = {k["name"]: k for k in table.kernels_of(os.path.join(CSRC, "libmcrt_exr.so"))}
-    assert sorted(kernels) == ["exrPackKernel"]
-    for name, k in kernels.items():
-        assert k["vgpr_spill"] == 0 and k["sgpr_spill"] == 0 and k["scratch"] == 0, (name, k)
-    for lib in OTHER_LIBS:
-        names = [k["name"] for k in table.kernels_of(os.path.join(CSRC, lib))]
-        assert names and not [n for n in names if "exr" in n.lower()], lib
-
-
-def test_the_libraries_find_the_exr_library_next_to_themselves_and_link_no_zlib():
-    assert os.path.exists(os.path.join(CSRC, "libmcrt_hip.so"))
-    for lib in ("libmcrt_hip.so", "libmcrt_hip_tol.so", "libmcrt_exr.so"):
-        path = os.path.join(CSRC, lib)
-        if lib.endswith("_tol.so") and not os.path.exists(path):
-            continue  # (MCRT_SKIP_TOLERANCE_BUILD=1 builds)
-        dyn = subprocess.run(["readelf", "-d", path], check=True, capture_output=True, text=True).stdout
-        needed = [l for l in dyn.splitlines() if "NEEDED" in l]
-        assert not [l for l in needed if "libz" in l], (lib, needed)
-        if lib != "libmcrt_exr.so":
-            assert "[libmcrt_exr.so]" in dyn, lib
-            assert any("$ORIGIN" in l for l in dyn.splitlines() if "RUNPATH" in l or "RPATH" in l), lib
-
-
-def test_the_calls_are_exported_and_the_abi_version_stays(pkg):
-    L = pkg.lib()
-    for name in ("mcrt_exr_save", "mcrt_exr_save_device"):
-        assert hasattr(L, name), name
-    assert L.mcrt_abi_version() == 2
-    for name in ("ExrChannel", "ExrParams", "ExrResult", "exr_layers"):
-        assert hasattr(pkg, name), name
-    assert hasattr(pkg.Context, "exr_save")
+from side_libraries import c_values
 
 
 def test_the_binding_lays_the_structs_out_as_the_header_does(pkg, tmp_path):
-    src = tmp_path / "sizes.c"
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "mcrt.h"\nint main(void){printf("%zu %zu %zu %zu %zu %zu\\n",sizeof(mcrt_exr_channel),'
-                   'sizeof(mcrt_exr_attribute),sizeof(mcrt_exr_params),sizeof(mcrt_exr_result),offsetof(mcrt_exr_channel,stride),'
-                   'offsetof(mcrt_exr_result,chunks));return 0;}\n')
-    exe = tmp_path / "sizes"
-    subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), "-o", str(exe), str(src)])
-    sizes = [int(x) for x in subprocess.check_output([str(exe)]).split()]
-    import ctypes as C
+    sizes = c_values(tmp_path, ["sizeof(mcrt_exr_channel)", "sizeof(mcrt_exr_attribute)", "sizeof(mcrt_exr_params)", "sizeof(mcrt_exr_result)",
+                                "offsetof(mcrt_exr_channel,stride)", "offsetof(mcrt_exr_result,chunks)"], "%zu %zu %zu %zu %zu %zu")
     assert sizes == [C.sizeof(pkg.ExrChannel), C.sizeof(pkg.ExrAttribute), C.sizeof(pkg.ExrParams), C.sizeof(pkg.ExrResult),
                      pkg.ExrChannel.stride.offset, pkg.ExrResult.chunks.offset]
 

@@ -1,29 +1,23 @@
 """CPU tier: the default-path kernels of the BUILT library spill no more than tests/golden/kernel_spill_budget.json allows
 (tools/kernel_spill_table.py reads the code objects' metadata: vgpr_spill_count, private_segment_fixed_size). A kernel that starts to
 spill more gets slower without any parity test noticing - round 5's renderKernelPM moved +-10 % on unrelated one-line edits."""
-import importlib.util
 import json
 import os
 
 import pytest
 
+import side_libraries
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def _tool():
-    spec = importlib.util.spec_from_file_location("kernel_spill_table", os.path.join(ROOT, "tools", "kernel_spill_table.py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return mod
 
 
 @pytest.mark.skipif(not os.path.exists("/opt/rocm/lib/llvm/bin/llvm-readelf"), reason="llvm-readelf not in this image")
 def test_default_path_kernels_stay_within_their_spill_budgets():
-    t = _tool()
+    t = side_libraries.tool("kernel_spill_table")
     if not os.path.exists(t.LIB):
         pytest.skip("libmcrt_hip.so not built")
     want = json.load(open(t.BUDGET))["kernels"]
-    have = {k["name"]: k for k in t.kernels_of()}
+    have = {k["name"]: k for k in side_libraries.kernels_of(t.LIB)}
     assert want, "empty budget"
     for name, w in want.items():
         assert name in have, "default-path kernel %s is not in the library" % name

@@ -1,70 +1,16 @@
-"""The ranking of the ID mattes is a code object of its own, like the image passes before it. libmcrt_matte.so holds exactly the two forms
-of the ranking, without spills or scratch (the tile form's keys are dynamic LDS, sized per launch); libmcrt_hip.so - the render path's
-device code, listed function by function in tests/golden/device_code_hashes.json - and the other side libraries hold no kernel of it, and
-the main libraries find the new one next to themselves (RUNPATH $ORIGIN)."""
+"""What only the ID mattes have (tests/side_libraries.py holds what libmcrt_matte.so may contain; the tile form's keys are dynamic LDS,
+sized per launch): the binding's struct layouts, exr_layers' names, strides and offsets, the attributes that name a layer."""
 import ctypes as C
-import importlib.util
-import os
-import subprocess
 
 import numpy as np
 
-from conftest import ROOT
-
-CSRC = os.path.join(ROOT, "monte-carlo-ray-tracer_amd", "csrc")
-
-
-def _tool(name):
-    spec = importlib.util.spec_from_file_location(name, os.path.join(ROOT, "tools", name + ".py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return mod
-
-
-def test_the_ranking_kernels_live_beside_the_render_path(pkg):
-    pkg.lib()
-    table = _tool("kernel_spill_table")
-    kernels = {k["name"]: k for k in table.kernels_of(os.path.join(CSRC, "libmcrt_matte.so"))}
-    assert sorted(kernels) == ["matteRankKernel", "matteRankMemoryKernel"]
-    for name, k in kernels.items():
-        assert k["vgpr_spill"] == 0 and k["sgpr_spill"] == 0 and k["scratch"] == 0, (name, k)
-    others = sorted(f for f in os.listdir(CSRC) if f.startswith("libmcrt_") and f.endswith(".so") and f != "libmcrt_matte.so")
-    assert len(others) >= 9, others
-    for lib in others:
-        names = [k["name"] for k in table.kernels_of(os.path.join(CSRC, lib))]
-        assert names and not [n for n in names if "matte" in n.lower()], lib
-
-
-def test_the_libraries_find_the_matte_library_next_to_themselves():
-    assert os.path.exists(os.path.join(CSRC, "libmcrt_hip.so"))
-    for lib in ("libmcrt_hip.so", "libmcrt_hip_tol.so"):
-        path = os.path.join(CSRC, lib)
-        if lib.endswith("_tol.so") and not os.path.exists(path):
-            continue  # (MCRT_SKIP_TOLERANCE_BUILD=1 builds)
-        dyn = subprocess.run(["readelf", "-d", path], check=True, capture_output=True, text=True).stdout
-        assert "[libmcrt_matte.so]" in dyn, lib
-        assert any("$ORIGIN" in l for l in dyn.splitlines() if "RUNPATH" in l or "RPATH" in l), lib
-
-
-def test_the_calls_are_exported_and_the_abi_version_stays(pkg):
-    L = pkg.lib()
-    for name in ("mcrt_render_matte", "mcrt_render_matte_device", "mcrt_matte_rank_device", "mcrt_matte_code", "mcrt_matte_manifest"):
-        assert hasattr(L, name), name
-    assert L.mcrt_abi_version() == 2
-    for name in ("MatteParams", "MatteBuffers", "matte_code", "matte_manifest", "matte_attributes", "exr_layers"):
-        assert hasattr(pkg, name), name
-    for name in ("render_matte", "render_matte_device", "matte_rank", "matte_rank_device"):
-        assert hasattr(pkg.Context, name), name
+from side_libraries import c_values
 
 
 def test_the_binding_lays_the_structs_out_as_the_header_does(pkg, tmp_path):
-    src = tmp_path / "sizes.c"
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "mcrt.h"\nint main(void){printf("%zu %zu %zu %zu %zu %zu %d %d %d\\n",sizeof(mcrt_matte_params),'
-                   'sizeof(mcrt_matte_buffers),offsetof(mcrt_matte_params,surface_key),offsetof(mcrt_matte_params,names),offsetof(mcrt_matte_params,reserved),'
-                   'offsetof(mcrt_matte_buffers,distinct),MCRT_MATTE_MATERIAL,MCRT_MATTE_SURFACE,MCRT_MATTE_CUSTOM);return 0;}\n')
-    exe = tmp_path / "sizes"
-    subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), "-o", str(exe), str(src)])
-    sizes = [int(x) for x in subprocess.check_output([str(exe)]).split()]
+    sizes = c_values(tmp_path, ["sizeof(mcrt_matte_params)", "sizeof(mcrt_matte_buffers)", "offsetof(mcrt_matte_params,surface_key)", "offsetof(mcrt_matte_params,names)",
+                                "offsetof(mcrt_matte_params,reserved)", "offsetof(mcrt_matte_buffers,distinct)", "MCRT_MATTE_MATERIAL", "MCRT_MATTE_SURFACE",
+                                "MCRT_MATTE_CUSTOM"], "%zu %zu %zu %zu %zu %zu %d %d %d")
     assert sizes == [C.sizeof(pkg.MatteParams), C.sizeof(pkg.MatteBuffers), pkg.MatteParams.surface_key.offset, pkg.MatteParams.names.offset,
                      pkg.MatteParams.reserved.offset, pkg.MatteBuffers.distinct.offset, pkg.MATTE_KEYS["material"], pkg.MATTE_KEYS["surface"],
                      pkg.MATTE_KEYS["custom"]]

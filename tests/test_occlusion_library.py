@@ -1,74 +1,22 @@
-"""The occlusion pass is a code object of its own, like the image passes before it. libmcrt_occlusion.so holds exactly the pass's two
-kernels, without spilled registers or scratch; libmcrt_hip.so - the render path's device code, listed function by function in
-tests/golden/device_code_hashes.json - and the other side libraries hold no kernel of it, and the main libraries find the new one next to
-themselves (RUNPATH $ORIGIN). What the calls refuse is checked here as far as no GPU is needed: a NULL context by the library, the
-parameters by the validation the host side calls (csrc/mcrt_occlusion.hpp occlusionSettingsOf, built into the CPU tier's emulation)."""
+"""What only the occlusion pass has (tests/side_libraries.py holds what libmcrt_occlusion.so may contain): the binding's channels and struct
+layouts, and what the calls refuse as far as no GPU is needed: a NULL context by the library, the parameters by the validation the host
+side calls (csrc/mcrt_occlusion.hpp occlusionSettingsOf, built into the CPU tier's emulation)."""
 import ctypes as C
-import importlib.util
 import math
-import os
-import subprocess
 
 import numpy as np
 
-from conftest import ROOT
-
-CSRC = os.path.join(ROOT, "monte-carlo-ray-tracer_amd", "csrc")
+from side_libraries import c_values
 
 
-def _tool(name):
-    spec = importlib.util.spec_from_file_location(name, os.path.join(ROOT, "tools", name + ".py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return mod
-
-
-def test_the_occlusion_kernels_live_beside_the_render_path(pkg):
-    pkg.lib()
-    table = _tool("kernel_spill_table")
-    kernels = {k["name"]: k for k in table.kernels_of(os.path.join(CSRC, "libmcrt_occlusion.so"))}
-    assert sorted(kernels) == ["occlusionRayKernel", "occlusionResolveKernel"]
-    for name, k in kernels.items():
-        assert k["vgpr_spill"] == 0 and k["sgpr_spill"] == 0 and k["scratch"] == 0, (name, k)
-    assert kernels["occlusionRayKernel"]["lds"] == 6 * 4 * 256 * 4 and kernels["occlusionResolveKernel"]["lds"] == 0  # (the Sobol byte tables)
-    others = sorted(f for f in os.listdir(CSRC) if f.startswith("libmcrt_") and f.endswith(".so") and f != "libmcrt_occlusion.so")
-    assert len(others) >= 12, others
-    for lib in others:
-        names = [k["name"] for k in table.kernels_of(os.path.join(CSRC, lib))]
-        assert names and not [n for n in names if "occlusion" in n.lower()], lib
-
-
-def test_the_libraries_find_the_occlusion_library_next_to_themselves():
-    assert os.path.exists(os.path.join(CSRC, "libmcrt_hip.so"))
-    for lib in ("libmcrt_hip.so", "libmcrt_hip_tol.so"):
-        path = os.path.join(CSRC, lib)
-        if lib.endswith("_tol.so") and not os.path.exists(path):
-            continue  # (MCRT_SKIP_TOLERANCE_BUILD=1 builds)
-        dyn = subprocess.run(["readelf", "-d", path], check=True, capture_output=True, text=True).stdout
-        assert "[libmcrt_occlusion.so]" in dyn, lib
-        assert any("$ORIGIN" in l for l in dyn.splitlines() if "RUNPATH" in l or "RPATH" in l), lib
-
-
-def test_the_calls_are_exported_and_the_abi_version_stays(pkg):
-    L = pkg.lib()
-    for name in ("mcrt_render_occlusion", "mcrt_render_occlusion_device"):
-        assert hasattr(L, name), name
-    assert L.mcrt_abi_version() == 2
-    for name in ("OcclusionParams", "OcclusionBuffers", "OCCLUSION_CHANNELS", "OCCLUSION_GEOMETRIC", "exr_layers"):
-        assert hasattr(pkg, name), name
-    for name in ("render_occlusion", "render_occlusion_device"):
-        assert hasattr(pkg.Context, name), name
+def test_the_channels_of_the_binding_are_the_struct_s_fields(pkg):
     assert list(pkg.OCCLUSION_CHANNELS) == [k for k, _ in pkg.OcclusionBuffers._fields_]
 
 
 def test_the_binding_lays_the_structs_out_as_the_header_does(pkg, tmp_path):
-    src = tmp_path / "sizes.c"
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "mcrt.h"\nint main(void){printf("%zu %zu %zu %zu %zu %zu %u %u\\n",sizeof(mcrt_occlusion_params),'
-                   'sizeof(mcrt_occlusion_buffers),offsetof(mcrt_occlusion_params,flags),offsetof(mcrt_occlusion_params,max_distance),'
-                   'offsetof(mcrt_occlusion_buffers,sky),offsetof(mcrt_occlusion_buffers,bent_normal),MCRT_OCCLUSION_GEOMETRIC,MCRT_OCCLUSION_MAX_RAYS);return 0;}\n')
-    exe = tmp_path / "sizes"
-    subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), "-o", str(exe), str(src)])
-    sizes = [int(x) for x in subprocess.check_output([str(exe)]).split()]
+    sizes = c_values(tmp_path, ["sizeof(mcrt_occlusion_params)", "sizeof(mcrt_occlusion_buffers)", "offsetof(mcrt_occlusion_params,flags)",
+                                "offsetof(mcrt_occlusion_params,max_distance)", "offsetof(mcrt_occlusion_buffers,sky)", "offsetof(mcrt_occlusion_buffers,bent_normal)",
+                                "MCRT_OCCLUSION_GEOMETRIC", "MCRT_OCCLUSION_MAX_RAYS"], "%zu %zu %zu %zu %zu %zu %u %u")
     assert sizes == [C.sizeof(pkg.OcclusionParams), C.sizeof(pkg.OcclusionBuffers), pkg.OcclusionParams.flags.offset, pkg.OcclusionParams.max_distance.offset,
                      pkg.OcclusionBuffers.sky.offset, pkg.OcclusionBuffers.bent_normal.offset, pkg.OCCLUSION_GEOMETRIC, pkg.OCCLUSION_MAX_RAYS]
     assert sizes[0] == 16

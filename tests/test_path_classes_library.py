@@ -1,98 +1,29 @@
-"""The path classes are a code object of their own, like the image passes before them. libmcrt_path_classes.so holds exactly the pass's
-four kernels, without scratch and within the registers profiles/NOTES_path_classes.md records (its table is read here: the numbers are
-upper bounds); libmcrt_hip.so - the render path's device code, listed function by function in tests/golden/device_code_hashes.json - and
-the other side libraries hold no kernel of these names, and the main libraries find the new one next to themselves (RUNPATH $ORIGIN).
-What the calls refuse is checked here as far as no GPU is needed."""
+"""What only the path classes have (tests/side_libraries.py holds what libmcrt_path_classes.so may contain, within the registers
+profiles/NOTES_path_classes.md records): the binding's struct layout and class numbers, the number of planes, the presets, and what the
+calls refuse as far as no GPU is needed."""
 import ctypes as C
-import importlib.util
 import os
-import re
 import subprocess
 
 import numpy as np
 import pytest
 
-from conftest import ROOT
+from side_libraries import CSRC, ROOT, c_values
 
-CSRC = os.path.join(ROOT, "monte-carlo-ray-tracer_amd", "csrc")
-KERNELS = ["pathClassesBeginKernel", "pathClassesRayKernel", "pathClassesResolveKernel", "pathClassesStepKernel"]
-SHADING = ("pathClassesRayKernel", "pathClassesStepKernel")
 FIELDS = ["flags", "max_depth", "class_plane"]
 NAMES = ["emission", "background", "diffuse_direct", "diffuse_indirect", "glossy_direct", "glossy_indirect", "transmission_direct", "transmission_indirect"]
 
 
-def _tool(name):
-    spec = importlib.util.spec_from_file_location(name, os.path.join(ROOT, "tools", name + ".py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return mod
-
-
-def recorded_resources():
-    """The table of profiles/NOTES_path_classes.md: kernel -> dict of vgpr, vgpr_spill, sgpr_spill, scratch, lds."""
-    rows = {}
-    for line in open(os.path.join(ROOT, "profiles", "NOTES_path_classes.md")):
-        m = re.match(r"\|\s*`(pathClasses\w+Kernel)`\s*\|\s*(\d+)\s*\|\s*(\d+)\s*\|\s*(\d+)\s*\|\s*(\d+)\s*\|\s*(\d+)\s*\|", line)
-        if m:
-            rows[m.group(1)] = dict(zip(("vgpr", "vgpr_spill", "sgpr_spill", "scratch", "lds"), (int(x) for x in m.groups()[1:])))
-    return rows
-
-
-def test_the_path_class_kernels_live_beside_the_render_path(pkg):
-    pkg.lib()
-    table = _tool("kernel_spill_table")
-    kernels = {k["name"]: k for k in table.kernels_of(os.path.join(CSRC, "libmcrt_path_classes.so"))}
-    assert sorted(kernels) == KERNELS
-    recorded = recorded_resources()
-    assert sorted(recorded) == KERNELS
-    for name, k in kernels.items():
-        assert k["scratch"] == 0 and k["vgpr_spill"] == 0, (name, k)  # (spilled SGPRs go to lanes of a VGPR, not to memory)
-        assert k["max_wg"] == 256, name
-        for word, bound in recorded[name].items():
-            assert k[word] <= bound, (name, word, k[word], bound)
-        # the Sobol byte tables, the sine / cosine table and 8 history entries for each of 256 lanes - or nothing
-        assert k["lds"] == (6 * 4 * 256 * 4 + 440 * 8 + 8 * 256 * 8 if name in SHADING else 0), name
-    others = sorted(f for f in os.listdir(CSRC) if f.startswith("libmcrt_") and f.endswith(".so") and f != "libmcrt_path_classes.so")
-    assert len(others) >= 15, others
-    for lib in others:
-        names = [k["name"] for k in table.kernels_of(os.path.join(CSRC, lib))]
-        assert names and not [n for n in names if n in KERNELS], lib
-
-
-def test_the_libraries_find_the_path_class_library_next_to_themselves():
-    assert os.path.exists(os.path.join(CSRC, "libmcrt_hip.so"))
-    for lib in ("libmcrt_hip.so", "libmcrt_hip_tol.so"):
-        path = os.path.join(CSRC, lib)
-        if lib.endswith("_tol.so") and not os.path.exists(path):
-            continue  # (MCRT_SKIP_TOLERANCE_BUILD=1 builds)
-        dyn = subprocess.run(["readelf", "-d", path], check=True, capture_output=True, text=True).stdout
-        assert "[libmcrt_path_classes.so]" in dyn, lib
-        assert any("$ORIGIN" in l for l in dyn.splitlines() if "RUNPATH" in l or "RPATH" in l), lib
-
-
-def test_the_calls_are_exported_and_the_abi_version_stays(pkg):
-    L = pkg.lib()
-    for name in ("mcrt_render_path_classes", "mcrt_render_path_classes_device", "mcrt_path_class_planes"):
-        assert hasattr(L, name), name
-    assert L.mcrt_abi_version() == 2
-    for name in ("PathClassParams", "PATH_CLASSES", "PATH_CLASSES_MAP", "PATH_CLASS_NAMES", "path_class_map"):
-        assert hasattr(pkg, name), name
-    for name in ("render_path_classes", "render_path_classes_device"):
-        assert hasattr(pkg.Context, name), name
+def test_the_binding_has_the_header_s_fields_and_class_names(pkg):
     assert [k for k, _ in pkg.PathClassParams._fields_] == FIELDS
     assert list(pkg.PATH_CLASS_NAMES) == NAMES
 
 
 def test_the_binding_lays_the_struct_out_as_the_header_does(pkg, tmp_path):
     """... and numbers the classes as the header does."""
-    src = tmp_path / "sizes.c"
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "mcrt.h"\nint main(void){printf("%zu %u %u ' + "%zu " * len(FIELDS) + "%d " * 8
-                   + '\\n",sizeof(mcrt_path_class_params),MCRT_PATH_CLASSES,(unsigned)MCRT_PATH_CLASSES_MAP,'
-                   + ",".join("offsetof(mcrt_path_class_params,%s)" % k for k in FIELDS) + ","
-                   + ",".join("(int)MCRT_PATH_CLASS_" + n.upper() for n in NAMES) + ');return 0;}\n')
-    exe = tmp_path / "sizes"
-    subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), "-o", str(exe), str(src)])
-    sizes = [int(x) for x in subprocess.check_output([str(exe)]).split()]
+    sizes = c_values(tmp_path, ["sizeof(mcrt_path_class_params)", "MCRT_PATH_CLASSES", "(unsigned)MCRT_PATH_CLASSES_MAP"]
+                     + ["offsetof(mcrt_path_class_params,%s)" % k for k in FIELDS] + ["(int)MCRT_PATH_CLASS_" + n.upper() for n in NAMES],
+                     "%zu %u %u " + "%zu " * len(FIELDS) + "%d " * 8)
     assert sizes == [C.sizeof(pkg.PathClassParams), pkg.PATH_CLASSES, pkg.PATH_CLASSES_MAP] + [getattr(pkg.PathClassParams, k).offset for k in FIELDS] + list(range(8))
     assert sizes[0] == 16 and C.sizeof(pkg.PathClassParams().class_plane) == 8
 
