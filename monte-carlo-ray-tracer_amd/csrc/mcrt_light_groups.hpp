@@ -38,6 +38,44 @@ struct LgParams {
     uint32_t planes, sky_plane, max_depth;
 };
 
+// ---------------------------------------------------------------------------------------------- the settings (host and emulation)
+// What the calls resolve from mcrt_light_group_params, here and nowhere else: host-only text, nothing of it is device code.
+struct LgSettings {
+    uint32_t groups, sky_plane, planes, max_depth;
+    const uint32_t* surface_group;
+};
+
+// The parameters with their defaults filled in; -> the number of planes, or 0 when the numbers are out of range (more than
+// MCRT_LIGHT_GROUPS_MAX groups - sky_plane is then not looked at - or a sky_plane above the groups).
+inline uint32_t lgSettingsOf(const mcrt_light_group_params* p, LgSettings& s) {
+    s.groups = p && p->num_groups ? p->num_groups : 1u;
+    s.max_depth = p ? p->max_depth : 0u;
+    s.surface_group = p ? p->surface_group : nullptr;
+    if (s.groups > MCRT_LIGHT_GROUPS_MAX) return 0u;
+    s.sky_plane = p && (p->flags & MCRT_LIGHT_GROUPS_SKY_PLANE) ? p->sky_plane : s.groups;
+    if (s.sky_plane > s.groups) return 0u;
+    s.planes = s.groups > s.sky_plane + 1u ? s.groups : s.sky_plane + 1u;
+    return s.planes;
+}
+
+// LgParams::plane for the scene's surfaces into plane[0 .. num_surfaces): an emitter's (a surface whose material carries
+// MCRT_MAT_EMISSIVE) is its group, every other surface's 0 - also one whose surf_material names no material. false: *bad is the first
+// emitter whose group is not one of the s.groups.
+inline bool lgSurfacePlanes(const LgSettings& s, const uint32_t* surf_material, uint32_t num_surfaces, const mcrt_material* materials, uint32_t num_materials,
+                            uint8_t* plane, uint32_t* bad) {
+    for (uint32_t i = 0; i < num_surfaces; i++) {
+        plane[i] = 0;
+        if (surf_material[i] >= num_materials || !(materials[surf_material[i]].flags & MCRT_MAT_EMISSIVE)) continue;
+        const uint32_t g = s.surface_group ? s.surface_group[i] : 0u;
+        if (g >= s.groups) {
+            *bad = i;
+            return false;
+        }
+        plane[i] = (uint8_t)g;
+    }
+    return true;
+}
+
 // The live list's counters and the pass's error word, in device memory; the host reads them after every step kernel.
 struct LgCounters {
     uint32_t live[2];   // entries of the two lists (ping-pong: iteration k reads list k & 1 and appends to the other)

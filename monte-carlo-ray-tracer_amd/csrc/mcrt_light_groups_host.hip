@@ -19,39 +19,22 @@ using namespace mcrt;
 
 namespace {
 
-struct Resolved {
-    uint32_t groups, sky_plane, planes, max_depth;
-    const uint32_t* surface_group;
-};
-
-// 0 when the numbers are out of range
-uint32_t resolveParams(const mcrt_light_group_params* p, Resolved& r) {
-    r.groups = p && p->num_groups ? p->num_groups : 1u;
-    r.max_depth = p ? p->max_depth : 0u;
-    r.surface_group = p ? p->surface_group : nullptr;
-    if (r.groups > MCRT_LIGHT_GROUPS_MAX) return 0u;
-    r.sky_plane = p && (p->flags & MCRT_LIGHT_GROUPS_SKY_PLANE) ? p->sky_plane : r.groups;
-    if (r.sky_plane > r.groups) return 0u;
-    r.planes = std::max(r.groups, r.sky_plane + 1u);
-    return r.planes;
-}
-
-int validate(mcrt_ctx* ctx, const mcrt_camera_desc* cam, const mcrt_light_group_params* params, const void* planes, Resolved& r, const char* what) {
+int validate(mcrt_ctx* ctx, const mcrt_camera_desc* cam, const mcrt_light_group_params* params, const void* planes, LgSettings& r, const char* what) {
     if (int rc = cameraPassReady(ctx, what)) return rc;
     if (int rc = checkCamera(ctx, cam, true, what, "cam is NULL")) return rc;
     if (!planes) return ctxFail(ctx, MCRT_ERR_INVALID, std::string(what) + ": planes is NULL");
     if (params && params->num_groups > MCRT_LIGHT_GROUPS_MAX)
         return ctxFail(ctx, MCRT_ERR_INVALID, std::string(what) + ": num_groups " + std::to_string(params->num_groups) + " is more than MCRT_LIGHT_GROUPS_MAX (" +
                                                   std::to_string(MCRT_LIGHT_GROUPS_MAX) + ")");
-    if (!resolveParams(params, r))
+    if (!lgSettingsOf(params, r))
         return ctxFail(ctx, MCRT_ERR_INVALID, std::string(what) + ": sky_plane " + std::to_string(params->sky_plane) + " is more than num_groups (" +
                                                   std::to_string(r.groups) + "): the sky takes a group's plane or the one after them");
     return checkPixelSlots(ctx, cam, 2, "rays", what);
 }
 
-// The plane of every surface of the uploaded scene into scratch slot 4: an emitter's (a surface whose material carries MCRT_MAT_EMISSIVE)
-// is its group, every other surface's 0. The scene's own arrays are read back from the device: the context keeps no host copy.
-int uploadPlanes(mcrt_ctx* ctx, const AovScene& scene, const Resolved& r, const char* what, const uint8_t** d_plane) {
+// The plane of every surface of the uploaded scene (lgSurfacePlanes) into scratch slot 4. The scene's own arrays are read back from the
+// device: the context keeps no host copy.
+int uploadPlanes(mcrt_ctx* ctx, const AovScene& scene, const LgSettings& r, const char* what, const uint8_t** d_plane) {
     uint32_t num_surfaces = 0, num_materials = 0;
     ctxSceneCounts(ctx, &num_surfaces, &num_materials);
     std::vector<uint32_t> surf_material(num_surfaces);
@@ -59,14 +42,10 @@ int uploadPlanes(mcrt_ctx* ctx, const AovScene& scene, const Resolved& r, const 
     MCRT_HIP_TRY(ctx, hipMemcpy(surf_material.data(), scene.sh.surf_material, (size_t)num_surfaces * 4, hipMemcpyDeviceToHost));
     MCRT_HIP_TRY(ctx, hipMemcpy(materials.data(), scene.sh.materials, (size_t)num_materials * sizeof(mcrt_material), hipMemcpyDeviceToHost));
     std::vector<uint8_t> plane(std::max<uint32_t>(num_surfaces, 1u), 0);
-    for (uint32_t i = 0; i < num_surfaces; i++) {
-        if (surf_material[i] >= num_materials || !(materials[surf_material[i]].flags & MCRT_MAT_EMISSIVE)) continue;
-        const uint32_t g = r.surface_group ? r.surface_group[i] : 0u;
-        if (g >= r.groups)
-            return ctxFail(ctx, MCRT_ERR_INVALID, std::string(what) + ": surface_group[" + std::to_string(i) + "] = " + std::to_string(g) + ", but surface " +
-                                                      std::to_string(i) + " is an emitter and there are " + std::to_string(r.groups) + " groups");
-        plane[i] = (uint8_t)g;
-    }
+    uint32_t i = 0;
+    if (!lgSurfacePlanes(r, surf_material.data(), num_surfaces, materials.data(), num_materials, plane.data(), &i))
+        return ctxFail(ctx, MCRT_ERR_INVALID, std::string(what) + ": surface_group[" + std::to_string(i) + "] = " + std::to_string(r.surface_group[i]) + ", but surface " +
+                                                  std::to_string(i) + " is an emitter and there are " + std::to_string(r.groups) + " groups");
     uint8_t* d = (uint8_t*)ctxPassScratch(ctx, kPassLightGroups, 4, plane.size());
     if (!d) return ctxFail(ctx, MCRT_ERR_HIP, std::string(what) + ": the surfaces' planes could not be allocated");
     MCRT_HIP_TRY(ctx, hipMemcpy(d, plane.data(), plane.size(), hipMemcpyHostToDevice));
@@ -77,15 +56,15 @@ int uploadPlanes(mcrt_ctx* ctx, const AovScene& scene, const Resolved& r, const 
 }  // namespace
 
 extern "C" uint32_t mcrt_light_group_planes(const mcrt_light_group_params* params) {
-    Resolved r;
-    return resolveParams(params, r);
+    LgSettings r;
+    return lgSettingsOf(params, r);
 }
 
 extern "C" int mcrt_render_light_groups_device(mcrt_ctx* ctx, const mcrt_camera_desc* cam, uint32_t global_seed, const mcrt_light_group_params* params,
                                                double* d_planes, mcrt_stats* stats) {
     const char* what = "mcrt_render_light_groups_device";
     if (!ctx) return MCRT_ERR_INVALID;
-    Resolved r;
+    LgSettings r;
     if (int rc = validate(ctx, cam, params, d_planes, r, what)) return rc;
     PassTimer timer(ctx);
     const CameraPass cp(ctx);
@@ -127,7 +106,7 @@ extern "C" int mcrt_render_light_groups(mcrt_ctx* ctx, const mcrt_camera_desc* c
                                         mcrt_stats* stats) {
     const char* what = "mcrt_render_light_groups";
     if (!ctx) return MCRT_ERR_INVALID;
-    Resolved r;
+    LgSettings r;
     if (int rc = validate(ctx, cam, params, planes, r, what)) return rc;
     FrameChannel ch[kLgPlanesMax];  // the planes, one behind the other
     const size_t frame = (size_t)cam->width * cam->height * 3;

@@ -33,6 +33,23 @@ struct PcParams {
     uint32_t planes, max_depth;
 };
 
+// The settings (host and emulation), resolved here and nowhere else - host-only text, nothing of it is device code: the parameters with
+// their defaults filled in (no map: the identity); -> P, or 0 when an entry is out of range (*bad: the first such class).
+inline uint32_t pcSettingsOf(const mcrt_path_class_params* p, PcParams& r, uint32_t* bad = nullptr) {
+    const bool mapped = p && (p->flags & MCRT_PATH_CLASSES_MAP);
+    r.max_depth = p ? p->max_depth : 0u;
+    r.planes = 0u;
+    for (uint32_t c = 0; c < MCRT_PATH_CLASSES; c++) {
+        r.class_plane[c] = mapped ? p->class_plane[c] : (uint8_t)c;
+        if (r.class_plane[c] >= MCRT_PATH_CLASSES) {
+            if (bad) *bad = c;
+            return 0u;
+        }
+        if (r.class_plane[c] + 1u > r.planes) r.planes = r.class_plane[c] + 1u;
+    }
+    return r.planes;
+}
+
 // pathBegin for sample s: the light groups', the sky of a camera ray that missed (iteration 0's miss) going to the background's plane.
 MCRT_HD bool pcBegin(const PcState& st, uint64_t s, double scene_ior, const PcParams& par) {
     LgParams lg;

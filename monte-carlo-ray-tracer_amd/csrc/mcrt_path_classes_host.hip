@@ -15,28 +15,12 @@ namespace {
 const char* const kClassNames[MCRT_PATH_CLASSES] = {"emission",      "background",      "diffuse_direct",      "diffuse_indirect",
                                                     "glossy_direct", "glossy_indirect", "transmission_direct", "transmission_indirect"};
 
-// The parameters with their defaults filled in; -> P, or 0 when an entry is out of range (*bad: the first such class).
-uint32_t resolveParams(const mcrt_path_class_params* p, PcParams& r, uint32_t* bad = nullptr) {
-    const bool mapped = p && (p->flags & MCRT_PATH_CLASSES_MAP);
-    r.max_depth = p ? p->max_depth : 0u;
-    r.planes = 0u;
-    for (uint32_t c = 0; c < MCRT_PATH_CLASSES; c++) {
-        r.class_plane[c] = mapped ? p->class_plane[c] : (uint8_t)c;
-        if (r.class_plane[c] >= MCRT_PATH_CLASSES) {
-            if (bad) *bad = c;
-            return 0u;
-        }
-        r.planes = std::max<uint32_t>(r.planes, r.class_plane[c] + 1u);
-    }
-    return r.planes;
-}
-
 int validate(mcrt_ctx* ctx, const mcrt_camera_desc* cam, const mcrt_path_class_params* params, const void* planes, PcParams& r, const char* what) {
     if (int rc = cameraPassReady(ctx, what)) return rc;
     if (int rc = checkCamera(ctx, cam, true, what, "cam is NULL")) return rc;
     if (!planes) return ctxFail(ctx, MCRT_ERR_INVALID, std::string(what) + ": planes is NULL");
     uint32_t bad = 0;
-    if (!resolveParams(params, r, &bad))
+    if (!pcSettingsOf(params, r, &bad))
         return ctxFail(ctx, MCRT_ERR_INVALID, std::string(what) + ": class_plane[" + std::to_string(bad) + "] (" + kClassNames[bad] + ") = " +
                                                   std::to_string(params->class_plane[bad]) + ", but there are at most " + std::to_string(MCRT_PATH_CLASSES) + " planes");
     return checkPixelSlots(ctx, cam, 2, "rays", what);
@@ -46,7 +30,7 @@ int validate(mcrt_ctx* ctx, const mcrt_camera_desc* cam, const mcrt_path_class_p
 
 extern "C" uint32_t mcrt_path_class_planes(const mcrt_path_class_params* params) {
     PcParams r;
-    return resolveParams(params, r);
+    return pcSettingsOf(params, r);
 }
 
 extern "C" int mcrt_render_path_classes_device(mcrt_ctx* ctx, const mcrt_camera_desc* cam, uint32_t global_seed, const mcrt_path_class_params* params,

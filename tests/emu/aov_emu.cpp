@@ -7,9 +7,6 @@
 
 extern "C" {
 
-// Owned rows of the camera's shard (what mcrt_shard_rows counts).
-uint32_t aov_emu_rows(const mcrt_camera_desc* cam) { return ownedRows(*cam); }
-
 // The camera rays of the frame, [pixel][sample][3] over the packed owned rows.
 int aov_emu_rays(const mcrt_scene_desc* scene, const mcrt_camera_desc* cam, uint32_t global_seed, double* start, double* direction) {
     std::vector<uint32_t> tab(kSobolTableWords);

@@ -10,9 +10,6 @@
 
 extern "C" {
 
-// Owned rows of the camera's shard (what mcrt_shard_rows counts).
-uint32_t lighting_emu_rows(const mcrt_camera_desc* cam) { return ownedRows(*cam); }
-
 // The lighting frame into `out` (host arrays over the packed owned rows, null = channel not wanted), in chunks of chunk_rays shadow and
 // bounce slots (0 = one chunk). stage_lds: emu_intersect's flavour of the walk.
 int lighting_emu_frame(const mcrt_scene_desc* scene, const mcrt_camera_desc* cam, uint32_t global_seed, int stage_lds, uint64_t chunk_rays,

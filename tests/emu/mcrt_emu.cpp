@@ -1299,3 +1299,26 @@ int emuCameraRays(const mcrt_scene_desc* scene, const Emu& E, const AovChunk& c,
 }
 
 }  // namespace
+
+extern "C" {
+
+// Owned rows of the camera's shard (what mcrt_shard_rows counts).
+uint32_t emu_owned_rows(const mcrt_camera_desc* cam) { return ownedRows(*cam); }
+
+// The surface every camera sample meets first (0xFFFFFFFF: none), [owned pixels][spp].
+int emu_first_hits(const mcrt_scene_desc* scene, const mcrt_camera_desc* cam, uint32_t global_seed, int stage_lds, uint32_t* surface) {
+    Emu E;
+    if (int rc = setup(E, scene, 0)) return rc;
+    const uint64_t pixels = (uint64_t)ownedRows(*cam) * cam->width;
+    const AovChunk c = chunkAt(*cam, global_seed, cam->sqrtspp * cam->sqrtspp, 0, pixels, pixels);
+    const uint64_t n = (uint64_t)c.pixels * c.spp;
+    std::vector<double> start(3 * n), direction(3 * n), t(n), uv(2 * n);
+    for (uint64_t r = 0; r < n; r++) {
+        const Ray ray = aovCameraRay<true>(c, E.sh_top.scene_ior, (uint32_t)(r / c.spp), (uint32_t)(r % c.spp), E.tab.data());
+        aovStore3(start.data(), r, ray.start);
+        aovStore3(direction.data(), r, ray.direction);
+    }
+    return emu_intersect(scene, n, start.data(), direction.data(), stage_lds, t.data(), surface, uv.data());
+}
+
+}  // extern "C"

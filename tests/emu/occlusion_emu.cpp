@@ -10,9 +10,6 @@
 
 extern "C" {
 
-// Owned rows of the camera's shard (what mcrt_shard_rows counts).
-uint32_t occlusion_emu_rows(const mcrt_camera_desc* cam) { return ownedRows(*cam); }
-
 // Why `params` is refused (the text mcrt_render_occlusion* records), or NULL; *rays: the number of rays they mean.
 const char* occlusion_emu_settings(const mcrt_occlusion_params* params, uint32_t* rays) {
     OcclusionSettings s;

@@ -2,50 +2,27 @@
 //
 // The path classes on the host: csrc/mcrt_path_classes.hpp (and csrc/mcrt_light_groups.hpp, csrc/mcrt_aov.hpp, csrc/mcrt_shade.hpp below
 // it) unchanged - the text the kernels of csrc/mcrt_path_classes.hip run - driven chunk by chunk and iteration by iteration the way
-// mcrt_render_path_classes_device drives them (mcrt_emu.cpp's chunk plan and emuCameraRays), live lists included, with the closest hits
-// from the emulation's sceneIntersect (emu_intersect). Not a CPU fallback: nothing in the product links or loads it.
+// mcrt_render_path_classes_device drives them (mcrt_emu.cpp's chunk plan and emuCameraRays, live_paths_emu.hpp's loop), live lists
+// included, with the closest hits from the emulation's sceneIntersect (emu_intersect). Not a CPU fallback: nothing in the product links
+// or loads it.
 #include "mcrt_emu.cpp"
+
+#include "live_paths_emu.hpp"
 
 #include "../../monte-carlo-ray-tracer_amd/csrc/mcrt_path_classes.hpp"
 
 extern "C" {
 
-// Owned rows of the camera's shard (what mcrt_shard_rows counts).
-uint32_t path_classes_emu_rows(const mcrt_camera_desc* cam) { return ownedRows(*cam); }
-
-// The surface every camera sample meets first (0xFFFFFFFF: none), [owned pixels][spp].
-int path_classes_emu_first_hits(const mcrt_scene_desc* scene, const mcrt_camera_desc* cam, uint32_t global_seed, int stage_lds, uint32_t* surface) {
-    Emu E;
-    if (int rc = setup(E, scene, 0)) return rc;
-    const uint64_t pixels = (uint64_t)ownedRows(*cam) * cam->width;
-    const AovChunk c = chunkAt(*cam, global_seed, cam->sqrtspp * cam->sqrtspp, 0, pixels, pixels);
-    const uint64_t n = (uint64_t)c.pixels * c.spp;
-    std::vector<double> start(3 * n), direction(3 * n), t(n), uv(2 * n);
-    for (uint64_t r = 0; r < n; r++) {
-        const Ray ray = aovCameraRay<true>(c, E.sh_top.scene_ior, (uint32_t)(r / c.spp), (uint32_t)(r % c.spp), E.tab.data());
-        aovStore3(start.data(), r, ray.start);
-        aovStore3(direction.data(), r, ray.direction);
-    }
-    return emu_intersect(scene, n, start.data(), direction.data(), stage_lds, t.data(), surface, uv.data());
-}
-
 // The planes into `out` (host array [planes][owned pixels][3]), in chunks of chunk_rays shadow and bounce slots of iteration 0 (0 = one
-// chunk). stage_lds: emu_intersect's flavour of the walk. list_order: what happens to a live list between the step that appended it
-// and the iteration that reads it - 0 nothing, 1 reversed, 2 shuffled (a fixed generator). info: [0] rays handed to the search,
-// [1] the most iterations a chunk took, [2] live samples summed over all iterations. Returns mcrt_status values for what the call refuses.
+// chunk). stage_lds, list_order: EmuLivePaths'. info: [0] rays handed to the search, [1] the most iterations a chunk took, [2] live
+// samples summed over all iterations. Returns mcrt_status values for what the call refuses.
 int path_classes_emu_frame(const mcrt_scene_desc* scene, const mcrt_camera_desc* cam, uint32_t global_seed, int stage_lds, uint64_t chunk_rays,
                            const mcrt_path_class_params* params, int list_order, double* out, uint64_t* info) {
     Emu E;
     if (int rc = setup(E, scene, 0)) return rc;
     const AovScene as = aovSceneOf(E);
     PcParams par;
-    par.max_depth = params ? params->max_depth : 0u;
-    par.planes = 0;
-    for (uint32_t c = 0; c < MCRT_PATH_CLASSES; c++) {
-        par.class_plane[c] = params && (params->flags & MCRT_PATH_CLASSES_MAP) ? params->class_plane[c] : (uint8_t)c;
-        if (par.class_plane[c] >= MCRT_PATH_CLASSES) return MCRT_ERR_INVALID;
-        par.planes = std::max<uint32_t>(par.planes, par.class_plane[c] + 1u);
-    }
+    if (!pcSettingsOf(params, par)) return MCRT_ERR_INVALID;
 
     const PixelChunks plan = emuPixelChunks(cam, 2, chunk_rays);
     const uint64_t max_n = plan.max_rays, total = plan.total_pixels;
@@ -53,56 +30,24 @@ int path_classes_emu_frame(const mcrt_scene_desc* scene, const mcrt_camera_desc*
     PcState st;
     pcPlaceState(st, state.data(), max_n);
     st.lg.radiance = radiance.data();
-    EmuRays lit_records(plan.max_slots);
-    const AovRays lit = lit_records.view();
-    std::vector<uint32_t> list[2];
-    double iors[kMaxIors];
-    RefractionHistory rh;
-    rh.iors = iors;
-    rh.stride = 1;
-    rh.size = 0;
-    uint64_t lcg = 0x9E3779B97F4A7C15ull;
+    EmuLivePaths paths(scene, stage_lds, plan.max_slots, list_order, par.max_depth);
     if (info) info[0] = info[1] = info[2] = 0;
     for (uint64_t first = 0; first < total; first += plan.chunk_pixels) {
         const AovChunk c = chunkAt(*cam, global_seed, plan.spp, first, plan.chunk_pixels, total);
-        const uint64_t n = (uint64_t)c.pixels * c.spp;
         if (int rc = emuCameraRays(scene, E, c, stage_lds, st.lg.ray)) return rc;
         for (uint64_t s = 0; s < max_n; s++) st.lobe[s] = 0xABABABABu;  // (a step that reads a lobe no step 0 wrote shows)
-        list[0].clear();
-        list[1].clear();
-        for (uint64_t s = 0; s < n; s++)  // pathClassesBeginKernel
-            if (pcBegin(st, s, as.sh.scene_ior, par)) list[0].push_back((uint32_t)s);
-        if (info) info[0] += n;
-        uint32_t k = 0;
-        for (; !list[k & 1u].empty(); k++) {
-            if (k >= kLgMaxIterations) return MCRT_ERR_UNSUPPORTED;
-            std::vector<uint32_t>& cur = list[k & 1u];
-            std::vector<uint32_t>& next = list[(k & 1u) ^ 1u];
-            if (list_order == 1) std::reverse(cur.begin(), cur.end());
-            if (list_order == 2)
-                for (size_t a = cur.size(); a > 1; a--) {
-                    lcg = lcg * 6364136223846793005ull + 1442695040888963407ull;
-                    std::swap(cur[a - 1], cur[(size_t)((lcg >> 33) % a)]);
-                }
-            const uint32_t live = (uint32_t)cur.size();
-            const bool last = par.max_depth != 0u && k == par.max_depth;
-            if (info) info[2] += live;
-            if (!last) {
-                for (uint32_t j = 0; j < live; j++) lgRays(c, as, st.lg, cur.data(), live, j, k, lit, rh, E.tab.data());  // pathClassesRayKernel
-                if (int rc = emu_intersect(scene, 2ull * live, lit.start, lit.direction, stage_lds, lit.t, lit.surface, lit.uv)) return rc;
-                if (info) info[0] += 2ull * live;
-            }
-            next.clear();
-            for (uint32_t j = 0; j < live; j++) {  // pathClassesStepKernel
-                bool too_deep = false;
-                if (pcStep(c, as, st, par, cur.data(), live, j, k, last, lit, rh, too_deep, E.tab.data())) next.push_back(cur[j]);
-                if (too_deep) return MCRT_ERR_UNSUPPORTED;
-            }
-            cur.clear();
-        }
-        if (info) info[1] = std::max<uint64_t>(info[1], k);
-        for (uint32_t p = 0; p < c.pixels; p++) lgResolvePixel(c, st.lg, par.planes, p, out, total);  // pathClassesResolveKernel
+        const int rc = paths.run(
+            c, [&](const AovChunk&, uint64_t s) { return pcBegin(st, s, as.sh.scene_ior, par); },  // pathClassesBeginKernel
+            [&](const AovChunk& c_, const uint32_t* list, uint32_t live, uint32_t j, uint32_t k, const AovRays& lit, RefractionHistory& rh) {
+                lgRays(c_, as, st.lg, list, live, j, k, lit, rh, E.tab.data());  // pathClassesRayKernel
+            },
+            [&](const AovChunk& c_, const uint32_t* list, uint32_t live, uint32_t j, uint32_t k, bool last, const AovRays& lit, RefractionHistory& rh, bool& too_deep) {
+                return pcStep(c_, as, st, par, list, live, j, k, last, lit, rh, too_deep, E.tab.data());  // pathClassesStepKernel
+            },
+            [&](const AovChunk& c_, uint32_t p) { lgResolvePixel(c_, st.lg, par.planes, p, out, total); });  // pathClassesResolveKernel
+        if (rc) return rc;
     }
+    if (info) info[0] = paths.rays, info[1] = paths.iterations, info[2] = paths.live;
     return 0;
 }
 

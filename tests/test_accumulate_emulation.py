@@ -14,15 +14,13 @@ Exact case: stores of small integers, 16 + 16 samples, whose sums are multiples 
 15 - every intermediate of both routes is then exact up to the one last division, which divides the same two numbers on both sides."""
 import ctypes as C
 import functools
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import test_pixel_stats_emulation as ps
 import test_robust_emulation as rb
-from conftest import ROOT, TESTS
+from emu_build import build_emu
 
 SEED = ps.SEED
 TOPS = 4
@@ -38,17 +36,7 @@ MEANING_SCENES = ("hexagon_room_diffuse", "coffee_maker_qsah")
 
 
 def load_accumulate_emu():
-    src = os.path.join(TESTS, "emu", "accumulate_emu.cpp")
-    out = os.path.join(TESTS, "emu", "_build", "libaccumulate_emu.so")
-    csrc = os.path.join(ROOT, "monte-carlo-ray-tracer_amd", "csrc")
-    deps = [src, os.path.join(csrc, "mcrt_accumulate.hpp"), os.path.join(csrc, "mcrt_robust.hpp"), os.path.join(csrc, "mcrt_math.hpp"),
-            os.path.join(ROOT, "include", "mcrt.h")]
-    if not os.path.exists(out) or any(os.path.getmtime(d) > os.path.getmtime(out) for d in deps):
-        os.makedirs(os.path.dirname(out), exist_ok=True)
-        tmp = "%s.%d.tmp" % (out, os.getpid())
-        subprocess.check_call(["g++", "-std=c++17", "-O2", "-ffp-contract=off", "-fPIC", "-shared", "-o", tmp, src])
-        os.replace(tmp, out)
-    L = C.CDLL(out)
+    L = C.CDLL(build_emu("accumulate_emu.cpp"))
     vp = C.c_void_p
     L.frame_merge_emu.argtypes = [C.c_uint64, vp, C.c_uint32, vp, C.c_uint32, vp]
     return L

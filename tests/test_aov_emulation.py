@@ -12,13 +12,12 @@ relative (conftest.rel_error) - the bound include/mcrt.h states for sums that ag
 device code by a multiplication with the reciprocal, two roundings apart per addend."""
 import ctypes as C
 import functools
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
-from conftest import ROOT, TESTS, golden_path, rel_error
+from conftest import golden_path, rel_error
+from emu_build import build_emu
 
 WIDTH, HEIGHT = 70, 13
 SEED = 0x5EED0A0F
@@ -32,19 +31,9 @@ DBL_MAX = np.finfo(np.float64).max
 
 def load_aov_emu():
     """Host build of the AOV pass (tests/emu/aov_emu.cpp = mcrt_emu.cpp + csrc/mcrt_aov.hpp), the way conftest.load_emu builds its library."""
-    src = os.path.join(TESTS, "emu", "aov_emu.cpp")
-    out = os.path.join(TESTS, "emu", "_build", "libaov_emu.so")
-    csrc = os.path.join(ROOT, "monte-carlo-ray-tracer_amd", "csrc")
-    deps = [src, os.path.join(TESTS, "emu", "mcrt_emu.cpp")] + [os.path.join(csrc, f) for f in os.listdir(csrc) if f.endswith(".hpp")]
-    if not os.path.exists(out) or any(os.path.getmtime(d) > os.path.getmtime(out) for d in deps):
-        os.makedirs(os.path.dirname(out), exist_ok=True)
-        tmp = "%s.%d.tmp" % (out, os.getpid())
-        subprocess.check_call(["g++", "-std=c++17", "-O2", "-ffp-contract=off", "-fPIC", "-shared", "-o", tmp, src])
-        os.replace(tmp, out)
-    L = C.CDLL(out)
+    L = C.CDLL(build_emu("aov_emu.cpp"))
     vp = C.c_void_p
-    L.aov_emu_rows.argtypes = [vp]
-    L.aov_emu_rows.restype = C.c_uint32
+    L.emu_owned_rows.argtypes, L.emu_owned_rows.restype = [vp], C.c_uint32
     L.aov_emu_rays.argtypes = [vp, vp, C.c_uint32, vp, vp]
     L.aov_emu_frame.argtypes = [vp, vp, C.c_uint32, C.c_int, C.c_uint64, vp, vp, vp, vp]
     return L
@@ -73,7 +62,7 @@ def emu_frame(scene, sqrtspp, chunk_rays=0, shard=None):
     import importlib
     pkg = importlib.import_module("monte-carlo-ray-tracer_amd")
     img, cam, L = _image(scene), camera(scene, sqrtspp, shard), _emu()
-    pixels, spp = L.aov_emu_rows(C.byref(cam)) * WIDTH, sqrtspp * sqrtspp
+    pixels, spp = L.emu_owned_rows(C.byref(cam)) * WIDTH, sqrtspp * sqrtspp
     ch = {k: np.empty((pixels,) + ((n,) if n > 1 else ()), dtype=dt) for k, (dt, n) in pkg.AOV_CHANNELS.items()}
     bufs = pkg.AovBuffers()
     for k, a in ch.items():

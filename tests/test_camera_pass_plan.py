@@ -8,12 +8,10 @@ min(max(2^17 * per_pixel, 2^24), 2^26); the light groups' min(min(max(2^17 * per
 sample_bytes = kLgStateBytes + 24 * planes + 2 * 76 + 8."""
 import ctypes as C
 import functools
-import os
-import subprocess
 
 import pytest
 
-from conftest import ROOT, TESTS
+from emu_build import build_emu
 
 LIMIT = 0xFFF00000  # 4293918720
 FIXED = 1 << 24
@@ -21,16 +19,7 @@ FIXED = 1 << 24
 
 @functools.lru_cache(maxsize=None)
 def _emu():
-    src = os.path.join(TESTS, "emu", "camera_pass_emu.cpp")
-    out = os.path.join(TESTS, "emu", "_build", "libcamera_pass_emu.so")
-    csrc = os.path.join(ROOT, "monte-carlo-ray-tracer_amd", "csrc")
-    deps = [src, os.path.join(ROOT, "include", "mcrt.h")] + [os.path.join(csrc, f) for f in os.listdir(csrc) if f.endswith(".hpp")]
-    if not os.path.exists(out) or any(os.path.getmtime(d) > os.path.getmtime(out) for d in deps):
-        os.makedirs(os.path.dirname(out), exist_ok=True)
-        tmp = "%s.%d.tmp" % (out, os.getpid())
-        subprocess.check_call(["g++", "-std=c++17", "-O2", "-ffp-contract=off", "-fPIC", "-shared", "-o", tmp, src])
-        os.replace(tmp, out)
-    L = C.CDLL(out)
+    L = C.CDLL(build_emu("camera_pass_emu.cpp"))
     L.camera_pass_emu_plan.argtypes = [C.c_uint64, C.c_uint32, C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p]
     L.camera_pass_emu_plan.restype = None
     for name, n in (("limit", 0), ("default", 0), ("lighting_default", 1), ("light_groups_default", 2), ("lg_state_bytes", 0)):

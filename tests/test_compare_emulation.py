@@ -25,6 +25,7 @@ import numpy as np
 import pytest
 
 from conftest import ROOT, TESTS
+from emu_build import build_emu
 
 SMALL = ((70, 13), (11, 11), (10, 40), (40, 10), (12, 11))
 LARGE = (257, 256)
@@ -51,21 +52,8 @@ class Result(C.Structure):
 FIELDS = [k for k, _ in Result._fields_ if k != "reserved"]
 
 
-def _deps():
-    csrc = os.path.join(ROOT, "monte-carlo-ray-tracer_amd", "csrc")
-    return [os.path.join(TESTS, "emu", "compare_emu.cpp"), os.path.join(TESTS, "emu", "wave_emu.hpp"), os.path.join(csrc, "mcrt_compare.hpp"),
-            os.path.join(csrc, "mcrt_robust.hpp"), os.path.join(csrc, "mcrt_math.hpp"), os.path.join(ROOT, "include", "mcrt.h")]
-
-
 def load_compare_emu():
-    deps = _deps()
-    out = os.path.join(TESTS, "emu", "_build", "libcompare_emu.so")
-    if not os.path.exists(out) or any(os.path.getmtime(d) > os.path.getmtime(out) for d in deps):
-        os.makedirs(os.path.dirname(out), exist_ok=True)
-        tmp = "%s.%d.tmp" % (out, os.getpid())
-        subprocess.check_call(["g++", "-std=c++17", "-O2", "-ffp-contract=off", "-fPIC", "-shared", "-o", tmp, deps[0]])
-        os.replace(tmp, out)
-    L = C.CDLL(out)
+    L = C.CDLL(build_emu("compare_emu.cpp"))
     vp = C.c_void_p
     L.compare_emu.argtypes = [C.c_uint32, C.c_uint32, vp, vp, vp, C.POINTER(Params), C.POINTER(Maps), C.POINTER(Result), C.c_int, C.c_int]
     L.compare_emu_weight.argtypes = [C.c_uint32]
@@ -381,7 +369,7 @@ def test_stand_alone_sanitizer_run(tmp_path):
     UndefinedBehaviorSanitizer: once, as a subprocess."""
     exe = str(tmp_path / "compare_emu_main")
     subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-DCOMPARE_EMU_MAIN", "-ffp-contract=off", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                           "-static-libasan", "-static-libubsan", "-pthread", "-o", exe, _deps()[0], "-ldl"])
+                           "-static-libasan", "-static-libubsan", "-pthread", "-o", exe, os.path.join(TESTS, "emu", "compare_emu.cpp"), "-ldl"])
     run = subprocess.run([exe], capture_output=True, text=True, timeout=300)
     assert run.returncode == 0 and "runtime error" not in run.stderr and "Sanitizer" not in run.stderr, (run.returncode, run.stdout, run.stderr[-2000:])
     assert run.stdout.startswith("compared ")

@@ -8,13 +8,11 @@ the same order, none of them a libm call, neither side contracted (the harness i
 one operation each) - so every bit agrees, NaNs included."""
 import ctypes as C
 import functools
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
-from conftest import ROOT, TESTS
+from emu_build import build_emu
 
 # explicit parameters everywhere (not the defaults: retuning those must not touch a test)
 PARAMS = dict(k=0.6, alpha=0.9, epsilon=1e-9)
@@ -25,17 +23,7 @@ SHAPES = [(1, 1, 3, 1, 4), (16, 16, 5, 2, 5), (17, 33, 3, 1, 9), (70, 13, 8, 2, 
 
 
 def load_denoise_dual_emu():
-    src = os.path.join(TESTS, "emu", "denoise_dual_emu.cpp")
-    out = os.path.join(TESTS, "emu", "_build", "libdenoise_dual_emu.so")
-    csrc = os.path.join(ROOT, "monte-carlo-ray-tracer_amd", "csrc")
-    deps = [src, os.path.join(TESTS, "emu", "wave_emu.hpp"), os.path.join(csrc, "mcrt_denoise_dual.hpp"), os.path.join(csrc, "mcrt_atrous.hpp"),
-            os.path.join(csrc, "mcrt_math.hpp"), os.path.join(ROOT, "include", "mcrt.h")]
-    if not os.path.exists(out) or any(os.path.getmtime(d) > os.path.getmtime(out) for d in deps):
-        os.makedirs(os.path.dirname(out), exist_ok=True)
-        tmp = "%s.%d.tmp" % (out, os.getpid())
-        subprocess.check_call(["g++", "-std=c++17", "-O2", "-ffp-contract=off", "-fPIC", "-shared", "-o", tmp, src])
-        os.replace(tmp, out)
-    L = C.CDLL(out)
+    L = C.CDLL(build_emu("denoise_dual_emu.cpp"))
     vp = C.c_void_p
     L.denoise_dual_emu.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, vp, C.c_int, vp]
     L.denoise_dual_emu_tile_lds_bytes.argtypes = [C.c_uint32, C.c_uint32]

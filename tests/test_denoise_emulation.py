@@ -7,14 +7,12 @@ the same order, none of them a libm call, neither side contracted (the harness i
 one operation each) - so every bit agrees, NaNs included."""
 import ctypes as C
 import functools
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import test_aov_emulation as aov
-from conftest import ROOT, TESTS
+from emu_build import build_emu
 
 NO_ALBEDO = 1
 GUIDES = ("shading_normal", "normal", "position", "coverage", "albedo")
@@ -23,17 +21,7 @@ PARAMS = dict(normal_power_log2=5, sigma_color=1.5, sigma_plane=0.25, albedo_flo
 
 
 def load_denoise_emu():
-    src = os.path.join(TESTS, "emu", "denoise_emu.cpp")
-    out = os.path.join(TESTS, "emu", "_build", "libdenoise_emu.so")
-    csrc = os.path.join(ROOT, "monte-carlo-ray-tracer_amd", "csrc")
-    deps = [src, os.path.join(TESTS, "emu", "wave_emu.hpp"), os.path.join(csrc, "mcrt_denoise.hpp"), os.path.join(csrc, "mcrt_math.hpp"),
-            os.path.join(ROOT, "include", "mcrt.h")]
-    if not os.path.exists(out) or any(os.path.getmtime(d) > os.path.getmtime(out) for d in deps):
-        os.makedirs(os.path.dirname(out), exist_ok=True)
-        tmp = "%s.%d.tmp" % (out, os.getpid())
-        subprocess.check_call(["g++", "-std=c++17", "-O2", "-ffp-contract=off", "-fPIC", "-shared", "-o", tmp, src])
-        os.replace(tmp, out)
-    L = C.CDLL(out)
+    L = C.CDLL(build_emu("denoise_emu.cpp"))
     vp = C.c_void_p
     L.denoise_emu.argtypes = [C.c_uint32, C.c_uint32, vp, vp, vp, C.c_int, vp]
     L.denoise_emu_tile_blocks.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32]

@@ -8,14 +8,12 @@ the same order, none of them a libm call, neither side contracted (the harness i
 one operation each) - so every bit agrees, NaNs included."""
 import ctypes as C
 import functools
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import test_denoise_emulation as dn
-from conftest import ROOT, TESTS
+from emu_build import build_emu
 
 NO_ALBEDO = dn.NO_ALBEDO
 GUIDES = dn.GUIDES
@@ -25,17 +23,7 @@ _dot, _max0 = dn._dot, dn._max0
 
 
 def load_denoise_var_emu():
-    src = os.path.join(TESTS, "emu", "denoise_var_emu.cpp")
-    out = os.path.join(TESTS, "emu", "_build", "libdenoise_var_emu.so")
-    csrc = os.path.join(ROOT, "monte-carlo-ray-tracer_amd", "csrc")
-    deps = [src, os.path.join(TESTS, "emu", "wave_emu.hpp"), os.path.join(csrc, "mcrt_denoise_var.hpp"), os.path.join(csrc, "mcrt_denoise.hpp"),
-            os.path.join(csrc, "mcrt_math.hpp"), os.path.join(ROOT, "include", "mcrt.h")]
-    if not os.path.exists(out) or any(os.path.getmtime(d) > os.path.getmtime(out) for d in deps):
-        os.makedirs(os.path.dirname(out), exist_ok=True)
-        tmp = "%s.%d.tmp" % (out, os.getpid())
-        subprocess.check_call(["g++", "-std=c++17", "-O2", "-ffp-contract=off", "-fPIC", "-shared", "-o", tmp, src])
-        os.replace(tmp, out)
-    L = C.CDLL(out)
+    L = C.CDLL(build_emu("denoise_var_emu.cpp"))
     vp = C.c_void_p
     L.denoise_var_emu.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, vp, C.c_int, vp, vp]
     L.denoise_var_emu_tile_lds_bytes.restype = C.c_uint32

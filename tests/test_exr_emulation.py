@@ -20,6 +20,7 @@ import numpy as np
 import pytest
 
 from conftest import ROOT, TESTS
+from emu_build import build_emu
 
 UINT, HALF, FLOAT = 0, 1, 2
 SRC_F64, SRC_U32 = 0, 1
@@ -61,18 +62,10 @@ def probe():
 
 
 def load_exr_emu(libz=None):
-    src = os.path.join(TESTS, "emu", "exr_emu.cpp")
-    out = os.path.join(TESTS, "emu", "_build", "libexr_emu%s.so" % ("" if libz is None else "_nolibz"))
-    csrc = os.path.join(ROOT, "monte-carlo-ray-tracer_amd", "csrc")
-    deps = [src, os.path.join(ROOT, "include", "mcrt.h")] + [os.path.join(csrc, f) for f in ("mcrt_exr.hpp", "mcrt_exr_file.hpp", "mcrt_exr_launch.hpp")]
-    if not os.path.exists(out) or any(os.path.getmtime(d) > os.path.getmtime(out) for d in deps):
-        os.makedirs(os.path.dirname(out), exist_ok=True)
-        tmp = "%s.%d.tmp" % (out, os.getpid())
-        flags = [] if libz is None else ['-DMCRT_EXR_LIBZ="%s"' % libz]
-        # (-fno-gnu-unique: the two builds keep their own "zlib loaded?" state in one process)
-        subprocess.check_call(["g++", "-std=c++17", "-O2", "-fPIC", "-shared", "-pthread", "-fno-gnu-unique"] + flags + ["-o", tmp, src, "-ldl"])
-        os.replace(tmp, out)
-    L = C.CDLL(out)
+    # (fp_contract=None: these builds have never carried -ffp-contract=off. -fno-gnu-unique: the two builds keep their own
+    # "zlib loaded?" state in one process)
+    L = C.CDLL(build_emu("exr_emu.cpp", "libexr_emu%s.so" % ("" if libz is None else "_nolibz"), fp_contract=None,
+                         flags=["-pthread", "-fno-gnu-unique"] + ([] if libz is None else ['-DMCRT_EXR_LIBZ="%s"' % libz]), link=["-ldl"]))
     vp = C.c_void_p
     L.exr_half_emu.argtypes = [vp, C.c_uint64, C.c_int, vp]
     L.exr_half_emu.restype = None

@@ -17,7 +17,8 @@ import numpy as np
 import pytest
 
 import test_exr_emulation as ex
-from conftest import ROOT, TESTS
+from conftest import TESTS
+from emu_build import build_emu
 
 OK, ERR_INVALID, ERR_IO, ERR_UNSUPPORTED = 0, ex.ERR_INVALID, ex.ERR_IO, ex.ERR_UNSUPPORTED
 NONE, ZIPS, ZIP = 0, 2, 3
@@ -45,19 +46,10 @@ class Info(C.Structure):
 
 
 def load_read_emu(libz=None):
-    src = os.path.join(TESTS, "emu", "exr_read_emu.cpp")
-    out = os.path.join(TESTS, "emu", "_build", "libexr_read_emu%s.so" % ("" if libz is None else "_nolibz"))
-    csrc = os.path.join(ROOT, "monte-carlo-ray-tracer_amd", "csrc")
-    deps = [src, os.path.join(TESTS, "emu", "wave_emu.hpp"), os.path.join(ROOT, "include", "mcrt.h")]
-    deps += [os.path.join(csrc, f) for f in ("mcrt_exr_read.hpp", "mcrt_exr_read_file.hpp", "mcrt_exr_read_launch.hpp")]
-    if not os.path.exists(out) or any(os.path.getmtime(d) > os.path.getmtime(out) for d in deps):
-        os.makedirs(os.path.dirname(out), exist_ok=True)
-        tmp = "%s.%d.tmp" % (out, os.getpid())
-        flags = [] if libz is None else ['-DMCRT_EXR_LIBZ="%s"' % libz]
-        # (-fno-gnu-unique: the two builds keep their own "zlib loaded?" state in one process)
-        subprocess.check_call(["g++", "-std=c++17", "-O2", "-fPIC", "-shared", "-pthread", "-fno-gnu-unique"] + flags + ["-o", tmp, src, "-ldl"])
-        os.replace(tmp, out)
-    L = C.CDLL(out)
+    # (fp_contract=None: these builds have never carried -ffp-contract=off. -fno-gnu-unique: the two builds keep their own
+    # "zlib loaded?" state in one process)
+    L = C.CDLL(build_emu("exr_read_emu.cpp", "libexr_read_emu%s.so" % ("" if libz is None else "_nolibz"), fp_contract=None,
+                         flags=["-pthread", "-fno-gnu-unique"] + ([] if libz is None else ['-DMCRT_EXR_LIBZ="%s"' % libz]), link=["-ldl"]))
     vp = C.c_void_p
     L.exr_read_half_emu.argtypes = [vp, C.c_uint64, vp]
     L.exr_read_half_emu.restype = None

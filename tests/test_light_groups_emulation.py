@@ -20,15 +20,14 @@ being non-negative."""
 import ctypes as C
 import functools
 import importlib
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import test_aov_emulation as aov
 import test_lighting_emulation as lit
-from conftest import ROOT, TESTS, rel_error
+from conftest import rel_error
+from emu_build import build_emu
 
 WIDTH, HEIGHT, SEED, SCENES = lit.WIDTH, lit.HEIGHT, lit.SEED, lit.SCENES
 PIXELS = WIDTH * HEIGHT
@@ -38,20 +37,11 @@ NO_SURFACE = 0xFFFFFFFF
 def load_light_groups_emu():
     """Host build of the light groups (tests/emu/light_groups_emu.cpp = mcrt_emu.cpp + csrc/mcrt_light_groups.hpp), the way
     test_lighting_emulation.load_lighting_emu builds its library."""
-    src = os.path.join(TESTS, "emu", "light_groups_emu.cpp")
-    out = os.path.join(TESTS, "emu", "_build", "liblight_groups_emu.so")
-    csrc = os.path.join(ROOT, "monte-carlo-ray-tracer_amd", "csrc")
-    deps = [src, os.path.join(TESTS, "emu", "mcrt_emu.cpp"), os.path.join(ROOT, "include", "mcrt.h")] + [os.path.join(csrc, f) for f in os.listdir(csrc) if f.endswith(".hpp")]
-    if not os.path.exists(out) or any(os.path.getmtime(d) > os.path.getmtime(out) for d in deps):
-        os.makedirs(os.path.dirname(out), exist_ok=True)
-        tmp = "%s.%d.tmp" % (out, os.getpid())
-        subprocess.check_call(["g++", "-std=c++17", "-O2", "-ffp-contract=off", "-fPIC", "-shared", "-o", tmp, src])
-        os.replace(tmp, out)
-    L = C.CDLL(out)
+    L = C.CDLL(build_emu("light_groups_emu.cpp"))
     vp = C.c_void_p
-    L.light_groups_emu_rows.argtypes = [vp]
-    L.light_groups_emu_rows.restype = C.c_uint32
-    L.light_groups_emu_first_hits.argtypes = [vp, vp, C.c_uint32, C.c_int, vp]
+    L.emu_owned_rows.argtypes, L.emu_owned_rows.restype = [vp], C.c_uint32
+    L.emu_first_hits.argtypes = [vp, vp, C.c_uint32, C.c_int, vp]
+    L.light_groups_emu_settings.argtypes = [vp, vp, C.c_uint32, vp, C.c_uint32, vp, vp, vp]
     L.light_groups_emu_frame.argtypes = [vp, vp, C.c_uint32, C.c_int, C.c_uint64, vp, C.c_int, vp, vp]
     return L
 
@@ -78,7 +68,7 @@ def emu_planes(scene_desc, cam, flavour, groups=None, num_groups=None, sky_plane
     first (whatever is not written shows). expect: the status the call must return."""
     L = _emu()
     par, keep, planes = params(groups, num_groups, sky_plane, max_depth)
-    pixels = L.light_groups_emu_rows(C.byref(cam)) * cam.width
+    pixels = L.emu_owned_rows(C.byref(cam)) * cam.width
     out = np.empty((planes, pixels, 3))
     out.view(np.uint8).fill(0xAB)
     info = np.zeros(3, dtype=np.uint64)
@@ -90,8 +80,8 @@ def emu_planes(scene_desc, cam, flavour, groups=None, num_groups=None, sky_plane
 def first_hits(scene_desc, cam, flavour):
     """[pixels, spp] the surface every camera sample meets first."""
     L = _emu()
-    surf = np.empty((L.light_groups_emu_rows(C.byref(cam)) * cam.width, cam.sqrtspp * cam.sqrtspp), dtype=np.uint32)
-    assert L.light_groups_emu_first_hits(C.byref(scene_desc), C.byref(cam), SEED, flavour, surf.ctypes.data) == 0
+    surf = np.empty((L.emu_owned_rows(C.byref(cam)) * cam.width, cam.sqrtspp * cam.sqrtspp), dtype=np.uint32)
+    assert L.emu_first_hits(C.byref(scene_desc), C.byref(cam), SEED, flavour, surf.ctypes.data) == 0
     return surf
 
 
@@ -118,7 +108,8 @@ def image_oracle(scene, sqrtspp):
 
 
 def assert_is_the_frame(plane, ref, what):
-    """plane == ref bit for bit in every word where ref is neither negative nor NaN (include/mcrt.h "Light groups")."""
+    """plane == ref bit for bit in every word where ref is neither negative nor NaN (include/mcrt.h "Light groups"; "Path classes",
+    promise 2)."""
     comparable = ~(np.isnan(ref) | (ref < 0.0))
     differ = (plane.view(np.uint64) != ref.view(np.uint64)) & comparable
     print("%s: %d of %d words differ from the path tracer's bits (%d not comparable)" % (what, differ.sum(), ref.size, (~comparable).sum()))
@@ -286,6 +277,25 @@ def test_a_bad_group_entry_and_bad_numbers_are_refused():
     emu_planes(s.scene, cam, 1, groups=s.groups, num_groups=1, expect=-1)  # lamp B's group 1 of 1
     emu_planes(s.scene, cam, 1, num_groups=16, expect=-1)
     emu_planes(s.scene, cam, 1, num_groups=2, sky_plane=3, expect=-1)
+
+
+def test_a_surface_whose_material_is_out_of_range_gets_plane_zero():
+    """The settings the host and the emulation share (csrc/mcrt_light_groups.hpp lgSettingsOf, lgSurfacePlanes), called directly - no
+    render, which would index other arrays with that material. Two surfaces: an emitter in group 1 of 2, and one whose surf_material is
+    num_materials. Behind the one material lies a second, emissive one that num_materials does not count: code that read it would take
+    surface 1 for an emitter and refuse its group 99."""
+    pkg = _pkg()
+    emitter = lit._material(pkg, flags=lit.OPAQUE | lit.EMISSIVE, emittance=(1.0, 1.0, 1.0))
+    mats = (pkg.Material * 2)(emitter, emitter)
+    par, keep, planes = params(groups=np.array([1, 99], dtype=np.uint32), num_groups=2, max_depth=3)
+    surf_material = np.array([0, 1], dtype=np.uint32)
+    out, plane, bad = np.full(4, 0xAB, dtype=np.uint32), np.full(2, 0xAB, dtype=np.uint8), C.c_uint32(0xAB)
+    L = _emu()
+    assert L.light_groups_emu_settings(C.byref(par), surf_material.ctypes.data, 2, mats, 1, out.ctypes.data, plane.ctypes.data, C.byref(bad)) == 0
+    assert list(out) == [2, 2, planes, 3] and planes == 3 and list(plane) == [1, 0] and bad.value == NO_SURFACE
+    # (with both materials counted, surface 1 is the emitter the refusal is about)
+    assert L.light_groups_emu_settings(C.byref(par), surf_material.ctypes.data, 2, mats, 2, out.ctypes.data, plane.ctypes.data, C.byref(bad)) == -1
+    assert bad.value == 1
 
 
 # ------------------------------------------------------------------ 3. max_depth, chunks, shards, list order, sky

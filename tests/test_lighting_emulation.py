@@ -20,14 +20,13 @@ non-negative, and the two sums of the same leading terms differ by roundings onl
 import ctypes as C
 import functools
 import importlib
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import test_aov_emulation as aov
-from conftest import ROOT, TESTS, rel_error
+from conftest import rel_error
+from emu_build import build_emu
 
 WIDTH, HEIGHT, SEED, SCENES = aov.WIDTH, aov.HEIGHT, aov.SEED, aov.SCENES
 PIXELS = WIDTH * HEIGHT
@@ -52,19 +51,9 @@ CONSTRUCTED = [(floor, bvh) for floor in FLOORS for bvh in (False, True)]
 def load_lighting_emu():
     """Host build of the lighting passes (tests/emu/lighting_emu.cpp = mcrt_emu.cpp + csrc/mcrt_lighting.hpp), the way
     test_occlusion_emulation.load_occlusion_emu builds its library."""
-    src = os.path.join(TESTS, "emu", "lighting_emu.cpp")
-    out = os.path.join(TESTS, "emu", "_build", "liblighting_emu.so")
-    csrc = os.path.join(ROOT, "monte-carlo-ray-tracer_amd", "csrc")
-    deps = [src, os.path.join(TESTS, "emu", "mcrt_emu.cpp"), os.path.join(ROOT, "include", "mcrt.h")] + [os.path.join(csrc, f) for f in os.listdir(csrc) if f.endswith(".hpp")]
-    if not os.path.exists(out) or any(os.path.getmtime(d) > os.path.getmtime(out) for d in deps):
-        os.makedirs(os.path.dirname(out), exist_ok=True)
-        tmp = "%s.%d.tmp" % (out, os.getpid())
-        subprocess.check_call(["g++", "-std=c++17", "-O2", "-ffp-contract=off", "-fPIC", "-shared", "-o", tmp, src])
-        os.replace(tmp, out)
-    L = C.CDLL(out)
+    L = C.CDLL(build_emu("lighting_emu.cpp"))
     vp = C.c_void_p
-    L.lighting_emu_rows.argtypes = [vp]
-    L.lighting_emu_rows.restype = C.c_uint32
+    L.emu_owned_rows.argtypes, L.emu_owned_rows.restype = [vp], C.c_uint32
     L.lighting_emu_frame.argtypes = [vp, vp, C.c_uint32, C.c_int, C.c_uint64, vp]
     return L
 
@@ -189,7 +178,7 @@ def emu_frame(scene_desc, cam, flavour, chunk_rays=0, channels=CHANNELS):
     """The emulation's frame over the camera's packed owned rows: dict channel -> [P,3]; every channel is allocated and filled with 0xAB
     bytes, only `channels` are handed over."""
     pkg, L = _pkg(), _emu()
-    P = L.lighting_emu_rows(C.byref(cam)) * cam.width
+    P = L.emu_owned_rows(C.byref(cam)) * cam.width
     res = {k: np.empty((P, 3)) for k in CHANNELS}
     bufs = pkg.LightingBuffers()
     for k, a in res.items():

@@ -9,14 +9,12 @@ three key modes. test_gpu_matte.py imports the definition and the synthetic case
 import ctypes as C
 import functools
 import json
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import test_aov_emulation as aov
-from conftest import ROOT, TESTS
+from emu_build import build_emu
 
 NO_KEY = 0xFFFFFFFF
 PIXELS = 70
@@ -31,17 +29,7 @@ HASH_VECTORS = {"": 0, "hello": 0x248bfa47, "The quick brown fox jumps over the 
 
 def load_matte_emu():
     """Host build of the ranking (tests/emu/matte_emu.cpp = wave_emu.hpp + csrc/mcrt_matte.hpp), the way the other emulations are built."""
-    src = os.path.join(TESTS, "emu", "matte_emu.cpp")
-    out = os.path.join(TESTS, "emu", "_build", "libmatte_emu.so")
-    csrc = os.path.join(ROOT, "monte-carlo-ray-tracer_amd", "csrc")
-    deps = [src, os.path.join(TESTS, "emu", "wave_emu.hpp"), os.path.join(csrc, "mcrt_matte.hpp"), os.path.join(csrc, "mcrt_math.hpp"),
-            os.path.join(ROOT, "include", "mcrt.h")]
-    if not os.path.exists(out) or any(os.path.getmtime(d) > os.path.getmtime(out) for d in deps):
-        os.makedirs(os.path.dirname(out), exist_ok=True)
-        tmp = "%s.%d.tmp" % (out, os.getpid())
-        subprocess.check_call(["g++", "-std=c++17", "-O2", "-ffp-contract=off", "-fPIC", "-shared", "-o", tmp, src])
-        os.replace(tmp, out)
-    L = C.CDLL(out)
+    L = C.CDLL(build_emu("matte_emu.cpp"))
     vp = C.c_void_p
     L.matte_emu_rank.argtypes = [C.c_uint64, C.c_uint32, vp, vp, C.c_uint32, vp, vp, C.c_int, C.c_uint64]
     L.matte_emu_tile_pixels.argtypes = [C.c_uint32]

@@ -27,16 +27,15 @@ Bounds: bit equality where the header promises it; where planes are added up in 
 conftest.rel_error <= 1e-12, include/mcrt.h's bound for sums of non-negative terms taken in another order."""
 import ctypes as C
 import functools
-import importlib
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import test_aov_emulation as aov
 import test_lighting_emulation as lit
-from conftest import ROOT, TESTS, rel_error
+from conftest import rel_error
+from emu_build import build_emu
+from test_light_groups_emulation import _pkg, assert_is_the_frame, constructed_flavour, first_hits, image_oracle  # (the GPU tests reach them as pc.*)
 
 WIDTH, HEIGHT, SEED, SCENES = lit.WIDTH, lit.HEIGHT, lit.SEED, lit.SCENES
 PIXELS = WIDTH * HEIGHT
@@ -51,20 +50,9 @@ MERGED_DIRECT = (0, 1, 2, 3, 2, 4, 2, 5)  # the three direct planes in plane 2
 def load_path_classes_emu():
     """Host build of the path classes (tests/emu/path_classes_emu.cpp = mcrt_emu.cpp + csrc/mcrt_path_classes.hpp), the way
     test_light_groups_emulation.load_light_groups_emu builds its library."""
-    src = os.path.join(TESTS, "emu", "path_classes_emu.cpp")
-    out = os.path.join(TESTS, "emu", "_build", "libpath_classes_emu.so")
-    csrc = os.path.join(ROOT, "monte-carlo-ray-tracer_amd", "csrc")
-    deps = [src, os.path.join(TESTS, "emu", "mcrt_emu.cpp"), os.path.join(ROOT, "include", "mcrt.h")] + [os.path.join(csrc, f) for f in os.listdir(csrc) if f.endswith(".hpp")]
-    if not os.path.exists(out) or any(os.path.getmtime(d) > os.path.getmtime(out) for d in deps):
-        os.makedirs(os.path.dirname(out), exist_ok=True)
-        tmp = "%s.%d.tmp" % (out, os.getpid())
-        subprocess.check_call(["g++", "-std=c++17", "-O2", "-ffp-contract=off", "-fPIC", "-shared", "-o", tmp, src])
-        os.replace(tmp, out)
-    L = C.CDLL(out)
+    L = C.CDLL(build_emu("path_classes_emu.cpp"))
     vp = C.c_void_p
-    L.path_classes_emu_rows.argtypes = [vp]
-    L.path_classes_emu_rows.restype = C.c_uint32
-    L.path_classes_emu_first_hits.argtypes = [vp, vp, C.c_uint32, C.c_int, vp]
+    L.emu_owned_rows.argtypes, L.emu_owned_rows.restype = [vp], C.c_uint32
     L.path_classes_emu_frame.argtypes = [vp, vp, C.c_uint32, C.c_int, C.c_uint64, vp, C.c_int, vp, vp]
     return L
 
@@ -74,31 +62,19 @@ def _emu():
     return load_path_classes_emu()
 
 
-def _pkg():
-    return importlib.import_module("monte-carlo-ray-tracer_amd")
-
-
 def emu_planes(scene_desc, cam, flavour, class_plane=None, max_depth=0, chunk_rays=0, order=0, expect=0):
     """The emulation's planes over the camera's packed owned rows: ([P, pixels, 3], info dict). The array is filled with 0xAB bytes
     first (whatever is not written shows). expect: the status the call must return."""
     L = _emu()
     par = _pkg().Context._path_class_params(class_plane, max_depth)
     planes = 8 if class_plane is None else min(max(class_plane) + 1, 8)
-    pixels = L.path_classes_emu_rows(C.byref(cam)) * cam.width
+    pixels = L.emu_owned_rows(C.byref(cam)) * cam.width
     out = np.empty((planes, pixels, 3))
     out.view(np.uint8).fill(0xAB)
     info = np.zeros(3, dtype=np.uint64)
     rc = L.path_classes_emu_frame(C.byref(scene_desc), C.byref(cam), SEED, flavour, chunk_rays, C.byref(par), order, out.ctypes.data, info.ctypes.data)
     assert rc == expect, "path_classes_emu_frame: %d" % rc
     return out, dict(rays=int(info[0]), iterations=int(info[1]), live=int(info[2]))
-
-
-def first_hits(scene_desc, cam, flavour):
-    """[pixels, spp] the surface every camera sample meets first."""
-    L = _emu()
-    surf = np.empty((L.path_classes_emu_rows(C.byref(cam)) * cam.width, cam.sqrtspp * cam.sqrtspp), dtype=np.uint32)
-    assert L.path_classes_emu_first_hits(C.byref(scene_desc), C.byref(cam), SEED, flavour, surf.ctypes.data) == 0
-    return surf
 
 
 def floor_first(scene_desc, cam, flavour):
@@ -111,10 +87,6 @@ def floor_first(scene_desc, cam, flavour):
     return on_floor.all(axis=1)
 
 
-def constructed_flavour(bvh):
-    return 3 if bvh else 1  # (test_lighting_emulation.constructed_case's)
-
-
 @functools.lru_cache(maxsize=None)
 def constructed_planes(floor, bvh, sqrtspp, class_plane=None, max_depth=0):
     """A constructed scene's planes, computed once (the GPU tests compare with them): ([P, PIXELS, 3], info)."""
@@ -124,24 +96,6 @@ def constructed_planes(floor, bvh, sqrtspp, class_plane=None, max_depth=0):
 @functools.lru_cache(maxsize=None)
 def image_planes(scene, sqrtspp, class_plane=None, max_depth=0):
     return emu_planes(aov._image(scene).scene, aov.camera(scene, sqrtspp), SCENES[scene], class_plane, max_depth)
-
-
-@functools.lru_cache(maxsize=None)
-def image_oracle(scene, sqrtspp):
-    import oracle_lib
-    frame, _ = oracle_lib.render(aov._image(scene), aov.camera(scene, sqrtspp), SEED, _pkg().INTEGRATOR_PATH_TRACER)
-    return frame.reshape(PIXELS, 3)
-
-
-def assert_is_the_frame(plane, ref, what):
-    """plane == ref bit for bit in every word where ref is neither negative nor NaN (include/mcrt.h "Path classes", promise 2)."""
-    comparable = ~(np.isnan(ref) | (ref < 0.0))
-    differ = (plane.view(np.uint64) != ref.view(np.uint64)) & comparable
-    print("%s: %d of %d words differ from the path tracer's bits (%d not comparable)" % (what, differ.sum(), ref.size, (~comparable).sum()))
-    for q in np.nonzero(differ.any(axis=1))[0][:5]:
-        print("   pixel %d: plane %r, path tracer %r" % (q, plane[q], ref[q]))
-    assert comparable.sum() > ref.size // 2, what
-    assert not differ.any(), what
 
 
 def assert_planes_add_up(planes, ref, what):

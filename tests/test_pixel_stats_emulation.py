@@ -11,31 +11,19 @@ halves, weighted by their counts, is the mean up to the rounding of two differen
 far inside 1e-14 relative where no cancellation happens (the radiance samples are non-negative)."""
 import ctypes as C
 import functools
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import test_aov_emulation as aov
-from conftest import ROOT, TESTS
+from emu_build import build_emu
 
 WIDTH, HEIGHT, SEED = 70, 13, 0x5EED0A0F
 ORACLE_SCENES = ("hexagon_room_diffuse", "coffee_maker_qsah", "ior_test")
 
 
 def load_pixel_stats_emu():
-    src = os.path.join(TESTS, "emu", "pixel_stats_emu.cpp")
-    out = os.path.join(TESTS, "emu", "_build", "libpixel_stats_emu.so")
-    csrc = os.path.join(ROOT, "monte-carlo-ray-tracer_amd", "csrc")
-    deps = [src, os.path.join(TESTS, "emu", "wave_emu.hpp"), os.path.join(csrc, "mcrt_pixel_stats.hpp"), os.path.join(csrc, "mcrt_math.hpp"),
-            os.path.join(ROOT, "include", "mcrt.h")]
-    if not os.path.exists(out) or any(os.path.getmtime(d) > os.path.getmtime(out) for d in deps):
-        os.makedirs(os.path.dirname(out), exist_ok=True)
-        tmp = "%s.%d.tmp" % (out, os.getpid())
-        subprocess.check_call(["g++", "-std=c++17", "-O2", "-ffp-contract=off", "-fPIC", "-shared", "-o", tmp, src])
-        os.replace(tmp, out)
-    L = C.CDLL(out)
+    L = C.CDLL(build_emu("pixel_stats_emu.cpp"))
     vp = C.c_void_p
     L.pixel_stats_emu.argtypes = [vp, C.c_uint64, C.c_uint32, C.c_int, vp, vp, vp]
     L.frame_noise_emu.argtypes = [C.c_uint64, C.c_uint32, vp, vp, vp]

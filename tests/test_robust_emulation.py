@@ -11,14 +11,12 @@ luminance before or after, 3 (n + 2) roundings of relative size 2^-53 at most on
 1e-12 the GPU tests use."""
 import ctypes as C
 import functools
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import test_pixel_stats_emulation as ps
-from conftest import ROOT, TESTS
+from emu_build import build_emu
 
 WIDTH, HEIGHT, SEED = ps.WIDTH, ps.HEIGHT, ps.SEED
 TOPS = 4
@@ -28,16 +26,7 @@ bits = ps.bits
 
 
 def load_robust_emu():
-    src = os.path.join(TESTS, "emu", "robust_emu.cpp")
-    out = os.path.join(TESTS, "emu", "_build", "librobust_emu.so")
-    csrc = os.path.join(ROOT, "monte-carlo-ray-tracer_amd", "csrc")
-    deps = [src, os.path.join(csrc, "mcrt_robust.hpp"), os.path.join(csrc, "mcrt_math.hpp"), os.path.join(ROOT, "include", "mcrt.h")]
-    if not os.path.exists(out) or any(os.path.getmtime(d) > os.path.getmtime(out) for d in deps):
-        os.makedirs(os.path.dirname(out), exist_ok=True)
-        tmp = "%s.%d.tmp" % (out, os.getpid())
-        subprocess.check_call(["g++", "-std=c++17", "-O2", "-ffp-contract=off", "-fPIC", "-shared", "-o", tmp, src])
-        os.replace(tmp, out)
-    L = C.CDLL(out)
+    L = C.CDLL(build_emu("robust_emu.cpp"))
     vp = C.c_void_p
     L.robust_highlights_emu.argtypes = [vp, C.c_uint64, C.c_uint32, vp, vp]
     L.robust_resolve_emu.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, C.c_double, C.c_double, C.c_uint32, vp, vp, vp]
