@@ -1462,8 +1462,8 @@ int mcrt_render_adaptive(mcrt_ctx* ctx, const mcrt_camera_desc* cam, uint32_t gl
  * than 0xFFF00000 records (what one closest-hit search takes) are refused (MCRT_ERR_UNSUPPORTED). The arrays are what
  * mcrt_intersect_device reads. mcrt_camera_rays: the same with HOST pointers.
  * Not done: lenses inside the render kernels (mcrt_render, variance and half-buffers, highlights, adaptive and converged rendering),
- * caller-supplied ray arrays as a model, stereo or omnidirectional-stereo cameras, a thin lens on the new models, photon-mapped frames,
- * an inverse mapping from world point to pixel. */
+ * stereo or omnidirectional-stereo cameras, a thin lens on the new models, photon-mapped frames, an inverse mapping from world point to
+ * pixel. (Caller-supplied ray arrays: "Ray sources" below, a state of its own beside the lens.) */
 enum { MCRT_LENS_NONE = 0, MCRT_LENS_PERSPECTIVE = 1, MCRT_LENS_ORTHOGRAPHIC = 2, MCRT_LENS_EQUIRECTANGULAR = 3, MCRT_LENS_FISHEYE = 4 };
 typedef struct mcrt_lens_desc {
     uint32_t model, flags;      /* flags: 0 */
@@ -1477,6 +1477,79 @@ int mcrt_camera_rays_device(mcrt_ctx* ctx, const mcrt_camera_desc* cam, uint32_t
                             mcrt_stats* stats /* may be NULL */);
 int mcrt_camera_rays(mcrt_ctx* ctx, const mcrt_camera_desc* cam, uint32_t global_seed, double* start, double* direction,
                      mcrt_stats* stats /* may be NULL */);
+
+/* ------------------------------------------------------------------------------------------
+ * Ray sources: caller-supplied rays and surface gathers for the passes that trace camera rays. With a source set on the context the
+ * first ray of every pixel sample comes from the caller's arrays instead of a camera: "what is the light along these rays" (a lens
+ * computed by the caller, rays shot again from the positions of an AOV frame) and "what light arrives at these surface points"
+ * (lightmap and vertex baking, irradiance probes - with the light groups per lamp). A source is a state of its own beside the lens;
+ * the two exclude each other. Under a source the camera of a call gives the frame's shape (width, height, sqrtspp, shard) and the
+ * sampler key of a pixel, y * width + x, and nothing else: eye, forward, left, up and the thin lens are not read, a thin-lens camera
+ * is accepted.
+ *
+ * `pixels` is the number of packed pixels the arrays were made for: owned rows * width of the camera's shard (mcrt_shard_rows).
+ * Packed pixel q is local row q / width, column q % width. Every call that uses the source checks `pixels` against its camera, and
+ * `spp` against sqrtspp^2 where the source reads it; a mismatch is MCRT_ERR_INVALID with a message that names both numbers.
+ * `first` and `second` are DEVICE pointers, the caller's: they must stay valid until the source is replaced or taken off, must not
+ * alias an output of a pass that runs under the source, nor the output of mcrt_camera_rays_device while set.
+ *
+ *   MCRT_RAY_SOURCE_RAYS     first = start, second = direction, [spp][pixels][3] doubles each: record i * pixels + q is sample i of
+ *                            packed pixel q - what mcrt_camera_rays_device writes and mcrt_intersect_device reads. With flag
+ *                            MCRT_RAY_SOURCE_PER_PIXEL the arrays are [pixels][3], every sample of pixel q takes record q, and spp
+ *                            is not read. The ray is makeRay(start, direction, scene_ior) with the six words' BITS copied: nothing
+ *                            is normalised, a -0 stays -0; a unit direction is the caller's duty. A record is usable when all six
+ *                            words are finite (v >= -DBL_MAX && v <= DBL_MAX) and the direction is not all zero (+0 or -0); an
+ *                            unusable record becomes start (0,0,0), direction (0,0,1): nothing non-finite reaches the closest-hit
+ *                            search. offset is not read.
+ *   MCRT_RAY_SOURCE_SURFACE  first = position, second = normal, [pixels][3] doubles each: the AOV pass's `position` and `normal` (or
+ *                            `shading_normal`) frames as they lie in device memory, or a lightmap's texels. flags must be 0, spp is
+ *                            not read. Per sample i of pixel (x, y), packed pixel q, in FP64, uncontracted:
+ *                              sampler at initiate(global_seed, y * width + x), setIndex(i)
+ *                              u0 = get(kDimPixel),  u1 = get(kDimPixel + 1)   (the film-position pair of the camera's own ray: the
+ *                                                                               sampler consumption is the camera's)
+ *                              P = position[q],  N = normal[q]
+ *                              nn = (N.x * N.x + N.y * N.y) + N.z * N.z
+ *                              Nn = nn > 0 && nn <= DBL_MAX ? N * (1 / sqrt(nn)) : (0, 0, 1)
+ *                              P = (0, 0, 0) unless its three words are finite
+ *                              direction = csFrom(orthonormalBasis(Nn), cosWeightedHemi(u0, u1))   (csrc/mcrt_math.hpp, mcrt_shade.hpp:
+ *                                          the occlusion pass's construction; sincos is the restated glibc routine)
+ *                              start = P + Nn * offset
+ *                            offset must be finite and >= 0 (the binding's default is 1e-9, the project's kEpsilon). The mean over a
+ *                            pixel's samples of the radiance along these rays, times pi, is the irradiance at P (the pdf of the
+ *                            direction is cos / pi); the light groups give it per lamp.
+ *
+ * mcrt_set_ray_source validates the descriptor and copies it into the context, where it stays until the next call; NULL or kind
+ * MCRT_RAY_SOURCE_NONE takes the source off, and every byte of every call is what it was. mcrt_get_ray_source returns the descriptor
+ * as it was given (all zero with none set). mcrt_set_ray_source_host is the same with HOST pointers: the arrays are copied into device
+ * memory the context owns and frees at the next set (either form) or at mcrt_destroy; *sanitised (may be NULL) receives the number
+ * of records the kernel will replace - RAYS: the unusable ones; SURFACE: a position that is not finite or a normal whose nn is not in
+ * (0, DBL_MAX]. mcrt_get_ray_source then returns the device pointers of the copy.
+ * Refused with MCRT_ERR_INVALID and a message: an unknown kind, unknown flag bits, non-zero reserved words, a NULL array,
+ * pixels == 0, spp == 0 where it is read, an offset that is not finite or below 0 (SURFACE), a lens set on the context (the message
+ * names mcrt_set_lens; mcrt_set_lens with a model is likewise refused while a source is set, naming mcrt_set_ray_source), a render in
+ * flight. While a source is set:
+ *   - mcrt_render_aov*, _matte*, _occlusion*, _lighting*, _light_groups* and _path_classes* and mcrt_camera_rays* take their rays
+ *     from it (mcrt_camera_rays_device then returns the rays as the passes trace them, sanitised);
+ *   - every call that makes its camera rays inside a render kernel refuses with MCRT_ERR_UNSUPPORTED and a message that names
+ *     mcrt_set_ray_source: mcrt_render*, mcrt_render_film_device, mcrt_render_multi and what is built on them (pixel statistics,
+ *     highlights, converged rendering), and mcrt_render_adaptive*.
+ * Not done: next-event estimation at P itself (a gather, not a path vertex: P's own material is never read), photon-mapped frames, a
+ * source inside the render kernels, per-ray outputs (a pixel's samples are still averaged). */
+enum { MCRT_RAY_SOURCE_NONE = 0, MCRT_RAY_SOURCE_RAYS = 1, MCRT_RAY_SOURCE_SURFACE = 2 };
+#define MCRT_RAY_SOURCE_PER_PIXEL 1u /* flags, RAYS: the arrays are [pixels][3] */
+typedef struct mcrt_ray_source_desc {
+    uint32_t      kind, flags;
+    uint64_t      pixels;          /* packed pixels the arrays were made for: owned rows * width */
+    uint32_t      spp, reserved0;  /* RAYS without PER_PIXEL: the samples per pixel the arrays hold; reserved0: 0 */
+    const double* first;           /* RAYS: start,     SURFACE: position */
+    const double* second;          /* RAYS: direction, SURFACE: normal */
+    double        offset;          /* SURFACE: start = P + Nn * offset, finite and >= 0 */
+    uint64_t      reserved[2];     /* 0 */
+} mcrt_ray_source_desc;            /* 64 bytes */
+int mcrt_set_ray_source(mcrt_ctx* ctx, const mcrt_ray_source_desc* source /* NULL or kind NONE: none */);
+int mcrt_set_ray_source_host(mcrt_ctx* ctx, const mcrt_ray_source_desc* source /* first, second: HOST pointers */,
+                             uint64_t* sanitised /* may be NULL */);
+int mcrt_get_ray_source(mcrt_ctx* ctx, mcrt_ray_source_desc* out);
 
 /* Photon emission pass on the GPU. Replaces the thread fan-out of
  * PhotonMapper::PhotonMapper (integrator/photon-mapper/photon-mapper.cpp:80-115: per emission

@@ -50,6 +50,8 @@ int validate(mcrt_ctx* ctx, const mcrt_camera_desc* cam, const mcrt_adaptive_par
     if (int rc = ctxIdle(ctx, what)) return rc;
     if (ctxLens(ctx))  // (the lists' camera rays are this library's own kernel, the perspective camera's)
         return ctxFail(ctx, MCRT_ERR_UNSUPPORTED, std::string(what) + ": a lens is set (mcrt_set_lens): adaptive sampling traces the camera's own rays only");
+    if (ctxRaySource(ctx))
+        return ctxFail(ctx, MCRT_ERR_UNSUPPORTED, std::string(what) + ": a ray source is set (mcrt_set_ray_source): adaptive sampling traces the camera's own rays only");
     if (!cam) return ctxFail(ctx, MCRT_ERR_INVALID, std::string(what) + ": camera is NULL");
     if (!frame) return ctxFail(ctx, MCRT_ERR_INVALID, std::string(what) + ": the frame (out_rgb) is NULL");
     if (int rc = ctxNeedScene(ctx, what)) return rc;

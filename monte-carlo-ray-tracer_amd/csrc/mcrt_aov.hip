@@ -17,6 +17,7 @@
 #include "mcrt_aov_launch.hpp"
 #include "mcrt_lens.hpp"
 #include "mcrt_lens_launch.hpp"
+#include "mcrt_ray_source.hpp"
 
 using namespace mcrt;
 
@@ -42,18 +43,46 @@ __device__ __forceinline__ void lensRaysOf(const AovChunk& c, LensSettings lens,
     }
 }
 
-// lens.model MCRT_LENS_NONE: the camera's own rays, the loop this kernel has always run (the sine / cosine table read from memory, not
-// staged). Any other model: the table staged in LDS as lightingRayKernel does, then that model's loop.
+// What the kernel takes of a lens OR a ray source (they exclude each other), in the bytes of LensSettings: the model, in LensSettings'
+// padding the stride between two samples of a source's arrays (a shard has fewer than 2^32 pixels; 0: per-pixel arrays), and three
+// words - a lens's width_world, fov_x, fov_y or a source's two arrays and its offset. So a source adds no argument to the kernel: the
+// loops of calls without one keep their registers (profiles/NOTES_ray_source.md: as arguments of their own the source's words spilled).
+struct RayHead {
+    uint32_t model, stride;
+    union Word {
+        double d;
+        const double* p;
+    } w[3];
+};
+static_assert(sizeof(RayHead) == sizeof(LensSettings), "RayHead is LensSettings' bytes");
+
+// The grid-stride loop of one kind of ray source (mcrt_ray_source.hpp): RAYS a guarded gather - chunk record i * c.pixels + p reads source
+// record i * stride + (c.first_pixel + p), consecutive lanes consecutive 24-byte records -, SURFACE 48 bytes per pixel and the
+// cosine-weighted direction about its normal.
+template <uint32_t kKind>
+__device__ __forceinline__ void sourceRaysOf(const AovChunk& c, const RayHead& h, double scene_ior, SobolTab tab, const AovRays& rays) {
+    const RaySource source{kKind, h.stride == 0u ? 1u : 0u, h.stride, 0u, h.w[0].p, h.w[1].p, h.w[2].d};
+    const uint64_t n = (uint64_t)c.pixels * c.spp;
+    for (uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; r < n; r += (uint64_t)gridDim.x * blockDim.x) {
+        const Ray ray = sourceRay<true>(c, source, scene_ior, (uint32_t)(r % c.pixels), (uint32_t)(r / c.pixels), tab);
+        aovStore3(rays.start, r, ray.start);
+        aovStore3(rays.direction, r, ray.direction);
+    }
+}
+
+// h.model MCRT_LENS_NONE: the camera's own rays, the loop this kernel has always run (the sine / cosine table read from memory, not
+// staged). Any other model: the table staged in LDS as lightingRayKernel does, then that model's loop - the two internal models past
+// MCRT_LENS_FISHEYE are the ray source's loops (launchSourceRays), which read nothing of the camera but the pixels' names.
 // Four waves a SIMD, what the kernel had before it learned the models (98 VGPRs then): left alone the compiler takes 140 VGPRs, three
 // waves; held to 128 it still spills nothing (profiles/NOTES_lens.md).
-__global__ void __launch_bounds__(kAovBlock) __attribute__((amdgpu_waves_per_eu(4, 4))) aovRayKernel(AovChunk c, LensSettings lens, double scene_ior, const uint32_t* sobol_tab, AovRays rays) {
+__global__ void __launch_bounds__(kAovBlock) __attribute__((amdgpu_waves_per_eu(4, 4))) aovRayKernel(AovChunk c, RayHead h, double scene_ior, const uint32_t* sobol_tab, AovRays rays) {
     __shared__ uint32_t ltab[kSobolTableWords];
     for (uint32_t i = threadIdx.x; i < (uint32_t)kSobolTableWords; i += blockDim.x) ltab[i] = sobol_tab[i];
-    if (lens.model != MCRT_LENS_NONE) glibc235::stageSinCosTab();  // (a kernel argument: every lane of the workgroup takes the same side)
+    if (h.model != MCRT_LENS_NONE) glibc235::stageSinCosTab();  // (a kernel argument: every lane of the workgroup takes the same side)
     __syncthreads();
     // The arguments' doubles and pointers into VGPRs before the branch: as SGPRs the union of what the loops read stays live across the
     // staging loops and the branch next to each loop's own FP64 constants (a pair each), and SGPRs spill to lanes. The values are the
-    // same bits; there are VGPRs to spare (profiles/NOTES_lens.md).
+    // same bits; there are VGPRs to spare (profiles/NOTES_lens.md). (The head's three words as doubles, whatever they hold.)
 #pragma unroll
     for (int k = 0; k < 3; k++) {
         toVgpr(c.cam.eye[k]);
@@ -65,14 +94,15 @@ __global__ void __launch_bounds__(kAovBlock) __attribute__((amdgpu_waves_per_eu(
     toVgpr(c.cam.sensor_width);
     toVgpr(c.cam.aperture_radius);
     toVgpr(c.cam.focus_distance);
-    toVgpr(lens.width_world);
-    toVgpr(lens.fov_x);
-    toVgpr(lens.fov_y);
+    toVgpr(h.w[0].d);
+    toVgpr(h.w[1].d);
+    toVgpr(h.w[2].d);
     toVgpr(scene_ior);
     toVgpr(rays.start);
     toVgpr(rays.direction);
     toVgpr(c.first_pixel);
-    switch (lens.model) {
+    const LensSettings lens{h.model, h.w[0].d, h.w[1].d, h.w[2].d};
+    switch (h.model) {
         case MCRT_LENS_NONE: {
             const uint64_t n = (uint64_t)c.pixels * c.spp;
             for (uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; r < n; r += (uint64_t)gridDim.x * blockDim.x) {
@@ -85,6 +115,10 @@ __global__ void __launch_bounds__(kAovBlock) __attribute__((amdgpu_waves_per_eu(
         case MCRT_LENS_PERSPECTIVE: lensRaysOf<MCRT_LENS_PERSPECTIVE>(c, lens, scene_ior, (SobolTab)ltab, rays); break;
         case MCRT_LENS_ORTHOGRAPHIC: lensRaysOf<MCRT_LENS_ORTHOGRAPHIC>(c, lens, scene_ior, (SobolTab)ltab, rays); break;
         case MCRT_LENS_EQUIRECTANGULAR: lensRaysOf<MCRT_LENS_EQUIRECTANGULAR>(c, lens, scene_ior, (SobolTab)ltab, rays); break;
+        // (the source's two loops as cases of their own and FISHEYE the default, as it was: with a source's loop as the default the
+        // compiler spills three constants of the thin-lens PERSPECTIVE loop, the kernel's register maximum - profiles/NOTES_ray_source.md)
+        case kLensModelSourceRays: sourceRaysOf<MCRT_RAY_SOURCE_RAYS>(c, h, scene_ior, (SobolTab)ltab, rays); break;
+        case kLensModelSourceSurface: sourceRaysOf<MCRT_RAY_SOURCE_SURFACE>(c, h, scene_ior, (SobolTab)ltab, rays); break;
         default: lensRaysOf<MCRT_LENS_FISHEYE>(c, lens, scene_ior, (SobolTab)ltab, rays); break;
     }
 }
@@ -101,14 +135,37 @@ __global__ void __launch_bounds__(kAovBlock) aovResolveKernel(AovChunk c, AovSce
     aovFinish(acc, c.spp, out, c.first_pixel + p);
 }
 
+int launchRays(void* stream, const AovChunk& c, const RayHead& h, double scene_ior, const uint32_t* sobol_tab, const AovRays& rays) {
+    const uint64_t n = (uint64_t)c.pixels * c.spp;
+    const uint32_t grid = (uint32_t)std::min<uint64_t>((n + kAovBlock - 1) / kAovBlock, 4096);
+    hipLaunchKernelGGL(aovRayKernel, dim3(grid), dim3(kAovBlock), 0, (hipStream_t)stream, c, h, scene_ior, sobol_tab, rays);
+    return (int)hipGetLastError();
+}
 }  // namespace
 
 namespace mcrt {
 int launchLensRays(void* stream, const AovChunk& c, const LensSettings& lens, double scene_ior, const uint32_t* sobol_tab, const AovRays& rays) {
-    const uint64_t n = (uint64_t)c.pixels * c.spp;
-    const uint32_t grid = (uint32_t)std::min<uint64_t>((n + kAovBlock - 1) / kAovBlock, 4096);
-    hipLaunchKernelGGL(aovRayKernel, dim3(grid), dim3(kAovBlock), 0, (hipStream_t)stream, c, lens, scene_ior, sobol_tab, rays);
-    return (int)hipGetLastError();
+    RayHead h{};
+    h.model = lens.model;
+    h.w[0].d = lens.width_world;
+    h.w[1].d = lens.fov_x;
+    h.w[2].d = lens.fov_y;
+    return launchRays(stream, c, h, scene_ior, sobol_tab, rays);
+}
+// The chunk's records must lie inside the source's arrays (first_pixel + pixels <= source.pixels < 2^32, and no more samples than
+// per-sample arrays hold): the calls check the camera's shard against the descriptor before any chunk is cut (checkCamera), and the
+// launch refuses what would read past them.
+int launchSourceRays(void* stream, const AovChunk& c, const RaySource& source, double scene_ior, const uint32_t* sobol_tab, const AovRays& rays) {
+    if ((source.kind != MCRT_RAY_SOURCE_RAYS && source.kind != MCRT_RAY_SOURCE_SURFACE) || !source.a || !source.b || source.pixels > 0xFFFFFFFFull ||
+        c.first_pixel + c.pixels > source.pixels || (raySourceReadsSpp(source) && c.spp > source.spp))
+        return (int)hipErrorInvalidValue;
+    RayHead h{};
+    h.model = source.kind == MCRT_RAY_SOURCE_RAYS ? kLensModelSourceRays : kLensModelSourceSurface;
+    h.stride = source.kind == MCRT_RAY_SOURCE_RAYS && !source.per_pixel ? (uint32_t)source.pixels : 0u;
+    h.w[0].p = source.a;
+    h.w[1].p = source.b;
+    h.w[2].d = source.offset;
+    return launchRays(stream, c, h, scene_ior, sobol_tab, rays);
 }
 int launchAovRays(void* stream, const AovChunk& c, double scene_ior, const uint32_t* sobol_tab, const AovRays& rays) {
     return launchLensRays(stream, c, LensSettings{MCRT_LENS_NONE, 0.0, 0.0, 0.0}, scene_ior, sobol_tab, rays);

@@ -92,6 +92,22 @@ inline int cameraPassReady(mcrt_ctx* ctx, const char* what) {  // (the scene fir
     return ctxIdle(ctx, what);
 }
 
+// The frame's order under the context's ray source ("Ray sources" in mcrt.h): the same chunks, the rays from the source's loops of
+// aovRayKernel (launchSourceRays, csrc/mcrt_aov.hip).
+struct SourcePixels {
+    RaySource source{};  // (kind MCRT_RAY_SOURCE_NONE, which the launch refuses, should the descriptor not be a valid one)
+    explicit SourcePixels(const mcrt_ray_source_desc& d) {
+        const char* why = nullptr;
+        if (raySourceSettings(d, source, &why) != MCRT_OK) source = RaySource{};  // (cannot happen: mcrt_set_ray_source lets no other descriptor into the context)
+    }
+    AovChunk chunk(const mcrt_camera_desc& cam, uint32_t global_seed, uint32_t spp, uint64_t first, uint64_t chunk_pixels, uint64_t total_pixels) const {
+        return chunkAt(cam, global_seed, spp, first, chunk_pixels, total_pixels);
+    }
+    int rays(hipStream_t stream, const AovChunk& c, double scene_ior, const uint32_t* sobol_tab, const AovRays& rays_) const {
+        return launchSourceRays(stream, c, source, scene_ior, sobol_tab, rays_);
+    }
+};
+
 // The camera's own checks. given: the call's other pointers are there; missing: what the message names when they or cam are not.
 inline int checkCamera(mcrt_ctx* ctx, const mcrt_camera_desc* cam, bool given, const char* what, const char* missing = "cam or buffers is NULL") {
     if (!cam || !given) return ctxFail(ctx, MCRT_ERR_INVALID, std::string(what) + ": " + missing);
@@ -102,6 +118,18 @@ inline int checkCamera(mcrt_ctx* ctx, const mcrt_camera_desc* cam, bool given, c
     if (const mcrt_lens_desc* lens = ctxLens(ctx))
         if (!lensTakesCamera(*lens, *cam))
             return ctxFail(ctx, MCRT_ERR_UNSUPPORTED, std::string(what) + ": a thin-lens camera under the lens of mcrt_set_lens - only MCRT_LENS_PERSPECTIVE has a thin lens");
+    if (const mcrt_ray_source_desc* source = ctxRaySource(ctx)) {  // the arrays were made for this shard's packed pixels (and samples)
+        const SourcePixels sp(*source);
+        const uint64_t pixels = (uint64_t)mcrt_shard_rows(cam, nullptr) * cam->width;
+        const uint32_t spp = cam->sqrtspp * cam->sqrtspp;
+        const int which = raySourceTakesCamera(sp.source, pixels, spp);
+        if (which == 1)
+            return ctxFail(ctx, MCRT_ERR_INVALID, std::string(what) + ": the ray source of mcrt_set_ray_source was made for " + std::to_string(sp.source.pixels) +
+                                                      " packed pixels, the camera's shard has " + std::to_string(pixels) + " (owned rows x width)");
+        if (which == 2)
+            return ctxFail(ctx, MCRT_ERR_INVALID, std::string(what) + ": the ray source of mcrt_set_ray_source holds " + std::to_string(sp.source.spp) +
+                                                      " samples per pixel, the camera takes " + std::to_string(spp) + " (sqrtspp squared)");
+    }
     return MCRT_OK;
 }
 
@@ -143,7 +171,7 @@ struct CameraPass {
 
 // How the chunks of a call name their pixels, as the chunk loop needs it: chunk(...) is the record of a chunk, rays(...) queues the
 // kernel that writes its camera rays. Here the frame's own order - pixel p of a chunk is packed pixel first_pixel + p, the rays are
-// libmcrt_aov.so's -; under a lens LensPixels below; the adaptive pass has a naming through a pixel list (mcrt_adaptive_host.hip).
+// libmcrt_aov.so's -; under a lens LensPixels below, under a ray source SourcePixels above; the adaptive pass has a naming through a pixel list (mcrt_adaptive_host.hip).
 struct FramePixels {
     AovChunk chunk(const mcrt_camera_desc& cam, uint32_t global_seed, uint32_t spp, uint64_t first, uint64_t chunk_pixels, uint64_t total_pixels) const {
         return chunkAt(cam, global_seed, spp, first, chunk_pixels, total_pixels);
@@ -198,6 +226,7 @@ template <class Body>
 int runChunks(mcrt_ctx* ctx, const CameraPass& cp, PassTimer& timer, const mcrt_camera_desc* cam, uint32_t global_seed, const PixelChunks& plan, const AovRays& rays,
               mcrt_stats* stats, Body body) {
     if (const mcrt_lens_desc* lens = ctxLens(ctx)) return runChunksOf(LensPixels(*lens), ctx, cp, timer, cam, global_seed, plan, rays, stats, body);
+    if (const mcrt_ray_source_desc* source = ctxRaySource(ctx)) return runChunksOf(SourcePixels(*source), ctx, cp, timer, cam, global_seed, plan, rays, stats, body);
     return runChunksOf(FramePixels{}, ctx, cp, timer, cam, global_seed, plan, rays, stats, body);
 }
 

@@ -131,6 +131,8 @@ struct mcrt_ctx {
     // a frame mcrt_render_finish renders again fills them again): packed like the frame, rgb not used; all nullptr = none, nothing in a render changes
     mcrt_frame_summary sample_targets{};
     mcrt_lens_desc lens{};  // mcrt_set_lens ("Camera models"): model MCRT_LENS_NONE = none set
+    mcrt_ray_source_desc ray_source{};  // mcrt_set_ray_source ("Ray sources"): kind MCRT_RAY_SOURCE_NONE = none set
+    DevBuf ray_source_owned[2];         // mcrt_set_ray_source_host: the arrays' device copies, freed at the next set or with the context
     std::map<std::string, std::string> options;  // mcrt_set_option; seeded from the MCRT_* environment variables at mcrt_create
     DevBuf pm_iors;  // refraction histories of the 1024-lane photon-mapping kernel
     // the frame in flight, kept so that mcrt_render_finish can run it again through the wavefront pipeline (deep refraction histories)
@@ -694,6 +696,9 @@ int launchRender(mcrt_ctx* ctx, const mcrt_camera_desc* cam, uint32_t global_see
     if (ctx->lens.model != MCRT_LENS_NONE)
         return fail(ctx, MCRT_ERR_UNSUPPORTED, "a lens is set (mcrt_set_lens): the render kernels trace the camera's own rays only - the camera-ray passes render "
                                                "under a lens; mcrt_set_lens(ctx, NULL) takes it off");
+    if (ctx->ray_source.kind != MCRT_RAY_SOURCE_NONE)
+        return fail(ctx, MCRT_ERR_UNSUPPORTED, "a ray source is set (mcrt_set_ray_source): the render kernels trace the camera's own rays only - the camera-ray "
+                                               "passes trace a source's; mcrt_set_ray_source(ctx, NULL) takes it off");
     // Option MCRT_DEVICE_ORDER=0 (per context, like every option; TEST ONLY: tools/shared_gpu_stress.py, which looks for the fault the
     // ordering was added against): this context's frames do not wait on the GPU for the device's previous launcher. The mutex stays
     // either way - "size this kernel's dynamic LDS, then launch it" must be one step (DeviceOrder's comment).
@@ -1781,4 +1786,13 @@ int ctxSampleTargetsBegin(mcrt_ctx* ctx, const mcrt_camera_desc* cam, const mcrt
 void ctxSampleTargetsEnd(mcrt_ctx* ctx) { ctx->sample_targets = mcrt_frame_summary{}; }
 const mcrt_lens_desc* ctxLens(const mcrt_ctx* ctx) { return ctx->lens.model != MCRT_LENS_NONE ? &ctx->lens : nullptr; }
 void ctxSetLens(mcrt_ctx* ctx, const mcrt_lens_desc& lens) { ctx->lens = lens; }
+const mcrt_ray_source_desc* ctxRaySource(const mcrt_ctx* ctx) { return ctx->ray_source.kind != MCRT_RAY_SOURCE_NONE ? &ctx->ray_source : nullptr; }
+void ctxSetRaySource(mcrt_ctx* ctx, const mcrt_ray_source_desc& source, void* owned_first, void* owned_second) {
+    (void)hipSetDevice(ctx->device);
+    ctx->ray_source = source;
+    ctx->ray_source_owned[0].release();
+    ctx->ray_source_owned[1].release();
+    ctx->ray_source_owned[0].p = owned_first;
+    ctx->ray_source_owned[1].p = owned_second;
+}
 }  // namespace mcrt

@@ -48,4 +48,9 @@ void ctxSampleTargetsEnd(mcrt_ctx* ctx);
 // camera-ray passes run their own ray kernels and the render calls are not guarded.
 const mcrt_lens_desc* ctxLens(const mcrt_ctx* ctx);
 void ctxSetLens(mcrt_ctx* ctx, const mcrt_lens_desc& lens);  // model MCRT_LENS_NONE: none
+// The context's ray source ("Ray sources" in mcrt.h; mcrt_ray_source_host.hip validates and writes it): nullptr while none is set.
+// ctxSetRaySource frees the device copies the context owned and adopts owned_first / owned_second (hipMalloc'ed, or nullptr: the
+// arrays are the caller's); kind MCRT_RAY_SOURCE_NONE: none.
+const mcrt_ray_source_desc* ctxRaySource(const mcrt_ctx* ctx);
+void ctxSetRaySource(mcrt_ctx* ctx, const mcrt_ray_source_desc& source, void* owned_first, void* owned_second);
 }  // namespace mcrt

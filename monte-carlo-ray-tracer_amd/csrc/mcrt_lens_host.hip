@@ -28,6 +28,9 @@ extern "C" int mcrt_set_lens(mcrt_ctx* ctx, const mcrt_lens_desc* lens) {
         ctxSetLens(ctx, mcrt_lens_desc{});
         return MCRT_OK;
     }
+    if (ctxRaySource(ctx))
+        return ctxFail(ctx, MCRT_ERR_INVALID, std::string(what) + ": a ray source is set (mcrt_set_ray_source) - a lens and a ray source exclude each other; "
+                                                                 "mcrt_set_ray_source(ctx, NULL) takes it off");
     LensSettings s;
     const char* why = nullptr;
     if (int rc = lensSettings(*lens, s, &why)) return ctxFail(ctx, rc, std::string(what) + ": " + why);
@@ -56,8 +59,10 @@ extern "C" int mcrt_camera_rays_device(mcrt_ctx* ctx, const mcrt_camera_desc* ca
     if (pixels) {  // one chunk: the shard's packed pixels
         const AovChunk c = chunkAt(*cam, global_seed, spp, 0, pixels, pixels);
         const mcrt_lens_desc* lens = ctxLens(ctx);
-        MCRT_HIP_TRY(ctx, (hipError_t)(lens ? LensPixels(*lens).rays(cp.stream, c, cp.scene.sh.scene_ior, cp.sobol_tab, rays)
-                                            : FramePixels{}.rays(cp.stream, c, cp.scene.sh.scene_ior, cp.sobol_tab, rays)));
+        const mcrt_ray_source_desc* source = ctxRaySource(ctx);
+        MCRT_HIP_TRY(ctx, (hipError_t)(lens     ? LensPixels(*lens).rays(cp.stream, c, cp.scene.sh.scene_ior, cp.sobol_tab, rays)
+                                       : source ? SourcePixels(*source).rays(cp.stream, c, cp.scene.sh.scene_ior, cp.sobol_tab, rays)
+                                                : FramePixels{}.rays(cp.stream, c, cp.scene.sh.scene_ior, cp.sobol_tab, rays)));
     }
     if (int rc = timer.end(cp.stream)) return rc;
     if (int rc = timer.finish(stats, pixels ? 1 : 0)) return rc;

@@ -114,6 +114,8 @@ int runLivePaths(mcrt_ctx* ctx, const char* what, const CameraPass& cp, PassTime
                  Step step, Resolve resolve) {
     if (const mcrt_lens_desc* lens = ctxLens(ctx))
         return runLivePathsOf(LensPixels(*lens), ctx, what, cp, timer, cam, global_seed, plan, camera_rays, stats, sc, max_depth, log, log_key, begin, rays_of, step, resolve);
+    if (const mcrt_ray_source_desc* source = ctxRaySource(ctx))
+        return runLivePathsOf(SourcePixels(*source), ctx, what, cp, timer, cam, global_seed, plan, camera_rays, stats, sc, max_depth, log, log_key, begin, rays_of, step, resolve);
     return runLivePathsOf(FramePixels{}, ctx, what, cp, timer, cam, global_seed, plan, camera_rays, stats, sc, max_depth, log, log_key, begin, rays_of, step, resolve);
 }
 

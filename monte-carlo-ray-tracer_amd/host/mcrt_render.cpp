@@ -85,6 +85,12 @@
 // unchanged. --lens-fov DEG[,DEG]: fov_x and fov_y in degrees (equirectangular: default 360,180; fisheye: the full angle, default 180).
 // --lens-width W: the orthographic frame's width in world units. Not with --photon, --adaptive, --converge, --stats, --robust,
 // --denoise-variance, --denoise-dual or --devices: those make their camera rays inside a render kernel.
+// --gather turns the run into a surface gather (mcrt_set_ray_source, include/mcrt.h "Ray sources"): the first-hit AOV pass of the camera
+// is rendered first, its `position` and `normal` frames (--gather-normal shading: `shading_normal`) become a SURFACE ray source, and
+// the frame - the light groups with everything in one plane, as under --lens - and --matte, --occlusion, --lighting, --light-groups
+// and --path-classes then trace cosine-weighted rays from those surface points: the frame times pi is the irradiance that arrives at
+// what each pixel sees, --light-groups gives it per lamp. --aov still writes the camera's own AOV frame. Not with --lens, nor with
+// what --lens excludes.
 // --devices renders the frame on several GPUs from this one process (mcrt_render_multi: one host thread per GPU).
 #include <cstdio>
 #include <cstdlib>
@@ -118,6 +124,9 @@ int main(int argc, char** argv) {
     uint32_t light_groups_depth = 0, path_classes_depth = 0;
     std::string lens_name;
     mcrt_lens_desc lens{};
+    bool gather = false;
+    std::string gather_normal = "normal";
+    std::vector<double> gather_position, gather_normals;
     mcrt_occlusion_params oparams{};
     bool compare_exr = false;
     mcrt_matte_params mparams{};
@@ -179,6 +188,8 @@ int main(int argc, char** argv) {
         else if (k == "--light-groups-by" && i + 1 < argc) light_groups_by = argv[++i];
         else if (k == "--light-groups-depth" && i + 1 < argc) light_groups_depth = (uint32_t)std::strtoul(argv[++i], nullptr, 10);
         else if (k == "--path-classes" && i + 1 < argc) path_classes = argv[++i];
+        else if (k == "--gather") gather = true;
+        else if (k == "--gather-normal" && i + 1 < argc) gather_normal = argv[++i];
         else if (k == "--lens" && i + 1 < argc) lens_name = argv[++i];
         else if (k == "--lens-fov" && i + 1 < argc) {
             char* rest = nullptr;
@@ -268,6 +279,19 @@ int main(int argc, char** argv) {
             return 2;
         }
     }
+    if (gather) {
+        if (gather_normal != "normal" && gather_normal != "shading") {
+            std::fprintf(stderr, "--gather-normal: normal or shading, not %s\n", gather_normal.c_str());
+            return 2;
+        }
+        if (!lens_name.empty() || photon || adaptive || converge || !pstats.empty() || !robust.empty() || !dvar.empty() || !ddual.empty() || devices.size() > 1) {
+            std::fprintf(stderr, "--gather is the path tracer on one device (not with --photon or --devices), and not with --lens, --adaptive, --converge, --stats, --robust, --denoise-variance or --denoise-dual\n");
+            return 2;
+        }
+    } else if (gather_normal != "normal") {
+        std::fprintf(stderr, "--gather-normal needs --gather\n");
+        return 2;
+    }
     if (lens_name.empty() && (lens.fov_x != 0.0 || lens.fov_y != 0.0 || lens.width_world != 0.0)) {
         std::fprintf(stderr, "--lens-fov and --lens-width need --lens\n");
         return 2;
@@ -291,6 +315,18 @@ int main(int argc, char** argv) {
         if (rc != MCRT_OK) std::fprintf(stderr, "device %d: %s\n", devices[d], mcrt_last_error(ctxs[d]));
     }
     mcrt_ctx* ctx = ctxs[0];
+    auto set_gather = [&]() {  // (pixels with no hit hold a zero normal: the kernel's fallback, +z from the origin)
+        mcrt_ray_source_desc d{};
+        d.kind = MCRT_RAY_SOURCE_SURFACE;
+        d.pixels = (uint64_t)cam.width * cam.height;
+        d.first = gather_position.data();
+        d.second = gather_normals.data();
+        d.offset = 1e-9;
+        uint64_t sanitised = 0;
+        const int r = mcrt_set_ray_source_host(ctx, &d, &sanitised);
+        if (r == MCRT_OK) std::printf("{\"gather\":\"%s\",\"pixels\":%llu,\"without_surface\":%llu}\n", gather_normal.c_str(), (unsigned long long)d.pixels, (unsigned long long)sanitised);
+        return r;
+    };
     if (rc == MCRT_OK && lens.model != MCRT_LENS_NONE) rc = mcrt_set_lens(ctx, &lens);
     if (compare_exr && rc == MCRT_OK) {  // the reference's channels, widened on the device into the [H][W][3] frame
         mcrt_exr_file* ref = nullptr;
@@ -382,7 +418,21 @@ int main(int argc, char** argv) {
             rc = mcrt_render_highlights(ctx, &cam, seed, mode, rgb.data(), &h, &b, &st);
         else
             rc = mcrt_render_pixel_stats(ctx, &cam, seed, mode, rgb.data(), &b, &st);
-    } else if (rc == MCRT_OK && lens.model != MCRT_LENS_NONE) {  // the beauty frame under the lens: everything in plane 0 of the light groups
+    } else if (rc == MCRT_OK && (lens.model != MCRT_LENS_NONE || gather)) {  // the frame under the lens or the source: everything in plane 0 of the light groups
+        if (gather) {  // the camera's first hits become the surface points the rays start from
+            const size_t px = (size_t)cam.width * cam.height;
+            gather_position.assign(px * 3, 0.0);
+            gather_normals.assign(px * 3, 0.0);
+            mcrt_aov_buffers gb{};
+            gb.position = gather_position.data();
+            (gather_normal == "shading" ? gb.shading_normal : gb.normal) = gather_normals.data();
+            rc = mcrt_render_aov(ctx, &cam, seed, &gb, nullptr);
+            if (rc == MCRT_OK) rc = set_gather();
+            if (rc != MCRT_OK) {
+                std::fprintf(stderr, "mcrt error %d: %s\n", rc, mcrt_last_error(ctx));
+                return 1;
+            }
+        }
         mcrt_light_group_params one{};
         one.num_groups = 1;
         one.flags = MCRT_LIGHT_GROUPS_SKY_PLANE;
@@ -570,7 +620,9 @@ int main(int argc, char** argv) {
         std::vector<uint32_t> surface(px), material(px);
         const mcrt_aov_buffers b{depth.data(), position.data(), normal.data(), shading_normal.data(), albedo.data(), coverage.data(), surface.data(), material.data()};
         mcrt_stats ast;
+        if (gather) (void)mcrt_set_ray_source(ctx, nullptr);  // (the camera's own AOV frame)
         rc = mcrt_render_aov(ctx, &cam, seed, &b, &ast);
+        if (gather && rc == MCRT_OK) rc = set_gather();
         auto dump = [&](const std::string& path, const void* data, size_t bytes) {
             FILE* o = std::fopen(path.c_str(), "wb");
             const bool ok = o && std::fwrite(data, 1, bytes, o) == bytes;
