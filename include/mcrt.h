@@ -1551,6 +1551,86 @@ int mcrt_set_ray_source_host(mcrt_ctx* ctx, const mcrt_ray_source_desc* source /
                              uint64_t* sanitised /* may be NULL */);
 int mcrt_get_ray_source(mcrt_ctx* ctx, mcrt_ray_source_desc* out);
 
+/* ------------------------------------------------------------------------------------------
+ * Light probes: spherical-harmonic radiance at points, split per lamp. A probe is the mean over a pixel's samples of the radiance
+ * along the sample's first ray TIMES a function of that ray's direction - here the first (L+1)^2 real spherical harmonics, L <= 2,
+ * from which the irradiance for any normal follows in closed form. Split by light group it is relightable: dimming a lamp is a
+ * weighted sum of coefficient sets. The walk is mcrt_render_light_groups' own - the same state, the same begin / ray / step
+ * launches, the same R_p per sample and plane ("Light groups" above) -; what differs is the resolve, a projection in place of the
+ * plain mean, and, with `positions`, where the first ray comes from.
+ * As under a ray source the camera gives the frame's shape and the sampler keys: width * height is the number of probes,
+ * sqrtspp^2 the rays per probe (spp), shard_* is honoured, `pixels` below is the shard's packed pixels (owned rows * width),
+ * packed pixel q is local row q / width, column q % width.
+ * The first rays. positions == NULL: whatever the context holds - the camera, a lens (mcrt_set_lens) or a ray source
+ * (mcrt_set_ray_source). With positions, DEVICE [pixels][3] doubles, the probe rays: sample i of pixel (x, y), packed pixel q, in
+ * FP64, uncontracted, consuming the sampler as MCRT_RAY_SOURCE_SURFACE does:
+ *     sampler at initiate(global_seed, y * width + x), setIndex(i)
+ *     u0 = get(kDimPixel),  u1 = get(kDimPixel + 1)
+ *     z  = 1.0 - (u0 + u0)
+ *     rr = 1.0 - z * z;  r = sqrt(rr > 0.0 ? rr : 0.0)
+ *     (s, c) = refSinCos(u1 * kTwoPi)             (the restated glibc routine)
+ *     direction = (r * c, r * s, z)               (uniform over the sphere: pdf 1 / (4 pi))
+ *     start = positions[q], or (0, 0, 0) unless its three words are finite
+ *     ray = makeRay(start, direction, scene_ior)
+ * mcrt_probe_rays_device writes exactly these rays into d_start and d_direction, [spp][pixels][3] doubles each, sample-major
+ * (record i * pixels + q), as mcrt_camera_rays_device does for a lens; fed back as a MCRT_RAY_SOURCE_RAYS source they give the
+ * bytes of the call with positions. A lens or a source on the context is refused by both (positions would be ambiguous).
+ * The projection. d = the direction of the sample's first ray as it was handed to the closest-hit search: the bits in the record,
+ * whatever made them. w = weight[i * pixels + q] when weight, DEVICE [spp][pixels] doubles, is given: for callers whose rays are
+ * not uniformly distributed (1 / pdf, up to a constant). The un-normalised basis:
+ *     b0 = 1
+ *     b1 = d.y            b2 = d.z                      b3 = d.x
+ *     b4 = d.x * d.y      b5 = d.y * d.z
+ *     b6 = 3.0 * (d.z * d.z) - 1.0
+ *     b7 = d.x * d.z      b8 = (d.x * d.x) - (d.y * d.y)
+ * Every word of the output - plane p, coefficient k, pixel, channel c - is (((0.0 + t(0)) + t(1)) + ...) / (double)spp, ascending
+ * i, one FP64 accumulator per word, with t(i) = R_p(i).c * b_k without a weight and t(i) = (R_p(i).c * w) * b_k with one (k = 0
+ * may skip the multiplication by 1: the bits are the same). Nothing is clamped: coefficients are signed.
+ * Normalisation is the caller's, not the kernel's. With uniform directions the mean of L * b_k estimates (1 / 4 pi) * integral of
+ * L b_k, so the coefficient of the real spherical harmonic Y_k = N_k b_k is L_k = 4 pi N_k * (output word), with the constants
+ * MCRT_PROBE_SH_N* below; the irradiance at normal n is then sum_k A_l(k) L_k Y_k(n), A_0 = pi, A_1 = 2 pi / 3, A_2 = pi / 4
+ * (the binding's probe_sh and probe_irradiance).
+ * Parameters: groups as in mcrt_render_light_groups (all zero: one group and the sky); order L = 0, 1, 2 gives K = (L + 1)^2
+ * coefficients (mcrt_probe_coefficients); flags and reserved 0.
+ * Output: d_coefficients, [P][K][rows][width][3] doubles, P = mcrt_light_group_planes(&groups), the rows this shard owns packed.
+ * What holds, bit for bit:
+ *   - coefficient 0 of every plane, with no weight, is the plane mcrt_render_light_groups returns under the same lens or source;
+ *   - a weight of all 1.0 changes nothing, a weight of all 2.0 doubles every word;
+ *   - positions gives the bytes of the same call with positions == NULL under a RAYS source fed with mcrt_probe_rays_device's arrays;
+ *   - a coefficient does not depend on chunking (MCRT_AOV_CHUNK_RAYS), sharding, order (the nine of order 2 begin with the four
+ *     of order 1) or how the OTHER emitters are grouped.
+ * Refused with MCRT_ERR_INVALID and a message: params or the output NULL, order > 2, flags or reserved non-zero, everything the
+ * light groups refuse, positions together with a lens or a ray source on the context (the message names mcrt_set_lens /
+ * mcrt_set_ray_source).
+ * stats: as the light groups'.
+ * Not done: probes of the path classes, order 3 and up, non-uniform built-in direction sets (a caller's own through a RAYS source
+ * and weight), any normalisation or irradiance on the device. */
+#define MCRT_PROBE_ORDER_MAX 2u
+#define MCRT_PROBE_SH_N0 0.28209479177387814 /* 1/2 sqrt(1/pi):  k = 0 */
+#define MCRT_PROBE_SH_N1 0.4886025119029199  /* 1/2 sqrt(3/pi):  k = 1, 2, 3 */
+#define MCRT_PROBE_SH_N4 1.0925484305920792  /* 1/2 sqrt(15/pi): k = 4, 5, 7 */
+#define MCRT_PROBE_SH_N6 0.31539156525252005 /* 1/4 sqrt(5/pi):  k = 6 */
+#define MCRT_PROBE_SH_N8 0.5462742152960396  /* 1/4 sqrt(15/pi): k = 8 */
+typedef struct mcrt_probe_params {
+    mcrt_light_group_params groups; /* as in mcrt_render_light_groups */
+    uint32_t      order;            /* L = 0, 1, 2: K = (L + 1)^2 coefficients */
+    uint32_t      flags;            /* 0 */
+    const double* positions;        /* DEVICE [pixels][3] or NULL: the context's camera, lens or ray source */
+    const double* weight;           /* DEVICE [spp][pixels] or NULL */
+    uint64_t      reserved[2];      /* 0 */
+} mcrt_probe_params;                /* 64 bytes */
+/* K of an order; 0 when it is out of range. */
+uint32_t mcrt_probe_coefficients(uint32_t order);
+int mcrt_render_probes_device(mcrt_ctx* ctx, const mcrt_camera_desc* cam, uint32_t global_seed, const mcrt_probe_params* params,
+                              double* d_coefficients, mcrt_stats* stats /* may be NULL */);
+/* Same with HOST pointers: positions [pixels][3] and weight [spp][pixels] of the shard's packed pixels, coefficients P * K FULL frames,
+ * [P][K][height][width][3]: rows this shard does not own are left untouched. */
+int mcrt_render_probes(mcrt_ctx* ctx, const mcrt_camera_desc* cam, uint32_t global_seed, const mcrt_probe_params* params,
+                       double* coefficients, mcrt_stats* stats /* may be NULL */);
+/* The probe rays of d_positions (DEVICE [pixels][3]) into d_start and d_direction, DEVICE [spp][pixels][3] each. */
+int mcrt_probe_rays_device(mcrt_ctx* ctx, const mcrt_camera_desc* cam, uint32_t global_seed, const double* d_positions, double* d_start,
+                           double* d_direction, mcrt_stats* stats /* may be NULL */);
+
 /* Photon emission pass on the GPU. Replaces the thread fan-out of
  * PhotonMapper::PhotonMapper (integrator/photon-mapper/photon-mapper.cpp:80-115: per emission
  * Sampler::initiate(light), setIndex(offset+i), light point + cosine direction, emitPhoton :225-277) for

@@ -308,6 +308,50 @@ RAY_SOURCE_NAMES = {RAY_SOURCE_NONE: "none", RAY_SOURCE_RAYS: "rays", RAY_SOURCE
 RAY_SOURCE_DEFAULT_OFFSET = 1e-9  # kEpsilon of csrc/mcrt_math.hpp
 
 
+class ProbeParams(C.Structure):
+    """mcrt_probe_params: groups (a LightGroupParams, as in render_light_groups), order (L = 0, 1, 2: K = (L + 1)^2 coefficients), flags
+    (0), positions (pointer to [pixels][3] doubles or NULL: the context's camera, lens or ray source), weight (pointer to [spp][pixels]
+    doubles or NULL), reserved (0). include/mcrt.h "Light probes" defines the call operation by operation."""
+    _fields_ = [("groups", LightGroupParams), ("order", C.c_uint32), ("flags", C.c_uint32), ("positions", C.c_void_p), ("weight", C.c_void_p),
+                ("reserved", C.c_uint64 * 2)]
+
+
+PROBE_ORDER_MAX = 2
+# MCRT_PROBE_SH_N*: Y_k = PROBE_SH_NORM[k] * b_k, the real spherical harmonics over the un-normalised basis the probe calls project on
+PROBE_SH_NORM = np.array([0.5 * math.sqrt(1.0 / math.pi)] + [0.5 * math.sqrt(3.0 / math.pi)] * 3 +
+                         [0.5 * math.sqrt(15.0 / math.pi), 0.5 * math.sqrt(15.0 / math.pi), 0.25 * math.sqrt(5.0 / math.pi), 0.5 * math.sqrt(15.0 / math.pi),
+                          0.25 * math.sqrt(15.0 / math.pi)])
+PROBE_SH_BAND = np.array([0, 1, 1, 1, 2, 2, 2, 2, 2])                      # l of coefficient k
+PROBE_IRRADIANCE_BAND = np.array([math.pi, 2.0 * math.pi / 3.0, math.pi / 4.0])  # A_l: the clamped cosine's zonal factors
+
+
+def probe_basis(directions):
+    """The un-normalised basis b_0 .. b_8 of unit directions [..., 3] -> [9, ...] (include/mcrt.h "Light probes")."""
+    d = np.asarray(directions, dtype=np.float64)
+    x, y, z = d[..., 0], d[..., 1], d[..., 2]
+    return np.stack([np.ones_like(x), y, z, x, x * y, y * z, 3.0 * (z * z) - 1.0, x * z, (x * x) - (y * y)])
+
+
+def probe_sh(coefficients):
+    """The raw coefficients of render_probes / bake_probes, [..., K, H, W, 3] (K = 1, 4 or 9), as coefficients L_lm of the real
+    spherical harmonics: times 4 pi N_k - the mean over uniform directions estimates the integral over the sphere divided by 4 pi."""
+    c = np.asarray(coefficients, dtype=np.float64)
+    k = c.shape[-4]
+    if k not in (1, 4, 9):
+        raise ValueError("probe_sh: [..., K, H, W, 3] with K = 1, 4 or 9, not %r" % (c.shape,))
+    return c * (4.0 * math.pi * PROBE_SH_NORM[:k])[:, None, None, None]
+
+
+def probe_irradiance(sh, normals):
+    """The irradiance at unit normals [H, W, 3] from probe_sh's coefficients [..., K, H, W, 3] -> [..., H, W, 3]:
+    sum_k A_l(k) L_k Y_k(n) with A = pi, 2 pi / 3, pi / 4 (bands past the order given are taken as zero)."""
+    sh = np.asarray(sh, dtype=np.float64)
+    k = sh.shape[-4]
+    y = probe_basis(normals)[:k] * PROBE_SH_NORM[:k, None, None]            # [K, H, W]
+    factor = PROBE_IRRADIANCE_BAND[PROBE_SH_BAND[:k]][:, None, None] * y    # [K, H, W]
+    return (sh * factor[..., None]).sum(axis=-4)
+
+
 class DenoiseParams(C.Structure):
     """mcrt_denoise_params: a zero field = the default (include/mcrt.h)."""
     _fields_ = [("iterations", C.c_uint32), ("normal_power_log2", C.c_uint32), ("sigma_color", C.c_double), ("sigma_plane", C.c_double),
@@ -997,6 +1041,12 @@ def lib():
         L.mcrt_set_ray_source.argtypes = [vp, C.POINTER(RaySourceDesc)]
         L.mcrt_set_ray_source_host.argtypes = [vp, C.POINTER(RaySourceDesc), C.POINTER(C.c_uint64)]
         L.mcrt_get_ray_source.argtypes = [vp, C.POINTER(RaySourceDesc)]
+    if hasattr(L, "mcrt_render_probes"):  # (likewise)
+        L.mcrt_probe_coefficients.argtypes = [C.c_uint32]
+        L.mcrt_probe_coefficients.restype = C.c_uint32
+        L.mcrt_render_probes.argtypes = [vp, C.POINTER(CameraDesc), C.c_uint32, C.POINTER(ProbeParams), vp, C.POINTER(Stats)]
+        L.mcrt_render_probes_device.argtypes = L.mcrt_render_probes.argtypes
+        L.mcrt_probe_rays_device.argtypes = [vp, C.POINTER(CameraDesc), C.c_uint32, vp, vp, vp, C.POINTER(Stats)]
     if hasattr(L, "mcrt_frame_compare"):  # (likewise)
         L.mcrt_frame_compare.argtypes = [vp, C.c_uint32, C.c_uint32, vp, vp, vp, C.POINTER(CompareParams), C.POINTER(CompareMaps), C.POINTER(CompareResult), C.POINTER(Stats)]
         L.mcrt_frame_compare_device.argtypes = L.mcrt_frame_compare.argtypes
@@ -1733,6 +1783,99 @@ class Context:
             if before.kind != RAY_SOURCE_NONE:
                 self._check(self._lib.mcrt_set_ray_source(self._h, C.byref(before)), "mcrt_set_ray_source")
                 self._ray_source_arrays = before_arrays
+
+    def _probe_params(self, order, groups, sky_plane, max_depth, num_groups, positions=None, weight=None):
+        """-> (ProbeParams, what it points into)."""
+        lg, keep = self._light_group_params(groups, sky_plane, max_depth, num_groups)
+        return ProbeParams(lg, int(order), 0, positions, weight), keep
+
+    def render_probes(self, cam, global_seed, positions=None, order=2, weight=None, groups=None, sky_plane=None, max_depth=0, num_groups=None, stats=None, out=None):
+        """mcrt_render_probes: light probes -> [P,K,H,W,3], K = (order + 1)^2: per plane of the light groups (groups, sky_plane,
+        max_depth, num_groups as in render_light_groups) the mean over a pixel's samples of the radiance along the sample's first ray
+        times the un-normalised spherical-harmonic basis of that ray's direction (include/mcrt.h "Light probes"; probe_sh normalises,
+        probe_irradiance evaluates). cam gives the frame's shape - width * height probes, sqrtspp^2 rays each - and the sampler keys.
+        positions: float64 [owned rows, W, 3] (or [pixels, 3]) - the rays leave these points uniformly over the sphere, and a lens or a
+        ray source on the context is refused -, or None: the first rays are the context's (camera, lens, ray source). weight: float64
+        [spp, owned rows, W] (or [spp, pixels]), 1 / pdf for first rays that are not uniformly distributed, or None. numpy arrays
+        (torch tensors are copied to the host). out: an array to write into instead of fresh zeros - the call only writes the rows
+        cam's shard owns. stats: a dict that receives mcrt_stats."""
+        self._sync_env()
+        pixels = len(shard_rows(cam)) * cam.width
+        spp = cam.sqrtspp * cam.sqrtspp
+
+        def host(a, size, what):
+            if a is None:
+                return None
+            a = np.ascontiguousarray(a.detach().cpu().numpy() if hasattr(a, "data_ptr") else a, dtype=np.float64)
+            if a.size != size:
+                raise ValueError("render_probes: %s holds %d values, the camera's shard takes %d" % (what, a.size, size))
+            return a
+        positions, weight = host(positions, pixels * 3, "positions"), host(weight, pixels * spp, "weight")
+        par, keep = self._probe_params(order, groups, sky_plane, max_depth, num_groups, None if positions is None else positions.ctypes.data,
+                                       None if weight is None else weight.ctypes.data)
+        planes = int(self._lib.mcrt_light_group_planes(C.byref(par.groups)))
+        k = int(self._lib.mcrt_probe_coefficients(int(order)))
+        shape = (max(planes, 1), max(k, 1), cam.height, cam.width, 3)  # (out of range: the call below says what is)
+        a = out if out is not None else np.zeros(shape)
+        assert a.dtype == np.float64 and a.shape == shape and a.flags["C_CONTIGUOUS"]
+        st = Stats()
+        self._check(self._lib.mcrt_render_probes(self._h, C.byref(cam), int(global_seed), C.byref(par), a.ctypes.data, C.byref(st)), "mcrt_render_probes")
+        if stats is not None:
+            stats.update(st.as_dict())
+        return a
+
+    def render_probes_device(self, cam, global_seed, pointer, positions=None, order=2, weight=None, groups=None, sky_plane=None, max_depth=0, num_groups=None):
+        """mcrt_render_probes_device: pointer = raw device pointer to [P][K][owned rows][W][3] doubles; positions, weight: raw device
+        pointers or None. Synchronous; returns the stats dict."""
+        self._sync_env()
+        par, keep = self._probe_params(order, groups, sky_plane, max_depth, num_groups, int(positions) if positions else None, int(weight) if weight else None)
+        st = Stats()
+        self._check(self._lib.mcrt_render_probes_device(self._h, C.byref(cam), int(global_seed), C.byref(par), int(pointer) if pointer else None, C.byref(st)),
+                    "mcrt_render_probes_device")
+        return st.as_dict()
+
+    def probe_rays_device(self, cam, global_seed, d_positions, d_start, d_direction):
+        """mcrt_probe_rays_device: raw device pointers - positions [owned rows][W][3], start and direction [spp][owned rows][W][3]
+        doubles each. Synchronous; returns the stats dict."""
+        self._sync_env()
+        st = Stats()
+        self._check(self._lib.mcrt_probe_rays_device(self._h, C.byref(cam), int(global_seed), int(d_positions) if d_positions else None,
+                                                     int(d_start) if d_start else None, int(d_direction) if d_direction else None, C.byref(st)), "mcrt_probe_rays_device")
+        return st.as_dict()
+
+    def probe_rays(self, cam, global_seed, positions, stats=None):
+        """The first rays render_probes traces from positions (float64 [owned rows, W, 3] or [pixels, 3]) -> (start, direction), each
+        [spp, owned rows, W, 3]: sample-major, what set_ray_source("rays", ...) takes. The arrays pass through torch tensors on the
+        context's device."""
+        import torch
+        rows = len(shard_rows(cam))
+        spp = cam.sqrtspp * cam.sqrtspp
+        device = "cuda:%d" % self._device_id
+        p = torch.as_tensor(np.ascontiguousarray(positions, dtype=np.float64).reshape(-1, 3)).to(device)
+        if p.shape[0] != rows * cam.width:
+            raise ValueError("probe_rays: positions holds %d points, the camera's shard takes %d" % (p.shape[0], rows * cam.width))
+        start = torch.zeros((spp, rows, cam.width, 3), dtype=torch.float64, device=device)
+        direction = torch.zeros_like(start)
+        torch.cuda.synchronize(device)
+        st = self.probe_rays_device(cam, global_seed, p.data_ptr(), start.data_ptr(), direction.data_ptr())
+        if stats is not None:
+            stats.update(st)
+        return start.cpu().numpy(), direction.cpu().numpy()
+
+    def bake_probes(self, points, rays=1024, order=2, global_seed=0, groups=None, sky_plane=None, max_depth=0, num_groups=None, stats=None):
+        """Light probes at points [N, 3] -> dict: "coefficients" [P, K, N, 3], the raw means of render_probes over
+        ceil(sqrt(rays))^2 uniform directions per point, and "sh" [P, K, N, 3], probe_sh of them: per plane of the light groups
+        (groups, sky_plane, max_depth, num_groups as in render_light_groups) the radiance arriving at each point as coefficients of the
+        real spherical harmonics; probe_irradiance(sh[..., None, :, :], normals[None]) is the irradiance for any normal. The camera is
+        N x 1 and gives nothing but the sampler keys. A lens or a ray source on the context is refused."""
+        points = np.ascontiguousarray(points, dtype=np.float64)
+        if points.ndim != 2 or points.shape[1] != 3 or points.shape[0] == 0:
+            raise ValueError("bake_probes: points of shape [N, 3], not %r" % (points.shape,))
+        cam = CameraDesc()
+        cam.width, cam.height, cam.sqrtspp = points.shape[0], 1, max(1, math.isqrt(max(int(rays), 1) - 1) + 1)
+        raw = self.render_probes(cam, global_seed, positions=points, order=order, groups=groups, sky_plane=sky_plane, max_depth=max_depth, num_groups=num_groups,
+                                 stats=stats)
+        return {"coefficients": raw[:, :, 0], "sh": probe_sh(raw)[:, :, 0]}
 
     def render_matte(self, cam, global_seed, key="material", ranks=MATTE_DEFAULT_RANKS, names=None, surface_key=None, aov=None, out=None, stats=None,
                      num_keys=None):

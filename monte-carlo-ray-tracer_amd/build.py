@@ -63,10 +63,11 @@ def sources():
 
 # the translation units that hold kernels of the render path: the tolerance library has its own objects of these
 KERNEL_TUS = ("mcrt_hip.hip", "mcrt_hip_lean.hip")
-# (mcrt_lens_host.hip, mcrt_ray_source_host.hip: the calls of the camera models and the ray sources, host code only - their rays are
-# branches of libmcrt_aov.so's aovRayKernel)
+# (mcrt_lens_host.hip, mcrt_ray_source_host.hip, mcrt_probes_host.hip: the calls of the camera models, the ray sources and the light
+# probes, host code only - their rays are branches of libmcrt_aov.so's aovRayKernel, the probes' projection one of
+# libmcrt_light_groups.so's lightGroupsResolveKernel)
 CORE_TUS = ["mcrt_hip.hip", "mcrt_hip_lean.hip", "mcrt_octree_gpu.hip", "mcrt_sah_gpu.hip", "mcrt_output.hip", "mcrt_multi.hip", "mcrt_image.cpp",
-            "mcrt_octree.cpp", "mcrt_bvh.cpp", "mcrt_lens_host.hip", "mcrt_ray_source_host.hip"]
+            "mcrt_octree.cpp", "mcrt_bvh.cpp", "mcrt_lens_host.hip", "mcrt_ray_source_host.hip", "mcrt_probes_host.hip"]
 TUS = CORE_TUS + [stem + "_host.hip" for stem in PASSES]
 OBJ = os.path.join(CSRC, "_obj")
 

@@ -17,6 +17,7 @@
 #include "mcrt_aov_launch.hpp"
 #include "mcrt_lens.hpp"
 #include "mcrt_lens_launch.hpp"
+#include "mcrt_probes.hpp"
 #include "mcrt_ray_source.hpp"
 
 using namespace mcrt;
@@ -70,9 +71,22 @@ __device__ __forceinline__ void sourceRaysOf(const AovChunk& c, const RayHead& h
     }
 }
 
+// The grid-stride loop of a probe call's rays (mcrt_probes.hpp): sourceRaysOf's shape - 24 bytes per pixel, the position, in the head's
+// first word, and a direction uniform over the sphere.
+__device__ __forceinline__ void probeRaysOf(const AovChunk& c, const RayHead& h, double scene_ior, SobolTab tab, const AovRays& rays) {
+    const double* positions = h.w[0].p;
+    const uint64_t n = (uint64_t)c.pixels * c.spp;
+    for (uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; r < n; r += (uint64_t)gridDim.x * blockDim.x) {
+        const Ray ray = probeRay<true>(c, positions, scene_ior, (uint32_t)(r % c.pixels), (uint32_t)(r / c.pixels), tab);
+        aovStore3(rays.start, r, ray.start);
+        aovStore3(rays.direction, r, ray.direction);
+    }
+}
+
 // h.model MCRT_LENS_NONE: the camera's own rays, the loop this kernel has always run (the sine / cosine table read from memory, not
-// staged). Any other model: the table staged in LDS as lightingRayKernel does, then that model's loop - the two internal models past
-// MCRT_LENS_FISHEYE are the ray source's loops (launchSourceRays), which read nothing of the camera but the pixels' names.
+// staged). Any other model: the table staged in LDS as lightingRayKernel does, then that model's loop - the internal models past
+// MCRT_LENS_FISHEYE are the ray source's two loops (launchSourceRays) and the probe rays' (launchProbeRays), which read nothing of the
+// camera but the pixels' names.
 // Four waves a SIMD, what the kernel had before it learned the models (98 VGPRs then): left alone the compiler takes 140 VGPRs, three
 // waves; held to 128 it still spills nothing (profiles/NOTES_lens.md).
 __global__ void __launch_bounds__(kAovBlock) __attribute__((amdgpu_waves_per_eu(4, 4))) aovRayKernel(AovChunk c, RayHead h, double scene_ior, const uint32_t* sobol_tab, AovRays rays) {
@@ -119,6 +133,7 @@ __global__ void __launch_bounds__(kAovBlock) __attribute__((amdgpu_waves_per_eu(
         // compiler spills three constants of the thin-lens PERSPECTIVE loop, the kernel's register maximum - profiles/NOTES_ray_source.md)
         case kLensModelSourceRays: sourceRaysOf<MCRT_RAY_SOURCE_RAYS>(c, h, scene_ior, (SobolTab)ltab, rays); break;
         case kLensModelSourceSurface: sourceRaysOf<MCRT_RAY_SOURCE_SURFACE>(c, h, scene_ior, (SobolTab)ltab, rays); break;
+        case kLensModelProbe: probeRaysOf(c, h, scene_ior, (SobolTab)ltab, rays); break;
         default: lensRaysOf<MCRT_LENS_FISHEYE>(c, lens, scene_ior, (SobolTab)ltab, rays); break;
     }
 }
@@ -165,6 +180,14 @@ int launchSourceRays(void* stream, const AovChunk& c, const RaySource& source, d
     h.w[0].p = source.a;
     h.w[1].p = source.b;
     h.w[2].d = source.offset;
+    return launchRays(stream, c, h, scene_ior, sobol_tab, rays);
+}
+// The chunk's pixels must lie inside positions' `pixels` records.
+int launchProbeRays(void* stream, const AovChunk& c, const double* positions, uint64_t pixels, double scene_ior, const uint32_t* sobol_tab, const AovRays& rays) {
+    if (!positions || pixels > 0xFFFFFFFFull || c.first_pixel + c.pixels > pixels) return (int)hipErrorInvalidValue;
+    RayHead h{};
+    h.model = kLensModelProbe;
+    h.w[0].p = positions;
     return launchRays(stream, c, h, scene_ior, sobol_tab, rays);
 }
 int launchAovRays(void* stream, const AovChunk& c, double scene_ior, const uint32_t* sobol_tab, const AovRays& rays) {

@@ -108,6 +108,19 @@ struct SourcePixels {
     }
 };
 
+// The frame's order of a probe call with positions ("Light probes" in mcrt.h): the same chunks, the rays from the probe loop of
+// aovRayKernel (launchProbeRays, csrc/mcrt_aov.hip). The call itself names it (mcrt_probes_host.hip): nothing of it is on the context.
+struct ProbePixels {
+    const double* positions;  // DEVICE [pixels][3]
+    uint64_t pixels;          // the shard's packed pixels
+    AovChunk chunk(const mcrt_camera_desc& cam, uint32_t global_seed, uint32_t spp, uint64_t first, uint64_t chunk_pixels, uint64_t total_pixels) const {
+        return chunkAt(cam, global_seed, spp, first, chunk_pixels, total_pixels);
+    }
+    int rays(hipStream_t stream, const AovChunk& c, double scene_ior, const uint32_t* sobol_tab, const AovRays& rays_) const {
+        return launchProbeRays(stream, c, positions, pixels, scene_ior, sobol_tab, rays_);
+    }
+};
+
 // The camera's own checks. given: the call's other pointers are there; missing: what the message names when they or cam are not.
 inline int checkCamera(mcrt_ctx* ctx, const mcrt_camera_desc* cam, bool given, const char* what, const char* missing = "cam or buffers is NULL") {
     if (!cam || !given) return ctxFail(ctx, MCRT_ERR_INVALID, std::string(what) + ": " + missing);
@@ -171,7 +184,7 @@ struct CameraPass {
 
 // How the chunks of a call name their pixels, as the chunk loop needs it: chunk(...) is the record of a chunk, rays(...) queues the
 // kernel that writes its camera rays. Here the frame's own order - pixel p of a chunk is packed pixel first_pixel + p, the rays are
-// libmcrt_aov.so's -; under a lens LensPixels below, under a ray source SourcePixels above; the adaptive pass has a naming through a pixel list (mcrt_adaptive_host.hip).
+// libmcrt_aov.so's -; under a lens LensPixels below, under a ray source SourcePixels above, a probe call's positions ProbePixels; the adaptive pass has a naming through a pixel list (mcrt_adaptive_host.hip).
 struct FramePixels {
     AovChunk chunk(const mcrt_camera_desc& cam, uint32_t global_seed, uint32_t spp, uint64_t first, uint64_t chunk_pixels, uint64_t total_pixels) const {
         return chunkAt(cam, global_seed, spp, first, chunk_pixels, total_pixels);

@@ -35,7 +35,7 @@ int intersectDeviceArrays(mcrt_ctx* ctx, uint64_t n, const double* d_start, cons
 // a channel is wanted - then the channels of `targets` other than rgb (mcrt_summary_channels.hpp; nullptr: not wanted) are what the pass
 // loops of the next renders of this context fill (their epilogue's launches), until ctxSampleTargetsEnd clears them (SampleTargetsScope does).
 struct AovScene;
-enum PassFamily { kPassAov, kPassDenoise, kPassPixelStats, kPassRobust, kPassDenoiseVar, kPassAccumulate, kPassDenoiseDual, kPassExr, kPassMatte, kPassCompare, kPassOcclusion, kPassLighting, kPassLightGroups, kPassPathClasses, kPassAdaptive, kPassFamilies };
+enum PassFamily { kPassAov, kPassDenoise, kPassPixelStats, kPassRobust, kPassDenoiseVar, kPassAccumulate, kPassDenoiseDual, kPassExr, kPassMatte, kPassCompare, kPassOcclusion, kPassLighting, kPassLightGroups, kPassPathClasses, kPassAdaptive, kPassProbes, kPassFamilies };
 constexpr int kPassSlots = 6;
 int ctxIdle(mcrt_ctx* ctx, const char* what);
 int ctxNeedScene(mcrt_ctx* ctx, const char* what);

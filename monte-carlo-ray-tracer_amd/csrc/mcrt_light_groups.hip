@@ -12,7 +12,8 @@
 //   lightGroupsStepKernel     one lane per live sample: vertex k rebuilt once more (nothing of it is stored), its terms added to their
 //                             planes - the sky's too when the bounce ray missed -, otherwise the state of vertex k + 1 stored and the
 //                             sample appended to the OTHER list
-//   lightGroupsResolveKernel  one lane per pixel: the samples' R_p in ascending order into one FP64 accumulator per word
+//   lightGroupsResolveKernel  one lane per pixel: the samples' R_p in ascending order into one FP64 accumulator per word (a probe call:
+//                             one lane per output word, R_p times a function of the first ray's direction - mcrt_probes.hpp)
 // The live list is what keeps the iterations as wide as the work: paths die at very different depths, and an iteration costs its live
 // samples only. A wave appends with ONE atomic: the ballot of its surviving lanes, its population count for the leader's atomicAdd on
 // the list's counter, mbcnt for each lane's place behind the leader's base. The order of the list depends on the order in which waves
@@ -68,10 +69,20 @@ __global__ void __launch_bounds__(kLgBlock) lightGroupsStepKernel(AovChunk c, Ao
     }
 }
 
-__global__ void __launch_bounds__(kLgBlock) lightGroupsResolveKernel(AovChunk c, LgState st, uint32_t planes, double* out, uint64_t frame_pixels) {
-    const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
-    if (p >= c.pixels) return;
-    lgResolvePixel(c, st, planes, p, out, frame_pixels);
+// proj.coefficients == 0: the plain mean, one lane per pixel, as ever. Otherwise a probe call's projection (mcrt_probes.hpp), one lane per
+// output word - (plane, k, channel) of a pixel -, because such a call has few pixels and many samples: 64 probes of 4096 rays would be
+// one wave looping 4096 times per plane as lanes per pixel, and are 64 * planes * K * 3 lanes this way. The branch is a kernel argument,
+// uniform over the launch.
+__global__ void __launch_bounds__(kLgBlock) lightGroupsResolveKernel(AovChunk c, LgState st, uint32_t planes, double* out, uint64_t frame_pixels, ProbeProjection proj) {
+    if (proj.coefficients == 0u) {
+        const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
+        if (p >= c.pixels) return;
+        lgResolvePixel(c, st, planes, p, out, frame_pixels);
+        return;
+    }
+    const uint64_t lanes = probeLanes(c, planes, proj);
+    for (uint64_t lane = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; lane < lanes; lane += (uint64_t)gridDim.x * blockDim.x)
+        probeResolveLane(c, st, proj, lane, out, frame_pixels);
 }
 
 }  // namespace
@@ -93,7 +104,17 @@ int launchLightGroupsStep(void* stream, const AovChunk& c, const AovScene& scene
     return (int)hipGetLastError();
 }
 int launchLightGroupsResolve(void* stream, const AovChunk& c, const LgState& st, uint32_t planes, double* out, uint64_t frame_pixels) {
-    hipLaunchKernelGGL(lightGroupsResolveKernel, dim3((c.pixels + kLgBlock - 1) / kLgBlock), dim3(kLgBlock), 0, (hipStream_t)stream, c, st, planes, out, frame_pixels);
+    hipLaunchKernelGGL(lightGroupsResolveKernel, dim3((c.pixels + kLgBlock - 1) / kLgBlock), dim3(kLgBlock), 0, (hipStream_t)stream, c, st, planes, out, frame_pixels,
+                       ProbeProjection{});
+    return (int)hipGetLastError();
+}
+int launchProbeResolve(void* stream, const AovChunk& c, const LgState& st, uint32_t planes, const ProbeProjection& proj, double* out, uint64_t frame_pixels) {
+    if (proj.coefficients == 0u || proj.coefficients > kProbeCoefficientsMax || !proj.direction || planes == 0u || planes > kLgPlanesMax || !out ||
+        c.first_pixel + c.pixels > frame_pixels || (uint64_t)c.pixels * c.spp > st.n)
+        return (int)hipErrorInvalidValue;
+    const uint64_t blocks = (probeLanes(c, planes, proj) + kLgBlock - 1) / kLgBlock;
+    if (blocks == 0) return (int)hipSuccess;
+    hipLaunchKernelGGL(lightGroupsResolveKernel, dim3((uint32_t)std::min<uint64_t>(blocks, 1u << 20)), dim3(kLgBlock), 0, (hipStream_t)stream, c, st, planes, out, frame_pixels, proj);
     return (int)hipGetLastError();
 }
 }  // namespace mcrt

@@ -4,6 +4,7 @@
 #pragma once
 
 #include "mcrt_light_groups.hpp"
+#include "mcrt_probes.hpp"
 
 namespace mcrt {
 
@@ -20,5 +21,9 @@ int launchLightGroupsStep(void* stream, const AovChunk& c, const AovScene& scene
                           uint32_t n_live, uint32_t k, bool last, const AovRays& lit, uint32_t* next_list, LgCounters* counters, uint32_t next);
 // out: `planes` frames of frame_pixels pixels each.
 int launchLightGroupsResolve(void* stream, const AovChunk& c, const LgState& st, uint32_t planes, double* out, uint64_t frame_pixels);
+// The same kernel's projection (include/mcrt.h "Light probes", mcrt_probes.hpp): out is planes * proj.coefficients frames of frame_pixels
+// pixels each; proj.direction holds the first-ray directions of the chunk's samples. What would read or write past the chunk's arrays
+// is hipErrorInvalidValue and nothing is queued.
+int launchProbeResolve(void* stream, const AovChunk& c, const LgState& st, uint32_t planes, const ProbeProjection& proj, double* out, uint64_t frame_pixels);
 
 }  // namespace mcrt

@@ -12,6 +12,8 @@
 //               [--occlusion PREFIX [--occlusion-rays N] [--occlusion-distance D]] [--lighting PREFIX]
 //               [--light-groups PREFIX [--light-groups-by material|light|one] [--light-groups-depth D]]
 //               [--path-classes PREFIX [--path-classes-depth D]]
+//   mcrt_render scene.mcrt out.exr --probes POINTS.txt [--probe-order L] [--probe-rays N] [--seed N] [--device D]
+//               [--light-groups-by material|light|one] [--light-groups-depth D] [--exr-compression none|zip]
 //
 // Writes the frame as raw FP64 RGB, row-major (what Image::operator() holds, camera/image.cpp:53-56),
 // and prints the statistics. --tga also develops it the way Image::save does (auto exposure / gain, tone map, sRGB bytes:
@@ -91,6 +93,12 @@
 // and --path-classes then trace cosine-weighted rays from those surface points: the frame times pi is the irradiance that arrives at
 // what each pixel sees, --light-groups gives it per lamp. --aov still writes the camera's own AOV frame. Not with --lens, nor with
 // what --lens excludes.
+// --probes turns the run into a light-probe bake (mcrt_render_probes, include/mcrt.h "Light probes"): POINTS.txt holds one point "x y z"
+// per line (blank lines and lines that start with # are skipped), N points in all; from each --probe-rays rays (default 1024, rounded up
+// to a square) leave uniformly over the sphere, and the light that travels along them is projected on the first (L + 1)^2 spherical
+// harmonics (--probe-order L = 0, 1, 2; default 2), per light group (--light-groups-by, --light-groups-depth as above). The output - the
+// second argument - is an N x 1 OpenEXR file (mcrt_exr_save) with the FLOAT channels probe.<plane>.<k>.R/G/B, the raw means (the header's
+// constants normalise them); no frame is rendered. Path tracer on one device; not with --lens, --gather or any other output.
 // --devices renders the frame on several GPUs from this one process (mcrt_render_multi: one host thread per GPU).
 #include <cstdio>
 #include <cstdlib>
@@ -124,6 +132,8 @@ int main(int argc, char** argv) {
     uint32_t light_groups_depth = 0, path_classes_depth = 0;
     std::string lens_name;
     mcrt_lens_desc lens{};
+    std::string probes;
+    uint32_t probe_order = MCRT_PROBE_ORDER_MAX, probe_rays = 1024;
     bool gather = false;
     std::string gather_normal = "normal";
     std::vector<double> gather_position, gather_normals;
@@ -188,6 +198,9 @@ int main(int argc, char** argv) {
         else if (k == "--light-groups-by" && i + 1 < argc) light_groups_by = argv[++i];
         else if (k == "--light-groups-depth" && i + 1 < argc) light_groups_depth = (uint32_t)std::strtoul(argv[++i], nullptr, 10);
         else if (k == "--path-classes" && i + 1 < argc) path_classes = argv[++i];
+        else if (k == "--probes" && i + 1 < argc) probes = argv[++i];
+        else if (k == "--probe-order") probe_order = (uint32_t)val();
+        else if (k == "--probe-rays") probe_rays = (uint32_t)val();
         else if (k == "--gather") gather = true;
         else if (k == "--gather-normal" && i + 1 < argc) gather_normal = argv[++i];
         else if (k == "--lens" && i + 1 < argc) lens_name = argv[++i];
@@ -266,6 +279,52 @@ int main(int argc, char** argv) {
         reference.resize(want / 8);
         if (!compare_exr) std::memcpy(reference.data(), bytes.data() + at, want);
     }
+    // the groups of --light-groups-by: surface_group and the planes' names without the sky's (false: a message was printed)
+    auto light_group_map = [&](std::vector<uint32_t>& group, std::vector<std::string>& names) {
+        // the groups of light_group_map (the Python binding): emitters are the surfaces whose material carries MCRT_MAT_EMISSIVE
+        const mcrt_scene_desc* sd = mcrt_image_scene(img);
+        group.assign(sd->num_surfaces, 0u);
+        names.clear();
+        if (light_groups_by == "material") {
+            std::vector<int> group_of(sd->num_materials, -1);
+            for (uint32_t m = 0; m < sd->num_materials; m++) {
+                if (!(sd->materials[m].flags & MCRT_MAT_EMISSIVE)) continue;
+                bool used = false;
+                for (uint32_t i = 0; i < sd->num_surfaces && !used; i++) used = sd->surf_material[i] == m;
+                if (!used) continue;
+                group_of[m] = (int)names.size();
+                names.push_back("material" + std::to_string(m));
+            }
+            for (uint32_t i = 0; i < sd->num_surfaces; i++)
+                if (group_of[sd->surf_material[i]] >= 0) group[i] = (uint32_t)group_of[sd->surf_material[i]];
+        } else if (light_groups_by == "light") {
+            for (uint32_t i = 0; i < sd->num_surfaces; i++)
+                if (sd->materials[sd->surf_material[i]].flags & MCRT_MAT_EMISSIVE) {
+                    group[i] = (uint32_t)names.size();
+                    names.push_back("light" + std::to_string(i));
+                }
+        } else if (light_groups_by != "one") {
+            std::fprintf(stderr, "--light-groups-by: material, light or one, not %s\n", light_groups_by.c_str());
+            return false;
+        }
+        if (names.empty()) names.push_back("lights");
+        if (names.size() > MCRT_LIGHT_GROUPS_MAX) {
+            std::fprintf(stderr, "--light-groups-by %s: %zu groups, at most %u can be rendered\n", light_groups_by.c_str(), names.size(), MCRT_LIGHT_GROUPS_MAX);
+            return false;
+        }
+        return true;
+    };
+    if (!probes.empty() && (!lens_name.empty() || gather || photon || adaptive || converge || devices.size() > 1 || !exr.empty() || !tga.empty() || !aov.empty() || !denoise.empty() ||
+                            !dvar.empty() || !ddual.empty() || !pstats.empty() || !robust.empty() || !matte.empty() || !compare.empty() || !occlusion.empty() ||
+                            !lighting.empty() || !light_groups.empty() || !path_classes.empty())) {
+        std::fprintf(stderr, "--probes is a run of its own on one device: the path tracer's probes into the OpenEXR file named as the output, with --probe-order, --probe-rays, "
+                             "--light-groups-by, --light-groups-depth, --seed, --device and --exr-compression only\n");
+        return 2;
+    }
+    if (!probes.empty() && (probe_order > MCRT_PROBE_ORDER_MAX || probe_rays == 0)) {
+        std::fprintf(stderr, "--probe-order: 0, 1 or 2; --probe-rays: at least 1\n");
+        return 2;
+    }
     if (!lens_name.empty()) {
         const char* models[] = {"orthographic", "equirectangular", "fisheye"};
         for (uint32_t m = 0; m < 3; m++)
@@ -315,6 +374,74 @@ int main(int argc, char** argv) {
         if (rc != MCRT_OK) std::fprintf(stderr, "device %d: %s\n", devices[d], mcrt_last_error(ctxs[d]));
     }
     mcrt_ctx* ctx = ctxs[0];
+    if (!probes.empty()) {  // the probe bake: no frame
+        if (rc != MCRT_OK) return 1;
+        std::vector<double> points;
+        if (FILE* in = std::fopen(probes.c_str(), "r")) {
+            char line[512];
+            while (std::fgets(line, sizeof line, in)) {
+                const char* t = line + std::strspn(line, " \t\r\n");
+                if (!*t || *t == '#') continue;
+                double v[3];
+                if (std::sscanf(t, "%lf %lf %lf", &v[0], &v[1], &v[2]) != 3) {
+                    std::fclose(in);
+                    std::fprintf(stderr, "--probes: %s: not a point \"x y z\": %s", probes.c_str(), line);
+                    return 2;
+                }
+                points.insert(points.end(), v, v + 3);
+            }
+            std::fclose(in);
+        } else {
+            std::fprintf(stderr, "--probes: cannot read %s\n", probes.c_str());
+            return 1;
+        }
+        if (points.empty()) {
+            std::fprintf(stderr, "--probes: %s holds no point\n", probes.c_str());
+            return 2;
+        }
+        std::vector<uint32_t> group;
+        std::vector<std::string> names;
+        if (!light_group_map(group, names)) return 1;
+        mcrt_probe_params pp{};
+        pp.groups.num_groups = (uint32_t)names.size();
+        pp.groups.max_depth = light_groups_depth;
+        pp.groups.surface_group = group.data();
+        pp.order = probe_order;
+        pp.positions = points.data();
+        names.push_back("sky");
+        mcrt_camera_desc pcam{};
+        pcam.width = (uint32_t)(points.size() / 3);
+        pcam.height = 1;
+        pcam.shard_count = 1;
+        for (pcam.sqrtspp = 1; (uint64_t)pcam.sqrtspp * pcam.sqrtspp < probe_rays;) pcam.sqrtspp++;
+        const uint32_t K = mcrt_probe_coefficients(probe_order);
+        const size_t frame = (size_t)pcam.width * 3;
+        std::vector<double> coefficients(names.size() * K * frame);
+        mcrt_stats pst;
+        rc = mcrt_render_probes(ctx, &pcam, seed, &pp, coefficients.data(), &pst);
+        if (rc != MCRT_OK) {
+            std::fprintf(stderr, "mcrt error %d: %s\n", rc, mcrt_last_error(ctx));
+            return 1;
+        }
+        exr = argv[2];
+        for (size_t p = 0; p < names.size(); p++)
+            for (uint32_t k = 0; k < K; k++) exr_layer("probe." + names[p] + "." + std::to_string(k), "RGB", coefficients.data() + (p * K + k) * frame, MCRT_EXR_FLOAT);
+        const std::string a_rays = std::to_string(pcam.sqrtspp * pcam.sqrtspp), a_seed = std::to_string(seed), a_order = std::to_string(probe_order);
+        const mcrt_exr_attribute attributes[] = {{"mcrt:probe_rays", a_rays.c_str()}, {"mcrt:seed", a_seed.c_str()}, {"mcrt:probe_order", a_order.c_str()}};
+        mcrt_exr_result er;
+        mcrt_stats est;
+        rc = mcrt_exr_save(ctx, exr.c_str(), pcam.width, 1, exr_channels.data(), (uint32_t)exr_channels.size(), attributes, 3, &eparams, &er, &est);
+        if (rc != MCRT_OK) {
+            std::fprintf(stderr, "mcrt error %d: %s\n", rc, mcrt_last_error(ctx));
+            return 1;
+        }
+        std::printf("{\"probes\":%u,\"rays\":%u,\"order\":%u,\"planes\":%zu,\"by\":\"%s\",\"max_depth\":%u,\"exr\":\"%s\",\"channels\":%zu,\"traced\":%llu,\"kernel_ms\":%.3f,\"total_ms\":%.3f}\n",
+                    pcam.width, pcam.sqrtspp * pcam.sqrtspp, probe_order, names.size(), light_groups_by.c_str(), light_groups_depth, exr.c_str(), exr_channels.size(),
+                    (unsigned long long)pst.rays, pst.kernel_ms, pst.total_ms);
+        for (mcrt_ctx* c : ctxs) mcrt_destroy(c);
+        mcrt_image_free(img);
+        return 0;
+    }
     auto set_gather = [&]() {  // (pixels with no hit hold a zero normal: the kernel's fallback, +z from the origin)
         mcrt_ray_source_desc d{};
         d.kind = MCRT_RAY_SOURCE_SURFACE;
@@ -832,37 +959,9 @@ int main(int argc, char** argv) {
             std::fprintf(stderr, "--light-groups: the light groups are the path tracer's (not with --photon)\n");
             return 1;
         }
-        // the groups of light_group_map (the Python binding): emitters are the surfaces whose material carries MCRT_MAT_EMISSIVE
-        const mcrt_scene_desc* sd = mcrt_image_scene(img);
-        std::vector<uint32_t> group(sd->num_surfaces, 0u);
+        std::vector<uint32_t> group;
         std::vector<std::string> names;
-        if (light_groups_by == "material") {
-            std::vector<int> group_of(sd->num_materials, -1);
-            for (uint32_t m = 0; m < sd->num_materials; m++) {
-                if (!(sd->materials[m].flags & MCRT_MAT_EMISSIVE)) continue;
-                bool used = false;
-                for (uint32_t i = 0; i < sd->num_surfaces && !used; i++) used = sd->surf_material[i] == m;
-                if (!used) continue;
-                group_of[m] = (int)names.size();
-                names.push_back("material" + std::to_string(m));
-            }
-            for (uint32_t i = 0; i < sd->num_surfaces; i++)
-                if (group_of[sd->surf_material[i]] >= 0) group[i] = (uint32_t)group_of[sd->surf_material[i]];
-        } else if (light_groups_by == "light") {
-            for (uint32_t i = 0; i < sd->num_surfaces; i++)
-                if (sd->materials[sd->surf_material[i]].flags & MCRT_MAT_EMISSIVE) {
-                    group[i] = (uint32_t)names.size();
-                    names.push_back("light" + std::to_string(i));
-                }
-        } else if (light_groups_by != "one") {
-            std::fprintf(stderr, "--light-groups-by: material, light or one, not %s\n", light_groups_by.c_str());
-            return 1;
-        }
-        if (names.empty()) names.push_back("lights");
-        if (names.size() > MCRT_LIGHT_GROUPS_MAX) {
-            std::fprintf(stderr, "--light-groups-by %s: %zu groups, at most %u can be rendered\n", light_groups_by.c_str(), names.size(), MCRT_LIGHT_GROUPS_MAX);
-            return 1;
-        }
+        if (!light_group_map(group, names)) return 1;
         mcrt_light_group_params gp{};
         gp.num_groups = (uint32_t)names.size();
         gp.max_depth = light_groups_depth;
