@@ -1209,7 +1209,8 @@ int mcrt_render_lighting(mcrt_ctx* ctx, const mcrt_camera_desc* cam, uint32_t gl
  *                  there: no light sample, no bounce. D = 1 is the lighting passes' cut - planes of direct light only -, and the
  *                  indirect light per group is the full planes minus these.
  * Output: d_planes, [P][rows][width][3] doubles, the rows this shard owns packed like d_out_rgb. cam->shard_* is honoured exactly as in
- * mcrt_render_aov_device; cam->film_* is IGNORED. Both calls are synchronous on the context's stream.
+ * mcrt_render_aov_device; cam->film_* is IGNORED unless flags carries MCRT_LIGHT_GROUPS_FILM ("Filtered planes" below). Both calls are synchronous on
+ * the context's stream.
  * What holds, bit for bit unless said otherwise:
  *   - The planes are a function of scene, camera, seed and parameters. They do not depend on chunking (option MCRT_AOV_CHUNK_RAYS: here
  *     the shadow and bounce slots of iteration 0 per chunk - 2 per sample, whole pixels, one at least; default: what 2^17 pixels take, at least
@@ -1228,10 +1229,14 @@ int mcrt_render_lighting(mcrt_ctx* ctx, const mcrt_camera_desc* cam, uint32_t gl
  * traces (a sample without a shadow or a bounce ray has a finite dummy traced in that slot; a sample whose ray missed is not alive: its
  * sky was added where the miss was found); kernel_ms (HIP events around the pass's
  * launches), total_ms, kernel_launches.
- * Not done: photon-mapped frames, filter-weighted means, nesting deeper than 8 media. (A split by lobe - diffuse / glossy /
+ * Not done: photon-mapped frames, nesting deeper than 8 media. (A split by lobe - diffuse / glossy /
  * transmission -: "Path classes" below.) */
 #define MCRT_LIGHT_GROUPS_MAX 15u
-enum { MCRT_LIGHT_GROUPS_SKY_PLANE = 1u }; /* mcrt_light_group_params.flags: sky_plane is given */
+enum {
+    MCRT_LIGHT_GROUPS_SKY_PLANE = 1u, /* mcrt_light_group_params.flags: sky_plane is given */
+    MCRT_LIGHT_GROUPS_FILM = 2u,      /* the planes through the camera's film ("Filtered planes") */
+    MCRT_LIGHT_GROUPS_FILM_CLAMP = 4u /* with FILM: max(., 0) on every word */
+};
 typedef struct mcrt_light_group_params {
     uint32_t num_groups;           /* G; 0 = 1 */
     uint32_t flags;                /* MCRT_LIGHT_GROUPS_* */
@@ -1276,7 +1281,8 @@ int mcrt_render_light_groups(mcrt_ctx* ctx, const mcrt_camera_desc* cam, uint32_
  *   max_depth    D, with the light groups' meaning: 0 = the whole path; with D > 0 iteration k == D takes only its miss or its
  *                sampleEmissive term and the path ends there.
  * Output: d_planes, [P][rows][width][3] doubles, the rows this shard owns packed like d_out_rgb. cam->shard_* is honoured exactly as in
- * mcrt_render_aov_device; cam->film_* is IGNORED. Both calls are synchronous on the context's stream.
+ * mcrt_render_aov_device; cam->film_* is IGNORED unless flags carries MCRT_PATH_CLASSES_FILM ("Filtered planes" below). Both calls are synchronous on
+ * the context's stream.
  * What holds, bit for bit unless said otherwise:
  *   1. The planes are a function of scene, camera, seed and parameters. They do not depend on chunking (option MCRT_AOV_CHUNK_RAYS, with
  *      the light groups' meaning and default), sharding, launch shape, or the order in which live samples are queued.
@@ -1292,7 +1298,7 @@ int mcrt_render_light_groups(mcrt_ctx* ctx, const mcrt_camera_desc* cam, uint32_
  * nests more than 8 dielectric media and a frame whose paths are still alive after 4096 iterations, as in the light groups.
  * stats: as in the light groups (rays = the camera rays and 2 per sample alive at every iteration that traces).
  * Not done: photon-mapped frames, a split of glossy into Dirac and rough, classification by any vertex other than the first, classes x
- * light groups in one call, albedo-divided planes, filter-weighted means, nesting deeper than 8 media. */
+ * light groups in one call, albedo-divided planes, nesting deeper than 8 media. */
 #define MCRT_PATH_CLASSES 8u
 enum {
     MCRT_PATH_CLASS_EMISSION = 0,
@@ -1304,7 +1310,11 @@ enum {
     MCRT_PATH_CLASS_TRANSMISSION_DIRECT = 6,
     MCRT_PATH_CLASS_TRANSMISSION_INDIRECT = 7
 };
-enum { MCRT_PATH_CLASSES_MAP = 1u }; /* mcrt_path_class_params.flags: class_plane is given */
+enum {
+    MCRT_PATH_CLASSES_MAP = 1u,       /* mcrt_path_class_params.flags: class_plane is given */
+    MCRT_PATH_CLASSES_FILM = 2u,      /* the planes through the camera's film ("Filtered planes") */
+    MCRT_PATH_CLASSES_FILM_CLAMP = 4u /* with FILM: max(., 0) on every word */
+};
 typedef struct mcrt_path_class_params {
     uint32_t flags;                          /* MCRT_PATH_CLASSES_* */
     uint32_t max_depth;                      /* D; 0 = the whole path */
@@ -1317,6 +1327,57 @@ int mcrt_render_path_classes_device(mcrt_ctx* ctx, const mcrt_camera_desc* cam, 
 /* Same with a HOST pointer to P FULL frames, [P][height][width][3]: rows this shard does not own are left untouched. */
 int mcrt_render_path_classes(mcrt_ctx* ctx, const mcrt_camera_desc* cam, uint32_t global_seed, const mcrt_path_class_params* params /* may be NULL */,
                              double* planes, mcrt_stats* stats /* may be NULL */);
+
+/* ------------------------------------------------------------------------------------------
+ * Filtered planes: the light groups' and the path classes' planes through the camera's reconstruction filter (film_filter, film_radius,
+ * film_cache_size) instead of the box mean, so that they add up to the FILTERED beauty frame - and, with one plane, a filtered beauty
+ * frame that is a function of its inputs bit for bit, with or without a lens (mcrt_render's is splatted with atomics and agrees with
+ * itself to rounding only). No new call: flags on the two parameter structs, whose sizes and MCRT_ABI_VERSION stay.
+ *   MCRT_LIGHT_GROUPS_FILM, MCRT_PATH_CLASSES_FILM              resolve the planes through the film
+ *   MCRT_LIGHT_GROUPS_FILM_CLAMP, MCRT_PATH_CLASSES_FILM_CLAMP  with FILM: Splat::get's max(., 0) on every word (ignored without FILM).
+ *       Planes are NOT clamped by default: a filter with negative lobes (Mitchell-Netravali, Catmull-Rom, Lanczos) gives signed planes,
+ *       and only unclamped planes add up. Clamped, the single plane is the reference's frame.
+ * Without FILM every byte of every call is what it was. With FILM and a film that does not splat (the default box: film_filter
+ * MCRT_FILM_BOX with film_radius 0 or 0.5) the plain resolve runs and the bytes are the unflagged call's.
+ * A film that splats, operation by operation. The walk and every sample's R_p are those of "Light groups" / "Path classes"; only the
+ * resolve differs.
+ *   Sample i of pixel (x, y) has the film position px = (double)x + get(kDimPixel), py = (double)y + get(kDimPixel + 1), the sampler at
+ *   initiate(global_seed, y*width + x), setIndex(i): the camera ray's own pair, also under a lens.
+ *   r = film_radius, or the filter's default radius when film_radius is 0 (film.cpp:31-44).
+ *   The sample COVERS output pixel (qx, qy) exactly when Film::deposit (film.cpp:61-79) would write it there:
+ *     max((long long)(px + 0.5 - r), 0) <= qx <= min((long long)(px - 0.5 + r), width - 1), the conversions truncating, and the same
+ *     in y with height.
+ *   Its weight there is w = filter(qy + 0.5 - py) * filter(qx + 0.5 - px), filter being Film::filter (film.cpp:86-97):
+ *     film_cache_size == 0: filter_function(2 / r * fabs(t)) (camera/filter.hpp; the widened box: 1)
+ *     otherwise:            table[(size_t)((film_cache_size - 1) / r * fabs(t) + 0.5)], table[k] = filter_function(2 k / (film_cache_size - 1))
+ *   Per plane p, output pixel and channel, over the covering samples s1, s2, ... in ascending packed source pixel (y*width + x), then
+ *   ascending sample index, one FP64 accumulator each, no operation contracted:
+ *     S = (((0.0 + R_p(s1) * w(s1)) + R_p(s2) * w(s2)) + ...)
+ *     W = ((0.0 + w(s1)) + w(s2)) + ...
+ *   and the word is W == 0 ? 0 : S / W - under CLAMP max(S / W, 0), a NaN giving 0 as in Splat::get. NaN and Inf are not filtered.
+ *   This is Film::deposit's own arithmetic - the same products v * weight, the same sums - in a FIXED order; the reference's order is
+ *   whatever its threads' atomics make it. Clamped, the single plane therefore agrees with the reference's frame (and mcrt_render's)
+ *   to rounding: 1e-12 relative in the exact library.
+ * The order is global, so the planes do not depend on chunking (MCRT_AOV_CHUNK_RAYS), bit for bit: chunks are contiguous ranges of
+ * packed pixels visited in ascending order on one stream, and a chunk's gather continues the running S and W where the chunk before
+ * left them. S lives in d_planes (zeroed by the call), W in one frame-sized array of the family's scratch; both are normalised in place
+ * after the last chunk. d_planes must therefore not be read before the call returns.
+ * What holds, bit for bit: the planes are a function of scene, camera (its film included), seed and parameters - not of chunking, launch
+ * shape, the live lists' order or the run; a group's plane does not depend on how the other emitters are grouped; the path classes'
+ * single plane is the light groups' single plane. To rounding: the unclamped planes add up to the single unclamped plane (1e-12 relative
+ * for a filter without negative lobes).
+ * Refused with a message that names the reason (MCRT_ERR_UNSUPPORTED unless said otherwise), d_planes untouched:
+ *   - cam->shard_count > 1: the gather needs the neighbours' rows (not done: an S, W output form like mcrt_render_film_device's)
+ *   - a ray source set on the context (mcrt_set_ray_source): its pixels have no film position
+ *   - the FILM flags inside mcrt_probe_params.groups (MCRT_ERR_INVALID): a probe has no film
+ *   - film_filter > MCRT_FILM_LANCZOS (MCRT_ERR_INVALID)
+ *   - film_cache_size == 1 (MCRT_ERR_INVALID): the table's step 2 / (film_cache_size - 1) has no value
+ *   - film_radius negative, not a number, or 1e6 and more (MCRT_ERR_INVALID): the window's rows are counted in 32 bits
+ * Adaptive sampling and the statistics calls stay refused for splatting films as they are.
+ * Option MCRT_FILM_GATHER=force (mcrt_set_option, per context; a test's lever): a film that does not splat goes through the gather too
+ * - radius 0.5, every weight 1, every window one pixel - and gives the plain resolve's bytes: S = sum of R_p, W = (double)spp.
+ * Not done: the AOV, matte, occlusion and lighting passes (box means are what denoisers and id passes want); sharded cameras; adaptive
+ * sampling and the statistics under a filter; a public gather over caller-supplied per-sample values. */
 
 /* ------------------------------------------------------------------------------------------
  * Adaptive sampling: a per-pixel stopping rule. mcrt_render_converged stops when the whole FRAME is quiet enough and until then samples

@@ -201,6 +201,8 @@ class LightGroupParams(C.Structure):
 
 LIGHT_GROUPS_MAX = 15
 LIGHT_GROUPS_SKY_PLANE = 1
+LIGHT_GROUPS_FILM = 2        # the planes through the camera's film (include/mcrt.h "Filtered planes")
+LIGHT_GROUPS_FILM_CLAMP = 4  # with LIGHT_GROUPS_FILM: max(., 0) on every word
 MAT_EMISSIVE = 1 << 3
 
 
@@ -243,6 +245,8 @@ class PathClassParams(C.Structure):
 
 PATH_CLASSES = 8
 PATH_CLASSES_MAP = 1
+PATH_CLASSES_FILM = 2        # the planes through the camera's film (include/mcrt.h "Filtered planes")
+PATH_CLASSES_FILM_CLAMP = 4  # with PATH_CLASSES_FILM: max(., 0) on every word
 PATH_CLASS_NAMES = ("emission", "background", "diffuse_direct", "diffuse_indirect", "glossy_direct", "glossy_indirect", "transmission_direct",
                     "transmission_indirect")
 
@@ -1572,24 +1576,27 @@ class Context:
         return st.as_dict()
 
     @staticmethod
-    def _light_group_params(groups, sky_plane, max_depth, num_groups):
+    def _light_group_params(groups, sky_plane, max_depth, num_groups, film=False, film_clamp=False):
         """-> (LightGroupParams, the array it points into). groups: [num_surfaces] group per surface, or None."""
         keep = None if groups is None else np.ascontiguousarray(groups, dtype=np.uint32)
         if num_groups is None:
             num_groups = 1 if keep is None or keep.size == 0 else int(keep.max()) + 1
-        par = LightGroupParams(int(num_groups), 0 if sky_plane is None else LIGHT_GROUPS_SKY_PLANE, 0 if sky_plane is None else int(sky_plane), int(max_depth),
-                               None if keep is None else keep.ctypes.data)
+        flags = (0 if sky_plane is None else LIGHT_GROUPS_SKY_PLANE) | (LIGHT_GROUPS_FILM if film else 0) | (LIGHT_GROUPS_FILM_CLAMP if film_clamp else 0)
+        par = LightGroupParams(int(num_groups), flags, 0 if sky_plane is None else int(sky_plane), int(max_depth), None if keep is None else keep.ctypes.data)
         return par, keep
 
-    def render_light_groups(self, cam, global_seed, groups=None, sky_plane=None, max_depth=0, stats=None, num_groups=None, out=None):
+    def render_light_groups(self, cam, global_seed, groups=None, sky_plane=None, max_depth=0, stats=None, num_groups=None, out=None, film=False, film_clamp=False):
         """mcrt_render_light_groups: the path-traced frame of cam and global_seed split by emitter, every bounce -> [P,H,W,3]: one plane
         per group and the sky's, which add up to the frame (include/mcrt.h "Light groups"). groups: [num_surfaces] the group of every
         surface (light_group_map builds it; entries of surfaces that emit nothing are ignored), None = every emitter in group 0.
         num_groups: default max(groups) + 1. sky_plane: the plane that takes the sky, default a plane of its own after the groups.
         max_depth: 0 = the whole path, 1 = direct light only. out: an array to write into instead of fresh zeros - the call only writes
-        the rows cam's shard owns. stats: a dict that receives mcrt_stats."""
+        the rows cam's shard owns. stats: a dict that receives mcrt_stats. film: the planes through cam's reconstruction filter
+        (film_filter, film_radius, film_cache_size) instead of the box mean, gathered in a fixed order - the same bytes run after run
+        (include/mcrt.h "Filtered planes"); film_clamp: max(., 0) on every word, as the film's own resolve has it (planes that are to
+        add up stay unclamped)."""
         self._sync_env()
-        par, keep = self._light_group_params(groups, sky_plane, max_depth, num_groups)
+        par, keep = self._light_group_params(groups, sky_plane, max_depth, num_groups, film, film_clamp)
         planes = int(self._lib.mcrt_light_group_planes(C.byref(par)))
         shape = (max(planes, 1), cam.height, cam.width, 3)  # (out of range: the call below says what is)
         a = out if out is not None else np.zeros(shape)
@@ -1600,35 +1607,36 @@ class Context:
             stats.update(st.as_dict())
         return a
 
-    def render_light_groups_device(self, cam, global_seed, pointer, groups=None, sky_plane=None, max_depth=0, num_groups=None):
+    def render_light_groups_device(self, cam, global_seed, pointer, groups=None, sky_plane=None, max_depth=0, num_groups=None, film=False, film_clamp=False):
         """mcrt_render_light_groups_device: pointer = raw device pointer to [P][owned rows][W][3] doubles (packed like render_device's
-        output). Synchronous; returns the stats dict."""
+        output). film, film_clamp: as in render_light_groups. Synchronous; returns the stats dict."""
         self._sync_env()
-        par, keep = self._light_group_params(groups, sky_plane, max_depth, num_groups)
+        par, keep = self._light_group_params(groups, sky_plane, max_depth, num_groups, film, film_clamp)
         st = Stats()
         self._check(self._lib.mcrt_render_light_groups_device(self._h, C.byref(cam), int(global_seed), C.byref(par), int(pointer) if pointer else None, C.byref(st)),
                     "mcrt_render_light_groups_device")
         return st.as_dict()
 
     @staticmethod
-    def _path_class_params(class_plane, max_depth):
+    def _path_class_params(class_plane, max_depth, film=False, film_clamp=False):
         """-> PathClassParams. class_plane: the plane of each of the eight classes, or None = the identity."""
-        par = PathClassParams(0, int(max_depth))
+        par = PathClassParams((PATH_CLASSES_FILM if film else 0) | (PATH_CLASSES_FILM_CLAMP if film_clamp else 0), int(max_depth))
         if class_plane is not None:
             entries = [int(p) for p in class_plane]
             assert len(entries) == PATH_CLASSES and all(0 <= p < 256 for p in entries), entries
-            par.flags = PATH_CLASSES_MAP
+            par.flags |= PATH_CLASSES_MAP
             par.class_plane[:] = entries
         return par
 
-    def render_path_classes(self, cam, global_seed, class_plane=None, max_depth=0, stats=None, out=None):
+    def render_path_classes(self, cam, global_seed, class_plane=None, max_depth=0, stats=None, out=None, film=False, film_clamp=False):
         """mcrt_render_path_classes: the path-traced frame of cam and global_seed split by what the first surface did with the light
         -> [P,H,W,3]: emission, background, and direct and indirect of diffuse, glossy and transmission (PATH_CLASS_NAMES), which add up
         to the frame (include/mcrt.h "Path classes"). class_plane: [8] the output plane of every class (path_class_map builds it),
         None = a plane each. max_depth: 0 = the whole path, 1 = no indirect light. out: an array to write into instead of fresh zeros -
-        the call only writes the rows cam's shard owns. stats: a dict that receives mcrt_stats."""
+        the call only writes the rows cam's shard owns. stats: a dict that receives mcrt_stats. film, film_clamp: the planes through
+        cam's reconstruction filter, as in render_light_groups (include/mcrt.h "Filtered planes")."""
         self._sync_env()
-        par = self._path_class_params(class_plane, max_depth)
+        par = self._path_class_params(class_plane, max_depth, film, film_clamp)
         planes = int(self._lib.mcrt_path_class_planes(C.byref(par)))
         shape = (max(planes, 1), cam.height, cam.width, 3)  # (out of range: the call below says what is)
         a = out if out is not None else np.zeros(shape)
@@ -1639,11 +1647,11 @@ class Context:
             stats.update(st.as_dict())
         return a
 
-    def render_path_classes_device(self, cam, global_seed, pointer, class_plane=None, max_depth=0):
+    def render_path_classes_device(self, cam, global_seed, pointer, class_plane=None, max_depth=0, film=False, film_clamp=False):
         """mcrt_render_path_classes_device: pointer = raw device pointer to [P][owned rows][W][3] doubles (packed like render_device's
-        output). Synchronous; returns the stats dict."""
+        output). film, film_clamp: as in render_light_groups. Synchronous; returns the stats dict."""
         self._sync_env()
-        par = self._path_class_params(class_plane, max_depth)
+        par = self._path_class_params(class_plane, max_depth, film, film_clamp)
         st = Stats()
         self._check(self._lib.mcrt_render_path_classes_device(self._h, C.byref(cam), int(global_seed), C.byref(par), int(pointer) if pointer else None, C.byref(st)),
                     "mcrt_render_path_classes_device")
@@ -1685,12 +1693,21 @@ class Context:
                                                       int(d_direction) if d_direction else None, C.byref(st)), "mcrt_camera_rays_device")
         return st.as_dict()
 
-    def render_lens(self, cam, global_seed, max_depth=0, stats=None, out=None):
+    def render_lens(self, cam, global_seed, max_depth=0, stats=None, out=None, film=False, film_clamp=False):
         """The beauty frame of cam and global_seed under the context's lens -> [H,W,3]: the light groups with every emitter and the sky in
         plane 0, which with no lens (or LENS_PERSPECTIVE) is mcrt_render's path-traced frame bit for bit. max_depth: 0 = the whole path.
-        out: an array to write into instead of fresh zeros - the call only writes the rows cam's shard owns."""
+        out: an array to write into instead of fresh zeros - the call only writes the rows cam's shard owns. film, film_clamp: through
+        cam's reconstruction filter, as in render_light_groups."""
         a = None if out is None else out.reshape((1,) + out.shape)
-        return self.render_light_groups(cam, global_seed, groups=None, sky_plane=0, max_depth=max_depth, stats=stats, num_groups=1, out=a)[0]
+        return self.render_light_groups(cam, global_seed, groups=None, sky_plane=0, max_depth=max_depth, stats=stats, num_groups=1, out=a, film=film,
+                                        film_clamp=film_clamp)[0]
+
+    def render_film(self, cam, global_seed, max_depth=0, stats=None):
+        """The filtered beauty frame of cam and global_seed -> [H,W,3], deterministic: one plane of the light groups through cam's
+        reconstruction filter, clamped like the film's own resolve (include/mcrt.h "Filtered planes"). It agrees with sample_image's
+        frame of the same camera to rounding - that one is splatted with atomics - and is the same bytes run after run, whatever the
+        chunking, with or without a lens. A camera with the default box film gives render_lens' frame."""
+        return self.render_lens(cam, global_seed, max_depth=max_depth, stats=stats, film=True, film_clamp=True)
 
     def set_ray_source(self, kind, first=None, second=None, per_pixel=False, offset=None):
         """mcrt_set_ray_source[_host]: the arrays the camera-ray passes (AOV, mattes, occlusion, lighting, light groups, path classes),

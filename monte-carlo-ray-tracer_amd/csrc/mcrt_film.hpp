@@ -25,6 +25,8 @@ MCRT_HD double mitchellNetravali(double B, double C, double x) {
     return d + (c + (b + a * x) * x) * x;
 }
 
+// kLds = false: refSin's table from memory (mcrt_libm.hpp), for a kernel that states no LDS - the same operations, the same bits
+template <bool kLds = true>
 MCRT_HD double filmFilterFunction(uint32_t type, double x) {  // filter.hpp
     switch (type) {
         case MCRT_FILM_MITCHELL_NETRAVALI: return mitchellNetravali(1.0 / 3.0, 1.0 / 3.0, x);
@@ -37,7 +39,7 @@ MCRT_HD double filmFilterFunction(uint32_t type, double x) {  // filter.hpp
         }
         case MCRT_FILM_LANCZOS:                                                // :65-69
             if (x == 0.0) return 1.0;
-            return 2.0 * refSin(kPi * x) * refSin(kPi * x / 2.0) / (kPi * kPi * x * x);  // two sin calls of different arguments: glibc's sin (mcrt_libm.hpp)
+            return 2.0 * refSin<kLds>(kPi * x) * refSin<kLds>(kPi * x / 2.0) / (kPi * kPi * x * x);  // two sin calls of different arguments: glibc's sin (mcrt_libm.hpp)
         default: return 1.0;  // box
     }
 }
@@ -71,8 +73,9 @@ struct FilmView {
     uint32_t width, height;
 };
 
+template <bool kLds = true>
 MCRT_HD double filmFilter(const FilmView& f, double x) {  // Film::filter, film.cpp:86-97
-    if (f.cache_size == 0) return filmFilterFunction(f.type, f.two_inv_radius * fabs(x));
+    if (f.cache_size == 0) return filmFilterFunction<kLds>(f.type, f.two_inv_radius * fabs(x));
     return f.cache[(size_t)(f.inv_dx * fabs(x) + 0.5)];
 }
 

@@ -54,6 +54,7 @@ inline void ldsTabStore(uint32_t, unsigned long long) {}
 #endif
 constexpr uint32_t kShadeStaticLds = 0u;
 }  // namespace glibc235
+template <bool kLds = true>
 MCRT_HD double refSin(double x) { return sin(x); }
 MCRT_HD double refCos(double x) { return cos(x); }
 template <bool kLds = true>
@@ -131,8 +132,8 @@ MCRT_HD double taylorSin(double xx, double x, double dx) {
     return x + t;
 }
 
-// do_cos(x, dx)
-template <bool kFused>
+// do_cos(x, dx). kLds = false (here and below): the table from memory, for a kernel that states no LDS (tabAt)
+template <bool kFused, bool kLds = true>
 MCRT_HD double doCos(double x, double dx) {
     if (x < 0.0) dx = -dx;
     const double ax = absD(x);
@@ -142,13 +143,13 @@ MCRT_HD double doCos(double x, double dx) {
     const double xx = x * x;
     const double s = fmaD<kFused>(x * xx, fmaD<kFused>(xx, kSn5, kSn3), x);                // s = x + x * xx * (sn3 + xx * sn5)
     const double c = xx * fmaD<kFused>(xx, fmaD<kFused>(xx, kCs6, kCs4), kCs2);            // c = xx * (cs2 + xx * (cs4 + xx * cs6))
-    const double sn = tabAt(k), ssn = tabAt(k + 1), cs = tabAt(k + 2), ccs = tabAt(k + 3);
+    const double sn = tabAt<kLds>(k), ssn = tabAt<kLds>(k + 1), cs = tabAt<kLds>(k + 2), ccs = tabAt<kLds>(k + 3);
     const double cor = fmaD<kFused>(-s, sn, fmaD<kFused>(-c, cs, fmaD<kFused>(-s, ssn, ccs)));     // cor = (ccs - s * ssn - cs * c) - sn * s
     return cs + cor;
 }
 
 // do_sin(x, dx)
-template <bool kFused>
+template <bool kFused, bool kLds = true>
 MCRT_HD double doSin(double x, double dx) {
     const double xold = x;
     if (absD(x) < 0.126) return taylorSin<kFused>(x * x, x, dx);
@@ -160,7 +161,7 @@ MCRT_HD double doSin(double x, double dx) {
     const double xx = x * x;
     const double s = x + fmaD<kFused>(x * xx, fmaD<kFused>(xx, kSn5, kSn3), dx);           // s = x + (dx + x * xx * (sn3 + xx * sn5))
     const double c = fmaD<kFused>(x, dx, xx * fmaD<kFused>(xx, fmaD<kFused>(xx, kCs6, kCs4), kCs2));  // c = x * dx + xx * (cs2 + xx * (cs4 + xx * cs6))
-    const double sn = tabAt(k), ssn = tabAt(k + 1), cs = tabAt(k + 2), ccs = tabAt(k + 3);
+    const double sn = tabAt<kLds>(k), ssn = tabAt<kLds>(k + 1), cs = tabAt<kLds>(k + 2), ccs = tabAt<kLds>(k + 3);
     const double cor = fmaD<kFused>(s, cs, fmaD<kFused>(-c, sn, fmaD<kFused>(s, ccs, ssn)));       // cor = (ssn + s * ccs - sn * c) + cs * s
     return copySign(sn + cor, xold);
 }
@@ -182,26 +183,27 @@ MCRT_HD int reduceSinCos(double x, double& a, double& da) {
 }
 
 // do_sincos(a, da, n)
-template <bool kFused>
+template <bool kFused, bool kLds = true>
 MCRT_HD double doSinCos(double a, double da, int n) {
-    const double r = (n & 1) ? doCos<kFused>(a, da) : doSin<kFused>(a, da);
+    const double r = (n & 1) ? doCos<kFused, kLds>(a, da) : doSin<kFused, kLds>(a, da);
     return (n & 2) ? -r : r;
 }
 
 }  // namespace glibc235
 
 // __sin of the FMA build (s_sin.c:201-251)
+template <bool kLds = true>
 MCRT_HD double refSin(double x) {
     using namespace glibc235;
     constexpr bool kFused = true;
     const unsigned k = (unsigned)(dBits(x) >> 32) & 0x7FFFFFFFu;
     if (k < 0x3e500000u) return x;                                                        // |x| < 2^-26
-    if (k < 0x3feb6000u) return doSin<kFused>(x, 0.0);                                    // |x| < 0.855469
-    if (k < 0x400368fdu) return copySign(doCos<kFused>(kHp0 - absD(x), kHp1), x);         // |x| < 2.426265
+    if (k < 0x3feb6000u) return doSin<kFused, kLds>(x, 0.0);                              // |x| < 0.855469
+    if (k < 0x400368fdu) return copySign(doCos<kFused, kLds>(kHp0 - absD(x), kHp1), x);         // |x| < 2.426265
     if (k < 0x419921FBu) {                                                                // |x| < 105414350
         double a, da;
         const int n = reduceSinCos<kFused>(x, a, da);
-        return doSinCos<kFused>(a, da, n);
+        return doSinCos<kFused, kLds>(a, da, n);
     }
     return sin(x);
 }

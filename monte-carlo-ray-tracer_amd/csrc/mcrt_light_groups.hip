@@ -13,7 +13,8 @@
 //                             planes - the sky's too when the bounce ray missed -, otherwise the state of vertex k + 1 stored and the
 //                             sample appended to the OTHER list
 //   lightGroupsResolveKernel  one lane per pixel: the samples' R_p in ascending order into one FP64 accumulator per word (a probe call:
-//                             one lane per output word, R_p times a function of the first ray's direction - mcrt_probes.hpp)
+//                             one lane per output word, R_p times a function of the first ray's direction - mcrt_probes.hpp; a call
+//                             with the FILM flag: the three branches of mcrt_film_gather.hpp)
 // The live list is what keeps the iterations as wide as the work: paths die at very different depths, and an iteration costs its live
 // samples only. A wave appends with ONE atomic: the ballot of its surviving lanes, its population count for the leader's atomicAdd on
 // the list's counter, mbcnt for each lane's place behind the leader's base. The order of the list depends on the order in which waves
@@ -73,7 +74,16 @@ __global__ void __launch_bounds__(kLgBlock) lightGroupsStepKernel(AovChunk c, Ao
 // output word - (plane, k, channel) of a pixel -, because such a call has few pixels and many samples: 64 probes of 4096 rays would be
 // one wave looping 4096 times per plane as lanes per pixel, and are 64 * planes * K * 3 lanes this way. The branch is a kernel argument,
 // uniform over the launch.
-__global__ void __launch_bounds__(kLgBlock) lightGroupsResolveKernel(AovChunk c, LgState st, uint32_t planes, double* out, uint64_t frame_pixels, ProbeProjection proj) {
+// film.mode != 0: a branch of the filtered planes (mcrt_film_gather.hpp) - the samples' film positions, the gather that continues S and
+// W, or the division after the last chunk -, lanes striding over that branch's work; like proj a kernel argument, uniform over the launch.
+__global__ void __launch_bounds__(kLgBlock) lightGroupsResolveKernel(AovChunk c, LgState st, uint32_t planes, double* out, uint64_t frame_pixels, ProbeProjection proj,
+                                                                     FilmGather film) {
+    if (film.mode != kFilmGatherNone) {
+        // (one lane each, no stride: in a loop the compiler keeps the constants of every filter in registers across it)
+        const uint64_t x = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+        if (x < filmGatherLanesX(c, film, frame_pixels)) filmGatherDo(c, st, film, blockIdx.y, (uint32_t)x, out, frame_pixels);
+        return;
+    }
     if (proj.coefficients == 0u) {
         const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
         if (p >= c.pixels) return;
@@ -105,7 +115,7 @@ int launchLightGroupsStep(void* stream, const AovChunk& c, const AovScene& scene
 }
 int launchLightGroupsResolve(void* stream, const AovChunk& c, const LgState& st, uint32_t planes, double* out, uint64_t frame_pixels) {
     hipLaunchKernelGGL(lightGroupsResolveKernel, dim3((c.pixels + kLgBlock - 1) / kLgBlock), dim3(kLgBlock), 0, (hipStream_t)stream, c, st, planes, out, frame_pixels,
-                       ProbeProjection{});
+                       ProbeProjection{}, FilmGather{});
     return (int)hipGetLastError();
 }
 int launchProbeResolve(void* stream, const AovChunk& c, const LgState& st, uint32_t planes, const ProbeProjection& proj, double* out, uint64_t frame_pixels) {
@@ -114,7 +124,15 @@ int launchProbeResolve(void* stream, const AovChunk& c, const LgState& st, uint3
         return (int)hipErrorInvalidValue;
     const uint64_t blocks = (probeLanes(c, planes, proj) + kLgBlock - 1) / kLgBlock;
     if (blocks == 0) return (int)hipSuccess;
-    hipLaunchKernelGGL(lightGroupsResolveKernel, dim3((uint32_t)std::min<uint64_t>(blocks, 1u << 20)), dim3(kLgBlock), 0, (hipStream_t)stream, c, st, planes, out, frame_pixels, proj);
+    hipLaunchKernelGGL(lightGroupsResolveKernel, dim3((uint32_t)std::min<uint64_t>(blocks, 1u << 20)), dim3(kLgBlock), 0, (hipStream_t)stream, c, st, planes, out, frame_pixels, proj, FilmGather{});
+    return (int)hipGetLastError();
+}
+int launchLightGroupsFilm(void* stream, const AovChunk& c, const LgState& st, uint32_t planes, const FilmGather& film, double* out, uint64_t frame_pixels) {
+    if (!filmGatherLaunchable(c, st, planes, film, out, frame_pixels)) return (int)hipErrorInvalidValue;
+    const uint64_t blocks = ((uint64_t)filmGatherLanesX(c, film, frame_pixels) + kLgBlock - 1) / kLgBlock;
+    if (blocks == 0) return (int)hipSuccess;
+    hipLaunchKernelGGL(lightGroupsResolveKernel, dim3((uint32_t)blocks, filmGatherLaneRows(planes, film)), dim3(kLgBlock), 0, (hipStream_t)stream, c, st, planes, out, frame_pixels,
+                       ProbeProjection{}, film);
     return (int)hipGetLastError();
 }
 }  // namespace mcrt

@@ -3,6 +3,7 @@
 // hipError_t as an int.
 #pragma once
 
+#include "mcrt_film_gather.hpp"
 #include "mcrt_light_groups.hpp"
 #include "mcrt_probes.hpp"
 
@@ -25,5 +26,9 @@ int launchLightGroupsResolve(void* stream, const AovChunk& c, const LgState& st,
 // pixels each; proj.direction holds the first-ray directions of the chunk's samples. What would read or write past the chunk's arrays
 // is hipErrorInvalidValue and nothing is queued.
 int launchProbeResolve(void* stream, const AovChunk& c, const LgState& st, uint32_t planes, const ProbeProjection& proj, double* out, uint64_t frame_pixels);
+// The same kernel's branches for the filtered planes (include/mcrt.h "Filtered planes", mcrt_film_gather.hpp), film.mode one of the
+// three: the chunk's film positions into film.offset; S in `out` and W in film.weight continued over the pixels the chunk reaches;
+// after the last chunk the division in place. What would read or write past an array is hipErrorInvalidValue and nothing is queued.
+int launchLightGroupsFilm(void* stream, const AovChunk& c, const LgState& st, uint32_t planes, const FilmGather& film, double* out, uint64_t frame_pixels);
 
 }  // namespace mcrt

@@ -7,7 +7,7 @@
 //   pathClassesRayKernel      one lane per LIVE sample: lgRays, the light groups' shadow and bounce rays of vertex k
 //   pathClassesStepKernel     one lane per live sample: pcStep - the terms of vertex k into the planes of the path's class (step 0 finds
 //                             the class and stores it), the state of vertex k + 1, the sample appended to the other list
-//   pathClassesResolveKernel  one lane per pixel: lgResolvePixel
+//   pathClassesResolveKernel  one lane per pixel: lgResolvePixel (a call with the FILM flag: the three branches of mcrt_film_gather.hpp)
 // Launch shape, the tables and the refraction history in LDS ([entry][lane]) and the wave-aggregated append (one ballot, one atomic per
 // wave, mbcnt for the lane's place) are mcrt_light_groups_device.hpp's, as in mcrt_light_groups.hip.
 #include <hip/hip_runtime.h>
@@ -59,7 +59,15 @@ __global__ void __launch_bounds__(kLgBlock) pathClassesStepKernel(AovChunk c, Ao
     }
 }
 
-__global__ void __launch_bounds__(kLgBlock) pathClassesResolveKernel(AovChunk c, LgState st, uint32_t planes, double* out, uint64_t frame_pixels) {
+// film.mode != 0: a branch of the filtered planes (mcrt_film_gather.hpp), as in lightGroupsResolveKernel; a kernel argument, uniform
+// over the launch.
+__global__ void __launch_bounds__(kLgBlock) pathClassesResolveKernel(AovChunk c, LgState st, uint32_t planes, double* out, uint64_t frame_pixels, FilmGather film) {
+    if (film.mode != kFilmGatherNone) {
+        // (one lane each, no stride: in a loop the compiler keeps the constants of every filter in registers across it)
+        const uint64_t x = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+        if (x < filmGatherLanesX(c, film, frame_pixels)) filmGatherDo(c, st, film, blockIdx.y, (uint32_t)x, out, frame_pixels);
+        return;
+    }
     const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
     if (p >= c.pixels) return;
     lgResolvePixel(c, st, planes, p, out, frame_pixels);
@@ -84,7 +92,16 @@ int launchPathClassesStep(void* stream, const AovChunk& c, const AovScene& scene
     return (int)hipGetLastError();
 }
 int launchPathClassesResolve(void* stream, const AovChunk& c, const PcState& st, uint32_t planes, double* out, uint64_t frame_pixels) {
-    hipLaunchKernelGGL(pathClassesResolveKernel, dim3((c.pixels + kLgBlock - 1) / kLgBlock), dim3(kLgBlock), 0, (hipStream_t)stream, c, st.lg, planes, out, frame_pixels);
+    hipLaunchKernelGGL(pathClassesResolveKernel, dim3((c.pixels + kLgBlock - 1) / kLgBlock), dim3(kLgBlock), 0, (hipStream_t)stream, c, st.lg, planes, out, frame_pixels,
+                       FilmGather{});
+    return (int)hipGetLastError();
+}
+int launchPathClassesFilm(void* stream, const AovChunk& c, const PcState& st, uint32_t planes, const FilmGather& film, double* out, uint64_t frame_pixels) {
+    if (!filmGatherLaunchable(c, st.lg, planes, film, out, frame_pixels)) return (int)hipErrorInvalidValue;
+    const uint64_t blocks = ((uint64_t)filmGatherLanesX(c, film, frame_pixels) + kLgBlock - 1) / kLgBlock;
+    if (blocks == 0) return (int)hipSuccess;
+    hipLaunchKernelGGL(pathClassesResolveKernel, dim3((uint32_t)blocks, filmGatherLaneRows(planes, film)), dim3(kLgBlock), 0, (hipStream_t)stream, c, st.lg, planes, out,
+                       frame_pixels, film);
     return (int)hipGetLastError();
 }
 }  // namespace mcrt

@@ -3,6 +3,7 @@
 // hipError_t as an int. They are the light groups' four (mcrt_light_groups_launch.hpp says what each reads and leaves), on PcState.
 #pragma once
 
+#include "mcrt_film_gather.hpp"
 #include "mcrt_path_classes.hpp"
 
 namespace mcrt {
@@ -13,5 +14,7 @@ int launchPathClassesRays(void* stream, const AovChunk& c, const AovScene& scene
 int launchPathClassesStep(void* stream, const AovChunk& c, const AovScene& scene, const uint32_t* sobol_tab, const PcState& st, const PcParams& par, const uint32_t* list,
                           uint32_t n_live, uint32_t k, bool last, const AovRays& lit, uint32_t* next_list, LgCounters* counters, uint32_t next);
 int launchPathClassesResolve(void* stream, const AovChunk& c, const PcState& st, uint32_t planes, double* out, uint64_t frame_pixels);
+// pathClassesResolveKernel's branches for the filtered planes: launchLightGroupsFilm's (mcrt_light_groups_launch.hpp), on PcState.
+int launchPathClassesFilm(void* stream, const AovChunk& c, const PcState& st, uint32_t planes, const FilmGather& film, double* out, uint64_t frame_pixels);
 
 }  // namespace mcrt

@@ -111,6 +111,8 @@ inline int probeSettings(const mcrt_probe_params& p, const char** why) {
     if (p.order > kProbeOrderMax) return *why = "order is more than MCRT_PROBE_ORDER_MAX (2)", MCRT_ERR_INVALID;
     if (p.flags != 0) return *why = "flags must be 0", MCRT_ERR_INVALID;
     if (p.reserved[0] != 0 || p.reserved[1] != 0) return *why = "reserved must be 0", MCRT_ERR_INVALID;
+    if (p.groups.flags & (MCRT_LIGHT_GROUPS_FILM | MCRT_LIGHT_GROUPS_FILM_CLAMP))
+        return *why = "groups.flags carries MCRT_LIGHT_GROUPS_FILM or MCRT_LIGHT_GROUPS_FILM_CLAMP - a probe has no film", MCRT_ERR_INVALID;
     return MCRT_OK;
 }
 

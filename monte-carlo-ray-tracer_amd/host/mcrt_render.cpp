@@ -12,6 +12,7 @@
 //               [--occlusion PREFIX [--occlusion-rays N] [--occlusion-distance D]] [--lighting PREFIX]
 //               [--light-groups PREFIX [--light-groups-by material|light|one] [--light-groups-depth D]]
 //               [--path-classes PREFIX [--path-classes-depth D]]
+//               [--film box|mitchell|catmull-rom|b-spline|hermite|gaussian|lanczos[,RADIUS[,CACHE]]]
 //   mcrt_render scene.mcrt out.exr --probes POINTS.txt [--probe-order L] [--probe-rays N] [--seed N] [--device D]
 //               [--light-groups-by material|light|one] [--light-groups-depth D] [--exr-compression none|zip]
 //
@@ -99,6 +100,11 @@
 // harmonics (--probe-order L = 0, 1, 2; default 2), per light group (--light-groups-by, --light-groups-depth as above). The output - the
 // second argument - is an N x 1 OpenEXR file (mcrt_exr_save) with the FLOAT channels probe.<plane>.<k>.R/G/B, the raw means (the header's
 // constants normalise them); no frame is rendered. Path tracer on one device; not with --lens, --gather or any other output.
+// --film NAME[,RADIUS[,CACHE]] sets the camera's reconstruction filter for the run (film_filter, film_radius - 0 or none: the filter's
+// default -, film_cache_size - 0 or none: no table): the frame is then the filtered one, and --light-groups and --path-classes carry
+// their FILM flag (include/mcrt.h "Filtered planes"): unclamped planes through the same filter, which add up to the frame; under
+// --lens the frame itself is the light groups' single plane with FILM | CLAMP. Not with --gather (a ray
+// source has no film positions).
 // --devices renders the frame on several GPUs from this one process (mcrt_render_multi: one host thread per GPU).
 #include <cstdio>
 #include <cstdlib>
@@ -130,7 +136,7 @@ int main(int argc, char** argv) {
     image.gain_compensation = from_bits(mcrt_image_param(img, "image_gain_ev_bits"));
     std::string tga, aov, denoise, dvar, dvar_out, ddual, ddual_out, pstats, robust, exr, matte, compare, compare_layer, occlusion, lighting, light_groups, light_groups_by = "material", path_classes;
     uint32_t light_groups_depth = 0, path_classes_depth = 0;
-    std::string lens_name;
+    std::string lens_name, film;
     mcrt_lens_desc lens{};
     std::string probes;
     uint32_t probe_order = MCRT_PROBE_ORDER_MAX, probe_rays = 1024;
@@ -204,6 +210,7 @@ int main(int argc, char** argv) {
         else if (k == "--gather") gather = true;
         else if (k == "--gather-normal" && i + 1 < argc) gather_normal = argv[++i];
         else if (k == "--lens" && i + 1 < argc) lens_name = argv[++i];
+        else if (k == "--film" && i + 1 < argc) film = argv[++i];
         else if (k == "--lens-fov" && i + 1 < argc) {
             char* rest = nullptr;
             const double to_radians = 3.14159265358979323846 / 180.0;
@@ -243,6 +250,28 @@ int main(int argc, char** argv) {
     }
     cam.shard_index = 0;
     cam.shard_count = 1;
+    if (!film.empty()) {  // NAME[,RADIUS[,CACHE]]
+        const char* const filters[] = {"box", "mitchell", "catmull-rom", "b-spline", "hermite", "gaussian", "lanczos"};
+        const std::string name = film.substr(0, film.find(','));
+        uint32_t filter = 0;
+        while (filter < 7 && name != filters[filter]) filter++;
+        if (filter == 7) {
+            std::fprintf(stderr, "--film: box, mitchell, catmull-rom, b-spline, hermite, gaussian or lanczos, not %s\n", name.c_str());
+            return 2;
+        }
+        if (gather) {
+            std::fprintf(stderr, "--film is not for --gather: a ray source's pixels have no film position\n");
+            return 2;
+        }
+        cam.film_filter = filter;
+        cam.film_radius = 0.0;
+        cam.film_cache_size = 0;
+        if (name.size() < film.size()) {
+            char* rest = nullptr;
+            cam.film_radius = std::strtod(film.c_str() + name.size() + 1, &rest);
+            if (rest && *rest == ',') cam.film_cache_size = (uint32_t)std::strtoul(rest + 1, nullptr, 10);
+        }
+    }
     // --compare's reference, read before anything is rendered: raw binary64, or .npy 1.0 of '<f8' in C order and shape (height, width, 3)
     std::vector<double> reference;
     if (!compare.empty()) {
@@ -562,7 +591,7 @@ int main(int argc, char** argv) {
         }
         mcrt_light_group_params one{};
         one.num_groups = 1;
-        one.flags = MCRT_LIGHT_GROUPS_SKY_PLANE;
+        one.flags = MCRT_LIGHT_GROUPS_SKY_PLANE | (film.empty() ? 0u : MCRT_LIGHT_GROUPS_FILM | MCRT_LIGHT_GROUPS_FILM_CLAMP);
         one.sky_plane = 0;
         rc = mcrt_render_light_groups(ctx, &cam, seed, &one, rgb.data(), &st);
     } else if (rc == MCRT_OK)
@@ -965,6 +994,7 @@ int main(int argc, char** argv) {
         mcrt_light_group_params gp{};
         gp.num_groups = (uint32_t)names.size();
         gp.max_depth = light_groups_depth;
+        gp.flags = film.empty() ? 0u : MCRT_LIGHT_GROUPS_FILM;
         gp.surface_group = group.data();
         names.push_back("sky");
         const size_t px = (size_t)cam.width * cam.height;
@@ -1009,6 +1039,7 @@ int main(int argc, char** argv) {
                                                       "glossy_direct", "glossy_indirect", "transmission_direct", "transmission_indirect"};
         mcrt_path_class_params pp{};
         pp.max_depth = path_classes_depth;
+        pp.flags = film.empty() ? 0u : MCRT_PATH_CLASSES_FILM;
         const size_t px = (size_t)cam.width * cam.height;
         std::vector<double> planes(MCRT_PATH_CLASSES * px * 3);
         mcrt_stats pst;
