@@ -1814,7 +1814,11 @@ int mcrt_libm(mcrt_ctx* ctx, int fn, uint64_t n, const double* a, const double* 
 /* LinearOctree<Photon>::knnSearch (octree/linear-octree.cpp:25-117) on the uploaded map
  * (which = 0 global, 1 caustic) for n query points p[n][3]. Outputs per query: count found
  * (≤ k), photon indices and squared distances sorted by ascending distance (ties by index),
- * each [n][k]; unused slots get 0xFFFFFFFF / +inf. Any k: k <= 768 is served by the wave-cooperative search,
+ * each [n][k]; unused slots get 0xFFFFFFFF / +inf. When more photons share the k-th distance than the answer has room for, the
+ * DISTANCES are still guaranteed - the k smallest of the map, bit for bit - and so is that the indices of a query are distinct, each a
+ * photon at exactly the distance reported with it, equal distances in ascending index order; WHICH of the photons tied at the k-th
+ * distance are returned is not: the reference keeps them by insertion order (linear-octree.cpp:58-77), the searches here by the order of
+ * their candidate buffers, and the forms of this call (wave-cooperative, four queries per wave, per lane) differ among themselves. Any k: k <= 768 is served by the wave-cooperative search,
  * larger k by the per-lane search. The search's frontier is unbounded like the reference's priority queue
  * (linear-octree.cpp:33): a wave-cooperative search that fills its 128 + 1 024 entries is repeated by the per-lane
  * search, whose frontier grows on demand (the same holds for photon-mapped frames: mcrt_render_finish). */

@@ -161,7 +161,6 @@ struct mcrt_ctx {
 
     // wavefront path tracer: slot pool, ray queue, control words {count[2], pop}, pinned read-back word
     DevBuf wf_pool, wf_queue, wf_ctrl, wf_film, wf_film_cache, wf_requests, wf_res_n, wf_res_r2, wf_res_idx, wf_res_d2, wf_stage, wf_est;
-    uint32_t wf_res_slots = 0, wf_res_k = 0;
     uint32_t wf_slots = 0;
     unsigned long long* wf_host = nullptr;   // pinned: one read-back word per half
 
@@ -500,19 +499,18 @@ int runWavefrontPass(mcrt_ctx* ctx, const WfFrame& fr, uint64_t slots, hipStream
     if (photon) {
         const uint32_t k = ctx->k_nearest;
         const bool knn_eval = opt.wf_pm_eval;  // (selectKernel: which kNN kernel)
-        if (ctx->wf_res_slots != slots || ctx->wf_res_k != k || (knn_eval ? !ctx->wf_stage.p : !ctx->wf_res_idx.p)) {
-            HIP_TRY(ctx, ctx->wf_requests.alloc((size_t)slots * sizeof(uint32_t)));
-            if (knn_eval) {
-                HIP_TRY(ctx, ctx->wf_stage.alloc((size_t)slots * kStageDoubles * sizeof(double)));
-                HIP_TRY(ctx, ctx->wf_est.alloc((size_t)slots * 6 * sizeof(double)));
-            } else {
-                HIP_TRY(ctx, ctx->wf_res_n.alloc((size_t)2 * slots * sizeof(uint32_t)));
-                HIP_TRY(ctx, ctx->wf_res_r2.alloc((size_t)2 * slots * sizeof(double)));
-                HIP_TRY(ctx, ctx->wf_res_idx.alloc((size_t)2 * k * slots * sizeof(uint32_t)));
-                HIP_TRY(ctx, ctx->wf_res_d2.alloc((size_t)2 * k * slots * sizeof(double)));
-            }
-            ctx->wf_res_slots = (uint32_t)slots;
-            ctx->wf_res_k = k;
+        // Every buffer is held to the size THIS pass needs of it (grow-only). One (slots, k) record for both kinds of launch let the
+        // raw buffers of an earlier k pass for those of a larger one once an evaluating frame had renewed the record in between -
+        // wfKnnKernel<false> then wrote 2 k slots entries into the smaller allocation (tests/test_gpu_knn_crowds.py met it).
+        HIP_TRY(ctx, ctx->wf_requests.reserve((size_t)slots * sizeof(uint32_t)));
+        if (knn_eval) {
+            HIP_TRY(ctx, ctx->wf_stage.reserve((size_t)slots * kStageDoubles * sizeof(double)));
+            HIP_TRY(ctx, ctx->wf_est.reserve((size_t)slots * 6 * sizeof(double)));
+        } else {
+            HIP_TRY(ctx, ctx->wf_res_n.reserve((size_t)2 * slots * sizeof(uint32_t)));
+            HIP_TRY(ctx, ctx->wf_res_r2.reserve((size_t)2 * slots * sizeof(double)));
+            HIP_TRY(ctx, ctx->wf_res_idx.reserve((size_t)2 * k * slots * sizeof(uint32_t)));
+            HIP_TRY(ctx, ctx->wf_res_d2.reserve((size_t)2 * k * slots * sizeof(double)));
         }
         HIP_TRY(ctx, ctx->knn_spill.reserve(wfKnnSpillBytes(knn_grid)));
         fillKnnArgs(ka, sa, ctrl, waveMapView(ctx, 0), waveMapView(ctx, 1), k, ctx->direct_visualization, ctx->wf_requests.as<uint32_t>(),

@@ -1498,6 +1498,9 @@ __global__ void __launch_bounds__(256) knnWaveKernel(const PhotonMapViewW map, u
         double r2;
         const uint32_t c = waveKnnSearch<R>(map, pt, k, W, r2, overflow, visits);
         waveSortResult<(R <= 4 ? 2 : R - 4)>(W, c);
+        // (the entries read below were written by other lanes: a hand-off that wants MCRT_LOCKSTEP() as in knnGroupKernel. LDS operations of a
+        // wave execute in order, so the device is right without it; stating it changes this kernel's instructions and with them the
+        // validated device code list - profiles/NOTES_knn_crowds.md)
         if (lane == 0) out_count[q] = c;
         for (uint32_t j = lane; j < k; j += 64) {
             out_index[q * k + j] = j < c ? W.idx[j] : 0xFFFFFFFFu;
@@ -1568,6 +1571,7 @@ __global__ void __launch_bounds__(256) knnGroupKernel(const PhotonMapViewW map, 
             double rr;
             const uint32_t cc = waveKnnSearch(map, qp, k, W, rr, overflow, visits);
             waveSortResult(W, cc);
+            MCRT_LOCKSTEP();  // (the sorted entries were written by other lanes)
             if (lane == 0) out_count[qq] = cc;
             for (uint32_t j = lane; j < k; j += 64) {
                 out_index[qq * k + j] = j < cc ? W.idx[j] : 0xFFFFFFFFu;

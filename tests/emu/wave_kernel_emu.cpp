@@ -496,6 +496,21 @@ void wemu_stats_outcome(const unsigned long long* words, uint32_t kernel_id, uin
     std::copy(v, v + 8, out);
 }
 
+// knnGroupKernel itself (four queries per wave, one per row of 16 lanes: csrc/mcrt_groupknn.hpp; a row that gives up has its query
+// repeated by the whole wave) on `grid` emulated workgroups of four waves, launched with the arguments mcrt_knn launches it with - the
+// repeated queries therefore search without a spill list, as on the device. upload_k: the k the record lists are built for.
+// out_index / out_d2: [n][k] ascending (distance2, index), padded like mcrt_knn. *flags: the kernel's overflow word (non-zero: a search
+// ran out of frontier and mcrt_knn would serve the call with the per-lane kernel). Returns 0, 3 for a bad argument, -301 from the lists.
+int wemu_knn_group(const mcrt_photon_map_desc* m, uint32_t upload_k, uint64_t n, const double* pts, uint32_t k, uint32_t grid, uint32_t* out_count,
+                   uint32_t* out_index, double* out_d2, unsigned long long* flags) {
+    if (!m || !pts || !flags || k == 0 || k > kGrpMaxK || grid == 0) return 3;
+    WaveMap wm;
+    if (wm.init(m, upload_k)) return -301;
+    *flags = 0ull;
+    launchGrid(grid, 256, [&] { knnGroupKernel(wm.view, n, pts, k, out_count, out_index, out_d2, flags); });
+    return 0;
+}
+
 // 0: the waves of a workgroup take turns; otherwise the seed of a random visiting order (wave_emu.hpp)
 void wemu_set_shuffle(unsigned long long seed) { wemu::shuffleSeed() = seed; }
 
